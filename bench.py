@@ -8,13 +8,21 @@ batch 32 per GPU, ResNet-18 encoder + MANO LBS + render + silhouette/texture los
 
 One step = the whole training iteration on a NEW batch: the batch is assembled on the device from the uint8 sample cache resident
 in HBM (hifihr_amd/data.py:batch_examples -> hifihr_freihand_batch: gather + affine warp + the K / joint / vertex / projection terms
-of `data_dic`) straight into the captured step's static inputs, then forward + losses + backward + fused Adam (one hipGraph replay at N = 1).  The same step on one resident batch is
-reported next to it (`resident_batch`).
+of `data_dic`) straight into the captured step's static inputs, then forward + losses + backward + fused Adam (one hipGraph replay at N = 1).
 
-Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` for the dominant hand-written kernel of the
-step (by time per step, measured here), `roofline_kernels` for every MFMA kernel of the convolution path, `roofline_render_fwd`,
-`roofline_render_bwd`, `roofline_mano_lbs` (the north star's HBM-bound kernels) and, at N = 1, `cpu_baseline` (the oracle step
-timed on the host cores on a bounded sample).
+Rank 0 prints ONE JSON line: `metric`, `value` (images/sec), `unit`, `higher_is_better`, `dtype` and `ms_per_step` (milliseconds of
+one timed step; `--steps` of them are timed).  A plain run does only what that line needs: set-up, `--warmup` steps, the timed steps.
+
+  --dump-outputs DIR   after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): the loss, every
+                       term of the loss dictionary and the parameters after the optimizer step (a fixed, seeded sample of them when
+                       the model has more than 2^23).  The inputs depend on the arguments only, so two builds can be compared output
+                       for output.
+  --full               everything else, behind the timed steps as before: the same step on one resident batch (`resident_batch`),
+                       `roofline` for the dominant hand-written kernel of the step (by time per step, measured here),
+                       `roofline_kernels` for every MFMA kernel of the convolution path, `roofline_render_fwd`, `roofline_render_bwd`,
+                       `roofline_mano_lbs` (the north star's HBM-bound kernels), the per-bucket all-reduce times at N > 1 and, at
+                       N = 1, `cpu_baseline` (the oracle step timed on the host cores on a bounded sample).  `--no-rooflines` and
+                       `--no-cpu-baseline` leave parts of it out.
 """
 import argparse
 import hashlib
@@ -48,9 +56,14 @@ def parse():
                     help="configs 3 / 5 only: the hand layer.  mano = MANO + vertex-colour texture stand-in; nimble-synthetic = the NIMBLE-SHAPED layer "
                          "(5 990 skin vertices / 11 976 faces, 25 joints, 20 / 30 / 10 PCA) on seeded synthetic tables; -uv = its texture as an "
                          "image sampled through per-face uvs (TexturesUV).  The real NIMBLE tables are absent: parity unpinned, declared")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: resident-batch replay, rooflines, per-bucket all-reduce "
+                         "times, CPU baseline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, loss terms, parameters) to DIR/<name>.npy as float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-rooflines", action="store_true",
-                    help="skip the roofline block behind the timed region (tools/profile_bench.sh: the rocprofv3 trace then ends with the timed replays)")
+                    help="with --full: skip the roofline block behind the timed region (the rocprofv3 trace then ends with the timed replays)")
     ap.add_argument("--graph", type=int, default=-1, help="0: eager; -1 or 1: hipGraph replay (N = 1: whole step; N > 1: the fastest of the data-parallel forms in a "
                     "short trial); 2: force the N > 1 form (one graph, then all-reduce + Adam); 3: force the segmented form (backward as one graph "
                     "launch per trunk segment, each bucket exchanged beside the next segment)")
@@ -411,6 +424,29 @@ def conv_path_rooflines(ops, lib, dev, nprof, prof=None, prof_how="roctracer (to
     return out
 
 
+DUMP_MAX_PARAMS = 1 << 23        # 32 MB of float32: the dump stays far below 64 MB whatever the encoder
+
+
+def dump_outputs(out_dir, loss, loss_dic, flat):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files -- `loss`, `loss_<term>` for every floating
+    tensor of the loss dictionary, and `params`: the flat parameter vector after the optimizer step, or DUMP_MAX_PARAMS of its entries
+    at fixed seeded positions (ascending) when it is longer."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+    save("loss", loss)
+    for k, v in sorted(loss_dic.items()):
+        if k != "loss" and torch.is_tensor(v) and v.is_floating_point():
+            save("loss_" + "".join(c if c.isalnum() or c in "_-" else "_" for c in k), v)
+    p = flat.flat.detach()
+    if p.numel() > DUMP_MAX_PARAMS:
+        idx = torch.randperm(p.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_PARAMS].sort().values
+        p = p[idx.to(p.device)]
+    save("params", p)
+
+
 def launch_ranks(a):
     """`python bench.py --gpus N` (N > 1) outside a launcher: start N rank processes of this script, one per GPU, and hand back rank 0's
     JSON line.  The parent never touches the GPU (no HIP call is made before this point: `import torch` alone does not initialise the
@@ -548,13 +584,14 @@ def main():
 
     for _ in range(a.warmup):
         eager_resident()
-    # a few profiled eager steps: which (shape, direction) every convolution-path kernel ran, the renderer's inputs
+    # --full: a few profiled eager steps: which (shape, direction) every convolution-path kernel ran, the renderer's inputs
     nprof = 3
-    ops.PROFILE.enable()
-    for _ in range(nprof):
-        eager_resident()
-    ops.PROFILE.disable()
-    ops.PROFILE.summary()
+    if a.full:
+        ops.PROFILE.enable()
+        for _ in range(nprof):
+            eager_resident()
+        ops.PROFILE.disable()
+        ops.PROFILE.summary()
     lib = ops.get_lib()
     B = a.batch
     extra = {}
@@ -673,21 +710,24 @@ def main():
         return dt, out
 
     resident_ms = None
-    if gstep is not None and step is step_streamed:
+    if a.full and gstep is not None and step is step_streamed:
         dt_r, _ = timed_region(gstep, a.steps)            # the same captured step replayed on ONE resident batch (round 1's figure)
         resident_ms = dt_r / a.steps * 1e3
     dt, (loss, loss_dic) = timed_region(step, a.steps)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, loss_dic, flat)
 
-    bucket_us = reducer.time_buckets() if world > 1 else None        # a collective: every rank takes part
-    # ---- rooflines.  Kernel times come from the form of the step the timed region ran: three REPLAYS of the captured graph under roctracer
-    # (single process), where every kernel runs alone on the stream in the graph's order -- the eager profile steps launch weight gradients on a
-    # side stream beside other kernels, which inflated them (round-3 review).  Data parallel / eager runs: three eager steps, on every rank.
-    if world > 1 and not a.no_rooflines:
+    bucket_us = reducer.time_buckets() if (world > 1 and a.full) else None        # a collective: every rank takes part
+    # ---- rooflines (--full).  Kernel times come from the form of the step the timed region ran: three REPLAYS of the captured graph under
+    # roctracer (single process), where every kernel runs alone on the stream in the graph's order -- the eager profile steps launch weight
+    # gradients on a side stream beside other kernels, which inflated them (round-3 review).  Data parallel / eager runs: three eager steps, on every rank.
+    rooflines = a.full and not a.no_rooflines
+    if world > 1 and rooflines:
         reducer.pause_hooks(False)                   # (the eager profile steps below exchange gradients through the hooks)
-    if rank != 0 and not a.no_rooflines:
+    if rank != 0 and rooflines:
         for _ in range(3):                           # the steps rank 0 profiles hold the gradient exchange: every rank runs them
             eager_resident()
-    if rank == 0 and not a.no_rooflines:
+    if rank == 0 and rooflines:
         kprof, kprof_how = None, "roctracer (torch.profiler) over 3 eager steps"
         if world == 1 and gstep is not None and step is step_streamed:
             kprof = instep_kernel_times(gstep, nsteps=3)
@@ -797,7 +837,7 @@ def main():
                            "bucket_bytes": [int(4 * (e_hi - e_lo)) for (_, _, e_lo, e_hi) in reducer.buckets],
                            "allreduce_us_per_bucket": bucket_us}
         out.update(extra)
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args_ns, examples, tables, a.cpu_batch, steps=tuple(int(x) for x in a.cpu_steps.split(",")))
         print(json.dumps(out))
     if world > 1:

@@ -87,9 +87,23 @@ def synth_tables():
     return synthetic_mano_tables(0)
 
 
+@pytest.fixture(scope="session")
+def mano_dense(golden_dir):
+    """(tables, golden) on MANO-STRUCTURED tables that ship (tools/make_golden.py mano_dense_tables: synthetic_mano_tables(0) with up to
+    6 non-zero skin weights per vertex and a dense, non-orthonormal PCA basis -- what the real model has and the synthetic tables lack)
+    and the reference's ManoLayer outputs on them (tests/golden/mano_dense.npz).  The stand-in for the real tables wherever no licence
+    holder's MANO_RIGHT.pkl is given."""
+    import dataclasses
+    import numpy as np
+    from hifihr_amd.mano_tables import synthetic_mano_tables
+    g = dict(np.load(os.path.join(golden_dir, "mano_dense.npz")))
+    tables = dataclasses.replace(synthetic_mano_tables(0), weights=g.pop("weights"), hands_components=g.pop("hands_components"),
+                                 hands_mean=g.pop("hands_mean"), source="mano-dense(seed=6)")
+    tables.check()
+    return tables, g
+
+
 def mano_pkl_path():
-    """A user-supplied MANO file (never shipped).  In the build container the reference mounts one."""
-    for p in (os.environ.get("HIFIHR_MANO_PKL"), "/root/reference/data/MANO_RIGHT.pkl"):
-        if p and os.path.exists(p):
-            return p
-    return None
+    """A licence holder's own MANO file (never shipped), named by HIFIHR_MANO_PKL."""
+    p = os.environ.get("HIFIHR_MANO_PKL")
+    return p if p and os.path.exists(p) else None

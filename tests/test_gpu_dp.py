@@ -25,7 +25,7 @@ def test_two_ranks_on_one_gpu_stay_in_sync():
 
 def test_bench_multi_rank_path_runs_end_to_end():
     """bench.py as the driver launches it for N > 1 (torch.distributed.run, one rank per GPU) -- here two ranks on the one GPU over gloo,
-    a functional run only: every rank must issue the same collectives in the same order through the profiled steps, the three step
+    a functional run only (`--full`): every rank must issue the same collectives in the same order through the profiled steps, the three step
     forms' constructors (collective-free) with their agreement all-reduces, the timing trial and the timed region.  Round 3 found the
     in-step kernel profile running its extra steps (which hold the gradient exchange) on rank 0 only: a collective mismatch that no
     single-process run can see."""
@@ -34,7 +34,7 @@ def test_bench_multi_rank_path_runs_end_to_end():
     env = dict(os.environ, HIFIHR_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--batch", "8"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--batch", "8"], env=env, capture_output=True, text=True, timeout=900)
     print(r.stdout[-2000:]); print(r.stderr[-3000:])
     assert r.returncode == 0
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -63,11 +63,12 @@ def test_bench_gpus_2_plain_invocation_starts_two_ranks():
 
 def test_bench_gpus_4_four_ranks_on_one_gpu():
     """`python bench.py --gpus 4 --batch 2`: FOUR ranks (gloo, one GPU) so that the first 8-GPU run is not the first run with more than two
-    ranks -- bucket boundaries, the agreement all-reduces and the timing trial with an even world size > 2."""
+    ranks -- bucket boundaries, the agreement all-reduces, the timing trial and (`--full`) the per-bucket all-reduce times with an even
+    world size > 2."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HIFIHR_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--batch", "2"], env=env, capture_output=True, text=True, timeout=1200)
     print(r.stdout[-2000:]); print(r.stderr[-3000:])
     assert r.returncode == 0

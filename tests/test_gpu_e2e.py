@@ -568,3 +568,32 @@ def test_deferred_weight_gradient_transforms_equal_the_immediate_ones():
             print(f"[margin] deferred (early and late flush) vs immediate weight gradients, second backward in scope = {twice}: worst |diff| / max|g| = {worst:.2e} (bound 2e-4)")
     finally:
         torch.cuda.set_stream(prev)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR`: the plain run prints the headline line alone (what `--full` adds is
+    absent), with `steps` == 2 and a positive `ms_per_step`; DIR holds the last timed step's loss, loss terms and parameters as finite
+    float32 arrays, and its loss is the one the line reports."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8",
+                        "--cache", "64", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    print(r.stdout[-2000:]); print(r.stderr[-3000:])
+    assert r.returncode == 0
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "images/sec" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True
+    assert not any(k in d for k in ("cpu_baseline", "roofline", "roofline_kernels", "resident_batch"))
+    files = sorted(os.listdir(out))
+    assert "loss.npy" in files and "params.npy" in files and any(f.startswith("loss_") for f in files)
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+    for f in files:
+        a = np.load(out / f)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), f
+    assert float(np.load(out / "loss.npy")) == np.float32(d["loss"])

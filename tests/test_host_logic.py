@@ -411,3 +411,34 @@ def test_staging_ring_releases_its_slots_in_groups():
     # a larger batch later: the slot grows, the others stay
     slot, host = p._stage(25 * 64)
     assert host.numel() == 1600 and p._slots[slot].numel() >= 1600
+
+
+def test_bench_dump_outputs_writes_float32_and_a_fixed_sample_of_long_parameter_vectors(tmp_path, monkeypatch):
+    """bench.dump_outputs (`--dump-outputs DIR`): float32 .npy files named after the loss terms, the loss itself, and the parameters --
+    a seeded, ascending sample of them once the vector is longer than DUMP_MAX_PARAMS, the same sample on every call."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_PARAMS", 1000)
+
+    class Flat:
+        flat = torch.arange(5000, dtype=torch.float64)
+    loss = torch.tensor(2.5, requires_grad=True) * 2
+    dic = {"loss": loss, "mano/joint": torch.ones(3, dtype=torch.float64), "count": torch.tensor([3]), "note": "x"}
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), loss, dic, Flat)
+    assert sorted(os.listdir(tmp_path / "a")) == ["loss.npy", "loss_mano_joint.npy", "params.npy"]
+    for f in os.listdir(tmp_path / "a"):
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 5.0
+    p = np.load(tmp_path / "a" / "params.npy")
+    assert p.shape == (1000,) and (np.diff(p) > 0).all() and p.min() >= 0 and p.max() < 5000
+
+
+def test_bench_plain_run_is_the_default_and_full_and_dump_are_options(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"

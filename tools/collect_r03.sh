@@ -6,13 +6,13 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03; mkdir -p $O
 export TMPDIR=/tmp
 last() { tail -1 "$1" > "$2"; }
-python3 bench.py > $O/bench_default.log 2>&1; last $O/bench_default.log $O/r03_bench_default.json
-python3 bench.py --config 3 --steps 15 --warmup 3 > $O/b3.log 2>&1; last $O/b3.log $O/r03_bench_cfg3.json
-python3 bench.py --config 5 --steps 15 --warmup 3 > $O/b5.log 2>&1; last $O/b5.log $O/r03_bench_cfg5.json
-python3 bench.py --encoder res50 --steps 15 --warmup 3 --no-cpu-baseline > $O/b50.log 2>&1; last $O/b50.log $O/r03_bench_res50.json
-python3 bench.py --config 3 --hand nimble-synthetic-uv --steps 15 --warmup 3 > $O/b3n.log 2>&1; last $O/b3n.log $O/r03_bench_cfg3_nimble_uv.json
-python3 bench.py --config 5 --hand nimble-synthetic-uv --steps 15 --warmup 3 > $O/b5n.log 2>&1; last $O/b5n.log $O/r03_bench_cfg5_nimble_uv.json
-python3 bench.py --config 5 --hand nimble-synthetic-uv --aa 1 --steps 15 --warmup 3 > $O/b5n1.log 2>&1; last $O/b5n1.log $O/r03_bench_cfg5_nimble_uv_aa1.json
+python3 bench.py --full > $O/bench_default.log 2>&1; last $O/bench_default.log $O/r03_bench_default.json
+python3 bench.py --full --config 3 --steps 15 --warmup 3 > $O/b3.log 2>&1; last $O/b3.log $O/r03_bench_cfg3.json
+python3 bench.py --full --config 5 --steps 15 --warmup 3 > $O/b5.log 2>&1; last $O/b5.log $O/r03_bench_cfg5.json
+python3 bench.py --full --encoder res50 --steps 15 --warmup 3 --no-cpu-baseline > $O/b50.log 2>&1; last $O/b50.log $O/r03_bench_res50.json
+python3 bench.py --full --config 3 --hand nimble-synthetic-uv --steps 15 --warmup 3 > $O/b3n.log 2>&1; last $O/b3n.log $O/r03_bench_cfg3_nimble_uv.json
+python3 bench.py --full --config 5 --hand nimble-synthetic-uv --steps 15 --warmup 3 > $O/b5n.log 2>&1; last $O/b5n.log $O/r03_bench_cfg5_nimble_uv.json
+python3 bench.py --full --config 5 --hand nimble-synthetic-uv --aa 1 --steps 15 --warmup 3 > $O/b5n1.log 2>&1; last $O/b5n1.log $O/r03_bench_cfg5_nimble_uv_aa1.json
 for spec in "res18:" "cfg3:--config 3" "cfg5:--config 5" "res50:--encoder res50" "cfg3_nimble_uv:--config 3 --hand nimble-synthetic-uv"; do
   tag=${spec%%:*}; args=${spec#*:}
   bash tools/profile_bench.sh r03_$tag $args > /dev/null 2>&1

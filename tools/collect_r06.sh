@@ -9,13 +9,13 @@ for b in tools/build_render_probe2.sh tools/build_halo_probe.sh tools/build_spli
 O=gpurun_out/r06; mkdir -p $O
 export TMPDIR=/tmp
 last() { tail -1 "$1" > "$2"; }
-python3 bench.py > $O/bench_default.log 2>&1; last $O/bench_default.log $O/r06_bench_default.json
-python3 bench.py --config 3 --steps 15 --warmup 3 > $O/b3.log 2>&1; last $O/b3.log $O/r06_bench_cfg3.json
-python3 bench.py --config 5 --steps 15 --warmup 3 > $O/b5.log 2>&1; last $O/b5.log $O/r06_bench_cfg5.json
-python3 bench.py --encoder res50 --steps 15 --warmup 3 --no-cpu-baseline > $O/b50.log 2>&1; last $O/b50.log $O/r06_bench_res50.json
-python3 bench.py --config 3 --hand nimble-synthetic-uv --steps 15 --warmup 3 > $O/b3n.log 2>&1; last $O/b3n.log $O/r06_bench_cfg3_nimble_uv.json
-python3 bench.py --config 5 --hand nimble-synthetic-uv --steps 15 --warmup 3 > $O/b5n.log 2>&1; last $O/b5n.log $O/r06_bench_cfg5_nimble_uv.json
-python3 bench.py --config 5 --hand nimble-synthetic-uv --aa 1 --steps 15 --warmup 3 > $O/b5n1.log 2>&1; last $O/b5n1.log $O/r06_bench_cfg5_nimble_uv_aa1.json
+python3 bench.py --full > $O/bench_default.log 2>&1; last $O/bench_default.log $O/r06_bench_default.json
+python3 bench.py --full --config 3 --steps 15 --warmup 3 > $O/b3.log 2>&1; last $O/b3.log $O/r06_bench_cfg3.json
+python3 bench.py --full --config 5 --steps 15 --warmup 3 > $O/b5.log 2>&1; last $O/b5.log $O/r06_bench_cfg5.json
+python3 bench.py --full --encoder res50 --steps 15 --warmup 3 --no-cpu-baseline > $O/b50.log 2>&1; last $O/b50.log $O/r06_bench_res50.json
+python3 bench.py --full --config 3 --hand nimble-synthetic-uv --steps 15 --warmup 3 > $O/b3n.log 2>&1; last $O/b3n.log $O/r06_bench_cfg3_nimble_uv.json
+python3 bench.py --full --config 5 --hand nimble-synthetic-uv --steps 15 --warmup 3 > $O/b5n.log 2>&1; last $O/b5n.log $O/r06_bench_cfg5_nimble_uv.json
+python3 bench.py --full --config 5 --hand nimble-synthetic-uv --aa 1 --steps 15 --warmup 3 > $O/b5n1.log 2>&1; last $O/b5n1.log $O/r06_bench_cfg5_nimble_uv_aa1.json
 for spec in "res18:" "cfg3:--config 3" "cfg5:--config 5" "res50:--encoder res50" "cfg3_nimble_uv:--config 3 --hand nimble-synthetic-uv"; do
   tag=${spec%%:*}; args=${spec#*:}
   bash tools/profile_bench.sh r06_$tag $args > /dev/null 2>&1
@@ -51,8 +51,8 @@ if [ "${1:-}" != quick ]; then bash tools/ablation.sh > $O/r06_ablation.txt 2>&1
 # the headline line once more, now that THIS tree's counter file exists (bench.py reads profiles/r*_kernel_traffic.json by source digest): the
 # line with `traffic` populated is the one to commit as r06_bench_default.json; the second run shows the box's drift
 cp $O/r06_kernel_traffic.json profiles/r06_kernel_traffic.json 2>/dev/null
-python3 bench.py > $O/bench_default_a.log 2>&1; last $O/bench_default_a.log $O/r06_bench_default.json
-python3 bench.py > $O/bench_default_b.log 2>&1; last $O/bench_default_b.log $O/r06_bench_default_second_run.json
+python3 bench.py --full > $O/bench_default_a.log 2>&1; last $O/bench_default_a.log $O/r06_bench_default.json
+python3 bench.py --full > $O/bench_default_b.log 2>&1; last $O/bench_default_b.log $O/r06_bench_default_second_run.json
 ls -la $O | tail -40
 if [ "${STAMPS_RC:-1}" != 0 ]; then echo "collect_r06: the render phase stamps are incomplete (tools/render_stamp2.py): NOT evidence" >&2; exit 1; fi
 if grep -l "Traceback (most recent call last)" $O/* 2>/dev/null; then echo "collect_r06: the files above hold a Python traceback: NOT evidence" >&2; exit 1; fi

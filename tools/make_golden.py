@@ -4,7 +4,7 @@
 Runs only where /root/reference exists (it never travels to the GPU box); only the small input /
 output vectors it writes are committed.  What is imported from the reference, unmodified:
 
-  utils/my_mano.py            ManoLayer (__init__ + forward)      -> mano_real.npz, mano_synth.npz
+  utils/my_mano.py            ManoLayer (__init__ + forward)      -> mano_real.npz, mano_synth.npz, mano_dense.npz
   utils/manopth/*             batch_rodrigues                      -> rodrigues.npz
   utils/pytorch_ssim          ssim                                 -> ssim.npz
   utils/Freihand_GNN_mano/network/resnet.py  (vendored torchvision ResNet) -> resnet18.npz
@@ -119,6 +119,37 @@ def gen_mano(name, tables, seed):
                         wv=wv.numpy(), wj=wj.numpy(), verts=verts.detach().numpy(), jtr=jtr.detach().numpy(),
                         gpose=pose.grad.numpy(), gbeta=beta.grad.numpy())
     print(name, "verts", tuple(verts.shape), "|verts|max", float(verts.abs().max()))
+
+
+def mano_dense_tables():
+    """Tables of this repo with what the real MANO model has and synthetic_mano_tables(0) lacks: up to 6 non-zero skin weights per
+    vertex (the synthetic ones keep 4) and a dense PCA basis whose rows are neither orthogonal nor of unit length.  Everything else is
+    synthetic_mano_tables(0); the three arrays that differ travel in mano_dense.npz (tests/conftest.py: mano_dense)."""
+    import dataclasses
+    base = synthetic_mano_tables(0)
+    rng = np.random.RandomState(6)
+    w = base.weights.astype(np.float64)
+    parent = [0, 0, 1, 2, 0, 4, 5, 0, 7, 8, 0, 10, 11, 0, 13, 14]       # the kinematic tree of _ready_arguments' kintree_table
+    for v in range(w.shape[0]):
+        top = int(np.argmax(w[v]))
+        extra = [parent[top]] + [j for j in rng.permutation(16) if j != parent[top] and w[v, j] == 0][:1]
+        for j in extra:
+            if w[v, j] == 0:
+                w[v, j] = rng.uniform(0.02, 0.12)
+        w[v] /= w[v].sum()
+    comps = base.hands_components.astype(np.float64) * rng.uniform(0.3, 2.5, size=(45, 1)) + 0.05 * rng.randn(45, 45)
+    mean = base.hands_mean.astype(np.float64) + 0.05 * rng.randn(45)
+    return dataclasses.replace(base, weights=w, hands_components=comps, hands_mean=mean, source="mano-dense(seed=6)").astype32()
+
+
+def gen_mano_dense():
+    """mano_dense.npz: the reference's ManoLayer on mano_dense_tables() (seed 1 cases, as mano_real.npz) + the arrays that differ."""
+    t = mano_dense_tables()
+    assert int((t.weights != 0).sum(1).max()) == 6
+    gen_mano("mano_dense.npz", t, seed=1)
+    g = dict(np.load(os.path.join(OUT, "mano_dense.npz")))
+    np.savez_compressed(os.path.join(OUT, "mano_dense.npz"), weights=t.weights, hands_components=t.hands_components,
+                        hands_mean=t.hands_mean, **g)
 
 
 def gen_rodrigues():
@@ -635,6 +666,13 @@ if __name__ == "__main__":
         m.ready_arguments = _ready_arguments
         sys.modules[m.__name__] = m
         gen_mano("mano_real.npz", load_mano_pkl(os.environ.get("HIFIHR_MANO_PKL") or os.path.join(REF, "data", "MANO_RIGHT.pkl")), seed=1)
+    elif only == "mano_dense":                  # MANO-structured tables of this repo (not derived from MANO data): committed
+        os.makedirs(OUT, exist_ok=True)
+        install_standins()
+        m = types.ModuleType("utils.mano.webuser.smpl_handpca_wrapper_HAND_only")
+        m.ready_arguments = _ready_arguments
+        sys.modules[m.__name__] = m
+        gen_mano_dense()
     elif os.environ.get("GOLDEN_ONLY") == "losses":
         os.makedirs(OUT, exist_ok=True)
         gen_losses()
