@@ -539,8 +539,10 @@ int hifihr_conv2d_bwd_data_pre_res(const float* dy, const float* wt, const float
 
 int hifihr_conv2d_bwd_data_pre_plus1x1_supported(int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
   // the fast (non-generic) gather of conv_igemm_kernel on parity classes: K % 16 == 0; a stride that makes classes; pad < the filter; the
-  // 1x1 / same stride / pad 0 convolution's outputs are the 3x3's (same OH x OW)
-  if (!conv_dims_ok(N, H, W, C, K, R, S, stride, pad) || stride < 2 || K % 16 || C % 4 || R * S > 62) return 0;
+  // 1x1 / same stride / pad 0 convolution's outputs are the 3x3's (same OH x OW).  pad < R and pad < S: parity class (0, 0)'s first tap
+  // row and column, pad % stride (csrc/conv.hip make_plan), then lie inside the filter, so the class has row AND column taps -- the kernel
+  // puts the extra tap behind the class's last tap row, and with row taps but no column taps it would run as an ordinary tap
+  if (!conv_dims_ok(N, H, W, C, K, R, S, stride, pad) || stride < 2 || K % 16 || C % 4 || R * S > 62 || pad >= R || pad >= S) return 0;
   const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
   if (OH != (H - 1) / stride + 1 || OW != (W - 1) / stride + 1) return 0;
   if ((long)N * OH * OW * K >= (1L << 30) || (long)C * R * S * K >= (1L << 30)) return 0;

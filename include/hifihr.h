@@ -478,7 +478,8 @@ int hifihr_conv2d_bwd_data_pre_res(const float* dy_d, const float* wt_d, const f
  * branch of a residual stage's first block (reference: vendored torchvision BasicBlock, network/res_encoder.py:364-373 runs both through
  * cuDNN / MIOpen and autograd adds the two gradients).  The 1x1 convolution's gradient lands on the pixels (stride i, stride j) only: it is one
  * more tap of that parity class of the strided launch instead of a launch of its own plus a residual pass (round 6).
- * _supported: 1 when the shape runs on that path (stride >= 2, K % 16 == 0, equal output grids); HIFIHR_DGRAD_PLUS1X1=0 switches it off. */
+ * _supported: 1 when the shape runs on that path (stride >= 2, K % 16 == 0, C % 4 == 0, equal output grids, pad < R and pad < S -- so that
+ * parity class (0, 0) has both tap rows and tap columns); HIFIHR_DGRAD_PLUS1X1=0 switches it off.  The call refuses every other shape. */
 int hifihr_conv2d_bwd_data_pre_plus1x1_supported(int N, int H, int W, int C, int K, int R, int S, int stride, int pad);
 int hifihr_conv2d_bwd_data_pre_plus1x1(const float* dy_d, const float* wt_d, const float* dy2_d, const float* wt2_d, float* dx_d, int N, int H,
                                        int W, int C, int K, int R, int S, int stride, int pad, void* stream);

@@ -685,6 +685,257 @@ def conv_wgrad_plus1x1_case(lib, device, N, H, W, C, K, stride=2, seed=0):
 
 
 # ------------------------------------------------------------------------------------------------
+# the convolution C ABI's contract: every entry point on any geometry (N, H, W, C, K, R, S, stride, pad) it is handed either refuses it
+# (HIFIHR_EINVAL, output untouched) or computes it -- against float64 autograd, err <= c * sqrt(L) * max|ref| with L the reduction length
+# ------------------------------------------------------------------------------------------------
+# c per direction: the largest err / (sqrt(L) max|ref|) seen over the contract sweep times >= 4 (tests/test_hostsim_conv_contract.py, the GPU
+# half in tests/test_gpu_conv.py).  A dropped tap or 16-channel chunk costs 1e-1 of max|ref| or more, c * sqrt(L) stays below 1e-3 at the sizes tested.
+CONV_CONTRACT_C = {"fwd": 3e-7, "dgrad": 3e-7, "wgrad": 3e-7}
+CONV_CONTRACT_STATS_C = 1e-6           # statistic sums: err <= c * sqrt(M) * sum over pixels of |y| (resp. y^2), M = N * OH * OW
+CONV_CONTRACT_LOG = {}                 # entry -> [accepted, rejected, largest err / (c sqrt(L) max|ref|)] (the tests print it)
+
+
+def _contract_log(entry, accepted, ratio=0.0):
+    row = CONV_CONTRACT_LOG.setdefault(entry, [0, 0, 0.0])
+    row[0 if accepted else 1] += 1
+    row[2] = max(row[2], ratio)
+
+
+def _contract_rejects(call, canaries, what):
+    """call() must fail with HIFIHR_EINVAL and leave every canary tensor as it was."""
+    from hifihr_amd._lib import HifihrError
+    before = [t.clone() for t in canaries]
+    try:
+        call()
+    except HifihrError as e:
+        assert "failed (-1)" in str(e), f"{what}: refused with a code other than HIFIHR_EINVAL: {e}"
+    else:
+        raise AssertionError(f"{what}: accepted, expected HIFIHR_EINVAL")
+    for a, b in zip(canaries, before):
+        assert torch.equal(a, b), f"{what}: refused but wrote its output"
+
+
+def _contract_close(entry, got, ref, L, what, kind=None, base=0.0):
+    """err <= c * sqrt(L) * max|ref| + tiny (float64 ref, got on any device); logs the ratio."""
+    c = CONV_CONTRACT_C[kind or entry]
+    scale = float(ref.abs().max())
+    err = float((got.detach().cpu().double() - base - ref).abs().max())
+    bound = c * max(L, 1) ** 0.5 * scale + 1e-12
+    _contract_log(entry, True, err / bound)
+    assert err <= bound, f"{what}: err {err:.3e} vs bound {bound:.3e} (max|ref| {scale:.3e}, L {L})"
+
+
+def conv_contract_expect(N, H, W, C, K, R, S, stride, pad):
+    """Which plain entries the header documents as accepting this geometry (include/hifihr.h: C % 4 == 0; backward-data K % 4 == 0,
+    K % 16 == 0 when stride > 1; backward-weight C % 4 == 0 and K % 4 == 0), given that the sizes themselves are valid."""
+    ok = min(N, H, W, C, K, R, S, stride) > 0 and pad >= 0 and H + 2 * pad >= R and W + 2 * pad >= S
+    return {"fwd": ok and C % 4 == 0, "dgrad": ok and K % 4 == 0 and (stride == 1 or K % 16 == 0), "wgrad": ok and C % 4 == 0 and K % 4 == 0}
+
+
+def conv_contract_case(lib, device, N, H, W, C, K, R, S, stride, pad, seed=0):
+    """Every convolution entry point of the C ABI on one geometry.  Plain entries (fwd, fwd_bnstats, bwd_data[_pre[_res]], bwd_weight) must accept
+    exactly what conv_contract_expect documents; the fused entries (bwd_data_pre_plus1x1, bwd_weight_plus1x1, bwd_weight_c3) must do what their
+    _supported predicate says.  An accepted call matches float64 autograd; a refused one returns HIFIHR_EINVAL and leaves its output's canary alone.
+    Returns {entry: accepted}."""
+    import torch.nn.functional as F
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, C, H, W, generator=gen, dtype=torch.float64)
+    w = torch.randn(K, C, R, S, generator=gen, dtype=torch.float64) / (C * R * S) ** 0.5
+    b = torch.randn(K, generator=gen, dtype=torch.float64)
+    xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    y = F.conv2d(xr, wr, None, stride=stride, padding=pad)
+    OH, OW = y.shape[2], y.shape[3]
+    gy = torch.randn(y.shape, generator=gen, dtype=torch.float64)
+    y.backward(gy)
+    ref, refx, refw = y.detach().permute(0, 2, 3, 1), xr.grad.permute(0, 2, 3, 1), wr.grad.permute(0, 2, 3, 1)
+    res = torch.randn(N, H, W, C, generator=gen, dtype=torch.float64)
+    d = lambda t: t.float().to(device).contiguous()
+    xd, wd, gyd, bd, resd = d(x.permute(0, 2, 3, 1)), d(w.permute(0, 2, 3, 1)), d(gy.permute(0, 2, 3, 1)), d(b), d(res)
+    wtd = d(w.permute(1, 2, 3, 0))                                                      # [C][R][S][K]: the pre-transposed filter
+    geo = (N, H, W, C, K, R, S, stride, pad)
+    Lf, Lw = C * R * S, N * OH * OW
+    Ld = K * -(-R // stride) * -(-S // stride)
+    expect = conv_contract_expect(*geo)
+    got = {}
+    canary = lambda *shape: torch.full(shape, 7.0, device=device)
+
+    # ---- forward: no bias, bias, ReLU, the balanced schedule; with statistics (+ balanced)
+    y_out = canary(N, OH, OW, K)
+    if not expect["fwd"]:
+        for e, call in (("fwd", lambda: lib.conv2d_fwd(xd, wd, None, y_out, *geo)),
+                        ("fwd_bnstats", lambda: lib.conv2d_fwd_bnstats(xd, wd, y_out, torch.zeros(lib.bn_stats_floats(K), device=device), *geo))):
+            _contract_rejects(call, [y_out], f"{e} {geo}")
+            _contract_log(e, False)
+            got[e] = False
+    else:
+        lib.conv2d_fwd(xd, wd, None, y_out, *geo)
+        _contract_close("fwd", y_out, ref, Lf, f"fwd {geo}")
+        y_b = canary(N, OH, OW, K)
+        lib.conv2d_fwd(xd, wd, bd, y_b, *geo)
+        _contract_close("fwd_bias", y_b, ref + b, Lf, f"fwd + bias {geo}", "fwd")
+        y_r = canary(N, OH, OW, K)
+        lib.conv2d_fwd(xd, wd, None, y_r, *geo, act=1)
+        _contract_close("fwd_relu", y_r, ref.clamp_min(0), Lf, f"fwd + ReLU {geo}", "fwd")
+        nb_f = lib.conv2d_workspace_bytes(*geo, False)
+        if nb_f:
+            ws = torch.zeros(nb_f // 4, device=device)
+            for rep in range(2):                            # twice: the second call must find the workspace clean
+                y_s = canary(N, OH, OW, K)
+                lib.conv2d_fwd(xd, wd, None, y_s, *geo, ws=ws)
+                _contract_close("fwd_ws", y_s, ref, Lf, f"fwd (balanced, call {rep}) {geo}", "fwd")
+                assert float(ws.abs().max()) == 0.0, f"fwd (balanced) {geo}: workspace not handed back clean"
+        M = N * OH * OW
+        for use_ws in ((False, True) if nb_f else (False,)):
+            e = "fwd_bnstats_ws" if use_ws else "fwd_bnstats"
+            ws = torch.zeros(nb_f // 4, device=device) if use_ws else None
+            y_s, st = canary(N, OH, OW, K), torch.zeros(lib.bn_stats_floats(K), device=device)
+            lib.conv2d_fwd_bnstats(xd, wd, y_s, st, *geo, ws=ws)
+            _contract_close(e, y_s, ref, Lf, f"{e} {geo}", "fwd")
+            assert ws is None or float(ws.abs().max()) == 0.0, f"{e} {geo}: workspace not handed back clean"
+            # the statistics of the y just checked against ref: its float64 column sums to the f32 rounding of the per-share partials
+            sums, yk = bn_slots(st, K).sum(0).double().cpu(), y_s.cpu().double().reshape(-1, K)
+            for i, (want, mag) in enumerate(((yk.sum(0), yk.abs().sum(0)), ((yk ** 2).sum(0), (yk ** 2).sum(0)))):
+                err = float(((sums[i] - want).abs() / (mag + 1e-30)).max())
+                bound = CONV_CONTRACT_STATS_C * M ** 0.5
+                _contract_log(e + "_stats", True, err / bound)
+                assert err <= bound, f"{e} {geo}: statistic {i} err {err:.3e} of sum|y| vs {bound:.3e}"
+        got["fwd"] = got["fwd_bnstats"] = True
+
+    # ---- backward-data: plain (transposes into scratch), pre-transposed, + residual, balanced
+    dx_out = canary(N, H, W, C)
+    scratch = torch.empty(K * R * S * C, device=device)
+    dcalls = (("bwd_data", lambda o: lib.conv2d_bwd_data(gyd, wd, o, scratch, *geo), refx),
+              ("bwd_data_pre", lambda o: lib.conv2d_bwd_data_pre(gyd, wtd, o, *geo), refx),
+              ("bwd_data_pre_res", lambda o: lib.conv2d_bwd_data_pre_res(gyd, wtd, resd, o, *geo), refx + res))
+    for e, call, want in dcalls:
+        if not expect["dgrad"]:
+            _contract_rejects(lambda: call(dx_out), [dx_out], f"{e} {geo}")
+            _contract_log(e, False)
+        else:
+            o = canary(N, H, W, C)
+            call(o)
+            _contract_close(e, o, want, Ld, f"{e} {geo}", "dgrad")
+    got["bwd_data"] = expect["dgrad"]
+    nb_b = lib.conv2d_workspace_bytes(*geo, True) if expect["dgrad"] else 0
+    if nb_b:
+        ws = torch.zeros(nb_b // 4, device=device)
+        for rep in range(2):
+            o = canary(N, H, W, C)
+            lib.conv2d_bwd_data(gyd, wd, o, scratch, *geo, ws=ws)
+            _contract_close("bwd_data_ws", o, refx, Ld, f"bwd_data (balanced, call {rep}) {geo}", "dgrad")
+            assert float(ws.abs().max()) == 0.0, f"bwd_data (balanced) {geo}: workspace not handed back clean"
+
+    # ---- backward-weight: accumulates; a second call adds; the slab form is bit-reproducible
+    dw = torch.full((K, R, S, C), 0.5, device=device)
+    if not expect["wgrad"]:
+        _contract_rejects(lambda: lib.conv2d_bwd_weight(xd, gyd, dw, *geo), [dw], f"bwd_weight {geo}")
+        _contract_log("bwd_weight", False)
+    else:
+        lib.conv2d_bwd_weight(xd, gyd, dw, *geo)
+        _contract_close("bwd_weight", dw, refw, Lw, f"bwd_weight {geo}", "wgrad", base=0.5)
+        lib.conv2d_bwd_weight(xd, gyd, dw, *geo)
+        _contract_close("bwd_weight_acc", dw, 2 * refw, Lw, f"bwd_weight (second call adds) {geo}", "wgrad", base=0.5)
+        nws = lib.conv2d_wgrad_workspace_bytes(*geo)
+        if nws:
+            wsw = torch.full((nws // 4,), 3.0, device=device)           # any contents
+            d1, d2 = torch.full((K, R, S, C), 0.5, device=device), torch.full((K, R, S, C), 0.5, device=device)
+            lib.conv2d_bwd_weight(xd, gyd, d1, *geo, ws=wsw)
+            lib.conv2d_bwd_weight(xd, gyd, d2, *geo, ws=wsw)
+            _contract_close("bwd_weight_ws", d1, refw, Lw, f"bwd_weight (slabs) {geo}", "wgrad", base=0.5)
+            assert torch.equal(d1, d2), f"bwd_weight (slabs) {geo}: not bit-reproducible"
+    got["bwd_weight"] = expect["wgrad"]
+
+    # ---- the fused entries: the second convolution is 1x1 / the same stride / pad 0 on the same input
+    w2 = torch.randn(K, C, 1, 1, generator=gen, dtype=torch.float64) / C ** 0.5
+    x2r, w2r = x.clone().requires_grad_(True), w2.clone().requires_grad_(True)
+    y2 = F.conv2d(x2r, w2r, None, stride=stride)
+    gy2 = torch.randn(y2.shape, generator=gen, dtype=torch.float64)
+    y2.backward(gy2)
+    gy2d, w2d, wt2d = d(gy2.permute(0, 2, 3, 1)), d(w2.permute(0, 2, 3, 1)), d(w2.reshape(K, C).t())
+    ok = lib.conv2d_bwd_data_pre_plus1x1_supported(*geo)
+    o = canary(N, H, W, C)
+    if not ok:
+        _contract_rejects(lambda: lib.conv2d_bwd_data_pre_plus1x1(gyd, wtd, gy2d, wt2d, o, *geo), [o], f"bwd_data_pre_plus1x1 {geo}")
+        _contract_log("bwd_data_pre_plus1x1", False)
+    else:
+        assert y2.shape == y.shape, f"bwd_data_pre_plus1x1 {geo}: accepted with different output grids"
+        lib.conv2d_bwd_data_pre_plus1x1(gyd, wtd, gy2d, wt2d, o, *geo)
+        want = refx + x2r.grad.permute(0, 2, 3, 1)
+        _contract_close("bwd_data_pre_plus1x1", o, want, Ld + K, f"bwd_data_pre_plus1x1 {geo}", "dgrad")
+        two, sep = canary(N, H, W, C), canary(N, H, W, C)                  # the two-launch form it replaces
+        lib.conv2d_bwd_data_pre(gy2d, wt2d, two, N, H, W, C, K, 1, 1, stride, 0)
+        lib.conv2d_bwd_data_pre_res(gyd, wtd, two, sep, *geo)
+        _contract_close("bwd_data_pre_plus1x1_vs_2", o, sep.cpu().double(), Ld + K, f"bwd_data_pre_plus1x1 vs two launches {geo}", "dgrad")
+    got["bwd_data_pre_plus1x1"] = ok
+
+    ok = lib.conv2d_bwd_weight_plus1x1_supported(*geo)
+    dw1, dw2 = torch.full((K, R, S, C), 0.5, device=device), torch.full((K, 1, 1, C), -0.25, device=device)
+    if not ok:
+        _contract_rejects(lambda: lib.conv2d_bwd_weight_plus1x1(xd, gyd, dw1, gy2d, dw2, *geo), [dw1, dw2], f"bwd_weight_plus1x1 {geo}")
+        _contract_log("bwd_weight_plus1x1", False)
+    else:
+        assert y2.shape == y.shape, f"bwd_weight_plus1x1 {geo}: accepted with different output grids"
+        lib.conv2d_bwd_weight_plus1x1(xd, gyd, dw1, gy2d, dw2, *geo)
+        _contract_close("bwd_weight_plus1x1", dw1, refw, Lw, f"bwd_weight_plus1x1 (first) {geo}", "wgrad", base=0.5)
+        _contract_close("bwd_weight_plus1x1", dw2, w2r.grad.permute(0, 2, 3, 1), Lw, f"bwd_weight_plus1x1 (1x1) {geo}", "wgrad", base=-0.25)
+        s1, s2 = torch.zeros(K, R, S, C, device=device), torch.zeros(K, 1, 1, C, device=device)
+        lib.conv2d_bwd_weight(xd, gyd, s1, *geo)
+        lib.conv2d_bwd_weight(xd, gy2d, s2, N, H, W, C, K, 1, 1, stride, 0)
+        _contract_close("bwd_weight_plus1x1_vs_2", dw1, s1.cpu().double(), Lw, f"bwd_weight_plus1x1 vs bwd_weight {geo}", "wgrad", base=0.5)
+        _contract_close("bwd_weight_plus1x1_vs_2", dw2, s2.cpu().double(), Lw, f"bwd_weight_plus1x1 vs bwd_weight (1x1) {geo}", "wgrad", base=-0.25)
+    got["bwd_weight_plus1x1"] = ok
+
+    # ---- the 3-channel stem parameter (NHWC4 input): asked on the C = 4 geometries
+    if C == 4:
+        ok = lib.conv2d_bwd_weight_c3_supported(N, H, W, K, R, S, stride, pad)
+        nws = lib.conv2d_wgrad_workspace_bytes(*geo)
+        ws = torch.full((max(nws, 4096) // 4,), 3.0, device=device)
+        dw3 = torch.full((K, R, S, 3), 0.25, device=device)
+        if not ok:
+            _contract_rejects(lambda: lib.conv2d_bwd_weight_c3(xd, gyd, dw3, N, H, W, K, R, S, stride, pad, ws), [dw3], f"bwd_weight_c3 {geo}")
+            _contract_log("bwd_weight_c3", False)
+        else:
+            lib.conv2d_bwd_weight_c3(xd, gyd, dw3, N, H, W, K, R, S, stride, pad, ws)
+            _contract_close("bwd_weight_c3", dw3, refw[..., :3], Lw, f"bwd_weight_c3 {geo}", "wgrad", base=0.25)
+            again = torch.full((K, R, S, 3), 0.25, device=device)
+            lib.conv2d_bwd_weight_c3(xd, gyd, again, N, H, W, K, R, S, stride, pad, ws)
+            assert torch.equal(again, dw3), f"bwd_weight_c3 {geo}: not bit-reproducible"
+        got["bwd_weight_c3"] = ok
+    return got
+
+
+def conv_pair_contract_case(lib, device, N, H, W, C, stride, K1, R1, pad1, K2, R2, pad2, seed=0):
+    """hifihr_conv2d_fwd_bnstats_pair on one pair: refused (EINVAL, outputs untouched) where its _supported says so; else both outputs equal
+    the two hifihr_conv2d_fwd_bnstats launches bit for bit, their statistics agree to the f32 rounding of per-share partials, and both
+    outputs match float64 conv2d.  Returns whether the pair was accepted."""
+    import torch.nn.functional as F
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, C, H, W, generator=gen, dtype=torch.float64)
+    w1 = torch.randn(K1, C, R1, R1, generator=gen, dtype=torch.float64) / (C * R1 * R1) ** 0.5
+    w2 = torch.randn(K2, C, R2, R2, generator=gen, dtype=torch.float64) / (C * R2 * R2) ** 0.5
+    r1, r2 = F.conv2d(x, w1, None, stride, pad1).permute(0, 2, 3, 1), F.conv2d(x, w2, None, stride, pad2).permute(0, 2, 3, 1)
+    d = lambda t: t.float().to(device).contiguous()
+    xd, w1d, w2d = d(x.permute(0, 2, 3, 1)), d(w1.permute(0, 2, 3, 1)), d(w2.permute(0, 2, 3, 1))
+    ya, yb = torch.full(r1.shape, 7.0, device=device), torch.full(r2.shape, 7.0, device=device)
+    sa, sb = torch.zeros(lib.bn_stats_floats(K1), device=device), torch.zeros(lib.bn_stats_floats(K2), device=device)
+    call = lambda: lib.conv2d_fwd_bnstats_pair(xd, w1d, ya, sa, K1, R1, pad1, w2d, yb, sb, K2, R2, pad2, N, H, W, C, stride)
+    what = f"fwd_bnstats_pair {(N, H, W, C, stride, K1, R1, pad1, K2, R2, pad2)}"
+    if not lib.conv2d_fwd_bnstats_pair_supported(N, H, W, C, stride, K1, R1, pad1, K2, R2, pad2):
+        _contract_rejects(call, [ya, yb, sa, sb], what)
+        _contract_log("fwd_bnstats_pair", False)
+        return False
+    call()
+    for (K, R, pad, y, s, r, wd) in ((K1, R1, pad1, ya, sa, r1, w1d), (K2, R2, pad2, yb, sb, r2, w2d)):
+        _contract_close("fwd_bnstats_pair", y, r, C * R * R, what, "fwd")
+        y1, s1 = torch.empty_like(y), torch.zeros_like(s)
+        lib.conv2d_fwd_bnstats(xd, wd, y1, s1, N, H, W, C, K, R, R, stride, pad)
+        assert torch.equal(y, y1), f"{what}: output differs from the separate launch"
+        p, q = bn_slots(s, K).sum(0).double().cpu(), bn_slots(s1, K).sum(0).double().cpu()
+        assert float((p - q).abs().max()) <= 1e-6 * float(q.abs().max()) + 1e-9, f"{what}: statistics differ from the separate launch"
+    return True
+
+
+# ------------------------------------------------------------------------------------------------
 # depthwise convolution (EfficientNet MBConv) vs plain PyTorch fp32 (F.pad + grouped F.conv2d autograd)
 # ------------------------------------------------------------------------------------------------
 def dwconv_case(lib, device, N, H, W, C, K, stride, seed=0):

@@ -612,3 +612,45 @@ def test_strided_dgrad_with_the_downsample_1x1_as_a_tap(lib, N, H, C, K):
 def test_strided_wgrad_with_the_downsample_1x1_in_the_same_launch(lib, N, H, C, K):
     """hifihr_conv2d_bwd_weight_plus1x1: the weight gradients of layer2.0 / layer3.0's conv1 and downsample[0] in one launch, at B = 32 and odd."""
     kc.conv_wgrad_plus1x1_case(lib, "cuda", N, H, H, C, K, seed=H + C + 1)
+
+
+# ---- the convolution C ABI's contract: every entry point on the emulator's geometry list (tests/test_hostsim_conv_contract.py), plus sizes
+#      where 256 CUs pick other balanced / stream-K / weight-gradient splits than the emulator's 4
+from test_hostsim_conv_contract import CONTRACT_GEOMS, DESCRIBED, PAIR_GEOMS, PLUS1X1_REGRESSIONS, dispatch_coverage  # noqa: E402
+
+CONTRACT_GEOMS_GPU = [
+    (8, 28, 28, 64, 128, 3, 3, 2, 1),      # ResNet layer2.0 class: fused plus1x1 launches, the gathering row-share forward
+    (16, 56, 56, 64, 64, 3, 3, 1, 1),      # conv_halo_kernel / conv_halo_wgrad_kernel
+    (8, 28, 28, 128, 128, 3, 3, 1, 1),     # the balanced schedules
+    (16, 28, 28, 136, 192, 3, 3, 2, 1),
+    (8, 30, 30, 32, 48, 5, 5, 1, 2),
+    (32, 14, 14, 256, 128, 1, 1, 1, 0),    # the GEMM kernels, the weight gradient on TN slabs
+    (8, 56, 56, 4, 64, 7, 7, 2, 3),        # the stem and its 3-channel parameter
+    (12, 29, 31, 32, 64, 3, 1, 3, 1),      # a parity class (0, 0) without column taps: plus1x1 backward-data refused
+    (8, 33, 35, 64, 32, 3, 5, 2, 1),
+]
+PAIR_GEOMS_GPU = [(16, 28, 28, 64, 2, 128, 3, 1, 128, 1, 0), (8, 29, 27, 32, 2, 128, 3, 0, 256, 1, 0)]
+
+
+@pytest.mark.parametrize("geo", CONTRACT_GEOMS + CONTRACT_GEOMS_GPU, ids=lambda g: "x".join(map(str, g)))
+def test_every_conv_entry_on_every_geometry(lib, geo):
+    """tests/kernel_cases.py conv_contract_case: refused (HIFIHR_EINVAL, output untouched) or equal to float64 autograd."""
+    kc.conv_contract_case(lib, "cuda", *geo, seed=sum(geo))
+
+
+@pytest.mark.parametrize("pair", PAIR_GEOMS + PAIR_GEOMS_GPU, ids=lambda g: "x".join(map(str, g)))
+def test_fwd_bnstats_pair_on_every_pair(lib, pair):
+    accepted = kc.conv_pair_contract_case(lib, "cuda", *pair, seed=sum(pair))
+    assert accepted == (pair[4] == 2 and pair[3] % 32 == 0 and pair[5] % 128 == 0 and pair[8] % 128 == 0 and {pair[6], pair[9]} <= {1, 3})
+
+
+def test_conv_contract_reaches_every_dispatch_path(lib):
+    names = dispatch_coverage(lib, CONTRACT_GEOMS + CONTRACT_GEOMS_GPU)
+    assert DESCRIBED <= names, f"no geometry reaches {sorted(DESCRIBED - names)}"
+    assert any(n.startswith("bgemm_tn") for n in names)
+    for g in PLUS1X1_REGRESSIONS + [CONTRACT_GEOMS_GPU[7]]:
+        assert not lib.conv2d_bwd_data_pre_plus1x1_supported(*g)
+    for N, H, C, K in [(32, 56, 64, 128), (32, 28, 128, 256)]:         # the network's layer2.0 / layer3.0 keep the fused launches
+        assert lib.conv2d_bwd_data_pre_plus1x1_supported(N, H, H, C, K, 3, 3, 2, 1)
+        assert lib.conv2d_bwd_weight_plus1x1_supported(N, H, H, C, K, 3, 3, 2, 1)
+        assert lib.conv2d_fwd_bnstats_pair_supported(N, H, H, C, 2, K, 3, 1, K, 1, 0)

@@ -93,7 +93,20 @@ def round6():
         del os.environ["HIFIHR_GEMM_CUS"]
 
 
-GROUPS = {"conv": conv, "render": render, "wino": wino, "round5": round5, "round6": round6}
+def contract():
+    """Every convolution entry point on the geometry list of tests/test_hostsim_conv_contract.py (refused calls included)."""
+    from test_hostsim_conv_contract import CONTRACT_GEOMS, PAIR_GEOMS
+    for g in CONTRACT_GEOMS:
+        kc.conv_contract_case(lib, "cpu", *g, seed=sum(g))
+    os.environ["HIFIHR_GEMM_CUS"] = "16"
+    try:
+        for p in PAIR_GEOMS:
+            kc.conv_pair_contract_case(lib, "cpu", *p, seed=sum(p))
+    finally:
+        del os.environ["HIFIHR_GEMM_CUS"]
+
+
+GROUPS = {"conv": conv, "render": render, "wino": wino, "round5": round5, "round6": round6, "contract": contract}
 for g in (sys.argv[1:] or list(GROUPS)):
     GROUPS[g]()
     print(f"asan: {g} clean", flush=True)
