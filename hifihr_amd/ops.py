@@ -439,7 +439,7 @@ class side_branch:
         FORWARD; in backward autograd runs the branch's nodes on the side stream again, and the only thing that orders them before what
         follows on the main stream is the first branch node's input gradient reaching a main-stream node.  With a frozen / detached
         trunk there is no such gradient, while the branch's convolutions still write their weight gradients straight into the flat
-        gradient buffer (_hifihr_direct_grad: no AccumulateGrad, so autograd does not sync the side stream as a leaf stream either):
+        gradient buffer (_direct_grad: no AccumulateGrad, so autograd does not sync the side stream as a leaf stream either):
         zero_grad / Adam of the main stream would race them, and a capture would end with an un-joined stream.  prepared_weights.__exit__
         calls this after backward, so the optimizer always runs behind the branch."""
         for key in list(side_branch._pending):
@@ -458,65 +458,53 @@ _GEMM_PAIR = os.environ.get("HIFIHR_GEMM_PAIR", "1") != "0"
 # the same for the 64 -> 64 layers (ResNet layer 1): Winograd F(2x2) data gradient + pixel-reduction weight gradient in one launch
 _C64_PAIR = os.environ.get("HIFIHR_C64_PAIR", "1") != "0"
 BRANCH_STREAMS = set() # raw handles of side streams that run convolutions BESIDE the main stream (models.Model's light branch)
-_CONV_WS = {}          # (device, branch stream or 0) -> zero-initialised, self-cleaning workspace of the balanced convolution schedule
 _CONV_WS_BYTES = {}    # (geometry, direction) -> bytes the library wants for it
+_SCRATCH = {}          # key -> grow-only float32 scratch tensor (launches on one stream are ordered: they can share it)
+_RETIRED_SCRATCH = []  # superseded scratch tensors stay allocated: a captured hipGraph may still replay launches that use their addresses
+
+
+def _scratch(key, numel, device, zeroed=False, alloc=None):
+    """The scratch tensor under `key`, with at least `numel` float32 elements; a larger request replaces it by one of `alloc` (default
+    `numel`) elements.  zeroed: allocated all zero (for buffers their kernels hand back all zero).  Allocated through torch's caching
+    allocator, which is legal inside a stream capture (the block then belongs to the graph's private pool)."""
+    t = _SCRATCH.get(key)
+    if t is None or t.numel() < numel:
+        if t is not None:
+            _RETIRED_SCRATCH.append(t)
+        t = (torch.zeros if zeroed else torch.empty)(alloc or numel, device=device, dtype=torch.float32)
+        _SCRATCH[key] = t
+    return t
 
 
 def _conv_ws(lib, device, geom, bwd):
-    """The shared convolution workspace if this shape uses the balanced (stream-K) schedule, else None
-    (include/hifihr.h, convolution section).  One buffer per device AND stream serves every layer: launches on one stream are ordered
-    and each one hands the buffer back all zero (the light estimator may run on a side stream beside the trunk: models.Model)."""
+    """The shared convolution workspace if this shape uses the balanced (stream-K) schedule, else None (include/hifihr.h, convolution
+    section); geom: (N, H, W, C, K, R, S, stride, pad), or ("wino", N, H, W, C, K, m) for the batched GEMM of a Winograd layer (whose
+    balanced kernel takes the same zero-initialised, self-cleaning workspace).  One buffer per device AND stream serves every layer:
+    launches on one stream are ordered and each one hands the buffer back all zero (the light estimator may run on a side stream beside
+    the trunk: models.Model)."""
     key = (geom, bwd)
     nb = _CONV_WS_BYTES.get(key)
     if nb is None:
-        nb = lib.conv2d_workspace_bytes(*geom, bwd)
+        nb = lib.wino_gemm_workspace_bytes(*geom[1:]) if geom[0] == "wino" else lib.conv2d_workspace_bytes(*geom, bwd)
         _CONV_WS_BYTES[key] = nb
     if nb == 0:
         return None
     # (a workspace of its own only for a registered BRANCH stream: keyed by every stream, the capture stream of a graphed step would
     #  get a fresh one allocated -- and zero-filled on every replay -- inside the capture)
     h = torch.cuda.current_stream(device).cuda_stream
-    wkey = (device, h if h in BRANCH_STREAMS else 0)
-    ws = _CONV_WS.get(wkey)
-    if ws is None or ws.numel() * 4 < nb:
-        if ws is not None:
-            _RETIRED_SCRATCH.append(ws)
-        ws = torch.zeros(max(nb, 32 << 20) // 4 + 64, dtype=torch.float32, device=device)
-        _CONV_WS[wkey] = ws
-    return ws
-
-
-_WINO_SCRATCH = {}     # (device, name) -> grow-only scratch tensor shared by every Winograd convolution (stream-ordered reuse)
-
-
-_WGRAD_SLABS = {}       # (device, stream handle) -> per-workgroup slab scratch of the layer-1 / stem weight-gradient kernels
+    return _scratch(("conv_ws", device, h if h in BRANCH_STREAMS else 0), (nb + 3) // 4, device, zeroed=True,
+                    alloc=max(nb, 32 << 20) // 4 + 64)
 
 
 def _wgrad_slabs(device, nbytes):
     """Scratch for hifihr_conv2d_bwd_weight_ws, one buffer per STREAM the launch is issued on (the weight gradients may run on a side
-    stream beside the main one, and the captured step on a third): launches on one stream are ordered, so they can share it.  Allocated
-    through torch's caching allocator, which is legal inside a stream capture (the block then belongs to the graph's private pool)."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    t = _WGRAD_SLABS.get(key)
-    if t is None or t.numel() * 4 < nbytes:
-        if t is not None:
-            _RETIRED_SCRATCH.append(t)
-        t = torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
-        _WGRAD_SLABS[key] = t
-    return t
-
-
-_RETIRED_SCRATCH = []  # superseded scratch tensors stay allocated: a captured hipGraph may still replay launches that use their addresses
+    stream beside the main one, and the captured step on a third): launches on one stream are ordered, so they can share it."""
+    return _scratch(("wgrad_slabs", device, torch.cuda.current_stream(device).cuda_stream), (nbytes + 3) // 4, device)
 
 
 def _wino_scratch(device, name, numel):
-    t = _WINO_SCRATCH.get((device, name))
-    if t is None or t.numel() < numel:
-        if t is not None:
-            _RETIRED_SCRATCH.append(t)
-        t = torch.empty(numel, device=device, dtype=torch.float32)
-        _WINO_SCRATCH[(device, name)] = t
-    return t
+    """grow-only scratch shared by every Winograd convolution (stream-ordered reuse)"""
+    return _scratch(("wino", device, name), numel, device)
 
 
 class _PrecisionStack(threading.local):                # one stack per THREAD: a scope entered in one thread never changes another's dispatch
@@ -821,19 +809,7 @@ def _wino_conv(lib, x, w_krsc, y, stats, N, H, W, C, K, flip, keep_v=False, bias
         U = _wino_scratch(dev, "U", P * K * C)
     V = torch.empty(P * T * C, device=dev, dtype=torch.float32) if keep_v else _wino_scratch(dev, "V", P * T * C)
     M = _wino_scratch(dev, "M", P * T * K)
-    key = ("wino", N, H, W, C, K, m)
-    nb = _CONV_WS_BYTES.get(key)
-    if nb is None:
-        nb = lib.wino_gemm_workspace_bytes(N, H, W, C, K, m)
-        _CONV_WS_BYTES[key] = nb
-    ws = None
-    if nb:
-        ws = _CONV_WS.get(dev)
-        if ws is None or ws.numel() * 4 < nb:
-            if ws is not None:
-                _RETIRED_SCRATCH.append(ws)
-            ws = torch.zeros(max(nb, 32 << 20) // 4 + 64, dtype=torch.float32, device=dev)
-            _CONV_WS[dev] = ws
+    ws = _conv_ws(lib, dev, ("wino", N, H, W, C, K, m), False)
     if PROFILE.on:            # (pair: the layer maps K -> C channels in this call's naming; bench.py times the pair launch for it)
         PROFILE.conv_log.append((("wino", N, H, W, K, C, m), "gemm-pair") if pair is not None else (("wino", N, H, W, C, K, m), "gemm"))
     if not prepared:
@@ -853,32 +829,253 @@ def _wino_conv(lib, x, w_krsc, y, stats, N, H, W, C, K, flip, keep_v=False, bias
     return V if keep_v else None
 
 
-def _stem_c3_wgrad(lib, ctx, x, gy):
+def _direct_grad(p, fmt=None):
+    """p's gradient is accumulated straight into the flat gradient buffer it lives in (hifihr_amd/optim.py FlatParams); `fmt`: only
+    when that buffer has this memory format."""
+    return getattr(p, "_hifihr_direct_grad", False) and p.grad is not None and (fmt is None or p.grad.is_contiguous(memory_format=fmt))
+
+
+def _grad_target(p, like, fmt=None):
+    """(tensor the kernel accumulates into, tensor to hand back to autograd or None): p.grad when _direct_grad(p, fmt), else a fresh
+    zero tensor shaped like `like` (in memory format `fmt`, contiguous without one)."""
+    if _direct_grad(p, fmt):
+        return p.grad, None
+    t = torch.zeros(like.shape, device=like.device) if fmt is None else torch.zeros_like(like, memory_format=fmt)
+    return t, t
+
+
+def _stem_c3_wgrad(lib, geom, w, w3, x, gy):
     """Weight gradient of the 3-channel stem on an NHWC4 image.  The slab kernel writes the parameter's [K][R][S][3] layout itself
     (hifihr_conv2d_bwd_weight_c3: straight into the flat gradient buffer); any other shape goes through a 4-channel temporary.
     -> the gradient to return to autograd (None when it was accumulated in place)."""
-    N, H, W, C, K, R, S, stride, pad = ctx.geom
-    w, w3 = ctx.w_param, ctx.w3
-    Cw = w3.shape[1]
-    direct = getattr(w, "_hifihr_direct_grad", False) and w.grad is not None and w.grad.is_contiguous(memory_format=_CL)
+    N, H, W, C, K, R, S, stride, pad = geom
     if PROFILE.on:
-        PROFILE.conv_log.append(((N, H, W, C, K, R, S, stride, pad), "wgrad"))
-    if Cw == 3 and lib.conv2d_bwd_weight_c3_supported(N, H, W, K, R, S, stride, pad):
-        tgt = w.grad if direct else torch.zeros_like(w3, memory_format=_CL)
-        nslab = lib.conv2d_wgrad_workspace_bytes(N, H, W, C, K, R, S, stride, pad)
+        PROFILE.conv_log.append((geom, "wgrad"))
+    nslab = lib.conv2d_wgrad_workspace_bytes(N, H, W, C, K, R, S, stride, pad)
+    if w3.shape[1] == 3 and lib.conv2d_bwd_weight_c3_supported(N, H, W, K, R, S, stride, pad):
+        tgt, dw = _grad_target(w, w3, _CL)
         PROFILE.bracket("conv_wgrad", lambda: lib.conv2d_bwd_weight_c3(x, gy, tgt, N, H, W, K, R, S, stride, pad, _wgrad_slabs(gy.device, nslab)))
     else:
         dw4 = torch.zeros((K, C, R, S), device=gy.device).contiguous(memory_format=_CL)
-        nslab = lib.conv2d_wgrad_workspace_bytes(N, H, W, C, K, R, S, stride, pad)
         PROFILE.bracket("conv_wgrad", lambda: lib.conv2d_bwd_weight(x, gy, dw4, N, H, W, C, K, R, S, stride, pad,
                                                                      ws=_wgrad_slabs(gy.device, nslab) if nslab else None))
-        if not direct:
-            return dw4[:, :Cw].contiguous(memory_format=_CL)
-        w.grad.add_(dw4[:, :Cw])
-    if direct:
+        if not _direct_grad(w, _CL):
+            return dw4[:, :w3.shape[1]].contiguous(memory_format=_CL)
+        w.grad.add_(dw4[:, :w3.shape[1]])
+        dw = None
+    if dw is None:
         _grad_ready(w)
-        return None
-    return tgt
+    return dw
+
+
+def _wino_u_bwd(lib, wk, U2, dev, C, K, m):
+    """U' of a Winograd layer (its [K][3][3][C] filter transposed, rotated and transformed): U2 from the step's weight_prep launch, else
+    computed here (a transpose plus a weight transform)."""
+    if U2 is None:
+        wt = _wino_scratch(dev, "wt", wk.numel())
+        lib.weight_transpose(wk, wt, K, 9, C)
+        U2 = _wino_scratch(dev, "U", (m + 2) ** 2 * K * C)
+        lib.wino_weight_transform(wt, U2, C, K, 1, m)
+    return U2
+
+
+def _wino_wgrad_slabs(lib, w, direct, own, dev, N, H, W, C, K, m):
+    """-> (dU, parts, defer): the buffer the Winograd weight-gradient product dU = Y'^T V writes.  parts > 0: `parts` slabs summed by the
+    transform (csrc/gemm.hip, no atomics, nothing to zero); 0: one atomically accumulated dU, zero-initialised once and handed back zeroed
+    by hifihr_wino_dw_transform.  defer: the F(4x4) transform joins the step's one deferred launch (_DeferredDw).  Slabs that outlive this
+    backward -- deferred, or `own`: read by a side-stream transform while the next layer's product already runs -- get a buffer of the
+    layer's own."""
+    parts = lib.wino_wgrad_parts(N, H, W, C, K, m)
+    if parts == 0:
+        return _scratch(("wino", dev, "dU", 16 * K * C), 16 * K * C, dev, zeroed=True), 0, False
+    defer = m == 4 and _DEFER_DW.wants(w, direct)
+    dU = _wino_scratch(dev, ("dUp", w.data_ptr()) if (own or defer) else "dUp", parts * (m + 2) ** 2 * K * C)
+    return dU, parts, defer
+
+
+def _wino_wgrad_tail(lib, V, Yt, slabs, tgt, N, H, W, C, K, m, paired):
+    """The Winograd weight gradient behind the dy transform: the product dU = Y'^T V over the tiles (unless `paired`: it ran in the
+    backward-data launch, hifihr_wino4_bwd_gemm_pair), then dw += G^T dU G -- deferred or now."""
+    dU, parts, defer = slabs
+    if not paired:
+        if parts > 0:
+            lib.wino_wgrad_gemm_parts(V, Yt, dU, N, H, W, C, K, parts, m)
+        else:
+            lib.wino_wgrad_gemm(V, Yt, dU, N, H, W, C, K)
+    if defer:
+        _DEFER_DW.add(dU, parts, tgt, K, C)
+    elif parts > 0:
+        lib.wino_dw_transform_parts(dU, parts, tgt, K, C, m)
+    else:
+        lib.wino_dw_transform(dU, tgt, K, C, clear=True)
+
+
+def _bias_relu_bwd(lib, gy, y, b, need_b, relu, grad_premasked, K):
+    """conv + bias (+ ReLU) epilogue: the masked gradient and the bias gradient in one small launch -> (gy, bias gradient or None)"""
+    db_t, db_ret = _grad_target(b, b) if (b is not None and need_b) else (None, None)
+    if relu and grad_premasked:
+        assert db_t is None, "grad_premasked needs a frozen bias (the bias gradient comes out of the masking pass)"
+    elif relu:
+        g = torch.empty_like(gy, memory_format=_CL)
+        PROFILE.bracket("bias_relu_bwd", lambda: lib.bias_relu_bwd(gy, y, gy.numel() // K, K, g, db_t))
+        gy = g
+    elif db_t is not None:
+        raise NotImplementedError("gradient of a conv bias without ReLU")   # only the frozen VGG19 has such a layer
+    if db_t is not None and db_ret is None:
+        _grad_ready(b)
+    return gy, db_ret
+
+
+def _wino_dgrad(lib, gy, wk, w, geom, tile, U2, mask, yt, pair, g_fork):
+    """backward-data of a stride-1 3x3 = the same Winograd pipeline on dy with the transposed, rotated filter U'; mask: [x > 0] applied in
+    the output transform (F(4x4)); yt: the dy transform Y' of the weight gradient, out of the same read; pair: (V, slabs) when the
+    weight-gradient product rides in the same launch"""
+    N, H, W, C, K = geom[:5]
+    dx = torch.empty((N, C, H, W), device=gy.device, dtype=torch.float32, memory_format=_CL)
+
+    def run():
+        U = _wino_u_bwd(lib, wk, U2, gy.device, C, K, tile[0])
+        _wino_conv(lib, gy, None, dx, None, N, H, W, K, C, 1, U=U, dy_out=yt, tile=tile, mask=mask,
+                   pair=None if pair is None else (pair[0], pair[1][0], pair[1][1]))
+    PROFILE.bracket("conv_dgrad_wino", run)
+    return dx if g_fork is None else dx + g_fork
+
+
+def _c64_dgrad(lib, gy, x, wk, w, geom, g_fork, pair):
+    """64 -> 64: the one-launch Winograd kernel on dy with U' (kind 2: transposed, rotated filter).  pair: the data gradient and the
+    pixel-reduction weight gradient share ONE launch (csrc/conv_halo.hip conv_c64_bwd_pair_kernel; on this stream also when weight
+    gradients otherwise go to the side stream) -> (dx, weight gradient to return to autograd or None)"""
+    N, H, W = geom[:3]
+    dx = torch.empty_like(x, memory_format=_CL)
+    U2 = _WEIGHT_PREP.get(w, wk, 2)
+    if not pair:
+        if PROFILE.on:
+            PROFILE.conv_log.append((geom, "dgrad-wino2"))
+        if g_fork is not None:
+            PROFILE.bracket("conv_dgrad", lambda: lib.conv3x3_c64_wino_res(gy, U2, g_fork, dx, N, H, W))
+        else:
+            PROFILE.bracket("conv_dgrad", lambda: lib.conv3x3_c64_wino(gy, U2, None, False, dx, None, N, H, W))
+        return dx, None
+    tgt, dw = _grad_target(w, wk, _CL)
+    if PROFILE.on:
+        PROFILE.conv_log.append((geom, "c64-pair"))
+    nslab = lib.conv2d_wgrad_workspace_bytes(*geom)
+    if nslab and dw is None and _DEFER_DW.wants(w, True):
+        # the slab sum joins the step's deferred launches (one per step in front of the optimizer): slabs in a buffer of the layer's own
+        own = _wino_scratch(gy.device, ("c64slabs", w.data_ptr()), (nslab + 3) // 4)
+        box = []
+        PROFILE.bracket("conv_dgrad", lambda: box.append(lib.conv3x3_c64_bwd_pair_slabs(gy, U2, g_fork, dx, x, own, N, H, W)))
+        _DEFER_DW.add_halo(own, box[-1], tgt)
+    else:
+        slabs = _wgrad_slabs(gy.device, nslab) if nslab else None
+        PROFILE.bracket("conv_dgrad", lambda: lib.conv3x3_c64_bwd_pair(gy, U2, g_fork, dx, x, tgt, N, H, W, ws=slabs))
+    return dx, dw
+
+
+def _direct_dgrad(lib, gy, x, wk, w, geom, g_fork, plus1x1):
+    """backward-data on the direct kernels: on the step's [C][R][S][K] transpose (with the fork residual, or a 1x1 convolution of the same
+    input as one more tap: plus1x1 = its (dy, transposed filter)), else on a transpose of its own followed by the residual add"""
+    dx = torch.empty_like(x, memory_format=_CL)
+    ws = _conv_ws(lib, x.device, geom, True)
+    if PROFILE.on:
+        PROFILE.conv_log.append((geom, "dgrad" if plus1x1 is None else "dgrad+1x1"))
+    wt = _WEIGHT_PREP.get(w, wk, 0)
+    if plus1x1 is not None:
+        assert wt is not None and g_fork is None
+        PROFILE.bracket("conv_dgrad", lambda: lib.conv2d_bwd_data_pre_plus1x1(gy, wt, plus1x1[0], plus1x1[1], dx, *geom))
+    elif wt is not None and g_fork is not None:
+        PROFILE.bracket("conv_dgrad", lambda: lib.conv2d_bwd_data_pre_res(gy, wt, g_fork, dx, *geom, ws=ws))
+    elif wt is not None:
+        PROFILE.bracket("conv_dgrad", lambda: lib.conv2d_bwd_data_pre(gy, wt, dx, *geom, ws=ws))
+    else:
+        scratch = torch.empty(wk.numel(), device=x.device, dtype=torch.float32)
+        PROFILE.bracket("conv_dgrad", lambda: lib.conv2d_bwd_data(gy, wk, dx, scratch, *geom, ws=ws))
+        if g_fork is not None:
+            dx = dx + g_fork
+    return dx
+
+
+def _conv_backward(gy, x, wk, y, v_saved, geom, w, b=None, *, need_x, need_w, need_b=False, relu=False, grad_premasked=False,
+                   mask_input_grad=False, wino_allowed=True, w3=None, g_fork=None, plus1x1=None):
+    """Backward of one convolution (_Conv2dMFMA; the fused functions that save its operands themselves call it directly).
+    x: the saved input (None where only the Winograd-transformed input v_saved is kept), wk: the filter as the forward read it (physical
+    [K][R][S][C]), y: the output where the ReLU mask is read from it, w / b: the parameters, w3: the 3-channel stem filter, g_fork: the
+    gradient of the input's other consumer, plus1x1: see _direct_dgrad.  -> (dx, dw, db); dw / db None where accumulated in place."""
+    lib = get_lib()
+    N, H, W, C, K, R, S, stride, pad = geom
+    gy = gy.contiguous(memory_format=_CL)
+    db = None
+    if relu or b is not None:
+        gy, db = _bias_relu_bwd(lib, gy, y, b, need_b, relu, grad_premasked, K)
+    dev = gy.device
+    # the data gradient: Winograd, the 64 -> 64 one-launch kernel (with the weight gradient in the same launch: c64_pair), or direct
+    wino_x = need_x and _wino_ok(C, K, R, S, stride, pad, wino_allowed)
+    c64_x = (need_x and not wino_x and w3 is None and _wino2_fused_ok(lib, N, H, W, C, K, R, S, stride, pad, wino_allowed, device=dev)
+             and _WEIGHT_PREP.get(w, wk, 2) is not None)
+    c64_pair = c64_x and need_w and v_saved is None and _C64_PAIR and lib.conv3x3_c64_bwd_pair_supported(N, H, W)
+    # the weight gradient: the stem's, c64_pair's, Winograd (Y' . V in the transform domain) or direct
+    wino_w = need_w and w3 is None and v_saved is not None
+    tile = _wino_tile(lib, N, H, W, C, K) if (wino_x or wino_w) else None
+    mask_in = wino_x and mask_input_grad and tile[0] == 4            # [x > 0] applied in the F(4x4) output transform, else in a pass of its own
+    dx = dw = yt = slabs = None
+    paired = False
+    if wino_x:
+        U2 = _WEIGHT_PREP.get(w, wk, 2 if tile[0] == 2 else 4)
+        if wino_w:
+            # the dy transform of the weight gradient comes out of backward-data's read of dy (a side-stream weight gradient reads it while
+            # the next layer's backward-data already runs: a buffer of its own); both products in one launch where F(4x4) has U' at hand
+            yt = _wino_scratch(dev, ("Yt", w.data_ptr()) if _ASYNC_WGRAD.active else "Yt", tile[1] * tile[2] * K)
+            paired = (tile[0] == 4 and U2 is not None and _GEMM_PAIR and min(C, K) % 64 == 0 and lib.wino4_bwd_gemm_pair_supported(N, H, W, C, K)
+                      and lib.wino_wgrad_parts(N, H, W, C, K, 4) > 0)
+            if paired:
+                slabs = _wino_wgrad_slabs(lib, w, _direct_grad(w, _CL), _ASYNC_WGRAD.active, dev, N, H, W, C, K, 4)
+        dx = _wino_dgrad(lib, gy, wk, w, geom, tile, U2, x if mask_in else None, yt, (v_saved, slabs) if paired else None, g_fork)
+    elif c64_x:
+        dx, dw = _c64_dgrad(lib, gy, x, wk, w, geom, g_fork, c64_pair)
+    elif need_x:
+        dx = _direct_dgrad(lib, gy, x, wk, w, geom, g_fork, plus1x1)
+    if mask_input_grad and dx is not None and not mask_in:
+        dxm = torch.empty_like(dx, memory_format=_CL)
+        PROFILE.bracket("bias_relu_bwd", lambda: lib.bias_relu_bwd(dx, x, dx.numel() // C, C, dxm, None))
+        dx = dxm
+    if need_w and w3 is not None:
+        dw = _stem_c3_wgrad(lib, geom, w, w3, x, gy)
+    elif c64_pair:
+        if dw is None:
+            _grad_ready(w)
+    elif need_w:
+        # accumulates (fp32 atomics) straight into the flat gradient buffer when the parameter lives in one
+        tgt, dw = _grad_target(w, wk, _CL)
+        if wino_w:
+            m, P, T = tile
+            Yt = yt if yt is not None else _wino_scratch(dev, ("Yt", w.data_ptr()) if _ASYNC_WGRAD.active else "Yt", P * T * K)
+            if slabs is None:
+                slabs = _wino_wgrad_slabs(lib, w, dw is None, _ASYNC_WGRAD.active, dev, N, H, W, C, K, m)
+            if PROFILE.on and not paired:
+                PROFILE.conv_log.append((("wino", N, H, W, C, K, m), "gemm-tn"))
+
+            def run_w():
+                if yt is None:
+                    lib.wino_dy_transform(gy, Yt, N, H, W, K, m)
+                _wino_wgrad_tail(lib, v_saved, Yt, slabs, tgt, N, H, W, C, K, m, paired)
+            go = lambda: PROFILE.bracket("conv_wgrad_wino", run_w)
+            keep = (gy, v_saved, Yt, tgt)
+        else:
+            if PROFILE.on:
+                PROFILE.conv_log.append((geom, "wgrad"))
+            nslab = lib.conv2d_wgrad_workspace_bytes(*geom)
+            go = lambda: PROFILE.bracket("conv_wgrad", lambda: lib.conv2d_bwd_weight(
+                x, gy, tgt, *geom, ws=_wgrad_slabs(gy.device, nslab) if nslab else None))
+            keep = (gy, x, tgt)
+        if _ASYNC_WGRAD.active and dw is None:
+            _ASYNC_WGRAD.launch(dev, go, keep)
+        else:
+            go()
+        if dw is None:
+            _grad_ready(w)
+    if dx is None and g_fork is not None:
+        dx = g_fork
+    return dx, dw, db
 
 
 class _Conv2dMFMA(torch.autograd.Function):
@@ -963,190 +1160,17 @@ class _Conv2dMFMA(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, *rest):
-        x, wk, y, v_saved = ctx.saved_tensors
-        lib = get_lib()
-        N, H, W, C, K, R, S, stride, pad = ctx.geom
-        g_fork = rest[-1] if (getattr(ctx, "fork", False) and rest) else None      # gradient of the input's other consumer (None: it had none; _CtxShim: no fork)
+        g_fork = rest[-1] if (ctx.fork and rest) else None      # gradient of the input's other consumer (None: it had none)
         if g_fork is not None:
             g_fork = g_fork.contiguous(memory_format=_CL)
         if gy is None:
             return (g_fork,) + (None,) * 9
-        gy = gy.contiguous(memory_format=_CL)
-        dx = dw = db_ret = Yt_done = pair_done = None
-        c64_pair_done = False
-        if ctx.relu or ctx.b_param is not None:
-            # conv + bias (+ ReLU) epilogue: masked gradient and the bias gradient in one small launch
-            b = ctx.b_param
-            db_t, db_ret = _acc_target(b, b.shape, gy.device) if (b is not None and ctx.needs_input_grad[5]) else (None, None)
-            if ctx.relu and ctx.grad_premasked:
-                assert db_t is None, "grad_premasked needs a frozen bias (the bias gradient comes out of the masking pass)"
-            elif ctx.relu:
-                g = torch.empty_like(gy, memory_format=_CL)
-                M = gy.numel() // K
-                PROFILE.bracket("bias_relu_bwd", lambda: lib.bias_relu_bwd(gy, y, M, K, g, db_t))
-                gy = g
-            elif db_t is not None:
-                raise NotImplementedError("gradient of a conv bias without ReLU")   # only the frozen VGG19 has such a layer
-            if b is not None and db_t is not None and db_ret is None:
-                _grad_ready(b)
-        masked = False
-        if ctx.needs_input_grad[0] and _wino_ok(C, K, R, S, stride, pad, ctx.wino_allowed):
-            # backward-data of a stride-1 3x3 = the same Winograd pipeline on dy with the transposed, rotated filter
-            dx = torch.empty((N, C, H, W), device=gy.device, dtype=torch.float32, memory_format=_CL)
-            tile = _wino_tile(lib, N, H, W, C, K)
-            wm, wP, wT = tile
-            mk = x if (ctx.mask_input_grad and wm == 4) else None         # [x > 0] applied in the output transform
-            masked = mk is not None
-            U2 = _WEIGHT_PREP.get(ctx.w_param, wk, 2 if wm == 2 else 4)
-            if ctx.needs_input_grad[1] and v_saved is not None:      # the Winograd backward-weight below wants A dy A^T: same read of dy
-                # a side-stream weight gradient reads it while the next layer's backward-data already runs: a buffer of its own
-                Yt_done = _wino_scratch(gy.device, ("Yt", ctx.w_param.data_ptr()) if _ASYNC_WGRAD.active else "Yt", wP * wT * K)
-            # both gradients wanted, F(4x4), prepared filter, weight gradient on THIS stream: the two products share one launch
-            if (Yt_done is not None and wm == 4 and U2 is not None and _GEMM_PAIR and min(C, K) % 64 == 0
-                    and lib.wino4_bwd_gemm_pair_supported(N, H, W, C, K)):
-                pparts = lib.wino_wgrad_parts(N, H, W, C, K, wm)
-                if pparts > 0:
-                    # (a side-stream weight-gradient transform reads the slabs while the next layer's pair already runs: a buffer of its own)
-                    own = _ASYNC_WGRAD.active or _DEFER_DW.wants(ctx.w_param, _direct_grad(ctx.w_param) and ctx.w_param.grad.is_contiguous(memory_format=_CL))
-                    pair_done = (v_saved, _wino_scratch(gy.device, ("dUp", ctx.w_param.data_ptr()) if own else "dUp",
-                                                        pparts * wP * K * C), pparts)
-
-            def run():
-                if U2 is not None:
-                    _wino_conv(lib, gy, None, dx, None, N, H, W, K, C, 1, U=U2, dy_out=Yt_done, tile=tile, mask=mk, pair=pair_done)
-                else:
-                    wt = _wino_scratch(gy.device, "wt", wk.numel())
-                    lib.weight_transpose(wk, wt, K, R * S, C)
-                    _wino_conv(lib, gy, wt, dx, None, N, H, W, K, C, 1, dy_out=Yt_done, tile=tile, mask=mk)
-            PROFILE.bracket("conv_dgrad_wino", run)
-            if g_fork is not None:
-                dx = dx + g_fork
-        elif ctx.needs_input_grad[0] and ctx.w3 is None and _wino2_fused_ok(lib, N, H, W, C, K, R, S, stride, pad, ctx.wino_allowed, device=gy.device) and \
-                _WEIGHT_PREP.get(ctx.w_param, wk, 2) is not None:
-            # 64 -> 64: the same one-launch Winograd kernel on dy with U' (kind 2: transposed, rotated filter)
-            dx = torch.empty_like(x, memory_format=_CL)
-            U2 = _WEIGHT_PREP.get(ctx.w_param, wk, 2)
-            if ctx.needs_input_grad[1] and v_saved is None and _C64_PAIR and lib.conv3x3_c64_bwd_pair_supported(N, H, W):
-                # both gradients wanted: the data gradient and the pixel-reduction weight gradient share ONE launch (csrc/conv_halo.hip
-                # conv_c64_bwd_pair_kernel; on this stream also when weight gradients otherwise go to the side stream)
-                w = ctx.w_param
-                tgt = w.grad if (getattr(w, "_hifihr_direct_grad", False) and w.grad is not None
-                                 and w.grad.is_contiguous(memory_format=_CL)) else None
-                if tgt is None:
-                    dw = torch.zeros_like(wk, memory_format=_CL)
-                    tgt = dw
-                if PROFILE.on:
-                    PROFILE.conv_log.append(((N, H, W, C, K, R, S, stride, pad), "c64-pair"))
-                nslab = lib.conv2d_wgrad_workspace_bytes(N, H, W, C, K, R, S, stride, pad)
-                if nslab and dw is None and _DEFER_DW.wants(w, True):
-                    # the slab sum joins the step's deferred launches (one per step in front of the optimizer): slabs in a buffer of the layer's own
-                    own = _wino_scratch(gy.device, ("c64slabs", w.data_ptr()), (nslab + 3) // 4)
-                    box = []
-                    PROFILE.bracket("conv_dgrad", lambda: box.append(lib.conv3x3_c64_bwd_pair_slabs(gy, U2, g_fork, dx, x, own, N, H, W)))
-                    _DEFER_DW.add_halo(own, box[-1], tgt)
-                else:
-                    slabs = _wgrad_slabs(gy.device, nslab) if nslab else None
-                    PROFILE.bracket("conv_dgrad", lambda: lib.conv3x3_c64_bwd_pair(gy, U2, g_fork, dx, x, tgt, N, H, W, ws=slabs))
-                c64_pair_done = True
-            elif PROFILE.on:
-                PROFILE.conv_log.append(((N, H, W, C, K, R, S, stride, pad), "dgrad-wino2"))
-            if c64_pair_done:
-                pass
-            elif g_fork is not None:
-                PROFILE.bracket("conv_dgrad", lambda: lib.conv3x3_c64_wino_res(gy, U2, g_fork, dx, N, H, W))
-            else:
-                PROFILE.bracket("conv_dgrad", lambda: lib.conv3x3_c64_wino(gy, U2, None, False, dx, None, N, H, W))
-        elif ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x, memory_format=_CL)
-            ws = _conv_ws(lib, x.device, (N, H, W, C, K, R, S, stride, pad), True)
-            if PROFILE.on:
-                PROFILE.conv_log.append(((N, H, W, C, K, R, S, stride, pad), "dgrad"))
-            wt = _WEIGHT_PREP.get(ctx.w_param, wk, 0)
-            plus = getattr(ctx, "plus1x1", None)          # (dy, transposed filter) of a 1x1 convolution of the same input (_Conv2dPair.backward)
-            if plus is not None:
-                assert wt is not None and g_fork is None
-                if PROFILE.on:
-                    PROFILE.conv_log[-1] = ((N, H, W, C, K, R, S, stride, pad), "dgrad+1x1")
-                PROFILE.bracket("conv_dgrad", lambda: lib.conv2d_bwd_data_pre_plus1x1(gy, wt, plus[0], plus[1], dx, N, H, W, C, K, R, S, stride, pad))
-            elif wt is not None and g_fork is not None:
-                PROFILE.bracket("conv_dgrad", lambda: lib.conv2d_bwd_data_pre_res(gy, wt, g_fork, dx, N, H, W, C, K, R, S, stride, pad, ws=ws))
-            elif wt is not None:                   # [C][R][S][K] transpose from the step's weight_prep launch
-                PROFILE.bracket("conv_dgrad", lambda: lib.conv2d_bwd_data_pre(gy, wt, dx, N, H, W, C, K, R, S, stride, pad, ws=ws))
-            else:
-                scratch = torch.empty(wk.numel(), device=x.device, dtype=torch.float32)
-                PROFILE.bracket("conv_dgrad", lambda: lib.conv2d_bwd_data(gy, wk, dx, scratch, N, H, W, C, K, R, S, stride, pad, ws=ws))
-                if g_fork is not None:
-                    dx = dx + g_fork
-        if ctx.mask_input_grad and dx is not None and not masked:
-            dxm = torch.empty_like(dx, memory_format=_CL)
-            PROFILE.bracket("bias_relu_bwd", lambda: lib.bias_relu_bwd(dx, x, dx.numel() // C, C, dxm, None))
-            dx = dxm
-        if ctx.needs_input_grad[1] and ctx.w3 is not None:
-            dw = _stem_c3_wgrad(lib, ctx, x, gy)
-        elif c64_pair_done:
-            if dw is None:
-                _grad_ready(ctx.w_param)
-        elif ctx.needs_input_grad[1]:
-            w = ctx.w_param
-            tgt = w.grad if (getattr(w, "_hifihr_direct_grad", False) and w.grad is not None
-                             and w.grad.is_contiguous(memory_format=_CL)) else None
-            if tgt is None:
-                dw = torch.zeros_like(wk, memory_format=_CL)
-                tgt = dw
-            # accumulates (fp32 atomics) straight into the flat gradient buffer when the parameter lives in one
-            if v_saved is not None:
-                wm, wP, T = _wino_tile(lib, N, H, W, C, K)
-                Yt = Yt_done if Yt_done is not None else _wino_scratch(
-                    gy.device, ("Yt", w.data_ptr()) if _ASYNC_WGRAD.active else "Yt", wP * T * K)
-                parts = lib.wino_wgrad_parts(N, H, W, C, K, wm)  # > 0: the slab form on csrc/gemm.hip (no atomics, nothing to zero)
-                defer = wm == 4 and parts > 0 and _DEFER_DW.wants(w, dw is None)
-                if parts > 0:
-                    dU = _wino_scratch(gy.device, ("dUp", w.data_ptr()) if (_ASYNC_WGRAD.active or defer) else "dUp", parts * wP * K * C)
-                else:
-                    key = (gy.device, "dU", 16 * K * C)
-                    dU = _WINO_SCRATCH.get(key)
-                    if dU is None:                               # zero-initialised once; wino_dw_transform hands it back zeroed
-                        dU = torch.zeros(16 * K * C, device=gy.device, dtype=torch.float32)
-                        _WINO_SCRATCH[key] = dU
-
-                if PROFILE.on and pair_done is None:
-                    PROFILE.conv_log.append((("wino", N, H, W, C, K, wm), "gemm-tn"))
-
-                def run_w():
-                    if Yt_done is None:
-                        lib.wino_dy_transform(gy, Yt, N, H, W, K, wm)
-                    if pair_done is not None:              # the product already ran beside backward-data (same slab buffer)
-                        if defer:
-                            _DEFER_DW.add(pair_done[1], pair_done[2], tgt, K, C)
-                        else:
-                            lib.wino_dw_transform_parts(pair_done[1], pair_done[2], tgt, K, C, wm)
-                    elif parts > 0:
-                        lib.wino_wgrad_gemm_parts(v_saved, Yt, dU, N, H, W, C, K, parts, wm)
-                        if defer:
-                            _DEFER_DW.add(dU, parts, tgt, K, C)
-                        else:
-                            lib.wino_dw_transform_parts(dU, parts, tgt, K, C, wm)
-                    else:
-                        lib.wino_wgrad_gemm(v_saved, Yt, dU, N, H, W, C, K)
-                        lib.wino_dw_transform(dU, tgt, K, C, clear=True)
-                go = lambda: PROFILE.bracket("conv_wgrad_wino", run_w)
-                keep = (gy, v_saved, Yt, tgt)
-            else:
-                if PROFILE.on:
-                    PROFILE.conv_log.append(((N, H, W, C, K, R, S, stride, pad), "wgrad"))
-                nslab = lib.conv2d_wgrad_workspace_bytes(N, H, W, C, K, R, S, stride, pad)
-                go = lambda: PROFILE.bracket("conv_wgrad", lambda: lib.conv2d_bwd_weight(
-                    x, gy, tgt, N, H, W, C, K, R, S, stride, pad, ws=_wgrad_slabs(gy.device, nslab) if nslab else None))
-                keep = (gy, x, tgt)
-            if _ASYNC_WGRAD.active and dw is None:
-                _ASYNC_WGRAD.launch(gy.device, go, keep)
-            else:
-                go()
-            if dw is None:
-                _grad_ready(w)
-        if dx is None and g_fork is not None:
-            dx = g_fork
-        return dx, dw, None, None, None, db_ret, None, None, None, None
+        x, wk, y, v_saved = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dw, db = _conv_backward(gy, x, wk, y, v_saved, ctx.geom, ctx.w_param, ctx.b_param, need_x=need[0], need_w=need[1], need_b=need[5],
+                                    relu=ctx.relu, grad_premasked=ctx.grad_premasked, mask_input_grad=ctx.mask_input_grad,
+                                    wino_allowed=ctx.wino_allowed, w3=ctx.w3, g_fork=g_fork)
+        return dx, dw, None, None, None, db, None, None, None, None
 
 
 def conv2d_bias_act(x, w, bias, stride=1, pad=0, relu=True, grad_premasked=False, mask_input_grad=False):
@@ -1202,11 +1226,8 @@ class _Conv2dPair(torch.autograd.Function):
         x, wk1, wk2 = ctx.saved_tensors
         need_x, need_w1, need_w2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
 
-        def shim(wk, geom, w, need_w, fork):
-            return _CtxShim((x, wk, None, None), geom=geom, w_param=w, b_param=None, relu=False, w3=None, wino_allowed=ctx.wino_allowed,
-                            grad_premasked=False, mask_input_grad=False, fork=fork,
-                            needs_input_grad=(need_x, need_w, False, False, False, False, False, False, False, False))
-        dx2 = dw2 = dx = dw1 = None
+        def conv(gy, wk, geom, w, need_x, need_w, **kw):
+            return _conv_backward(gy, x, wk, None, None, geom, w, need_x=need_x, need_w=need_w, wino_allowed=ctx.wino_allowed, **kw)
         # Both gradients present and the step's re-laid-out filters at hand: the 1x1 convolution's data gradient -- it lands on the pixels
         # (stride i, stride j) only -- rides in the 3x3 convolution's backward-data launch as one more tap of that parity class
         # (hifihr_conv2d_bwd_data_pre_plus1x1), instead of a launch of its own whose mostly-zero result comes back in as the fork residual.
@@ -1223,35 +1244,27 @@ class _Conv2dPair(torch.autograd.Function):
             # 3x3's launch (hifihr_conv2d_bwd_weight_plus1x1) unless weight gradients run on the side stream
             w_both = (need_w1 and need_w2 and not _ASYNC_WGRAD.active
                       and lib.conv2d_bwd_weight_plus1x1_supported(N, H, W, C, K1, R, S, stride, pad))
+            dw1 = dw2 = None
             if w_both:
                 gy1c = gy1.contiguous(memory_format=_CL)
-
-                def target(w, wk):
-                    if getattr(w, "_hifihr_direct_grad", False) and w.grad is not None and w.grad.is_contiguous(memory_format=_CL):
-                        return w.grad, None
-                    t = torch.zeros_like(wk, memory_format=_CL)
-                    return t, t
-                t1, dw1 = target(ctx.w1, wk1)
-                t2, dw2 = target(ctx.w2, wk2)
+                t1, dw1 = _grad_target(ctx.w1, wk1, _CL)
+                t2, dw2 = _grad_target(ctx.w2, wk2, _CL)
                 if PROFILE.on:
-                    PROFILE.conv_log.append(((N, H, W, C, K1, R, S, stride, pad), "wgrad+1x1"))
+                    PROFILE.conv_log.append((ctx.geom1, "wgrad+1x1"))
                 PROFILE.bracket("conv_wgrad", lambda: lib.conv2d_bwd_weight_plus1x1(x, gy1c, t1, plus[0], t2, N, H, W, C, K1, R, S, stride, pad))
                 if dw1 is None:
                     _grad_ready(ctx.w1)
                 if dw2 is None:
                     _grad_ready(ctx.w2)
             else:
-                s2 = shim(wk2, ctx.geom2, ctx.w2, need_w2, False)
-                s2.needs_input_grad = (False,) + tuple(s2.needs_input_grad[1:])      # its weight gradient only
-                dw2 = _Conv2dMFMA.backward(s2, gy2)[1]
-            s1 = shim(wk1, ctx.geom1, ctx.w1, need_w1 and not w_both, False)
-            s1.plus1x1 = plus
-            dx, dw1b = _Conv2dMFMA.backward(s1, gy1)[:2]
+                dw2 = conv(gy2, wk2, ctx.geom2, ctx.w2, False, need_w2)[1]          # its weight gradient only
+            dx, dw1b, _ = conv(gy1, wk1, ctx.geom1, ctx.w1, need_x, need_w1 and not w_both, plus1x1=plus)
             return dx, (dw1 if w_both else dw1b), dw2, None
+        dx2 = dw2 = dw1 = None
         if gy2 is not None:
-            dx2, dw2 = _Conv2dMFMA.backward(shim(wk2, ctx.geom2, ctx.w2, need_w2, False), gy2)[:2]
+            dx2, dw2, _ = conv(gy2, wk2, ctx.geom2, ctx.w2, need_x, need_w2)
         if gy1 is not None:
-            dx, dw1 = _Conv2dMFMA.backward(shim(wk1, ctx.geom1, ctx.w1, need_w1, True), gy1, dx2)[:2]      # (dx2 enters as the fork residual)
+            dx, dw1, _ = conv(gy1, wk1, ctx.geom1, ctx.w1, need_x, need_w1, g_fork=dx2)      # (dx2 enters as the fork residual)
         else:
             dx = dx2
         return dx, dw1, dw2, None
@@ -1301,28 +1314,30 @@ class _BNAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, y, gamma, beta, save_mean, save_invstd = ctx.saved_tensors
-        y = y if (ctx.act == 1 and ctx.has_res) else None
-        lib = get_lib()
-        dy = dy.contiguous(memory_format=_CL)
-        dx = torch.empty_like(x, memory_format=_CL)
-        dres = torch.empty_like(x, memory_format=_CL) if ctx.has_res else None
-        red = _ZERO_POOL.acquire(lib.bn_stats_floats(ctx.C), x.device)
+        dx, dg, db, dres = _bn_act_backward(dy, x, y if (ctx.act == 1 and ctx.has_res) else None, gamma, beta, save_mean, save_invstd, ctx.act,
+                                            ctx.gamma_param, ctx.beta_param, ctx.has_res)
+        return dx, None, dg, db, dres, None, None, None, None, None
 
-        def acc_target(p):
-            if getattr(p, "_hifihr_direct_grad", False) and p.grad is not None:
-                return p.grad, None                 # accumulate straight into the flat gradient buffer
-            t = torch.zeros(ctx.C, device=x.device)
-            return t, t
-        dg_t, dg_ret = acc_target(ctx.gamma_param)
-        db_t, db_ret = acc_target(ctx.beta_param)
-        PROFILE.bracket("bn_bwd", lambda: lib.bn_act_bwd(dy, y, x, save_mean, save_invstd, gamma, beta, ctx.act, ctx.M, ctx.C, red,
-                                                         dx, dres, dg_t, db_t))
-        _ZERO_POOL.release(red)
-        if dg_ret is None:
-            _grad_ready(ctx.gamma_param)
-        if db_ret is None:
-            _grad_ready(ctx.beta_param)
-        return dx, None, dg_ret, db_ret, dres, None, None, None, None, None
+
+def _bn_act_backward(dy, x, y, gamma, beta, save_mean, save_invstd, act, gamma_param, beta_param, has_res):
+    """Backward of act(batch_norm(x) (+ residual)) -> (dx, dgamma, dbeta, dresidual); dgamma / dbeta None where accumulated in place.
+    y: the output where the ReLU mask is read from it (a residual was added), else None (csrc/bn.hip masked_grad recomputes it from x)."""
+    lib = get_lib()
+    C = x.shape[1]
+    dy = dy.contiguous(memory_format=_CL)
+    dx = torch.empty_like(x, memory_format=_CL)
+    dres = torch.empty_like(x, memory_format=_CL) if has_res else None
+    red = _ZERO_POOL.acquire(lib.bn_stats_floats(C), x.device)
+    dg_t, dg_ret = _grad_target(gamma_param, gamma)
+    db_t, db_ret = _grad_target(beta_param, beta)
+    PROFILE.bracket("bn_bwd", lambda: lib.bn_act_bwd(dy, y, x, save_mean, save_invstd, gamma, beta, act, x.numel() // C, C, red,
+                                                     dx, dres, dg_t, db_t))
+    _ZERO_POOL.release(red)
+    if dg_ret is None:
+        _grad_ready(gamma_param)
+    if db_ret is None:
+        _grad_ready(beta_param)
+    return dx, dg_ret, db_ret, dres
 
 
 class _BNActEval(torch.autograd.Function):
@@ -1357,15 +1372,6 @@ class _BNActEval(torch.autograd.Function):
         return g * sc, (g * xhat).sum((0, 2, 3)), g.sum((0, 2, 3)), (g if ctx.has_res else None), None, None, None, None
 
 
-class _CtxShim:
-    """What _Conv2dMFMA.backward / _BNAct.backward read from their autograd context, for the fused functions that run those backward
-    passes on tensors they saved themselves."""
-
-    def __init__(self, saved, **kw):
-        self.saved_tensors = saved
-        self.__dict__.update(kw)
-
-
 def bn_wino_fusable(x, w, bn, stride, pad):
     """A train-mode BatchNorm2d + ReLU in front of this convolution can run inside its Winograd input transform (csrc/wino4_bn.hip)."""
     if os.environ.get("HIFIHR_BN_WINO_FUSE", "1") == "0" or not bn.training or not x.is_cuda:
@@ -1389,27 +1395,6 @@ class _WinoLink:
 
     def __init__(self):
         self.lazy, self.red, self.g = False, None, None
-
-
-def _direct_grad(p):
-    return getattr(p, "_hifihr_direct_grad", False) and p.grad is not None
-
-
-def _wino_gemm_ws(lib, dev, N, H, W, C, K, m):
-    key = ("wino", N, H, W, C, K, m)
-    nb = _CONV_WS_BYTES.get(key)
-    if nb is None:
-        nb = lib.wino_gemm_workspace_bytes(N, H, W, C, K, m)
-        _CONV_WS_BYTES[key] = nb
-    if not nb:
-        return None
-    ws = _CONV_WS.get(dev)
-    if ws is None or ws.numel() * 4 < nb:
-        if ws is not None:
-            _RETIRED_SCRATCH.append(ws)
-        ws = torch.zeros(max(nb, 32 << 20) // 4 + 64, dtype=torch.float32, device=dev)
-        _CONV_WS[dev] = ws
-    return ws
 
 
 class _BNActWinoConv(torch.autograd.Function):
@@ -1451,7 +1436,7 @@ class _BNActWinoConv(torch.autograd.Function):
             lib.wino_bn_input_transform(x, stats, gamma, beta, res, out, V, N, H, W, C, m, eps, momentum, save_mean, save_invstd,
                                         running_mean, running_var)
             M = _wino_scratch(dev, "M", P * T * K)
-            lib.wino_gemm(V, Uu, M, N, H, W, C, K, ws=_wino_gemm_ws(lib, dev, N, H, W, C, K, m), m=m)
+            lib.wino_gemm(V, Uu, M, N, H, W, C, K, ws=_conv_ws(lib, dev, ("wino", N, H, W, C, K, m), False), m=m)
             lib.wino_output_transform(M, y, stats_next, N, H, W, K, m=m)
         if PROFILE.on:
             PROFILE.conv_log.append((("wino", N, H, W, C, K, m), "gemm"))
@@ -1484,29 +1469,23 @@ class _BNActWinoConv(torch.autograd.Function):
         gy = gy.contiguous(memory_format=_CL)
         link, in_link = ctx.link, ctx.in_link
         if os.environ.get("HIFIHR_BN_WINO_BWD", "1") == "0":      # A/B: the unfused backward (Winograd pipeline, add, batch-norm backward)
-            conv = _CtxShim((None, wk, None, V), geom=ctx.geom, w_param=w, b_param=None, relu=False, w3=None, wino_allowed=True,
-                            grad_premasked=False, mask_input_grad=False,
-                            needs_input_grad=(True, need[5], False, False, False, False, False))
-            d_a, dw = _Conv2dMFMA.backward(conv, gy)[:2]
+            d_a, dw, _ = _conv_backward(gy, None, wk, None, V, ctx.geom, w, need_x=True, need_w=need[5])
             if g_out is not None:
                 d_a = d_a + g_out
-            bn = _CtxShim((x, out if ctx.has_res else x.new_empty(0), gamma, beta, save_mean, save_invstd), act=1, has_res=ctx.has_res,
-                          M=N * H * W, C=C, gamma_param=ctx.gamma_param, beta_param=ctx.beta_param)
-            dx, _, dg, db, dres = _BNAct.backward(bn, d_a)[:5]
+            dx, dg, db, dres = _bn_act_backward(d_a, x, out if ctx.has_res else None, gamma, beta, save_mean, save_invstd, 1,
+                                                ctx.gamma_param, ctx.beta_param, ctx.has_res)
             return dx, None, dg, db, dres, dw, None, None, None, None, None, None, None
 
-        def acc_target(p, n):
-            if _direct_grad(p):
-                return p.grad, None
-            t = torch.zeros(n, device=dev)
-            return t, t
         res_out = out if ctx.has_res else None
         gadd = g_out.contiguous(memory_format=_CL) if g_out is not None else None
         g_in = torch.empty_like(x, memory_format=_CL)
         red = _ZERO_POOL.acquire(lib.bn_stats_floats(C), dev)
         lazy_in = link.lazy and link.red is not None            # gy is the masked gradient of the NEXT batch-norm, un-applied
         dw_box = [None]
-        direct_w = _direct_grad(w) and w.grad.is_contiguous(memory_format=_CL)
+        direct_w = _direct_grad(w, _CL)
+        # 2 + 4a. the backward-data product and the backward-weight product do not depend on each other: ONE launch whose workgroups
+        # split between them (hifihr_wino4_bwd_gemm_pair; HIFIHR_GEMM_PAIR=0: two launches)
+        pair = need[5] and m == 4 and _GEMM_PAIR and lib.wino4_bwd_gemm_pair_supported(N, H, W, C, K)
 
         def run():
             # 1. transforms of d loss / d y: V' (backward-data) and Y' (backward-weight)
@@ -1518,40 +1497,21 @@ class _BNActWinoConv(torch.autograd.Function):
             else:
                 lib.wino_input_dy_transform(gy, V2, Yt, N, H, W, K, m)
             # 2. backward-data product on the rotated transposed filter
-            U2 = _WEIGHT_PREP.get(w, wk, 4)
-            if U2 is None:
-                wt = _wino_scratch(dev, "wt", wk.numel())
-                lib.weight_transpose(wk, wt, K, 9, C)
-                U2 = _wino_scratch(dev, "U", P * K * C)
-                lib.wino_weight_transform(wt, U2, C, K, 1, m)
+            U2 = _wino_u_bwd(lib, wk, _WEIGHT_PREP.get(w, wk, 4), dev, C, K, m)
             M2 = _wino_scratch(dev, "M", P * T * C)
-            pair = need[5] and m == 4 and _GEMM_PAIR and lib.wino4_bwd_gemm_pair_supported(N, H, W, C, K)
-            defer = need[5] and m == 4 and _DEFER_DW.wants(w, direct_w)       # dw += G^T dU G joins the step's one deferred launch
-            slab_key = ("dUp", w.data_ptr()) if defer else "dUp"
+            slabs = _wino_wgrad_slabs(lib, w, direct_w, False, dev, N, H, W, C, K, m) if need[5] else None
             if pair:
-                # 2 + 4a. the backward-data product and the backward-weight product do not depend on each other: ONE launch whose
-                # workgroups split between them (hifihr_wino4_bwd_gemm_pair; HIFIHR_GEMM_PAIR=0: two launches)
-                parts = lib.wino_wgrad_parts(N, H, W, C, K, m)
-                dU = _wino_scratch(dev, slab_key, parts * P * K * C)
-                lib.wino4_bwd_gemm_pair(V2, U2, M2, V, Yt, dU, N, H, W, C, K, parts)
+                lib.wino4_bwd_gemm_pair(V2, U2, M2, V, Yt, slabs[0], N, H, W, C, K, slabs[1])
             else:
-                lib.wino_gemm(V2, U2, M2, N, H, W, K, C, ws=_wino_gemm_ws(lib, dev, N, H, W, K, C, m), m=m)
+                lib.wino_gemm(V2, U2, M2, N, H, W, K, C, ws=_conv_ws(lib, dev, ("wino", N, H, W, K, C, m), False), m=m)
             # 3. output transform + identity-branch gradient + ReLU mask + batch-norm reduction
             lib.wino_output_transform_bnred(M2, x, res_out, gadd, save_mean, save_invstd, gamma, beta, red, g_in, N, H, W, C, m)
             # 4. backward-weight: dU = Y'^T V over the tiles (slabs, fixed order), dw += G^T dU G
             if need[5]:
-                tgt = w.grad if direct_w else torch.zeros_like(wk, memory_format=_CL)
-                if not pair:
-                    parts = lib.wino_wgrad_parts(N, H, W, C, K, m)
-                    dU = _wino_scratch(dev, slab_key, parts * P * K * C)
-                    lib.wino_wgrad_gemm_parts(V, Yt, dU, N, H, W, C, K, parts, m)
-                if defer and parts > 0:
-                    _DEFER_DW.add(dU, parts, tgt, K, C)
-                else:
-                    lib.wino_dw_transform_parts(dU, parts, tgt, K, C, m)
-                dw_box[0] = None if direct_w else tgt
+                tgt, dw_box[0] = _grad_target(w, wk, _CL)
+                _wino_wgrad_tail(lib, V, Yt, slabs, tgt, N, H, W, C, K, m, pair)
         if PROFILE.on:
-            if need[5] and m == 4 and _GEMM_PAIR and lib.wino4_bwd_gemm_pair_supported(N, H, W, C, K):
+            if pair:
                 PROFILE.conv_log.append((("wino", N, H, W, C, K, m), "gemm-pair"))
             else:
                 PROFILE.conv_log.append((("wino", N, H, W, K, C, m), "gemm"))
@@ -1575,8 +1535,8 @@ class _BNActWinoConv(torch.autograd.Function):
             dx = g_in                            # NOT d loss / d x yet: see _WinoLink
         else:
             dx = torch.empty_like(x, memory_format=_CL)
-            dg_t, dg_ret = acc_target(ctx.gamma_param, C)
-            db_t, db_ret = acc_target(ctx.beta_param, C)
+            dg_t, dg_ret = _grad_target(ctx.gamma_param, gamma)
+            db_t, db_ret = _grad_target(ctx.beta_param, beta)
             PROFILE.bracket("bn_bwd", lambda: lib.bn_bwd_apply(g_in, x, save_mean, save_invstd, gamma, N * H * W, C, red, dx, dg_t, db_t))
             _ZERO_POOL.release(red)
             if dg_ret is None:
@@ -1660,8 +1620,8 @@ class _BNReluMaxPool(torch.autograd.Function):
         _DEFER_DW.flush_early(x.device)           # behind the stem's pooling only the stem is left: the deferred weight-gradient launch runs beside it
         dx = torch.empty_like(x, memory_format=_CL)
         red = _ZERO_POOL.acquire(lib.bn_stats_floats(C), x.device)
-        dg_t, dg_ret = _bn_acc_target(ctx.gamma_param, C, x.device)
-        db_t, db_ret = _bn_acc_target(ctx.beta_param, C, x.device)
+        dg_t, dg_ret = _grad_target(ctx.gamma_param, gamma)
+        db_t, db_ret = _grad_target(ctx.beta_param, beta)
         if y is not None:
             PROFILE.bracket("bn_pool_bwd", lambda: lib.bn_relu_maxpool_bwd_y(gy, y, tap, x, save_mean, save_invstd, gamma, beta, N, H, W, C, red, dx,
                                                                             dg_t, db_t))
@@ -1674,13 +1634,6 @@ class _BNReluMaxPool(torch.autograd.Function):
         if db_ret is None:
             _grad_ready(ctx.beta_param)
         return dx, None, dg_ret, db_ret, None, None, None, None
-
-
-def _bn_acc_target(p, C, device):
-    if getattr(p, "_hifihr_direct_grad", False) and p.grad is not None:
-        return p.grad, None                 # accumulate straight into the flat gradient buffer
-    t = torch.zeros(C, device=device)
-    return t, t
 
 
 def bn_relu_maxpool(x, stats, bn: torch.nn.BatchNorm2d):
@@ -1900,13 +1853,13 @@ class _Linear(torch.autograd.Function):
         need_dx = ctx.needs_input_grad[0]
         dz = torch.empty(B, O, device=dy.device)
         dx = torch.empty_like(x) if need_dx else None
-        dw_t, dw_ret = _acc_target(pw, pw.shape, dy.device)
-        db_t, db_ret = _acc_target(pb, pb.shape, dy.device) if pb is not None else (None, None)
+        dw_t, dw_ret = _grad_target(pw, pw)
+        db_t, db_ret = _grad_target(pb, pb) if pb is not None else (None, None)
         bn = None
         dg_ret = dbt_ret = None
         if gamma is not None:
-            dg_t, dg_ret = _acc_target(pg, pg.shape, dy.device)
-            dbt_t, dbt_ret = _acc_target(pbeta, pbeta.shape, dy.device)
+            dg_t, dg_ret = _grad_target(pg, pg)
+            dbt_t, dbt_ret = _grad_target(pbeta, pbeta)
             bn = (gamma, z, sm, si, dg_t, dbt_t)
         PROFILE.bracket("linear_bwd", lambda: lib.linear_bwd(dy, y, x, w, ctx.act, dz, dw_t, db_t, dx, bn))
         for p, ret in ((pw, dw_ret), (pb, db_ret), (pg, dg_ret), (pbeta, dbt_ret)):
@@ -1957,10 +1910,10 @@ class _LinearGroup(torch.autograd.Function):
                 first = dx is None
                 if first:
                     dx = shared[key] = torch.empty_like(xs[i])
-            dw_t, dws[i] = _acc_target(pws[i], pws[i].shape, dy.device)
+            dw_t, dws[i] = _grad_target(pws[i], pws[i])
             db_t = None
             if pbs[i] is not None:
-                db_t, dbs[i] = _acc_target(pbs[i], pbs[i].shape, dy.device)
+                db_t, dbs[i] = _grad_target(pbs[i], pbs[i])
             dxs[i] = dx if (dx is not None and first) else None          # (returned once: the shared buffer holds the sum)
             members.append(dict(x=xs[i], w=ws_c[i], y=ys[i], act=ctx.acts[i], dy=dy, dz=torch.empty_like(dy), dW=dw_t, db=db_t, dx=dx))
             ready += [p for p, ret in ((pws[i], dws[i]), (pbs[i], dbs[i])) if p is not None and ret is None]
@@ -2111,7 +2064,7 @@ class _SqueezeExcite(torch.autograd.Function):
         rets = []
         tgts = []
         for p in (pw1, pb1, pw2, pb2):
-            t, r = _acc_target(p, p.shape, dev)
+            t, r = _grad_target(p, p)
             tgts.append(t); rets.append(r)
         dmean = torch.empty(B, C, device=dev)
         dz2, dz1 = torch.empty(B, C, device=dev), torch.empty(B, SQ, device=dev)
@@ -2179,15 +2132,6 @@ def squeeze_excite(x, reduce_conv, expand_conv):
 # ------------------------------------------------------------------------------------------------
 # pooling (csrc/pool.hip)
 # ------------------------------------------------------------------------------------------------
-def _acc_target(p, shape, device):
-    """(tensor the kernel accumulates into, tensor to hand back to autograd or None): straight into the flat gradient
-    buffer when the parameter lives in one (hifihr_amd/optim.py FlatParams)."""
-    if getattr(p, "_hifihr_direct_grad", False) and p.grad is not None:
-        return p.grad, None
-    t = torch.zeros(shape, device=device)
-    return t, t
-
-
 class _MMPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p):
@@ -2209,7 +2153,7 @@ class _MMPool(torch.autograd.Function):
         B, C, H, W = ctx.shape
         gy = gy.contiguous()
         dx = torch.empty((B, C, H, W), device=gy.device, memory_format=_CL) if ctx.needs_input_grad[0] else None
-        dp_t, dp_ret = _acc_target(ctx.p_param, p.shape, gy.device) if ctx.needs_input_grad[1] else (None, None)
+        dp_t, dp_ret = _grad_target(ctx.p_param, p) if ctx.needs_input_grad[1] else (None, None)
         if dx is None:
             raise NotImplementedError("mmpool backward without an input gradient")
         PROFILE.bracket("mmpool_bwd", lambda: get_lib().mmpool_bwd(gy, p, argmax, xmax, xavg, B, H * W, C, dx, dp_t))
@@ -2415,10 +2359,7 @@ class _DwConv(torch.autograd.Function):
             PROFILE.bracket("dwconv_dgrad", lambda: lib.dwconv2d_bwd_data(gy, w, dx, *ctx.geom))
         if ctx.needs_input_grad[1]:
             p = ctx.w_param
-            tgt = p.grad if (getattr(p, "_hifihr_direct_grad", False) and p.grad is not None and p.grad.is_contiguous()) else None
-            if tgt is None:
-                dw = torch.zeros_like(w)
-                tgt = dw
+            tgt, dw = _grad_target(p, w, torch.contiguous_format)
             PROFILE.bracket("dwconv_wgrad", lambda: lib.dwconv2d_bwd_weight(x, gy, tgt, *ctx.geom))
             if dw is None:
                 _grad_ready(p)
@@ -2469,10 +2410,7 @@ class _BNSwishDwConv(torch.autograd.Function):
         dw = None
         if ctx.needs_input_grad[8]:
             p = ctx.w_param
-            tgt = p.grad if (getattr(p, "_hifihr_direct_grad", False) and p.grad is not None and p.grad.is_contiguous()) else None
-            if tgt is None:
-                dw = torch.zeros_like(w)
-                tgt = dw
+            tgt, dw = _grad_target(p, w, torch.contiguous_format)
             PROFILE.bracket("dwconv_wgrad", lambda: lib.dwconv2d_bwd_weight_bnswish(e, save_mean, save_invstd, gamma, beta, gy, tgt, *ctx.geom))
             if dw is None:
                 _grad_ready(p)
@@ -2480,14 +2418,8 @@ class _BNSwishDwConv(torch.autograd.Function):
         PROFILE.bracket("dwconv_dgrad", lambda: lib.dwconv2d_bwd_data(gy, w, da, *ctx.geom))
         de = torch.empty_like(e, memory_format=_CL)
         red = _ZERO_POOL.acquire(lib.bn_stats_floats(ctx.C), e.device)
-
-        def acc_target(p):
-            if getattr(p, "_hifihr_direct_grad", False) and p.grad is not None:
-                return p.grad, None
-            t = torch.zeros(ctx.C, device=e.device)
-            return t, t
-        dg_t, dg_ret = acc_target(ctx.gamma_param)
-        db_t, db_ret = acc_target(ctx.beta_param)
+        dg_t, dg_ret = _grad_target(ctx.gamma_param, gamma)
+        db_t, db_ret = _grad_target(ctx.beta_param, beta)
         PROFILE.bracket("bn_bwd", lambda: lib.bn_act_bwd(da, None, e, save_mean, save_invstd, gamma, beta, 2, ctx.M, ctx.C, red, de, None, dg_t, db_t))
         _ZERO_POOL.release(red)
         if dg_ret is None:

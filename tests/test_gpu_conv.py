@@ -654,3 +654,279 @@ def test_conv_contract_reaches_every_dispatch_path(lib):
         assert lib.conv2d_bwd_data_pre_plus1x1_supported(N, H, H, C, K, 3, 3, 2, 1)
         assert lib.conv2d_bwd_weight_plus1x1_supported(N, H, H, C, K, 3, 3, 2, 1)
         assert lib.conv2d_fwd_bnstats_pair_supported(N, H, H, C, 2, K, 3, 1, K, 1, 0)
+
+
+# ---- ops.py's dispatch among those entry points: every path of the convolution forward / backward, driven through the public functions
+#      (conv2d, conv2d_bias_act, conv2d_pair, bn_act_wino_conv) and compared with float64 autograd.  Each case runs forward + backward twice
+#      (a layer is served by the step's weight_prep launch from the second prepared_weights() scope on) and checks the second iteration's
+#      ops.PROFILE.conv_log entries, which name the path taken.  Tolerances of test_winograd_f4_path / conv_case: outputs and input gradients
+#      within 5e-5 of their maximum, parameter gradients within 1e-4; 2e-4 behind a batch-norm (the trunk tests').
+_CL = torch.channels_last
+ROOFLINE_DIRECTIONS = {"fwd", "dgrad", "wgrad", "gemm", "gemm-tn", "gemm-pair", "fwd-pair", "fwd-wino2", "dgrad-wino2", "c64-pair",
+                       "wgrad+1x1", "dgrad+1x1"}             # every direction bench.py:conv_path_rooflines prices
+
+
+def _pick(cands, ok, what):
+    for g in cands:
+        if ok(*g):
+            return g
+    raise AssertionError(f"no candidate geometry takes {what}")
+
+
+def _geoms(lib):
+    from hifihr_amd import ops
+    dev = torch.device("cuda", 0)
+    f4 = _pick([(16, 14, 14, 128, 128), (32, 14, 14, 128, 128), (32, 28, 28, 128, 128), (32, 14, 14, 256, 256)],
+               lambda N, H, W, C, K: (ops._wino_ok(C, K, 3, 3, 1, 1) and ops._wino_tile(lib, N, H, W, C, K)[0] == 4
+                                      and lib.wino4_bwd_gemm_pair_supported(N, H, W, C, K) and lib.wino_wgrad_parts(N, H, W, C, K, 4) > 0
+                                      and lib.wino_bn_input_supported(C, 4) and lib.wino_bn_input_supported(K, 4)), "the paired F(4x4) backward")
+    f2 = _pick([(3, 9, 9, 128, 160), (4, 14, 14, 96, 128)],
+               lambda N, H, W, C, K: (ops._wino_ok(C, K, 3, 3, 1, 1) and ops._wino_tile(lib, N, H, W, C, K)[0] == 2
+                                      and lib.wino_wgrad_parts(N, H, W, C, K, 2) == 0), "F(2x2) with the atomic weight gradient")
+    c64 = _pick([(4, 28, 28), (8, 28, 28), (8, 56, 56)],
+                lambda N, H, W: (ops._wino2_fused_ok(lib, N, H, W, 64, 64, 3, 3, 1, 1, device=dev) and lib.conv3x3_c64_bwd_pair_supported(N, H, W)
+                                 and lib.conv2d_wgrad_workspace_bytes(N, H, W, 64, 64, 3, 3, 1, 1) > 0), "the 64 -> 64 one-launch kernels")
+    s2 = _pick([(4, 28, 28, 64, 128), (8, 28, 28, 64, 128), (8, 56, 56, 64, 128)],
+               lambda N, H, W, C, K: (lib.conv2d_fwd_bnstats_pair_supported(N, H, W, C, 2, K, 3, 1, K, 1, 0)
+                                      and lib.conv2d_bwd_data_pre_plus1x1_supported(N, H, W, C, K, 3, 3, 2, 1)
+                                      and lib.conv2d_bwd_weight_plus1x1_supported(N, H, W, C, K, 3, 3, 2, 1)), "the strided pair with plus1x1")
+    stem = _pick([(4, 56, 56, 64, 7, 2, 3), (8, 56, 56, 64, 7, 2, 3)],
+                 lambda N, H, W, K, R, st, pd: lib.conv2d_bwd_weight_c3_supported(N, H, W, K, R, R, st, pd), "the c3 stem weight gradient")
+    stem4 = _pick([(2, 16, 16, 16, 3, 1, 1), (2, 9, 9, 16, 3, 1, 1)],
+                  lambda N, H, W, K, R, st, pd: not lib.conv2d_bwd_weight_c3_supported(N, H, W, K, R, R, st, pd), "the 4-channel stem temporary")
+    for N, H, W, C, K in (f4, f2):
+        assert not ops._wino2_fused_ok(lib, N, H, W, C, K, 3, 3, 1, 1, device=dev)
+    return dict(f4=f4, f2=f2, c64=c64, s2=s2, stem=stem, stem4=stem4, light=(4, 14, 14, 48, 48))
+
+
+def _rand(shape, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(shape, generator=g) * scale
+
+
+def _leaf(t, grad=True):
+    t = t.cuda().contiguous(memory_format=_CL) if t.dim() == 4 else t.cuda()
+    return t.requires_grad_(grad)
+
+
+def _param(t, grad=True):
+    return torch.nn.Parameter(t.cuda().contiguous(memory_format=_CL) if t.dim() == 4 else t.cuda(), requires_grad=grad)
+
+
+def _conv_setup(N, H, W, C, K, R, stride, pad, call="conv2d", bias=False, mask_input=False, premasked=False, fork=False,
+                want_stats=False, x_grad=True, w_grad=True, stem=False):
+    """-> (fwd, ref, inputs, params) of one convolution: fwd() our outputs; ref(ours, *inputs64, *params64) float64 autograd's (the ReLU
+    pattern taken from our forward: which side of zero a float rounds to is not the dispatch's business)."""
+    from hifihr_amd import ops
+    import torch.nn.functional as F
+    Cw = 3 if stem else C
+    x = _rand((N, C, H, W), N + H + C)
+    if stem:
+        x[:, 3] = 0                                      # NHWC4 image: zero fourth plane
+    if mask_input:
+        x = x.clamp_min(0)                               # x is a ReLU's output
+    x = _leaf(x, x_grad)
+    w = _param(_rand((K, Cw, R, R), K + R, (Cw * R * R) ** -0.5), w_grad)
+    b = _param(_rand((K,), 7, 0.1), not premasked) if (bias or call == "bias_act") else None
+    relu = call == "bias_act"
+    params = [w] + ([b] if b is not None else [])
+
+    def fwd():
+        if call == "bias_act":
+            return [ops.conv2d_bias_act(x, w, b, stride, pad, True, grad_premasked=premasked, mask_input_grad=mask_input)]
+        r = ops.conv2d(x, w, stride, pad, want_stats=want_stats, fork=fork)
+        r = r if isinstance(r, tuple) else (r,)
+        return [r[0]] + ([r[-1]] if fork else [])
+
+    def ref(ours, x64, w64, b64=None):
+        xi = x64[:, :3] if stem else x64
+        if mask_input:
+            xi = xi * (xi > 0)                           # the ReLU backward of x's producer: dx comes back multiplied by [x > 0]
+        y = F.conv2d(xi, w64, b64, stride, pad)
+        if relu:
+            y = y * (ours[0] > 0)
+        return [y] + ([x64] if fork else [])
+    return fwd, ref, [x], params
+
+
+def _pair_setup(N, H, W, C, K):
+    from hifihr_amd import ops
+    import torch.nn.functional as F
+    x = _leaf(_rand((N, C, H, W), 11))
+    w1 = _param(_rand((K, C, 3, 3), 12, (9 * C) ** -0.5))
+    w2 = _param(_rand((K, C, 1, 1), 13, C ** -0.5))
+
+    def fwd():
+        y1, _, y2, _ = ops.conv2d_pair(x, w1, w2, 2)
+        return [y1, y2]
+    return fwd, lambda ours, x64, a, b: [F.conv2d(x64, a, None, 2, 1), F.conv2d(x64, b, None, 2, 0)], [x], [w1, w2]
+
+
+def _bn_wino_setup(N, H, W, C, K):
+    """producer conv2d(want_stats) (1x1, frozen filter) -> bn_act_wino_conv with an identity branch (whose output, relu(bn(x) + residual),
+    gives the ReLU pattern)"""
+    from hifihr_amd import ops
+    import torch.nn.functional as F
+    x0 = _leaf(_rand((N, 64, H, W), 21))
+    w0 = _param(_rand((C, 64, 1, 1), 22, 0.125), False)
+    res = _leaf(_rand((N, C, H, W), 23))
+    w = _param(_rand((K, C, 3, 3), 24, (9 * C) ** -0.5))
+    bn = torch.nn.BatchNorm2d(C).cuda().train()
+    with torch.no_grad():
+        bn.weight.copy_(1 + 0.1 * _rand((C,), 25)); bn.bias.copy_(0.1 * _rand((C,), 26))
+
+    def fwd():
+        xr, st = ops.conv2d(x0, w0, 1, 0, want_stats=True)
+        y, _, out = ops.bn_act_wino_conv(xr, st, bn, res, w, False)
+        return [y, out]
+
+    def ref(ours, x64, r64, w064, w64, g64, b64):
+        z = F.batch_norm(F.conv2d(x64, w064), None, None, g64, b64, True, 0.0, bn.eps) + r64
+        a = z * (ours[1] > 0)
+        return [F.conv2d(a, w64, None, 1, 1), a]
+    return fwd, ref, [x0, res], [w0, w, bn.weight, bn.bias]
+
+
+def _cases(lib):
+    """name -> (expected conv_log entries of one iteration, setup, options)"""
+    G = _geoms(lib)
+    wk = lambda g, C, K, m: ("wino",) + tuple(g[:3]) + (C, K, m)
+    d9 = lambda N, H, W, C, K, R, st, pd: (N, H, W, C, K, R, R, st, pd)
+    N, H, W, C, K = G["f4"]
+    f4 = lambda **kw: _conv_setup(N, H, W, C, K, 3, 1, 1, **kw)
+    f4_paired = [(wk(G["f4"], C, K, 4), "gemm"), (wk(G["f4"], C, K, 4), "gemm-pair")]
+    f4_apart = [(wk(G["f4"], C, K, 4), "gemm"), (wk(G["f4"], K, C, 4), "gemm"), (wk(G["f4"], C, K, 4), "gemm-tn")]
+    n2, h2, w2, c2, k2 = G["f2"]
+    f2 = lambda **kw: _conv_setup(n2, h2, w2, c2, k2, 3, 1, 1, **kw)
+    f2_log = [(wk(G["f2"], c2, k2, 2), "gemm"), (wk(G["f2"], k2, c2, 2), "gemm"), (wk(G["f2"], c2, k2, 2), "gemm-tn")]
+    nc, hc, wc = G["c64"]
+    c64 = lambda **kw: _conv_setup(nc, hc, wc, 64, 64, 3, 1, 1, **kw)
+    gc = d9(nc, hc, wc, 64, 64, 3, 1, 1)
+    ns, hs, ws_, cs, ks = G["s2"]
+    s2 = lambda **kw: _conv_setup(ns, hs, ws_, cs, ks, 3, 2, 1, **kw)
+    gs, gs1 = d9(ns, hs, ws_, cs, ks, 3, 2, 1), d9(ns, hs, ws_, cs, ks, 1, 2, 0)
+    direct = lambda g: [(g, "fwd"), (g, "dgrad"), (g, "wgrad")]
+    gl = d9(*G["light"], 3, 1, 0)
+    st_, st4 = G["stem"], G["stem4"]
+    gst, gst4 = d9(*st_[:3], 4, *st_[3:]), d9(*st4[:3], 4, *st4[3:])
+    stem = lambda g: (lambda: _conv_setup(*g[:3], 4, *g[3:], stem=True, x_grad=False))
+    pair_fwd = (("pair", ns, hs, ws_, cs, ks, ks, 2), "fwd-pair")
+    return {
+        # forward: F(4x4) on the prepared U; backward-data on the prepared U' paired with the weight-gradient product; slabs deferred
+        "f4": (f4_paired, f4, dict(direct=True)),
+        "f4_async": (f4_paired, f4, dict(direct=True, async_wgrad=True)),          # the pair with its own slab buffer, transform on the side stream
+        "f4_grad_to_autograd": (f4_paired, f4, dict()),                          # slabs transformed at once into a fresh tensor
+        # no scope: U and U' computed in place (the transpose fallback), two products, slabs transformed at once
+        "f4_unprepared": (f4_apart, f4, dict(direct=True, scope=False)),
+        "f4_bias_relu": (f4_paired, lambda: f4(call="bias_act"), dict(direct=True)),
+        "f4_mask_in_output_transform": (f4_paired, lambda: f4(call="bias_act", mask_input=True), dict(direct=True)),
+        "f4_premasked_frozen_w": (f4_apart[:2], lambda: f4(call="bias_act", premasked=True, w_grad=False), dict(premasked=True)),
+        "f4_stats_unprepared": (f4_apart, lambda: f4(want_stats=True), dict(scope=False)),
+        # F(2x2): channels off the slab GEMM's multiple of 64 -> the atomic (parts == 0) weight-gradient product
+        "f2_atomic": (f2_log, f2, dict(direct=True)),
+        "f2_atomic_async": (f2_log, f2, dict(direct=True, async_wgrad=True)),
+        "f2_bias_relu_mask_apart_unprepared": (f2_log, lambda: f2(call="bias_act", mask_input=True), dict(scope=False)),
+        # 64 -> 64: the register-resident Winograd kernels
+        "c64_pair_deferred": ([(gc, "fwd-wino2"), (gc, "c64-pair")], c64, dict(direct=True)),
+        "c64_pair_immediate": ([(gc, "fwd-wino2"), (gc, "c64-pair")], c64, dict()),
+        "c64_pair_async": ([(gc, "fwd-wino2"), (gc, "c64-pair")], c64, dict(direct=True, async_wgrad=True)),
+        "c64_res": ([(gc, "fwd-wino2"), (gc, "dgrad-wino2")], lambda: c64(fork=True, w_grad=False), dict()),
+        "c64_plain": ([(gc, "fwd-wino2"), (gc, "dgrad-wino2")], lambda: c64(w_grad=False), dict()),
+        "direct_wgrad_slabs": ([(gc, "fwd-wino2"), (gc, "wgrad")], lambda: c64(x_grad=False), dict(direct=True)),
+        "direct_wgrad_slabs_async": ([(gc, "fwd-wino2"), (gc, "wgrad")], lambda: c64(x_grad=False), dict(direct=True, async_wgrad=True)),
+        "direct_unprepared_fork": (direct(gc), lambda: c64(fork=True), dict(scope=False)),
+        # the direct kernels
+        "direct_pre_res": (direct(gs), lambda: s2(fork=True), dict(direct=True)),
+        "direct_pre_stats": (direct(gs), lambda: s2(want_stats=True), dict(direct=True)),
+        "direct_pre_async": (direct(gs), s2, dict(direct=True, async_wgrad=True)),
+        "direct_scratch_fork": (direct(gs), lambda: s2(fork=True), dict(scope=False)),
+        "direct_bias_relu": (direct(gl), lambda: _conv_setup(*G["light"], 3, 1, 0, call="bias_act"), dict(direct=True)),
+        "direct_bias_relu_mask": (direct(gl), lambda: _conv_setup(*G["light"], 3, 1, 0, call="bias_act", mask_input=True), dict()),
+        # the 3-channel stem on an NHWC4 image: the padded filter prepared (kind 5) or built in place
+        "stem_c3": ([(gst, "fwd"), (gst, "wgrad")], stem(st_), dict(direct=True)),
+        "stem_c3_async": ([(gst, "fwd"), (gst, "wgrad")], stem(st_), dict(direct=True, async_wgrad=True)),
+        "stem_c3_unprepared": ([(gst, "fwd"), (gst, "wgrad")], stem(st_), dict(scope=False)),
+        "stem_c4_temporary": ([(gst4, "fwd"), (gst4, "wgrad")], stem(st4), dict(direct=True)),
+        "stem_c4_temporary_async": ([(gst4, "fwd"), (gst4, "wgrad")], stem(st4), dict(direct=True, async_wgrad=True)),
+        "stem_c4_temporary_to_autograd": ([(gst4, "fwd"), (gst4, "wgrad")], stem(st4), dict()),
+        # conv1 + downsample[0] of a stage's first block
+        "pair_both_wgrads": ([pair_fwd, (gs, "dgrad+1x1"), (gs, "wgrad+1x1")], lambda: _pair_setup(*G["s2"]), dict(direct=True)),
+        "pair_w_apart": ([pair_fwd, (gs, "dgrad+1x1"), (gs, "wgrad"), (gs1, "wgrad")], lambda: _pair_setup(*G["s2"]),
+                         dict(direct=True, async_wgrad=True)),
+        "pair_fork_fallback": ([pair_fwd, (gs, "dgrad"), (gs, "wgrad"), (gs1, "dgrad"), (gs1, "wgrad")], lambda: _pair_setup(*G["s2"]),
+                               dict(scope=False)),
+        # batch-norm + ReLU inside the Winograd input transform, backward fused or (HIFIHR_BN_WINO_BWD=0) through the plain backward passes
+        "bn_wino_fused": ([(d9(N, H, W, 64, C, 1, 1, 0), "fwd"), (d9(N, H, W, 64, C, 1, 1, 0), "dgrad")] + f4_paired,
+                          lambda: _bn_wino_setup(N, H, W, C, K), dict(direct=True, tol=2e-4, wtol=2e-4)),
+        "bn_wino_fused_to_autograd": ([(d9(N, H, W, 64, C, 1, 1, 0), "fwd"), (d9(N, H, W, 64, C, 1, 1, 0), "dgrad")] + f4_paired,
+                                      lambda: _bn_wino_setup(N, H, W, C, K), dict(tol=2e-4, wtol=2e-4)),
+        "bn_wino_unfused": ([(d9(N, H, W, 64, C, 1, 1, 0), "fwd"), (d9(N, H, W, 64, C, 1, 1, 0), "dgrad")] + f4_paired,
+                            lambda: _bn_wino_setup(N, H, W, C, K), dict(direct=True, tol=2e-4, wtol=2e-4, env={"HIFIHR_BN_WINO_BWD": "0"})),
+    }
+
+
+DISPATCH_CASES = ["f4", "f4_async", "f4_grad_to_autograd", "f4_unprepared", "f4_bias_relu", "f4_mask_in_output_transform", "f4_premasked_frozen_w",
+                  "f4_stats_unprepared", "f2_atomic", "f2_atomic_async", "f2_bias_relu_mask_apart_unprepared", "c64_pair_deferred",
+                  "c64_pair_immediate", "c64_pair_async", "c64_res", "c64_plain", "direct_wgrad_slabs", "direct_wgrad_slabs_async",
+                  "direct_unprepared_fork", "direct_pre_res", "direct_pre_stats", "direct_pre_async", "direct_scratch_fork", "direct_bias_relu",
+                  "direct_bias_relu_mask", "stem_c3", "stem_c3_async", "stem_c3_unprepared", "stem_c4_temporary", "stem_c4_temporary_async",
+                  "stem_c4_temporary_to_autograd", "pair_both_wgrads", "pair_w_apart", "pair_fork_fallback", "bn_wino_fused",
+                  "bn_wino_fused_to_autograd", "bn_wino_unfused"]
+
+
+def _run_dispatch_case(expect, setup, monkeypatch, scope=True, async_wgrad=False, direct=False, premasked=False, tol=5e-5, wtol=1e-4, env=None):
+    import contextlib
+    from collections import Counter
+    from hifihr_amd import ops
+    for k, v in (env or {}).items():
+        monkeypatch.setenv(k, v)
+    fwd, ref, inputs, params = setup()
+    trained = [p for p in params if p.requires_grad]
+    for p in trained:
+        p._hifihr_direct_grad = direct
+    base = None
+    for _ in range(2):
+        for t in inputs + trained:
+            t.grad = torch.zeros_like(t) if (direct and any(t is p for p in trained)) else None
+        ops.PROFILE.enable()
+        ops.PROFILE.conv_log.clear()
+        try:
+            with (ops.prepared_weights(async_wgrad=async_wgrad) if scope else contextlib.nullcontext()):
+                outs = fwd()
+                if base is None:
+                    base = [_rand(o.shape, 99 + i) for i, o in enumerate(outs)]
+                # premasked: the gradient reaching the layer already carries its ReLU's mask (what its consumer would have applied)
+                gs = [g * (o.detach().cpu() > 0) for g, o in zip(base, outs)] if premasked else base
+                (sum((o * g.cuda()).sum() for o, g in zip(outs, gs))).backward()
+            torch.cuda.synchronize()
+            log = list(ops.PROFILE.conv_log)
+        finally:
+            ops.PROFILE.disable()
+            ops.PROFILE.conv_log.clear()
+    assert Counter(log) == Counter(expect), f"conv_log {log}, expected {expect}"
+    ours = [o.detach().cpu().double() for o in outs]
+    leaves = [t.detach().cpu().double().requires_grad_(t.requires_grad) for t in inputs + params]
+    r = ref(ours, *leaves)
+    sum((o * g.double()).sum() for o, g in zip(r, gs)).backward()
+
+    def close(a, b, rel, what):
+        err, top = float((a.detach().cpu().double() - b.detach()).abs().max()), float(b.detach().abs().max())
+        assert err <= rel * top + 1e-6, f"{what}: {err:.3e} of max {top:.3e}"
+    for i, (a, b) in enumerate(zip(ours, r)):
+        close(a, b, tol, f"output {i}")
+    for i, (t, t64) in enumerate(zip(inputs + params, leaves)):
+        if t.requires_grad:
+            assert t.grad is not None, f"no gradient for leaf {i}"
+            close(t.grad, t64.grad, tol if i < len(inputs) else wtol, f"gradient of leaf {i}")
+
+
+@pytest.mark.parametrize("name", DISPATCH_CASES)
+def test_conv_dispatch_path(lib, monkeypatch, name):
+    expect, setup, opts = _cases(lib)[name]
+    _run_dispatch_case(expect, setup, monkeypatch, **opts)
+
+
+def test_conv_dispatch_cases_cover_every_priced_direction(lib):
+    cases = _cases(lib)
+    assert sorted(cases) == sorted(DISPATCH_CASES)
+    assert {d for expect, _, _ in cases.values() for _, d in expect} == ROOFLINE_DIRECTIONS
