@@ -17,6 +17,7 @@
 //                              NCHW(3) -> NHWC(4, zero padded) repack the first convolution consumes.
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstdlib>
 
 #include "hifihr_internal.h"
@@ -720,14 +721,6 @@ __global__ __launch_bounds__(256) void image_to_nhwc4_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-static int pick_tile(long M, int OC, bool generic) {
-  // 0: 128x128, 1: 128x64, 2: 64x64.  Measured on MI355X at B = 32 (tools/time_conv.py, round 1): the 64x64 tile wins
-  // on every ResNet-18 layer (7 resident workgroups per CU hide the per-chunk barrier), except the 4-channel stem.
-  if (const char* e = getenv("HIFIHR_CONV_TILE")) return atoi(e);     // tuning/diagnostic override
-  (void)M; (void)OC;
-  return generic ? 1 : 2;
-}
-
 template <int BM, int BN>
 static void launch_igemm_tile(const ConvGeom& g, long Mmax, int classes, bool generic, int bk, const float* src, const float* wgt,
                               const float* bias, float* dst, float* stats, hipStream_t st) {
@@ -743,17 +736,6 @@ static void launch_igemm_tile(const ConvGeom& g, long Mmax, int classes, bool ge
 
 // ---- balanced schedule (one gather class, source channels % 32 == 0) ----
 constexpr int kSkMinChunks = 16;         // K chunks per tile below which splitting is not worth a workspace round trip
-
-static int device_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
 
 // variant of the persistent kernel: tile, K-chunk depth and the number of workgroups that are resident per CU
 struct SkVariant {
@@ -803,11 +785,10 @@ static SkPlan sk_plan(const ConvGeom& g) {
   return p;
 }
 
-size_t conv_sk_workspace_bytes(const ConvGeom& g) {
-  const SkPlan p = sk_plan(g);
-  if (!p.use) return 0;
-  return (size_t)((p.tiles * sizeof(unsigned) + 255) / 256 * 256) + (size_t)p.tiles * p.v.bm * p.v.bn * sizeof(float);
+static size_t sk_bytes(const SkPlan& p) {
+  return p.use ? (size_t)((p.tiles * sizeof(unsigned) + 255) / 256 * 256) + (size_t)p.tiles * p.v.bm * p.v.bn * sizeof(float) : 0;
 }
+size_t conv_sk_workspace_bytes(const ConvGeom& g) { return sk_bytes(sk_plan(g)); }
 
 template <int BM, int BN, int BK>
 static void launch_sk(const SkPlan& p, const ConvGeom& g, const float* src, const float* wgt, float* dst, float* stats, void* sk_ws,
@@ -858,7 +839,7 @@ __global__ __launch_bounds__(256) void conv3x3_oc4_kernel(const float* __restric
   const float* wq = wl + q * QS;
   // workgroup = 16 x 16 output pixels (the rows above / below are re-read from L1, not from L2: one contiguous run of pixels per workgroup
   // made every vertical tap an L2 read, 0.76 ms); wave w, team t = (lane >> 2): pixels (x0 + t, y0 + 4 w + u), u = 0 .. 3
-  const int tx = W + 15 >> 4, ty = H + 15 >> 4;
+  const int tx = (W + 15) >> 4, ty = (H + 15) >> 4;
   const long tiles = (long)N * ty * tx;
   const int t = (threadIdx.x & 63) >> 2, wv_ = threadIdx.x >> 6;
   for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -1058,81 +1039,109 @@ __global__ __launch_bounds__(256) void slab_sum_acc_kernel(const float* __restri
   }
 }
 
-static bool conv_wgrad_is_gemm(const ConvGeom& g) {
-  // a 64 x 256 filter is only four 64x64 tiles: 128 row slabs of it (71 us at 32 x 56 x 56) lose to conv_wgrad_kernel's atomics (55 us)
-  return conv_is_gemm(g) && (long)g.OC * g.IC >= 32768 && bgemm_tn_supported(g.OC, g.IC, (int)((long)g.N * g.OH * g.OW));
+// Which kernel a forward / backward-data convolution runs on: decided here and nowhere else (launch_conv_igemm and conv_describe read it).
+// Precedence: the four-output-channel kernels; 1x1 / stride 1 as a GEMM (csrc/gemm.hip, the plan carries that product's NtPlan); the halo
+// kernel; the row-share GEMM with the patch gather in its loader waves (strided forward); the stem kernel; conv_igemm_kernel on the balanced
+// schedule (needs ws_bytes of workspace); conv_igemm_kernel on a tile grid.  The halo, gather and stem kernels and the ragged GEMM read a
+// zero page that cannot be allocated on first use inside a stream capture (zero_page = false): the next candidate takes the launch.
+enum class ConvKernel { tiled, sk, oc4_tile, oc4, gemm, halo, rows, stem };
+static const char* const kConvKernelName[] = {"conv_igemm_kernel", "conv_igemm_kernel", "conv3x3_oc4_tile_kernel", "conv3x3_oc4_kernel", "" /* the NtPlan's */,
+                                              "conv_halo_kernel", "bgemm_nt_rows_kernel<2>", "conv_stem_kernel"};      // as rocprof names them
+struct ConvPlan {
+  hipError_t err;          // not hipSuccess: the launch answers it
+  ConvKernel kernel;
+  NtPlan nt;               // gemm
+  SkPlan sk;               // sk
+  int tile, bk, classes;   // tiled: 0: 128x128, 1: 128x64, 2: 64x64; K-chunk depth; parity classes of a strided backward-data
+  bool generic;            // tiled: the gather that takes any channel count
+  long Mmax;               // tiled: rows of the largest class
+};
+static ConvPlan plan_conv(const ConvGeom& g, const float* bias, const float* stats, size_t ws_bytes, bool zero_page) {
+  ConvPlan p{};
+  p.err = hipErrorInvalidValue;
+  if ((stats != nullptr && g.dgrad) || g.IC % 4 != 0) return p;   // stats: all zero on entry (self-cleaning, see bn.hip)
+  // the fast gather uses 32-bit element offsets (scaled by 4 in the address) and a 63-bit tap mask
+  if ((long)g.N * g.IH * g.IW * g.IC >= (1L << 30) || (long)g.OC * g.R * g.S * g.IC >= (1L << 30)) return p;
+  const bool res = g.residual != nullptr || g.src2 != nullptr;   // (only conv_igemm_kernel adds a residual / runs a second convolution's tap: the specialised kernels are skipped)
+  if (g.src2 != nullptr && (!g.dgrad || g.stride < 2 || g.wgt2 == nullptr || g.batch > 1 || g.IC % 16 != 0 || g.R * g.S > 62)) return p;
+  if (res && !g.dgrad) return p;
+  p.err = hipSuccess;
+  static const int oc4_tiled = [] { const char* e = getenv("HIFIHR_OC4_TILE"); return e ? atoi(e) : 1; }();
+  if (!res && conv_oc4_supported(g, bias, stats)) { p.kernel = (g.IC == 64 && oc4_tiled) ? ConvKernel::oc4_tile : ConvKernel::oc4; return p; }
+  // (the GEMM kernels have no activation epilogue: a fused ReLU keeps the implicit-GEMM kernel; the statistics of a batch-norm consumer
+  // come out of the row-share kernel's epilogue)
+  if (!res && conv_is_gemm(g) && bias == nullptr && !g.relu && (stats == nullptr || bgemm_nt_stats_supported(g.OC))) {
+    // 1x1 / stride 1: y[M][OC] = x[M][IC] . w[OC][IC]^T, and backward-data the same product on (dy, w^T)
+    p.nt = plan_nt((int)((long)g.N * g.OH * g.OW), 0, g.OC, g.IC, 1, stats != nullptr);
+    if (zero_page || p.nt.kernel != NtKernel::rows_ragged) { p.kernel = ConvKernel::gemm; return p; }
+  }
+  if (!res && zero_page && conv_halo_supported(g, bias)) { p.kernel = ConvKernel::halo; return p; }
+  if (zero_page && conv_rows_supported(g, bias) && (stats == nullptr || bgemm_nt_stats_supported(g.OC))) { p.kernel = ConvKernel::rows; return p; }
+  if (zero_page && conv_stem_supported(g, bias)) { p.kernel = ConvKernel::stem; return p; }
+  p.generic = (g.IC % 16) != 0 || g.R * g.S > 62;   // (62 tap bits + the row bit + the "no tap" bit of the gather's mask)
+  p.bk = (g.IC % 32 == 0) ? 32 : 16;
+  if (const char* e = getenv("HIFIHR_CONV_BK")) p.bk = (atoi(e) == 32 && g.IC % 32 == 0) ? 32 : 16;   // tuning override
+  p.classes = g.dgrad ? g.stride * g.stride : 1;
+  // strided dgrad needs source channels % 16 == 0
+  if ((p.generic && g.dgrad && g.stride != 1) || (g.batch > 1 && (p.classes != 1 || bias != nullptr || stats != nullptr))) { p.err = hipErrorInvalidValue; return p; }
+  const int st_ = g.dgrad ? g.stride : 1;
+  p.Mmax = (long)g.N * ((g.OH + st_ - 1) / st_) * ((g.OW + st_ - 1) / st_);
+  // Measured on MI355X at B = 32 (tools/time_conv.py, round 1): the 64x64 tile wins on every ResNet-18 layer (7 resident workgroups per CU
+  // hide the per-chunk barrier), except the 4-channel stem.  HIFIHR_CONV_TILE: tuning / diagnostic override
+  p.tile = p.generic ? 1 : 2;
+  if (const char* e = getenv("HIFIHR_CONV_TILE")) p.tile = atoi(e);
+  if (ws_bytes > 0 && p.tile == 2 && p.bk == 32 && bias == nullptr && g.src2 == nullptr) {
+    p.sk = sk_plan(g);
+    if (p.sk.use && ws_bytes >= sk_bytes(p.sk)) p.kernel = ConvKernel::sk;
+  }
+  return p;
 }
-static size_t conv_wgrad_gemm_bytes(const ConvGeom& g) {
-  return (size_t)bgemm_tn_parts(g.OC, g.IC, (int)((long)g.N * g.OH * g.OW), 1) * g.OC * g.IC * sizeof(float);
+// the kernel of a forward (g.dgrad = 0) or backward-data (g.dgrad = 1) convolution as rocprof names it, for the launch a caller makes
+// without bias, activation and statistics, with the workspace conv_sk_workspace_bytes asks for and the zero page present
+// (a geometry the launch refuses, p.err, is described by the kernel the plan stopped at: "conv_igemm_kernel" for the argument errors)
+void conv_describe(const ConvGeom& g, char* out, int cap) {
+  const ConvPlan p = plan_conv(g, nullptr, nullptr, conv_sk_workspace_bytes(g), true);
+  if (p.kernel == ConvKernel::gemm) describe_nt(p.nt, out, cap);
+  else snprintf(out, cap, "%s", kConvKernelName[(int)p.kernel]);
 }
 
 hipError_t launch_conv_igemm(const ConvGeom& g, const float* src, const float* wgt, const float* bias, float* dst, float* stats,
                              void* sk_ws, size_t sk_ws_bytes, hipStream_t st) {
-  if (stats != nullptr && g.dgrad) return hipErrorInvalidValue;   // stats: all zero on entry (self-cleaning, see bn.hip)
-  if (g.IC % 4 != 0) return hipErrorInvalidValue;
-  // the fast gather uses 32-bit element offsets (scaled by 4 in the address) and a 63-bit tap mask
-  if ((long)g.N * g.IH * g.IW * g.IC >= (1L << 30) || (long)g.OC * g.R * g.S * g.IC >= (1L << 30)) return hipErrorInvalidValue;
-  const bool res = g.residual != nullptr || g.src2 != nullptr;   // (only conv_igemm_kernel adds a residual / runs a second convolution's tap: the specialised kernels are skipped)
-  if (g.src2 != nullptr && (!g.dgrad || g.stride < 2 || g.wgt2 == nullptr || g.batch > 1 || g.IC % 16 != 0 || g.R * g.S > 62)) return hipErrorInvalidValue;
-  if (res && !g.dgrad) return hipErrorInvalidValue;
-  if (!res && conv_oc4_supported(g, bias, stats)) {
-    const long M = (long)g.N * g.OH * g.OW;
-    long blocks = (long)g.N * ((g.OH + 15) / 16) * ((g.OW + 15) / 16);     // 16 x 16-pixel tiles
-    const long cap = (long)device_cus() * 16;              // grid-stride: the filter goes to LDS once per workgroup
-    if (blocks > cap) blocks = cap;
-    static const int tiled = [] { const char* e = getenv("HIFIHR_OC4_TILE"); return e ? atoi(e) : 1; }();
-    if (g.IC == 64 && tiled) {
-      long tb = (long)g.N * ((g.OH + 7) / 8) * ((g.OW + 15) / 16);             // 16 x 8-pixel tiles, two workgroups per CU
-      if (tb > (long)device_cus() * 2) tb = (long)device_cus() * 2;
-      hipLaunchKernelGGL(conv3x3_oc4_tile_kernel<64>, dim3((unsigned)tb), dim3(256), 0, st, src, wgt, dst, g.N, g.OH, g.OW, g.dgrad ? -1 : 1);
-    } else if (g.IC == 64) hipLaunchKernelGGL(conv3x3_oc4_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, st, src, wgt, dst, g.N, g.OH, g.OW, g.dgrad ? -1 : 1);
-    else hipLaunchKernelGGL(conv3x3_oc4_kernel<32>, dim3((unsigned)blocks), dim3(256), 0, st, src, wgt, dst, g.N, g.OH, g.OW, g.dgrad ? -1 : 1);
-    return hipGetLastError();
-  }
-  // (the GEMM kernels have no activation epilogue: a fused ReLU keeps the implicit-GEMM kernel)
-  if (!res && conv_is_gemm(g) && bias == nullptr && !g.relu && (stats == nullptr || bgemm_nt_stats_supported(g.OC))) {
-    // 1x1 / stride 1: y[M][OC] = x[M][IC] . w[OC][IC]^T, and backward-data the same product on (dy, w^T): the GEMM kernels of
-    // csrc/gemm.hip (bgemm_nt_rows_kernel: N % 128 == 0; the statistics of a batch-norm consumer come out of its epilogue)
-    const long M = (long)g.N * g.OH * g.OW;
-    const hipError_t e = launch_bgemm_nt(src, wgt, dst, (int)M, g.OC, g.IC, 1, nullptr, 0, st, stats);      // (statistics: the row-share kernel's epilogue)
-    // hipErrorNotReady: the ragged form wants the zero page and this is its first use inside a stream capture -- the implicit-GEMM
-    // kernel below takes the launch, as for the halo and stem kernels
-    if (e != hipErrorNotReady) return e;
-  }
-  if (!res && conv_halo_supported(g, bias)) {
-    if (const float* zeros = conv_halo_zero_page(st)) return launch_conv_halo(g, src, wgt, bias, dst, stats, zeros, st);
-  }
-  if (conv_rows_supported(g, bias) && (stats == nullptr || bgemm_nt_stats_supported(g.OC))) {
-    // strided 3x3 / 1x1 forward: the row-share GEMM with the patch gather in its loader waves (csrc/gemm.hip); without the zero page
-    // (first use inside a stream capture) the implicit-GEMM kernel below takes the launch
-    if (const float* zeros = conv_halo_zero_page(st)) return launch_conv_rows(g, src, wgt, dst, stats, zeros, st);
-  }
-  if (conv_stem_supported(g, bias)) {
-    if (const float* zeros = conv_halo_zero_page(st)) return launch_conv_stem(g, src, wgt, dst, stats, zeros, st);
-  }
-  const bool generic = (g.IC % 16) != 0 || g.R * g.S > 62;   // (62 tap bits + the row bit + the "no tap" bit of the gather's mask)
-  if (generic && g.dgrad && g.stride != 1) return hipErrorInvalidValue;   // strided dgrad needs source channels % 16 == 0
-  int bk = (g.IC % 32 == 0) ? 32 : 16;
-  if (const char* e = getenv("HIFIHR_CONV_BK")) bk = (atoi(e) == 32 && g.IC % 32 == 0) ? 32 : 16;   // tuning override
-  const int classes = g.dgrad ? g.stride * g.stride : 1;
-  if (g.batch > 1 && (classes != 1 || bias != nullptr || stats != nullptr)) return hipErrorInvalidValue;
-  const int st_ = g.dgrad ? g.stride : 1;
-  const long Mmax = (long)g.N * ((g.OH + st_ - 1) / st_) * ((g.OW + st_ - 1) / st_);   // rows of the largest class
-  const int tile = pick_tile(Mmax * classes, g.OC, generic);
-  if (sk_ws != nullptr && tile == 2 && bk == 32 && bias == nullptr && g.src2 == nullptr) {
-    const SkPlan p = sk_plan(g);
-    if (p.use && sk_ws_bytes >= conv_sk_workspace_bytes(g)) {
-      if (p.v.bm == 64) launch_sk<64, 64, 32>(p, g, src, wgt, dst, stats, sk_ws, st);
-      else if (p.v.bn == 128) launch_sk<128, 128, 16>(p, g, src, wgt, dst, stats, sk_ws, st);
-      else if (p.v.bk == 16) launch_sk<128, 64, 16>(p, g, src, wgt, dst, stats, sk_ws, st);
-      else launch_sk<128, 64, 32>(p, g, src, wgt, dst, stats, sk_ws, st);
-      return hipGetLastError();
+  const size_t ws_bytes = sk_ws != nullptr ? sk_ws_bytes : 0;
+  ConvPlan p = plan_conv(g, bias, stats, ws_bytes, true);
+  // the zero page is asked for (and allocated on first use) only by a plan that reads it; without it the plan is made again
+  const bool reads_zeros = p.kernel == ConvKernel::halo || p.kernel == ConvKernel::rows || p.kernel == ConvKernel::stem ||
+                           (p.kernel == ConvKernel::gemm && p.nt.kernel == NtKernel::rows_ragged);
+  const float* zeros = (p.err == hipSuccess && reads_zeros) ? conv_halo_zero_page(st) : nullptr;
+  if (reads_zeros && zeros == nullptr) p = plan_conv(g, bias, stats, ws_bytes, false);
+  if (p.err != hipSuccess) return p.err;
+  const int sign = g.dgrad ? -1 : 1;
+  switch (p.kernel) {
+    case ConvKernel::oc4_tile:
+    case ConvKernel::oc4: {
+      // 16 x 8-pixel tiles, two workgroups per CU; 16 x 16-pixel tiles, grid-stride (the filter goes to LDS once per workgroup)
+      const bool t = p.kernel == ConvKernel::oc4_tile;
+      long blocks = (long)g.N * ((g.OH + (t ? 7 : 15)) / (t ? 8 : 16)) * ((g.OW + 15) / 16);
+      if (blocks > (long)device_cus() * (t ? 2 : 16)) blocks = (long)device_cus() * (t ? 2 : 16);
+      if (t) hipLaunchKernelGGL(conv3x3_oc4_tile_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, st, src, wgt, dst, g.N, g.OH, g.OW, sign);
+      else if (g.IC == 64) hipLaunchKernelGGL(conv3x3_oc4_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, st, src, wgt, dst, g.N, g.OH, g.OW, sign);
+      else hipLaunchKernelGGL(conv3x3_oc4_kernel<32>, dim3((unsigned)blocks), dim3(256), 0, st, src, wgt, dst, g.N, g.OH, g.OW, sign);
+      break;
     }
-  }
-  switch (tile) {
-    case 0: launch_igemm_tile<128, 128>(g, Mmax, classes, generic, bk, src, wgt, bias, dst, stats, st); break;
-    case 1: launch_igemm_tile<128, 64>(g, Mmax, classes, generic, bk, src, wgt, bias, dst, stats, st); break;
-    default: launch_igemm_tile<64, 64>(g, Mmax, classes, generic, bk, src, wgt, bias, dst, stats, st);
+    case ConvKernel::gemm: return launch_bgemm_nt_plan(p.nt, src, wgt, dst, nullptr, 0, st, stats);
+    case ConvKernel::halo: return launch_conv_halo(g, src, wgt, bias, dst, stats, zeros, st);
+    case ConvKernel::rows: return launch_conv_rows(g, src, wgt, dst, stats, zeros, st);
+    case ConvKernel::stem: return launch_conv_stem(g, src, wgt, dst, stats, zeros, st);
+    case ConvKernel::sk:
+      if (p.sk.v.bm == 64) launch_sk<64, 64, 32>(p.sk, g, src, wgt, dst, stats, sk_ws, st);
+      else if (p.sk.v.bn == 128) launch_sk<128, 128, 16>(p.sk, g, src, wgt, dst, stats, sk_ws, st);
+      else if (p.sk.v.bk == 16) launch_sk<128, 64, 16>(p.sk, g, src, wgt, dst, stats, sk_ws, st);
+      else launch_sk<128, 64, 32>(p.sk, g, src, wgt, dst, stats, sk_ws, st);
+      break;
+    case ConvKernel::tiled:
+      if (p.tile == 0) launch_igemm_tile<128, 128>(g, p.Mmax, p.classes, p.generic, p.bk, src, wgt, bias, dst, stats, st);
+      else if (p.tile == 1) launch_igemm_tile<128, 64>(g, p.Mmax, p.classes, p.generic, p.bk, src, wgt, bias, dst, stats, st);
+      else launch_igemm_tile<64, 64>(g, p.Mmax, p.classes, p.generic, p.bk, src, wgt, bias, dst, stats, st);
   }
   return hipGetLastError();
 }
@@ -1157,26 +1166,60 @@ static void launch_wgrad_tile(const ConvGeom& g, int Q, long M, int slots, const
                      dw, cps, dy2, dw2, qtiles1);
 }
 
+// Which kernel a weight gradient runs on and the scratch it wants: decided here and nowhere else.  Precedence: 1x1 / stride 1 as the TN
+// product of csrc/gemm.hip over row slabs, summed in slab order (needs the caller's scratch); the halo and stem slab kernels (the caller's
+// scratch when it is large enough, else library-owned scratch: csrc/conv_halo.hip); conv_wgrad_kernel's atomics on a tile grid.
+enum class WgradKernel { tiled, gemm, halo, stem };
+static const char* const kWgradKernelName[] = {"conv_wgrad_kernel", "" /* the TN product's */, "conv_halo_wgrad_kernel", "conv_stem_wgrad_kernel"};
+struct WgradPlan {
+  WgradKernel kernel;
+  size_t ws_bytes;         // scratch the kernel wants (tiled: none)
+  int parts;               // gemm: row slabs
+  int bm, bn, bkw, slots;  // tiled: tile, K-chunk depth, resident workgroups to fill
+};
+static WgradPlan plan_wgrad(const ConvGeom& g, size_t ws_bytes) {
+  WgradPlan p{};
+  // 0: 128x128 (4 resident per CU), 1: 64x128, n >= 2: 64x64 with n workgroups per CU.  Measured at B = 32 (tools/time_wgrad.py):
+  // the atomic epilogue moves (workgroups x tile bytes), so below 512 output channels the 64x64 tile (a quarter of the atomic
+  // volume, 8 per CU) wins by 5-15 %; the 29.6 GFLOP layer-4 shapes keep the 128x128 tile (100 vs 81 TF).
+  // (every plan carries the tile: the slab kernels hand a launch they cannot set up inside a stream capture to the atomics kernel)
+  int tile = (g.OC % 128 == 0 && g.OC >= 512) ? 0 : 8;
+  if (const char* e = getenv("HIFIHR_WGRAD_TILE")) tile = atoi(e);
+  p.bkw = 16;
+  if (const char* e = getenv("HIFIHR_WGRAD_BK")) p.bkw = (atoi(e) == 32 && tile != 1) ? 32 : 16;
+  p.bm = tile == 0 ? 128 : 64; p.bn = (tile == 0 || tile == 1) ? 128 : 64;
+  p.slots = device_cus() * (tile == 0 ? (p.bkw == 32 ? 2 : 4) : (tile == 1 || tile == 2) ? 4 : tile);
+  const int M = (int)((long)g.N * g.OH * g.OW);
+  // a 64 x 256 filter is only four 64x64 tiles: 128 row slabs of it (71 us at 32 x 56 x 56) lose to conv_wgrad_kernel's atomics (55 us)
+  if (conv_is_gemm(g) && (long)g.OC * g.IC >= 32768 && bgemm_tn_supported(g.OC, g.IC, M)) {
+    p.parts = bgemm_tn_parts(g.OC, g.IC, M, 1);
+    p.ws_bytes = (size_t)p.parts * g.OC * g.IC * sizeof(float);
+    if (ws_bytes >= p.ws_bytes) { p.kernel = WgradKernel::gemm; return p; }
+  }
+  p.ws_bytes = 0;
+  if (conv_halo_wgrad_supported(g)) { p.kernel = WgradKernel::halo; p.ws_bytes = conv_halo_wgrad_slab_bytes(); }
+  else if (conv_stem_wgrad_supported(g)) { p.kernel = WgradKernel::stem; p.ws_bytes = conv_stem_wgrad_slab_bytes(); }
+  return p;
+}
+size_t conv_wgrad_workspace_bytes(const ConvGeom& g) { return plan_wgrad(g, SIZE_MAX).ws_bytes; }
+void conv_wgrad_describe(const ConvGeom& g, char* out, int cap) {      // with the scratch conv_wgrad_workspace_bytes asks for
+  const WgradKernel k = plan_wgrad(g, SIZE_MAX).kernel;
+  if (k == WgradKernel::gemm) bgemm_describe_batch(1, g.OC, g.IC, (int)((long)g.N * g.OH * g.OW), 1, out, cap);
+  else snprintf(out, cap, "%s", kWgradKernelName[(int)k]);
+}
+
 // dw += the weight gradient of the strided convolution g, dw2 += the weight gradient of the 1x1 / same stride / pad 0 convolution of the same
 // input with the same output channels, in ONE launch of conv_wgrad_kernel (see its header)
 bool conv_wgrad_plus1x1_supported(const ConvGeom& g) {
   static const int on = [] { const char* e = getenv("HIFIHR_WGRAD_PLUS1X1"); return e ? atoi(e) : 1; }();
   return on && !g.dgrad && g.stride >= 2 && g.pad < g.R && g.pad < g.S && g.batch <= 1 && g.IC % 4 == 0 && g.OC % 4 == 0 &&
-         g.OH == (g.IH - 1) / g.stride + 1 && g.OW == (g.IW - 1) / g.stride + 1 && !conv_halo_wgrad_supported(g) && !conv_stem_wgrad_supported(g) &&
-         !conv_wgrad_is_gemm(g);
+         g.OH == (g.IH - 1) / g.stride + 1 && g.OW == (g.IW - 1) / g.stride + 1 && plan_wgrad(g, SIZE_MAX).kernel == WgradKernel::tiled;
 }
 hipError_t launch_conv_wgrad_plus1x1(const ConvGeom& g, const float* x, const float* dy, float* dw, const float* dy2, float* dw2, hipStream_t st) {
   if (!conv_wgrad_plus1x1_supported(g) || dy2 == nullptr || dw2 == nullptr) return hipErrorInvalidValue;
   const long M = (long)g.N * g.OH * g.OW;
   launch_wgrad_tile<64, 64, 16>(g, g.R * g.S * g.IC, M, device_cus() * 8, x, dy, dw, st, dy2, dw2);
   return hipGetLastError();
-}
-
-size_t conv_wgrad_workspace_bytes(const ConvGeom& g) {
-  if (conv_wgrad_is_gemm(g)) return conv_wgrad_gemm_bytes(g);
-  if (conv_halo_wgrad_supported(g)) return conv_halo_wgrad_slab_bytes();
-  if (conv_stem_wgrad_supported(g)) return conv_stem_wgrad_slab_bytes();
-  return 0;
 }
 
 // The stem with a 3-channel parameter (reference conv1 = nn.Conv2d(3, 64, 7, 2, 3)): x is NHWC4 with a zero fourth plane, dw3 is
@@ -1191,41 +1234,26 @@ hipError_t launch_conv_wgrad(const ConvGeom& g, const float* x, const float* dy,
   const long M = (long)g.N * g.OH * g.OW;
   const int Q = g.R * g.S * g.IC;
   if (g.IC % 4 != 0 || g.OC % 4 != 0) return hipErrorInvalidValue;
-  if (conv_wgrad_is_gemm(g) && ws != nullptr && ws_bytes >= conv_wgrad_gemm_bytes(g)) {
-    // 1x1 / stride 1: dw[OC][IC] += dy[M][OC]^T . x[M][IC] -- the TN product of csrc/gemm.hip over row slabs, summed in slab order
-    const int parts = bgemm_tn_parts(g.OC, g.IC, (int)M, 1);
-    const hipError_t e = launch_bgemm_tn(dy, x, static_cast<float*>(ws), g.OC, g.IC, (int)M, 1, parts, st);
+  const WgradPlan p = plan_wgrad(g, ws != nullptr ? ws_bytes : 0);
+  float* slabs = ws_bytes >= p.ws_bytes ? static_cast<float*>(ws) : nullptr;
+  hipError_t e = hipErrorNotReady;
+  if (p.kernel == WgradKernel::gemm) {
+    // dw[OC][IC] += dy[M][OC]^T . x[M][IC]
+    e = launch_bgemm_tn(dy, x, slabs, g.OC, g.IC, (int)M, 1, p.parts, st);
     if (e != hipSuccess) return e;
     const long n4 = (long)g.OC * g.IC / 4;
-    hipLaunchKernelGGL(slab_sum_acc_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, static_cast<const float*>(ws), parts, n4, dw);
+    hipLaunchKernelGGL(slab_sum_acc_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, slabs, p.parts, n4, dw);
     return hipGetLastError();
   }
-  // slab kernels: the caller's scratch (any contents) when it is large enough, else library-owned scratch (csrc/conv_halo.hip)
-  if (conv_halo_wgrad_supported(g)) {
-    const hipError_t e = launch_conv_halo_wgrad(g, x, dy, dw, ws_bytes >= conv_halo_wgrad_slab_bytes() ? static_cast<float*>(ws) : nullptr, st);
-    if (e != hipErrorNotReady) return e;
-  }
-  if (conv_stem_wgrad_supported(g)) {
-    const hipError_t e = launch_conv_stem_wgrad(g, x, dy, dw, ws_bytes >= conv_stem_wgrad_slab_bytes() ? static_cast<float*>(ws) : nullptr, st);
-    if (e != hipErrorNotReady) return e;
-  }
-  // 0: 128x128 (4 resident per CU), 1: 64x128, n >= 2: 64x64 with n workgroups per CU.  Measured at B = 32 (tools/time_wgrad.py):
-  // the atomic epilogue moves (workgroups x tile bytes), so below 512 output channels the 64x64 tile (a quarter of the atomic
-  // volume, 8 per CU) wins by 5-15 %; the 29.6 GFLOP layer-4 shapes keep the 128x128 tile (100 vs 81 TF).
-  int tile = (g.OC % 128 == 0 && g.OC >= 512) ? 0 : 8;
-  if (const char* e = getenv("HIFIHR_WGRAD_TILE")) tile = atoi(e);
-  const int cus = device_cus();
-  int bkw = 16;
-  if (const char* e = getenv("HIFIHR_WGRAD_BK")) bkw = atoi(e);
-  if (tile == 0) {
-    if (bkw == 32) launch_wgrad_tile<128, 128, 32>(g, Q, M, cus * 2, x, dy, dw, st);
-    else launch_wgrad_tile<128, 128, 16>(g, Q, M, cus * 4, x, dy, dw, st);
-  } else if (tile == 1) {
-    launch_wgrad_tile<64, 128, 16>(g, Q, M, cus * 4, x, dy, dw, st);
-  } else {
-    if (bkw == 32) launch_wgrad_tile<64, 64, 32>(g, Q, M, cus * (tile == 2 ? 4 : tile), x, dy, dw, st);
-    else launch_wgrad_tile<64, 64, 16>(g, Q, M, cus * (tile == 2 ? 4 : tile), x, dy, dw, st);
-  }
+  // hipErrorNotReady (first use of the library's scratch or of the zero page inside a stream capture): the atomics kernel takes the launch
+  if (p.kernel == WgradKernel::halo) e = launch_conv_halo_wgrad(g, x, dy, dw, slabs, st);
+  if (p.kernel == WgradKernel::stem) e = launch_conv_stem_wgrad(g, x, dy, dw, slabs, st);
+  if (e != hipErrorNotReady) return e;
+  if (p.bm == 128 && p.bkw == 32) launch_wgrad_tile<128, 128, 32>(g, Q, M, p.slots, x, dy, dw, st);
+  else if (p.bm == 128) launch_wgrad_tile<128, 128, 16>(g, Q, M, p.slots, x, dy, dw, st);
+  else if (p.bn == 128) launch_wgrad_tile<64, 128, 16>(g, Q, M, p.slots, x, dy, dw, st);
+  else if (p.bkw == 32) launch_wgrad_tile<64, 64, 32>(g, Q, M, p.slots, x, dy, dw, st);
+  else launch_wgrad_tile<64, 64, 16>(g, Q, M, p.slots, x, dy, dw, st);
   return hipGetLastError();
 }
 

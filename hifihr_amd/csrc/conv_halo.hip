@@ -1371,17 +1371,6 @@ extern "C" int hifihr_halo_stamp_read(unsigned long long* out8, int reset) {
 namespace hifihr {
 #endif
 
-static int halo_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
-            ? p.multiProcessorCount : 256;
-  }
-  return n;
-}
-
 // 256 zero bytes the halo's out-of-image pixels are read from.  Allocated on first use (never inside a stream capture: the caller
 // then falls back to conv_igemm_kernel for that launch).
 const float* conv_halo_zero_page(hipStream_t st) {
@@ -1439,7 +1428,7 @@ bool conv_stem_wgrad_supported(const ConvGeom& g) {
   return on && conv_stem_supported(g, nullptr);
 }
 
-size_t conv_stem_wgrad_slab_bytes() { return (size_t)halo_cus() * 64 * 196 * sizeof(float); }
+size_t conv_stem_wgrad_slab_bytes() { return (size_t)device_cus() * 64 * 196 * sizeof(float); }
 
 hipError_t launch_conv_stem_wgrad(const ConvGeom& g, const float* x, const float* dy, float* dw, float* slabs, hipStream_t st, int dw_channels) {
   if (!conv_stem_wgrad_supported(g) || (dw_channels != 3 && dw_channels != 4)) return hipErrorInvalidValue;
@@ -1449,11 +1438,11 @@ hipError_t launch_conv_stem_wgrad(const ConvGeom& g, const float* x, const float
   a.x = x; a.dy = dy; a.zeros = zeros; a.N = g.N; a.IH = g.IH; a.IW = g.IW; a.OH = g.OH; a.OW = g.OW;
   a.ctiles = g.OW / kTW;
   a.total = g.N * a.ctiles * g.OH;
-  int G = halo_cus();
+  int G = device_cus();
   a.per = (a.total + G - 1) / G;
   if (a.per < 4) a.per = 4;
   G = (a.total + a.per - 1) / a.per;
-  a.slabs = slabs != nullptr ? slabs : halo_wgrad_scratch(st, (size_t)halo_cus() * kTaps * 64 * 64 * sizeof(float));      // (the pool's buffers: 9 x 64 x 64 >= 64 x 196 floats each)
+  a.slabs = slabs != nullptr ? slabs : halo_wgrad_scratch(st, (size_t)device_cus() * kTaps * 64 * 64 * sizeof(float));      // (the pool's buffers: 9 x 64 x 64 >= 64 x 196 floats each)
   if (a.slabs == nullptr) return hipErrorNotReady;
   hipLaunchKernelGGL(conv_stem_wgrad_kernel, dim3(G), dim3(512), 0, st, a);
   hipLaunchKernelGGL(conv_stem_wgrad_reduce_kernel, dim3(64 * 196 / 64), dim3(256), 0, st, a.slabs, G, dw, dw_channels);
@@ -1465,7 +1454,7 @@ bool conv_halo_wgrad_supported(const ConvGeom& g) {
   return on && conv_halo_supported(g, nullptr) && !g.dgrad && g.OW % kTW == 0;      // (the dy tiles of the weight gradient are not masked)
 }
 
-size_t conv_halo_wgrad_slab_bytes() { return (size_t)halo_cus() * kTaps * 64 * 64 * sizeof(float); }
+size_t conv_halo_wgrad_slab_bytes() { return (size_t)device_cus() * kTaps * 64 * 64 * sizeof(float); }
 
 hipError_t launch_conv_halo_wgrad(const ConvGeom& g, const float* x, const float* dy, float* dw, float* slabs, hipStream_t st) {
   if (!conv_halo_wgrad_supported(g)) return hipErrorInvalidValue;
@@ -1475,11 +1464,11 @@ hipError_t launch_conv_halo_wgrad(const ConvGeom& g, const float* x, const float
   a.x = x; a.dy = dy; a.zeros = zeros; a.N = g.N; a.H = g.OH; a.W = g.OW;
   a.ctiles = g.OW / kTW;
   a.total = g.N * a.ctiles * g.OH;
-  int G = halo_cus();
+  int G = device_cus();
   a.per = (a.total + G - 1) / G;
   if (a.per < 4) a.per = 4;
   G = (a.total + a.per - 1) / a.per;
-  a.slabs = slabs != nullptr ? slabs : halo_wgrad_scratch(st, (size_t)halo_cus() * kTaps * 64 * 64 * sizeof(float));
+  a.slabs = slabs != nullptr ? slabs : halo_wgrad_scratch(st, (size_t)device_cus() * kTaps * 64 * 64 * sizeof(float));
   if (a.slabs == nullptr) return hipErrorNotReady;
   hipLaunchKernelGGL(conv_halo_wgrad_kernel, dim3(G), dim3(256 + 64 * kNL), 0, st, a);
   hipLaunchKernelGGL(conv_halo_wgrad_reduce_kernel, dim3(kTaps * 64 * 64 / 64), dim3(256), 0, st, a.slabs, G, dw);
@@ -1499,7 +1488,7 @@ hipError_t launch_conv_stem(const ConvGeom& g, const float* src, const float* wg
   a.N = g.N; a.IH = g.IH; a.IW = g.IW; a.OH = g.OH; a.OW = g.OW;
   a.ctiles = g.OW / kTW;
   a.total = g.N * a.ctiles * g.OH;
-  int G = halo_cus();
+  int G = device_cus();
   a.per = (a.total + G - 1) / G;
   if (a.per < 4) a.per = 4;
   G = (a.total + a.per - 1) / a.per;
@@ -1515,7 +1504,7 @@ hipError_t launch_conv_halo(const ConvGeom& g, const float* src, const float* wg
   a.N = g.N; a.H = g.OH; a.W = g.OW; a.sign = g.dgrad ? -1 : 1;
   a.ctiles = (g.OW + kTW - 1) / kTW;                         // the last column tile may be ragged (512 = 36 x 14 + 8)
   a.total = g.N * a.ctiles * g.OH;
-  int G = halo_cus();
+  int G = device_cus();
   a.per = (a.total + G - 1) / G;
   if (a.per < 4) a.per = 4;                                  // tiny problems: fewer workgroups, tiles of >= 4 rows
   G = (a.total + a.per - 1) / a.per;
@@ -1541,7 +1530,7 @@ hipError_t launch_conv_wino2(const float* src, const float* U, const float* bias
   a.N = N; a.H = H; a.W = W;
   a.ctiles = (W + kTW - 1) / kTW;                           // the last column tile may be ragged (W even: whole 2 x 2 tiles)
   a.total = N * a.ctiles * H;
-  int G = halo_cus();
+  int G = device_cus();
   a.per = (a.total + G - 1) / G;
   if (a.per < 4) a.per = 4;
   a.per = (a.per + 1) & ~1;                                  // even shares: every tile is whole 2 x 2 Winograd tiles
@@ -1564,7 +1553,7 @@ bool conv_c64_bwd_pair_supported(int N, int H, int W) {
   static const int on = [] { const char* e = getenv("HIFIHR_C64_PAIR"); return e ? atoi(e) : 1; }();
   ConvGeom g{};
   g.N = N; g.IH = H; g.IW = W; g.IC = 64; g.OC = 64; g.R = 3; g.S = 3; g.stride = 1; g.pad = 1; g.OH = H; g.OW = W; g.dgrad = 0; g.batch = 1;
-  return on && conv_wino2_supported(N, H, W, 64, 64) && conv_halo_wgrad_supported(g) && halo_cus() >= 2;
+  return on && conv_wino2_supported(N, H, W, 64, 64) && conv_halo_wgrad_supported(g) && device_cus() >= 2;
 }
 
 hipError_t launch_conv_halo_wgrad_reduce_multi(const HaloReduceJob* jobs, int njobs, hipStream_t st) {
@@ -1587,7 +1576,7 @@ hipError_t launch_conv_c64_bwd_pair(const float* dy, const float* U_bwd, const f
   const float* zeros = conv_halo_zero_page(st);
   if (zeros == nullptr) return hipErrorNotReady;
   static const int pct = [] { const char* e = getenv("HIFIHR_C64_PAIR_DGRAD_PCT"); int v = e ? atoi(e) : 44; return v < 5 ? 5 : (v > 95 ? 95 : v); }();
-  const int cus = halo_cus();
+  const int cus = device_cus();
   int ga = (cus * pct + 50) / 100;
   if (ga < 1) ga = 1;
   if (ga > cus - 1) ga = cus - 1;
@@ -1608,7 +1597,7 @@ hipError_t launch_conv_c64_bwd_pair(const float* dy, const float* U_bwd, const f
   w.per = (w.total + gb - 1) / gb;
   if (w.per < 4) w.per = 4;
   gb = (w.total + w.per - 1) / w.per;
-  w.slabs = slabs != nullptr ? slabs : halo_wgrad_scratch(st, (size_t)halo_cus() * kTaps * 64 * 64 * sizeof(float));
+  w.slabs = slabs != nullptr ? slabs : halo_wgrad_scratch(st, (size_t)device_cus() * kTaps * 64 * 64 * sizeof(float));
   if (w.slabs == nullptr) return hipErrorNotReady;
   if (res != nullptr) hipLaunchKernelGGL((conv_c64_bwd_pair_kernel<true>), dim3(ga + gb), dim3(256 + 64 * kNL), 0, st, d, ga, w);
   else hipLaunchKernelGGL((conv_c64_bwd_pair_kernel<false>), dim3(ga + gb), dim3(256 + 64 * kNL), 0, st, d, ga, w);

@@ -734,7 +734,6 @@ __global__ __launch_bounds__(256 + 64 * NLOAD) void bgemm_nt_sk_kernel(BgemmArgs
 // split the COLUMNS of a tile, 32 each, and take all of its 16-row blocks, so a short tile simply has fewer blocks); whole tiles
 // only: nothing is exchanged between workgroups and nothing needs a workspace.  LDS: 4 stages x (A 128x32 + B 128x32) = 128 KB.
 // ------------------------------------------------------------------------------------------------
-static int gemm_cus();
 struct RowsTile { int p, nt, m0, rows; };
 // q = n / d, r = n - q d for 0 <= n, 0 < d < 2^31: one 32-bit unsigned division when n fits (every shape of the step does; ~30 instructions),
 // the 64-bit sequence (several hundred cycles of dependent VALU work) otherwise
@@ -1536,65 +1535,83 @@ __global__ __launch_bounds__(512) void bgemm_nt_tn_pair_kernel(BgemmArgs a, long
   else tn_rows_body(b, per_b, lds, (int)blockIdx.x - ga, (int)gridDim.x - ga);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Host side.  Every switch of this file is read in gemm_env() (the compute-unit count in gemm_cus()); which kernel a product runs on, on
+// what grid and with how much workspace is decided in plan_nt() / plan_tn() and nowhere else: the launchers, bgemm_describe, the
+// workspace and slab-count queries and the pair launch all read the plan.
+// ------------------------------------------------------------------------------------------------
+constexpr int kUnset = -(1 << 30);
+static int env_int(const char* name, int unset) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : unset;
+}
+// HIFIHR_GEMM_CUS (tests: the emulator reports 4 compute units, and the XCD-coherent TN schedule needs a multiple of 8 workgroups)
 static int gemm_cus() {
-  // HIFIHR_GEMM_CUS (tests: the emulator reports 4 compute units, and the XCD-coherent TN schedule needs a multiple of 8 workgroups)
-  if (const char* e = getenv("HIFIHR_GEMM_CUS")) { const int v = atoi(e); if (v > 0) return v; }
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
+  const int v = env_int("HIFIHR_GEMM_CUS", 0);
+  return v > 0 ? v : device_cus();
 }
-
-// loader waves of the wave-specialised kernels (0: the 4-wave kernels); HIFIHR_GEMM_WS overrides (tuning)
-static int gemm_ws_loaders() {
-  if (const char* e = getenv("HIFIHR_GEMM_WS")) return atoi(e);
-  return 4;
+struct GemmEnv {
+  // read once per process, all of them at the first call of gemm_env() (a switch set after a process's first GEMM is not seen, even where
+  // the feature it governs has not run yet): HIFIHR_GEMM_ROWS=0 (NT products on the older kernels), _RAGGED (0: no ragged N / K on the row-share kernel, 2: every
+  // shape it can take), _TN_ROWS=0 (the per-tile TN kernels), _TN_SPLIT=0 (no T-split), _TN_COHERENT=0 (contiguous shares), _TN_SKIP=0 (walk
+  // the zero rows behind a tile mosaic), _PAIR=0 (two launches), _PAIR_NT_WEIGHT (percent), _PAIR_MAX_GFLOP, HIFIHR_CONV_ROWS (2: every
+  // shape), HIFIHR_CONV_ROWS_PAIR=0 (two launches)
+  int rows, ragged, tn_rows, tn_split, tn_coherent, tn_skip, pair, pair_nt_weight, conv_rows, conv_rows_pair;
+  double pair_max_gflop;
+  // re-read on every call (the tuning scripts and the tests change them inside one process): HIFIHR_GEMM_CUS, _WS (loader waves of the
+  // wave-specialised kernels, 0: the 4-wave kernels), _SK=0 (never the persistent stream-K kernel), _NT_TILE / _TN_TILE (1000 bm + bn)
+  // and _TN_PARTS (slabs of the per-tile TN kernels), whose presence alone switches the row-share kernels off (kUnset: not there)
+  int cus, loaders, sk, nt_tile, tn_tile, tn_parts;
+  bool rows_on() const { return rows && nt_tile == kUnset; }
+  bool tn_rows_on() const { return tn_rows && tn_tile == kUnset && tn_parts == kUnset; }
+};
+static GemmEnv gemm_env() {
+  static const GemmEnv once = [] {
+    GemmEnv e{};
+    e.rows = env_int("HIFIHR_GEMM_ROWS", 1); e.ragged = env_int("HIFIHR_GEMM_RAGGED", 1);
+    e.tn_rows = env_int("HIFIHR_GEMM_TN_ROWS", 1); e.tn_split = env_int("HIFIHR_GEMM_TN_SPLIT", 1);
+    e.tn_coherent = env_int("HIFIHR_GEMM_TN_COHERENT", 1); e.tn_skip = env_int("HIFIHR_GEMM_TN_SKIP", 1);
+    e.pair = env_int("HIFIHR_GEMM_PAIR", 1); e.pair_nt_weight = env_int("HIFIHR_GEMM_PAIR_NT_WEIGHT", 100);
+    if (e.pair_nt_weight <= 0) e.pair_nt_weight = 100;
+    const char* g = getenv("HIFIHR_GEMM_PAIR_MAX_GFLOP");
+    e.pair_max_gflop = (g && atof(g) > 0) ? atof(g) : 12.0;
+    e.conv_rows = env_int("HIFIHR_CONV_ROWS", 1); e.conv_rows_pair = env_int("HIFIHR_CONV_ROWS_PAIR", 1);
+    return e;
+  }();
+  GemmEnv e = once;
+  e.cus = gemm_cus(); e.loaders = env_int("HIFIHR_GEMM_WS", 4); e.sk = env_int("HIFIHR_GEMM_SK", 1);
+  e.nt_tile = env_int("HIFIHR_GEMM_NT_TILE", kUnset); e.tn_tile = env_int("HIFIHR_GEMM_TN_TILE", kUnset); e.tn_parts = env_int("HIFIHR_GEMM_TN_PARTS", kUnset);
+  return e;
 }
-
 // Tile choice, measured on MI355X at B = 32 (tools/time_gemm.py, profiles/r02_time_gemm.txt):
 //   NT  reduction length >= 512: 128x128 wave-specialised (4 loader waves); shorter reductions (4-8 chunks per tile): the 4-wave
 //       64x64 kernel -- a tile's fixed cost (first loads, store tail) then weighs more than the macro-tile's operand reuse, and
 //       four small workgroups per CU overlap it.
 //   TN  >= 512 x 256 outputs: 128x128 wave-specialised, one workgroup per CU (slabs = 256 / tiles); smaller outputs: 64x64 tiles
 //       with the t range split until ~512 workgroups exist.
-static void nt_tile(int M, int N, int K, int* bm, int* bn) {
-  (void)M;
-  if (K >= 512 && N % 128 == 0) { *bm = 128; *bn = 128; }
+static void nt_tile(const GemmEnv& e, int N, int K, int* bm, int* bn) {
+  if (e.nt_tile != kUnset) { *bm = e.nt_tile / 1000; *bn = e.nt_tile % 1000; if (N % *bn) *bn = 64; }
+  else if (K >= 512 && N % 128 == 0) { *bm = 128; *bn = 128; }
   else { *bm = 64; *bn = 64; }
 }
-static int gemm_cus();
-static void tn_tile(int M, int N, int batch, int* bm, int* bn) {
+static void tn_tile(const GemmEnv& e, int M, int N, int batch, int* bm, int* bn) {
   *bm = 64; *bn = 64;
+  if (e.tn_tile != kUnset) { *bm = e.tn_tile / 1000; *bn = e.tn_tile % 1000; if (M % *bm) *bm = 64; if (N % *bn) *bn = 64; return; }
   if ((long)M * N >= 512L * 256 && M % 128 == 0 && N % 128 == 0) {
     // 128x128 tiles run one workgroup per CU: more tiles than CUs only pays when the rounds come out nearly whole.  The 36 problems of a
     // Winograd F(4x4, 3x3) layer give 288 / 576 tiles (1.125 / 2.25 rounds): the 64x64 kernel (several workgroups per CU) is faster there
     // (tools/time_gemm_tn_f4.py: 85 -> 69 us at 256 x 512 channels, 136 -> 131 at 512 x 512)
     const long t128 = (long)(M / 128) * (N / 128) * batch;
-    const int cus = gemm_cus();
-    const long rounds = (t128 + cus - 1) / cus;
-    if (t128 <= cus || (double)rounds * cus <= 1.15 * (double)t128) { *bm = 128; *bn = 128; }
+    const long rounds = (t128 + e.cus - 1) / e.cus;
+    if (t128 <= e.cus || (double)rounds * e.cus <= 1.15 * (double)t128) { *bm = 128; *bn = 128; }
   }
 }
+static bool tile_exists(int bm, int bn) { return (bm == 64 || bm == 128) && (bn == 64 || bn == 128); }
 
-size_t bgemm_nt_workspace_bytes(int M, int N, int K, int batch);
-
-// the persistent row-share kernel serves every NT product whose N is a multiple of 128 (HIFIHR_GEMM_ROWS=0: the older kernels)
-static bool nt_rows(int N) {
-  static const int on = [] { const char* e = getenv("HIFIHR_GEMM_ROWS"); return e ? atoi(e) : 1; }();
-  return on && N % 128 == 0 && getenv("HIFIHR_GEMM_NT_TILE") == nullptr;
-}
-
-// the persistent row-share TN kernel: complete products (one slab) when every CU gets at least eight 16-row blocks (HIFIHR_GEMM_TN_ROWS=0:
-// the per-tile kernels with T-split slabs)
-static bool tn_rows(int M, int N, int T, int batch) {
-  static const int on = [] { const char* e = getenv("HIFIHR_GEMM_TN_ROWS"); return e ? atoi(e) : 1; }();
-  if (!on || N % 128 != 0 || M % 16 != 0 || T % 32 != 0 || T < 64) return false;
-  if (getenv("HIFIHR_GEMM_TN_TILE") != nullptr || getenv("HIFIHR_GEMM_TN_PARTS") != nullptr) return false;
-  return (long)batch * (N / 128) * (M / 16) >= 8L * gemm_cus();      // (256 x 256 channels, 4.5 blocks per CU: 38 us here, 35 on the 64x64 kernel)
+// the persistent row-share TN kernel: complete products (one slab) when every CU gets at least eight 16-row blocks
+static bool tn_rows(const GemmEnv& e, int M, int N, int T, int batch) {
+  if (!e.tn_rows_on() || N % 128 != 0 || M % 16 != 0 || T % 32 != 0 || T < 64) return false;
+  return (long)batch * (N / 128) * (M / 16) >= 8L * e.cus;      // (256 x 256 channels, 4.5 blocks per CU: 38 us here, 35 on the 64x64 kernel)
 }
 
 // T-split on the same kernel (round 5): a product with too few 16-row blocks for the row-share schedule -- the 1x1 backward-weight
@@ -1602,97 +1619,158 @@ static bool tn_rows(int M, int N, int T, int batch) {
 // the kernel walks as P problems of their own (part s of problem p starts at A + (p P + s) T' M: the plain problem stride), each
 // landing in slab s; the consumers sum the slabs in slab order, as they do behind the per-tile kernels these shapes ran on
 // (bgemm_ws_kernel<128,128,true>: 30 TF on the 1x1 product; bgemm_tn_kernel<64,64>: 0.43 of the peak).  P = the smallest divisor of
-// the chunk count that gives every CU ~7 blocks with at least 4 chunks per part.  HIFIHR_GEMM_TN_SPLIT=0: the per-tile kernels.
+// the chunk count that gives every CU ~7 blocks with at least 4 chunks per part.
 // MEASURED (tools/time_gemm_tn_split.py, gpurun_out/tn_split_*.txt): the 36 products of a 128-channel F(4x4) layer 26.7 -> 25.4 us, of a
 // 256-channel one 35.8 -> 31.6 us; SINGLE products lose (1x1 backward-weight 256 -> 512 at 14 x 14: 22.9 -> 25.4 us, 512 -> 512: 36.8 ->
 // 42.3 us: 28 / 14 slabs of a whole filter each) -- batched products only.
 // Long reductions (VGG19's layers at 112 x 112 / 56 x 56: T = 9 408 ... 37 632) stay on the per-tile kernels too: config 3 measured
 // 34.41 ms/step without the split against 34.49 / 34.53 with it (gpurun_out/c3_*.json).
-static int tn_rows_split(int M, int N, int T, int batch) {
-  if (batch < 2 || T > 4096) return 0;
-  static const int on = [] { const char* e = getenv("HIFIHR_GEMM_TN_SPLIT"); return e ? atoi(e) : 1; }();
-  static const int on_rows = [] { const char* e = getenv("HIFIHR_GEMM_TN_ROWS"); return e ? atoi(e) : 1; }();
-  if (!on || !on_rows || N % 128 != 0 || M % 16 != 0 || T % 32 != 0 || T < 64) return 0;
-  if (getenv("HIFIHR_GEMM_TN_TILE") != nullptr || getenv("HIFIHR_GEMM_TN_PARTS") != nullptr) return 0;
+static int tn_rows_split(const GemmEnv& e, int M, int N, int T, int batch) {
+  if (batch < 2 || T > 4096 || !e.tn_split || !e.tn_rows_on() || N % 128 != 0 || M % 16 != 0 || T % 32 != 0 || T < 64) return 0;
   const int nch = T / 32;
-  const long blocks = (long)batch * (N / 128) * (M / 16), need = 7L * gemm_cus();
+  const long blocks = (long)batch * (N / 128) * (M / 16), need = 7L * e.cus;
   for (int P = 2; P <= nch / 4; ++P)
     if (nch % P == 0 && blocks * P >= need) return P;
   return 0;
 }
 
-// which kernel instantiation a shape runs on, as rocprof names it (bench.py groups its roofline lines by this)
-void bgemm_describe(int tn, int M, int N, int K, char* out, int cap) { bgemm_describe_batch(tn, M, N, K, 16, out, cap); }
-
-void bgemm_describe_batch(int tn, int M, int N, int K, int batch, char* out, int cap) {
-  int bm, bn;
-  const char* e;
-  if (tn) {
-    tn_tile(M, N, batch, &bm, &bn);
-    if ((e = getenv("HIFIHR_GEMM_TN_TILE")) != nullptr) { const int v = atoi(e); bm = v / 1000; bn = v % 1000; if (M % bm) bm = 64; if (N % bn) bn = 64; }
-  } else {
-    nt_tile(M, N, K, &bm, &bn);
-    if ((e = getenv("HIFIHR_GEMM_NT_TILE")) != nullptr) { const int v = atoi(e); bm = v / 1000; bn = v % 1000; if (N % bn) bn = 64; }
-  }
-  const int nload = gemm_ws_loaders();
-  // (the instantiation rocprof lists: <0> plain, <1> ragged N / K; <2> = the gathering form, named by hifihr_conv2d_describe)
-  if (!tn && (nt_rows(N) || bgemm_nt_ragged_supported(M, N, K))) { snprintf(out, cap, "bgemm_nt_rows_kernel<%d>", bgemm_nt_ragged_supported(M, N, K) ? 1 : 0); return; }
-  if (tn && (tn_rows(M, N, K, batch) || tn_rows_split(M, N, K, batch))) { snprintf(out, cap, "bgemm_tn_rows_kernel"); return; }
-  if (!tn && bm == 128 && bn == 128 && nload > 0 && bgemm_nt_workspace_bytes(M, N, K, 16) > 0) snprintf(out, cap, "bgemm_nt_sk_kernel<%d>", nload == 2 ? 2 : 4);
-  else if (bm == 128 && bn == 128 && nload > 0) snprintf(out, cap, "bgemm_ws_kernel<128, 128, %s, %d>", tn ? "true" : "false", nload == 1 ? 1 : nload == 4 ? 4 : 2);
-  else snprintf(out, cap, "%s<%d, %d>", tn ? "bgemm_tn_kernel" : "bgemm_nt_kernel", bm, bn);
-}
-
 bool bgemm_nt_supported(int M, int N, int K) { return M > 0 && K >= 32 && K % 32 == 0 && N >= 64 && N % 64 == 0; }
 bool bgemm_tn_supported(int M, int N, int T) { return T > 0 && M >= 64 && M % 64 == 0 && N >= 64 && N % 64 == 0; }
-
-static size_t sk_flag_bytes(int G) { return (size_t)((G + 1) * 4 * sizeof(unsigned) + 255) / 256 * 256; }
-
-// bytes of zero-initialised, self-cleaning workspace the persistent NT kernel wants for this shape (0: the shape runs on a
-// kernel that needs none)
-size_t bgemm_nt_workspace_bytes(int M, int N, int K, int batch) {
-  if (!bgemm_nt_supported(M, N, K) || batch <= 0 || gemm_ws_loaders() <= 0) return 0;
-  if (nt_rows(N)) return 0;                    // whole tiles only: nothing is exchanged between workgroups
-  if (const char* e = getenv("HIFIHR_GEMM_SK")) { if (atoi(e) == 0) return 0; }
-  int bm, bn;
-  nt_tile(M, N, K, &bm, &bn);
-  if (const char* e = getenv("HIFIHR_GEMM_NT_TILE")) { const int v = atoi(e); bm = v / 1000; bn = v % 1000; if (N % bn) bn = 64; }
-  if (bm != 128 || bn != 128) return 0;
-  const int G = gemm_cus(), nch = K / 32;
-  const long total = (long)((M + 127) / 128) * (N / 128) * batch * nch;
-  const long per = (total + G - 1) / G;
-  if (per < nch) return 0;                    // shares shorter than a tile would split it three ways: the per-tile kernel instead
-  // measured (tools/time_gemm.py, profiles/r02_time_gemm.txt): 832 tiles x 16 chunks 141.5 -> 132.7 us, but 416 x 16 71.7 -> 76.3 and the
-  // 4- / 8-chunk tiles much worse (the tile epilogue stalls the whole workgroup, nothing else is resident on the CU to cover it):
-  // only where the per-tile kernel would run >= 3 rounds
-  if (total / nch < 3L * G) return 0;
-  return sk_flag_bytes(G) + (size_t)G * 128 * 128 * sizeof(float);
-}
 
 // ragged N / K on the row-share kernel (EfficientNet's 1x1 convolutions).  Measured at batch 48 against conv_igemm_kernel
 // (tools/time_conv1x1.py with EFFNET=1, HIFIHR_GEMM_RAGGED=0 for the other side): a wash on most shapes -- these products are 20-50 us
 // launches on 2 352-9 408 rows, bounded by their size, and the implicit GEMM's 64-column tiles waste less of a 136- or 232-wide output --
 // a win where the 128-column tiles are >= 90 % full and the reduction is long (1392 -> 384: 45 -> 35 us, 232 -> 1392: 28.5 -> 25.7), a loss
-// below (32 -> 192: 45 -> 54, 576 -> 136: 30 -> 35).  Hence: tiles >= 90 % full and K >= 128 (HIFIHR_GEMM_RAGGED=2: every shape the kernel
-// can take, for the A/B).
-bool bgemm_nt_ragged_supported(int M, int N, int K) {
-  static const int on = [] { const char* e = getenv("HIFIHR_GEMM_RAGGED"); return e ? atoi(e) : 1; }();
-  if (!on || !nt_rows(128) || M <= 0 || N < 96 || N % 4 != 0 || K < 16 || K % 4 != 0 || (N % 128 == 0 && K % 32 == 0)) return false;
-  if (on >= 2) return true;
+// below (32 -> 192: 45 -> 54, 576 -> 136: 30 -> 35).  Hence: tiles >= 90 % full and K >= 128.
+static bool nt_ragged(const GemmEnv& e, int M, int N, int K) {
+  if (!e.ragged || !e.rows_on() || M <= 0 || N < 96 || N % 4 != 0 || K < 16 || K % 4 != 0 || (N % 128 == 0 && K % 32 == 0)) return false;
+  if (e.ragged >= 2) return true;
   return K >= 128 && 10L * N >= 9L * ((N + 127) / 128 * 128);
 }
-bool bgemm_nt_stats_supported(int N) { return nt_rows(N) || (nt_rows(128) && N >= 96 && N % 4 == 0); }      // the statistics epilogue exists in the row-share kernel only
+bool bgemm_nt_ragged_supported(int M, int N, int K) { return nt_ragged(gemm_env(), M, N, K); }
+bool bgemm_nt_stats_supported(int N) {      // the statistics epilogue exists in the row-share kernel only
+  return gemm_env().rows_on() && (N % 128 == 0 || (N >= 96 && N % 4 == 0));
+}
+
+// Equal shares of `total` units of a row-share kernel's work for `cus` workgroups (the pair launches pass the CUs of one side), at least
+// min_per each -> the workgroups.  NT: rows of the flattened (problem, 128-column tile, row) space, at least one 16-row block; TN: 16-row
+// blocks of the (problem, column tile, block) space, at least 4.
+static int row_shares(long total, int cus, long min_per, long* per_out) {
+  long per = (total + cus - 1) / cus;
+  if (per < min_per) per = min_per;
+  *per_out = per;
+  return (int)((total + per - 1) / per);
+}
+static int nt_shares(int M, int N, int batch, int cus, long* per) { return row_shares((long)batch * ((N + 127) / 128) * M, cus, 16, per); }
+static int tn_shares(int M, int N, int problems, int cus, long* per) { return row_shares((long)problems * (N / 128) * (M / 16), cus, 4, per); }
+static size_t sk_flag_bytes(int G) { return (size_t)((G + 1) * 4 * sizeof(unsigned) + 255) / 256 * 256; }
+
+// The NT plan.  Precedence: the row-share kernel with ragged N / K, the plain row-share kernel (N % 128 == 0), then by tile -- 128x128 with
+// loader waves: the persistent stream-K kernel where its workspace pays, else one workgroup per tile -- and the 4-wave kernels.
+// M_alloc > M: the problems of the batch are M_alloc rows apart in A and C, only the first M of each are computed (the mosaic tile count of
+// the F(4x4, 3x3) pipeline is rounded up for the backward-weight products); only the plain row-share kernel walks the real rows, every
+// other kernel computes all M_alloc.
+static NtPlan plan_nt(const GemmEnv& e, int M, int M_alloc, int N, int K, int batch, bool stats) {
+  const bool rows = e.rows_on() && N % 128 == 0;
+  if (M_alloc > M && !(rows && !nt_ragged(e, M, N, K) && bgemm_nt_supported(M_alloc, N, K) && batch > 0 && !stats)) M = M_alloc;
+  if (M_alloc < M) M_alloc = M;
+  const bool ragged = nt_ragged(e, M, N, K);
+  NtPlan p{};
+  p.M = M; p.M_alloc = M_alloc; p.N = N; p.K = K; p.batch = batch; p.loaders = e.loaders;
+  p.ok = (bgemm_nt_supported(M, N, K) || ragged) && batch > 0 && !(stats && (batch != 1 || !(rows || ragged)));
+  if (ragged || rows) { p.kernel = ragged ? NtKernel::rows_ragged : NtKernel::rows; p.G = nt_shares(M, N, batch, e.cus, &p.per); return p; }
+  nt_tile(e, N, K, &p.bm, &p.bn);
+  if (p.bm != 128 || p.bn != 128 || e.loaders <= 0) { p.kernel = NtKernel::tile; p.ok = p.ok && tile_exists(p.bm, p.bn); return p; }
+  p.kernel = NtKernel::ws;
+  if (!p.ok || !e.sk) return p;
+  // the persistent kernel: zero-initialised, self-cleaning flags + one slab per workgroup
+  const int G = e.cus, nch = K / 32;
+  const long total = (long)((M + 127) / 128) * (N / 128) * batch * nch;
+  const long per = (total + G - 1) / G;
+  if (per < nch) return p;                    // shares shorter than a tile would split it three ways: the per-tile kernel instead
+  // measured (tools/time_gemm.py, profiles/r02_time_gemm.txt): 832 tiles x 16 chunks 141.5 -> 132.7 us, but 416 x 16 71.7 -> 76.3 and the
+  // 4- / 8-chunk tiles much worse (the tile epilogue stalls the whole workgroup, nothing else is resident on the CU to cover it):
+  // only where the per-tile kernel would run >= 3 rounds
+  if (total / nch < 3L * G) return p;
+  p.kernel = NtKernel::sk; p.G = G;
+  p.ws_bytes = sk_flag_bytes(G) + (size_t)G * 128 * 128 * sizeof(float);
+  return p;
+}
+
+NtPlan plan_nt(int M, int M_alloc, int N, int K, int batch, bool stats) { return plan_nt(gemm_env(), M, M_alloc, N, K, batch, stats); }
+
+// the kernel instantiation of a plan, as rocprof names it (bench.py groups its roofline lines by this); <0> plain, <1> ragged N / K (<2>,
+// the gathering form, is named by the convolution plan)
+void describe_nt(const NtPlan& p, char* out, int cap) {
+  if (p.kernel == NtKernel::rows || p.kernel == NtKernel::rows_ragged) snprintf(out, cap, "bgemm_nt_rows_kernel<%d>", p.kernel == NtKernel::rows ? 0 : 1);
+  else if (p.kernel == NtKernel::sk) snprintf(out, cap, "bgemm_nt_sk_kernel<%d>", p.loaders == 2 ? 2 : 4);
+  else if (p.kernel == NtKernel::ws) snprintf(out, cap, "bgemm_ws_kernel<128, 128, false, %d>", p.loaders == 1 ? 1 : p.loaders == 4 ? 4 : 2);
+  else snprintf(out, cap, "bgemm_nt_kernel<%d, %d>", p.bm, p.bn);
+}
+// bytes of zero-initialised, self-cleaning workspace the persistent NT kernel wants for this shape (0: the shape runs on a
+// kernel that needs none)
+size_t bgemm_nt_workspace_bytes(int M, int N, int K, int batch) { return plan_nt(M, 0, N, K, batch, false).ws_bytes; }
+
+// The TN plan.  The row-share kernel with complete products (one slab), the same kernel with the T range cut into P parts, else the
+// per-tile kernels with `parts` slabs of cps chunks each (parts_given > 0: the caller's slab count instead of the plan's own).
+enum class TnKernel { rows, ws, tile };
+struct TnPlan {
+  bool ok;                 // false: launch_bgemm_tn answers hipErrorInvalidValue
+  TnKernel kernel;
+  int parts;               // slabs the product is written in
+  int bm, bn, loaders, cps;
+  int G; long per;         // rows: workgroups and their share of 16-row blocks
+};
+static TnPlan plan_tn(const GemmEnv& e, int M, int N, int T, int batch, int parts_given = 0) {
+  TnPlan p{};
+  p.ok = true; p.loaders = e.loaders;
+  if (const int P = tn_rows(e, M, N, T, batch) ? 1 : tn_rows_split(e, M, N, T, batch)) {
+    p.kernel = TnKernel::rows; p.parts = P; p.cps = T / P / 32;
+    p.G = tn_shares(M, N, batch * P, e.cus, &p.per);
+    return p;
+  }
+  tn_tile(e, M, N, batch, &p.bm, &p.bn);
+  p.kernel = (p.bm == 128 && p.bn == 128 && e.loaders > 0) ? TnKernel::ws : TnKernel::tile;
+  const int nch = (T + 31) / 32;
+  p.parts = parts_given > 0 ? parts_given : e.tn_parts;
+  if (p.parts <= 0) {                                        // (kUnset or not positive: the plan's own count)
+    const int tiles = (M / p.bm) * (N / p.bn) * batch;
+    // 128x128 (one workgroup per CU): fill the CUs once; 64x64: ~2 workgroups per CU; at least 7 chunks per slab so that the slab
+    // round trip (written here, summed by wino_dw_transform_parts) stays small next to the reduction.  With the 36 problems of an
+    // F(4x4, 3x3) layer the 64x64 kernel does best at ~4.5 workgroups per CU (tools/time_gemm_tn_f4.py).
+    int splits = ((p.bm == 128 && p.bn == 128) ? e.cus : batch > 16 ? (9 * e.cus / 2 + tiles / 2) : 2 * e.cus) / tiles;
+    if (splits > nch / 7) splits = nch / 7;      // (7, not 8: the 49 chunks of a 28 x 28 F(4x4) layer split 7 x 7 -- 30.6 -> 25.9 us)
+    if (splits < 1) splits = 1;
+    const int cps = (nch + splits - 1) / splits;
+    p.parts = (nch + cps - 1) / cps;
+  }
+  p.cps = (nch + p.parts - 1) / p.parts;
+  p.ok = tile_exists(p.bm, p.bn) && (nch + p.cps - 1) / p.cps == p.parts;      // (a slab count that no chunk count per slab produces)
+  return p;
+}
+
+void bgemm_describe(int tn, int M, int N, int K, char* out, int cap) { bgemm_describe_batch(tn, M, N, K, 16, out, cap); }
+
+void bgemm_describe_batch(int tn, int M, int N, int K, int batch, char* out, int cap) {
+  if (!tn) return describe_nt(plan_nt(M, 0, N, K, batch, false), out, cap);
+  const TnPlan p = plan_tn(gemm_env(), M, N, K, batch);
+  if (p.kernel == TnKernel::rows) snprintf(out, cap, "bgemm_tn_rows_kernel");
+  else if (p.kernel == TnKernel::ws) snprintf(out, cap, "bgemm_ws_kernel<128, 128, true, %d>", p.loaders == 1 ? 1 : p.loaders == 4 ? 4 : 2);
+  else snprintf(out, cap, "bgemm_tn_kernel<%d, %d>", p.bm, p.bn);
+}
 
 // ---- forward convolutions on the row-share kernel with the gather in its loader waves (MODE 2) ----
-bool conv_rows_supported(const ConvGeom& g, const float* bias) {
-  static const int on = [] { const char* e = getenv("HIFIHR_CONV_ROWS"); return e ? atoi(e) : 1; }();
-  if (!on || !nt_rows(128) || g.dgrad || bias != nullptr || g.relu || g.batch > 1) return false;
+static bool conv_rows_ok(const GemmEnv& e, const ConvGeom& g, const float* bias) {
+  const int on = e.conv_rows;
+  if (!on || !e.rows_on() || g.dgrad || bias != nullptr || g.relu || g.batch > 1) return false;
   if (g.IC % 32 != 0 || g.OC % 128 != 0 || g.R != g.S || (g.R != 1 && g.R != 3)) return false;
   const long M = (long)g.N * g.OH * g.OW;
   if (M >= (1L << 31) || (long)g.N * g.IH * g.IW * g.IC >= (1L << 31)) return false;
   if (on >= 2) return true;                                  // (every shape the kernel takes: the A/B)
   return g.stride == 2;                                      // stride 1: 1x1 is a plain GEMM already, 3x3 runs as Winograd / on the halo kernel
 }
+
+bool conv_rows_supported(const ConvGeom& g, const float* bias) { return conv_rows_ok(gemm_env(), g, bias); }
 
 static BgemmArgs conv_rows_args(const ConvGeom& g, const float* src, const float* wgt, float* dst, float* stats, const float* zeros) {
   BgemmArgs a{};
@@ -1733,9 +1811,9 @@ __global__ __launch_bounds__(512) void bgemm_nt_rows_pair2_kernel(BgemmArgs a, l
   else nt_rows_body<2>(b, per_b, lds, (int)blockIdx.x - ga, (int)gridDim.x - ga);
 }
 bool conv_rows_pair_supported(const ConvGeom& g1, const ConvGeom& g2) {
-  static const int on = [] { const char* e = getenv("HIFIHR_CONV_ROWS_PAIR"); return e ? atoi(e) : 1; }();
-  return on && conv_rows_supported(g1, nullptr) && conv_rows_supported(g2, nullptr) && g1.N == g2.N && g1.IH == g2.IH && g1.IW == g2.IW &&
-         g1.IC == g2.IC && gemm_cus() >= 16;
+  const GemmEnv e = gemm_env();
+  return e.conv_rows_pair && conv_rows_ok(e, g1, nullptr) && conv_rows_ok(e, g2, nullptr) && g1.N == g2.N && g1.IH == g2.IH && g1.IW == g2.IW &&
+         g1.IC == g2.IC && e.cus >= 16;
 }
 hipError_t launch_conv_rows_pair(const ConvGeom& g1, const float* src, const float* w1, float* y1, float* stats1, const ConvGeom& g2, const float* w2,
                                  float* y2, float* stats2, const float* zeros, hipStream_t st) {
@@ -1753,110 +1831,60 @@ hipError_t launch_conv_rows_pair(const ConvGeom& g1, const float* src, const flo
   return hipGetLastError();
 }
 
-hipError_t launch_bgemm_nt(const float* A, const float* B, float* C, int M, int N, int K, int batch, void* ws, size_t ws_bytes, hipStream_t st,
-                           float* stats, int M_alloc) {
-  // M_alloc > M: the problems of the batch are M_alloc rows apart in A and C, only the first M of each are computed (the mosaic tile
-  // count of the F(4x4, 3x3) pipeline is rounded up for the backward-weight products; the row-share kernel walks the real rows)
-  if (M_alloc > M && nt_rows(N) && !bgemm_nt_ragged_supported(M, N, K) && bgemm_nt_supported(M_alloc, N, K) && batch > 0 && stats == nullptr &&
-      (long)M_alloc * K < (1L << 31) && (long)N * K < (1L << 31)) {
-    BgemmArgs a{};
-    a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.K = K; a.lda = K; a.ldb = K; a.ldc = N;
-    a.sa = (long)M_alloc * K; a.sb = (long)N * K; a.sc = (long)M_alloc * N; a.batch = batch;
-    a.tiles_n = N / 128; a.tiles_m = (M + 127) / 128; a.splits = 1; a.cps = K / 32; a.sc_split = 0;
-    const long total = (long)batch * a.tiles_n * M;
-    const int cus = gemm_cus();
-    long per = (total + cus - 1) / cus;
-    if (per < 16) per = 16;
-    const int G = (int)((total + per - 1) / per);
-    hipLaunchKernelGGL(bgemm_nt_rows_kernel<0>, dim3(G), dim3(512), 0, st, a, per);
-    return hipGetLastError();
-  }
-  if (M_alloc > M) M = M_alloc;
-  const bool ragged = bgemm_nt_ragged_supported(M, N, K);
-  if ((!bgemm_nt_supported(M, N, K) && !ragged) || batch <= 0) return hipErrorInvalidValue;
-  if (stats != nullptr && (batch != 1 || !(nt_rows(N) || ragged))) return hipErrorInvalidValue;
-  if ((long)M * K >= (1L << 31) || (long)N * K >= (1L << 31)) return hipErrorInvalidValue;      // 32-bit element offsets
+// the BgemmArgs of a plain NT problem (tiles of the row-share kernels; the per-tile launches set their own tile counts)
+static BgemmArgs nt_args(const NtPlan& p, const float* A, const float* B, float* C) {
   BgemmArgs a{};
-  a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.K = K; a.lda = K; a.ldb = K; a.ldc = N;
-  a.sa = (long)M * K; a.sb = (long)N * K; a.sc = (long)M * N; a.batch = batch;
+  a.A = A; a.B = B; a.C = C; a.M = p.M; a.N = p.N; a.K = p.K; a.lda = p.K; a.ldb = p.K; a.ldc = p.N;
+  a.sa = (long)p.M_alloc * p.K; a.sb = (long)p.N * p.K; a.sc = (long)p.M_alloc * p.N; a.batch = p.batch;
+  a.tiles_n = (p.N + 127) / 128; a.tiles_m = (p.M + 127) / 128; a.splits = 1; a.cps = (p.K + 31) / 32; a.sc_split = 0;
+  return a;
+}
+static bool nt_fits32(const NtPlan& p) { return (long)p.M_alloc * p.K < (1L << 31) && (long)p.N * p.K < (1L << 31); }      // 32-bit element offsets
+
+hipError_t launch_bgemm_nt_plan(const NtPlan& p, const float* A, const float* B, float* C, void* ws, size_t ws_bytes, hipStream_t st, float* stats) {
+  if (!p.ok || !nt_fits32(p)) return hipErrorInvalidValue;
+  BgemmArgs a = nt_args(p, A, B, C);
   a.stats = stats;
-  if (ragged) {
+  if (p.kernel == NtKernel::rows) {
+    hipLaunchKernelGGL(bgemm_nt_rows_kernel<0>, dim3(p.G), dim3(512), 0, st, a, p.per);
+  } else if (p.kernel == NtKernel::rows_ragged) {
     a.zeros = conv_halo_zero_page(st);                       // (allocated on first use outside a capture: csrc/conv_halo.hip)
     if (a.zeros == nullptr) return hipErrorNotReady;
-    a.tiles_n = (N + 127) / 128; a.tiles_m = (M + 127) / 128; a.splits = 1; a.cps = (K + 31) / 32; a.sc_split = 0;
-    const long total = (long)batch * a.tiles_n * M;
-    const int cus = gemm_cus();
-    long per = (total + cus - 1) / cus;
-    if (per < 16) per = 16;
-    const int G = (int)((total + per - 1) / per);
-    hipLaunchKernelGGL(bgemm_nt_rows_kernel<1>, dim3(G), dim3(512), 0, st, a, per);
-    return hipGetLastError();
+    hipLaunchKernelGGL(bgemm_nt_rows_kernel<1>, dim3(p.G), dim3(512), 0, st, a, p.per);
+  } else if (p.kernel == NtKernel::sk && ws != nullptr && ws_bytes >= p.ws_bytes) {
+    a.tiles_n = p.N / 128;
+    float* slabs = reinterpret_cast<float*>(static_cast<char*>(ws) + sk_flag_bytes(p.G));
+    if (p.loaders == 2) hipLaunchKernelGGL((bgemm_nt_sk_kernel<2>), dim3(p.G), dim3(384), 0, st, a, slabs, static_cast<unsigned*>(ws));
+    else hipLaunchKernelGGL((bgemm_nt_sk_kernel<4>), dim3(p.G), dim3(512), 0, st, a, slabs, static_cast<unsigned*>(ws));
+  } else {
+    // one workgroup per tile (the stream-K plan without its workspace: the wave-specialised kernel on the same tile)
+    a.tiles_m = (p.M + p.bm - 1) / p.bm; a.tiles_n = p.N / p.bn;
+    const dim3 grid((unsigned)(a.tiles_m * a.tiles_n * p.batch));
+    if (p.kernel != NtKernel::tile && p.loaders == 1) hipLaunchKernelGGL((bgemm_ws_kernel<128, 128, false, 1>), grid, dim3(320), 0, st, a);
+    else if (p.kernel != NtKernel::tile && p.loaders == 4) hipLaunchKernelGGL((bgemm_ws_kernel<128, 128, false, 4>), grid, dim3(512), 0, st, a);
+    else if (p.kernel != NtKernel::tile) hipLaunchKernelGGL((bgemm_ws_kernel<128, 128, false, 2>), grid, dim3(384), 0, st, a);
+    else if (p.bm == 128 && p.bn == 128) hipLaunchKernelGGL((bgemm_nt_kernel<128, 128>), grid, dim3(256), 0, st, a);
+    else if (p.bm == 128) hipLaunchKernelGGL((bgemm_nt_kernel<128, 64>), grid, dim3(256), 0, st, a);
+    else if (p.bn == 128) hipLaunchKernelGGL((bgemm_nt_kernel<64, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((bgemm_nt_kernel<64, 64>), grid, dim3(256), 0, st, a);
   }
-  if (nt_rows(N)) {
-    a.tiles_n = N / 128; a.tiles_m = (M + 127) / 128; a.splits = 1; a.cps = K / 32; a.sc_split = 0;
-    const long total = (long)batch * a.tiles_n * M;
-    const int cus = gemm_cus();
-    long per = (total + cus - 1) / cus;
-    if (per < 16) per = 16;
-    const int G = (int)((total + per - 1) / per);
-    hipLaunchKernelGGL(bgemm_nt_rows_kernel<0>, dim3(G), dim3(512), 0, st, a, per);
-    return hipGetLastError();
-  }
-  int bm, bn;
-  nt_tile(M, N, K, &bm, &bn);
-  if (const char* e = getenv("HIFIHR_GEMM_NT_TILE")) { const int v = atoi(e); bm = v / 1000; bn = v % 1000; if (N % bn) bn = 64; }
-  a.tiles_m = (M + bm - 1) / bm; a.tiles_n = N / bn; a.splits = 1; a.cps = K / 32; a.sc_split = 0;
-  const dim3 grid((unsigned)(a.tiles_m * a.tiles_n * batch));
-  const int nload = gemm_ws_loaders();
-  if (nload > 0 && bm == 128 && bn == 128 && ws != nullptr && ws_bytes >= bgemm_nt_workspace_bytes(M, N, K, batch) &&
-      bgemm_nt_workspace_bytes(M, N, K, batch) > 0) {
-    const int G = gemm_cus();
-    unsigned* flags = static_cast<unsigned*>(ws);
-    float* slabs = reinterpret_cast<float*>(static_cast<char*>(ws) + sk_flag_bytes(G));
-    if (nload == 2) hipLaunchKernelGGL((bgemm_nt_sk_kernel<2>), dim3(G), dim3(384), 0, st, a, slabs, flags);
-    else hipLaunchKernelGGL((bgemm_nt_sk_kernel<4>), dim3(G), dim3(512), 0, st, a, slabs, flags);
-    return hipGetLastError();
-  }
-  if (nload > 0 && bm == 128 && bn == 128) {
-    if (nload == 1) hipLaunchKernelGGL((bgemm_ws_kernel<128, 128, false, 1>), grid, dim3(320), 0, st, a);
-    else if (nload == 4) hipLaunchKernelGGL((bgemm_ws_kernel<128, 128, false, 4>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((bgemm_ws_kernel<128, 128, false, 2>), grid, dim3(384), 0, st, a);
-    return hipGetLastError();
-  }
-  if (bm == 128 && bn == 128) hipLaunchKernelGGL((bgemm_nt_kernel<128, 128>), grid, dim3(256), 0, st, a);
-  else if (bm == 128 && bn == 64) hipLaunchKernelGGL((bgemm_nt_kernel<128, 64>), grid, dim3(256), 0, st, a);
-  else if (bm == 64 && bn == 128) hipLaunchKernelGGL((bgemm_nt_kernel<64, 128>), grid, dim3(256), 0, st, a);
-  else if (bm == 64 && bn == 64) hipLaunchKernelGGL((bgemm_nt_kernel<64, 64>), grid, dim3(256), 0, st, a);
-  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
-// number of K-split slabs launch_bgemm_tn writes for this shape (the caller provides parts * batch * M * N floats)
-int bgemm_tn_parts(int M, int N, int T, int batch) {
-  if (tn_rows(M, N, T, batch)) return 1;
-  if (const int P = tn_rows_split(M, N, T, batch)) return P;
-  if (const char* e = getenv("HIFIHR_GEMM_TN_PARTS")) { const int v = atoi(e); if (v > 0) return v; }
-  int bm, bn;
-  tn_tile(M, N, batch, &bm, &bn);
-  if (const char* e = getenv("HIFIHR_GEMM_TN_TILE")) { const int v = atoi(e); bm = v / 1000; bn = v % 1000; if (M % bm) bm = 64; if (N % bn) bn = 64; }
-  const int tiles = (M / bm) * (N / bn) * batch, nch = (T + 31) / 32;
-  // 128x128 (one workgroup per CU): fill the CUs once; 64x64: ~2 workgroups per CU; at least 7 chunks per slab so that the slab
-  // round trip (written here, summed by wino_dw_transform_parts) stays small next to the reduction.  With the 36 problems of an
-  // F(4x4, 3x3) layer the 64x64 kernel does best at ~4.5 workgroups per CU (tools/time_gemm_tn_f4.py).
-  int splits = ((bm == 128 && bn == 128) ? gemm_cus() : batch > 16 ? (9 * gemm_cus() / 2 + tiles / 2) : 2 * gemm_cus()) / tiles;
-  if (splits > nch / 7) splits = nch / 7;      // (7, not 8: the 49 chunks of a 28 x 28 F(4x4) layer split 7 x 7 -- 30.6 -> 25.9 us)
-  if (splits < 1) splits = 1;
-  const int cps = (nch + splits - 1) / splits;
-  return (nch + cps - 1) / cps;
+hipError_t launch_bgemm_nt(const float* A, const float* B, float* C, int M, int N, int K, int batch, void* ws, size_t ws_bytes, hipStream_t st,
+                           float* stats, int M_alloc) {
+  return launch_bgemm_nt_plan(plan_nt(M, M_alloc, N, K, batch, stats != nullptr), A, B, C, ws, ws_bytes, st, stats);
 }
+
+// number of K-split slabs launch_bgemm_tn writes for this shape (the caller provides parts * batch * M * N floats)
+int bgemm_tn_parts(int M, int N, int T, int batch) { return plan_tn(gemm_env(), M, N, T, batch).parts; }
 
 // XCD-coherent schedule of the TN row-share kernel for G workgroups (BgemmArgs::co_r): the smallest number r of problems per XCD and round
 // that gives every workgroup of the XCD at least one whole 128-row tile per round, while the operands of those r problems fit the XCD's L2
-// and at least one full round exists.  HIFIHR_GEMM_TN_COHERENT=0: contiguous shares.
+// and at least one full round exists.
 static void tn_coherent(BgemmArgs& a, int G) {
-  static const int on = [] { const char* e = getenv("HIFIHR_GEMM_TN_COHERENT"); return e ? atoi(e) : 1; }();
   a.co_r = 0; a.co_rounds = 0;
-  if (!on || G < 8 || G % 8 != 0 || a.M % 16 != 0) return;
+  if (G < 8 || G % 8 != 0 || a.M % 16 != 0) return;
   const int W = G / 8;
   const long bpp = (long)a.tiles_n * (a.M / 16);
   if (bpp <= 8) return;                                     // one tile per problem: no two workgroups share a panel
@@ -1869,49 +1897,44 @@ static void tn_coherent(BgemmArgs& a, int G) {
   }
 }
 
+// the BgemmArgs every TN launch shares: `problems` problems of Tp rows each
+static BgemmArgs tn_args(const float* A, const float* B, float* Cparts, int M, int N, int Tp, int problems) {
+  BgemmArgs a{};
+  a.A = A; a.B = B; a.C = Cparts; a.M = M; a.N = N; a.K = Tp; a.lda = M; a.ldb = N; a.ldc = N;
+  a.sa = (long)Tp * M; a.sb = (long)Tp * N; a.sc = (long)M * N; a.batch = problems;
+  return a;
+}
+// ... of the row-share kernel on G workgroups: the T range is walked as P parts (P problems of T / P rows each, one slab per part; P = 1:
+// the whole reduction, one slab); rows t >= T_valid (> 0) of both operands are zero and are skipped
+static BgemmArgs tn_rows_args(const GemmEnv& e, const float* A, const float* B, float* Cparts, int M, int N, int T, int batch, int P, int T_valid, int G) {
+  BgemmArgs a = tn_args(A, B, Cparts, M, N, T / P, batch * P);
+  a.tiles_n = N / 128; a.tiles_m = (M + 127) / 128; a.splits = P; a.cps = T / P / 32; a.sc_split = P > 1 ? (long)batch * M * N : 0;
+  a.k_valid = (e.tn_skip && T_valid > 0 && T_valid < T) ? T_valid : 0;
+  if (e.tn_coherent) tn_coherent(a, G);
+  return a;
+}
+
 hipError_t launch_bgemm_tn(const float* A, const float* B, float* Cparts, int M, int N, int T, int batch, int parts, hipStream_t st, int T_valid) {
   if (!bgemm_tn_supported(M, N, T) || batch <= 0 || parts <= 0 || T_valid < 0 || T_valid > T) return hipErrorInvalidValue;
-  BgemmArgs a{};
-  static const int skip_on = [] { const char* e = getenv("HIFIHR_GEMM_TN_SKIP"); return e ? atoi(e) : 1; }();      // (0: walk the zero rows too, A/B timing)
-  a.k_valid = (skip_on && T_valid < T) ? T_valid : 0;        // (row-share kernel only: the per-tile kernels walk every row)
-  a.A = A; a.B = B; a.C = Cparts; a.M = M; a.N = N; a.K = T; a.lda = M; a.ldb = N; a.ldc = N;
-  a.sa = (long)T * M; a.sb = (long)T * N; a.sc = (long)M * N; a.batch = batch;
-  const int P = tn_rows(M, N, T, batch) ? 1 : tn_rows_split(M, N, T, batch);
-  if (P > 0) {
-    if (parts != P) return hipErrorInvalidValue;
-    const int Tp = T / P;                                    // (P == 1: the whole reduction per tile, one slab)
-    a.K = Tp; a.sa = (long)Tp * M; a.sb = (long)Tp * N; a.batch = batch * P;
-    a.tiles_n = N / 128; a.tiles_m = (M + 127) / 128; a.splits = P; a.cps = Tp / 32; a.sc_split = P > 1 ? (long)batch * M * N : 0;
-    const long total = (long)a.batch * a.tiles_n * (M / 16);
-    const int cus = gemm_cus();
-    long per = (total + cus - 1) / cus;
-    if (per < 4) per = 4;
-    const int G = (int)((total + per - 1) / per);
-    tn_coherent(a, G);
-    hipLaunchKernelGGL(bgemm_tn_rows_kernel, dim3(G), dim3(512), 0, st, a, per);
+  const GemmEnv e = gemm_env();
+  const TnPlan p = plan_tn(e, M, N, T, batch, parts);
+  if (!p.ok || p.parts != parts) return hipErrorInvalidValue;            // parts must come from bgemm_tn_parts
+  if (p.kernel == TnKernel::rows) {
+    const BgemmArgs a = tn_rows_args(e, A, B, Cparts, M, N, T, batch, parts, T_valid, p.G);
+    hipLaunchKernelGGL(bgemm_tn_rows_kernel, dim3(p.G), dim3(512), 0, st, a, p.per);
     return hipGetLastError();
   }
-  int bm, bn;
-  tn_tile(M, N, batch, &bm, &bn);
-  if (const char* e = getenv("HIFIHR_GEMM_TN_TILE")) { const int v = atoi(e); bm = v / 1000; bn = v % 1000; if (M % bm) bm = 64; if (N % bn) bn = 64; }
-  a.tiles_m = M / bm; a.tiles_n = N / bn;
-  const int nch = (T + 31) / 32;
-  a.cps = (nch + parts - 1) / parts;
-  if ((nch + a.cps - 1) / a.cps != parts) return hipErrorInvalidValue;       // parts must come from bgemm_tn_parts
-  a.splits = parts; a.sc_split = (long)batch * M * N;
+  // the per-tile kernels: every tile walks `parts` slabs of cps chunks (and every row: no k_valid)
+  BgemmArgs a = tn_args(A, B, Cparts, M, N, T, batch);
+  a.tiles_m = M / p.bm; a.tiles_n = N / p.bn; a.cps = p.cps; a.splits = parts; a.sc_split = (long)batch * M * N;
   const dim3 grid((unsigned)(a.tiles_m * a.tiles_n * batch * parts));
-  const int nload = gemm_ws_loaders();
-  if (nload > 0 && bm == 128 && bn == 128) {
-    if (nload == 1) hipLaunchKernelGGL((bgemm_ws_kernel<128, 128, true, 1>), grid, dim3(320), 0, st, a);
-    else if (nload == 4) hipLaunchKernelGGL((bgemm_ws_kernel<128, 128, true, 4>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((bgemm_ws_kernel<128, 128, true, 2>), grid, dim3(384), 0, st, a);
-    return hipGetLastError();
-  }
-  if (bm == 128 && bn == 128) hipLaunchKernelGGL((bgemm_tn_kernel<128, 128>), grid, dim3(256), 0, st, a);
-  else if (bm == 128 && bn == 64) hipLaunchKernelGGL((bgemm_tn_kernel<128, 64>), grid, dim3(256), 0, st, a);
-  else if (bm == 64 && bn == 128) hipLaunchKernelGGL((bgemm_tn_kernel<64, 128>), grid, dim3(256), 0, st, a);
-  else if (bm == 64 && bn == 64) hipLaunchKernelGGL((bgemm_tn_kernel<64, 64>), grid, dim3(256), 0, st, a);
-  else return hipErrorInvalidValue;
+  if (p.kernel == TnKernel::ws && p.loaders == 1) hipLaunchKernelGGL((bgemm_ws_kernel<128, 128, true, 1>), grid, dim3(320), 0, st, a);
+  else if (p.kernel == TnKernel::ws && p.loaders == 4) hipLaunchKernelGGL((bgemm_ws_kernel<128, 128, true, 4>), grid, dim3(512), 0, st, a);
+  else if (p.kernel == TnKernel::ws) hipLaunchKernelGGL((bgemm_ws_kernel<128, 128, true, 2>), grid, dim3(384), 0, st, a);
+  else if (p.bm == 128 && p.bn == 128) hipLaunchKernelGGL((bgemm_tn_kernel<128, 128>), grid, dim3(256), 0, st, a);
+  else if (p.bm == 128) hipLaunchKernelGGL((bgemm_tn_kernel<128, 64>), grid, dim3(256), 0, st, a);
+  else if (p.bn == 128) hipLaunchKernelGGL((bgemm_tn_kernel<64, 128>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((bgemm_tn_kernel<64, 64>), grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -1919,55 +1942,36 @@ hipError_t launch_bgemm_tn(const float* A, const float* B, float* Cparts, int M,
 // C2parts = A2^T . B2 (row-share TN form, one slab or the T-split) in ONE launch.  hipErrorNotSupported: one of the two is not on its
 // row-share kernel (the caller then launches them separately).  The CUs are divided in proportion to the products' flops, the NT side
 // weighted by HIFIHR_GEMM_PAIR_NT_WEIGHT / 100 (default 100; measured on the ResNet-18 step: 70 -> 5.33 ms, 85 -> 5.21, 100 -> 5.17, 110 -> 5.22, 130 -> 5.50; separate launches 5.27).
-bool bgemm_nt_tn_pair_supported(int M, int M_alloc, int N, int K, int batch, int M2, int N2, int T2, int batch2, int parts2) {
-  static const int on = [] { const char* e = getenv("HIFIHR_GEMM_PAIR"); return e ? atoi(e) : 1; }();
-  if (M_alloc < M) M_alloc = M;
-  if (!on || !nt_rows(N) || bgemm_nt_ragged_supported(M, N, K) || !bgemm_nt_supported(M_alloc, N, K) || batch <= 0 ||
-      (long)M_alloc * K >= (1L << 31) || (long)N * K >= (1L << 31))
-    return false;
+static bool pair_plans(const GemmEnv& e, int M, int M_alloc, int N, int K, int batch, int M2, int N2, int T2, int batch2, int parts2, NtPlan* nt) {
+  *nt = plan_nt(e, M, M_alloc, N, K, batch, false);
+  if (!e.pair || !nt->ok || nt->kernel != NtKernel::rows || !nt_fits32(*nt)) return false;
   if (!bgemm_tn_supported(M2, N2, T2) || batch2 <= 0 || parts2 <= 0) return false;
-  const int P = tn_rows(M2, N2, T2, batch2) ? 1 : tn_rows_split(M2, N2, T2, batch2);
-  if (P <= 0 || P != parts2) return false;
+  const TnPlan tn = plan_tn(e, M2, N2, T2, batch2);
+  if (tn.kernel != TnKernel::rows || tn.parts != parts2) return false;
   // Long products gain nothing from sharing a launch (their ends are a small part of them): VGG19's layers at 112 x 112 / 56 x 56 (22-44
   // GFLOP each) measured 33.71 ms/step apart against 33.75 paired (config 3); the ResNet layers (1.9-8.5 GFLOP) 5.25 -> 5.16 ms/step.
-  static const double max_gf = [] { const char* e = getenv("HIFIHR_GEMM_PAIR_MAX_GFLOP"); const double v = e ? atof(e) : 12.0; return v > 0 ? v : 12.0; }();
-  return 2.0 * batch * (double)M * N * K <= max_gf * 1e9;
+  return 2.0 * batch * (double)M * N * K <= e.pair_max_gflop * 1e9;
+}
+bool bgemm_nt_tn_pair_supported(int M, int M_alloc, int N, int K, int batch, int M2, int N2, int T2, int batch2, int parts2) {
+  NtPlan nt;
+  return pair_plans(gemm_env(), M, M_alloc, N, K, batch, M2, N2, T2, batch2, parts2, &nt);
 }
 
 hipError_t launch_bgemm_nt_tn_pair(const float* A, const float* B, float* C, int M, int M_alloc, int N, int K, int batch, const float* A2,
                                    const float* B2, float* C2parts, int M2, int N2, int T2, int batch2, int parts2, hipStream_t st, int T2_valid) {
-  if (!bgemm_nt_tn_pair_supported(M, M_alloc, N, K, batch, M2, N2, T2, batch2, parts2)) return hipErrorNotSupported;
+  const GemmEnv e = gemm_env();
+  NtPlan nt;
+  if (!pair_plans(e, M, M_alloc, N, K, batch, M2, N2, T2, batch2, parts2, &nt)) return hipErrorNotSupported;
   if (T2_valid < 0 || T2_valid > T2) return hipErrorInvalidValue;
-  if (M_alloc < M) M_alloc = M;                               // (M_alloc > M: problems M_alloc rows apart, M of them computed -- see launch_bgemm_nt)
-  const int P = parts2;
-  BgemmArgs a{};
-  a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.K = K; a.lda = K; a.ldb = K; a.ldc = N;
-  a.sa = (long)M_alloc * K; a.sb = (long)N * K; a.sc = (long)M_alloc * N; a.batch = batch;
-  a.tiles_n = N / 128; a.tiles_m = (M + 127) / 128; a.splits = 1; a.cps = K / 32; a.sc_split = 0;
-  BgemmArgs b{};
-  const int Tp = T2 / P;
-  b.A = A2; b.B = B2; b.C = C2parts; b.M = M2; b.N = N2; b.K = Tp; b.lda = M2; b.ldb = N2; b.ldc = N2;
-  b.sa = (long)Tp * M2; b.sb = (long)Tp * N2; b.sc = (long)M2 * N2; b.batch = batch2 * P;
-  b.tiles_n = N2 / 128; b.tiles_m = (M2 + 127) / 128; b.splits = P; b.cps = Tp / 32; b.sc_split = P > 1 ? (long)batch2 * M2 * N2 : 0;
-  static const int skip_on = [] { const char* e = getenv("HIFIHR_GEMM_TN_SKIP"); return e ? atoi(e) : 1; }();
-  b.k_valid = (skip_on && T2_valid > 0 && T2_valid < T2) ? T2_valid : 0;
-  const int T2w = b.k_valid > 0 ? (b.k_valid + 3) / 4 * 4 : T2;          // rows whose k-steps run (the split of the CUs follows the work)
-  static const int wnt = [] { const char* e = getenv("HIFIHR_GEMM_PAIR_NT_WEIGHT"); const int v = e ? atoi(e) : 100; return v > 0 ? v : 100; }();
-  const double fa = 2.0 * batch * (double)M * N * K * (wnt / 100.0), fb = 2.0 * batch2 * (double)M2 * N2 * T2w;
-  const int cus = gemm_cus();
-  int ga = (int)(cus * fa / (fa + fb) + 0.5);
+  const int T2w = (e.tn_skip && T2_valid > 0 && T2_valid < T2) ? (T2_valid + 3) / 4 * 4 : T2;      // rows whose k-steps run (the split of the CUs follows the work)
+  const double fa = 2.0 * batch * (double)M * N * K * (e.pair_nt_weight / 100.0), fb = 2.0 * batch2 * (double)M2 * N2 * T2w;
+  int ga = (int)(e.cus * fa / (fa + fb) + 0.5);
   if (ga < 8) ga = 8;
-  if (ga > cus - 8) ga = cus - 8;
-  int gb = cus - ga;
-  const long total_a = (long)batch * a.tiles_n * M;
-  long per_a = (total_a + ga - 1) / ga;
-  if (per_a < 16) per_a = 16;
-  ga = (int)((total_a + per_a - 1) / per_a);
-  const long total_b = (long)b.batch * b.tiles_n * (M2 / 16);
-  long per_b = (total_b + gb - 1) / gb;
-  if (per_b < 4) per_b = 4;
-  gb = (int)((total_b + per_b - 1) / per_b);
-  tn_coherent(b, gb);
+  if (ga > e.cus - 8) ga = e.cus - 8;
+  long per_a, per_b;
+  const int gb = tn_shares(M2, N2, batch2 * parts2, e.cus - ga, &per_b);
+  ga = nt_shares(M, N, batch, ga, &per_a);
+  const BgemmArgs a = nt_args(nt, A, B, C), b = tn_rows_args(e, A2, B2, C2parts, M2, N2, T2, batch2, parts2, T2_valid, gb);
   hipLaunchKernelGGL(bgemm_nt_tn_pair_kernel, dim3(ga + gb), dim3(512), 0, st, a, per_a, ga, b, per_b);
   return hipGetLastError();
 }
@@ -2012,16 +2016,10 @@ extern "C" int hifihr_probe_split_bf16(const float* x, void* out, long n, void* 
 // c[b][M][N] = a[b][M][K] . b[b][N][K]^T on the split images (same byte sizes and strides as the f32 operands); N % 128 == 0, K % 64 == 0
 extern "C" int hifihr_probe_bgemm_nt_bf16x3(const void* A, const void* B, float* C, int M, int N, int K, int batch, void* stream) {
   if (N % 128 != 0 || K % 64 != 0 || M <= 0 || batch <= 0) return -1;
-  hifihr::BgemmArgs a{};
-  a.A = reinterpret_cast<const float*>(A); a.B = reinterpret_cast<const float*>(B); a.C = C; a.M = M; a.N = N; a.K = K; a.lda = K; a.ldb = K; a.ldc = N;
-  a.sa = (long)M * K; a.sb = (long)N * K; a.sc = (long)M * N; a.batch = batch;
-  a.tiles_n = N / 128; a.tiles_m = (M + 127) / 128; a.splits = 1; a.cps = K / 32; a.sc_split = 0;
-  const long total = (long)batch * a.tiles_n * M;
-  const int cus = hifihr::gemm_cus();
-  long per = (total + cus - 1) / cus;
-  if (per < 16) per = 16;
-  const int G = (int)((total + per - 1) / per);
-  hipLaunchKernelGGL(hifihr::bgemm_nt_rows_bf16x3_kernel, dim3(G), dim3(512), 0, (hipStream_t)stream, a, per);
+  const hifihr::NtPlan p = hifihr::plan_nt(M, 0, N, K, batch, false);      // (the plain row-share form's arguments and shares)
+  if (!p.ok || p.kernel != hifihr::NtKernel::rows) return -1;
+  const hifihr::BgemmArgs a = hifihr::nt_args(p, reinterpret_cast<const float*>(A), reinterpret_cast<const float*>(B), C);
+  hipLaunchKernelGGL(hifihr::bgemm_nt_rows_bf16x3_kernel, dim3(p.G), dim3(512), 0, (hipStream_t)stream, a, p.per);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 #endif

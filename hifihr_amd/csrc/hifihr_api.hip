@@ -459,17 +459,9 @@ int hifihr_conv2d_fwd(const float* x, const float* w, const float* bias, int act
 int hifihr_conv2d_describe(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dgrad, char* out, int cap) {
   if (!out || cap < 24 || !conv_dims_ok(N, H, W, C, K, R, S, stride, pad)) return fail(HIFIHR_EINVAL, "hifihr_conv2d_describe: bad argument");
   const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
-  const hifihr::ConvGeom g = dgrad == 1 ? hifihr::ConvGeom{N, OH, OW, K, H, W, C, R, S, stride, pad, 1} : hifihr::ConvGeom{N, H, W, C, OH, OW, K, R, S, stride, pad, 0};
-  if (hifihr::conv_is_gemm(g)) {          // 1x1 / stride 1: the GEMM kernels (the weight gradient needs the caller's workspace for that)
-    const long M = (long)N * OH * OW;
-    const bool wg = hifihr::conv_wgrad_workspace_bytes(g) > 0;      // (a 1x1 shape has no other slab kernel)
-    if (dgrad == 2 && wg) hifihr::bgemm_describe_batch(1, K, C, (int)M, 1, out, cap);
-    else if (dgrad != 2) hifihr::bgemm_describe_batch(0, (int)M, g.OC, g.IC, 1, out, cap);
-    if (dgrad != 2 || wg) return HIFIHR_OK;
-  }
-  if (dgrad == 2) snprintf(out, cap, "%s", hifihr::conv_halo_wgrad_supported(g) ? "conv_halo_wgrad_kernel" : hifihr::conv_stem_wgrad_supported(g) ? "conv_stem_wgrad_kernel" : "conv_wgrad_kernel");
-  else snprintf(out, cap, "%s", hifihr::conv_halo_supported(g, nullptr) ? "conv_halo_kernel" : hifihr::conv_stem_supported(g, nullptr) ? "conv_stem_kernel" :
-                (dgrad == 0 && hifihr::conv_rows_supported(g, nullptr)) ? "bgemm_nt_rows_kernel<2>" : "conv_igemm_kernel");      // (strided forward: the gathering row-share GEMM)
+  if (dgrad == 1) hifihr::conv_describe(hifihr::ConvGeom{N, OH, OW, K, H, W, C, R, S, stride, pad, 1}, out, cap);
+  else if (dgrad == 2) hifihr::conv_wgrad_describe(hifihr::ConvGeom{N, H, W, C, OH, OW, K, R, S, stride, pad, 0}, out, cap);
+  else hifihr::conv_describe(hifihr::ConvGeom{N, H, W, C, OH, OW, K, R, S, stride, pad, 0}, out, cap);
   return HIFIHR_OK;
 }
 
@@ -1267,8 +1259,7 @@ int hifihr_wino_gemm_m(const float* V, const float* U, float* M, int N, int H, i
   if (!V || !U || !M || T4 <= 0 || T4 >= (1L << 30) || !hifihr::bgemm_nt_supported((int)T4, K, C))
     return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: bad argument (F(4x4, 3x3) needs C % 32 == 0, K % 64 == 0)");
   const long Tr = hifihr::wino4_tiles_real(N, H, W);       // mosaic tiles: the rows behind the last mosaic are padding (zeros in V, unread in M)
-  if (Tr < T4) HIP_TRY(hifihr::launch_bgemm_nt(V, U, M, (int)Tr, K, C, 36, ws, ws_bytes, (hipStream_t)stream, nullptr, (int)T4));
-  else HIP_TRY(hifihr::launch_bgemm_nt(V, U, M, (int)T4, K, C, 36, ws, ws_bytes, (hipStream_t)stream));
+  HIP_TRY(hifihr::launch_bgemm_nt(V, U, M, (int)(Tr < T4 ? Tr : T4), K, C, 36, ws, ws_bytes, (hipStream_t)stream, nullptr, (int)T4));
   return HIFIHR_OK;
 }
 
@@ -1291,8 +1282,7 @@ int hifihr_wino4_bwd_gemm_pair(const float* V2, const float* U2, float* M2, cons
   if (e == hipSuccess) return HIFIHR_OK;
   if (e != hipErrorNotSupported) HIP_TRY(e);
   // not a pair of row-share products: the two launches of hifihr_wino_gemm_m (with C and K exchanged) / hifihr_wino_wgrad_gemm_parts_m
-  if (Tr < T4) HIP_TRY(hifihr::launch_bgemm_nt(V2, U2, M2, (int)Tr, C, K, 36, nullptr, 0, (hipStream_t)stream, nullptr, (int)T4));
-  else HIP_TRY(hifihr::launch_bgemm_nt(V2, U2, M2, (int)T4, C, K, 36, nullptr, 0, (hipStream_t)stream));
+  HIP_TRY(hifihr::launch_bgemm_nt(V2, U2, M2, (int)(Tr < T4 ? Tr : T4), C, K, 36, nullptr, 0, (hipStream_t)stream, nullptr, (int)T4));
   HIP_TRY(hifihr::launch_bgemm_tn(Yt, Vx, dU_parts, K, C, (int)T4, 36, parts, (hipStream_t)stream, (int)(Tr < T4 ? Tr : T4)));
   return HIFIHR_OK;
 }

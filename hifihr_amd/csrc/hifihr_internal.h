@@ -9,6 +9,18 @@
 
 namespace hifihr {
 
+// compute units of the current device: the one device query behind every grid that is sized by the chip (256 while it cannot be asked;
+// the query is repeated until it succeeds)
+inline int device_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+  }
+  return cus > 0 ? cus : 256;
+}
+
 constexpr int kNVP = 800;   // padded vertex count of the SoA MANO tables (rows are 16-byte aligned)
 
 // Device-resident MANO tables, structure-of-arrays over the vertex index so that a wave reads 256
@@ -106,6 +118,10 @@ struct ConvGeom {
 hipError_t launch_conv_igemm(const ConvGeom& g, const float* src, const float* wgt, const float* bias, float* dst, float* stats,
                              void* sk_ws, size_t sk_ws_bytes, hipStream_t st);
 size_t conv_sk_workspace_bytes(const ConvGeom& g);
+// the kernel a convolution runs on, as rocprof names it (csrc/conv.hip: plan_conv / plan_wgrad): forward or backward-data (g.dgrad) without
+// bias, activation and statistics; the weight gradient of the forward geometry g -- both with the workspace their queries ask for
+void conv_describe(const ConvGeom& g, char* out, int cap);
+void conv_wgrad_describe(const ConvGeom& g, char* out, int cap);
 bool conv_wgrad_plus1x1_supported(const ConvGeom& g);
 hipError_t launch_conv_wgrad_plus1x1(const ConvGeom& g, const float* x, const float* dy, float* dw, const float* dy2, float* dw2, hipStream_t st);
 // 3x3 / stride 1 / 64 -> 64 channels with the input halo staged once per tile (csrc/conv_halo.hip); forward (+ BN statistics) and dgrad
@@ -425,6 +441,21 @@ bool conv_rows_pair_supported(const ConvGeom& g1, const ConvGeom& g2);
 hipError_t launch_conv_rows_pair(const ConvGeom& g1, const float* src, const float* w1, float* y1, float* stats1, const ConvGeom& g2, const float* w2,
                                  float* y2, float* stats2, const float* zeros, hipStream_t st);
 bool bgemm_nt_ragged_supported(int M, int N, int K);   // bgemm_nt_rows_kernel<true>: N % 4 == 0, K % 4 == 0, N not a multiple of 128 or K not of 32
+// Which kernel an NT product runs on, its grid and the workspace it wants: decided once, in plan_nt (csrc/gemm.hip), and read by the launch,
+// bgemm_describe, the workspace query and the plan of a 1x1 convolution (csrc/conv.hip)
+enum class NtKernel { rows, rows_ragged, sk, ws, tile };      // bgemm_nt_rows_kernel<0>, <1>, bgemm_nt_sk_kernel, bgemm_ws_kernel, bgemm_nt_kernel
+struct NtPlan {
+  bool ok;                      // false: the launch answers hipErrorInvalidValue
+  NtKernel kernel;
+  int M, M_alloc, N, K, batch;  // M rows of each problem are computed; the problems are M_alloc >= M rows apart
+  int bm, bn, loaders;          // tile and loader waves of the per-tile kernels
+  int G;                        // persistent kernels: workgroups ...
+  long per;                     // ... and the rows of a row-share workgroup
+  size_t ws_bytes;              // sk: the workspace; without it the launch runs the same tile on bgemm_ws_kernel
+};
+NtPlan plan_nt(int M, int M_alloc, int N, int K, int batch, bool stats);      // M_alloc <= M: the problems are M rows apart
+void describe_nt(const NtPlan& p, char* out, int cap);
+hipError_t launch_bgemm_nt_plan(const NtPlan& p, const float* A, const float* B, float* C, void* ws, size_t ws_bytes, hipStream_t st, float* stats_or_null);
 hipError_t launch_bgemm_nt(const float* A, const float* B, float* C, int M, int N, int K, int batch, void* ws, size_t ws_bytes, hipStream_t st,
                            float* stats_or_null = nullptr, int M_alloc = 0);      // stats: only with N % 128 == 0 and batch == 1 (else hipErrorInvalidValue)
 int bgemm_tn_parts(int M, int N, int T, int batch);

@@ -1025,12 +1025,7 @@ hipError_t launch_render_fwd(const RenderDev& r, const float* verts, const float
   float4* frec = face_records(r, B, ws);
   const TexUvDev td = uv != nullptr ? TexUvDev{uv->faces_uvs, uv->verts_uvs, uv->maps, nullptr, uv->TH, uv->TW} : TexUvDev{};
   if (f3) {
-    static const int cus = [] {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                 ? prop.multiProcessorCount : 256;
-    }();
+    const int cus = device_cus();
     static const int per_cu = [] { const char* e = getenv("HIFIHR_RENDER_WGS"); const int v = e ? atoi(e) : 16; return v > 0 ? v : 16; }();
     const dim3 grid3((unsigned)(cus * per_cu));
     static const int cap_forced = [] { const char* e = getenv("HIFIHR_RENDER_CAP"); return e ? atoi(e) : 0; }();

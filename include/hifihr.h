@@ -506,9 +506,13 @@ typedef struct hifihr_prep_job {
 } hifihr_prep_job;
 int hifihr_weight_prep(const hifihr_prep_job* jobs_d, int njobs, int blocks_per_job, void* stream);
 
-/* Name of the kernel a bias-free convolution of this shape runs on, as a profiler lists it: direction 0 forward, 1 backward-data
- * ("conv_halo_kernel": 3x3 / stride 1 / 64 -> 64 channels with the width a multiple of 14, csrc/conv_halo.hip; else
- * "conv_igemm_kernel"), 2 backward-weight ("conv_halo_wgrad_kernel" / "conv_wgrad_kernel").  Measurement only. */
+/* Name of the kernel a convolution of this shape runs on, as a profiler lists it: direction 0 forward, 1 backward-data (e.g.
+ * "conv_halo_kernel", "bgemm_nt_rows_kernel<0>", "conv3x3_oc4_kernel", "conv_igemm_kernel"), 2 backward-weight (e.g.
+ * "conv_halo_wgrad_kernel", "bgemm_tn_rows_kernel", "conv_wgrad_kernel").  The name comes from the same plan the launch reads
+ * (csrc/conv.hip plan_conv / plan_wgrad).  This entry has no bias, activation, statistics or workspace arguments: it describes the
+ * launch a caller makes with bias = stats = NULL, no activation, the workspace that hifihr_conv2d_workspace_bytes /
+ * hifihr_conv2d_wgrad_workspace_bytes ask for, and the zero page present (i.e. not the first use inside a stream capture).
+ * Measurement only. */
 int hifihr_conv2d_describe(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int direction, char* out, int cap);
 
 /* conv2d_fwd that also accumulates the per-channel sum and sum of squares of y into stats_d (hifihr_bn_stats_floats(K)

@@ -58,6 +58,7 @@ void syncthreads();
 uint32_t wave_exchange(uint32_t v, int src_lane);                 // value of src_lane (or own if out of range)
 unsigned long long wave_ballot(bool p);
 void launch(dim3 grid, dim3 block, size_t smem, const std::function<void()>& body);
+void note_launch(const char* kernel);                             // the launch log (hostsim_launch_log): the kernel as the launch site spells it
 int lane_id();
 void wave_gather2(float a, float b, float* A64, float* B64);      // every lane's (a, b), lane-indexed
 void yield_now();                                                 // spin loops on another workgroup's flag: let the OS run it
@@ -233,4 +234,4 @@ static inline hs_floatx4 __builtin_amdgcn_mfma_f32_16x16x4f32(float a, float b, 
 }
 
 #define hipLaunchKernelGGL(kernel, grid, block, smem, stream, ...) \
-  ::hostsim::launch((grid), (block), (smem), [=]() { kernel(__VA_ARGS__); })
+  (::hostsim::note_launch(#kernel), ::hostsim::launch((grid), (block), (smem), [=]() { kernel(__VA_ARGS__); }))

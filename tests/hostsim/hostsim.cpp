@@ -5,6 +5,8 @@
 
 #include <atomic>
 #include <cstdio>
+#include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -194,7 +196,31 @@ void launch(dim3 grid, dim3 block, size_t smem, const std::function<void()>& bod
   }
 }
 
+// The launch log: one line per hipLaunchKernelGGL, the kernel as its launch site spells it (template arguments symbolic where the site is
+// itself a template), without the parentheses that protect the commas of a template argument list from the macro.
+// Nothing is recorded before the first hostsim_launch_log() call: a process that never reads the log keeps none.
+static std::mutex log_mu;
+static bool log_on = false;
+static std::string launch_log, launch_log_out;
+void note_launch(const char* kernel) {
+  std::string k(kernel);
+  if (k.size() >= 2 && k.front() == '(' && k.back() == ')') k = k.substr(1, k.size() - 2);
+  std::lock_guard<std::mutex> lock(log_mu);
+  if (!log_on) return;
+  launch_log += k;
+  launch_log += '\n';
+}
+
 }  // namespace hostsim
+
+// the kernels launched since the last call, one per line; the log is cleared (the pointer stays valid until the next call)
+extern "C" const char* hostsim_launch_log(void) {
+  std::lock_guard<std::mutex> lock(hostsim::log_mu);
+  hostsim::log_on = true;
+  hostsim::launch_log_out.swap(hostsim::launch_log);
+  hostsim::launch_log.clear();
+  return hostsim::launch_log_out.c_str();
+}
 
 // The RCCL wrapper (csrc/comm.hip) has no kernels and is not emulated: its entry points exist so that the binding loads, and fail.
 extern "C" {

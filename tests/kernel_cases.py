@@ -28,6 +28,14 @@ def build_hostsim() -> HifihrLib:
     return HifihrLib(HOSTSIM_LIB)
 
 
+def launch_log(lib):
+    """The kernels the emulator library launched since the last call, as their launch sites spell them (tests/hostsim/hostsim.cpp:
+    template arguments are symbolic where the launch site is itself a template); the log is cleared."""
+    import ctypes
+    lib.c.hostsim_launch_log.restype = ctypes.c_char_p
+    return lib.c.hostsim_launch_log().decode().splitlines()
+
+
 def _dev(x, device):
     return torch.as_tensor(x).to(device).contiguous()
 

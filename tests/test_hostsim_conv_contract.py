@@ -3,6 +3,8 @@ schedule, the three backward-data forms, backward-weight with its slab form, the
 3-channel stem gradient) on a fixed list of geometries -- square and non-square filters, strides 1-4, every pad below the filter and some at
 or above it, channel counts that are and are not multiples of 16.  An entry either refuses a geometry (HIFIHR_EINVAL, output untouched) or
 matches float64 autograd (tests/kernel_cases.py conv_contract_case).  The GPU half runs the same list in tests/test_gpu_conv.py."""
+import re
+
 import pytest
 
 import kernel_cases as kc
@@ -105,14 +107,12 @@ PAIR_GEOMS = [
 
 # the kernels hifihr_conv2d_describe can name (directions 0, 1, 2) that the list must keep reaching
 DESCRIBED = {"conv_halo_kernel", "conv_stem_kernel", "bgemm_nt_rows_kernel<2>", "conv_igemm_kernel", "conv_halo_wgrad_kernel",
-             "conv_stem_wgrad_kernel", "conv_wgrad_kernel", "bgemm_nt_rows_kernel<0>", "bgemm_nt_rows_kernel<1>"}
+             "conv_stem_wgrad_kernel", "conv_wgrad_kernel", "bgemm_nt_rows_kernel<0>", "bgemm_nt_rows_kernel<1>", "conv3x3_oc4_kernel",
+             "conv3x3_oc4_tile_kernel"}
 
-
-def _reaches_oc4(N, H, W, C, K, R, S, stride, pad, dgrad):
-    """conv3x3_oc4_kernel (csrc/conv.hip conv_oc4_supported): 3x3 / stride 1 / pad 1 onto 4 channels from 32 or 64 (describe names the
-    implicit-GEMM kernel for it)."""
-    oc, ic = (C, K) if dgrad else (K, C)
-    return (R, S, stride, pad) == (3, 3, 1, 1) and oc == 4 and ic in (32, 64)
+# kernels that run beside the one hifihr_conv2d_describe names: the filter transpose of the plain backward-data entry, the sums over the
+# slabs of a weight gradient
+HELPER_KERNELS = {"weight_transpose_kernel", "slab_sum_acc_kernel", "conv_halo_wgrad_reduce_kernel", "conv_stem_wgrad_reduce_kernel"}
 
 
 def dispatch_coverage(lib, geoms):
@@ -169,12 +169,42 @@ def test_fwd_bnstats_pair_on_every_pair(hostsim_lib, monkeypatch, pair):
     assert accepted == (pair[4] == 2 and pair[3] % 32 == 0 and pair[5] % 128 == 0 and pair[8] % 128 == 0 and {pair[6], pair[9]} <= {1, 3})
 
 
+@pytest.mark.parametrize("geo", CONTRACT_GEOMS, ids=lambda g: "x".join(map(str, g)))
+def test_describe_names_the_kernel_that_runs(hostsim_lib, geo):
+    """hifihr_conv2d_describe against the emulator's launch log: every plain entry that accepts the geometry (forward without bias,
+    backward-data, backward-weight, each with the workspace its query asks for) launches exactly the kernel describe names, helper kernels
+    aside.  Names are compared up to the template arguments (the log spells those as the launch site does)."""
+    import torch
+    lib = hostsim_lib
+    N, H, W, C, K, R, S, stride, pad = geo
+    OH, OW = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
+    x, w, gy = torch.ones(N, H, W, C), torch.ones(K, R, S, C), torch.ones(N, OH, OW, K)
+    ws_of = lambda nbytes: torch.zeros((nbytes + 3) // 4) if nbytes else None
+    # (a logged template argument list without an identifier is literal: bgemm_nt_rows_kernel<0> / <1> / <2> are then told apart)
+    literal = lambda name: "<" not in name or not re.search(r"[A-Za-z_]", name.split("<", 1)[1].replace("true", "").replace("false", ""))
+    base = lambda name: name.split("<")[0]
+    expect = kc.conv_contract_expect(*geo)
+    calls = (("fwd", 0, lambda: lib.conv2d_fwd(x, w, None, torch.empty(N, OH, OW, K), *geo, ws=ws_of(lib.conv2d_workspace_bytes(*geo, False)))),
+             ("dgrad", 1, lambda: lib.conv2d_bwd_data(gy, w, torch.empty(N, H, W, C), torch.empty(K * R * S * C), *geo,
+                                                      ws=ws_of(lib.conv2d_workspace_bytes(*geo, True)))),
+             ("wgrad", 2, lambda: lib.conv2d_bwd_weight(x, gy, torch.zeros(K, R, S, C), *geo, ws=ws_of(lib.conv2d_wgrad_workspace_bytes(*geo)))))
+    for entry, direction, call in calls:
+        if not expect[entry]:
+            continue
+        kc.launch_log(lib)
+        call()
+        ran = [k for k in kc.launch_log(lib) if base(k) not in HELPER_KERNELS]
+        named = lib.conv2d_describe(*geo, direction)
+        assert [base(k) for k in ran] == [base(named)], f"{entry} {geo}: describe names {named}, the launch log shows {ran}"
+        if literal(ran[0]) and "<" in named:
+            assert ran[0].replace(" ", "") == named.replace(" ", ""), f"{entry} {geo}: describe names {named}, the launch log shows {ran}"
+
+
 def test_the_list_reaches_every_dispatch_path(hostsim_lib):
     """A geometry edit that stops reaching a kernel fails here instead of shrinking the coverage quietly."""
     names = dispatch_coverage(hostsim_lib, CONTRACT_GEOMS)
     assert DESCRIBED <= names, f"no geometry reaches {sorted(DESCRIBED - names)}"
     assert any(n.startswith("bgemm_tn") for n in names), "no 1x1 weight gradient on the TN GEMM slabs"
-    assert any(_reaches_oc4(*g, dgrad=False) for g in CONTRACT_GEOMS) and any(_reaches_oc4(*g, dgrad=True) for g in CONTRACT_GEOMS)
     # and what the entries are asked about: both answers of every predicate occur in the list
     lib = hostsim_lib
     for pred in (lib.conv2d_bwd_data_pre_plus1x1_supported, lib.conv2d_bwd_weight_plus1x1_supported):

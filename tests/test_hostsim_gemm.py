@@ -9,6 +9,12 @@ def hostsim_lib():
     return kc.build_hostsim()
 
 
+def _ran_only(lib, kernel):
+    """the emulator's launch log since the last look shows `kernel` (as bgemm_describe spells it) and nothing else"""
+    log = kc.launch_log(lib)
+    assert log and set(log) == {kernel}, (kernel, log)
+
+
 @pytest.mark.parametrize("M,N,K,batch", [(128, 128, 32, 1), (98, 128, 64, 2), (200, 64, 96, 1), (130, 192, 32, 2), (40, 256, 64, 1)])
 def test_bgemm_nt(hostsim_lib, M, N, K, batch):
     kc.bgemm_case(hostsim_lib, "cpu", M, N, K, batch, seed=M + N)
@@ -26,11 +32,19 @@ def test_bgemm_wave_specialised_forms(hostsim_lib, ws, monkeypatch):
     monkeypatch.setenv("HIFIHR_GEMM_NT_TILE", "128128")
     monkeypatch.setenv("HIFIHR_GEMM_TN_TILE", "128128")
     monkeypatch.setenv("HIFIHR_GEMM_WS", str(ws))
-    kc.bgemm_case(hostsim_lib, "cpu", 200, 128, 160, 2, seed=ws)
-    kc.bgemm_case(hostsim_lib, "cpu", 128, 256, 32, 1, seed=ws + 10)
+    nt = "bgemm_nt_kernel<128, 128>" if ws == 0 else f"bgemm_ws_kernel<128, 128, false, {ws}>"
+    tn = "bgemm_tn_kernel<128, 128>" if ws == 0 else f"bgemm_ws_kernel<128, 128, true, {ws}>"
+    kc.launch_log(hostsim_lib)
+    for M, N, K, batch, seed in ((200, 128, 160, 2, ws), (128, 256, 32, 1, ws + 10)):
+        assert hostsim_lib.bgemm_describe(False, M, N, K, batch) == nt
+        kc.bgemm_case(hostsim_lib, "cpu", M, N, K, batch, seed=seed)
+        _ran_only(hostsim_lib, nt)
+    assert hostsim_lib.bgemm_describe(True, 128, 128, 300, 2) == tn
     kc.bgemm_tn_case(hostsim_lib, "cpu", 128, 128, 300, 2, seed=ws + 20)
+    _ran_only(hostsim_lib, tn)
     monkeypatch.setenv("HIFIHR_GEMM_TN_PARTS", "3")
     assert kc.bgemm_tn_case(hostsim_lib, "cpu", 128, 256, 32 * 9 + 5, 1, seed=ws + 30) == 3
+    _ran_only(hostsim_lib, tn)
 
 
 @pytest.mark.parametrize("ws", [2, 4])
@@ -39,12 +53,21 @@ def test_bgemm_persistent_balanced_form(hostsim_lib, ws, monkeypatch):
     between neighbouring workgroups (slab + flag hand-off), ragged M, several problems per batch; the workspace comes back clean."""
     monkeypatch.setenv("HIFIHR_GEMM_NT_TILE", "128128")
     monkeypatch.setenv("HIFIHR_GEMM_WS", str(ws))
-    assert kc.bgemm_case(hostsim_lib, "cpu", 300, 128, 96, 5, seed=ws) > 0          # 15 tiles x 3 chunks over 4 workgroups
-    assert kc.bgemm_case(hostsim_lib, "cpu", 128, 256, 160, 6, seed=ws + 1) > 0     # 12 tiles x 5 chunks
-    assert kc.bgemm_case(hostsim_lib, "cpu", 130, 128, 64, 7, seed=ws + 2) > 0      # 14 tiles x 2 chunks
+    sk, per_tile = f"bgemm_nt_sk_kernel<{ws}>", f"bgemm_ws_kernel<128, 128, false, {ws}>"
+    kc.launch_log(hostsim_lib)
+    for M, N, K, batch, seed in ((300, 128, 96, 5, ws),             # 15 tiles x 3 chunks over 4 workgroups
+                                 (128, 256, 160, 6, ws + 1),        # 12 tiles x 5 chunks
+                                 (130, 128, 64, 7, ws + 2)):        # 14 tiles x 2 chunks
+        assert hostsim_lib.bgemm_describe(False, M, N, K, batch) == sk
+        assert kc.bgemm_case(hostsim_lib, "cpu", M, N, K, batch, seed=seed) > 0
+        _ran_only(hostsim_lib, sk)
+    assert hostsim_lib.bgemm_describe(False, 300, 128, 96, 3) == per_tile
     assert kc.bgemm_case(hostsim_lib, "cpu", 300, 128, 96, 3, seed=ws) == 0         # 9 tiles < 3 rounds: one workgroup per tile
+    _ran_only(hostsim_lib, per_tile)
     monkeypatch.setenv("HIFIHR_GEMM_SK", "0")
+    assert hostsim_lib.bgemm_describe(False, 300, 128, 96, 5) == per_tile
     assert kc.bgemm_case(hostsim_lib, "cpu", 300, 128, 96, 5, seed=ws) == 0         # switched off
+    _ran_only(hostsim_lib, per_tile)
 
 
 @pytest.mark.parametrize("M,N,K,batch", [(300, 256, 96, 3), (50, 128, 32, 5), (129, 384, 64, 2), (17, 128, 160, 9), (1000, 128, 32, 1)])
@@ -53,7 +76,9 @@ def test_bgemm_nt_row_shares(hostsim_lib, M, N, K, batch):
     (problem, column tile, row) space -- shares that end inside a tile (short tiles with 1..8 row blocks), that cross column-tile and
     problem boundaries, and chunk streams that run across tile boundaries."""
     assert hostsim_lib.bgemm_describe(False, M, N, K) .startswith("bgemm_nt_rows_kernel<")
+    kc.launch_log(hostsim_lib)
     assert kc.bgemm_case(hostsim_lib, "cpu", M, N, K, batch, seed=M + K) == 0        # no workspace
+    _ran_only(hostsim_lib, hostsim_lib.bgemm_describe(False, M, N, K, batch))
 
 
 @pytest.mark.parametrize("M,N,T,batch", [(128, 128, 64, 4), (192, 256, 96, 2), (64, 128, 128, 8), (512, 128, 64, 1), (320, 128, 96, 3), (448, 384, 64, 1)])
@@ -61,7 +86,9 @@ def test_bgemm_tn_row_shares(hostsim_lib, M, N, T, batch):
     """bgemm_tn_rows_kernel (N % 128 == 0, M % 64 == 0, T % 32 == 0, at least eight 16-row blocks per CU; hostsim reports 4 CUs): shares that end
     inside a 128-row tile, tails cut into 64 / 32 / 16-row tiles, tiles that cross problem boundaries, complete products in ONE slab."""
     assert hostsim_lib.bgemm_describe(True, M, N, T, batch) == "bgemm_tn_rows_kernel"
+    kc.launch_log(hostsim_lib)
     assert kc.bgemm_tn_case(hostsim_lib, "cpu", M, N, T, batch, seed=M + T) == 1
+    _ran_only(hostsim_lib, "bgemm_tn_rows_kernel")
 
 
 @pytest.mark.parametrize("M,N,T,batch,cus", [(256, 128, 64, 20, 16), (256, 256, 64, 18, 16), (128, 256, 96, 9, 8)])
@@ -73,7 +100,9 @@ def test_bgemm_tn_xcd_coherent_schedule(hostsim_lib, monkeypatch, M, N, T, batch
     import torch
     monkeypatch.setenv("HIFIHR_GEMM_CUS", str(cus))
     assert hostsim_lib.bgemm_describe(True, M, N, T, batch) == "bgemm_tn_rows_kernel"
+    kc.launch_log(hostsim_lib)
     assert kc.bgemm_tn_case(hostsim_lib, "cpu", M, N, T, batch, seed=M + T + batch) == 1
+    _ran_only(hostsim_lib, "bgemm_tn_rows_kernel")
     gen = torch.Generator().manual_seed(5)
     a = torch.randn(batch, T, M, generator=gen); b = torch.randn(batch, T, N, generator=gen)
     c1 = torch.full((1, batch, M, N), 7.0); c0 = torch.full((1, batch, M, N), 7.0)
@@ -107,7 +136,9 @@ def test_row_share_kernels_keep_the_summation_order(hostsim_lib):
         a = torch.randn(batch, M, K, generator=gen); b = torch.randn(batch, N, K, generator=gen)
         assert hostsim_lib.bgemm_describe(False, M, N, K).startswith("bgemm_nt_rows_kernel<")
         c = torch.full((batch, M, N), 7.0)
+        kc.launch_log(hostsim_lib)
         hostsim_lib.bgemm_nt(a, b, c, M, N, K, batch)
+        _ran_only(hostsim_lib, hostsim_lib.bgemm_describe(False, M, N, K, batch))
         an, bn = a.numpy(), b.numpy()
         ref = np.zeros((batch, M, N), np.float32)
         # (the NT body's order inside a 32-deep chunk: half h, component kc of the lanes' 16-byte fragments, lane group g -> k = 16 h + 4 g + kc)
@@ -119,7 +150,9 @@ def test_row_share_kernels_keep_the_summation_order(hostsim_lib):
         a = torch.randn(batch, T, M, generator=gen); b = torch.randn(batch, T, N, generator=gen)
         assert hostsim_lib.bgemm_describe(True, M, N, T, batch) == "bgemm_tn_rows_kernel"
         c = torch.full((1, batch, M, N), 7.0)
+        kc.launch_log(hostsim_lib)
         hostsim_lib.bgemm_tn(a, b, c, M, N, T, batch, 1)
+        _ran_only(hostsim_lib, "bgemm_tn_rows_kernel")
         an, bn = a.numpy(), b.numpy()
         ref = np.zeros((batch, M, N), np.float32)
         for t in range(T):
@@ -135,7 +168,9 @@ def test_row_share_kernels_keep_the_summation_order(hostsim_lib):
     V = torch.randn(36, T4, C, generator=gen); Y = torch.randn(36, T4, K, generator=gen)
     V[:, Tr:] = 0; Y[:, Tr:] = 0
     dU = torch.full((parts, 36, K, C), 7.0)
+    kc.launch_log(hostsim_lib)
     hostsim_lib.wino_wgrad_gemm_parts(V, Y, dU, Nn, H, H, C, K, parts, m=4)
+    _ran_only(hostsim_lib, "bgemm_tn_rows_kernel")
     vn, yn = V.numpy(), Y.numpy()
     ref = np.zeros((36, K, C), np.float32)
     for t in range(Tr):
