@@ -130,6 +130,13 @@ class HifihrLib:
         c.hifihr_conv2d_wgrad_workspace_bytes.restype = c_size_t
         c.hifihr_image_to_nhwc4.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_void_p]
         c.hifihr_image_to_nhwc4_padded.argtypes = [_c_float_p, _c_float_p] + [c_int] * 8 + [c_void_p]
+        c.hifihr_image_scale_to_nhwc4.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, _c_float_p, _c_float_p, c_void_p]
+        c.hifihr_maxpool2d_fwd_notap.argtypes = [_c_float_p] + [c_int] * 7 + [_c_float_p, c_void_p]
+        c.hifihr_lpips_tap_max_channels.argtypes = []
+        c.hifihr_lpips_tap_max_channels.restype = c_int
+        c.hifihr_lpips_tap_partial_floats.argtypes = [c_int]
+        c.hifihr_lpips_tap_partial_floats.restype = c_size_t
+        c.hifihr_lpips_tap.argtypes = [_c_float_p] * 3 + [c_int] * 4 + [_c_float_p, _c_float_p, c_void_p]
         c.hifihr_geom_loss_fwd.argtypes = [_c_float_p] * 6 + [_c_int_p] + [c_int] * 7 + [_c_float_p] * 3 + [c_void_p]
         c.hifihr_geom_loss_bwd.argtypes = [_c_float_p] * 6 + [_c_int_p] * 3 + [c_int] * 7 + [_c_float_p] * 6 + [c_void_p]
         c.hifihr_photo_loss_partial_floats.argtypes = []
@@ -924,6 +931,27 @@ class HifihrLib:
         pl, pr, pt, pb = pad4
         self.check(self.c.hifihr_image_to_nhwc4_padded(_fp(images), _fp(out), B, H, W, pt, pl, pb, pr, int(bool(normalize)),
                                                        _stream_of(images)), "hifihr_image_to_nhwc4_padded")
+
+    # ---- LPIPS (csrc/lpips.hip) -----------------------------------------
+    def image_scale_to_nhwc4(self, images, out, shift3, scale3):
+        """out[B, H, W, 4] = ((images - shift[c]) / scale[c], 0); shift3 / scale3: three Python floats each (the package's ScalingLayer)."""
+        B, _, H, W = images.shape
+        sh, sc = (c_float * 3)(*[float(v) for v in shift3]), (c_float * 3)(*[float(v) for v in scale3])
+        self.check(self.c.hifihr_image_scale_to_nhwc4(_fp(images), _fp(out), B, H, W, sh, sc, _stream_of(images)), "hifihr_image_scale_to_nhwc4")
+
+    def maxpool2d_fwd_notap(self, x, N, H, W, C, k, s, p, y):
+        self.check(self.c.hifihr_maxpool2d_fwd_notap(_fp(x), N, H, W, C, k, s, p, _fp(y), _stream_of(x)), "hifihr_maxpool2d_fwd_notap")
+
+    def lpips_tap_max_channels(self):
+        return int(self.c.hifihr_lpips_tap_max_channels())
+
+    def lpips_tap_partial_floats(self, B):
+        return int(self.c.hifihr_lpips_tap_partial_floats(int(B)))
+
+    def lpips_tap(self, f0, f1, w, B, HW, C, partial, val, accumulate=False):
+        """val[b] (+)= mean over pixels of sum_c w_c (n0_c - n1_c)^2 on two channels-last maps [B][HW][C] (include/hifihr.h)."""
+        self.check(self.c.hifihr_lpips_tap(_fp(f0), _fp(f1), _fp(w), B, HW, C, int(bool(accumulate)), _fp(partial), _fp(val), _stream_of(f0)),
+                   "hifihr_lpips_tap")
 
     # ---- SSIM ----------------------------------------------------------
     def ssim_partial_count(self, planes, H, W):

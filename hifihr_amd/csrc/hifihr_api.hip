@@ -626,6 +626,35 @@ int hifihr_image_to_nhwc4_padded(const float* images, float* out, int B, int H, 
   return HIFIHR_OK;
 }
 
+// ---- LPIPS(net="alex") forward (lpips.hip) ----
+int hifihr_image_scale_to_nhwc4(const float* images, float* out, int B, int H, int W, const float* shift3_host, const float* scale3_host,
+                                void* stream) {
+  if (!images || !out || !shift3_host || !scale3_host || B <= 0 || H <= 0 || W <= 0)
+    return fail(HIFIHR_EINVAL, "hifihr_image_scale_to_nhwc4: bad argument");
+  for (int c = 0; c < 3; ++c)
+    if (!(scale3_host[c] != 0.f)) return fail(HIFIHR_EINVAL, "hifihr_image_scale_to_nhwc4: scale[%d] is zero or NaN", c);
+  HIP_TRY(hifihr::launch_image_scale_to_nhwc4(images, out, B, H, W, shift3_host, scale3_host, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_maxpool2d_fwd_notap(const float* x, int N, int H, int W, int C, int k, int s, int p, float* y, void* stream) {
+  if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C < 4 || C % 4 != 0 || !(k == 3 && s == 2 && p == 0) || H < k || W < k)
+    return fail(HIFIHR_EINVAL, "hifihr_maxpool2d_fwd_notap: bad argument (C % 4 == 0; (k,s,p) = (3,2,0); H, W >= 3)");
+  HIP_TRY(hifihr::launch_maxpool_notap(x, N, H, W, C, k, s, p, y, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_lpips_tap_max_channels(void) { return hifihr::lpips_tap_max_channels(); }
+size_t hifihr_lpips_tap_partial_floats(int B) { return hifihr::lpips_tap_partial_floats(B); }
+
+int hifihr_lpips_tap(const float* f0, const float* f1, const float* w, int B, int HW, int C, int accumulate, float* partial, float* val,
+                     void* stream) {
+  if (!f0 || !f1 || !w || !partial || !val || B <= 0 || B > 65535 || HW <= 0 || C < 4 || C % 4 != 0 || C > hifihr::lpips_tap_max_channels())
+    return fail(HIFIHR_EINVAL, "hifihr_lpips_tap: bad argument (C % 4 == 0, 4 <= C <= %d; B <= 65535)", hifihr::lpips_tap_max_channels());
+  HIP_TRY(hifihr::launch_lpips_tap(f0, f1, w, B, HW, C, accumulate ? 1 : 0, partial, val, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
 int hifihr_ssim_partial_count(int planes, int H, int W) {
   if (planes <= 0 || H <= 0 || W <= 0) return 0;
   const int t = hifihr::ssim_tile_edge();

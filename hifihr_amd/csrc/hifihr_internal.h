@@ -252,6 +252,15 @@ hipError_t launch_weight_transpose(const float* w, float* wt, int K, int RS, int
 hipError_t launch_image_to_nhwc4(const float* img, float* out, int B, int H, int W, int OH, int OW, int pt, int pl, int normalize,
                                  hipStream_t st);
 
+// LPIPS(net="alex") forward (lpips.hip): ScalingLayer + repack, the tapless MaxPool2d(3, 2), one tap of the metric
+hipError_t launch_image_scale_to_nhwc4(const float* img, float* out, int B, int H, int W, const float* shift3, const float* scale3,
+                                       hipStream_t st);
+hipError_t launch_maxpool_notap(const float* x, int N, int H, int W, int C, int k, int s, int p, float* y, hipStream_t st);
+int lpips_tap_max_channels();
+size_t lpips_tap_partial_floats(int B);
+hipError_t launch_lpips_tap(const float* f0, const float* f1, const float* w, int B, int HW, int C, int accumulate, float* partial, float* val,
+                            hipStream_t st);
+
 struct SsimWindow {
   float g[11];      // normalised 1-D gaussian (sigma 1.5), as pytorch_ssim.gaussian builds it
 };

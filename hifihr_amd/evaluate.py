@@ -2,8 +2,9 @@
 MPJPE / MPVPE after Procrustes alignment; utils/train_utils.py:267-290 align_w_scale) with the alignment batched on the
 device (csrc/eval.hip) instead of a per-sample numpy / scipy loop.  SURVEY.md section 8(f) N2.
 
-LPIPS (train_hrnet.py:156) needs AlexNet weights that cannot be downloaded here: reported as None unless the caller
-passes an `lpips_fn`."""
+LPIPS (train_hrnet.py:156-158) is opt-in: `Evaluator(lpips_fn=hifihr_amd.lpips.LPIPS(...))` -- the AlexNet metric on this package's
+kernels, with weights loaded by `load_state_dict_lpips` (train_hrnet.py --lpips_weights) or, without any, seeded ones.  With no
+`lpips_fn` it is reported as None.  Parity with the `lpips` package and with the real weights is unpinned: neither is available here."""
 from __future__ import annotations
 
 import torch

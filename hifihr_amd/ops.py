@@ -2251,6 +2251,47 @@ def image_to_nhwc4(images, pad4=None, normalize=True):
 
 
 # ------------------------------------------------------------------------------------------------
+# LPIPS(net="alex") forward (csrc/lpips.hip; the module is hifihr_amd/lpips.py).  Inference only: no autograd.Function, the
+# caller refuses inputs that require a gradient.
+# ------------------------------------------------------------------------------------------------
+def image_scale_to_nhwc4(images, shift3, scale3, out=None):
+    """(images - shift[c]) / scale[c] + repack: [B,3,H,W] -> logical [B,4,H,W] channels_last (4th channel zero), one launch.
+    out: a channels_last [B,4,H,W] tensor (e.g. one half of a larger batch) to write into."""
+    require_cuda(images)
+    B, _, H, W = images.shape
+    if out is None:
+        out = torch.empty((B, 4, H, W), device=images.device, dtype=torch.float32, memory_format=_CL)
+    assert out.shape == (B, 4, H, W) and out.is_contiguous(memory_format=_CL), (out.shape, out.stride())
+    PROFILE.bracket("image_scale", lambda: get_lib().image_scale_to_nhwc4(images.contiguous(), out, shift3, scale3))
+    return out
+
+
+def maxpool2d_notap(x, k=3, s=2, p=0):
+    """nn.MaxPool2d(3, 2) on channels_last activations for inference: no tap bytes, no backward (hifihr_maxpool2d_fwd_notap)."""
+    require_cuda(x)
+    if x.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("maxpool2d_notap is forward-only")
+    x = x.contiguous(memory_format=_CL)
+    N, C, H, W = x.shape
+    OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    y = torch.empty((N, C, max(OH, 0), max(OW, 0)), device=x.device, memory_format=_CL)
+    PROFILE.bracket("maxpool_fwd", lambda: get_lib().maxpool2d_fwd_notap(x, N, H, W, C, k, s, p, y))
+    return y
+
+
+def lpips_tap(f0, f1, w, val, accumulate):
+    """val[b] (+)= mean_pixels sum_c w_c (n0_c - n1_c)^2, n = f / (|f|_c + 1e-10), on two channels_last maps [B,C,H,W] (the halves of one
+    batch are fine) and the tap's `lin` weights w[C]; two launches (tap + fixed-order finish), deterministic."""
+    require_cuda(f0, f1, w, val)
+    B, C, H, W = f0.shape
+    assert f1.shape == f0.shape and f0.is_contiguous(memory_format=_CL) and f1.is_contiguous(memory_format=_CL) and w.numel() == C
+    lib = get_lib()
+    partial = torch.empty(lib.lpips_tap_partial_floats(B), device=f0.device, dtype=torch.float32)
+    PROFILE.bracket("lpips_tap", lambda: lib.lpips_tap(f0, f1, w, B, H * W, C, partial, val, accumulate))
+    return val
+
+
+# ------------------------------------------------------------------------------------------------
 # fused SSIM
 # ------------------------------------------------------------------------------------------------
 def _ssim_window():

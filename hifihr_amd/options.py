@@ -18,6 +18,7 @@ _DEFAULTS = dict(
     lambda_mrgb=1e-3, lambda_iou=1e-3, lambda_bone_direc=0.1, lambda_bone_direc_3d=0.1, lambda_edge_len=0.1,
     lambda_percep=1e-5, lambda_ssim_tex=0.001, lambda_scale=100.0, lambda_mscale=0.1, lambda_laplacian=0.1,
     ROOT=9, ROOT_NIMBLE=11,
+    lpips_weights=None,    # [path, ...]: AlexNet + lin weights for the evaluation pass's LPIPS (hifihr_amd/lpips.py); None = LPIPS not reported
 )
 
 # lambda values of reference config/FreiHAND/full_rhd_freihand.json, used by the

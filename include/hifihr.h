@@ -665,6 +665,33 @@ int hifihr_image_to_nhwc4_padded(const float* images_d, float* out_d, int B, int
                                  int pad_bottom, int pad_right, int normalize, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * LPIPS(net="alex"), version 0.1, forward only (csrc/lpips.hip).  Replaces `lpips.LPIPS(net="alex")` of the reference's
+ * evaluation pass (built at train_hrnet.py:563, called at :158); the five convolutions of the AlexNet trunk
+ * (torchvision features[0:12]) run on hifihr_conv2d_fwd with act = 1.  hifihr_amd/lpips.py is the caller.
+ *
+ * image_scale_to_nhwc4: the package's ScalingLayer fused with the repack the stem reads (train_hrnet.py:158,563):
+ *   out[B][H][W][4] = ((images[B][3][H][W] - shift[c]) / scale[c], 0); shift3_host / scale3_host are HOST arrays of 3 floats
+ *   (scale != 0).  One launch, true division.
+ * maxpool2d_fwd_notap: nn.MaxPool2d(k, s, p) for inference, (k, s, p) = (3, 2, 0) only (the AlexNet pools, train_hrnet.py:158,563);
+ *   y[N][OH][OW][C], OH = (H - 3)/2 + 1; no winning-tap bytes, no backward.  C % 4 == 0, H, W >= 3.  hifihr_maxpool2d_fwd
+ *   keeps its own set {(3,2,1), (3,1,1), (2,2,0)}.
+ * lpips_tap: one tap of the metric (train_hrnet.py:158,563: normalize_tensor, the squared difference, the tap's `lin` layer
+ *   and spatial_average of the package) on two channels-last maps f0_d, f1_d [B][HW][C] -- e.g. the two halves of one [2B]
+ *   batch -- and the 1x1 `lin` weights w_d[C] (no bias):
+ *     n = f / (sqrt(sum_c f^2) + 1e-10),   val_d[b] = (accumulate ? val_d[b] : 0) + mean_pixels sum_c w_c (n0_c - n1_c)^2.
+ *   Direct form (n0 - n1 per channel, never the expanded sums): identical maps give exactly 0.  Deterministic (fixed-order
+ *   partial sums, no float atomics).  C % 4 == 0, 4 <= C <= hifihr_lpips_tap_max_channels() (512), B <= 65535; anything else
+ *   is HIFIHR_EINVAL with val_d untouched.  partial_d: scratch of hifihr_lpips_tap_partial_floats(B) floats (any contents).
+ * ---------------------------------------------------------------------------------------------- */
+int hifihr_image_scale_to_nhwc4(const float* images_d, float* out_d, int B, int H, int W, const float* shift3_host,
+                                const float* scale3_host, void* stream);
+int hifihr_maxpool2d_fwd_notap(const float* x_d, int N, int H, int W, int C, int k, int s, int p, float* y_d, void* stream);
+int hifihr_lpips_tap_max_channels(void);
+size_t hifihr_lpips_tap_partial_floats(int B);
+int hifihr_lpips_tap(const float* f0_d, const float* f1_d, const float* w_d, int B, int HW, int C, int accumulate, float* partial_d,
+                     float* val_d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused SSIM (11x11 gaussian window sigma 1.5, zero padding, C1 = 0.01^2, C2 = 0.03^2, mean over all elements).
  * Replaces pytorch_ssim.ssim(img1, img2)   reference utils/pytorch_ssim/__init__.py:17-37,65-73
  * (called at reference losses.py:375 for the ssim_tex term) and its autograd w.r.t. img1.

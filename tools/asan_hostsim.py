@@ -106,7 +106,23 @@ def contract():
         del os.environ["HIFIHR_GEMM_CUS"]
 
 
-GROUPS = {"conv": conv, "render": render, "wino": wino, "round5": round5, "round6": round6, "contract": contract}
+def lpips():
+    """The LPIPS entries (csrc/lpips.hip): every (lanes per pixel, float4 per lane) instance of the tap kernel at widths that leave lanes
+    without channels and with a ragged last pass, the tapless pool, the scaling repack, and the two AlexNet convolution geometries."""
+    import lpips_cases as lc
+    for (B, HW, C, same) in [(2, 225, 64, 1), (3, 49, 192, 2), (1, 9, 384, None), (2, 15, 256, 1), (1, 1, 4, None), (2, 5, 100, 1),
+                             (2, 5, 176, 1), (2, 5, 320, 1), (1, 2, 512, None), (1, 64 * 4 * 2 + 3, 256, None)]:
+        lc.tap_case(lib, "cpu", B, HW, C, seed=C + HW, identical_sample=same)
+    lc.tap_rejects_case(lib, "cpu")
+    for (N, H, W, C) in [(2, 15, 15, 64), (1, 7, 9, 8), (1, 3, 3, 4)]:
+        lc.pool_notap_case(lib, "cpu", N, H, W, C, seed=H + C)
+    lc.pool_rejects_case(lib, "cpu")
+    lc.scale_repack_case(lib, "cpu")
+    lc.conv_bias_relu_contract_case(lib, "cpu", 1, 31, 35, 4, 64, 11, 4, 2, seed=11)
+    lc.conv_bias_relu_contract_case(lib, "cpu", 1, 7, 6, 64, 192, 5, 1, 2, seed=5)
+
+
+GROUPS = {"conv": conv, "render": render, "wino": wino, "round5": round5, "round6": round6, "contract": contract, "lpips": lpips}
 for g in (sys.argv[1:] or list(GROUPS)):
     GROUPS[g]()
     print(f"asan: {g} clean", flush=True)

@@ -54,6 +54,10 @@ def parse(argv=None):
     ap.add_argument("--print_freq", type=int, default=50)
     ap.add_argument("--dist_timeout_min", type=float, default=60.0, help="collective timeout of the process group: has to cover rank 0's "
                     "evaluation pass, during which the other ranks wait in a barrier")
+    ap.add_argument("--lpips_weights", nargs="+", default=None, metavar="PATH",
+                    help="report LPIPS(net='alex') beside PSNR / SSIM in the evaluation pass (reference train_hrnet.py:158,563): one or two torch "
+                         "files -- torchvision's alexnet state dict and the lpips package's alex.pth, or the package's full LPIPS state dict "
+                         "(hifihr_amd/lpips.py: load_state_dict_lpips).  Without it LPIPS is not reported.")
     ap.add_argument("--override", default=None, help='JSON object of option overrides, e.g. \'{"total_epochs": 2}\'')
     return ap.parse_args(argv)
 
@@ -71,6 +75,10 @@ def build_args(cli):
     args.state_output = os.path.join(args.base_out_path, "model")       # options/train_options.py:208-220
     args.pred_output = os.path.join(args.base_out_path, "json")         # :214 (the pred.json dumps)
     args.texture_stand_in = 0
+    if cli.lpips_weights:
+        args.lpips_weights = list(cli.lpips_weights)
+    elif isinstance(getattr(args, "lpips_weights", None), str):        # a JSON may name one file
+        args.lpips_weights = [args.lpips_weights]
     if args.hand_model == "nimble" and cli.nimble_layer in ("synthetic", "synthetic-uv"):
         print("[train_hrnet] hand_model 'nimble': NIMBLE-shaped layer on seeded synthetic tables (hifihr_amd/nimble_tables.py); the real "
               "NIMBLE assets are not available (SURVEY.md section 8 A9)")
@@ -221,13 +229,28 @@ def ho3d_eval_cache(cli, frames, device):
     return HO3DDeviceCache(frames["images_u8"], frames["hand_masks_u8"], Ks, xyz, device=device, bboxes=boxes, root_xyz=xyz[:, 0])
 
 
+_LPIPS = {}
+
+
+def make_evaluator(args, device):
+    """Evaluator of the evaluation pass; with --lpips_weights it also reports LPIPS (the module is built and loaded once per device)."""
+    from hifihr_amd.evaluate import Evaluator
+    paths = getattr(args, "lpips_weights", None)
+    if not paths:
+        return Evaluator()
+    key = (str(device), tuple(paths))
+    if key not in _LPIPS:
+        from hifihr_amd.lpips import LPIPS, load_lpips_weights
+        _LPIPS[key] = load_lpips_weights(LPIPS(net="alex"), *paths).to(device)
+    return Evaluator(lpips_fn=_LPIPS[key])
+
+
 def run_evaluation_ho3d(model, cache, args, device, epoch):
     """The reference's HO-3D evaluation pass (train_hrnet.py:55-64 the evaluation queries, :124-136 joints back in the HO-3D order and
     OpenGL axes, :286-293 `pred.json` for the challenge server; texture metrics when rendering): no ground truth exists for this split,
     the product is the dump.  -> (path, n, texture metrics)."""
-    from hifihr_amd.evaluate import Evaluator
     from hifihr_amd.traineval import data_dic
-    ev = Evaluator()
+    ev = make_evaluator(args, device)
     model.eval()
     with torch.no_grad():
         for lo in range(0, cache.n, args.val_batch):
@@ -243,9 +266,8 @@ def run_evaluation_ho3d(model, cache, args, device, epoch):
 
 
 def run_evaluation(model, cache, arrays, args, device):
-    from hifihr_amd.evaluate import Evaluator
     from hifihr_amd.traineval import data_dic
-    ev = Evaluator()
+    ev = make_evaluator(args, device)
     model.eval()
     n = cache.n
     with torch.no_grad():
