@@ -828,9 +828,8 @@ hipError_t launch_bn_act_fwd(const float* x, float* stats, const float* gamma, c
                              float* running_mean, float* running_var, hipStream_t st) {
   if (!bn_c_ok(C)) return hipErrorInvalidValue;
   if (C <= kFuseMaxC) {
-    if (C <= 1024) hipLaunchKernelGGL((bn_act_fwd_kernel<false, 1>), dim3(bn_grid(M, C, true)), dim3(256), 0, st, x, stats, gamma, beta, residual, act, M, C, eps,
-                       momentum, y, save_mean, save_invstd, running_mean, running_var);
-    else hipLaunchKernelGGL((bn_act_fwd_kernel<false, kMaxNG>), dim3(bn_grid(M, C, true)), dim3(256), 0, st, x, stats, gamma, beta, residual, act, M, C, eps,
+    // (C <= kFuseMaxC <= 1024: one channel group per thread; the fused form has no kMaxNG instantiation)
+    hipLaunchKernelGGL((bn_act_fwd_kernel<false, 1>), dim3(bn_grid(M, C, true)), dim3(256), 0, st, x, stats, gamma, beta, residual, act, M, C, eps,
                        momentum, y, save_mean, save_invstd, running_mean, running_var);
   } else {
     hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3((C + 255) / 256), dim3(256), 0, st, stats, M, C, eps, momentum, save_mean,
@@ -872,9 +871,7 @@ hipError_t launch_bn_act_bwd(const float* dy, const float* y, const float* x, co
   else hipLaunchKernelGGL((bn_bwd_reduce_kernel<kMaxNG>), dim3(bn_reduce_grid(M, C)), dim3(256), 0, st, dy, y, x, save_mean, save_invstd, gamma, beta, act,
                      M, C, red);
   if (C <= kFuseMaxC) {
-    if (C <= 1024) hipLaunchKernelGGL((bn_bwd_apply_kernel<false, 1>), dim3(bn_grid(M, C, true)), dim3(256), 0, st, dy, y, x, save_mean, save_invstd, gamma, beta,
-                       red, act, M, C, dx, dres, dgamma_acc, dbeta_acc);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<false, kMaxNG>), dim3(bn_grid(M, C, true)), dim3(256), 0, st, dy, y, x, save_mean, save_invstd, gamma, beta,
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<false, 1>), dim3(bn_grid(M, C, true)), dim3(256), 0, st, dy, y, x, save_mean, save_invstd, gamma, beta,
                        red, act, M, C, dx, dres, dgamma_acc, dbeta_acc);
   } else {
     hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3((C + 255) / 256), dim3(256), 0, st, red, C, dgamma_acc, dbeta_acc);
@@ -891,9 +888,7 @@ hipError_t launch_bn_act_bwd(const float* dy, const float* y, const float* x, co
 hipError_t launch_bn_bwd_apply(const float* g, const float* x, const float* save_mean, const float* save_invstd, const float* gamma, long M,
                                int C, float* red, float* dx, float* dgamma_acc, float* dbeta_acc, hipStream_t st) {
   if (!bn_c_ok(C) || C > kFuseMaxC) return hipErrorInvalidValue;
-  if (C <= 1024) hipLaunchKernelGGL((bn_bwd_apply_kernel<false, 1>), dim3(bn_grid(M, C, true)), dim3(256), 0, st, g, (const float*)nullptr, x, save_mean, save_invstd,
-                     gamma, (const float*)nullptr, red, 0, M, C, dx, (float*)nullptr, dgamma_acc, dbeta_acc);
-  else hipLaunchKernelGGL((bn_bwd_apply_kernel<false, kMaxNG>), dim3(bn_grid(M, C, true)), dim3(256), 0, st, g, (const float*)nullptr, x, save_mean, save_invstd,
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<false, 1>), dim3(bn_grid(M, C, true)), dim3(256), 0, st, g, (const float*)nullptr, x, save_mean, save_invstd,
                      gamma, (const float*)nullptr, red, 0, M, C, dx, (float*)nullptr, dgamma_acc, dbeta_acc);
   return hipGetLastError();
 }

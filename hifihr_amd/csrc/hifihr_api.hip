@@ -773,13 +773,22 @@ int hifihr_bn_relu_maxpool_bwd_y(const float* gy, const float* pooled, const uns
   return HIFIHR_OK;
 }
 
+// The output size a depthwise entry accepts along one axis (include/hifihr.h): the implied bottom / right padding
+// pb = (O - 1) * stride + K - I - pad is at most K - 1 (no window lies in the padding alone) and at least -(stride - 1)
+// (the rows a floor division leaves unused; anything below would crop rows that a whole window still covers).
+static int dw_axis_ok(int I, int O, int K, int stride, int pad) {
+  if (I <= 0 || O <= 0 || pad < 0 || pad > K - 1) return 0;
+  const long pb = (long)(O - 1) * stride + K - I - pad;
+  return pb <= K - 1 && pb >= -(long)(stride - 1);
+}
 static int dw_ok(int N, int H, int W, int C, int OH, int OW, int K, int stride, int pt, int pl) {
-  return N > 0 && H > 0 && W > 0 && C >= 4 && C % 4 == 0 && OH > 0 && OW > 0 && (K == 3 || K == 5) && (stride == 1 || stride == 2) && pt >= 0 && pl >= 0;
+  return N > 0 && C >= 4 && C % 4 == 0 && (K == 3 || K == 5) && (stride == 1 || stride == 2) && dw_axis_ok(H, OH, K, stride, pt) &&
+         dw_axis_ok(W, OW, K, stride, pl);
 }
 
 int hifihr_dwconv2d_fwd(const float* x, const float* w, float* y, float* stats, int N, int H, int W, int C, int OH, int OW, int K,
                         int stride, int pad_top, int pad_left, void* stream) {
-  if (!x || !w || !y || !dw_ok(N, H, W, C, OH, OW, K, stride, pad_top, pad_left)) return fail(HIFIHR_EINVAL, "hifihr_dwconv2d_fwd: bad argument");
+  if (!x || !w || !y || !dw_ok(N, H, W, C, OH, OW, K, stride, pad_top, pad_left)) return fail(HIFIHR_EINVAL, "hifihr_dwconv2d_fwd: bad argument (C % 4 == 0; K 3 or 5; stride 1 or 2; 0 <= pad <= K - 1; -(stride - 1) <= implied bottom / right pad <= K - 1)");
   hifihr::DwGeom g{N, H, W, C, OH, OW, K, stride, pad_top, pad_left};
   HIP_TRY(hifihr::launch_dwconv_fwd(g, x, w, y, stats, (hipStream_t)stream));
   return HIFIHR_OK;
@@ -789,7 +798,7 @@ int hifihr_dwconv2d_fwd_bnswish(const float* x, const float* mean, const float* 
                                 const float* w, float* y, float* stats, int N, int H, int W, int C, int OH, int OW, int K, int stride,
                                 int pad_top, int pad_left, void* stream) {
   if (!x || !mean || !invstd || !gamma || !beta || !w || !y || !dw_ok(N, H, W, C, OH, OW, K, stride, pad_top, pad_left))
-    return fail(HIFIHR_EINVAL, "hifihr_dwconv2d_fwd_bnswish: bad argument");
+    return fail(HIFIHR_EINVAL, "hifihr_dwconv2d_fwd_bnswish: bad argument (C % 4 == 0; K 3 or 5; stride 1 or 2; 0 <= pad <= K - 1; -(stride - 1) <= implied bottom / right pad <= K - 1)");
   hifihr::DwGeom g{N, H, W, C, OH, OW, K, stride, pad_top, pad_left};
   HIP_TRY(hifihr::launch_dwconv_fwd(g, x, w, y, stats, (hipStream_t)stream, mean, invstd, gamma, beta));
   return HIFIHR_OK;
@@ -799,7 +808,7 @@ int hifihr_dwconv2d_bwd_weight_bnswish(const float* x, const float* mean, const 
                                        const float* dy, float* dw, int N, int H, int W, int C, int OH, int OW, int K, int stride,
                                        int pad_top, int pad_left, void* stream) {
   if (!x || !mean || !invstd || !gamma || !beta || !dy || !dw || !dw_ok(N, H, W, C, OH, OW, K, stride, pad_top, pad_left))
-    return fail(HIFIHR_EINVAL, "hifihr_dwconv2d_bwd_weight_bnswish: bad argument");
+    return fail(HIFIHR_EINVAL, "hifihr_dwconv2d_bwd_weight_bnswish: bad argument (C % 4 == 0; K 3 or 5; stride 1 or 2; 0 <= pad <= K - 1; -(stride - 1) <= implied bottom / right pad <= K - 1)");
   hifihr::DwGeom g{N, H, W, C, OH, OW, K, stride, pad_top, pad_left};
   HIP_TRY(hifihr::launch_dwconv_bwd_weight(g, x, dy, dw, (hipStream_t)stream, mean, invstd, gamma, beta));
   return HIFIHR_OK;
@@ -807,15 +816,15 @@ int hifihr_dwconv2d_bwd_weight_bnswish(const float* x, const float* mean, const 
 
 int hifihr_bn_finalize_fwd(float* stats, long M, int C, float eps, float momentum, float* save_mean, float* save_invstd,
                            float* running_mean, float* running_var, void* stream) {
-  if (!stats || !save_mean || !save_invstd || M <= 0 || C < 4 || C % 4 != 0 || (running_mean == nullptr) != (running_var == nullptr))
-    return fail(HIFIHR_EINVAL, "hifihr_bn_finalize_fwd: bad argument");
+  if (!stats || !save_mean || !save_invstd || !bn_dims_ok(M, C) || (running_mean == nullptr) != (running_var == nullptr))
+    return fail(HIFIHR_EINVAL, "hifihr_bn_finalize_fwd: bad argument (C % 4 == 0, C <= 4096; running statistics both or neither)");
   HIP_TRY(hifihr::launch_bn_finalize_fwd(stats, M, C, eps, momentum, save_mean, save_invstd, running_mean, running_var, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 
 int hifihr_dwconv2d_bwd_data(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int OH, int OW, int K, int stride,
                              int pad_top, int pad_left, void* stream) {
-  if (!dy || !w || !dx || !dw_ok(N, H, W, C, OH, OW, K, stride, pad_top, pad_left)) return fail(HIFIHR_EINVAL, "hifihr_dwconv2d_bwd_data: bad argument");
+  if (!dy || !w || !dx || !dw_ok(N, H, W, C, OH, OW, K, stride, pad_top, pad_left)) return fail(HIFIHR_EINVAL, "hifihr_dwconv2d_bwd_data: bad argument (C % 4 == 0; K 3 or 5; stride 1 or 2; 0 <= pad <= K - 1; -(stride - 1) <= implied bottom / right pad <= K - 1)");
   hifihr::DwGeom g{N, H, W, C, OH, OW, K, stride, pad_top, pad_left};
   HIP_TRY(hifihr::launch_dwconv_bwd_data(g, dy, w, dx, (hipStream_t)stream));
   return HIFIHR_OK;
@@ -823,7 +832,7 @@ int hifihr_dwconv2d_bwd_data(const float* dy, const float* w, float* dx, int N, 
 
 int hifihr_dwconv2d_bwd_weight(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int OH, int OW, int K,
                                int stride, int pad_top, int pad_left, void* stream) {
-  if (!x || !dy || !dw || !dw_ok(N, H, W, C, OH, OW, K, stride, pad_top, pad_left)) return fail(HIFIHR_EINVAL, "hifihr_dwconv2d_bwd_weight: bad argument");
+  if (!x || !dy || !dw || !dw_ok(N, H, W, C, OH, OW, K, stride, pad_top, pad_left)) return fail(HIFIHR_EINVAL, "hifihr_dwconv2d_bwd_weight: bad argument (C % 4 == 0; K 3 or 5; stride 1 or 2; 0 <= pad <= K - 1; -(stride - 1) <= implied bottom / right pad <= K - 1)");
   hifihr::DwGeom g{N, H, W, C, OH, OW, K, stride, pad_top, pad_left};
   HIP_TRY(hifihr::launch_dwconv_bwd_weight(g, x, dy, dw, (hipStream_t)stream));
   return HIFIHR_OK;
@@ -863,14 +872,14 @@ int hifihr_maxpool2d_bwd(const float* gy, const unsigned char* tap, int N, int H
 }
 
 int hifihr_maxpool2d_fwd_flat(const float* x, int N, int H, int W, int C, int k, int s, int p, float* y_flat, unsigned char* tap, void* stream) {
-  if (!x || !y_flat || !tap || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 != 0)
+  if (!x || !y_flat || !tap || N <= 0 || H <= 0 || W <= 0 || C < 4 || C % 4 != 0 || !pool_ok(k, s, p) || H + 2 * p < k || W + 2 * p < k)
     return fail(HIFIHR_EINVAL, "hifihr_maxpool2d_fwd_flat: bad argument (C % 4 == 0; (k,s,p) in {(3,2,1), (3,1,1), (2,2,0)})");
   HIP_TRY(hifihr::launch_maxpool_flat(x, tap, N, H, W, C, k, s, p, y_flat, 0, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 
 int hifihr_maxpool2d_bwd_flat(const float* gy_flat, const unsigned char* tap, int N, int H, int W, int C, int k, int s, int p, float* dx, void* stream) {
-  if (!gy_flat || !dx || !tap || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 != 0)
+  if (!gy_flat || !dx || !tap || N <= 0 || H <= 0 || W <= 0 || C < 4 || C % 4 != 0 || !pool_ok(k, s, p) || H + 2 * p < k || W + 2 * p < k)
     return fail(HIFIHR_EINVAL, "hifihr_maxpool2d_bwd_flat: bad argument (C % 4 == 0; (k,s,p) in {(3,2,1), (3,1,1), (2,2,0)})");
   HIP_TRY(hifihr::launch_maxpool_flat(gy_flat, const_cast<unsigned char*>(tap), N, H, W, C, k, s, p, dx, 1, (hipStream_t)stream));
   return HIFIHR_OK;
@@ -1417,7 +1426,8 @@ int hifihr_wino_bn_bwd_dual_transform(const float* g, const float* y, const floa
 
 int hifihr_bn_bwd_apply(const float* g, const float* x, const float* save_mean, const float* save_invstd, const float* gamma, long M, int C,
                         float* red, float* dx, float* dgamma_acc, float* dbeta_acc, void* stream) {
-  if (!g || !x || !save_mean || !save_invstd || !gamma || !red || !dx || M <= 0) return fail(HIFIHR_EINVAL, "hifihr_bn_bwd_apply: bad argument");
+  if (!g || !x || !save_mean || !save_invstd || !gamma || !red || !dx || M <= 0 || C < 4 || C % 4 != 0 || C > 512)
+    return fail(HIFIHR_EINVAL, "hifihr_bn_bwd_apply: bad argument (C % 4 == 0, C <= 512)");
   HIP_TRY(hifihr::launch_bn_bwd_apply(g, x, save_mean, save_invstd, gamma, M, C, red, dx, dgamma_acc, dbeta_acc, (hipStream_t)stream));
   return HIFIHR_OK;
 }

@@ -546,9 +546,13 @@ int hifihr_conv2d_fwd_bnstats_pair(const float* x_d, const float* w1_d, float* y
  * the reduction inside hifihr_bn_act_bwd) ADD into stats_d / red_scratch_d, which must be all zero on entry;
  * hifihr_bn_act_fwd / hifihr_bn_act_bwd fold the slots inside their apply kernel (no separate finalize launch) and the
  * last workgroup of that kernel to finish -- elected through arrival counters stored behind the slots -- writes the zeros
- * back, so one zero-initialised buffer serves every step without a memset launch.
+ * back, so one zero-initialised buffer serves every step without a memset launch.  (Handed back zeroed: the slots and the arrival counters,
+ * the first 128 C + 64 floats; the 2 C floats behind them are scratch of the wide-layer backward, written before they are read.)
  *   fwd: y = act( (x - mean) * invstd * gamma + beta + residual? ); writes save_mean/save_invstd[C] and updates
- *        running_mean/var (momentum, unbiased variance) when given.
+ *        running_mean/var (momentum, unbiased variance) when given (both or neither: one NULL is HIFIHR_EINVAL).
+ *        M = 1 (nn.BatchNorm2d raises there) is defined: batch variance 0, save_invstd = 1 / sqrt(eps), y = act(beta + residual?), and
+ *        running_var takes the BIASED value (0) -- the unbiased M / (M - 1) factor is applied for M > 1 only.  The same rule holds for
+ *        hifihr_bn_finalize_fwd and the fused stem entry.
  *   bwd: g = dy * act'(z) (ReLU: y > 0 from y_d -- or, with y_d NULL and no residual input in the forward, the mask recomputed from x, needs beta_d; swish: z recomputed from x, needs beta_d); dx = gamma*invstd*(g - mean(g) - xhat*mean(g*xhat)); dres (may be NULL) = g;
  *        dgamma_acc[C] += sum g*xhat, dbeta_acc[C] += sum g (either may be NULL).
  * ---------------------------------------------------------------------------------------------- */
@@ -593,7 +597,13 @@ int hifihr_bn_relu_maxpool_bwd_y(const float* pooled_grad_d, const float* pooled
  * Replaces the depthwise Conv2dStaticSamePadding of the reference's EfficientNet MBConv blocks
  * (reference network/efficientnet_pt/model.py:49-55,80; utils.py:122-145) and its autograd.
  * x[N][H][W][C], w[C][K][K] (= torch [C,1,K,K]), y[N][OH][OW][C]; stride 1 or 2; pad_top/pad_left explicit, bottom/right
- * implied by OH/OW.  bwd_weight ACCUMULATES into dw (fp32 atomics).  fwd: stats_d (may be NULL) = batch-norm slot buffer
+ * implied by OH/OW:  pad_bottom = (OH - 1) * stride + K - H - pad_top (columns alike), the zero rows the last window needs below the
+ * image.  Accepted: C % 4 == 0, 0 <= pad_top <= K - 1 and -(stride - 1) <= pad_bottom <= K - 1, i.e. y is
+ * conv2d(F.pad(x, (pad_left, max(pad_right, 0), pad_top, max(pad_bottom, 0))), stride), OH = floor((H + pad_top + pad_bottom - K) / stride) + 1:
+ * a negative pad_bottom down to -(stride - 1) is the row(s) a stride-2 floor division leaves unread (H + pads - K odd), not a crop.
+ * Anything else -- an output smaller than the windows that fit (a crop), windows that lie in the padding alone, a pad of K or
+ * more, OH <= 0 -- is HIFIHR_EINVAL with nothing written.  An input smaller than the filter is fine (H = 1, K = 5, pads 2 + 2).
+ * bwd_data OVERWRITES dx.  bwd_weight ACCUMULATES into dw (fp32 atomics).  fwd: stats_d (may be NULL) = batch-norm slot buffer
  * (hifihr_bn_stats_floats(C) floats, all zero on entry, self-cleaning: see the batch-norm section) that receives the
  * per-channel sum / sum of squares of y, so the BatchNorm that follows needs no statistics pass.
  * ---------------------------------------------------------------------------------------------- */
@@ -696,7 +706,7 @@ int hifihr_lpips_tap(const float* f0_d, const float* f1_d, const float* w_d, int
  * Replaces pytorch_ssim.ssim(img1, img2)   reference utils/pytorch_ssim/__init__.py:17-37,65-73
  * (called at reference losses.py:375 for the ssim_tex term) and its autograd w.r.t. img1.
  * img1/img2: [planes][H][W] with planes = B*C (contiguous NCHW); window11_h: the 11 normalised taps (HOST).
- * fwd writes one partial sum per 16x16 tile: SSIM = sum(partial[0..hifihr_ssim_partial_count)) / (planes*H*W)
+ * fwd writes one partial sum per tile (32x32; hifihr_ssim_partial_count of them): SSIM = sum(partial[0..hifihr_ssim_partial_count)) / (planes*H*W)
  * (summed by the caller; deterministic).  dA/dB/dC ([planes][H][W] each, all three or none) receive the
  * derivative maps the backward call consumes.  bwd: gimg1 = grad_out[0] * d mean(SSIM) / d img1; grad_out_d is
  * a DEVICE scalar (no host sync).

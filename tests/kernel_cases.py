@@ -2264,3 +2264,1006 @@ def joint_terms_case(lib, device, B, mse, seed=0, use2=True, use3=True):
         assert float((g2.cpu() - j2d.grad).abs().max()) <= 1e-5 * float(j2d.grad.abs().max()) + 1e-9
     if use3:
         assert float((g3.cpu() - j3d.grad).abs().max()) <= 1e-5 * float(j3d.grad.abs().max()) + 1e-9
+
+
+# ------------------------------------------------------------------------------------------------
+# The layer contract: batch-norm (csrc/bn.hip), pooling (csrc/pool.hip), depthwise convolution (csrc/dwconv.hip), squeeze-excite
+# (csrc/se.hip) and SSIM (csrc/ssim.hip) on fixed geometry lists (tests/test_hostsim_layer_contract.py; the GPU half in
+# tests/test_gpu_conv.py and tests/test_gpu_tail.py), in the conv contract's form:
+#   * an entry either refuses a geometry (HIFIHR_EINVAL, every output untouched) or matches a FLOAT64 reference of the same operation
+#     within  err <= min(c sqrt(L), cap) max|ref| + floor,  L the reduction length of the quantity;
+#   * every tensor sits inside a larger allocation (class Guards): margins of inputs are NaN (an out-of-bounds read poisons the output),
+#     margins of outputs a canary that must survive bit for bit;
+#   * accepted calls run twice on the same scratch; self-cleaning buffers must be all zero after each call; accumulate / overwrite as
+#     include/hifihr.h states them.
+# The references take a dtype: run in float32 they are "plain fp32 PyTorch on the CPU", whose worst err / (sqrt(L) max|ref|) over the
+# emulator lists (tools/layer_contract_c.py prints them) times 4 is the constant c below.  cap = the relative tolerance the family's
+# older case in this file asserts (never looser than that).  floor: fp32 torch's own absolute error where the reference is (near) zero,
+# times 4, measured by the same tool.
+# ------------------------------------------------------------------------------------------------
+GUARD_FLOATS = 256
+LAYER_CONTRACT_C = {
+    # kind: (c, cap)                  fp32 torch's worst ratio (tools/layer_contract_c.py) x 4; the quantities and L; (where cap comes from)
+    "bn_sum": (6.5e-7, 1e-4),         # 1.62e-07 x 4   per-channel sum / sum of squares (bn_stats, the depthwise forward's slots), L = rows   (bn_act_case rtol 1e-4)
+    "bn_stat": (6.2e-7, 1e-5),        # 1.53e-07 x 4   save_mean / save_invstd / running statistics, L = 1     (bn_act_case rtol 1e-5)
+    "bn_y": (8.2e-7, 2e-5),           # 2.03e-07 x 4   y, L = 1                                                (bn_act_case 2e-5)
+    "bn_dx": (2.8e-6, 2e-4),          # 7.00e-07 x 4   dx, L = 1                                               (bn_act_case 2e-4)
+    "bn_dparam": (1.9e-7, 2e-4),      # 4.53e-08 x 4   dgamma / dbeta, L = M                                   (bn_act_case 2e-4)
+    "pool_dx": (1.3e-7, 2e-6),        # 3.03e-08 x 4   max-pool dx, L = ceil(k / s)^2 gradients per pixel      (maxpool_case 2e-6)
+    "mm_y": (3.2e-7, 1e-5),           # 7.88e-08 x 4   mmpool y / xavg, L = HW                                 (mmpool_case 1e-5)
+    "mm_dx": (2.9e-7, 1e-5),          # 7.07e-08 x 4   mmpool dx, L = 1                                        (mmpool_case 1e-5)
+    "mm_dp": (1.5e-7, 1e-4),          # 3.71e-08 x 4   mmpool dp, L = B C                                      (mmpool_case 1e-4)
+    "dw_fwd": (1.9e-7, 2e-5),         # 4.65e-08 x 4   depthwise y, L = K K                                    (dwconv_case 2e-5)
+    "dw_pre": (2.1e-7, 3e-5),         # 5.21e-08 x 4   depthwise y with bn + swish on load, L = K K            (dwconv_bnswish_case 3e-5)
+    "dw_dgrad": (2.2e-7, 2e-5),       # 5.49e-08 x 4   depthwise dx, L = K K                                   (dwconv_case 2e-5)
+    "dw_wgrad": (1.5e-7, 1e-4),       # 3.66e-08 x 4   depthwise dw, L = N OH OW                               (dwconv_case 1e-4)
+    "dw_wgrad_pre": (3.7e-7, 2e-4),   # 9.06e-08 x 4   the same with bn + swish on load                        (dwconv_bnswish_case 2e-4)
+    "se_pool": (2.0e-7, 1e-5),        # 4.96e-08 x 4   se_pool mean / se_bwd_gate sums, L = HW                 (se_case 1e-5, absolute on |mean| <~ 1)
+    "se_y": (2.9e-7, 3e-5),           # 7.03e-08 x 4   se_scale y, drop_connect_add out, L = 1                 (se_case 3e-5)
+    "se_mlp": (3.3e-7, 2e-5),         # 8.04e-08 x 4   se_mlp_fwd z1, h1 (L = C), gate (L = SQ), mean (L = 1)  (se_case 2e-5)
+    "se_grad": (6.6e-7, 3e-4),        # 1.64e-07 x 4   se_mlp_bwd dw1 / db1 / dw2 / db2 (L = B), dz2 (1), dz1 (C), dmean (SQ)   (se_case 3e-4)
+    "ssim_val": (5.0e-7, 2e-6),       # 1.25e-07 x 4   SSIM value, ssim_finish, L = planes H W                 (ssim_case 2e-6)
+    "ssim_part": (5.3e-7, 2e-6),      # 1.31e-07 x 4   per-tile partial sums, L = 1024                         (ssim_case 2e-6 on their sum)
+    "ssim_map": (1.9e-4, 2.1e-3),     # 4.68e-05 x 4   the three derivative maps, L = 121: two constant images put 1 / (s1 + s2 + C2)^2 = 1.2e6 in
+    #                                                  front of the rounding of E[x^2] - mu^2.  No older case looks at the maps themselves (cap =
+    #                                                  c sqrt(121)); the gradient they feed keeps ssim_case's 2e-4 in the next line
+    "ssim_grad": (4.4e-5, 2e-4),      # 1.10e-05 x 4   d SSIM / d img1, L = 121 (the same pair)                (ssim_case 2e-4)
+}
+# fp32 torch's absolute error x 4 where the reference is zero to rounding (an identical pair: maps and gradient are 1e-15 in float64)
+LAYER_CONTRACT_FLOOR = {
+    "ssim_map": 7.7e-6,               # 1.91e-06 x 4
+    "ssim_grad": 6.5e-8,              # 1.61e-08 x 4
+}
+LAYER_CONTRACT_LOG = {}               # entry -> [accepted, refused, largest err / bound] (the tests print it)
+
+
+def _layer_log(entry, accepted, ratio=0.0):
+    row = LAYER_CONTRACT_LOG.setdefault(entry, [0, 0, 0.0])
+    row[0 if accepted else 1] += 1
+    row[2] = max(row[2], ratio) if ratio == ratio else float("inf")
+
+
+def layer_bound(kind, ref, L, cond=0.0):
+    """min(c sqrt(L), cap) max|ref| + c cond + floor.  cond: the size of the terms whose CANCELLATION gives the quantity, where the operation
+    itself has one (the references state it: batch-norm's y = x sc + sh with sh = beta - mean sc; dx = gamma invstd (g - mean g - xhat mean(g xhat)),
+    which vanishes identically at M <= 2; SSIM's variances E[x^2] - mu^2 under a denominator of 9e-4; a sum added onto a prefilled
+    accumulator).  fp32 rounds each term to eps times ITS size, so no fp32 evaluation -- torch's included -- can be held to eps max|ref|
+    there; the constants c were measured against the same expression."""
+    c, cap = LAYER_CONTRACT_C[kind]
+    scale = float(ref.abs().max()) if ref.numel() else 0.0
+    return min(c * max(L, 1) ** 0.5, cap) * scale + c * float(cond) + LAYER_CONTRACT_FLOOR.get(kind, 0.0)
+
+
+def layer_err(got, ref):
+    """max |got - ref| in float64; NaN (a poisoned output) when any element is NaN."""
+    if ref.numel() == 0:
+        return 0.0
+    d = (got.detach().cpu().double().reshape(ref.shape) - ref).abs()
+    return float("nan") if bool(torch.isnan(d).any()) else float(d.max())
+
+
+def layer_passes(kind, got, ref, L, cond=0.0):
+    """The comparator itself (the detection check feeds it references with one contribution removed)."""
+    return layer_err(got, ref) <= layer_bound(kind, ref, L, cond)
+
+
+def _close_ref(entry, ref, name, got, tag, prefill=0.0):
+    """got against ref[name] = (kind, L, tensor[, cond]).  prefill: what the accumulator held before the call (taken off `got` by the caller;
+    the sum onto it is rounded at its size)."""
+    q = ref[name]
+    _layer_close(entry, q[0], got, q[2], q[1], f"{tag}: {entry} {name}", (q[3] if len(q) > 3 else 0.0) + abs(prefill))
+
+
+def _slots_clean(buf, C, what):
+    """The self-cleaning part of a statistics / reduction buffer: the 32 slots and the 64 arrival counters behind them (include/hifihr.h).
+    The last 2 C floats are plain scratch of the wide-layer backward (written before they are read)."""
+    assert float(buf[:32 * 4 * C + 64].abs().max()) == 0.0, what
+
+
+def _layer_close(entry, kind, got, ref, L, what, cond=0.0):
+    err, bound = layer_err(got, ref), layer_bound(kind, ref, L, cond)
+    _layer_log(entry, True, (err / bound) if bound > 0 else (0.0 if err == 0 else float("inf")))
+    assert err <= bound, f"{what}: err {err:.3e} vs bound {bound:.3e} (kind {kind}, max|ref| {float(ref.abs().max()) if ref.numel() else 0:.3e}, L {L})"
+
+
+def _layer_equal(entry, got, want, what):
+    _layer_log(entry, True, 0.0)
+    assert got.shape == want.shape and torch.equal(got.cpu(), want.cpu()), f"{what}: not bit-identical"
+
+
+def layer_contract_report(title, prefixes=("",)):
+    """The tally of the entries whose names start with one of `prefixes`: accepted / refused calls and the largest err / bound; printed, and
+    appended to layer_contract_tally.txt in the directory HIFIHR_REPORT_DIR names, when it names one."""
+    rows = [(e, v) for e, v in sorted(LAYER_CONTRACT_LOG.items()) if e.startswith(tuple(prefixes))]
+    lines = [f"layer contract, {title} (entry: accepted / refused calls, largest err / bound):"]
+    lines += [f"  {e:28s} {a:5d} / {r:4d}   {worst:6.3f}" for e, (a, r, worst) in rows]
+    print("\n" + "\n".join(lines))
+    out = os.environ.get("HIFIHR_REPORT_DIR")
+    if out and os.path.isdir(out):
+        with open(os.path.join(out, "layer_contract_tally.txt"), "a") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+_CANARY = {torch.float32: -1234.5, torch.uint8: 0xA5, torch.int32: -1234567}
+_POISON = {torch.float32: float("nan"), torch.uint8: 0xFF, torch.int32: 0x7FFFFFF0}
+
+
+class Guards:
+    """Tensors inside larger allocations: at least GUARD_FLOATS elements of margin on each side (1 KiB for fp32: the view keeps the
+    16-byte -- and for the float64 statistic slots 8-byte -- alignment a plain allocation has; offset_floats shifts it on purpose)."""
+
+    def __init__(self, device):
+        self.device, self.outs = device, []
+
+    def _place(self, n, dtype, fill, offset):
+        whole = torch.full((GUARD_FLOATS + offset + n + GUARD_FLOATS,), fill, dtype=dtype, device=self.device)
+        return whole, GUARD_FLOATS + offset, GUARD_FLOATS + offset + n
+
+    def inp(self, t, offset_floats=0):
+        """A copy of t whose surroundings are NaN (float) / out-of-range values (bytes, ints)."""
+        if t is None:
+            return None
+        t = t.contiguous()
+        whole, lo, hi = self._place(t.numel(), t.dtype, _POISON[t.dtype], offset_floats)
+        view = whole[lo:hi].view(t.shape)
+        view.copy_(t.to(self.device))
+        return view
+
+    def out(self, *shape, fill=None, dtype=torch.float32, offset_floats=0):
+        """An output of `shape`: canary around it and -- unless `fill` gives the prefill -- inside it."""
+        n = 1
+        for s in shape:
+            n *= int(s)
+        canary = _CANARY[dtype]
+        whole, lo, hi = self._place(n, dtype, canary, offset_floats)
+        view = whole[lo:hi].view(*shape)
+        if fill is not None:
+            view.fill_(fill)
+        self.outs.append((whole, lo, hi, canary))
+        return view
+
+    def intact(self, what):
+        for whole, lo, hi, canary in self.outs:
+            ok = bool((whole[:lo] == canary).all()) and bool((whole[hi:] == canary).all())
+            assert ok, f"{what}: wrote outside an output (guard band changed)"
+
+    def wholes(self):
+        return [w for w, _, _, _ in self.outs]
+
+
+def _refuses(entry, call, guards, what):
+    _contract_rejects(call, guards.wholes(), what)
+    _layer_log(entry, False)
+
+
+def _is_canary(t):
+    return bool((t == _CANARY[t.dtype]).all())
+
+
+# ---- batch-norm ------------------------------------------------------------------------------------------------------------------
+def bn_contract_expect(M, C):
+    """include/hifihr.h: C % 4 == 0, 4 <= C <= 4096 for every batch-norm entry; hifihr_bn_bwd_apply C <= 512."""
+    ok = M > 0 and C >= 4 and C % 4 == 0 and C <= 4096
+    return {"bn_stats": ok, "bn_act_fwd": ok, "bn_act_eval": ok, "bn_act_bwd": ok, "bn_finalize_fwd": ok, "bn_bwd_apply": ok and C <= 512}
+
+
+def bn_stem_contract_expect(N, H, W, C):
+    """include/hifihr.h: the fused stem takes C % 4 == 0, C <= 512, H, W >= 2."""
+    return N > 0 and H >= 2 and W >= 2 and C >= 4 and C % 4 == 0 and C <= 512
+
+
+def bn_contract_inputs(M, C, residual, seed):
+    gen = torch.Generator().manual_seed(seed)
+    Cc = max(4, (C + 3) // 4 * 4)                              # refused channel counts still get buffers a 4-wide lane could touch
+    x = torch.randn(M, Cc, generator=gen) * 1.5 + 0.3
+    gamma = 1 + 0.1 * torch.randn(Cc, generator=gen); beta = 0.1 * torch.randn(Cc, generator=gen)
+    res = torch.randn(M, Cc, generator=gen) if residual else None
+    rm0, rv0 = torch.randn(Cc, generator=gen) * 0.1, 1 + 0.1 * torch.rand(Cc, generator=gen)
+    gy = torch.randn(M, Cc, generator=gen)
+    return dict(x=x, gamma=gamma, beta=beta, res=res, rm0=rm0, rv0=rv0, gy=gy)
+
+
+def _act_fwd_bwd(z, gy, act, mask=None):
+    """(y, g = gy * act'(z)) in z's dtype; act 1 takes the ReLU mask when given."""
+    if act == 1:
+        m = (z > 0) if mask is None else mask
+        return z * m, gy * m
+    if act == 2:
+        s = torch.sigmoid(z)
+        return z * s, gy * (s * (1 + z * (1 - s)))
+    return z, gy
+
+
+def bn_contract_ref(inp, act, eps, mom, dt=torch.float64, mask=None, drop_row=None):
+    """Training-mode batch-norm + residual + activation and its backward on x[M][C], written out (no autograd: M = 1, where nn.BatchNorm2d
+    raises, is defined by the same formulas -- variance 0, invstd = 1 / sqrt(eps), running variance updated with the biased value).
+    Returns {name: (kind, L, tensor)} plus the intermediates z, xhat.  drop_row: that row is left out of the sums (detection check)."""
+    x, gamma, beta, gy = (inp[k].to(dt) for k in ("x", "gamma", "beta", "gy"))
+    res = inp["res"].to(dt) if inp["res"] is not None else None
+    M = x.shape[0]
+    xs = x if drop_row is None else torch.cat([x[:drop_row], x[drop_row + 1:]])
+    s1, s2 = xs.sum(0), (xs * xs).sum(0)
+    mean = x.mean(0)
+    var = ((x - mean) ** 2).mean(0)
+    invstd = (var + eps).rsqrt()
+    xhat = (x - mean) * invstd
+    z = xhat * gamma + beta + (res if res is not None else 0)
+    y, g = _act_fwd_bwd(z, gy, act, mask)
+    gs = g if drop_row is None else torch.cat([g[:drop_row], g[drop_row + 1:]])
+    xh = xhat if drop_row is None else torch.cat([xhat[:drop_row], xhat[drop_row + 1:]])
+    dbeta, dgamma = gs.sum(0), (gs * xh).sum(0)
+    dx = gamma * invstd * (g - g.sum(0) / M - xhat * (g * xhat).sum(0) / M)
+    rm = (1 - mom) * inp["rm0"].to(dt) + mom * mean
+    rv = (1 - mom) * inp["rv0"].to(dt) + mom * (var * (M / (M - 1)) if M > 1 else var)
+    ze = (x - inp["rm0"].to(dt)) * (inp["rv0"].to(dt) + eps).rsqrt() * gamma + beta + (res if res is not None else 0)
+    ye, _ = _act_fwd_bwd(ze, gy, act)
+    # the cancelling terms (layer_bound): y = x sc + sh, the two of size |mean| sc; dx's three terms of size gamma invstd |g|; xhat inside dgamma
+    gmax = float(g.abs().max())
+    cy = float((mean * invstd * gamma).abs().max())
+    cye = float((inp["rm0"].to(dt) * (inp["rv0"].to(dt) + eps).rsqrt() * gamma).abs().max())
+    cz = float(gy.abs().max()) * cy if act == 2 else 0.0                  # swish' recomputed from z = x sc + sh (|swish''| <= 1/2)
+    cdx = float((gamma * invstd).abs().max()) * (gmax + cz)
+    cdg = (float((mean * invstd).abs().max()) * gmax + cz) * M ** 0.5
+    out = {"sum": ("bn_sum", M, s1), "sumsq": ("bn_sum", M, s2), "mean": ("bn_stat", 1, mean), "invstd": ("bn_stat", 1, invstd),
+           "rm": ("bn_stat", 1, rm), "rv": ("bn_stat", 1, rv), "y": ("bn_y", 1, y, cy), "y_eval": ("bn_y", 1, ye, cye), "dx": ("bn_dx", 1, dx, cdx),
+           "dgamma": ("bn_dparam", M, dgamma, cdg), "dbeta": ("bn_dparam", M, dbeta, cz * M ** 0.5)}
+    return out, dict(z=z, ze=ze, xhat=xhat, g=g)
+
+
+def _relu_mask(z64, y_got, what):
+    """The ReLU mask of the float64 reference, with the kernel's own decision (y > 0) where fp32 cannot tell the sign of z: |z| within
+    4e-6 max(1, max|z|) (the bound on y itself).  Outside that zone the two must agree."""
+    amb = z64.abs() <= 4e-6 * max(1.0, float(z64.abs().max()))
+    m_ref, m_got = z64 > 0, y_got.cpu().reshape(z64.shape) > 0
+    assert bool((m_ref == m_got)[~amb].all()), f"{what}: ReLU zero pattern differs where the sign of z is not in doubt"
+    return torch.where(amb, m_got, m_ref)
+
+
+def bn_contract_case(lib, device, M, C, act=0, residual=False, y_given=True, running=True, eps=1e-5, mom=0.1, seed=0):
+    """Every plain batch-norm entry on x[M][C].  Returns {entry: accepted}."""
+    expect = bn_contract_expect(M, C)
+    inp = bn_contract_inputs(M, C, residual, seed)
+    Cc = inp["x"].shape[1]
+    tag = f"bn M={M} C={C} act={act} res={residual}"
+    G = Guards(device)
+    x, gamma, beta, res, gy = (G.inp(inp[k]) for k in ("x", "gamma", "beta", "res", "gy"))
+    nst = max(lib.bn_stats_floats(C), lib.bn_stats_floats(Cc))
+    stats = G.out(nst, fill=0.0)
+    y, sm, si = G.out(M, Cc), G.out(Cc), G.out(Cc)
+    rm, rv = G.out(Cc), G.out(Cc)
+    args_ok = not (act == 2 and residual)
+    if not expect["bn_stats"]:
+        _refuses("bn_stats", lambda: lib.bn_stats(x, M, C, stats), G, tag)
+        _refuses("bn_act_fwd", lambda: lib.bn_act_fwd(x, stats, gamma, beta, res, act, M, C, eps, mom, y, sm, si, rm, rv), G, tag)
+        _refuses("bn_act_eval", lambda: lib.bn_act_eval(x, gamma, beta, gamma, beta, res, act, M, C, eps, y), G, tag)
+        _refuses("bn_finalize_fwd", lambda: lib.bn_finalize_fwd(stats, M, C, eps, mom, sm, si, rm, rv), G, tag)
+        dxo, dgm, dbt = G.out(M, Cc), G.out(Cc), G.out(Cc)
+        _refuses("bn_act_bwd", lambda: lib.bn_act_bwd(gy, None, x, gamma, beta, gamma, beta, act, M, C, stats, dxo, None, dgm, dbt), G, tag)
+        _refuses("bn_bwd_apply", lambda: lib.bn_bwd_apply(gy, x, gamma, beta, gamma, M, C, stats, dxo, dgm, dbt), G, tag)
+        assert float(stats.abs().max()) == 0.0
+        return {e: False for e in expect}
+    if not args_ok:                                             # swish takes no residual: refused by the forward and the evaluation entry
+        _refuses("bn_act_fwd", lambda: lib.bn_act_fwd(x, stats, gamma, beta, res, act, M, C, eps, mom, y, sm, si, rm, rv), G, tag + " swish + residual")
+        _refuses("bn_act_eval", lambda: lib.bn_act_eval(x, gamma, beta, gamma, beta, res, act, M, C, eps, y), G, tag + " swish + residual")
+        return {"bn_act_fwd": False, "bn_act_eval": False}
+    ref, mid = bn_contract_ref(inp, act, eps, mom)
+    close = lambda entry, name, got: _close_ref(entry, ref, name, got, tag)
+    # one running statistic without the other is refused
+    _refuses("bn_act_fwd", lambda: lib.bn_act_fwd(x, stats, gamma, beta, res, act, M, C, eps, mom, y, sm, si, rm, None), G, tag + " one running statistic")
+    _refuses("bn_finalize_fwd", lambda: lib.bn_finalize_fwd(stats, M, C, eps, mom, sm, si, None, rv), G, tag + " one running statistic")
+    ys = []
+    for rep in range(2):                                       # twice on the same slot buffer
+        lib.bn_stats(x, M, C, stats)
+        sl = bn_slots(stats, C).sum(0).cpu()
+        close("bn_stats", "sum", sl[0]); close("bn_stats", "sumsq", sl[1])
+        rm.copy_(inp["rm0"]); rv.copy_(inp["rv0"])
+        y.fill_(_CANARY[torch.float32])
+        lib.bn_act_fwd(x, stats, gamma, beta, res, act, M, C, eps, mom, y, sm, si, rm if running else None, rv if running else None)
+        assert float(stats.abs().max()) == 0.0, f"{tag}: bn_act_fwd must hand the whole slot buffer back zeroed (call {rep + 1})"
+        close("bn_act_fwd", "y", y); close("bn_act_fwd", "mean", sm); close("bn_act_fwd", "invstd", si)
+        if running:
+            close("bn_act_fwd", "rm", rm); close("bn_act_fwd", "rv", rv)
+        else:
+            assert torch.equal(rm.cpu(), inp["rm0"]) and torch.equal(rv.cpu(), inp["rv0"])
+        ys.append(y.clone())
+    G.intact(tag + " forward")
+    # the statistics half alone: the same save_mean / save_invstd bits as the fused apply, the slots handed back zeroed
+    sm2, si2, rm2, rv2 = G.out(Cc), G.out(Cc), G.out(Cc), G.out(Cc)
+    rm2.copy_(inp["rm0"]); rv2.copy_(inp["rv0"])
+    lib.bn_stats(x, M, C, stats)
+    lib.bn_finalize_fwd(stats, M, C, eps, mom, sm2, si2, rm2 if running else None, rv2 if running else None)
+    assert float(stats.abs().max()) == 0.0, f"{tag}: bn_finalize_fwd must hand the whole slot buffer back zeroed"
+    close("bn_finalize_fwd", "mean", sm2); close("bn_finalize_fwd", "invstd", si2)
+    if running:
+        close("bn_finalize_fwd", "rm", rm2); close("bn_finalize_fwd", "rv", rv2)
+    # evaluation mode: running statistics in, nothing updated, no atomics -> two calls agree to the bit
+    rm0, rv0 = G.inp(inp["rm0"]), G.inp(inp["rv0"])
+    ye, ye2 = G.out(M, Cc), G.out(M, Cc)
+    lib.bn_act_eval(x, rm0, rv0, gamma, beta, res, act, M, C, eps, ye)
+    lib.bn_act_eval(x, rm0, rv0, gamma, beta, res, act, M, C, eps, ye2)
+    close("bn_act_eval", "y_eval", ye)
+    _layer_equal("bn_act_eval", ye2, ye, f"{tag}: bn_act_eval twice")
+    # backward: the ReLU mask is the forward's own where fp32 cannot tell the sign
+    if act == 1:
+        ref, mid = bn_contract_ref(inp, act, eps, mom, mask=_relu_mask(mid["z"], y, tag))
+    use_y = act == 1 and (y_given or residual)
+    if act == 1 and not use_y:
+        _refuses("bn_act_bwd", lambda: lib.bn_act_bwd(gy, None, x, sm, si, gamma, None, 1, M, C, stats, y, None, None, None), G, tag + " act 1 without y and beta")
+    dxo, dres = G.out(M, Cc), (G.out(M, Cc) if residual else None)
+    dgm, dbt = G.out(Cc), G.out(Cc)
+    for rep in range(2):
+        dgm.fill_(0.5); dbt.fill_(-0.25); dxo.fill_(_CANARY[torch.float32])
+        lib.bn_act_bwd(gy, y if use_y else None, x, sm, si, gamma, beta, act, M, C, stats, dxo, dres, dgm, dbt)
+        _slots_clean(stats, C, f"{tag}: bn_act_bwd must hand the slots and arrival counters back zeroed (call {rep + 1})")
+        close("bn_act_bwd", "dx", dxo)
+        _close_ref("bn_act_bwd", ref, "dgamma", dgm.cpu().double() - 0.5, tag, 0.5); _close_ref("bn_act_bwd", ref, "dbeta", dbt.cpu().double() + 0.25, tag, 0.25)
+        if residual:
+            _layer_equal("bn_act_bwd", dres, mid["g"].float(), f"{tag}: dres = g")
+    lib.bn_act_bwd(gy, y if use_y else None, x, sm, si, gamma, beta, act, M, C, stats, dxo, None, None, None)      # dgamma / dbeta may be NULL
+    close("bn_act_bwd", "dx", dxo)
+    # the apply half alone (C <= 512): g is the masked gradient, the first slot of red holds (sum g, sum g xhat)
+    g32 = G.inp(mid["g"].float())
+    red_fill = torch.zeros(nst)
+    red_fill[:2 * C] = torch.cat([ref["dbeta"][2], ref["dgamma"][2]]).float()
+    dxa = G.out(M, Cc)
+    if expect["bn_bwd_apply"]:
+        for rep in range(2):
+            stats.copy_(red_fill); dgm.fill_(0.5); dbt.fill_(-0.25)
+            lib.bn_bwd_apply(g32, x, sm, si, gamma, M, C, stats, dxa, dgm, dbt)
+            _slots_clean(stats, C, f"{tag}: bn_bwd_apply must hand the slots and arrival counters back zeroed")
+            close("bn_bwd_apply", "dx", dxa)
+            _close_ref("bn_bwd_apply", ref, "dgamma", dgm.cpu().double() - 0.5, tag, 0.5); _close_ref("bn_bwd_apply", ref, "dbeta", dbt.cpu().double() + 0.25, tag, 0.25)
+    else:
+        _refuses("bn_bwd_apply", lambda: lib.bn_bwd_apply(g32, x, sm, si, gamma, M, C, stats, dxa, dgm, dbt), G, tag)
+    G.intact(tag)
+    return dict(expect)
+
+
+def bn_stem_contract_inputs(N, H, W, C, seed):
+    gen = torch.Generator().manual_seed(seed)
+    Cc = max(4, (C + 3) // 4 * 4)
+    x = torch.randn(N, H, W, Cc, generator=gen) * 1.5 + 0.3
+    gamma = 1 + 0.1 * torch.randn(Cc, generator=gen); beta = 0.1 * torch.randn(Cc, generator=gen) - 0.3     # plenty of ReLU zeros: ties
+    gamma[1] = 2e-4; beta[1] = 0.05                      # a near-zero scale (positive shift: every tap passes the ReLU)
+    gamma[2] = -0.8                                      # a negative scale: the winner is the SMALLEST x of the window
+    rm0, rv0 = torch.randn(Cc, generator=gen) * 0.1, 1 + 0.1 * torch.rand(Cc, generator=gen)
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    gy = torch.randn(N, OH, OW, Cc, generator=gen)
+    return dict(x=x.reshape(-1, Cc), gamma=gamma, beta=beta, res=None, rm0=rm0, rv0=rv0, gy=gy)
+
+
+def _pool_scatter(gy, tap, N, H, W, k, s, p):
+    """dz[N][H][W][C] (float64) = the pooled gradient gy[N][OH][OW][C] scattered to the winning taps (tap = r * k + s bytes)."""
+    OH, OW, C = gy.shape[1], gy.shape[2], gy.shape[3]
+    t = tap.cpu().reshape(N, OH, OW, C).long()
+    oh = torch.arange(OH).view(1, OH, 1, 1); ow = torch.arange(OW).view(1, 1, OW, 1)
+    ih, iw = oh * s - p + t // k, ow * s - p + t % k
+    assert bool(((ih >= 0) & (ih < H) & (iw >= 0) & (iw < W)).all()), "a winning tap outside the image"
+    n = torch.arange(N).view(N, 1, 1, 1).expand_as(t); c = torch.arange(C).view(1, 1, 1, C).expand_as(t)
+    dz = torch.zeros(N, H, W, C, dtype=torch.float64)
+    dz.index_put_((n, ih.expand_as(t), iw.expand_as(t), c), gy.double(), accumulate=True)
+    return dz, (n, ih.expand_as(t), iw.expand_as(t), c)
+
+
+def bn_stem_contract_case(lib, device, N, H, W, C, seed=0, eps=1e-5, mom=0.1):
+    """hifihr_bn_relu_maxpool_fwd / _bwd / _bwd_y: MaxPool2d(3, 2, 1)(relu(bn(x))).  The forward equals bn_act_fwd + maxpool2d_fwd of the same
+    library bit for bit and the float64 reference within the bound; the winning taps are the kernel's own, each checked to hold its window's
+    float64 maximum to the bound of y (fp32 cannot order closer values), and the backward reference scatters through them."""
+    accepted = bn_stem_contract_expect(N, H, W, C)
+    assert lib.bn_relu_maxpool_supported(N, H, W, C) == accepted, f"bn_relu_maxpool_supported({N}, {H}, {W}, {C})"
+    inp = bn_stem_contract_inputs(N, H, W, C, seed)
+    Cc, M = inp["x"].shape[1], N * H * W
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    tag = f"bn stem {N}x{H}x{W}x{C}"
+    G = Guards(device)
+    x, gamma, beta, gy = (G.inp(inp[k]) for k in ("x", "gamma", "beta", "gy"))
+    nst = max(lib.bn_stats_floats(C), lib.bn_stats_floats(Cc))
+    stats = G.out(nst, fill=0.0)
+    y, tap = G.out(N, OH, OW, Cc), G.out(N * OH * OW * Cc, dtype=torch.uint8)
+    sm, si, rm, rv = G.out(Cc), G.out(Cc), G.out(Cc), G.out(Cc)
+    dx, dgm, dbt = G.out(N, H, W, Cc), G.out(Cc), G.out(Cc)
+    if not accepted:
+        _refuses("bn_relu_maxpool_fwd", lambda: lib.bn_relu_maxpool_fwd(x, stats, gamma, beta, N, H, W, C, eps, mom, y, tap, sm, si, rm, rv), G, tag)
+        _refuses("bn_relu_maxpool_bwd", lambda: lib.bn_relu_maxpool_bwd(gy, tap, x, gamma, beta, gamma, beta, N, H, W, C, stats, dx, dgm, dbt), G, tag)
+        _refuses("bn_relu_maxpool_bwd_y", lambda: lib.bn_relu_maxpool_bwd_y(gy, y, tap, x, gamma, beta, gamma, beta, N, H, W, C, stats, dx, dgm, dbt), G, tag)
+        return False
+    ref, mid = bn_contract_ref(dict(inp, gy=torch.zeros(M, Cc)), 1, eps, mom)
+    close = lambda entry, name, got: _close_ref(entry, ref, name, got, tag)
+    for rep in range(2):
+        lib.bn_stats(x, M, C, stats)
+        stats2 = stats.clone()
+        rm.copy_(inp["rm0"]); rv.copy_(inp["rv0"])
+        lib.bn_relu_maxpool_fwd(x, stats, gamma, beta, N, H, W, C, eps, mom, y, tap, sm, si, rm, rv)
+        assert float(stats.abs().max()) == 0.0, f"{tag}: the fused stem forward must hand the whole slot buffer back zeroed"
+        for name, got in (("mean", sm), ("invstd", si), ("rm", rm), ("rv", rv)):
+            close("bn_relu_maxpool_fwd", name, got)
+    # the unfused pair of the same library: the same bits
+    yf, sm2, si2 = G.out(M, Cc), G.out(Cc), G.out(Cc)
+    lib.bn_act_fwd(x, stats2, gamma, beta, None, 1, M, C, eps, mom, yf, sm2, si2, None, None)
+    y2, tap2 = G.out(N, OH, OW, Cc), G.out(N * OH * OW * Cc, dtype=torch.uint8)
+    lib.maxpool2d_fwd(yf, N, H, W, C, 3, 2, 1, y2, tap2)
+    _layer_equal("bn_relu_maxpool_fwd", torch.cat([sm, si]), torch.cat([sm2, si2]), f"{tag}: batch statistics vs bn_act_fwd")
+    _layer_equal("bn_relu_maxpool_fwd", y, y2, f"{tag}: pooled vs bn_act_fwd + maxpool2d_fwd")
+    _layer_equal("bn_relu_maxpool_fwd", tap, tap2, f"{tag}: taps vs bn_act_fwd + maxpool2d_fwd")
+    # float64: each winning tap holds its window's maximum of relu(z), the pooled value is that maximum
+    import torch.nn.functional as F
+    a64 = torch.relu(mid["z"]).reshape(N, H, W, Cc)
+    pooled64 = F.max_pool2d(a64.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
+    _layer_close("bn_relu_maxpool_fwd", "bn_y", y, pooled64, 1, f"{tag}: pooled", ref["y"][3])
+    _, where = _pool_scatter(inp["gy"], tap, N, H, W, 3, 2, 1)
+    slack = layer_bound("bn_y", a64, 1, ref["y"][3])
+    assert float((pooled64 - a64[where]).abs().max()) <= 2 * slack + 1e-300, f"{tag}: a winning tap does not hold its window's maximum"
+    # backward: scatter through the kernel's taps, ReLU mask as in bn_contract_case, then the batch-norm backward in float64
+    dz, _ = _pool_scatter(inp["gy"], tap, N, H, W, 3, 2, 1)
+    full = dict(inp, gy=dz.reshape(M, Cc))
+    mask = _relu_mask(mid["z"], yf, tag)
+    refb, _ = bn_contract_ref(full, 1, eps, mom, mask=mask)
+    for entry, call in (("bn_relu_maxpool_bwd", lambda: lib.bn_relu_maxpool_bwd(gy, tap, x, sm, si, gamma, beta, N, H, W, C, stats, dx, dgm, dbt)),
+                        ("bn_relu_maxpool_bwd_y", lambda: lib.bn_relu_maxpool_bwd_y(gy, y, tap, x, sm, si, gamma, beta, N, H, W, C, stats, dx, dgm, dbt))):
+        for rep in range(2):
+            dx.fill_(_CANARY[torch.float32]); dgm.fill_(0.5); dbt.fill_(-0.25)
+            call()
+            _slots_clean(stats, C, f"{tag}: {entry} must hand the slots and arrival counters back zeroed")
+            _close_ref(entry, refb, "dx", dx, tag)
+            _close_ref(entry, refb, "dgamma", dgm.cpu().double() - 0.5, tag, 0.5)
+            _close_ref(entry, refb, "dbeta", dbt.cpu().double() + 0.25, tag, 0.25)
+    G.intact(tag)
+    return True
+
+
+# ---- pooling -----------------------------------------------------------------------------------------------------------------------
+POOL_KSP = ((3, 2, 1), (3, 1, 1), (2, 2, 0))
+
+
+def pool_contract_expect(N, H, W, C, k, s, p):
+    """include/hifihr.h: C % 4 == 0; the tapped entries take (k, s, p) in {(3,2,1), (3,1,1), (2,2,0)}, the inference pool (3,2,0) alone;
+    the padded image must hold one window."""
+    ok = min(N, H, W) > 0 and C >= 4 and C % 4 == 0 and H + 2 * p >= k and W + 2 * p >= k
+    tapped = ok and (k, s, p) in POOL_KSP
+    return {"maxpool2d_fwd": tapped, "maxpool2d_bwd": tapped, "maxpool2d_bwd_relu": tapped, "maxpool2d_fwd_flat": tapped,
+            "maxpool2d_bwd_flat": tapped, "maxpool2d_fwd_notap": ok and (k, s, p) == (3, 2, 0)}
+
+
+def _taps_of(idx, OH, OW, W, k, s, p):
+    """ATen's flat winner index [N][C][OH][OW] -> the tap byte r * k + s in [N][OH][OW][C] order."""
+    oh = torch.arange(OH).view(1, 1, OH, 1); ow = torch.arange(OW).view(1, 1, 1, OW)
+    r, c = idx // W - (oh * s - p), idx % W - (ow * s - p)
+    return (r * k + c).permute(0, 2, 3, 1).contiguous().to(torch.uint8)
+
+
+def _same_values(got, want):
+    got, want = got.cpu(), want.cpu()
+    return torch.equal(torch.isnan(got), torch.isnan(want)) and torch.equal(torch.nan_to_num(got, nan=0.0), torch.nan_to_num(want, nan=0.0))
+
+
+def pool_contract_case(lib, device, N, H, W, C, k, s, p, mode="random", seed=0):
+    """The six max-pool entries on one geometry.  mode: random / ties (post-ReLU zeros) / special (a window of -inf, a NaN: forward only,
+    ATen's `(val > max) || isnan(val)` rule and index).  Values, taps, the flat forms and a second call: bit-identical."""
+    import torch.nn.functional as F
+    expect = pool_contract_expect(N, H, W, C, k, s, p)
+    gen = torch.Generator().manual_seed(seed)
+    Cc = max(4, (C + 3) // 4 * 4)
+    tag = f"pool {N}x{H}x{W}x{C} ({k},{s},{p}) {mode}"
+    z = torch.randn(N, H, W, Cc, generator=gen)
+    x = torch.relu(z) if mode == "ties" else z.clone()
+    if mode == "special":
+        x[:, :min(H, 3), :min(W, 3), :] = float("-inf")          # the first window(s): every in-range tap -inf
+        x[-1, H // 2, W // 2, 1] = float("nan")
+        x[0, -1, -1, 2] = float("nan")
+    OHt, OWt = (H + 2 * p - k) // s + 1 if s > 0 else 0, (W + 2 * p - k) // s + 1 if s > 0 else 0        # the documented size (floor; may be <= 0)
+    OHa, OWa = max(OHt, 1), max(OWt, 1)                                                                 # buffers for refused calls
+    G = Guards(device)
+    xd = G.inp(x)
+    y, tap = G.out(N, OHa, OWa, Cc), G.out(N * OHa * OWa * Cc, dtype=torch.uint8)
+    yflat, tapf = G.out(N, Cc * OHa * OWa), G.out(N * OHa * OWa * Cc, dtype=torch.uint8)
+    dx, dxf, dxr = G.out(N, H, W, Cc), G.out(N, H, W, Cc), G.out(N, H, W, Cc)
+    gy_t = torch.randn(N, OHa, OWa, Cc, generator=gen)
+    gy = G.inp(gy_t)
+    gyflat = G.inp(gy_t.permute(0, 3, 1, 2).reshape(N, -1))
+    tap_in = G.inp(torch.zeros(N * OHa * OWa * Cc, dtype=torch.uint8))
+    ypos = G.inp(torch.ones(N, OHa, OWa, Cc))
+    calls = {"maxpool2d_fwd": lambda: lib.maxpool2d_fwd(xd, N, H, W, C, k, s, p, y, tap),
+             "maxpool2d_fwd_flat": lambda: lib.maxpool2d_fwd_flat(xd, N, H, W, C, k, s, p, yflat, tapf),
+             "maxpool2d_bwd": lambda: lib.maxpool2d_bwd(gy, tap_in, N, H, W, C, k, s, p, dx),
+             "maxpool2d_bwd_flat": lambda: lib.maxpool2d_bwd_flat(gyflat, tap_in, N, H, W, C, k, s, p, dxf),
+             "maxpool2d_bwd_relu": lambda: lib.maxpool2d_bwd(gy, tap_in, N, H, W, C, k, s, p, dxr, relu_y=ypos)}
+    ynt = G.out(N, OHa, OWa, Cc)
+    if expect["maxpool2d_fwd_notap"]:
+        ref = F.max_pool2d(x.double().permute(0, 3, 1, 2), k, s, p).permute(0, 2, 3, 1)
+        for rep in range(2):
+            ynt.fill_(_CANARY[torch.float32])
+            lib.maxpool2d_fwd_notap(xd, N, H, W, C, k, s, p, ynt)
+            _layer_log("maxpool2d_fwd_notap", True)
+            assert _same_values(ynt, ref.float()), f"{tag}: maxpool2d_fwd_notap values"
+        ynt.fill_(_CANARY[torch.float32])                      # (a NaN output would make the refusals' before / after comparison fail)
+    else:
+        _refuses("maxpool2d_fwd_notap", lambda: lib.maxpool2d_fwd_notap(xd, N, H, W, C, k, s, p, ynt), G, tag)
+    if not expect["maxpool2d_fwd"]:
+        for e, call in calls.items():
+            _refuses(e, call, G, f"{tag}: {e}")
+        G.intact(tag)
+        return expect
+    assert (OHt, OWt) == (OHa, OWa)
+    ref, idx = F.max_pool2d(x.double().permute(0, 3, 1, 2), k, s, p, return_indices=True)
+    ref, taps = ref.permute(0, 2, 3, 1).float(), _taps_of(idx, OHt, OWt, W, k, s, p)
+    for rep in range(2):
+        y.fill_(_CANARY[torch.float32]); yflat.fill_(_CANARY[torch.float32])
+        calls["maxpool2d_fwd"](); calls["maxpool2d_fwd_flat"]()
+        _layer_log("maxpool2d_fwd", True); _layer_log("maxpool2d_fwd_flat", True)
+        assert _same_values(y, ref), f"{tag}: maxpool2d_fwd values"
+        assert torch.equal(tap.cpu().view(N, OHt, OWt, Cc), taps), f"{tag}: winning taps (ATen's rule and index)"
+        assert _same_values(yflat, ref.permute(0, 3, 1, 2).reshape(N, -1)), f"{tag}: maxpool2d_fwd_flat values"
+        assert torch.equal(tapf, tap), f"{tag}: maxpool2d_fwd_flat taps"
+    if mode != "special":
+        # float64 autograd of the pool; with ties ATen's winner is the tap the kernels recorded (checked above)
+        xr = x.double().permute(0, 3, 1, 2).clone().requires_grad_(True)
+        F.max_pool2d(xr, k, s, p).backward(gy_t.double().permute(0, 3, 1, 2))
+        refdx = xr.grad.permute(0, 2, 3, 1)
+        zr = z.double().permute(0, 3, 1, 2).clone().requires_grad_(True)          # pool(relu(z)): x = relu(z) is the pool's input
+        F.max_pool2d(torch.relu(zr), k, s, p).backward(gy_t.double().permute(0, 3, 1, 2))
+        refdz = zr.grad.permute(0, 2, 3, 1)
+        xrelu = G.inp(torch.relu(z))
+        yr, tapr = G.out(N, OHt, OWt, Cc), G.out(N * OHt * OWt * Cc, dtype=torch.uint8)
+        lib.maxpool2d_fwd(xrelu, N, H, W, C, k, s, p, yr, tapr)
+        Ldx = ((k + s - 1) // s) ** 2
+        for rep in range(2):
+            for t in (dx, dxf, dxr):
+                t.fill_(_CANARY[torch.float32])                                     # overwritten, not accumulated
+            lib.maxpool2d_bwd(gy, tap, N, H, W, C, k, s, p, dx)
+            lib.maxpool2d_bwd_flat(gyflat, tap, N, H, W, C, k, s, p, dxf)
+            lib.maxpool2d_bwd(gy, tapr, N, H, W, C, k, s, p, dxr, relu_y=yr)
+            _layer_close("maxpool2d_bwd", "pool_dx", dx, refdx, Ldx, f"{tag}: maxpool2d_bwd")
+            _layer_equal("maxpool2d_bwd_flat", dxf, dx, f"{tag}: maxpool2d_bwd_flat vs maxpool2d_bwd")
+            _layer_close("maxpool2d_bwd_relu", "pool_dx", dxr, refdz, Ldx, f"{tag}: maxpool2d_bwd_relu vs autograd of max_pool2d(relu(z))")
+    G.intact(tag)
+    return expect
+
+
+def mmpool_contract_expect(B, HW, C):
+    return B > 0 and HW > 0 and C >= 4 and C % 4 == 0
+
+
+def mmpool_contract_ref(x, p0, gy, dt=torch.float64, drop_pixel=None):
+    """MMPool((1, 1)) on x[B][HW][C] and its backward, written out; the argmax is the first maximum in scan order."""
+    x, gy = x.to(dt), gy.to(dt)
+    B, HW, C = x.shape
+    w = torch.sigmoid(torch.tensor(p0, dtype=dt))
+    xmax, am = x.max(1)
+    am = (x == xmax.unsqueeze(1)).to(torch.int64).argmax(1)          # first maximum (torch.max's choice among ties is not specified)
+    xs = x if drop_pixel is None else torch.cat([x[:, :drop_pixel], x[:, drop_pixel + 1:]], 1)
+    xavg = xs.sum(1) / HW
+    y = xmax * w + xavg * (1 - w)
+    dx = (gy * (1 - w) / HW).unsqueeze(1).expand(B, HW, C).clone()
+    dx.scatter_add_(1, am.unsqueeze(1), (gy * w).unsqueeze(1))
+    S = (gy * (xmax - xavg)).sum()
+    dp = S * w * (1 - w)                                              # (1 - w cancels for large p: the term S w is what fp32 rounds)
+    return {"y": ("mm_y", HW, y), "xavg": ("mm_y", HW, xavg), "xmax": xmax, "argmax": am, "dx": ("mm_dx", 1, dx), "dp": ("mm_dp", B * C, dp.reshape(1), float((S * w).abs()))}
+
+
+def mmpool_contract_inputs(B, HW, C, ties, seed):
+    gen = torch.Generator().manual_seed(seed)
+    Cc = max(4, (C + 3) // 4 * 4)
+    x = torch.randn(B, HW, Cc, generator=gen)
+    if ties:
+        x = torch.relu(x - 0.5)
+    return x, torch.randn(B, Cc, generator=gen)
+
+
+def mmpool_contract_case(lib, device, B, HW, C, p0=0.3, ties=False, seed=0):
+    accepted = mmpool_contract_expect(B, HW, C)
+    x_t, gy_t = mmpool_contract_inputs(B, HW, C, ties, seed)
+    Cc = x_t.shape[2]
+    tag = f"mmpool B={B} HW={HW} C={C} p={p0} ties={ties}"
+    G = Guards(device)
+    x, gy, pd = G.inp(x_t), G.inp(gy_t), G.inp(torch.tensor([p0]))
+    y, am, xmax, xavg = G.out(B, Cc), G.out(B, Cc, dtype=torch.int32), G.out(B, Cc), G.out(B, Cc)
+    dx, dp = G.out(B, HW, Cc), G.out(1)
+    if not accepted:
+        _refuses("mmpool_fwd", lambda: lib.mmpool_fwd(x, pd, B, HW, C, y, am, xmax, xavg), G, tag)
+        _refuses("mmpool_bwd", lambda: lib.mmpool_bwd(gy, pd, G.inp(torch.zeros(B, Cc, dtype=torch.int32)), gy, gy, B, HW, C, dx, dp), G, tag)
+        return False
+    ref = mmpool_contract_ref(x_t, p0, gy_t)
+    close = lambda entry, name, got: _close_ref(entry, ref, name, got, tag)
+    for rep in range(2):
+        lib.mmpool_fwd(x, pd, B, HW, C, y, am, xmax, xavg)
+        close("mmpool_fwd", "y", y); close("mmpool_fwd", "xavg", xavg)
+        _layer_equal("mmpool_fwd", xmax, ref["xmax"].float(), f"{tag}: xmax")
+        _layer_equal("mmpool_fwd", am.long(), ref["argmax"], f"{tag}: argmax (first maximum in scan order)")
+        dx.fill_(_CANARY[torch.float32]); dp.fill_(0.25)
+        lib.mmpool_bwd(gy, pd, am, xmax, xavg, B, HW, C, dx, dp)
+        close("mmpool_bwd", "dx", dx); _close_ref("mmpool_bwd", ref, "dp", dp.cpu().double() - 0.25, tag, 0.25)
+    dx2 = G.out(B, HW, Cc)
+    lib.mmpool_bwd(gy, pd, am, xmax, xavg, B, HW, C, dx2, None)                  # dp_acc may be NULL
+    _layer_equal("mmpool_bwd", dx2, dx, f"{tag}: dx with dp_acc NULL")
+    G.intact(tag)
+    return True
+
+
+# ---- depthwise convolution -------------------------------------------------------------------------------------------------------
+def dw_same_geom(N, H, W, C, K, stride):
+    """TensorFlow 'same' padding for this very input size: (N, H, W, C, K, stride, pad_top, pad_left, OH, OW)."""
+    OH, OW = -(-H // stride), -(-W // stride)
+    ph, pw = max((OH - 1) * stride + K - H, 0), max((OW - 1) * stride + K - W, 0)
+    return (N, H, W, C, K, stride, ph // 2, pw // 2, OH, OW)
+
+
+def dw_pad_geom(N, H, W, C, K, stride, pad):
+    """Symmetric explicit padding `pad` as nn.Conv2d counts the output (floor)."""
+    return (N, H, W, C, K, stride, pad, pad, (H + 2 * pad - K) // stride + 1, (W + 2 * pad - K) // stride + 1)
+
+
+def dw_contract_expect(N, H, W, C, K, stride, pt, pl, OH, OW):
+    """include/hifihr.h: C % 4 == 0, K 3 or 5, stride 1 or 2, 0 <= pad_top <= K - 1 and the implied bottom pad
+    (OH - 1) stride + K - H - pad_top within [-(stride - 1), K - 1] (columns alike).  All five entries take the same set."""
+    def axis(I, O, pad):
+        return I > 0 and O > 0 and 0 <= pad <= K - 1 and -(stride - 1) <= (O - 1) * stride + K - I - pad <= K - 1
+    return N > 0 and C >= 4 and C % 4 == 0 and K in (3, 5) and stride in (1, 2) and axis(H, OH, pt) and axis(W, OW, pl)
+
+
+def dw_contract_inputs(N, H, W, C, K, OH, OW, seed):
+    gen = torch.Generator().manual_seed(seed)
+    Cc, Kc, OHc, OWc = max(4, (C + 3) // 4 * 4), max(K, 1), max(OH, 1), max(OW, 1)
+    x = torch.randn(N, H, W, Cc, generator=gen) * 1.5 + 0.3
+    w = torch.randn(Cc, Kc, Kc, generator=gen) / Kc
+    gy = torch.randn(N, OHc, OWc, Cc, generator=gen)
+    mean, invstd = 0.3 + 0.2 * torch.randn(Cc, generator=gen), 1 / (1.5 + 0.2 * torch.rand(Cc, generator=gen))
+    gamma, beta = torch.rand(Cc, generator=gen) + 0.5, torch.randn(Cc, generator=gen) * 0.3
+    return dict(x=x, w=w, gy=gy, mean=mean, invstd=invstd, gamma=gamma, beta=beta)
+
+
+def dw_contract_ref(inp, geom, pre, dt=torch.float64, drop_tap=False):
+    """F.pad with the implied bottom / right padding + grouped F.conv2d in `dt`, gradients by autograd.  pre: the input is
+    swish(x * sc + sh) with sc = invstd gamma, sh = beta - mean sc (batch-norm + swish on load).  drop_tap: one filter tap is zeroed
+    (detection check)."""
+    import torch.nn.functional as F
+    N, H, W, C, K, stride, pt, pl, OH, OW = geom
+    x = inp["x"].to(dt).permute(0, 3, 1, 2)
+    w = inp["w"].to(dt).clone()
+    if drop_tap:
+        w[:, pt, pl] = 0                                          # the tap that meets pixel (0, 0) at output (0, 0): in range on every geometry
+    wr = w.reshape(C, 1, K, K).requires_grad_(True)
+    if pre:
+        sc = inp["invstd"].to(dt) * inp["gamma"].to(dt)
+        sh = inp["beta"].to(dt) - inp["mean"].to(dt) * sc
+        z = x * sc.view(1, C, 1, 1) + sh.view(1, C, 1, 1)
+        a = z * torch.sigmoid(z)
+    else:
+        a = x
+    a = a.detach().requires_grad_(True)
+    pb, pr = (OH - 1) * stride + K - H - pt, (OW - 1) * stride + K - W - pl
+    y = F.conv2d(F.pad(a, (pl, max(pr, 0), pt, max(pb, 0))), wr, None, stride, 0, 1, C)
+    assert y.shape[2:] == (OH, OW), (y.shape, geom)
+    y.backward(inp["gy"].to(dt).permute(0, 3, 1, 2))
+    yn = y.detach().permute(0, 2, 3, 1)
+    flat = yn.reshape(-1, C)
+    Ly = N * OH * OW
+    return {"y": ("dw_pre" if pre else "dw_fwd", K * K, yn), "sum": ("bn_sum", Ly, flat.sum(0)), "sumsq": ("bn_sum", Ly, (flat * flat).sum(0)),
+            "dx": ("dw_dgrad", K * K, a.grad.permute(0, 2, 3, 1)), "dw": ("dw_wgrad_pre" if pre else "dw_wgrad", Ly, wr.grad.reshape(C, K, K))}
+
+
+def dw_contract_case(lib, device, N, H, W, C, K, stride, pt, pl, OH, OW, seed=0):
+    """The five depthwise entries on one geometry.  Returns accepted."""
+    geom = (N, H, W, C, K, stride, pt, pl, OH, OW)
+    accepted = dw_contract_expect(*geom)
+    inp = dw_contract_inputs(N, H, W, C, K, OH, OW, seed)
+    Cc, OHc, OWc = inp["x"].shape[3], inp["gy"].shape[1], inp["gy"].shape[2]
+    tag = "dw " + "x".join(map(str, geom))
+    G = Guards(device)
+    x, w, gy, mean, invstd, gamma, beta = (G.inp(inp[k]) for k in ("x", "w", "gy", "mean", "invstd", "gamma", "beta"))
+    y, dx, dw = G.out(N, OHc, OWc, Cc), G.out(N, H, W, Cc), G.out(*inp["w"].shape)
+    stats = G.out(lib.bn_stats_floats(Cc), fill=0.0)
+    a = (N, H, W, C, OH, OW, K, stride, pt, pl)
+    calls = {"dwconv2d_fwd": lambda st=None: lib.dwconv2d_fwd(x, w, y, *a, stats=st),
+             "dwconv2d_fwd_bnswish": lambda st=None: lib.dwconv2d_fwd_bnswish(x, mean, invstd, gamma, beta, w, y, *a, stats=st),
+             "dwconv2d_bwd_data": lambda: lib.dwconv2d_bwd_data(gy, w, dx, *a),
+             "dwconv2d_bwd_weight": lambda: lib.dwconv2d_bwd_weight(x, gy, dw, *a),
+             "dwconv2d_bwd_weight_bnswish": lambda: lib.dwconv2d_bwd_weight_bnswish(x, mean, invstd, gamma, beta, gy, dw, *a)}
+    if not accepted:
+        for e, call in calls.items():
+            _refuses(e, call, G, f"{tag}: {e}")
+        assert float(stats.abs().max()) == 0.0
+        return False
+    for pre, fwd, wgrad in ((False, "dwconv2d_fwd", "dwconv2d_bwd_weight"), (True, "dwconv2d_fwd_bnswish", "dwconv2d_bwd_weight_bnswish")):
+        ref = dw_contract_ref(inp, geom, pre)
+        close = lambda entry, name, got: _close_ref(entry, ref, name, got, tag)
+        y.fill_(_CANARY[torch.float32])
+        calls[fwd]()                                                        # statistics NULL
+        close(fwd, "y", y)
+        y0 = y.clone()
+        for rep in range(2):                                                # statistics given: the same y bits, sums added to zeroed slots
+            y.fill_(_CANARY[torch.float32])
+            calls[fwd](stats)
+            _layer_equal(fwd, y, y0, f"{tag}: {fwd} with and without statistics")
+            sl = bn_slots(stats, C).sum(0).cpu()
+            close(fwd, "sum", sl[0]); close(fwd, "sumsq", sl[1])
+            stats.zero_()
+        for rep in range(2):
+            dw.fill_(0.25)                                                  # accumulates
+            calls[wgrad]()
+            _close_ref(wgrad, ref, "dw", dw.cpu().double() - 0.25, tag, 0.25)
+        if not pre:
+            for rep in range(2):
+                dx.fill_(_CANARY[torch.float32])                            # overwritten
+                calls["dwconv2d_bwd_data"]()
+                close("dwconv2d_bwd_data", "dx", dx)
+            dx0 = dx.clone()
+            calls["dwconv2d_bwd_data"]()
+            _layer_equal("dwconv2d_bwd_data", dx, dx0, f"{tag}: dwconv2d_bwd_data twice")
+    G.intact(tag)
+    return True
+
+
+# ---- squeeze-excite --------------------------------------------------------------------------------------------------------------
+def se_contract_expect(B, HW, C, SQ):
+    """include/hifihr.h: the three plain entries take any C % 4 == 0; the fused MLP pair C <= 4096 and SQ <= 256."""
+    plain = B > 0 and HW > 0 and C >= 4 and C % 4 == 0
+    mlp = B > 0 and C >= 4 and C % 4 == 0 and C <= 4096 and 1 <= SQ <= 256
+    return {"se_pool": plain, "se_scale": plain, "se_bwd_gate": plain, "se_mlp_fwd": mlp, "se_mlp_bwd": mlp}
+
+
+def se_contract_inputs(B, HW, C, SQ, seed):
+    gen = torch.Generator().manual_seed(seed)
+    rnd = lambda *s: torch.randn(*s, generator=gen)
+    Cc = max(4, (C + 3) // 4 * 4)
+    return dict(x=rnd(B, HW, Cc), gy=rnd(B, HW, Cc), gate=torch.sigmoid(rnd(B, Cc)), add=rnd(B, Cc), mean=rnd(B, Cc) * 0.5,
+                w1=rnd(SQ, Cc) / Cc ** 0.5, b1=rnd(SQ) * 0.1, w2=rnd(Cc, SQ) / SQ ** 0.5, b2=rnd(Cc) * 0.1, dgate=rnd(B, Cc))
+
+
+def se_plain_ref(inp, dt=torch.float64, drop_pixel=None):
+    x, gy, gate, add = (inp[k].to(dt) for k in ("x", "gy", "gate", "add"))
+    HW = x.shape[1]
+    keep = slice(None) if drop_pixel is None else [i for i in range(HW) if i != drop_pixel]
+    return {"pool": ("se_pool", HW, x[:, keep].sum(1) / HW), "bwd_gate": ("se_pool", HW, (gy * x)[:, keep].sum(1)),
+            "scale": ("se_y", 1, x * gate.unsqueeze(1)), "scale_add": ("se_y", 1, gy * gate.unsqueeze(1) + add.unsqueeze(1) / HW)}
+
+
+def se_mlp_fwd_ref(inp, dt=torch.float64):
+    mean, w1, b1, w2, b2 = (inp[k].to(dt) for k in ("mean", "w1", "b1", "w2", "b2"))
+    C, SQ = w1.shape[1], w1.shape[0]
+    z1 = mean @ w1.t() + b1
+    h1 = z1 * torch.sigmoid(z1)
+    gate = torch.sigmoid(h1 @ w2.t() + b2)
+    return {"mean": ("se_mlp", 1, mean), "z1": ("se_mlp", C, z1), "h1": ("se_mlp", C, h1), "gate": ("se_mlp", SQ, gate)}
+
+
+def se_mlp_bwd_ref(inp, gate, z1, h1, mean, dt=torch.float64, drop_sample=None):
+    """The MLP backward from the forward's saved tensors (gate, z1, h1, mean as the kernel wrote them)."""
+    dgate, w1, w2 = (inp[k].to(dt) for k in ("dgate", "w1", "w2"))
+    gate, z1, h1, mean = (t.detach().cpu().to(dt) for t in (gate, z1, h1, mean))
+    B, C, SQ = dgate.shape[0], w1.shape[1], w1.shape[0]
+    dz2 = dgate * gate * (1 - gate)
+    s = torch.sigmoid(z1)
+    dz1 = (dz2 @ w2) * (s + z1 * s * (1 - s))
+    keep = slice(None) if drop_sample is None else [i for i in range(B) if i != drop_sample]
+    return {"dz2": ("se_grad", 1, dz2), "dz1": ("se_grad", C, dz1), "dmean": ("se_grad", SQ, dz1 @ w1),
+            "dw1": ("se_grad", B, dz1[keep].t() @ mean[keep]), "db1": ("se_grad", B, dz1[keep].sum(0)),
+            "dw2": ("se_grad", B, dz2[keep].t() @ h1[keep]), "db2": ("se_grad", B, dz2[keep].sum(0))}
+
+
+def se_contract_case(lib, device, B, HW, C, SQ, seed=0):
+    """se_pool / se_scale / se_bwd_gate and the fused MLP pair on one geometry.  Returns {entry: accepted}."""
+    expect = se_contract_expect(B, HW, C, SQ)
+    assert lib.se_mlp_supported(C, SQ) == (C >= 4 and C % 4 == 0 and C <= 4096 and 1 <= SQ <= 256), f"se_mlp_supported({C}, {SQ})"
+    inp = se_contract_inputs(B, HW, C, max(SQ, 1), seed)
+    Cc, SQc = inp["x"].shape[2], inp["w1"].shape[0]
+    tag = f"se B={B} HW={HW} C={C} SQ={SQ}"
+    G = Guards(device)
+    x, gy, gate, add = (G.inp(inp[k]) for k in ("x", "gy", "gate", "add"))
+    acc, yo = G.out(B, Cc, fill=0.0), G.out(B, HW, Cc)
+    if not expect["se_pool"]:
+        _refuses("se_pool", lambda: lib.se_pool(x, B, HW, C, acc), G, tag)
+        _refuses("se_bwd_gate", lambda: lib.se_bwd_gate(gy, x, B, HW, C, acc), G, tag)
+        _refuses("se_scale", lambda: lib.se_scale(x, gate, None, 0.0, B, HW, C, yo), G, tag)
+    else:
+        ref = se_plain_ref(inp)
+        close = lambda entry, name, got: _close_ref(entry, ref, name, got, tag)
+        for rep in range(2):
+            acc.zero_(); lib.se_pool(x, B, HW, C, acc); close("se_pool", "pool", acc)
+            acc.zero_(); lib.se_bwd_gate(gy, x, B, HW, C, acc); close("se_bwd_gate", "bwd_gate", acc)
+        yo2 = G.out(B, HW, Cc)
+        lib.se_scale(x, gate, None, 0.0, B, HW, C, yo); close("se_scale", "scale", yo)
+        lib.se_scale(x, gate, None, 0.0, B, HW, C, yo2); _layer_equal("se_scale", yo2, yo, f"{tag}: se_scale twice")
+        lib.se_scale(gy, gate, add, 1.0 / HW, B, HW, C, yo); close("se_scale", "scale_add", yo)
+    # the fused MLP pair, on means given directly (its own bound, independent of the pooling error)
+    w1, b1, w2t, b2, dgate = G.inp(inp["w1"]), G.inp(inp["b1"]), G.inp(inp["w2"].t().contiguous()), G.inp(inp["b2"]), G.inp(inp["dgate"])
+    macc = G.out(B, Cc, fill=0.0)
+    mean, z1, h1, g2 = G.out(B, Cc), G.out(B, SQc), G.out(B, SQc), G.out(B, Cc)
+    dacc = G.out(B, Cc, fill=0.0)
+    dz2, dz1, dmean = G.out(B, Cc), G.out(B, SQc), G.out(B, Cc)
+    fw1, fb1, fw2, fb2 = G.out(SQc, Cc), G.out(SQc), G.out(Cc, SQc), G.out(Cc)
+    if not expect["se_mlp_fwd"]:
+        _refuses("se_mlp_fwd", lambda: lib.se_mlp_fwd(macc, w1, b1, w2t, b2, B, C, SQ, mean, z1, h1, g2), G, tag)
+        _refuses("se_mlp_bwd", lambda: lib.se_mlp_bwd(dacc, gate, z1, h1, gate, w1, w2t, B, C, SQ, dz2, dz1, dmean, fw1, fb1, fw2, fb2), G, tag)
+        assert float(macc.abs().max()) == 0.0 and float(dacc.abs().max()) == 0.0
+        G.intact(tag)
+        return expect
+    ref = se_mlp_fwd_ref(inp)
+    first = None
+    for rep in range(2):
+        macc.copy_(inp["mean"])
+        lib.se_mlp_fwd(macc, w1, b1, w2t, b2, B, C, SQ, mean, z1, h1, g2)
+        assert float(macc.abs().max()) == 0.0, f"{tag}: se_mlp_fwd hands the accumulator back zeroed"
+        for name, got in (("mean", mean), ("z1", z1), ("h1", h1), ("gate", g2)):
+            _close_ref("se_mlp_fwd", ref, name, got, tag)
+        now = torch.cat([t.reshape(-1) for t in (mean, z1, h1, g2)]).clone()
+        if first is not None:
+            _layer_equal("se_mlp_fwd", now, first, f"{tag}: se_mlp_fwd twice")
+        first = now
+    refb = se_mlp_bwd_ref(inp, g2, z1, h1, mean)
+    first = None
+    for rep in range(2):
+        dacc.copy_(inp["dgate"])
+        for t in (fw1, fb1, fw2, fb2):
+            t.fill_(0.25)                                                   # += semantics
+        lib.se_mlp_bwd(dacc, g2, z1, h1, mean, w1, w2t, B, C, SQ, dz2, dz1, dmean, fw1, fb1, fw2, fb2)
+        assert float(dacc.abs().max()) == 0.0, f"{tag}: se_mlp_bwd hands the accumulator back zeroed"
+        for name, got in (("dz2", dz2), ("dz1", dz1), ("dmean", dmean), ("dw1", fw1.cpu().double() - 0.25), ("db1", fb1.cpu().double() - 0.25),
+                          ("dw2", fw2.cpu().double() - 0.25), ("db2", fb2.cpu().double() - 0.25)):
+            _close_ref("se_mlp_bwd", refb, name, got, tag, 0.25 if name[1] in "wb" else 0.0)
+        now = torch.cat([t.reshape(-1) for t in (dz2, dz1, dmean, fw1, fw2, fb2)]).clone()          # (db1 goes through float atomics)
+        if first is not None:
+            _layer_equal("se_mlp_bwd", now, first, f"{tag}: se_mlp_bwd twice (every element summed by one thread in a fixed order)")
+        first = now
+    G.intact(tag)
+    return expect
+
+
+def drop_connect_contract_case(lib, device, B, per_sample, keep, with_skip, seed=0):
+    """out = x / keep * floor(keep + u[b]) (+ skip); u chosen so that both branches of the floor occur when B > 1."""
+    accepted = B > 0 and per_sample > 0 and per_sample % 4 == 0 and keep > 0
+    gen = torch.Generator().manual_seed(seed)
+    n = max(4, (per_sample + 3) // 4 * 4)
+    x_t, skip_t = torch.randn(B, n, generator=gen), torch.randn(B, n, generator=gen)
+    u_t = torch.rand(B, generator=gen)
+    u_t[0] = 0.999                                              # kept for every keep > 0.001
+    if B > 1:
+        u_t[1] = 0.0                                            # dropped whenever keep < 1
+    tag = f"drop_connect B={B} per_sample={per_sample} keep={keep} skip={with_skip}"
+    G = Guards(device)
+    x, skip, u, out = G.inp(x_t), (G.inp(skip_t) if with_skip else None), G.inp(u_t), G.out(B, n)
+    call = lambda: lib.drop_connect_add(x, skip, u, keep, B, per_sample, out)
+    if not accepted:
+        _refuses("drop_connect_add", call, G, tag)
+        return False
+    m = torch.floor(torch.tensor(keep, dtype=torch.float32) + u_t).double()         # the mask is decided in fp32, as the entry documents
+    if B > 1 and keep < 1:
+        assert set(m.tolist()) == {0.0, 1.0}
+    ref = x_t.double() / float(torch.tensor(keep, dtype=torch.float32)) * m.unsqueeze(1) + (skip_t.double() if with_skip else 0)
+    call()
+    _layer_close("drop_connect_add", "se_y", out, ref, 1, tag)
+    out2 = G.out(B, n)
+    lib.drop_connect_add(x, skip, u, keep, B, per_sample, out2)
+    _layer_equal("drop_connect_add", out2, out, tag + " twice")
+    G.intact(tag)
+    return True
+
+
+# ---- SSIM ------------------------------------------------------------------------------------------------------------------------
+SSIM_TILE = 32
+
+
+def ssim_contract_inputs(planes, H, W, kind, seed):
+    gen = torch.Generator().manual_seed(seed)
+    a = torch.rand(1, planes, H, W, generator=gen)
+    if kind == "random":
+        b = (a + 0.3 * torch.rand(1, planes, H, W, generator=gen)).clamp(0, 1)
+    elif kind == "identical":
+        b = a.clone()
+    elif kind == "constants":
+        a, b = torch.full_like(a, 0.25), torch.full_like(a, 0.75)
+    elif kind == "masked":                                      # a render-like pair: the image times a mask against the image
+        yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+        mask = (((yy - H / 2) ** 2 + (xx - W / 2) ** 2) <= (0.35 * max(H, W, 2)) ** 2).float()
+        b, a = a.clone(), a * mask
+    else:
+        raise ValueError(kind)
+    return a, b
+
+
+def _ssim_window_tensor(dt):
+    import math
+    g = torch.Tensor([math.exp(-(x - 11 // 2) ** 2 / float(2 * 1.5 ** 2)) for x in range(11)])
+    return (g / g.sum()).to(dt)                                 # the fp32 taps the kernels are handed, exact in float64
+
+
+def ssim_contract_ref(a, b, grad_out, dt=torch.float64, drop_tile=False):
+    """pytorch_ssim.ssim written out in `dt` with the three derivative maps the kernels save (d s / d mu1 in total, d s / d E[x^2],
+    d s / d E[xy]), the per-tile partial sums and the gradient d(grad_out * mean SSIM) / d img1 by autograd."""
+    import torch.nn.functional as F
+    a, b = a.to(dt), b.to(dt)
+    _, P, H, W = a.shape
+    g = _ssim_window_tensor(dt)
+    w = (g.unsqueeze(1) @ g.unsqueeze(0)).view(1, 1, 11, 11).expand(P, 1, 11, 11).contiguous()
+    ar = a.clone().requires_grad_(True)
+    conv = lambda t: F.conv2d(t, w, padding=5, groups=P)
+    mu1, mu2 = conv(ar), conv(b)
+    e11, e22, e12 = conv(ar * ar), conv(b * b), conv(ar * b)
+    C1, C2 = 0.01 ** 2, 0.03 ** 2
+    a1, a2 = 2 * mu1 * mu2 + C1, 2 * (e12 - mu1 * mu2) + C2
+    b1, b2 = mu1 * mu1 + mu2 * mu2 + C1, (e11 - mu1 * mu1) + (e22 - mu2 * mu2) + C2
+    s = a1 * a2 / (b1 * b2)
+    val = s.mean()
+    (val * grad_out).backward()
+    sd, m1, m2 = s.detach(), mu1.detach(), mu2.detach()
+    a1, a2, b1, b2 = a1.detach(), a2.detach(), b1.detach(), b2.detach()
+    dA = 2 * m2 * (a2 - a1) / (b1 * b2) - 2 * m1 * sd / b1 + 2 * m1 * sd / b2
+    dB = -sd / b2
+    dC = 2 * a1 / (b1 * b2)
+    th, tw = -(-H // SSIM_TILE), -(-W // SSIM_TILE)
+    sp = F.pad(sd[0], (0, tw * SSIM_TILE - W, 0, th * SSIM_TILE - H))
+    part = sp.view(P, th, SSIM_TILE, tw, SSIM_TILE).sum((2, 4)).reshape(-1)
+    total = part.sum() if not drop_tile else part[1:].sum()
+    n = P * H * W
+    # first-order size of the rounding of s = a1 a2 / (b1 b2) per pixel, in units of eps: a2 and b2 are differences of window moments
+    e11d, e22d, e12d = e11.detach(), e22.detach(), e12.detach()
+    cs = a1.abs() * 2 * (e12d.abs() + (m1 * m2).abs()) / (b1 * b2) + sd.abs() * (e11d + m1 * m1 + e22d + m2 * m2) / b2
+    cpart = F.pad(cs[0], (0, tw * SSIM_TILE - W, 0, th * SSIM_TILE - H)).view(P, th, SSIM_TILE, tw, SSIM_TILE).sum((2, 4))
+    return {"value": ("ssim_val", n, (total / n).reshape(1), float(cs.mean())), "partial": ("ssim_part", SSIM_TILE * SSIM_TILE, part, float(cpart.max())), "dA": ("ssim_map", 121, dA[0]),
+            "dB": ("ssim_map", 121, dB[0]), "dC": ("ssim_map", 121, dC[0]), "grad": ("ssim_grad", 121, ar.grad[0])}
+
+
+def ssim_contract_case(lib, device, planes, H, W, kind="random", seed=0, misaligned=True):
+    """ssim_fwd / ssim_bwd / ssim_bwd_scaled / ssim_finish / ssim_partial_count on one image size.  On W % 4 == 0 the whole call is repeated
+    with every plane shifted by one float (the scalar staging form): value, partials, maps and gradient must be the aligned call's bits."""
+    from hifihr_amd.ops import _ssim_window
+    win = _ssim_window()
+    a_t, b_t = ssim_contract_inputs(planes, H, W, kind, seed)
+    gout, lam = 2.0, 0.37
+    tag = f"ssim {planes}x{H}x{W} {kind}"
+    count = lib.ssim_partial_count(planes, H, W)
+    assert count == planes * (-(-H // SSIM_TILE)) * (-(-W // SSIM_TILE)), f"{tag}: ssim_partial_count"
+    assert lib.ssim_partial_count(0, H, W) == 0 and lib.ssim_partial_count(planes, 0, W) == 0
+    ref = ssim_contract_ref(a_t, b_t, gout)
+    close = lambda entry, name, got: _close_ref(entry, ref, name, got, tag)
+    G = Guards(device)
+    n = planes * H * W
+    results = []
+    for off in ((0, 1) if (misaligned and W % 4 == 0) else (0,)):
+        a, b = G.inp(a_t, offset_floats=off), G.inp(b_t, offset_floats=off)
+        part = G.out(count)
+        maps = [G.out(1, planes, H, W, offset_floats=off) for _ in range(3)]
+        g1, g2, out = G.out(1, planes, H, W), G.out(1, planes, H, W), G.out(1)
+        go = G.inp(torch.full((1,), gout))
+        for rep in range(2):
+            part.fill_(_CANARY[torch.float32])
+            lib.ssim_fwd(win, a, b, part, maps[0], maps[1], maps[2])
+            close("ssim_fwd", "partial", part)
+            close("ssim_fwd", "value", part.cpu().double().sum().reshape(1) / n)
+            for name, m in zip(("dA", "dB", "dC"), maps):
+                close("ssim_fwd", name, m)
+            g1.fill_(_CANARY[torch.float32])
+            lib.ssim_bwd(win, a, b, maps[0], maps[1], maps[2], go, g1)
+            close("ssim_bwd", "grad", g1)
+            lib.ssim_bwd_scaled(win, a, b, maps[0], maps[1], maps[2], go, -lam, g2)
+            _layer_close("ssim_bwd_scaled", "ssim_grad", g2, -lam * ref["grad"][2], 121, f"{tag}: ssim_bwd_scaled")
+            lib.ssim_finish(part, 1.0 / n, 0.0, out)
+            close("ssim_finish", "value", out)
+            now = torch.cat([t.reshape(-1).clone() for t in (part, maps[0], maps[1], maps[2], g1, g2, out)])
+            results.append(now)
+        part2 = G.out(count)
+        lib.ssim_fwd(win, a, b, part2, None, None, None)                   # without the derivative maps
+        _layer_equal("ssim_fwd", part2, part, f"{tag}: partials without the maps")
+        _refuses("ssim_fwd", lambda: lib.ssim_fwd(win, a, b, part2, maps[0], None, maps[2]), G, tag + " two of three maps")
+    for r in results[1:]:
+        _layer_equal("ssim_fwd", r, results[0], f"{tag}: a second call / the planes shifted by one float (scalar staging) give the same bits")
+    G.intact(tag)
+    return True
+
+
+def ssim_finish_contract_case(lib, device, count, seed=0):
+    """out = offset + scale * sum(partial[0 .. count)) against a float64 sum (L = count)."""
+    gen = torch.Generator().manual_seed(seed)
+    p_t = torch.rand(count, generator=gen) * 1024              # partials of a 32 x 32 tile lie in [0, 1024]
+    G = Guards(device)
+    p, out = G.inp(p_t), G.out(1)
+    for scale, offset in ((1.0 / (1024.0 * count), 0.0), (-0.37 / (1024.0 * count), 0.37)):
+        ref = float(torch.tensor(offset, dtype=torch.float32)) + float(torch.tensor(scale, dtype=torch.float32)) * p_t.double().sum()
+        lib.ssim_finish(p, scale, offset, out)
+        sref = (float(torch.tensor(scale, dtype=torch.float32)) * p_t.double().sum()).reshape(1)
+        # the bound is on the scaled sum (the offset lambda cancels most of it in the loss term)
+        err, bound = layer_err(out, ref.reshape(1)), layer_bound("ssim_val", sref, count) + 6e-8 * max(abs(offset), float(ref.abs()))
+        _layer_log("ssim_finish", True, err / bound)
+        assert err <= bound, f"ssim_finish count={count}: err {err:.3e} vs bound {bound:.3e}"
+    _refuses("ssim_finish", lambda: lib.ssim_finish(p[:0], 1.0, 0.0, out), G, "ssim_finish count 0")
+    G.intact(f"ssim_finish {count}")
+    return True

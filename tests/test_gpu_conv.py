@@ -930,3 +930,40 @@ def test_conv_dispatch_cases_cover_every_priced_direction(lib):
     cases = _cases(lib)
     assert sorted(cases) == sorted(DISPATCH_CASES)
     assert {d for expect, _, _ in cases.values() for _, d in expect} == ROOFLINE_DIRECTIONS
+
+
+# ---- the layer contract (tests/kernel_cases.py "The layer contract"): batch-norm and depthwise entries on the emulator's lists
+# (tests/test_hostsim_layer_contract.py) plus sizes the emulator cannot afford.  Pooling, squeeze-excite and SSIM: tests/test_gpu_tail.py
+from test_hostsim_layer_contract import BN_GEOMS, BN_STEM_GEOMS, DW_GEOMS  # noqa: E402
+
+# (M, C, act, residual, y_given, running)
+BN_GEOMS_GPU = [
+    (32 * 112 * 112, 64, 1, False, True, True),          # the stem's size: the grid caps of bn_grid / bn_reduce_grid engaged
+    (32 * 7 * 7, 2048, 1, True, True, True),             # ResNet-50 layer 4: ReLU + residual on four channel groups per thread
+    (48 * 14 * 14, 1392, 2, False, True, True),          # EfficientNet-b3 expand: swish above 1024 channels
+    (3, 4096, 1, True, True, True),
+]
+BN_STEM_GEOMS_GPU = [(8, 112, 112, 64), (3, 37, 21, 64)]
+# (N, H, W, C, K, stride) at TensorFlow-same padding
+DW_GEOMS_GPU = [kc.dw_same_geom(48, 56, 56, 144, 3, 2), kc.dw_same_geom(48, 14, 14, 1392, 5, 1)]
+
+
+@pytest.fixture(scope="module")
+def layer_tally():
+    yield None
+    kc.layer_contract_report("batch-norm and depthwise entries on the GPU", ("bn_", "dwconv"))
+
+
+@pytest.mark.parametrize("geo", BN_GEOMS + BN_GEOMS_GPU, ids=lambda g: "x".join(map(str, g)))
+def test_bn_contract_every_entry_on_every_geometry(lib, layer_tally, geo):
+    kc.bn_contract_case(lib, "cuda", *geo, seed=sum(map(int, geo)))
+
+
+@pytest.mark.parametrize("geo", BN_STEM_GEOMS + BN_STEM_GEOMS_GPU, ids=lambda g: "x".join(map(str, g)))
+def test_bn_stem_contract_on_every_geometry(lib, layer_tally, geo):
+    assert kc.bn_stem_contract_case(lib, "cuda", *geo, seed=sum(geo)) == kc.bn_stem_contract_expect(*geo)
+
+
+@pytest.mark.parametrize("geo", DW_GEOMS + DW_GEOMS_GPU, ids=lambda g: "x".join(map(str, g)))
+def test_dwconv_contract_every_entry_on_every_geometry(lib, layer_tally, geo):
+    assert kc.dw_contract_case(lib, "cuda", *geo, seed=sum(geo)) == kc.dw_contract_expect(*geo)

@@ -354,3 +354,50 @@ def test_texture_pca_backward_batch_tiles(lib, B, K, n):
     """texpca_bwd_kernel's (pieces of n, batch tiles) grid: one image per workgroup for a small texture, tiles of images for a large one,
     a batch that does not divide into the tiles."""
     kc.texture_pca_case(lib, "cuda", B, K, n, seed=B + K)
+
+
+# ---- the layer contract (tests/kernel_cases.py "The layer contract"): pooling, squeeze-excite and SSIM entries on the emulator's lists
+# (tests/test_hostsim_layer_contract.py) plus sizes the emulator cannot afford.  Batch-norm and depthwise: tests/test_gpu_conv.py
+from test_hostsim_layer_contract import (DROP_GEOMS, MMPOOL_GEOMS, POOL_GEOMS, SE_GEOMS, SSIM_FINISH_COUNTS,  # noqa: E402
+                                         SSIM_GEOMS)
+
+MMPOOL_GEOMS_GPU = [(48, 49, 1536, 0.3, False)]
+POOL_GEOMS_GPU = [(8, 112, 112, 64, 3, 2, 1, "ties"), (4, 57, 31, 64, 2, 2, 0, "random")]
+SE_GEOMS_GPU = [(48, 56 * 56, 144, 6), (49, 7 * 7, 2304, 96)]
+SSIM_GEOMS_GPU = [(6, 512, 512, "masked"), (6, 100, 100, "random"), (1, 224, 224, "random")]      # (37 x 21 and 1 x 1 are in the emulator's list)
+
+
+@pytest.fixture(scope="module")
+def layer_tally():
+    yield None
+    kc.layer_contract_report("pooling, squeeze-excite and SSIM entries on the GPU", ("maxpool", "mmpool", "se_", "drop_", "ssim"))
+
+
+@pytest.mark.parametrize("geo", POOL_GEOMS + POOL_GEOMS_GPU, ids=lambda g: "x".join(map(str, g)))
+def test_maxpool_contract_every_entry_on_every_geometry(lib, layer_tally, geo):
+    kc.pool_contract_case(lib, "cuda", *geo, seed=sum(geo[:7]))
+
+
+@pytest.mark.parametrize("geo", MMPOOL_GEOMS + MMPOOL_GEOMS_GPU, ids=lambda g: "x".join(map(str, g)))
+def test_mmpool_contract_on_every_geometry(lib, layer_tally, geo):
+    assert kc.mmpool_contract_case(lib, "cuda", *geo, seed=geo[0] + geo[1] + geo[2]) == kc.mmpool_contract_expect(*geo[:3])
+
+
+@pytest.mark.parametrize("geo", SE_GEOMS + SE_GEOMS_GPU, ids=lambda g: "x".join(map(str, g)))
+def test_se_contract_every_entry_on_every_geometry(lib, layer_tally, geo):
+    kc.se_contract_case(lib, "cuda", *geo, seed=sum(geo))
+
+
+@pytest.mark.parametrize("geo", DROP_GEOMS, ids=lambda g: "x".join(map(str, g)))
+def test_drop_connect_contract_on_every_geometry(lib, layer_tally, geo):
+    kc.drop_connect_contract_case(lib, "cuda", *geo, seed=geo[0] + geo[1])
+
+
+@pytest.mark.parametrize("geo", SSIM_GEOMS + SSIM_GEOMS_GPU, ids=lambda g: "x".join(map(str, g)))
+def test_ssim_contract_every_entry_on_every_geometry(lib, layer_tally, geo):
+    kc.ssim_contract_case(lib, "cuda", *geo, seed=sum(geo[:3]))
+
+
+@pytest.mark.parametrize("count", SSIM_FINISH_COUNTS)
+def test_ssim_finish_contract_on_every_count(lib, layer_tally, count):
+    kc.ssim_finish_contract_case(lib, "cuda", count, seed=count)

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Where the constants of tests/kernel_cases.py LAYER_CONTRACT_C / LAYER_CONTRACT_FLOOR come from: the layer contract's float64 references run
+in float32 -- plain fp32 PyTorch on the CPU -- over the emulator geometry lists of tests/test_hostsim_layer_contract.py, compared with the same
+references in float64.  Per kind it prints the worst  err / (sqrt(L) max|ref| + cond)  (c is 4 times that) and, over the comparisons whose
+reference is zero to rounding, the worst absolute error (the floor is 4 times that).  No kernel runs.
+
+    python tools/layer_contract_c.py
+"""
+import os
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
+import kernel_cases as kc                      # noqa: E402
+import test_hostsim_layer_contract as lists    # noqa: E402
+
+RATIO, FLOOR = {}, {}
+F32, F64 = torch.float32, torch.float64
+
+
+def note(kind, got, ref, L, cond=0.0, where=""):
+    err = kc.layer_err(got, ref)
+    scale = max(L, 1) ** 0.5 * (float(ref.abs().max()) if ref.numel() else 0.0) + cond
+    if scale < 1e-9:                            # a reference that is zero to rounding: its error is a floor, not a ratio
+        if err > FLOOR.get(kind, (0.0, ""))[0]:
+            FLOOR[kind] = (err, where)
+    elif err / scale > RATIO.get(kind, (0.0, ""))[0]:
+        RATIO[kind] = (err / scale, where)
+
+
+def both(ref64, ref32, names, where):
+    for n in names:
+        q = ref64[n]
+        note(q[0], ref32[n][2], q[2], q[1], q[3] if len(q) > 3 else 0.0, f"{where} {n}")
+
+
+def main():
+    torch.manual_seed(0)
+    for g in lists.BN_GEOMS:
+        M, C, act, residual = g[:4]
+        if not kc.bn_contract_expect(M, C)["bn_stats"] or (act == 2 and residual):
+            continue
+        inp = kc.bn_contract_inputs(M, C, residual, sum(map(int, g)))
+        r64, mid = kc.bn_contract_ref(inp, act, 1e-5, 0.1)
+        mask = (mid["z"] > 0) if act == 1 else None                       # the fp32 run keeps the float64 run's ReLU decisions
+        r32, _ = kc.bn_contract_ref(inp, act, 1e-5, 0.1, dt=F32, mask=mask)
+        both(r64, r32, ("sum", "sumsq", "mean", "invstd", "rm", "rv", "y", "y_eval", "dx", "dgamma", "dbeta"), f"bn {g}")
+    import torch.nn.functional as Fn
+    for g in lists.POOL_GEOMS:
+        N, H, W, C, k, s, p, mode = g
+        if not kc.pool_contract_expect(*g[:7])["maxpool2d_bwd"] or mode == "special":
+            continue
+        gen = torch.Generator().manual_seed(sum(g[:7]))
+        x = torch.randn(N, H, W, C, generator=gen)
+        x = torch.relu(x) if mode == "ties" else x
+        OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+        gy = torch.randn(N, OH, OW, C, generator=gen)
+        grads = []
+        for dt in (F64, F32):
+            xr = x.to(dt).permute(0, 3, 1, 2).clone().requires_grad_(True)
+            Fn.max_pool2d(xr, k, s, p).backward(gy.to(dt).permute(0, 3, 1, 2))
+            grads.append(xr.grad)
+        note("pool_dx", grads[1], grads[0], ((k + s - 1) // s) ** 2, where=f"pool {g}")
+    for g in lists.MMPOOL_GEOMS:
+        if kc.mmpool_contract_expect(*g[:3]):
+            x, gy = kc.mmpool_contract_inputs(g[0], g[1], g[2], g[4], g[0] + g[1] + g[2])
+            both(kc.mmpool_contract_ref(x, g[3], gy), kc.mmpool_contract_ref(x, g[3], gy, dt=F32), ("y", "xavg", "dx", "dp"), f"mmpool {g}")
+    for g in lists.DW_GEOMS:
+        if kc.dw_contract_expect(*g):
+            inp = kc.dw_contract_inputs(g[0], g[1], g[2], g[3], g[4], g[8], g[9], sum(g))
+            for pre in (False, True):
+                both(kc.dw_contract_ref(inp, g, pre), kc.dw_contract_ref(inp, g, pre, dt=F32), ("y", "sum", "sumsq", "dw") + (() if pre else ("dx",)),
+                     f"dw {g} pre={pre}")
+    for g in lists.SE_GEOMS:
+        B, HW, C, SQ = g
+        exp = kc.se_contract_expect(*g)
+        inp = kc.se_contract_inputs(B, HW, C, max(SQ, 1), sum(g))
+        if exp["se_pool"]:
+            both(kc.se_plain_ref(inp), kc.se_plain_ref(inp, dt=F32), ("pool", "bwd_gate", "scale", "scale_add"), f"se {g}")
+        if exp["se_mlp_fwd"]:
+            f64, f32 = kc.se_mlp_fwd_ref(inp), kc.se_mlp_fwd_ref(inp, dt=F32)
+            both(f64, f32, ("z1", "h1", "gate"), f"se {g}")
+            saved = [f32[k][2] for k in ("gate", "z1", "h1", "mean")]         # the backward starts from the fp32 forward's tensors, as the entry does
+            both(kc.se_mlp_bwd_ref(inp, *saved), kc.se_mlp_bwd_ref(inp, *saved, dt=F32), ("dz2", "dz1", "dmean", "dw1", "db1", "dw2", "db2"), f"se {g}")
+    for g in lists.DROP_GEOMS:
+        B, n, keep, with_skip = g
+        if n % 4 == 0 and keep > 0:
+            gen = torch.Generator().manual_seed(B + n)
+            x, u = torch.randn(B, n, generator=gen), torch.rand(B, generator=gen)
+            m = torch.floor(torch.tensor(keep) + u)
+            k32 = float(torch.tensor(keep, dtype=F32))
+            note("se_y", x / keep * m.unsqueeze(1), x.double() / k32 * m.double().unsqueeze(1), 1, where=f"drop {g}")
+    for g in lists.SSIM_GEOMS:
+        a, b = kc.ssim_contract_inputs(g[0], g[1], g[2], g[3], sum(g[:3]))
+        both(kc.ssim_contract_ref(a, b, 2.0), kc.ssim_contract_ref(a, b, 2.0, dt=F32), ("value", "partial", "dA", "dB", "dC", "grad"), f"ssim {g}")
+    for count in lists.SSIM_FINISH_COUNTS:
+        p = torch.rand(count, generator=torch.Generator().manual_seed(count)) * 1024
+        note("ssim_val", p.sum().reshape(1), p.double().sum().reshape(1), count, where=f"ssim_finish {count}")
+    print(f"{'kind':14s} {'fp32 torch ratio':>17s} {'x 4':>10s} {'table c':>10s} {'cap':>8s}   worst at")
+    for kind, (c, cap) in kc.LAYER_CONTRACT_C.items():
+        r, where = RATIO.get(kind, (0.0, "-"))
+        print(f"{kind:14s} {r:17.3e} {4 * r:10.2e} {c:10.2e} {cap:8.0e}   {where}")
+    print("floors (references that are zero to rounding): kind, fp32 torch's absolute error, x 4, table floor")
+    for kind, (e, where) in sorted(FLOOR.items()):
+        print(f"{kind:14s} {e:17.3e} {4 * e:10.2e} {kc.LAYER_CONTRACT_FLOOR.get(kind, 0.0):10.2e}   {where}")
+
+
+if __name__ == "__main__":
+    main()
