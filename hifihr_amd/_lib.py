@@ -47,7 +47,7 @@ def _ip(t):
 
 
 def _stream_of(t):
-    if t.is_cuda:
+    if t is not None and t.is_cuda:
         return c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
     return c_void_p(0)
 

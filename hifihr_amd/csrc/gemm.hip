@@ -1839,7 +1839,9 @@ static BgemmArgs nt_args(const NtPlan& p, const float* A, const float* B, float*
   a.tiles_n = (p.N + 127) / 128; a.tiles_m = (p.M + 127) / 128; a.splits = 1; a.cps = (p.K + 31) / 32; a.sc_split = 0;
   return a;
 }
-static bool nt_fits32(const NtPlan& p) { return (long)p.M_alloc * p.K < (1L << 31) && (long)p.N * p.K < (1L << 31); }      // 32-bit element offsets
+// 32-bit element offsets inside one problem's operands (the C entries refuse with this same predicate before they plan)
+bool bgemm_nt_fits32(long M_alloc, int N, int K) { return M_alloc * K < (1L << 31) && (long)N * K < (1L << 31); }
+static bool nt_fits32(const NtPlan& p) { return bgemm_nt_fits32(p.M_alloc, p.N, p.K); }
 
 hipError_t launch_bgemm_nt_plan(const NtPlan& p, const float* A, const float* B, float* C, void* ws, size_t ws_bytes, hipStream_t st, float* stats) {
   if (!p.ok || !nt_fits32(p)) return hipErrorInvalidValue;

@@ -1063,8 +1063,8 @@ int hifihr_linear_bwd(const float* dy, const float* y, const float* x, const flo
                       const float* z, const float* save_mean, const float* save_invstd, float* dz_scratch, float* dW_acc, float* db_acc,
                       float* dgamma_acc, float* dbeta_acc, float* dx, void* stream) {
   if (!dy || !x || !w || B <= 0 || I <= 0 || O <= 0 || act < 0 || act > 3 || ((act == 1 || act == 3) && !y) ||
-      (act == 2 && !z) || (dx && !dz_scratch))
-    return fail(HIFIHR_EINVAL, "hifihr_linear_bwd: bad argument (act 1 / 3 need y, act 2 needs z; dx needs dz_scratch)");
+      (act == 2 && !z) || (act >= 2 && gamma) || (dx && !dz_scratch))
+    return fail(HIFIHR_EINVAL, "hifihr_linear_bwd: bad argument (act 1 / 3 need y, act 2 needs z; swish / sigmoid take no batch-norm; dx needs dz_scratch)");
   if (gamma && (!z || !save_mean || !save_invstd || B > 64))
     return fail(HIFIHR_EINVAL, "hifihr_linear_bwd: batch-norm needs z, save_mean, save_invstd and B <= 64");
   hifihr::LinearArgs a{x, w, nullptr, const_cast<float*>(y), const_cast<float*>(z), gamma, nullptr, const_cast<float*>(save_mean),
@@ -1151,6 +1151,8 @@ static int wino_m(int N, int H, int W, int C, int K) {
   if (!hifihr::bgemm_nt_supported((int)T4, K, C) || !hifihr::bgemm_nt_supported((int)T4, C, K) || !hifihr::bgemm_tn_supported(K, C, (int)T4)) return 2;
   return 4;
 }
+// one rule for every _m entry: the output-tile edge is 2 (F(2x2, 3x3)) or 4 (F(4x4, 3x3)); anything else is refused, the queries answer 0
+static bool wino_m_ok(int m) { return m == 2 || m == 4; }
 static long wino_T(int m, int N, int H, int W) { return m == 4 ? hifihr::wino4_tiles(N, H, W) : (long)N * ((H + m - 1) / m) * ((W + m - 1) / m); }
 
 long hifihr_wino_tiles(int N, int H, int W, int m) { return (N > 0 && H > 0 && W > 0 && (m == 2 || m == 4)) ? wino_T(m, N, H, W) : 0; }
@@ -1165,7 +1167,7 @@ int hifihr_wino_tile(int N, int H, int W, int C, int K) {
 }
 
 size_t hifihr_wino_gemm_workspace_bytes_m(int N, int H, int W, int C, int K, int m) {
-  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return 0;
+  if (!wino_m_ok(m) || N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return 0;
   if (m == 4) return hifihr::bgemm_nt_workspace_bytes((int)wino_T(4, N, H, W), K, C, 36);
   return hifihr_wino_gemm_workspace_bytes(N, H, W, C, K);
 }
@@ -1183,6 +1185,8 @@ size_t hifihr_bgemm_nt_workspace_bytes(int M, int N, int K, int batch) { return 
 int hifihr_bgemm_nt(const float* A, const float* B, float* C, int M, int N, int K, int batch, void* ws, size_t ws_bytes, void* stream) {
   if (!A || !B || !C || batch <= 0 || !hifihr::bgemm_nt_supported(M, N, K))
     return fail(HIFIHR_EINVAL, "hifihr_bgemm_nt: bad argument (K % 32 == 0, N % 64 == 0)");
+  if (!hifihr::bgemm_nt_fits32(M, N, K))         // the kernels index an operand of one problem with 32-bit element offsets
+    return fail(HIFIHR_EINVAL, "hifihr_bgemm_nt: M * K and N * K must stay below 2^31 elements");
   HIP_TRY(hifihr::launch_bgemm_nt(A, B, C, M, N, K, batch, ws, ws_bytes, (hipStream_t)stream));
   return HIFIHR_OK;
 }
@@ -1209,12 +1213,14 @@ int hifihr_bgemm_tn_parts(int M, int N, int T, int batch) {
 int hifihr_bgemm_tn(const float* A, const float* B, float* C_parts, int M, int N, int T, int batch, int parts, void* stream) {
   if (!A || !B || !C_parts || batch <= 0 || parts <= 0 || !hifihr::bgemm_tn_supported(M, N, T))
     return fail(HIFIHR_EINVAL, "hifihr_bgemm_tn: bad argument (M % 64 == 0, N % 64 == 0)");
+  if (parts != hifihr::bgemm_tn_parts(M, N, T, batch))
+    return fail(HIFIHR_EINVAL, "hifihr_bgemm_tn: parts must be hifihr_bgemm_tn_parts(M, N, T, batch)");
   HIP_TRY(hifihr::launch_bgemm_tn(A, B, C_parts, M, N, T, batch, parts, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 
 int hifihr_wino_wgrad_parts_m(int N, int H, int W, int C, int K, int m) {
-  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || !use_bgemm()) return 0;
+  if (!wino_m_ok(m) || N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || !use_bgemm()) return 0;
   if (m == 4) {
     const long T4 = wino_T(4, N, H, W);
     return (T4 < (1L << 30) && hifihr::bgemm_tn_supported(K, C, (int)T4)) ? hifihr::bgemm_tn_parts(K, C, (int)T4, 36) : 0;
@@ -1230,6 +1236,7 @@ int hifihr_wino_wgrad_parts(int N, int H, int W, int C, int K) {
 }
 
 int hifihr_wino_wgrad_gemm_parts_m(const float* V, const float* Y, float* dU_parts, int N, int H, int W, int C, int K, int parts, int m, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_wgrad_gemm_parts: m must be 2 or 4");
   if (m != 4) return hifihr_wino_wgrad_gemm_parts(V, Y, dU_parts, N, H, W, C, K, parts, stream);
   if (!V || !Y || !dU_parts || N <= 0 || H <= 0 || W <= 0 || parts <= 0)
     return fail(HIFIHR_EINVAL, "hifihr_wino_wgrad_gemm_parts: bad argument");
@@ -1285,6 +1292,7 @@ int hifihr_wino_weight_transform(const float* w, float* U, int K, int C, int fli
 }
 
 int hifihr_wino_input_transform_m(const float* x, float* V, int N, int H, int W, int C, int m, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_input_transform: m must be 2 or 4");
   if (m != 4) return hifihr_wino_input_transform(x, V, N, H, W, C, stream);
   if (!x || !V || N <= 0 || H <= 0 || W <= 0 || C < 4 || C % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_input_transform: bad argument");
   HIP_TRY(hifihr::launch_wino4_input_transform(x, V, nullptr, N, H, W, C, (hipStream_t)stream));
@@ -1292,10 +1300,12 @@ int hifihr_wino_input_transform_m(const float* x, float* V, int N, int H, int W,
 }
 
 int hifihr_wino_gemm_m(const float* V, const float* U, float* M, int N, int H, int W, int C, int K, int m, void* ws, size_t ws_bytes, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: m must be 2 or 4");
   if (m != 4) return hifihr_wino_gemm(V, U, M, N, H, W, C, K, ws, ws_bytes, stream);
   const long T4 = (N > 0 && H > 0 && W > 0) ? wino_T(4, N, H, W) : 0;
   if (!V || !U || !M || T4 <= 0 || T4 >= (1L << 30) || !hifihr::bgemm_nt_supported((int)T4, K, C))
     return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: bad argument (F(4x4, 3x3) needs C % 32 == 0, K % 64 == 0)");
+  if (!hifihr::bgemm_nt_fits32(T4, K, C)) return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: T * C and K * C must stay below 2^31 elements");
   const long Tr = hifihr::wino4_tiles_real(N, H, W);       // mosaic tiles: the rows behind the last mosaic are padding (zeros in V, unread in M)
   HIP_TRY(hifihr::launch_bgemm_nt(V, U, M, (int)(Tr < T4 ? Tr : T4), K, C, 36, ws, ws_bytes, (hipStream_t)stream, nullptr, (int)T4));
   return HIFIHR_OK;
@@ -1314,6 +1324,7 @@ int hifihr_wino4_bwd_gemm_pair(const float* V2, const float* U2, float* M2, cons
   if (!V2 || !U2 || !M2 || !Vx || !Yt || !dU_parts || T4 <= 0 || T4 >= (1L << 30) || parts <= 0 || !hifihr::bgemm_nt_supported((int)T4, C, K) ||
       !hifihr::bgemm_tn_supported(K, C, (int)T4) || parts != hifihr::bgemm_tn_parts(K, C, (int)T4, 36))
     return fail(HIFIHR_EINVAL, "hifihr_wino4_bwd_gemm_pair: bad argument (C, K % 64 == 0; parts = hifihr_wino_wgrad_parts_m(N, H, W, C, K, 4))");
+  if (!hifihr::bgemm_nt_fits32(T4, C, K)) return fail(HIFIHR_EINVAL, "hifihr_wino4_bwd_gemm_pair: T * K and C * K must stay below 2^31 elements");
   const long Tr = hifihr::wino4_tiles_real(N, H, W);
   const hipError_t e = hifihr::launch_bgemm_nt_tn_pair(V2, U2, M2, (int)(Tr < T4 ? Tr : T4), (int)T4, C, K, 36, Yt, Vx, dU_parts, K, C, (int)T4, 36,
                                                        parts, (hipStream_t)stream, (int)(Tr < T4 ? Tr : T4));
@@ -1326,6 +1337,7 @@ int hifihr_wino4_bwd_gemm_pair(const float* V2, const float* U2, float* M2, cons
 }
 
 int hifihr_wino_dy_transform_m(const float* dy, float* Y, int N, int H, int W, int K, int m, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_dy_transform: m must be 2 or 4");
   if (m != 4) return hifihr_wino_dy_transform(dy, Y, N, H, W, K, stream);
   if (!dy || !Y || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_dy_transform: bad argument");
   HIP_TRY(hifihr::launch_wino4_dy_transform(dy, Y, N, H, W, K, (hipStream_t)stream));
@@ -1333,6 +1345,7 @@ int hifihr_wino_dy_transform_m(const float* dy, float* Y, int N, int H, int W, i
 }
 
 int hifihr_wino_output_transform_m(const float* M, float* y, float* stats, int N, int H, int W, int K, int m, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform: m must be 2 or 4");
   if (m != 4) return hifihr_wino_output_transform(M, y, stats, N, H, W, K, stream);
   if (!M || !y || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform: bad argument");
   HIP_TRY(hifihr::launch_wino4_output_transform(M, y, stats, nullptr, 0, nullptr, N, H, W, K, (hipStream_t)stream));
@@ -1433,6 +1446,7 @@ int hifihr_bn_bwd_apply(const float* g, const float* x, const float* save_mean, 
 }
 
 int hifihr_wino_input_dy_transform_m(const float* dy, float* V, float* Yt, int N, int H, int W, int K, int m, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_input_dy_transform: m must be 2 or 4");
   if (m != 4) return hifihr_wino_input_dy_transform(dy, V, Yt, N, H, W, K, stream);
   if (!dy || !V || !Yt || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0)
     return fail(HIFIHR_EINVAL, "hifihr_wino_input_dy_transform: bad argument");
@@ -1441,6 +1455,7 @@ int hifihr_wino_input_dy_transform_m(const float* dy, float* V, float* Yt, int N
 }
 
 int hifihr_wino_output_transform_act_m(const float* M, float* y, const float* bias, int act, int N, int H, int W, int K, int m, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_act: m must be 2 or 4");
   if (m != 4) return hifihr_wino_output_transform_act(M, y, bias, act, N, H, W, K, stream);
   if (!M || !y || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0 || act < 0 || act > 1)
     return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_act: bad argument");
@@ -1467,6 +1482,7 @@ int hifihr_wino_gemm(const float* V, const float* U, float* M, int N, int H, int
     return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: bad argument (C % 32 == 0, K % 4 == 0)");
   const long T = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
   if (use_bgemm() && T < (1L << 30) && hifihr::bgemm_nt_supported((int)T, K, C)) {
+    if (!hifihr::bgemm_nt_fits32(T, K, C)) return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: T * C and K * C must stay below 2^31 elements");
     HIP_TRY(hifihr::launch_bgemm_nt(V, U, M, (int)T, K, C, 16, ws, ws_bytes, (hipStream_t)stream));
     return HIFIHR_OK;
   }

@@ -440,6 +440,7 @@ struct BgemmArgs {
 void bgemm_describe(int tn, int M, int N, int K, char* out, int cap);
 void bgemm_describe_batch(int tn, int M, int N, int K, int batch, char* out, int cap);
 bool bgemm_nt_supported(int M, int N, int K);
+bool bgemm_nt_fits32(long M_alloc, int N, int K);      // operands of one problem below 2^31 elements (M_alloc: rows allocated per problem)
 bool bgemm_tn_supported(int M, int N, int T);
 size_t bgemm_nt_workspace_bytes(int M, int N, int K, int batch);
 bool bgemm_nt_stats_supported(int N);      // launch_bgemm_nt(..., stats != null) is available for this N

@@ -317,8 +317,17 @@ int hifihr_wino_output_transform_act(const float* m_d, float* y_d, const float* 
                                      int K, void* stream);
 /* Winograd F(4x4, 3x3) (csrc/wino4.hip): the same pipeline with 4x4 output tiles -- 36 positions, T = N * ceil(H/4) * ceil(W/4), 4x fewer
  * multiplications than the direct convolution (F(2x2, 3x3): 2.25x), results within 1e-5 of it.  Every entry point above has an `_m`
- * form that takes the tile edge m (2 or 4; the plain names are m = 2); all calls of one layer must use the same m, and buffers are sized
+ * form that takes the tile edge m (2 or 4; the plain names are m = 2; ANY other m is refused with HIFIHR_EINVAL by every _m entry, and the
+ * _m queries -- hifihr_wino_tiles, _tiles_computed, _gemm_workspace_bytes_m, _wgrad_parts_m -- answer 0 for it: no entry falls back to
+ * F(2x2, 3x3) on an m it does not know); all calls of one layer must use the same m, and buffers are sized
  * with P = (m + 2)^2 positions: U[P][K][C], V[P][T][C], M[P][T][K], Y'[P][T][K], du_parts[parts][P][K][C].
+ * The transforms of both tile edges take ANY N, H, W > 0 -- images smaller than one tile included (H or W of 1, 2, 3 at m = 4: the tile is
+ * zero-padded like any ragged last tile) -- and any C resp. K that is a multiple of 4; the weight and dw transforms any K > 0.  They write every
+ * row t < hifihr_wino_tiles_computed of V / Y' and ZEROS into the rows behind it (the padding of the mosaic form); the output transforms read
+ * rows t < hifihr_wino_tiles_computed of M only, and the products may leave the rows of M behind it unwritten.  act of the _act forms is 0 or 1.
+ * The products on csrc/gemm.hip (hifihr_wino_gemm[_m], hifihr_wino4_bwd_gemm_pair) refuse, like hifihr_bgemm_nt, operands of 2^31 elements or
+ * more per position (T * C, T * K, K * C) with HIFIHR_EINVAL.
+ * (tests/test_hostsim_gemm_contract.py holds every entry to this, around a float64 product, against float64 conv2d.)
  * hifihr_wino_tile(N, H, W, C, K) returns the m this library prefers for a layer: 4 where the batched GEMMs of csrc/gemm.hip take the
  * shape in all three directions (C % 64 == 0, K % 64 == 0, H, W >= 4), else 2.  m = 4 has the slab form of backward-weight only
  * (hifihr_wino_wgrad_parts_m > 0).  The per-step weight re-layout (hifihr_weight_prep) has job kinds 3 / 4 for U[36][K][C] / U'[36][C][K]. */
@@ -449,6 +458,18 @@ int hifihr_wino4_dw_transform_multi(const hifihr_wino_dw_job* jobs, int njobs, v
  *                    balanced kernel (one workgroup per CU, stream-K shares), else one workgroup per tile
  *   hifihr_bgemm_tn: c_parts[z][b][M][N] = sum over the t rows of slab z of a[b][t][M] (x) b[b][t][N]   (M, N % 64 == 0, any T);
  *                    `parts` = hifihr_bgemm_tn_parts(M, N, T, batch) slabs, to be summed by the consumer (no atomics).
+ *                    Slab z holds the rows  32 cps z <= t < min(T, 32 cps (z + 1)),  cps = ceil(ceil(T / 32) / parts)  chunks of 32 rows
+ *                    per slab; no slab is empty, every element of every slab is written (overwritten, not accumulated).
+ * The contract of these entries (tests/test_hostsim_gemm_contract.py):
+ *   - M, N, K / T, batch > 0 and the multiples above, non-null a, b, c; hifihr_bgemm_nt also M * K < 2^31 and N * K < 2^31 (the kernels
+ *     index one problem's operand with 32-bit element offsets).  Anything else: HIFIHR_EINVAL, nothing written.
+ *   - hifihr_bgemm_tn takes exactly parts == hifihr_bgemm_tn_parts(M, N, T, batch); any other count (0, parts + 1, ...) is HIFIHR_EINVAL.
+ *     hifihr_bgemm_tn_parts answers 0 for a shape hifihr_bgemm_tn refuses.
+ *   - hifihr_bgemm_nt_workspace_bytes answers 0 for a shape that needs no workspace or that hifihr_bgemm_nt refuses.  A workspace that is
+ *     NULL or smaller than that is not an error: the product runs with one workgroup per tile and the workspace is not touched.
+ *   - hifihr_bgemm_nt writes every element of c once and reads nothing of it; operands are read inside a[b][M][K] / b[b][N][K] only.
+ *   - hifihr_bgemm_describe[_batch]: out non-null, cap >= 8, batch > 0, else HIFIHR_EINVAL; "" for a shape the product entries refuse.
+ *   - two calls on the same operands give the same bits (no atomics; the stream-K kernel hands its tiles over in a fixed order).
  * Winograd backward-weight on it: parts = hifihr_wino_wgrad_parts(N, H, W, C, K) (0: shape unsupported, use hifihr_wino_wgrad_gemm),
  *   hifihr_wino_wgrad_gemm_parts(V, Y', du_parts[parts][16][K][C])  then
  *   hifihr_wino_dw_transform_parts: dw[K][3][3][C] += G^T (sum of the slabs) G   -- nothing zero-initialised, bit-reproducible. */
@@ -464,7 +485,8 @@ int hifihr_wino_wgrad_parts(int N, int H, int W, int C, int K);
 int hifihr_wino_wgrad_gemm_parts(const float* v_d, const float* yt_d, float* du_parts_d, int N, int H, int W, int C, int K, int parts,
                                  void* stream);
 int hifihr_wino_dw_transform_parts(const float* du_parts_d, int parts, float* dw_acc_d, int K, int C, void* stream);
-/* [K][RS][C] -> [C][RS][K] (the transpose backward-data consumes). */
+/* [K][RS][C] -> [C][RS][K] (the transpose backward-data consumes).  K, RS, C > 0 (any values: no multiple is required), non-null pointers,
+ * else HIFIHR_EINVAL; every element of wt_d is written once. */
 int hifihr_weight_transpose(const float* w_d, float* wt_d, int K, int RS, int C, void* stream);
 /* hifihr_conv2d_bwd_data on weights that are ALREADY transposed to [C][R][S][K] (hifihr_weight_transpose / hifihr_weight_prep). */
 int hifihr_conv2d_bwd_data_pre(const float* dy_d, const float* wt_d, float* dx_d, int N, int H, int W, int C, int K, int R, int S,
@@ -498,7 +520,8 @@ int hifihr_conv2d_bwd_weight_plus1x1(const float* x_d, const float* dy_d, float*
  *   kind 2: dst = U'[16][C][K], the backward-data weights of src[K][3][3][C]              (= weight_transpose + transform, flip 1)
  *   kind 3 / 4: the F(4x4, 3x3) forms of 1 / 2, U[36][K][C] / U'[36][C][K]
  *   kind 5: dst[K][RS][C4] = src[K][RS][C] with the channels zero-padded to C4 = the next multiple of 4 (the 3-channel stem filter)
- * blocks_per_job: workgroups per job (each job is a grid-stride loop). */
+ * blocks_per_job: workgroups per job (each job is a grid-stride loop; any count > 0 gives the same bits).  jobs_d NULL, njobs <= 0 or
+ * blocks_per_job <= 0: HIFIHR_EINVAL, nothing written.  Every job's dst equals, bit for bit, what the separate entry it names writes. */
 typedef struct hifihr_prep_job {
   const float* src;
   float* dst;
@@ -787,6 +810,14 @@ int hifihr_loss_total_bwd(const float* gtotal_d, float* const* grads, const int*
  * (unbiased variance), z_d[B][O] receives the pre-normalisation output, save_mean_d / save_invstd_d[O] the statistics.
  * bwd: dy_d = gradient of y; y_d (act 1) gives the ReLU mask; dz_scratch_d[B][O]; dW_acc_d[O][I], db_acc_d[O],
  *      dgamma_acc_d[O], dbeta_acc_d[O] ACCUMULATE (pass the gradient buffers); dx_d[B][I] is overwritten (NULL: skipped).
+ * The contract of these entries (tests/test_hostsim_gemm_contract.py):
+ *   - B, I, O > 0 (any values), act 0..3, non-null x, w, y (fwd) / dy, x, w (bwd); act 1 / 3 need y_d and act 2 needs z_d in the backward,
+ *     act 2 needs z_d in the forward, dx_d needs dz_scratch_d.  Batch-norm: B <= 64, act 0 / 1 only (both directions), beta, z, save_mean,
+ *     save_invstd given, running_mean_d and running_var_d both or neither.  Anything else: HIFIHR_EINVAL, nothing written.
+ *   - z_d is written only with batch-norm or act 2, save_mean_d / save_invstd_d only with batch-norm, the running statistics only when given.
+ *   - B = 1 with batch-norm (nn.BatchNorm1d raises): the hifihr_bn_* rule for M = 1 -- variance 0, save_invstd = 1 / sqrt(eps),
+ *     y = act(beta) to rounding, the running variance takes the BIASED value (0), dz and so dW, dx vanish.
+ *   - two calls give the same bits, EXCEPT dx_d at O > 64: it is summed over 64-feature splits of O with fp32 atomics (equal up to their order).
  * ---------------------------------------------------------------------------------------------- */
 int hifihr_linear_fwd(const float* x_d, const float* w_d, const float* b_d /* or NULL */, int B, int I, int O, int act,
                       const float* gamma_d /* or NULL: no batch-norm */, const float* beta_d, float eps, float momentum,
@@ -800,7 +831,9 @@ int hifihr_linear_bwd(const float* dy_d, const float* y_d, const float* x_d, con
 /* Grouped launches for independent layers of the same depth (the HandEncoder's five to six heads, reference
  * network/res_encoder.py:112-131, 146-160): up to 6 members per call, no batch-norm, act 0 / 1; one launch forward, two backward
  * instead of one / two PER LAYER (each is a latency-bound ~8 us kernel on 8-32 workgroups).  `descs` is a HOST array.
- * bwd members: dy, y (act 1), dz_scratch[B][O] required; dW_acc / db_acc accumulate (NULL: skipped); dx overwritten (NULL: skipped). */
+ * bwd members: dy, y (act 1), dz_scratch[B][O] required; dW_acc / db_acc accumulate (NULL: skipped); dx overwritten (NULL: skipped).
+ * n outside 1..6, a member with act 2 / 3, a null x / w / y or a size <= 0: HIFIHR_EINVAL, nothing written.  Members may differ in B, I, O;
+ * every member's results are bit-identical to its single launch (dx at O > 64: up to the order of its atomics). */
 typedef struct hifihr_linear_desc {
   const float *x, *w, *b; /* b may be NULL */
   float* y;

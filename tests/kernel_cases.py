@@ -3267,3 +3267,905 @@ def ssim_finish_contract_case(lib, device, count, seed=0):
     _refuses("ssim_finish", lambda: lib.ssim_finish(p[:0], 1.0, 0.0, out), G, "ssim_finish count 0")
     G.intact(f"ssim_finish {count}")
     return True
+
+
+# ------------------------------------------------------------------------------------------------
+# The GEMM contract: the batched products of csrc/gemm.hip and hifihr_weight_transpose on fixed shape lists
+# (tests/test_hostsim_gemm_contract.py; the GPU half in tests/test_gpu_gemm.py), in the layer contract's form: an entry refuses
+# (HIFIHR_EINVAL, outputs untouched) or matches torch.matmul in float64 inside NaN / canary guard bands, twice on the same workspace with
+# identical bits.  Two input families: randn (bound c sqrt(L) max|ref|, kinds gemm_nt / gemm_tn below) and small integers, whose products
+# and partial sums are all exact in fp32 -- the result then equals the float64 reference BIT FOR BIT whatever the summation order, so a
+# dropped, repeated or permuted k-step or a share boundary off by one fails at any tolerance.
+# ------------------------------------------------------------------------------------------------
+GEMM_CONTRACT_ENTRIES = ("bgemm", "weight_transpose", "weight_prep", "linear", "wino", "_wino", "_weight_prep")      # prefixes of the entries this contract logs (LAYER_CONTRACT_LOG)
+GEMM_CONTRACT_KINDS = ("gemm_nt", "gemm_tn", "lin_y", "lin_stat", "lin_bn_y", "lin_dw", "lin_dx")
+LAYER_CONTRACT_C.update({
+    # kind: (c, cap)                  fp32 torch's worst ratio (tools/layer_contract_c.py) x 4; the quantities and L; (where cap comes from)
+    "gemm_nt": (2.2e-7, 2e-6),        # 5.41e-08 x 4   hifihr_bgemm_nt c, L = K       (bgemm_case: 2e-6 sqrt(K); c <= 2e-6 keeps c sqrt(L) below it at every K >= 1)
+    "gemm_tn": (1.9e-7, 2e-6),        # 4.70e-08 x 4   hifihr_bgemm_tn slabs (L = rows of the slab) and their sum (L = T)   (bgemm_tn_case: 2e-6 sqrt(T))
+    #                                  (the emulator's worst err / bound is 0.59, above one half, on the 259-row slabs of 256 x 256 x 777: the kernel adds its
+    #                                  k-steps to ONE accumulator in t order, whose rounding grows with the running sum, where fp32 torch -- the
+    #                                  measure of c -- sums in blocks; the next shapes sit at 0.35 and below)
+})
+GEMM_INT_A, GEMM_INT_B = 30, 26        # |a| <= 30, |b| <= 26 in the integer family: 780 L < 2^24 for every L <= 21 509
+
+
+def gemm_operands(fill, batch, rows_a, rows_b, L, seed, transposed):
+    """a[batch][rows_a][L], b[batch][rows_b][L] (transposed: [batch][L][rows]) -- randn, or integers that differ from row to row and from
+    k to k with different periods in a and b (61 and 53: the pair (a, b) at one k repeats after 3233 steps only)."""
+    if fill == "randn":
+        gen = torch.Generator().manual_seed(seed)
+        a, b = torch.randn(batch, rows_a, L, generator=gen), torch.randn(batch, rows_b, L, generator=gen)
+    else:
+        p = torch.arange(batch).view(-1, 1, 1)
+        k = torch.arange(L).view(1, 1, -1)
+        ra, rb = torch.arange(rows_a).view(1, -1, 1), torch.arange(rows_b).view(1, -1, 1)
+        a = ((ra * 7 + k * 13 + p * 3 + seed) % (2 * GEMM_INT_A + 1) - GEMM_INT_A).float()
+        b = ((rb * 11 + k * 17 + p * 5 + seed) % (2 * GEMM_INT_B + 1) - GEMM_INT_B).float()
+    if transposed:
+        a, b = a.transpose(1, 2).contiguous(), b.transpose(1, 2).contiguous()
+    return a, b
+
+
+def gemm_ints_exact(L):
+    """every partial sum of the integer family is an integer below 2^24: exact in fp32"""
+    return GEMM_INT_A * GEMM_INT_B * L < 2 ** 24
+
+
+def bgemm_nt_expect(M, N, K, batch):
+    """include/hifihr.h: K % 32 == 0, N % 64 == 0, any M > 0, batch > 0, operands below 2^31 elements per problem."""
+    return M > 0 and batch > 0 and K >= 32 and K % 32 == 0 and N >= 64 and N % 64 == 0 and M * K < 2 ** 31 and N * K < 2 ** 31
+
+
+def bgemm_tn_expect(M, N, T, batch):
+    return T > 0 and batch > 0 and M >= 64 and M % 64 == 0 and N >= 64 and N % 64 == 0
+
+
+def bgemm_tn_slab_rows(T, parts, z):
+    """include/hifihr.h: slab z of `parts` holds rows 32 cps z <= t < min(T, 32 cps (z + 1)), cps = ceil(ceil(T / 32) / parts)."""
+    cps = -(-(-(-T // 32)) // parts)
+    return 32 * cps * z, min(T, 32 * cps * (z + 1))
+
+
+def bgemm_nt_contract_case(lib, device, M, N, K, batch, ws_mode="full", seed=0, fills=("randn", "ints"), drop=None):
+    """hifihr_bgemm_nt / _workspace_bytes / _describe_batch on one shape.  ws_mode: "full" (what the query asks for), "short" (one float
+    less: the per-tile fallback, workspace untouched), "none".  -> (accepted, workspace bytes the shape asks for)."""
+    what = f"bgemm_nt {M}x{N}x{K}x{batch} ({ws_mode})"
+    if not bgemm_nt_expect(M, N, K, batch):
+        G = Guards(device)
+        small = M * K < 2 ** 31 and N * K < 2 ** 31          # (beyond 32-bit offsets: the predicate path alone, nothing large is allocated)
+        a = G.inp(torch.zeros(max(batch, 1), max(M, 1) if small else 1, max(K, 1)))
+        b = G.inp(torch.zeros(max(batch, 1), max(N, 1) if small else 1, max(K, 1)))
+        c = G.out(max(batch, 1), max(M, 1) if small else 1, max(N, 1))
+        _refuses("bgemm_nt", lambda: lib.bgemm_nt(a, b, c, M, N, K, batch), G, what)
+        if small:
+            assert lib.bgemm_nt_workspace_bytes(M, N, K, batch) == 0, f"{what}: a workspace for a refused shape"
+            assert batch <= 0 or lib.bgemm_describe(False, M, N, K, batch) == "", f"{what}: a kernel name for a refused shape"
+        return False, 0
+    nb = lib.bgemm_nt_workspace_bytes(M, N, K, batch)
+    assert nb % 4 == 0
+    assert lib.bgemm_describe(False, M, N, K, batch) != ""
+    G = Guards(device)
+    c = G.out(batch, M, N)
+    nws = {"full": nb // 4, "short": nb // 4 - 1, "none": 0}[ws_mode]
+    ws = G.out(nws, fill=0.0) if nws > 0 else None                       # ONE workspace for every run of the case
+    for fill in fills:
+        a, b = gemm_operands(fill, batch, M, N, K, seed, False)
+        ref = torch.matmul(a.double(), b.double().transpose(1, 2))
+        ad, bd = G.inp(a), G.inp(b)
+        first = None
+        for rep in range(2 if fill == fills[0] else 1):                   # the first family twice: identical bits
+            c.fill_(_CANARY[torch.float32])
+            lib.bgemm_nt(ad, bd, c, M, N, K, batch, ws=ws)
+            tag = f"{what} {fill} rep {rep}"
+            G.intact(tag)
+            assert ws is None or float(ws.abs().max()) == 0.0, f"{tag}: workspace not handed back all zero"
+            if fill == "ints":
+                assert gemm_ints_exact(K)
+                _layer_equal("bgemm_nt", c, ref.float(), tag)
+            else:
+                _layer_close("bgemm_nt", "gemm_nt", c, ref, K, tag)
+            assert first is None or torch.equal(first, c), f"{what} {fill}: two runs differ"
+            first = c.clone()
+    c.fill_(_CANARY[torch.float32])
+    for args in ((None, bd, c), (ad, None, c), (ad, bd, None)):
+        _refuses("bgemm_nt", lambda: lib.bgemm_nt(*args, M, N, K, batch), G, f"{what}: null pointer")
+    return True, nb
+
+
+def bgemm_tn_contract_case(lib, device, M, N, T, batch, seed=0, fills=("randn", "ints")):
+    """hifihr_bgemm_tn / _tn_parts / _describe_batch on one shape: every slab against the rows the header gives it, and the slabs' sum.
+    -> slab count (0: refused)."""
+    what = f"bgemm_tn {M}x{N}x{T}x{batch}"
+    parts = lib.bgemm_tn_parts(M, N, T, batch)
+    if not bgemm_tn_expect(M, N, T, batch):
+        assert parts == 0, f"{what}: slabs for a refused shape"
+        G = Guards(device)
+        a = G.inp(torch.zeros(max(batch, 1), max(T, 1), max(M, 1)))
+        b = G.inp(torch.zeros(max(batch, 1), max(T, 1), max(N, 1)))
+        c = G.out(2, max(batch, 1), max(M, 1), max(N, 1))
+        for p in (1, 2):
+            _refuses("bgemm_tn", lambda: lib.bgemm_tn(a, b, c, M, N, T, batch, p), G, what)
+        assert batch <= 0 or lib.bgemm_describe(True, M, N, T, batch) == "", f"{what}: a kernel name for a refused shape"
+        return 0
+    assert parts >= 1 and lib.bgemm_describe(True, M, N, T, batch) != ""
+    rows = [bgemm_tn_slab_rows(T, parts, z) for z in range(parts)]
+    assert all(lo < hi for lo, hi in rows) and rows[-1][1] == T, f"{what}: {parts} slabs leave one empty or rows uncovered ({rows})"
+    G = Guards(device)
+    cp = G.out(parts + 1, batch, M, N)                                           # (one slab more than asked for: room for the refused calls below)
+    for fill in fills:
+        a, b = gemm_operands(fill, batch, M, N, T, seed, True)                   # a[batch][T][M], b[batch][T][N]
+        a64, b64 = a.double(), b.double()
+        ad, bd = G.inp(a), G.inp(b)
+        first = None
+        for rep in range(2 if fill == fills[0] else 1):                           # the first family twice: identical bits
+            cp.fill_(_CANARY[torch.float32])
+            lib.bgemm_tn(ad, bd, cp, M, N, T, batch, parts)
+            tag = f"{what} {fill} ({parts} slabs) rep {rep}"
+            G.intact(tag)
+            assert _is_canary(cp[parts]), f"{tag}: wrote behind the last slab"
+            assert first is None or torch.equal(first, cp), f"{what} {fill}: two runs differ"
+            first = cp.clone()
+        for z, (lo, hi) in enumerate(rows):
+            ref = torch.matmul(a64[:, lo:hi].transpose(1, 2), b64[:, lo:hi])
+            if fill == "ints":
+                assert gemm_ints_exact(T)
+                _layer_equal("bgemm_tn", cp[z], ref.float(), f"{tag} slab {z} (rows {lo}..{hi})")
+            else:
+                _layer_close("bgemm_tn", "gemm_tn", cp[z], ref, hi - lo, f"{tag} slab {z} (rows {lo}..{hi})")
+        if fill == "randn":
+            full = torch.matmul(a64.transpose(1, 2), b64)
+            _layer_close("bgemm_tn", "gemm_tn", cp[:parts].double().sum(0), full, T, f"{tag} sum of the slabs")
+    cp.fill_(_CANARY[torch.float32])
+    for p in (parts + 1, 0, -1):
+        _refuses("bgemm_tn", lambda: lib.bgemm_tn(ad, bd, cp, M, N, T, batch, p), G, f"{what}: parts = {p}, the plan's {parts}")
+    for args in ((None, bd, cp), (ad, None, cp), (ad, bd, None)):
+        _refuses("bgemm_tn", lambda: lib.bgemm_tn(*args, M, N, T, batch, parts), G, f"{what}: null pointer")
+    return parts
+
+
+def weight_transpose_contract_case(lib, device, K, RS, C, seed=0):
+    """hifihr_weight_transpose: [K][RS][C] -> [C][RS][K], a copy (bit for bit), any positive sizes."""
+    what = f"weight_transpose {K}x{RS}x{C}"
+    G = Guards(device)
+    if not (K > 0 and RS > 0 and C > 0):
+        w, wt = G.inp(torch.zeros(max(K, 1), max(RS, 1), max(C, 1))), G.out(max(C, 1), max(RS, 1), max(K, 1))
+        _refuses("weight_transpose", lambda: lib.weight_transpose(w, wt, K, RS, C), G, what)
+        return False
+    w = torch.randn(K, RS, C, generator=torch.Generator().manual_seed(seed))
+    wd, wt = G.inp(w), G.out(C, RS, K)
+    for rep in range(2):
+        wt.fill_(_CANARY[torch.float32])
+        lib.weight_transpose(wd, wt, K, RS, C)
+        G.intact(what)
+        _layer_equal("weight_transpose", wt, w.permute(2, 1, 0).contiguous(), what)
+    for args in ((None, wt), (wd, None)):
+        _refuses("weight_transpose", lambda: lib.weight_transpose(*args, K, RS, C), G, f"{what}: null pointer")
+    return True
+
+
+# ---- fully connected (csrc/mlp.hip) ------------------------------------------------------------------------------------------------
+# Reference: nn.Linear, BatchNorm1d (training mode) and the activation under float64 autograd.  Quantities -> (kind, L, tensor[, cond]):
+#   lin_y   y / z without batch-norm, L = I;      lin_stat  save_mean / save_invstd / running statistics;      lin_bn_y  y behind batch-norm
+#   lin_dw  dW / db (L = B), dgamma / dbeta (L = B);      lin_dx  dx, L = O
+# Batch-norm puts  amp = max |gamma| invstd  in front of the rounding of z (c sqrt(I) max|z|) and of the cancellation g - mean g -
+# xhat mean(g xhat) of its backward: those sizes are the `cond` of the quantities behind it (layer_bound), and tools/layer_contract_c.py
+# measures fp32 torch against the same expression.
+LAYER_CONTRACT_C.update({
+    "lin_y": (2.9e-7, 3e-5),          # 7.06e-08 x 4   (linear_case: 3e-5 max(1, max|y|))
+    "lin_stat": (2.0e-7, 1e-5),       # 4.82e-08 x 4   (linear_case: running_mean rtol 1e-5)
+    "lin_bn_y": (7.1e-8, 3e-5),       # 1.77e-08 x 4   (linear_case: 3e-5)
+    "lin_dw": (7.3e-7, 2e-4),         # 1.82e-07 x 4   (linear_case: 2e-4)
+    "lin_dx": (4.1e-7, 2e-4),         # 1.01e-07 x 4   (linear_case: 2e-4)
+})
+LINEAR_MAX_GROUP, LINEAR_BN_MAX_B = 6, 64
+
+
+def linear_contract_expect(B, I, O, act, bn):
+    """include/hifihr.h: any B, I, O > 0, act 0..3; batch-norm at B <= 64 and act 0 / 1 only."""
+    return B > 0 and I > 0 and O > 0 and 0 <= act <= 3 and not (bn and (B > LINEAR_BN_MAX_B or act >= 2))
+
+
+def linear_contract_inputs(B, I, O, seed):
+    gen = torch.Generator().manual_seed(seed)
+    rnd = lambda *s: torch.randn(*s, generator=gen)
+    return {"x": rnd(B, I), "w": rnd(O, I) / I ** 0.5, "b": rnd(O) * 0.1, "gamma": 1 + 0.2 * rnd(O), "beta": 0.1 * rnd(O), "rm0": 0.1 * rnd(O),
+            "rv0": 1 + 0.1 * torch.rand(O, generator=gen), "gy": rnd(B, O)}
+
+
+def linear_contract_ref(inp, act, bn, eps=1e-5, mom=0.1, dt=torch.float64, mask=None, drop_row=None, drop_k=None, drop_o=None):
+    """Float64 (or dt) autograd of act(BatchNorm1d?(x W^T + b)).  mask: the ReLU decisions to use instead of the reference's own (the
+    kernel's, where z is zero to rounding).  drop_row / drop_k: the detection check's reference without one batch row of the reductions
+    over B / one input feature of the reductions over I / one output feature of the reduction over O (dx)."""
+    import torch.nn.functional as Fn
+    t = {k: v.to(dt) for k, v in inp.items()}
+    x, w, gy = t["x"], t["w"], t["gy"]
+    if drop_k is not None:
+        x = x.clone(); x[:, drop_k] = 0
+    if drop_row is not None:
+        gy = gy.clone(); gy[drop_row] = 0
+    if drop_o is not None:
+        gy = gy.clone(); gy[:, drop_o] = 0
+    xr, wr, br, gr, ber = (v.clone().requires_grad_(True) for v in (x, w, t["b"], t["gamma"], t["beta"]))
+    z = Fn.linear(xr, wr, br)
+    B, I = x.shape
+    O = w.shape[0]
+    out = {"z": ("lin_y", I, z.detach())}
+    pre, amp = z, 0.0
+    zmax = float(z.detach().abs().max())
+    if bn:
+        rm, rv = t["rm0"].clone(), t["rv0"].clone()
+        mu, var = z.mean(0), z.var(0, unbiased=False)
+        invstd = (var + eps).rsqrt()
+        pre = (z - mu) * invstd * gr + ber
+        amp = float((gr.detach().abs() * invstd.detach()).max())
+        ismax = float(invstd.detach().max())
+        zerr = I ** 0.5 * zmax                                 # the size c multiplies for z itself
+        unb = var * (B / (B - 1)) if B > 1 else var            # (B = 1: the biased value, as bn.hip's M = 1 rule)
+        out.update({"save_mean": ("lin_stat", 1, mu.detach(), zerr), "save_invstd": ("lin_stat", 1, invstd.detach(), ismax ** 2 * zerr),
+                    "running_mean": ("lin_stat", 1, ((1 - mom) * rm + mom * mu).detach(), mom * zerr),
+                    "running_var": ("lin_stat", 1, ((1 - mom) * rv + mom * unb).detach(), mom * 2 * float(var.detach().max()) ** 0.5 * zerr)})
+    if act == 1:
+        m = (pre.detach() > 0) if mask is None else mask
+        y = pre * m.to(dt)
+    elif act == 2:
+        y = pre * torch.sigmoid(pre)
+    elif act == 3:
+        y = torch.sigmoid(pre)
+    else:
+        y = pre
+    out["y"] = ("lin_bn_y", I, y.detach(), amp * I ** 0.5 * zmax) if bn else ("lin_y", I, y.detach())
+    y.backward(gy)
+    gmax, xmax, wmax = float(gy.abs().max()), float(x.abs().max()), float(w.abs().max())
+    A = amp * gmax * (B ** 0.5 if bn else 0.0)                 # batch-norm's backward: g - mean g - xhat mean(g xhat), sums over B, times gamma invstd
+    if bn:                                                    # ... and the forward's rounding of z reaches it through xhat and the statistics
+        A += amp * ismax * gmax * I ** 0.5 * zmax * B ** 0.5
+    out.update({"dW": ("lin_dw", B, wr.grad, B ** 0.5 * A * xmax), "db": ("lin_dw", B, br.grad, B ** 0.5 * A),
+                "dx": ("lin_dx", O, xr.grad, O ** 0.5 * A * wmax)})
+    if bn:
+        xh = float(((z - mu) * invstd).detach().abs().max())
+        out.update({"dgamma": ("lin_dw", B, gr.grad, B ** 0.5 * gmax * (xh + ismax * I ** 0.5 * zmax)), "dbeta": ("lin_dw", B, ber.grad)})
+    return out
+
+
+def _lin_q(ref, name):
+    q = ref[name]
+    return q[0], q[1], q[2], (q[3] if len(q) > 3 else 0.0)
+
+
+def linear_contract_case(lib, device, B, I, O, act, bn, running=True, need_dx=True, seed=0, eps=1e-5, mom=0.1):
+    """hifihr_linear_fwd / _bwd on one shape: forward outputs, saved statistics, running statistics (both or neither), the ACCUMULATE
+    semantics of dW / db / dgamma / dbeta on a non-zero prefill, dx overwritten or skipped; twice, identical bits.  -> accepted."""
+    from hifihr_amd._lib import _fp, _stream_of
+    what = f"linear {B}x{I}x{O} act {act} bn {bn}"
+    G = Guards(device)
+    ok = linear_contract_expect(B, I, O, act, bn)
+    inp = linear_contract_inputs(max(B, 1), max(I, 1), max(O, 1), seed)
+    Bq, Oq, Iq = max(B, 1), max(O, 1), max(I, 1)
+    x, w, b, gy = (G.inp(inp[k]) for k in ("x", "w", "b", "gy"))
+    gamma, beta = G.inp(inp["gamma"]), G.inp(inp["beta"])
+    y, z, sm, si = G.out(Bq, Oq), G.out(Bq, Oq), G.out(Oq), G.out(Oq)
+    rm, rv = G.out(Oq), G.out(Oq)
+    rm.copy_(inp["rm0"]); rv.copy_(inp["rv0"])
+    dz, dW, db, dg, dbt, dx = G.out(Bq, Oq), G.out(Oq, Iq, fill=0.5), G.out(Oq, fill=-0.25), G.out(Oq, fill=0.125), G.out(Oq, fill=2.0), G.out(Bq, Iq)
+
+    def fwd(Bc=B, Ic=I, Oc=O, actc=act, with_bn=bn, rmc=rm, rvc=rv, zc=z, **over):
+        a = dict(x=x, w=w, y=y)
+        a.update(over)
+        # (the binding takes its sizes from the tensors: the C entry itself, for explicit B, I, O)
+        lib.check(lib.c.hifihr_linear_fwd(_fp(a["x"]), _fp(a["w"]), _fp(b), Bc, Ic, Oc, int(actc), _fp(gamma if with_bn else None), _fp(beta if with_bn else None),
+                                          float(eps), float(mom), _fp(rmc if with_bn else None), _fp(rvc if with_bn else None), _fp(a["y"]),
+                                          _fp(zc if (with_bn or actc == 2) else None), _fp(sm if with_bn else None), _fp(si if with_bn else None),
+                                          _stream_of(x)), "hifihr_linear_fwd")
+
+    def bwd(Bc=B, Ic=I, Oc=O, actc=act, with_bn=bn, dxc=dx, dzc=dz, **over):
+        a = dict(dy=gy, x=x, w=w, y=y)
+        a.update(over)
+        lib.check(lib.c.hifihr_linear_bwd(_fp(a["dy"]), _fp(a["y"]), _fp(a["x"]), _fp(a["w"]), Bc, Ic, Oc, int(actc), _fp(gamma if with_bn else None),
+                                          _fp(z if (with_bn or actc == 2) else None), _fp(sm if with_bn else None), _fp(si if with_bn else None),
+                                          _fp(dzc), _fp(dW), _fp(db), _fp(dg if with_bn else None), _fp(dbt if with_bn else None), _fp(dxc),
+                                          _stream_of(x)), "hifihr_linear_bwd")
+
+    if not ok:
+        _refuses("linear_fwd", fwd, G, what)
+        _refuses("linear_bwd", bwd, G, what)
+        return False
+    rm_on = running and bn
+    first = None
+    for rep in range(2):
+        for t_ in (y, z, sm, si, dz, dx):
+            t_.fill_(_CANARY[torch.float32])
+        rm.copy_(inp["rm0"]); rv.copy_(inp["rv0"])
+        dW.fill_(0.5); db.fill_(-0.25); dg.fill_(0.125); dbt.fill_(2.0)
+        fwd(rmc=rm if rm_on else None, rvc=rv if rm_on else None)
+        tag = f"{what} rep {rep}"
+        G.intact(tag)
+        mask = None
+        if act == 1:            # the kernel's ReLU decisions; they may differ from float64's only where the pre-activation is zero to rounding
+            mask = (y.cpu() > 0)
+            kind, L, pre64, cond = _lin_q(linear_contract_ref(inp, 0, bn, eps, mom), "y")
+            flips = mask != (pre64 > 0)
+            assert not bool(flips.any()) or float(pre64.abs()[flips].max()) <= layer_bound(kind, pre64, L, cond), f"{tag}: ReLU mask differs where z is not zero to rounding"
+        ref = linear_contract_ref(inp, act, bn, eps, mom, mask=mask)
+        for name, got in (("y", y),) + ((("z", z),) if (bn or act == 2) else ()) + ((("save_mean", sm), ("save_invstd", si)) if bn else ()) + \
+                ((("running_mean", rm), ("running_var", rv)) if rm_on else ()):
+            kind, L, r, cond = _lin_q(ref, name)
+            _layer_close("linear_fwd", kind, got, r, L, f"{tag} {name}", cond)
+        if not (bn or act == 2):
+            assert _is_canary(z), f"{tag}: z written without batch-norm or swish"
+        if not bn:
+            assert _is_canary(sm) and _is_canary(si), f"{tag}: statistics written without batch-norm"
+        if not rm_on:
+            assert torch.equal(rm.cpu(), inp["rm0"]) and torch.equal(rv.cpu(), inp["rv0"]), f"{tag}: running statistics touched"
+        bwd(dxc=dx if need_dx else None)
+        G.intact(tag)
+        for name, got, pre in (("dW", dW, 0.5), ("db", db, -0.25)) + ((("dgamma", dg, 0.125), ("dbeta", dbt, 2.0)) if bn else ()):
+            kind, L, r, cond = _lin_q(ref, name)
+            _layer_close("linear_bwd", kind, got.cpu().double() - pre, r, L, f"{tag} {name} (accumulated onto {pre})", cond + abs(pre))
+        if need_dx:
+            kind, L, r, cond = _lin_q(ref, "dx")
+            _layer_close("linear_bwd", kind, dx, r, L, f"{tag} dx", cond)
+        else:
+            assert _is_canary(dx), f"{tag}: dx written although NULL was passed"
+        if not bn:
+            assert float((dg - 0.125).abs().max()) == 0 and float((dbt - 2.0).abs().max()) == 0
+        # (dx at O > 64 is summed over 64-feature splits with fp32 atomics -- include/hifihr.h: the same bits only up to their order)
+        now = [t_.clone() for t_ in (y, z, sm, si, rm, rv, dW, db, dg, dbt) + ((dx,) if O <= 64 else ())]
+        assert first is None or all(torch.equal(p, q) for p, q in zip(first, now)), f"{what}: two runs differ"
+        first = now
+    # refusals on the accepted shape: null pointers, a bad act, sizes, the batch-norm rules
+    keep = [t_.clone() for t_ in G.wholes()]
+    for over in ({"x": None}, {"w": None}, {"y": None}):
+        _refuses("linear_fwd", lambda: fwd(**over), G, f"{what}: null pointer")
+    for over in ({"dy": None}, {"x": None}, {"w": None}):
+        _refuses("linear_bwd", lambda: bwd(**over), G, f"{what}: null pointer")
+    for kw in ({"actc": -1}, {"actc": 4}, {"Bc": 0}, {"Ic": 0}, {"Oc": 0}):
+        _refuses("linear_fwd", lambda: fwd(**kw), G, f"{what}: {kw}")
+        _refuses("linear_bwd", lambda: bwd(**kw), G, f"{what}: {kw}")
+    if act == 1:
+        _refuses("linear_bwd", lambda: bwd(y=None), G, f"{what}: act 1 without y")
+    if act == 2:
+        _refuses("linear_fwd", lambda: fwd(zc=None), G, f"{what}: swish without z")
+    _refuses("linear_bwd", lambda: bwd(dzc=None), G, f"{what}: dx without dz_scratch")
+    if bn:
+        _refuses("linear_fwd", lambda: fwd(rvc=None), G, f"{what}: running_mean without running_var")
+        _refuses("linear_fwd", lambda: fwd(rmc=None), G, f"{what}: running_var without running_mean")
+    assert all(torch.equal(p, q) for p, q in zip(keep, G.wholes()))
+    return True
+
+
+def linear_group_contract_case(lib, device, members, seed=0):
+    """hifihr_linear_fwd_group / _bwd_group: members = [(B, I, O, act, with_dx)], 1..6 of them, act 0 / 1: every member bit-identical to its
+    single launch (hifihr_linear_fwd / _bwd), accumulators on a non-zero prefill.  -> accepted."""
+    what = f"linear group {members}"
+    G = Guards(device)
+    ok = 1 <= len(members) <= LINEAR_MAX_GROUP and all(m[3] in (0, 1) and min(m[:3]) > 0 for m in members)
+    grp, single = [], []
+    for i, (B, I, O, act, with_dx) in enumerate(members):
+        inp = linear_contract_inputs(max(B, 1), max(I, 1), max(O, 1), seed + i)
+        Bq, Iq, Oq = max(B, 1), max(I, 1), max(O, 1)
+        both = []
+        for _ in range(2):
+            both.append({"x": G.inp(inp["x"]), "w": G.inp(inp["w"]), "b": G.inp(inp["b"]) if i % 2 == 0 else None, "dy": G.inp(inp["gy"]), "act": act,
+                         "y": G.out(Bq, Oq), "dz": G.out(Bq, Oq), "dW": G.out(Oq, Iq, fill=0.5) if i != 1 else None,
+                         "db": G.out(Oq, fill=-0.25) if i != 1 else None, "dx": G.out(Bq, Iq) if with_dx else None})
+        if min(B, I, O) <= 0:                                  # (the descriptor takes its sizes from the tensors: a refused size goes in by hand below)
+            both[0]["sizes"] = (B, I, O)
+        grp.append(both[0]); single.append(both[1])
+
+    def descs():
+        arr = lib._descs(grp)
+        for d, m in zip(arr, grp):
+            if "sizes" in m:
+                d.B, d.I, d.O = m["sizes"]
+        return arr
+
+    from hifihr_amd._lib import _stream_of
+    call = lambda name, n=None: lib.check(getattr(lib.c, name)(descs(), len(grp) if n is None else n, _stream_of(grp[0]["x"])), name)
+    if not ok:
+        _refuses("linear_fwd_group", lambda: call("hifihr_linear_fwd_group"), G, what)
+        _refuses("linear_bwd_group", lambda: call("hifihr_linear_bwd_group"), G, what)
+        return False
+    for rep in range(2):
+        for m in grp + single:
+            for k, pre in (("y", None), ("dz", None), ("dx", None), ("dW", 0.5), ("db", -0.25)):
+                if m[k] is not None:
+                    m[k].fill_(_CANARY[torch.float32] if pre is None else pre)
+        call("hifihr_linear_fwd_group")
+        call("hifihr_linear_bwd_group")
+        G.intact(what)
+        for i, (g, s) in enumerate(zip(grp, single)):
+            lib.linear_fwd(s["x"], s["w"], s["b"], s["act"], s["y"])
+            lib.linear_bwd(s["dy"], s["y"], s["x"], s["w"], s["act"], s["dz"], s["dW"], s["db"], s["dx"])
+            _layer_equal("linear_fwd_group", g["y"], s["y"], f"{what} member {i} y")
+            for k in ("dW", "db", "dx"):
+                if g[k] is not None and not (k == "dx" and members[i][2] > 64):
+                    _layer_equal("linear_bwd_group", g[k], s[k], f"{what} member {i} {k}")
+            if g["dx"] is not None and members[i][2] > 64:      # (fp32 atomics over the 64-feature splits: equal up to their order)
+                ref = linear_contract_ref(linear_contract_inputs(*members[i][:3], seed + i), members[i][3], False, mask=(g["y"].cpu() > 0) if members[i][3] else None)
+                kind, L, r, cond = _lin_q(ref, "dx")
+                _layer_close("linear_bwd_group", kind, g["dx"], r, L, f"{what} member {i} dx", cond)
+    G.intact(what)
+    for n in (0, -1, LINEAR_MAX_GROUP + 1):
+        _refuses("linear_fwd_group", lambda: call("hifihr_linear_fwd_group", n), G, f"{what}: n = {n}")
+        _refuses("linear_bwd_group", lambda: call("hifihr_linear_bwd_group", n), G, f"{what}: n = {n}")
+    return True
+
+# ---- Winograd F(2x2, 3x3) / F(4x4, 3x3) transforms (csrc/wino.hip, wino4.hip) --------------------------------------------------------
+# The oracle is float64 conv2d and its autograd, never the transform matrices: the kernel's own transforms are chained around a FLOAT64
+# matmul in the test (kernel V and U cast to float64, product in torch, result cast to fp32 and handed to the kernel's output transform), so
+# every channel count the transforms take (C % 4 == 0) is covered, not only those the library's GEMM takes; where it does take them the
+# library product runs as well, into a canary-filled M / dU_parts, and must match the float64 product (kinds gemm_nt / gemm_tn).
+WINO_CONTRACT_KINDS = ("wino_fwd", "wino4_fwd", "wino_wgrad", "wino4_wgrad")
+LAYER_CONTRACT_C.update({
+    # fwd kinds also hold backward-data (the same pipeline on dy, L = 9 K)
+    "wino_fwd": (1.6e-7, 3e-5),       # 4.00e-08 x 4   F(2x2) y / dx, L = 9 C / 9 K: fp32 conv2d against float64             (wino_case 3e-5)
+    "wino4_fwd": (4.9e-6, 5e-5),      # 1.23e-06 x 4   F(4x4) y / dx: the test's chain with an FP32 product on the emulator (fp32 direct convolution is another
+    #                                                  algorithm: F(4x4)'s interpolation points amplify the rounding of V and U); the CAP, not c, binds from
+    #                                                  C = 12 on (c sqrt(9 C) > 5e-5)                                   (wino_case 5e-5)
+    "wino_wgrad": (1.6e-7, 1e-4),     # 3.93e-08 x 4   F(2x2) dw, L = N H W: fp32 conv2d autograd against float64                (wino_case 1e-4)
+    "wino4_wgrad": (5.5e-6, 1e-4),    # 1.38e-06 x 4   F(4x4) dw: the chain with an fp32 product, as wino4_fwd; the cap binds from N H W = 331 on   (wino_case 1e-4)
+})
+
+
+def wino_contract_expect(N, H, W, C, K, m):
+    """include/hifihr.h: m 2 or 4, C % 4 == 0 and K % 4 == 0 (the transforms move channels four at a time), any N, H, W > 0."""
+    return m in (2, 4) and min(N, H, W) > 0 and C >= 4 and C % 4 == 0 and K >= 4 and K % 4 == 0
+
+
+def wino_contract_inputs(N, H, W, C, K, seed):
+    gen = torch.Generator().manual_seed(seed)
+    return {"x": torch.randn(N, C, H, W, generator=gen), "w": torch.randn(K, C, 3, 3, generator=gen) / (9 * C) ** 0.5,
+            "gy": torch.randn(N, K, H, W, generator=gen), "bias": torch.randn(K, generator=gen) * 0.3}
+
+
+def wino_contract_ref(inp, dt=torch.float64, drop_tap=False, drop_pixel=False):
+    """conv2d (3x3, stride 1, pad 1) and its autograd in NHWC: name -> (L, tensor) for y, dx, dw.  drop_tap / drop_pixel: the detection
+    check's reference without the filter's centre tap (y, dx) / without one output pixel's contribution (dw)."""
+    import torch.nn.functional as Fn
+    x, w, gy = (inp[k].to(dt) for k in ("x", "w", "gy"))
+    if drop_tap:
+        w = w.clone(); w[:, :, 1, 1] = 0
+    if drop_pixel:
+        gy = gy.clone(); gy[0, :, 0, 0] = 0
+    xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    y = Fn.conv2d(xr, wr, None, 1, 1)
+    y.backward(gy)
+    N, C, H, W = x.shape
+    K = w.shape[0]
+    nhwc = lambda t: t.detach().permute(0, 2, 3, 1).contiguous()
+    return {"y": (9 * C, nhwc(y)), "dx": (9 * K, nhwc(xr.grad)), "dw": (N * H * W, nhwc(wr.grad))}
+
+
+def _wino_fused_and_refused(lib, G, ent, what, N, H, W, C, K, m, P, T, w, wt, U, U2, V, V2, Yt, dUp, dw):
+    """hifihr_weight_prep against the separate launches (bit for bit) and the refusals of the entries the chain only ever accepts."""
+    from hifihr_amd._lib import _stream_of
+    import ctypes
+    # the per-step re-layout in one launch: transpose, U and U' of this layer == hifihr_weight_transpose / hifihr_wino_weight_transform_m
+    kinds = (0, 1, 2) if m == 2 else (0, 3, 4)
+    dsts = [G.out(C, 9, K), G.out(P, K, C), G.out(P, C, K)]
+    table = lib.prep_jobs([(w, d, K, C, 9, k) for d, k in zip(dsts, kinds)], w.device)
+    for blocks in (1, 3):
+        for d in dsts:
+            d.fill_(_CANARY[torch.float32])
+        lib.weight_prep(table, 3, blocks)
+        G.intact(what)
+        for d, want, name in zip(dsts, (wt, U, U2), ("transpose", "U", "U' (flipped)")):
+            _layer_equal(ent("weight_prep"), d.reshape(-1), want.reshape(-1), f"{what}: weight_prep {name}, {blocks} workgroups per job")
+    for args in ((None, 3, 1), (table, 0, 1), (table, -1, 1), (table, 3, 0)):
+        tb, nj, bl = args
+        _refuses(ent("weight_prep"), lambda: lib.check(lib.c.hifihr_weight_prep(ctypes.c_void_p(tb.data_ptr() if tb is not None else 0), nj, bl, _stream_of(w)), "hifihr_weight_prep"),
+                 G, f"{what}: weight_prep {('null table', nj, bl)}")
+    # the weight-gradient transforms: a channel count that is no multiple of 4, no filters, no slabs, no jobs
+    if m == 2:
+        for Kb, Cb in ((K, C + 2), (0, C), (K, 0)):
+            _refuses(ent("wino_dw_transform"), lambda: lib.wino_dw_transform(dUp[0], dw, Kb, Cb), G, f"{what}: wino_dw_transform K {Kb} C {Cb}")
+        _refuses(ent("wino_dw_transform"), lambda: lib.wino_dw_transform(None, dw, K, C), G, f"{what}: wino_dw_transform null dU")
+    else:
+        for job in ((dUp, 2, dw, K, C + 2), (dUp, 0, dw, K, C), (dUp, 2, dw, 0, C), (dUp, 2, dw, K, 0)):
+            _refuses(ent("wino4_dw_transform_multi"), lambda: lib.wino4_dw_transform_multi([(dUp, 2, dw, K, C), job]), G, f"{what}: multi, bad job {job[1:2] + job[3:]}")
+        _refuses(ent("wino4_dw_transform_multi"), lambda: lib.check(lib.c.hifihr_wino4_dw_transform_multi(None, 1, _stream_of(w)), "hifihr_wino4_dw_transform_multi"), G, f"{what}: multi, null jobs")
+        raw = ctypes.create_string_buffer(32)
+        _refuses(ent("wino4_dw_transform_multi"), lambda: lib.check(lib.c.hifihr_wino4_dw_transform_multi(ctypes.cast(raw, ctypes.c_void_p), 0, _stream_of(w)), "hifihr_wino4_dw_transform_multi"), G, f"{what}: multi, no jobs")
+        raw = ctypes.create_string_buffer(32)                                   # (a job of null pointers)
+        _refuses(ent("wino4_dw_transform_multi"), lambda: lib.check(lib.c.hifihr_wino4_dw_transform_multi(ctypes.cast(raw, ctypes.c_void_p), 1, _stream_of(w)), "hifihr_wino4_dw_transform_multi"), G, f"{what}: multi, null pointers in a job")
+        # the pair launch: its predicate answers 1 only where both products are the library's; the launch refuses other channel counts, a slab
+        # count that is not the plan's, null pointers
+        lib._pair_ok.pop((N, H, W, C, K), None)
+        parts = lib.wino_wgrad_parts(N, H, W, C, K, 4)
+        can = C % 64 == 0 and K % 64 == 0
+        assert not lib.wino4_bwd_gemm_pair_supported(N, H, W, C, K) or (can and parts > 0), f"{what}: pair predicate on channels the products refuse"
+        assert can == (parts > 0), f"{what}: hifihr_wino_wgrad_parts_m {parts}"
+        M2, dUq = G.out(P, T, C), G.out(max(parts, 1) + 1, P, K, C)
+        bad = [(V2, U2, M2, V, Yt, dUq, parts + 1), (V2, U2, M2, V, Yt, dUq, 0)] + ([] if can else [(V2, U2, M2, V, Yt, dUq, 1)])
+        bad += [(None, U2, M2, V, Yt, dUq, max(parts, 1)), (V2, U2, None, V, Yt, dUq, max(parts, 1)), (V2, U2, M2, V, Yt, None, max(parts, 1))]
+        for a in bad:
+            _refuses(ent("wino4_bwd_gemm_pair"), lambda: lib.wino4_bwd_gemm_pair(*a[:6], N, H, W, C, K, a[6]), G, f"{what}: pair launch, parts {a[6]} / null pointer")
+
+
+def wino_chain_contract_case(lib, device, N, H, W, C, K, m, seed=0, product=torch.float64, log=True):
+    """Every transform entry of one layer around a float64 (product=...) matmul; -> accepted.  Buffers between the stages are prefilled
+    with the canary in the first run and NaN in the second: results must not depend on it."""
+    what = f"wino {N}x{H}x{W} C {C} K {K} m {m}"
+    P = (m + 2) ** 2 if m > 0 else 16
+    ok = wino_contract_expect(N, H, W, C, K, m)
+    nan = float("nan")
+    Nq, Hq, Wq, Cq, Kq = (max(v, 1) for v in (N, H, W, C, K))
+    inp = wino_contract_inputs(Nq, Hq, Wq, Cq, Kq, seed)
+    nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous()
+    if not ok:
+        G = Guards(device)
+        Tq = Nq * Hq * Wq
+        x, w, gy = G.inp(nhwc(inp["x"])), G.inp(nhwc(inp["w"])), G.inp(nhwc(inp["gy"]))
+        U, V, Mm, Yt, y, dw = G.out(36, Kq, Cq), G.out(36, Tq, Cq), G.out(36, Tq, Kq), G.out(36, Tq, Kq), G.out(Nq, Hq, Wq, Kq), G.out(Kq, 3, 3, Cq)
+        Vk = G.out(36, Tq, Kq)
+        assert m in (2, 4) or (lib.wino_tiles(N, H, W, m) == 0 and lib.wino_tiles_computed(N, H, W, m) == 0 and lib.wino_wgrad_parts(N, H, W, 64, 64, m) == 0
+                               and lib.wino_gemm_workspace_bytes(N, H, W, 64, 64, m) == 0), f"{what}: a query answers for an m that is refused"
+        geo_ok, c_ok, k_ok = m in (2, 4) and min(N, H, W) > 0, C >= 4 and C % 4 == 0, K >= 4 and K % 4 == 0
+        calls = {}
+        if not (geo_ok and c_ok):                                            # the entries that see C ...
+            calls.update({"wino_input_transform": lambda: lib.wino_input_transform(x, V, N, H, W, C, m)})
+        if not (m in (2, 4) and c_ok and K > 0):
+            calls.update({"wino_weight_transform": lambda: lib.wino_weight_transform(w, U, K, C, 0, m),
+                          "wino_dw_transform_parts": lambda: lib.wino_dw_transform_parts(U, 1, dw, K, C, m)})
+        if not (geo_ok and k_ok):                                            # ... and those that see K
+            calls.update({"wino_output_transform": lambda: lib.wino_output_transform(Mm, y, None, N, H, W, K, m=m),
+                          "wino_output_transform_act": lambda: lib.wino_output_transform(Mm, y, None, N, H, W, K, act=1, m=m),
+                          "wino_dy_transform": lambda: lib.wino_dy_transform(gy, Yt, N, H, W, K, m),
+                          "wino_input_dy_transform": lambda: lib.wino_input_dy_transform(gy, Vk, Yt, N, H, W, K, m)})
+        if m not in (2, 4):                                                  # (a bad m: the products too; sizes the products would take)
+            calls["wino_gemm"] = lambda: lib.wino_gemm(V, U, Mm, N, H, W, C, K, m=m)
+            calls["wino_wgrad_gemm_parts"] = lambda: lib.wino_wgrad_gemm_parts(V, Yt, U, N, H, W, C, K, 1, m)
+        for e, call in calls.items():
+            _refuses(e, call, G, f"{what}: {e}")
+        return False
+    T, Tr = lib.wino_tiles(N, H, W, m), lib.wino_tiles_computed(N, H, W, m)
+    assert 0 < Tr <= T
+    ref = wino_contract_ref(inp)
+    fk, wk = ("wino4_fwd", "wino4_wgrad") if m == 4 else ("wino_fwd", "wino_wgrad")
+    ent = lambda e: e if log else "_" + e
+    results = []
+    for prefill in (None, nan):
+        G = Guards(device)
+        x, w, gy, bias = G.inp(nhwc(inp["x"])), G.inp(nhwc(inp["w"])), G.inp(nhwc(inp["gy"])), G.inp(inp["bias"])
+        U, V = G.out(P, K, C, fill=prefill), G.out(P, T, C, fill=prefill)
+        lib.wino_weight_transform(w, U, K, C, 0, m)
+        lib.wino_input_transform(x, V, N, H, W, C, m)
+        G.intact(what)
+        assert not bool(torch.isnan(V[:, :Tr]).any()) and not bool((V[:, :Tr] == _CANARY[torch.float32]).any()), f"{what}: a computed row of V is unwritten"
+        assert T == Tr or float(V[:, Tr:].abs().max()) == 0.0, f"{what}: the rows of V behind the last mosaic tile are not zero"
+        Mm = torch.matmul(V.cpu().to(product), U.cpu().to(product).transpose(1, 2)).float()      # [P][T][K]
+        Mm[:, Tr:] = nan                                                        # (unread by the output transform)
+        Md = G.inp(Mm)
+        y = G.out(N, H, W, K)
+        stats = G.out(lib.bn_stats_floats(K), fill=0.0)
+        lib.wino_output_transform(Md, y, stats, N, H, W, K, m=m)
+        G.intact(what)
+        _layer_close(ent("wino_output_transform"), fk, y, ref["y"][1], ref["y"][0], f"{what} y")
+        flat = ref["y"][1].reshape(-1, K)
+        st = bn_slots(stats, K).sum(0).cpu()
+        _layer_close(ent("wino_output_transform"), "bn_sum", st[0], flat.sum(0), N * H * W, f"{what} statistics: sum", cond=float(flat.abs().sum(0).max()) * layer_bound(fk, torch.ones(1), ref["y"][0]) / LAYER_CONTRACT_C["bn_sum"][0])
+        # the consumer (include/hifihr.h "SELF-CLEANING"): hifihr_bn_act_fwd folds the slots this producer filled and hands the slots and
+        # arrival counters back all zero; its batch mean is the mean of the y just compared
+        gam, bet = G.inp(torch.ones(K)), G.inp(torch.zeros(K))
+        ybn, smean, sinv = G.out(N, H, W, K), G.out(K), G.out(K)
+        lib.bn_act_fwd(y, stats, gam, bet, None, 0, N * H * W, K, 1e-5, 0.1, ybn, smean, sinv, None, None)
+        G.intact(what)
+        _slots_clean(stats, K, f"{what}: statistics slots / counters not handed back zeroed by their consumer")
+        stats.zero_()                                                          # (the 2 K scratch floats behind them are not part of the promise)
+        assert layer_err(smean, flat.mean(0)) <= layer_bound(fk, ref["y"][1], ref["y"][0]) + 1e-6 * float(flat.abs().max()), f"{what}: batch mean from the slots"
+        y0 = G.out(N, H, W, K)
+        lib.wino_output_transform(Md, y0, None, N, H, W, K, m=m)
+        assert torch.equal(y0, y), f"{what}: y depends on whether statistics are taken"
+        for act in (0, 1):
+            ya = G.out(N, H, W, K)
+            lib.wino_output_transform(Md, ya, None, N, H, W, K, bias=bias, act=act, m=m)
+            ra = ref["y"][1] + inp["bias"].double()
+            _layer_close(ent("wino_output_transform_act"), fk, ya, torch.relu(ra) if act else ra, ref["y"][0], f"{what} bias, act {act}", cond=float(ref["y"][1].abs().max()))
+        _refuses(ent("wino_output_transform_act"), lambda: lib.wino_output_transform(Md, ya, None, N, H, W, K, bias=bias, act=2, m=m), G, f"{what}: act 2")
+        # backward-data: the same pipeline on dy with the transposed, rotated filter
+        wt = G.out(C, 3, 3, K, fill=prefill)
+        lib.weight_transpose(w, wt, K, 9, C)
+        U2, V2 = G.out(P, C, K, fill=prefill), G.out(P, T, K, fill=prefill)
+        lib.wino_weight_transform(wt, U2, C, K, 1, m)
+        lib.wino_input_transform(gy, V2, N, H, W, K, m)
+        V2b, Ytb, Yt = G.out(P, T, K, fill=prefill), G.out(P, T, K, fill=prefill), G.out(P, T, K, fill=prefill)
+        lib.wino_input_dy_transform(gy, V2b, Ytb, N, H, W, K, m)
+        lib.wino_dy_transform(gy, Yt, N, H, W, K, m)
+        G.intact(what)
+        _layer_equal(ent("wino_input_dy_transform"), V2b[:, :Tr], V2[:, :Tr], f"{what}: dual dy transform, V")
+        _layer_equal(ent("wino_input_dy_transform"), Ytb[:, :Tr], Yt[:, :Tr], f"{what}: dual dy transform, Y'")
+        assert T == Tr or (float(V2b[:, Tr:].abs().max()) == 0.0 and float(Ytb[:, Tr:].abs().max()) == 0.0 and float(Yt[:, Tr:].abs().max()) == 0.0), \
+            f"{what}: the rows of V / Y' behind the last mosaic tile are not zero"
+        M2 = torch.matmul(V2.cpu().to(product), U2.cpu().to(product).transpose(1, 2)).float()
+        M2[:, Tr:] = nan
+        dx = G.out(N, H, W, C)
+        lib.wino_output_transform(G.inp(M2), dx, None, N, H, W, C, m=m)
+        _layer_close(ent("wino_output_transform"), fk, dx, ref["dx"][1], ref["dx"][0], f"{what} dx")
+        # backward-weight: dU = Y'^T V per position, in two slabs, accumulated onto a prefilled dw
+        dU = torch.matmul(Yt.cpu().to(product).transpose(1, 2), V.cpu().to(product))                # [P][K][C]
+        half = (dU * 0.5).float()
+        dUp = G.inp(torch.stack([half, (dU - half.to(product)).float()]))
+        dw = G.out(K, 3, 3, C, fill=0.5)
+        lib.wino_dw_transform_parts(dUp, 2, dw, K, C, m)
+        G.intact(what)
+        _layer_close(ent("wino_dw_transform_parts"), wk, dw.cpu().double() - 0.5, ref["dw"][1], ref["dw"][0], f"{what} dw (slabs)", cond=0.5)
+        if m == 4:                                                              # several layers in one launch: the per-layer call's bits
+            dwm, dwn = G.out(K, 3, 3, C, fill=0.5), G.out(K, 3, 3, C, fill=-1.0)
+            lib.wino4_dw_transform_multi([(dUp, 2, dwm, K, C), (dUp[1:], 1, dwn, K, C)])
+            dws = G.out(K, 3, 3, C, fill=-1.0)
+            lib.wino_dw_transform_parts(dUp[1:], 1, dws, K, C, m)
+            _layer_equal(ent("wino4_dw_transform_multi"), dwm, dw, f"{what}: multi, job 0")
+            _layer_equal(ent("wino4_dw_transform_multi"), dwn, dws, f"{what}: multi, job 1")
+        else:                                                                   # the atomics form: dU read, then handed back all zero
+            dUa, dwa = G.out(P, K, C), G.out(K, 3, 3, C, fill=0.5)
+            dUa.copy_(dU.float())
+            lib.wino_dw_transform(dUa, dwa, K, C)
+            assert float(dUa.abs().max()) == 0.0, f"{what}: the dU accumulator must come back zeroed"
+            _layer_close(ent("wino_dw_transform"), "wino_wgrad", dwa.cpu().double() - 0.5, ref["dw"][1], ref["dw"][0], f"{what} dw (atomics form)", cond=0.5)
+        G.intact(what)
+        results.append([t.clone() for t in (U, V[:, :Tr], y, dx, dw, Yt[:, :Tr])])
+        if prefill is None:
+            _wino_fused_and_refused(lib, G, ent, what, N, H, W, C, K, m, P, T, w, wt, U, U2, V, V2, Yt, dUp, dw)
+        # the library's own products, where it takes the channel counts: into canary-filled M / dU_parts
+        if prefill is None and C % 32 == 0 and K % 64 == 0 and C % 64 == 0 and product == torch.float64:
+            nb = lib.wino_gemm_workspace_bytes(N, H, W, C, K, m)
+            ws = G.out(nb // 4, fill=0.0) if nb else None
+            Ml = G.out(P, T, K)
+            lib.wino_gemm(V, U, Ml, N, H, W, C, K, ws=ws, m=m)
+            G.intact(what)
+            assert ws is None or float(ws.abs().max()) == 0.0
+            _layer_close(ent("wino_gemm"), "gemm_nt", Ml[:, :Tr], torch.matmul(V[:, :Tr].cpu().double(), U.cpu().double().transpose(1, 2)), C, f"{what} M")
+            parts = lib.wino_wgrad_parts(N, H, W, C, K, m)
+            if parts > 0:
+                dUl = G.out(parts + 1, P, K, C)
+                lib.wino_wgrad_gemm_parts(V, Yt, dUl, N, H, W, C, K, parts, m)
+                G.intact(what)
+                assert _is_canary(dUl[parts])
+                _layer_close(ent("wino_wgrad_gemm_parts"), "gemm_tn", dUl[:parts].double().sum(0), dU.double(), T, f"{what} dU slabs")
+                _refuses(ent("wino_wgrad_gemm_parts"), lambda: lib.wino_wgrad_gemm_parts(V, Yt, dUl, N, H, W, C, K, parts + 1, m), G, f"{what}: parts + 1")
+                if m == 4:                                                      # both backward products in one launch: the separate launches' bits
+                    M2a, M2b, dUq = G.out(P, T, C), G.out(P, T, C), G.out(parts, P, K, C)
+                    lib.wino_gemm(V2, U2, M2a, N, H, W, K, C, ws=None, m=m)
+                    lib.wino4_bwd_gemm_pair(V2, U2, M2b, V, Yt, dUq, N, H, W, C, K, parts)
+                    G.intact(what)
+                    _layer_equal(ent("wino4_bwd_gemm_pair"), M2b[:, :Tr], M2a[:, :Tr], f"{what}: pair launch, M2")
+                    _layer_equal(ent("wino4_bwd_gemm_pair"), dUq, dUl[:parts], f"{what}: pair launch, dU slabs")
+                    # (rows behind the last mosaic tile: unread by the output transform; the row-share kernel skips them, the per-tile
+                    # kernels write the product of V's zero rows)
+                    pad_ok = lambda t: _is_canary(t) or float(t.abs().max()) == 0.0
+                    assert T == Tr or (pad_ok(M2b[:, Tr:]) and pad_ok(Ml[:, Tr:])), f"{what}: rows of M behind the last mosaic tile are neither untouched nor zero"
+    assert all(torch.equal(a, b) for a, b in zip(*results)), f"{what}: a result depends on the prefill of a buffer between two stages"
+    return True
+
+
+
+# ---- batch-norm fused into the F(4x4, 3x3) transforms (csrc/wino4_bn.hip) ---------------------------------------------------------------
+def wino_bn_contract_expect(C, m):
+    """include/hifihr.h: m = 4, C % 4 == 0, C <= 512 (hifihr_wino_bn_input_supported)."""
+    return m == 4 and C >= 4 and C % 4 == 0 and C <= 512
+
+
+def wino_bn_contract_case(lib, device, N, H, W, C, m, residual, addend, seed=0):
+    """hifihr_wino_bn_input_transform, hifihr_wino_output_transform_bnred and hifihr_wino_bn_bwd_dual_transform inside guard bands: refused
+    (HIFIHR_EINVAL, nothing written), or bit-identical to the separate launches they replace -- hifihr_bn_act_fwd + input transform,
+    output transform (+ addend) + the masking of hifihr_bn_act_bwd, hifihr_bn_bwd_apply + dual dy transform -- each of which has its own
+    contract against float64; statistics and reduction buffers handed back zeroed; twice, identical bits.  -> accepted."""
+    what = f"wino_bn {N}x{H}x{W} C {C} m {m} residual {residual} addend {addend}"
+    ok = wino_bn_contract_expect(C, m)
+    assert lib.wino_bn_input_supported(C, m) == ok, f"{what}: hifihr_wino_bn_input_supported"
+    gen = torch.Generator().manual_seed(seed)
+    G = Guards(device)
+    Cq, M = max(C, 4), N * H * W
+    T = lib.wino_tiles(N, H, W, 4)
+    x = G.inp(torch.randn(N, H, W, Cq, generator=gen) * 1.3 + 0.2)
+    res = G.inp(torch.randn(N, H, W, Cq, generator=gen)) if residual else None
+    gadd = G.inp(torch.randn(N, H, W, Cq, generator=gen)) if addend else None
+    gamma, beta = G.inp(1 + 0.1 * torch.randn(Cq, generator=gen)), G.inp(0.1 * torch.randn(Cq, generator=gen))
+    Mm = G.inp(torch.randn(36, T, Cq, generator=gen))
+    nst = lib.bn_stats_floats(Cq)
+    st, red = G.out(nst, fill=0.0), G.out(nst, fill=0.0)
+    V1, out1, g1 = G.out(36, T, Cq), (G.out(N, H, W, Cq) if residual else None), G.out(N, H, W, Cq)
+    sm1, si1, rm1, rv1 = G.out(Cq), G.out(Cq), G.out(Cq, fill=0.0), G.out(Cq, fill=1.0)
+    V2, Y2, dg2, db2 = G.out(36, T, Cq), G.out(36, T, Cq), G.out(Cq, fill=0.5), G.out(Cq, fill=-0.25)
+    fused_in = lambda Cc=C, mm=m, o=out1, r=res: lib.wino_bn_input_transform(x, st, gamma, beta, r, o, V1, N, H, W, Cc, mm, 1e-5, 0.1, sm1, si1, rm1, rv1)
+    fused_red = lambda Cc=C, mm=m: lib.wino_output_transform_bnred(Mm, x, out1, gadd, sm1, si1, gamma, beta, red, g1, N, H, W, Cc, mm)
+    fused_dual = lambda Cc=C, mm=m: lib.wino_bn_bwd_dual_transform(g1, x, sm1, si1, gamma, red, V2, Y2, N, H, W, Cc, mm, dg2, db2)
+    if not ok:
+        for e, call in (("wino_bn_input_transform", fused_in), ("wino_output_transform_bnred", fused_red), ("wino_bn_bwd_dual_transform", fused_dual)):
+            _refuses(e, call, G, f"{what}: {e}")
+        return False
+    # the separate launches (plain buffers: their own contracts guard them)
+    d0 = lambda *s: torch.empty(*s, device=device)
+    st0 = torch.zeros(nst, device=device)
+    lib.bn_stats(x, M, C, st0)
+    a0, sm0, si0, rm0, rv0 = d0(N, H, W, C), d0(C), d0(C), torch.zeros(C, device=device), torch.ones(C, device=device)
+    lib.bn_act_fwd(x, st0, gamma, beta, res, 1, M, C, 1e-5, 0.1, a0, sm0, si0, rm0, rv0)
+    V0 = d0(36, T, C)
+    lib.wino_input_transform(a0, V0, N, H, W, C, 4)
+    dA = d0(N, H, W, C)
+    lib.wino_output_transform(Mm, dA, None, N, H, W, C, m=4)
+    dA = dA + gadd if addend else dA
+    red0 = torch.zeros(nst, device=device)
+    dx0, dres0, dg0, db0 = d0(N, H, W, C), d0(N, H, W, C), torch.zeros(C, device=device), torch.zeros(C, device=device)
+    lib.bn_act_bwd(dA, a0 if residual else None, x, sm0, si0, gamma, beta, 1, M, C, red0, dx0, dres0, dg0, db0)
+    first = None
+    for rep in range(2):
+        for t in (V1, g1, V2, Y2, sm1, si1) + ((out1,) if residual else ()):
+            t.fill_(_CANARY[torch.float32])
+        rm1.fill_(0.0); rv1.fill_(1.0); dg2.fill_(0.5); db2.fill_(-0.25)
+        lib.bn_stats(x, M, C, st)
+        fused_in()
+        G.intact(what)
+        _slots_clean(st, C, f"{what}: statistics not handed back zeroed")
+        _layer_equal("wino_bn_input_transform", V1, V0, f"{what}: V")
+        for got, want, n in ((sm1, sm0, "save_mean"), (si1, si0, "save_invstd"), (rm1, rm0, "running_mean"), (rv1, rv0, "running_var")) + (((out1, a0, "out"),) if residual else ()):
+            _layer_equal("wino_bn_input_transform", got, want, f"{what}: {n}")
+        fused_red()
+        G.intact(what)
+        _layer_equal("wino_output_transform_bnred", g1, dres0, f"{what}: masked gradient")
+        # the sums the fused reduction left in `red`, through both of their consumers: hifihr_bn_bwd_apply, and the dual transform on a copy
+        red_copy = red.clone()
+        dx1, dg1, db1 = d0(N, H, W, C), torch.full((C,), 0.5, device=device), torch.full((C,), -0.25, device=device)
+        lib.bn_bwd_apply(g1, x, sm1, si1, gamma, M, C, red, dx1, dg1, db1)
+        _slots_clean(red, C, f"{what}: reduction buffer not handed back zeroed by hifihr_bn_bwd_apply")
+        err = float((dx1 - dx0).abs().max())                                  # (the reductions add in another order: wino_bn_bwd_case's tolerance)
+        assert err <= 2e-5 * float(dx0.abs().max()) + 1e-7, f"{what}: dx through the fused reduction: {err}"
+        red.copy_(red_copy)
+        fused_dual()
+        G.intact(what)
+        _slots_clean(red, C, f"{what}: reduction buffer not handed back zeroed by the dual transform")
+        V0b, Y0b = d0(36, T, C), d0(36, T, C)
+        lib.wino_input_dy_transform(dx1, V0b, Y0b, N, H, W, C, 4)
+        _layer_equal("wino_bn_bwd_dual_transform", V2, V0b, f"{what}: V of dx")
+        _layer_equal("wino_bn_bwd_dual_transform", Y2, Y0b, f"{what}: Y' of dx")
+        _layer_equal("wino_bn_bwd_dual_transform", dg2, dg1, f"{what}: dgamma (accumulated onto 0.5)")
+        _layer_equal("wino_bn_bwd_dual_transform", db2, db1, f"{what}: dbeta (accumulated onto -0.25)")
+        red.zero_()
+        now = [t.clone() for t in (V1, g1, V2, Y2, sm1, si1, rm1, rv1, dg2, db2)]
+        assert first is None or all(torch.equal(a, b) for a, b in zip(first, now)), f"{what}: two runs differ"
+        first = now
+    # refusals on the accepted shape: the other tile edge, residual without out (and the reverse), null pointers
+    for e, call in (("wino_bn_input_transform", fused_in), ("wino_output_transform_bnred", fused_red), ("wino_bn_bwd_dual_transform", fused_dual)):
+        _refuses(e, lambda: call(mm=2), G, f"{what}: {e} at m = 2")
+        _refuses(e, lambda: call(Cc=C + 2), G, f"{what}: {e} at C + 2")
+    _refuses("wino_bn_input_transform", (lambda: fused_in(o=None)) if residual else (lambda: fused_in(o=g1)), G, f"{what}: residual and out: both or neither")
+    return True
+
+
+# ---- the lists of the GEMM contract (tests/test_hostsim_gemm_contract.py, the GPU halves, tools/layer_contract_c.py, tools/asan_hostsim.py) ----
+import os as _os
+
+# ---- routing: name -> environment (every HIFIHR_GEMM_* switch not named is removed for the case) -------------------------------------------
+GEMM_SWITCHES = ("HIFIHR_GEMM_CUS", "HIFIHR_GEMM_NT_TILE", "HIFIHR_GEMM_TN_TILE", "HIFIHR_GEMM_WS", "HIFIHR_GEMM_TN_PARTS", "HIFIHR_GEMM_SK")
+GEMM_ROUTES = {
+    "default": {},
+    "cus16": {"HIFIHR_GEMM_CUS": "16"},                                           # a multiple of 8 workgroups: the XCD-coherent TN schedule
+    "t128": {"HIFIHR_GEMM_NT_TILE": "128128", "HIFIHR_GEMM_TN_TILE": "128128", "HIFIHR_GEMM_WS": "0"},      # the 4-wave kernels
+    "t128x64": {"HIFIHR_GEMM_NT_TILE": "128064", "HIFIHR_GEMM_TN_TILE": "128064"},
+    "t64x128": {"HIFIHR_GEMM_NT_TILE": "64128", "HIFIHR_GEMM_TN_TILE": "64128"},
+    "t64": {"HIFIHR_GEMM_NT_TILE": "64064", "HIFIHR_GEMM_TN_TILE": "64064"},
+    "ws1": {"HIFIHR_GEMM_NT_TILE": "128128", "HIFIHR_GEMM_TN_TILE": "128128", "HIFIHR_GEMM_WS": "1"},       # wave-specialised, 1 / 2 / 4 loader waves
+    "ws2": {"HIFIHR_GEMM_NT_TILE": "128128", "HIFIHR_GEMM_TN_TILE": "128128", "HIFIHR_GEMM_WS": "2"},
+    "ws4": {"HIFIHR_GEMM_NT_TILE": "128128", "HIFIHR_GEMM_TN_TILE": "128128", "HIFIHR_GEMM_WS": "4"},
+    "ws2p3": {"HIFIHR_GEMM_TN_TILE": "128128", "HIFIHR_GEMM_WS": "2", "HIFIHR_GEMM_TN_PARTS": "3"},         # a slab count of the caller's
+}
+
+# ---- NT: (M, N, K, batch, route, workspace) -------------------------------------------------------------------------------------------------
+# M in {1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 300}, N in {64, 128, 192, 256, 576 (K = 128: ragged N on the row-share kernel)},
+# K in {32, 64, 96, 160, 512}, batch in {1, 2, 5, 36}
+NT_SHAPES = [
+    (1, 64, 32, 1, "default", "full"), (15, 128, 32, 2, "default", "full"), (16, 128, 64, 1, "default", "full"), (17, 192, 96, 2, "default", "full"),
+    (63, 256, 32, 5, "default", "full"), (64, 64, 160, 1, "default", "full"), (65, 128, 96, 2, "default", "full"), (127, 128, 160, 2, "default", "full"),
+    (128, 256, 64, 1, "default", "full"), (129, 64, 512, 1, "default", "full"), (17, 128, 512, 2, "default", "full"), (1, 128, 512, 5, "default", "full"),
+    (16, 192, 32, 36, "default", "full"), (17, 128, 32, 36, "default", "full"), (17, 256, 160, 5, "default", "full"), (63, 192, 64, 1, "default", "full"), (127, 64, 96, 5, "default", "full"),
+    (128, 192, 160, 2, "default", "full"), (65, 256, 512, 1, "default", "full"), (300, 256, 96, 2, "default", "full"), (300, 64, 64, 2, "default", "full"),
+    (15, 576, 128, 1, "default", "full"), (129, 576, 128, 2, "default", "full"), (300, 576, 128, 1, "default", "full"), (1, 576, 128, 5, "default", "full"),
+    (129, 128, 64, 2, "t128", "full"), (300, 256, 32, 1, "t128", "full"), (1, 128, 96, 1, "t128", "full"),
+    (65, 64, 64, 2, "t128x64", "full"), (300, 192, 32, 1, "t128x64", "full"), (63, 128, 96, 2, "t64x128", "full"), (129, 256, 32, 1, "t64x128", "full"),
+    (17, 128, 32, 5, "t64", "full"), (127, 256, 64, 1, "t64", "full"),
+    (127, 128, 160, 2, "ws1", "full"), (300, 256, 32, 1, "ws2", "full"), (129, 128, 96, 2, "ws4", "full"),
+    # 128x128 tiles over >= 3 rounds of the 4 workgroups: the persistent stream-K kernel with its workspace, the per-tile fallback without
+    (300, 128, 96, 5, "ws2", "full"), (300, 128, 64, 5, "ws4", "full"), (300, 128, 96, 5, "ws1", "full"),
+    (300, 128, 96, 5, "ws2", "short"), (300, 128, 96, 5, "ws4", "none"),
+    # refused: K in {0, 16, 48}, N in {0, 32, 96}, M = 0, batch = 0
+    (17, 128, 0, 1, "default", "none"), (17, 128, 16, 1, "default", "none"), (17, 128, 48, 1, "default", "none"),
+    (17, 0, 32, 1, "default", "none"), (17, 32, 32, 1, "default", "none"), (17, 96, 32, 1, "default", "none"),
+    (0, 128, 32, 1, "default", "none"), (17, 128, 32, 0, "default", "none"), (17, 96, 128, 1, "default", "none"),
+    # beyond 32-bit element offsets (M K = 2^31, N K = 2^31): the predicate alone, nothing large is allocated
+    (2 ** 26, 64, 32, 1, "default", "none"), (1, 2 ** 26, 32, 1, "default", "none"),
+]
+
+# ---- TN: (M, N, T, batch, route) ---------------------------------------------------------------------------------------------------------------
+# M, N in {64, 128, 192, 256, 320}, T in {1, 4, 31, 32, 33, 63, 64, 65, 96, 777} (+ 256: the T-split on 4 compute units), batch in {1, 2, 16, 36}
+TN_SHAPES = [
+    (64, 64, 1, 1, "default"), (64, 128, 4, 2, "default"), (128, 64, 31, 1, "default"), (128, 128, 32, 2, "default"), (192, 64, 33, 1, "default"),
+    (64, 192, 63, 2, "default"), (256, 128, 64, 1, "default"), (64, 256, 65, 16, "default"), (320, 320, 33, 1, "default"), (64, 64, 777, 1, "default"),
+    (256, 256, 777, 1, "default"), (64, 64, 32, 36, "default"), (256, 320, 31, 2, "default"), (192, 192, 96, 1, "default"), (64, 128, 1, 36, "default"),
+    # the row-share kernel, complete products in one slab: N % 128 == 0, T % 32 == 0, T >= 64, eight 16-row blocks per compute unit
+    (128, 128, 64, 16, "default"), (320, 128, 96, 2, "default"), (192, 256, 96, 2, "default"), (64, 128, 64, 36, "default"), (320, 256, 64, 2, "default"),
+    (128, 128, 256, 2, "default"),                                   # too few blocks, 8 chunks: the T-split, two slabs
+    (256, 128, 64, 16, "cus16"),                                     # the XCD-coherent schedule
+    (128, 128, 65, 2, "t128"), (256, 128, 777, 1, "t128"), (128, 64, 96, 2, "t128x64"), (256, 192, 33, 1, "t128x64"), (64, 128, 63, 2, "t64x128"),
+    (192, 256, 4, 1, "t64x128"), (128, 128, 96, 1, "t64"),
+    (128, 256, 96, 2, "ws1"), (256, 128, 33, 1, "ws2"), (128, 128, 777, 1, "ws4"), (128, 128, 777, 1, "ws2p3"),
+    # refused
+    (0, 64, 32, 1, "default"), (32, 64, 32, 1, "default"), (96, 64, 32, 1, "default"), (64, 0, 32, 1, "default"), (64, 96, 32, 1, "default"),
+    (64, 64, 0, 1, "default"), (64, 64, 32, 0, "default"),
+]
+
+# ---- hifihr_weight_transpose: (K, RS, C) -----------------------------------------------------------------------------------------------------
+TRANSPOSE_SHAPES = [(1, 1, 1), (3, 9, 5), (64, 9, 3), (7, 1, 64), (33, 9, 31), (64, 49, 4), (130, 1, 257), (256, 9, 64),
+                    (0, 9, 4), (4, 0, 4), (4, 9, 0), (-1, 9, 4)]
+
+# ---- fully connected: (B, I, O, act, bn, running, need_dx) -------------------------------------------------------------------------------------
+# B in {1, 2, 31, 32, 33, 63, 64, 65, 70, 129} (32- and 64-row blocks of the forward, one to three of them), I in {1, 3, 4, 31, 32, 33, 36, 72,
+# 128, 1038, 1100} (16-byte loads at I % 4 == 0, the 32-wide chunks), O in {1, 3, 20, 33, 48, 300}, act 0..3; batch-norm at B in {1, 2, 64}
+LINEAR_SHAPES = [
+    (1, 1, 1, 0, False, False, True), (2, 3, 3, 1, False, False, True), (31, 4, 20, 2, False, False, True), (32, 31, 33, 3, False, False, True),
+    (33, 32, 48, 1, False, False, False), (63, 33, 300, 0, False, False, True), (64, 36, 1, 1, False, False, True), (65, 72, 3, 2, False, False, False),
+    (70, 128, 20, 3, False, False, True), (129, 1038, 33, 1, False, False, True), (2, 1100, 48, 0, False, False, True), (32, 128, 300, 1, False, False, True),
+    (129, 4, 3, 0, False, False, True), (1, 1038, 300, 2, False, False, True), (64, 1100, 20, 3, False, False, False),
+    (1, 36, 20, 1, True, True, True), (2, 72, 33, 1, True, True, True), (64, 128, 48, 1, True, True, True), (64, 33, 300, 0, True, False, True),
+    (2, 3, 1, 0, True, True, False), (1, 1100, 3, 0, True, False, True), (32, 31, 20, 1, True, True, True),
+    # refused: batch-norm above 64 rows, batch-norm with swish / sigmoid
+    (65, 36, 20, 1, True, True, True), (32, 36, 20, 2, True, True, True), (32, 36, 20, 3, True, True, True),
+]
+# groups: members (B, I, O, act, with_dx); 1..6 members, different sizes in one launch, with and without dx
+LINEAR_GROUPS = [
+    [(32, 36, 20, 1, True)],
+    [(2, 3, 1, 0, True), (33, 128, 48, 1, False)],
+    [(1, 1, 3, 1, True), (64, 72, 20, 0, True), (65, 33, 33, 1, False), (31, 4, 300, 0, True), (129, 32, 3, 1, True), (70, 1038, 20, 0, False)],
+    [(32, 128, 48, 1, True), (32, 128, 48, 0, True), (32, 1100, 1, 1, False)],
+    # refused: 7 members, act 2 / 3
+    [(2, 4, 4, 0, True)] * 7, [(2, 4, 4, 0, True), (2, 4, 4, 2, True)], [(2, 4, 4, 3, True)],
+]
+
+# ---- Winograd transforms: (N, H, W, C, K), each at m = 2 and m = 4 ----------------------------------------------------------------------------
+# H, W in {1, 2, 3, 4, 5, 6, 7, 9, 13, 14} (images below one tile, ragged last tiles, non-square), N in {1, 2, 3, 16, 17, 32} (at m = 4 the
+# tiles of 16 square images with H % 4 in {1, 2} are cut from 4 x 4-image mosaics: those and their plain neighbours), C, K in {4, 8, 24, 32, 64,
+# 100} for the transforms alone and 64 / 128 where the library's own products run as well
+WINO_LAYERS = [
+    (1, 1, 1, 4, 8), (1, 2, 3, 8, 4), (2, 3, 1, 24, 32), (1, 4, 2, 32, 24), (1, 5, 6, 100, 8), (3, 6, 5, 8, 100), (1, 7, 9, 64, 4), (2, 9, 7, 4, 64),
+    (1, 13, 14, 8, 8), (1, 14, 13, 24, 4),
+    (16, 5, 5, 4, 4), (16, 6, 6, 8, 4), (17, 5, 5, 4, 8), (16, 5, 6, 4, 4), (32, 5, 5, 4, 4), (16, 13, 13, 4, 4), (16, 14, 14, 4, 4), (16, 7, 7, 4, 4),
+    (1, 4, 4, 64, 64), (2, 7, 5, 128, 64), (3, 9, 9, 8, 24), (16, 6, 6, 64, 64),
+]
+WINO_GEOMS = [g + (m,) for g in WINO_LAYERS for m in (2, 4)]
+WINO_GEOMS += [(1, 4, 4, 8, 8, 0), (1, 4, 4, 8, 8, 3), (1, 4, 4, 8, 8, 8), (2, 5, 5, 64, 64, 3),               # refused: m
+               (1, 4, 4, 6, 8, 2), (1, 4, 4, 6, 8, 4), (1, 4, 4, 8, 6, 2), (1, 4, 4, 8, 6, 4), (1, 4, 4, 0, 8, 4),      # refused: C, K
+               (0, 4, 4, 8, 8, 4), (1, 0, 4, 8, 8, 2), (1, 4, 0, 8, 8, 4)]                                           # refused: N, H, W
+
+# the F(4x4) layer whose two backward products the emulator takes as ONE launch (hifihr_wino4_bwd_gemm_pair_supported) wants 16 compute units
+WINO_LAYERS.append((16, 5, 5, 128, 128))
+WINO_LAYERS.append((1, 4, 4, 176, 192))                    # K C / 4 > 8192: the weight-gradient transform's second kernel
+WINO_GEOMS[:0] = [g + (m,) for g in WINO_LAYERS[-2:] for m in (2, 4)]
+
+
+def wino_route(g):
+    return "cus16" if tuple(g[3:5]) == (128, 128) else "default"
+
+
+# ---- batch-norm fused into the F(4x4) transforms: (N, H, W, C, m, residual, addend) --------------------------------------------------------------
+WINO_BN_GEOMS = [(1, 1, 1, 4, 4, False, False), (1, 5, 6, 8, 4, True, True), (2, 3, 7, 24, 4, False, True), (16, 5, 5, 64, 4, True, False),
+                 (16, 6, 6, 4, 4, False, False), (1, 9, 13, 100, 4, True, True), (3, 4, 4, 260, 4, False, False), (2, 3, 3, 512, 4, True, True),
+                 (1, 14, 2, 512, 4, False, True),
+                 (2, 3, 3, 516, 4, True, True), (1, 4, 4, 516, 4, False, False), (1, 4, 4, 6, 4, False, True), (1, 5, 6, 8, 2, True, True),      # refused
+                 (1, 5, 6, 8, 0, False, False), (1, 5, 6, 1024, 4, False, False)]
+
+
+class gemm_route:
+    """The HIFIHR_GEMM_* switches of one route, for the duration of a case (the library re-reads them on every call)."""
+
+    def __init__(self, name):
+        self.env = GEMM_ROUTES[name]
+
+    def __enter__(self):
+        self.saved = {k: _os.environ.pop(k, None) for k in GEMM_SWITCHES}
+        _os.environ.update(self.env)
+
+    def __exit__(self, *exc):
+        for k, v in self.saved.items():
+            _os.environ.pop(k, None)
+            if v is not None:
+                _os.environ[k] = v

@@ -401,3 +401,27 @@ def test_ssim_contract_every_entry_on_every_geometry(lib, layer_tally, geo):
 @pytest.mark.parametrize("count", SSIM_FINISH_COUNTS)
 def test_ssim_finish_contract_on_every_count(lib, layer_tally, count):
     kc.ssim_finish_contract_case(lib, "cuda", count, seed=count)
+
+
+# ---- the GEMM contract's fully-connected half (tests/kernel_cases.py "fully connected"): the emulator's lists
+# (tests/test_hostsim_gemm_contract.py) plus the regression heads' own sizes at batch 64 and a wide squeeze-excite layer
+from kernel_cases import LINEAR_GROUPS, LINEAR_SHAPES  # noqa: E402
+
+LINEAR_SHAPES_GPU = [(64, 2048, 512, 1, True, True, True), (129, 2304, 96, 2, False, False, True), (48, 96, 2304, 3, False, False, True)]
+LINEAR_GROUPS_GPU = [[(64, 512, 128, 1, True), (64, 512, 32, 0, True), (64, 512, 300, 1, False), (64, 1100, 48, 1, True), (33, 512, 3, 0, True)]]
+
+
+@pytest.fixture(scope="module")
+def linear_tally():
+    yield None
+    kc.layer_contract_report("fully-connected entries on the GPU", ("linear",))
+
+
+@pytest.mark.parametrize("geo", LINEAR_SHAPES + LINEAR_SHAPES_GPU, ids=lambda g: "x".join(map(str, g)))
+def test_linear_contract_on_every_shape(lib, linear_tally, geo):
+    assert kc.linear_contract_case(lib, "cuda", *geo, seed=sum(map(int, geo))) == kc.linear_contract_expect(*geo[:5])
+
+
+@pytest.mark.parametrize("members", LINEAR_GROUPS + LINEAR_GROUPS_GPU, ids=lambda ms: f"{len(ms)}x" + "_".join(map(str, ms[0])))
+def test_linear_group_contract(lib, linear_tally, members):
+    assert kc.linear_group_contract_case(lib, "cuda", list(members), seed=len(members)) == (len(members) <= kc.LINEAR_MAX_GROUP and all(m[3] < 2 for m in members))

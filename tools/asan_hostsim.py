@@ -122,7 +122,31 @@ def lpips():
     lc.conv_bias_relu_contract_case(lib, "cpu", 1, 7, 6, 64, 192, 5, 1, 2, seed=5)
 
 
-GROUPS = {"conv": conv, "render": render, "wino": wino, "round5": round5, "round6": round6, "contract": contract, "lpips": lpips}
+def gemm_contract():
+    """Every GEMM, Winograd-transform and fully-connected entry on the lists of tests/test_hostsim_gemm_contract.py (refused calls included),
+    each GEMM shape under its own routing switches."""
+    gl = kc
+    for g in gl.NT_SHAPES:
+        with gl.gemm_route(g[4]):
+            kc.bgemm_nt_contract_case(lib, "cpu", *g[:4], ws_mode=g[5], seed=sum(g[:4]) % 1000)
+    for g in gl.TN_SHAPES:
+        with gl.gemm_route(g[4]):
+            kc.bgemm_tn_contract_case(lib, "cpu", *g[:4], seed=sum(g[:4]) % 1000)
+    for g in gl.TRANSPOSE_SHAPES:
+        kc.weight_transpose_contract_case(lib, "cpu", *g, seed=sum(g))
+    for g in gl.WINO_GEOMS:
+        with gl.gemm_route(gl.wino_route(g)):
+            kc.wino_chain_contract_case(lib, "cpu", *g, seed=sum(g))
+    for g in gl.WINO_BN_GEOMS:
+        kc.wino_bn_contract_case(lib, "cpu", *g, seed=sum(map(int, g)))
+    for g in gl.LINEAR_SHAPES:
+        kc.linear_contract_case(lib, "cpu", *g, seed=sum(map(int, g)))
+    for ms in gl.LINEAR_GROUPS:
+        kc.linear_group_contract_case(lib, "cpu", list(ms), seed=len(ms))
+
+
+GROUPS = {"conv": conv, "render": render, "wino": wino, "round5": round5, "round6": round6, "contract": contract, "lpips": lpips,
+          "gemm_contract": gemm_contract}
 for g in (sys.argv[1:] or list(GROUPS)):
     GROUPS[g]()
     print(f"asan: {g} clean", flush=True)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# AddressSanitizer over the kernel sources on the CPU emulator: bash tools/asan_hostsim.sh [conv|render|wino|contract|lpips ...]
+# AddressSanitizer over the kernel sources on the CPU emulator: bash tools/asan_hostsim.sh [conv|render|wino|contract|lpips|gemm_contract ...]
 # (GPU ASan / xnack+ builds are not available on the pool; ASan warns about swapcontext -- the emulator's fibers -- once, harmlessly.)
 set -eu
 cd "$(dirname "$0")/.."

@@ -15,6 +15,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
 import kernel_cases as kc                      # noqa: E402
 import test_hostsim_layer_contract as lists    # noqa: E402
+gemm_lists = kc                               # (the GEMM contract's lists live next to its case bodies)
 
 RATIO, FLOOR = {}, {}
 F32, F64 = torch.float32, torch.float64
@@ -98,6 +99,51 @@ def main():
     for count in lists.SSIM_FINISH_COUNTS:
         p = torch.rand(count, generator=torch.Generator().manual_seed(count)) * 1024
         note("ssim_val", p.sum().reshape(1), p.double().sum().reshape(1), count, where=f"ssim_finish {count}")
+    # the GEMM contract (tests/test_hostsim_gemm_contract.py): torch.matmul in fp32 against float64, every slab of the TN products
+    for g in gemm_lists.NT_SHAPES:
+        M, N, K, batch = g[:4]
+        if kc.bgemm_nt_expect(M, N, K, batch):
+            a, b = kc.gemm_operands("randn", batch, M, N, K, sum(g[:4]) % 1000, False)
+            note("gemm_nt", torch.matmul(a, b.transpose(1, 2)), torch.matmul(a.double(), b.double().transpose(1, 2)), K, where=f"nt {g[:4]}")
+    for g in gemm_lists.TN_SHAPES:
+        M, N, T, batch = g[:4]
+        if kc.bgemm_tn_expect(M, N, T, batch):
+            a, b = kc.gemm_operands("randn", batch, M, N, T, sum(g[:4]) % 1000, True)
+            for lo, hi in {(0, T)} | {kc.bgemm_tn_slab_rows(T, 3, z) for z in range(3) if T >= 96}:
+                note("gemm_tn", torch.matmul(a[:, lo:hi].transpose(1, 2), b[:, lo:hi]),
+                     torch.matmul(a[:, lo:hi].double().transpose(1, 2), b[:, lo:hi].double()), hi - lo, where=f"tn {g[:4]} rows {lo}..{hi}")
+    for g in gemm_lists.LINEAR_SHAPES:
+        B, I, O, act, bn = g[:5]
+        if kc.linear_contract_expect(B, I, O, act, bn):
+            inp = kc.linear_contract_inputs(B, I, O, sum(map(int, g)))
+            r64 = kc.linear_contract_ref(inp, act, bn)
+            mask = (r64["y"][2] > 0) if act == 1 else None                    # the fp32 run keeps the float64 run's ReLU decisions
+            r32 = kc.linear_contract_ref(inp, act, bn, dt=F32, mask=mask)
+            both(r64, r32, [n for n in r64], f"linear {g}")
+    # Winograd: F(2x2) and every weight gradient against fp32 conv2d and its autograd; F(4x4) y / dx / dw are another algorithm than fp32 direct
+    # convolution: the test's own chain (kernel transforms on the emulator around a matmul) with the float64 product replaced by an fp32 one
+    lib = kc.build_hostsim()
+    table = dict(kc.LAYER_CONTRACT_C)
+    for g in gemm_lists.WINO_GEOMS:
+        if not kc.wino_contract_expect(*g):
+            continue
+        inp = kc.wino_contract_inputs(*g[:5], sum(g))
+        if g[5] == 2:
+            r64, r32 = kc.wino_contract_ref(inp), kc.wino_contract_ref(inp, dt=F32)
+            for n, kind in (("y", "wino_fwd"), ("dx", "wino_fwd"), ("dw", "wino_wgrad")):
+                note(kind, r32[n][1], r64[n][1], r64[n][0], where=f"wino {g} {n}")
+        else:
+            for kind in ("wino4_fwd", "wino4_wgrad", "bn_sum"):
+                kc.LAYER_CONTRACT_C[kind] = (1.0, float("inf"))               # bound = sqrt(L) max|ref| + cond: the logged err / bound is the ratio
+            before = {e: v[2] for e, v in kc.LAYER_CONTRACT_LOG.items()}
+            for e in ("_wino_output_transform", "_wino_output_transform_act", "_wino_dw_transform_parts"):
+                kc.LAYER_CONTRACT_LOG.pop(e, None)
+            kc.wino_chain_contract_case(lib, "cpu", *g, seed=sum(g), product=F32, log=False)
+            kc.LAYER_CONTRACT_C.update(table)
+            for e, kind in (("_wino_output_transform", "wino4_fwd"), ("_wino_dw_transform_parts", "wino4_wgrad")):
+                r = kc.LAYER_CONTRACT_LOG[e][2]
+                if r > RATIO.get(kind, (0.0, ""))[0]:
+                    RATIO[kind] = (r, f"wino {g} (fp32 product, emulator)")
     print(f"{'kind':14s} {'fp32 torch ratio':>17s} {'x 4':>10s} {'table c':>10s} {'cap':>8s}   worst at")
     for kind, (c, cap) in kc.LAYER_CONTRACT_C.items():
         r, where = RATIO.get(kind, (0.0, "-"))
