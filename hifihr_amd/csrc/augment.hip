@@ -211,16 +211,25 @@ __global__ __launch_bounds__(256) void freihand_batch_meta_kernel(BatchMeta m) {
 // The kernels follow that arithmetic step by step (IEEE double on the device, integer accumulation): bit-exact with Pillow
 // (tests/golden/ho3d_path.npz holds Pillow's own outputs).
 //   ho3d_coeff_kernel     (4 tables, B) x 256: table t = filter (t >> 1: bilinear, bicubic) x axis (t & 1: x, y): per output row / column its
-//                         first source index, tap count and <= kHoTaps fixed-point coefficients (Resample.c precompute_coeffs +
+//                         first source index, tap count and <= ho_taps(out_size) fixed-point coefficients (Resample.c precompute_coeffs +
 //                         normalize_coeffs_8bpc)
-//   ho3d_resample_kernel  thread = output pixel: for each of its <= kHoTaps source rows the horizontal sum (rounded, clipped to 8 bits),
+//   ho3d_resample_kernel  thread = output pixel: for each of its source rows the horizontal sum (rounded, clipped to 8 bits),
 //                         then the vertical sum of those; frame as u8 / 255 in three planes, mask as round(u8 / 255)
 //   ho3d_meta_kernel      uv21_crop = (uv21 - centre) * scale + 112, K_crop = T . S . K (:1186-1210), xyz21 gathered
 // ------------------------------------------------------------------------------------------------
-constexpr int kHoTaps = 16;          // taps per output element: 2 * ceil(support) + 1 <= 13 for a 640-pixel window with the bicubic filter
+constexpr int kHoMaxWindow = 800;    // HIFIHR_HO3D_MAX_WINDOW: the longest edge of a crop box that is resampled (hifihr_amd.data.ho3d_crop_windows
+                                     // makes at most 640 / 0.8 = 800 pixels at any inp_res); a longer, an empty or an inverted box gives zeros
 constexpr int kHoBits = 32 - 8 - 2;  // PRECISION_BITS of Resample.c
 
-struct Ho3dTables {                  // per sample and table: bounds[out][2] = (first source index, taps), kk[out][kHoTaps]
+// Row length of the coefficient tables at an output size: what Resample.c allocates per output element for the widest filter (bicubic,
+// support 2) at the longest window, ksize = 2 ceil(support x scale) + 1, and never more than the window holds.  15 at out_size 256,
+// 17 at 224, 201 at 16, 800 at 1.
+__host__ __device__ inline int ho_taps(int out_size) {
+  const int k = 2 * ((2 * kHoMaxWindow + out_size - 1) / out_size) + 1;
+  return k < kHoMaxWindow ? k : kHoMaxWindow;
+}
+
+struct Ho3dTables {                  // per sample and table: bounds[out][2] = (first source index, taps), kk[out][ho_taps(out)]
   int* bounds;
   int* kk;
 };
@@ -238,11 +247,12 @@ __global__ __launch_bounds__(256) void ho3d_coeff_kernel(const int* __restrict__
   const int b = blockIdx.y, t = blockIdx.x;                  // table t: filter t >> 1, axis t & 1
   const int xx = threadIdx.x;
   if (xx >= out_size) return;
+  const int taps = ho_taps(out_size);
   const int* box = boxes + b * 4;                            // x0, y0, x1, y1 of the rounded crop box
   const int in_size = (t & 1) ? box[3] - box[1] : box[2] - box[0];
   const int bicubic = t >> 1;
   int* bo = tb.bounds + ((size_t)(b * 4 + t) * out_size + xx) * 2;
-  int* ko = tb.kk + ((size_t)(b * 4 + t) * out_size + xx) * kHoTaps;
+  int* ko = tb.kk + ((size_t)(b * 4 + t) * out_size + xx) * taps;
   const double scale = (double)in_size / (double)out_size;
   const double filterscale = scale < 1.0 ? 1.0 : scale;
   const double support = (bicubic ? 2.0 : 1.0) * filterscale;
@@ -253,18 +263,16 @@ __global__ __launch_bounds__(256) void ho3d_coeff_kernel(const int* __restrict__
   int xmax = (int)(center + support + 0.5);
   if (xmax > in_size) xmax = in_size;
   xmax -= xmin;
-  if (xmax > kHoTaps) xmax = kHoTaps;                        // (cannot happen for windows <= 640 pixels; keeps the table in bounds)
-  if (xmax < 0) xmax = 0;
-  double k[kHoTaps];
+  // no taps -- the resampler then writes 0 -- for an empty or inverted box (Pillow raises there) and for a window above kHoMaxWindow,
+  // whose rows could outgrow the table (xmax <= ksize <= taps for every window up to it)
+  if (xmax < 0 || in_size <= 0 || in_size > kHoMaxWindow) xmax = 0;
+  if (xmax > taps) xmax = taps;                              // (cannot happen; keeps the table in bounds)
+  // Resample.c keeps the filter values in an array and divides them by their sum; evaluating the filter twice gives the same doubles
   double ww = 0.0;
-  for (int x = 0; x < kHoTaps; ++x) {
-    double w = 0.0;
-    if (x < xmax) { w = ho_filter(bicubic, (x + xmin - center + 0.5) * ss); ww += w; }
-    k[x] = w;
-  }
-  for (int x = 0; x < kHoTaps; ++x) {
-    double v = k[x];
-    if (x < xmax && ww != 0.0) v /= ww;
+  for (int x = 0; x < xmax; ++x) ww += ho_filter(bicubic, (x + xmin - center + 0.5) * ss);
+  for (int x = 0; x < xmax; ++x) {
+    double v = ho_filter(bicubic, (x + xmin - center + 0.5) * ss);
+    if (ww != 0.0) v /= ww;
     ko[x] = v < 0 ? (int)(-0.5 + v * (double)(1 << kHoBits)) : (int)(0.5 + v * (double)(1 << kHoBits));
   }
   bo[0] = xmin; bo[1] = xmax;
@@ -289,8 +297,9 @@ __global__ __launch_bounds__(256) void ho3d_resample_kernel(const uint32_t* __re
   const int bx0 = box[0], by0 = box[1];
   const size_t tx = (size_t)(b * 4 + 2 * which) * out_size + xx, ty = (size_t)(b * 4 + 2 * which + 1) * out_size + yy;
   const int x0 = tb.bounds[tx * 2], nx = tb.bounds[tx * 2 + 1], y0 = tb.bounds[ty * 2], ny = tb.bounds[ty * 2 + 1];
-  const int* kx = tb.kk + tx * kHoTaps;
-  const int* ky = tb.kk + ty * kHoTaps;
+  const int taps = ho_taps(out_size);
+  const int* kx = tb.kk + tx * taps;
+  const int* ky = tb.kk + ty * taps;
   const size_t frame = (size_t)idx[b] * FH * FW;
   const int half = 1 << (kHoBits - 1);
   int v0 = half, v1 = half, v2 = half;
@@ -369,11 +378,11 @@ hipError_t launch_ho3d_batch(const uint32_t* img, const uint8_t* mask, const flo
   return hipGetLastError();
 }
 
-size_t ho3d_workspace_bytes(int B, int out_size) { return (size_t)B * 4 * out_size * (2 + kHoTaps) * sizeof(int); }
+size_t ho3d_workspace_bytes(int B, int out_size) { return (size_t)B * 4 * out_size * (2 + ho_taps(out_size)) * sizeof(int); }
 
 hipError_t launch_freihand_augment(const uint32_t* img, const uint8_t* mask, const int* idx, const int* coef, int B, int H, int W,
                                    float* out_img, float* out_mask, hipStream_t st) {
-  if (B <= 0 || H <= 0 || W <= 0 || (long)H * W >= (1L << 24)) return hipErrorInvalidValue;
+  if (B <= 0 || H <= 0 || W <= 0 || (long)H * W >= (1L << 24)) return hipErrorInvalidValue;      // (the entry refuses these first)
   launch_augment_planes(img, mask, idx, coef, B, H, W, out_img, out_mask, nullptr, st);
   return hipGetLastError();
 }

@@ -5,9 +5,8 @@
 // centre, Frobenius-normalise, scipy.linalg.orthogonal_procrustes, apply).  With A = (gt - mean)/s1 and B = (pred - mean)/s2
 // (s = Frobenius norm + 1e-8), scipy takes  u w v^T = svd(A^T B),  R = u v^T,  scale = sum(w)  -- no determinant
 // correction, a reflection is allowed -- and the aligned prediction is  (B R^T) scale s1 + mean(gt).
-// R is the orthogonal polar factor of M = A^T B:  M = R P,  P = (M^T M)^(1/2) = V diag(w) V^T,  so
-//   R = M V diag(1/w) V^T   and   scale = trace(P) = sum(w),
-// with V, w^2 from a Jacobi eigen-decomposition of the symmetric 3x3 M^T M.  All of it in fp64 (numpy does the same on
+// R is the orthogonal polar factor of M = A^T B and scale = sum(w); both come from a one-sided Jacobi SVD of the 3x3 M (polar3 below),
+// which also completes R where M is rank-deficient (coplanar / collinear points), as scipy's full SVD does.  All of it in fp64 (numpy does the same on
 // fp64 arrays); the points are read as fp32, 12 bytes per point per set: the kernel is HBM / latency bound and tiny.
 #include <hip/hip_runtime.h>
 
@@ -31,35 +30,82 @@ __device__ double block_sum(double v, double* red) {
   return red[0];
 }
 
-// eigen-decomposition of a symmetric 3x3 (cyclic Jacobi): S = V diag(l) V^T
-__device__ void jacobi3(double S[3][3], double V[3][3], double l[3]) {
+// Orthogonal polar factor R = U V^T and scale = sum of the singular values of a 3x3 M = U diag(w) V^T, from a one-sided (Hestenes) Jacobi
+// SVD of M itself: right rotations make the columns of W = M V orthogonal, their lengths are w.  Working on M -- not on M^T M -- keeps
+// the condition number unsquared, so a singular value of 1e-8 of the largest still has its direction to fp64 rounding.  The third left
+// vector is never taken from a (possibly vanishing) column: it is +-(u1 x u2), the sign read off the column where that column is
+// above rounding.  Rank-deficient M (LAPACK returns SOME orthonormal completion there, scipy takes it): the missing directions are
+// completed to the proper rotation, det R = +1; see include/hifihr.h for what is and is not unique then.
+__device__ void polar3(const double M[3][3], double R[3][3], double* scale) {
+  double W[3][3], V[3][3];
   for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 32; ++sweep) {
-    const double off = S[0][1] * S[0][1] + S[0][2] * S[0][2] + S[1][2] * S[1][2];
-    const double diag = S[0][0] * S[0][0] + S[1][1] * S[1][1] + S[2][2] * S[2][2];
-    if (off <= 1e-60 + 1e-34 * diag) break;
+    for (int j = 0; j < 3; ++j) { W[i][j] = M[i][j]; V[i][j] = i == j ? 1.0 : 0.0; }
+  for (int sweep = 0; sweep < 40; ++sweep) {
+    bool rotated = false;
     for (int p = 0; p < 2; ++p)
       for (int q = p + 1; q < 3; ++q) {
-        if (S[p][q] == 0.0) continue;
-        const double theta = (S[q][q] - S[p][p]) / (2.0 * S[p][q]);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        double al = 0.0, be = 0.0, ga = 0.0;
+        for (int k = 0; k < 3; ++k) { al += W[k][p] * W[k][p]; be += W[k][q] * W[k][q]; ga += W[k][p] * W[k][q]; }
+        if (ga == 0.0 || fabs(ga) <= 2.3e-16 * sqrt(al) * sqrt(be)) continue;
+        rotated = true;
+        const double zeta = (be - al) / (2.0 * ga);
+        const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
         const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 3; ++k) {              // S <- S J (columns p, q)
-          const double a = S[k][p], b = S[k][q];
-          S[k][p] = c * a - s * b; S[k][q] = s * a + c * b;
-        }
-        for (int k = 0; k < 3; ++k) {              // S <- J^T S (rows p, q)
-          const double a = S[p][k], b = S[q][k];
-          S[p][k] = c * a - s * b; S[q][k] = s * a + c * b;
-        }
-        for (int k = 0; k < 3; ++k) {              // V <- V J
-          const double a = V[k][p], b = V[k][q];
-          V[k][p] = c * a - s * b; V[k][q] = s * a + c * b;
+        for (int k = 0; k < 3; ++k) {
+          const double a = W[k][p], b = W[k][q];
+          W[k][p] = c * a - s * b; W[k][q] = s * a + c * b;
+          const double e = V[k][p], f = V[k][q];
+          V[k][p] = c * e - s * f; V[k][q] = s * e + c * f;
         }
       }
+    if (!rotated) break;
   }
-  l[0] = S[0][0]; l[1] = S[1][1]; l[2] = S[2][2];
+  double w[3];
+  int o[3] = {0, 1, 2};
+  for (int k = 0; k < 3; ++k) w[k] = sqrt(W[0][k] * W[0][k] + W[1][k] * W[1][k] + W[2][k] * W[2][k]);
+  for (int i = 0; i < 2; ++i)                       // descending order of w
+    for (int j = 0; j < 2 - i; ++j)
+      if (w[o[j]] < w[o[j + 1]]) { const int tmp = o[j]; o[j] = o[j + 1]; o[j + 1] = tmp; }
+  *scale = w[0] + w[1] + w[2];
+  const double w1 = w[o[0]], w2 = w[o[1]], w3 = w[o[2]];
+  const double kRank = 1e-14;                        // a column below this fraction of the largest is rounding of the sums that made M
+  double u[3][3], v[3][3];                           // [k][.]: k-th left / right singular vector
+  for (int k = 0; k < 3; ++k)
+    for (int i = 0; i < 3; ++i) v[k][i] = V[i][o[k]];
+  if (!(w1 > 0.0)) {                                 // M = 0 (a set that is a single point): scale = 0, any R serves
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) R[i][j] = i == j ? 1.0 : 0.0;
+    return;
+  }
+  for (int i = 0; i < 3; ++i) u[0][i] = W[i][o[0]] / w1;
+  double n2 = 0.0;
+  if (w2 > kRank * w1) {                             // u2: the second column, re-orthogonalised against u1
+    double d = 0.0;
+    for (int i = 0; i < 3; ++i) d += W[i][o[1]] * u[0][i];
+    for (int i = 0; i < 3; ++i) { u[1][i] = W[i][o[1]] - d * u[0][i]; n2 += u[1][i] * u[1][i]; }
+  }
+  if (!(w2 > kRank * w1) || !(n2 > 0.0)) {           // rank 1: any unit vector orthogonal to u1 (the axis u1 is smallest along)
+    int m = 0;
+    for (int i = 1; i < 3; ++i) if (fabs(u[0][i]) < fabs(u[0][m])) m = i;
+    n2 = 0.0;
+    for (int i = 0; i < 3; ++i) { u[1][i] = (i == m ? 1.0 : 0.0) - u[0][m] * u[0][i]; n2 += u[1][i] * u[1][i]; }
+  }
+  n2 = sqrt(n2);
+  for (int i = 0; i < 3; ++i) u[1][i] /= n2;
+  u[2][0] = u[0][1] * u[1][2] - u[0][2] * u[1][1];
+  u[2][1] = u[0][2] * u[1][0] - u[0][0] * u[1][2];
+  u[2][2] = u[0][0] * u[1][1] - u[0][1] * u[1][0];
+  double sgn;
+  if (w3 > kRank * w1 && w2 > kRank * w1) {          // the data decide between the rotation and the reflection
+    sgn = (W[0][o[2]] * u[2][0] + W[1][o[2]] * u[2][1] + W[2][o[2]] * u[2][2]) >= 0.0 ? 1.0 : -1.0;
+  } else {                                           // they do not: det U = det V, the proper rotation
+    const double detv = v[0][0] * (v[1][1] * v[2][2] - v[1][2] * v[2][1]) - v[0][1] * (v[1][0] * v[2][2] - v[1][2] * v[2][0]) +
+                        v[0][2] * (v[1][0] * v[2][1] - v[1][1] * v[2][0]);
+    sgn = detv >= 0.0 ? 1.0 : -1.0;
+  }
+  for (int i = 0; i < 3; ++i) u[2][i] *= sgn;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) R[i][j] = u[0][i] * v[0][j] + u[1][i] * v[1][j] + u[2][i] * v[2][j];
 }
 
 }  // namespace
@@ -91,25 +137,12 @@ __global__ __launch_bounds__(kThreads) void procrustes_kernel(const float* __res
   for (int k = 0; k < 9; ++k) m[k] = block_sum(m[k], red);
   const double s1 = sqrt(n1) + 1e-8, s2 = sqrt(n2) + 1e-8;
   if (threadIdx.x == 0) {
-    double M[3][3], S[3][3], V[3][3], l[3];
+    double M[3][3], R[3][3], scale;
     for (int i = 0; i < 3; ++i)
       for (int j = 0; j < 3; ++j) M[i][j] = m[i * 3 + j] / (s1 * s2);          // A^T B
+    polar3(M, R, &scale);
     for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) S[i][j] = M[0][i] * M[0][j] + M[1][i] * M[1][j] + M[2][i] * M[2][j];   // M^T M
-    jacobi3(S, V, l);
-    double w[3], scale = 0.0;
-    for (int k = 0; k < 3; ++k) { w[k] = sqrt(l[k] > 0.0 ? l[k] : 0.0); scale += w[k]; }
-    // R = M V diag(1/w) V^T; a vanishing singular value (coplanar input) leaves that direction out instead of dividing by 0
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) {
-        double r = 0.0;
-        for (int k = 0; k < 3; ++k) {
-          if (w[k] <= 1e-150) continue;
-          const double mv = M[i][0] * V[0][k] + M[i][1] * V[1][k] + M[i][2] * V[2][k];
-          r += mv / w[k] * V[j][k];
-        }
-        sR[i * 3 + j] = r;
-      }
+      for (int j = 0; j < 3; ++j) sR[i * 3 + j] = R[i][j];
     sScale = scale;
   }
   __syncthreads();

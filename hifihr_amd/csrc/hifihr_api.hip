@@ -419,6 +419,7 @@ int hifihr_adam_step_counted(float* params, const float* grads, float* exp_avg, 
   if (!params || !grads || !exp_avg || !exp_avg_sq || !state_d) return fail(HIFIHR_EINVAL, "hifihr_adam_step_counted: bad argument");
   if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) || ((uintptr_t)state_d & 7))
     return fail(HIFIHR_EINVAL, "hifihr_adam_step_counted: buffers must be 16-byte aligned (the state: 8)");
+  if (n == 0) return HIFIHR_OK;                  // as hifihr_adam_step: nothing launched, the counter stays
   HIP_TRY(hifihr::launch_adam_counted(params, grads, exp_avg, exp_avg_sq, n, grad_scale, eps, weight_decay, state_d, (hipStream_t)stream));
   return HIFIHR_OK;
 }
@@ -1518,8 +1519,9 @@ int hifihr_wino_output_transform(const float* M, float* y, float* stats, int N, 
 
 int hifihr_freihand_augment(const uint32_t* img_rgbx, const uint8_t* mask, const int* idx, const int* coef_fix, int B, int H, int W,
                             float* out_img, float* out_mask, void* stream) {
-  if (!idx || !coef_fix || (!out_img && !out_mask) || (out_img && !img_rgbx) || (out_mask && !mask) || B <= 0 || H <= 0 || W <= 0)
-    return fail(HIFIHR_EINVAL, "hifihr_freihand_augment: bad argument");
+  if (!idx || !coef_fix || (!out_img && !out_mask) || (out_img && !img_rgbx) || (out_mask && !mask) || B <= 0 || H <= 0 || W <= 0 ||
+      (long)H * W >= (1L << 24))
+    return fail(HIFIHR_EINVAL, "hifihr_freihand_augment: bad argument (H * W < 2^24)");
   HIP_TRY(hifihr::launch_freihand_augment(img_rgbx, mask, idx, coef_fix, B, H, W, out_img, out_mask, (hipStream_t)stream));
   return HIFIHR_OK;
 }

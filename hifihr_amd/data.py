@@ -272,6 +272,9 @@ def ho3d_crop_windows(uv21, center_noise, scale_noise, inp_res=224, img_wh=(640.
     return center.astype(f), scale, size, box
 
 
+HO3D_MAX_WINDOW = 800          # HIFIHR_HO3D_MAX_WINDOW (include/hifihr.h): the longest box edge hifihr_ho3d_batch resamples
+
+
 class HO3DDeviceCache:
     """The decoded HO-3D training frames resident in device memory + the per-batch hand crop on the device (reference
     data/dataset.py:1023-1215).  images_u8 [n,480,640,3], hand_masks_u8 [n,480,640] (channel 0 of the reference's mask image, 0 / 255),
@@ -316,6 +319,10 @@ class HO3DDeviceCache:
             center_noise = torch.stack([d[0] for d in draws]).numpy()
             scale_noise = torch.cat([d[1] for d in draws]).numpy()
         center, scale, _, box = ho3d_crop_windows(self.window_pts[idxs.numpy()], center_noise, scale_noise, self.inp_res, (float(self.W), float(self.H)))
+        edges = np.concatenate([box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]])
+        if B and (int(edges.max()) > HO3D_MAX_WINDOW or int(edges.min()) <= 0):       # the device cannot refuse a box: it would write zeros
+            raise ValueError(f"HO-3D crop window of {int(edges.min())} .. {int(edges.max())} pixels: hifihr_ho3d_batch resamples boxes of "
+                             f"1 .. {HO3D_MAX_WINDOW} pixels on an edge (include/hifihr.h)")
         slot, host = self._stage(8 * B)
         hv = host.numpy()
         hv[:B] = idxs.numpy().astype(np.int32)

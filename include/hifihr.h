@@ -42,6 +42,11 @@ int hifihr_device_count(void);
  *           side='right', use_pca=True, ncomps=48 => 45 effective PCA coefficients, axis-angle root)
  *          batch_rodrigues/quat2mat      reference utils/manopth/rodrigues_layer.py:43-54,15-40
  *          xyz_from_vertice              reference utils/Freihand_GNN_mano/Freihand_trainer_mano_fullsup.py:175-215
+ * Rodrigues keeps the reference's form, angle = || axisang + 1e-8 ||: a rotation vector of exactly 0 (and of exactly pi) is regular, forward
+ * and backward; the one singular input is the reference's own, every component exactly -1e-8 (angle 0, 0 / 0): NaN here as in fp32 and
+ * float64 PyTorch.
+ * All compute entries below: B = 0 is accepted and writes nothing (nothing is launched); B < 0, root_id >= 21 and a NULL among the
+ * pointers not marked optional are refused with HIFIHR_EINVAL, nothing launched or written.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct hifihr_mano hifihr_mano_t;
 
@@ -61,7 +66,7 @@ int hifihr_mano_lbs_fwd(const hifihr_mano_t* h, const float* pose_d, const float
                         float* verts_d, float* jtr_d, float* saved_vposed_d, void* stream);
 
 /* Gradient of the above: gverts[B][778][3], gjtr[B][21][3] (either may be NULL = zero) ->
- * gpose[B][48], gbeta[B][10] (overwritten).  Deterministic (no float atomics). */
+ * gpose[B][48], gbeta[B][10] (overwritten).  Deterministic (no float atomics).  jtr_d of the forward may be NULL too. */
 int hifihr_mano_lbs_bwd(const hifihr_mano_t* h, const float* pose_d, const float* beta_d,
                         const float* saved_vposed_d, const float* gverts_d, const float* gjtr_d, int B,
                         float* gpose_d, float* gbeta_d, void* stream);
@@ -120,7 +125,11 @@ int hifihr_lbs_fwd(const hifihr_lbs_t* h, const float* theta_d, const float* bet
 
 /* Gradient: gverts[B][V][3], gjoints[B][J][3] (may be NULL = zero) -> gtheta[B][J][3] (overwritten), gbeta[B][S] (ACCUMULATED: the
  * caller passes it zeroed).  scratch[B][J][12] must be zero on entry; it is left holding d(loss)/d(A_j).  Sums over vertices use float
- * atomics: results vary in the last bits from run to run. */
+ * atomics: results vary in the last bits from run to run.
+ * Accumulated / overwritten: gtheta is OVERWRITTEN; gbeta is ACCUMULATED onto whatever it holds; scratch is ACCUMULATED onto its zeros and
+ * comes back as d(sum gverts . verts) / d(A_j) = sum_v weights[v][j] gverts_v [v_shaped_v; 1]^T, 3 x 4 row-major (the gjoints part of the
+ * gradient goes down the chain without passing through it).  B = 0: accepted, nothing written; B < 0 or a NULL among theta, gverts,
+ * scratch, gtheta, verts (and beta / gbeta when S > 0): HIFIHR_EINVAL. */
 int hifihr_lbs_bwd(const hifihr_lbs_t* h, const float* theta_d, const float* beta_d, const float* gverts_d, const float* gjoints_d,
                    int B, float* scratch_zeroed_d, float* gtheta_d, float* gbeta_zeroed_d, void* stream);
 
@@ -190,6 +199,8 @@ int hifihr_render_bwd_uv(const hifihr_renderer_t* h, const float* verts_d, const
  * hand's texture).  NIMBLE's own basis is not available: the caller supplies one (n = 778 * 3 vertex
  * colours for the declared stand-in, n = 1024 * 1024 * 3 for a UV map).  HBM-bound: 4 n (K + 1 + B) algorithmic bytes.
  * bwd: dcoef_zeroed_d[B][K] (ZERO on entry) += sum_n gtex[b][n] basis[k][n]   (float atomics: reproducible to rounding).
+ * tex_d is OVERWRITTEN (no atomics: the same bits on every call); dcoef_zeroed_d is ACCUMULATED onto whatever it holds.
+ * Refused (HIFIHR_EINVAL, nothing launched or written): B <= 0, K outside 1 .. 32, n < 4 or n % 4 != 0, a NULL pointer other than mean_d.
  * ---------------------------------------------------------------------------------------------- */
 int hifihr_texture_pca_fwd(const float* coef_d, const float* basis_d, const float* mean_d /* or NULL */, int B, int K, long n,
                            float* tex_d, void* stream);
@@ -219,6 +230,12 @@ int hifihr_comm_destroy(hifihr_comm* comm);
  * Replaces optimizer.step() of torch.optim.Adam(betas=(0.9,0.999), eps=1e-8, weight_decay=0|0.01)
  * reference train_hrnet.py:111-113, 546-551.  All four buffers are device fp32[n], 16-byte aligned.
  * grads are multiplied by grad_scale before use (1/world_size after a sum all-reduce).  `step` counts from 1.
+ * Deterministic (no atomics on the data): the same inputs give the same bits.  A zero gradient on zero moments leaves the parameters
+ * bit-identical at weight_decay 0 (0 / (0 + eps) = 0).
+ * Refused (HIFIHR_EINVAL, nothing launched or written), by all three entries: a NULL buffer (state_d / dyn_d included), a buffer
+ * that is not 16-byte aligned (state_d: 8-byte), and for hifihr_adam_step `step` < 1.
+ * n = 0 is accepted by all three and is NOT a step: nothing is launched, nothing is written, and hifihr_adam_step_counted's
+ * counter and running products stay as they are.
  * ---------------------------------------------------------------------------------------------- */
 int hifihr_adam_step(float* params_d, const float* grads_d, float* exp_avg_d, float* exp_avg_sq_d, size_t n,
                      float grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
@@ -766,6 +783,23 @@ int hifihr_ssim_bwd_scaled(const float* window11_h, const float* img1_d, const f
  *   bwd: grad_rgba[B][4][H][W] (overwritten; alpha channel 0: re_sil is detached in the reference) from gout_d[>=2]
  *   (texture, mrgb; may be NULL) and g_re_img_d (gradient arriving at re_img_m, e.g. from SSIM; may be NULL).
  * sil_post (models_res_nimble.py:219-220): re_sil[B][H][W] and maskRGBs[B][3][H][W] = images * (re_sil > 0) (may be NULL).
+ *
+ * What the contract tests pin (tests/test_hostsim_tail_contract.py):
+ *   - every output of these entries is OVERWRITTEN, and every one is deterministic (fixed summation order, no float atomics): the same
+ *     bits on a second call.  A term whose element count is 0 (F = 0, NS = 0, NP = 0, a joint set that is not given) is exactly 0.
+ *   - zero lengths.  The edge term gives an edge whose PREDICTED length is exactly 0 no gradient (autograd: 0 / 0 = NaN); an edge whose
+ *     gt length is 0 keeps the gradient of its predicted length.  sign(0) = 0: identical pred and gt give zero L1 gradients.  The bone
+ *     terms use v / (|v| + 1e-4): at |v| = 0 the radial part of the gradient, vn (dn . v) / |v|, is taken as zero (autograd: NaN) and
+ *     2 dn / 1e-4 remains.
+ *   - NaN alpha.  re_sil = NaN at that pixel (NaN > 0 is false), re_img_m = NaN at that pixel only, mask_rgbs / maskRGBs = 0 there; all
+ *     four photo_loss outputs are NaN; the backward reads out[3] = NaN, so EVERY rgb gradient is NaN (with gout_d NULL too: 0 x NaN) and the
+ *     alpha channel stays exact zeros.
+ *   - refused (HIFIHR_EINVAL, nothing launched or written): geom_loss: B / J / V <= 0, F / NS / NP < 0, F > 0 without faces, NS > 0 without
+ *     shape, NP > 0 without pose, the backward with F > 0 and no vertex -> face tables, NULL partial / out / gout / lambda or a NULL
+ *     joints / verts pointer.  joint_terms: J != 21, B <= 0, neither set given, a set without its gt, a gradient without its input, NULL
+ *     out / gout / lambda.  photo_loss / sil_post: B / H / W <= 0, H * W % 4 != 0, a NULL pointer other than g_re_img_d / gout_d
+ *     (sil_post: imgs_d may be NULL when mask_rgbs_d is).  loss_total: nparts outside 1 .. 4, a count outside 0 .. 64, a length below
+ *     its count or above 64, a NULL pointer.  light_split: B <= 0, NULL lights / colors / directions / glights.
  * ---------------------------------------------------------------------------------------------- */
 int hifihr_geom_loss_fwd(const float* joints_d, const float* joints_gt_d, const float* verts_d, const float* verts_gt_d,
                          const float* shape_d, const float* pose_d, const int32_t* faces_d, int B, int J, int V, int F, int NS,
@@ -883,6 +917,16 @@ int hifihr_se_mlp_bwd(float* dgate_acc_d, const float* gate_d, const float* z1_d
  * scipy.linalg.orthogonal_procrustes -- no determinant correction --, apply).
  *   aligned_d[B][N][3] (or NULL) = the aligned prediction;  err_sum_d[B] = sum_n || aligned_n - gt_n ||_2
  * (MPJPE / MPVPE = sum_b err_sum_d[b] / (B N), in the unit of the inputs).
+ * The rotation is the orthogonal polar factor R = U V^T of M = A^T B = U diag(w) V^T (A, B the centred, normalised gt and pred), from
+ * a singular value decomposition of M itself, as scipy takes it: a direction whose singular value vanishes is KEPT.
+ * Rank-deficient input (a set that is coplanar, collinear or a single point, N <= 3 included): R is then not unique -- LAPACK returns
+ * some orthonormal completion, scipy uses that one; this entry completes with the proper rotation (det R = +1) -- and aligned_d may
+ * differ from scipy's by the freedom: a reflection through the plane, a rotation about the line.  When only pred is degenerate the
+ * freedom acts on nothing and aligned_d is unique.  The distances || aligned_n - gt_n || and err_sum_d do not depend on the choice
+ * and equal scipy's.  A singular value down to 1e-12 of the largest still decides R (the points are read as fp32, everything after
+ * is fp64); below 1e-14 it counts as zero.  N = 1, or gt a single repeated point: scale 0, aligned_n = mean(gt).
+ * Deterministic: a second call gives the same bits, and err_sum_d is the same bits with aligned_d NULL or given.
+ * Refused (HIFIHR_EINVAL, nothing launched or written): B <= 0, N <= 0, pred_d / gt_d / err_sum_d NULL.
  * ---------------------------------------------------------------------------------------------- */
 int hifihr_procrustes_error(const float* pred_d, const float* gt_d, int B, int N, float* aligned_d /* or NULL */,
                             float* err_sum_d, void* stream);
@@ -897,6 +941,9 @@ int hifihr_procrustes_error(const float* pred_d, const float* gt_d, int B, int N
  *                         {FIX(a), FIX(b), FIX(c + a/2 + b/2), FIX(d), FIX(e), FIX(f + d/2 + e/2)}, FIX(v) = floor(v * 65536 + 0.5)
  *   out_img_d[B][3][H][W] = u8 / 255,  out_mask_d[B][3][H][W] = round(u8 / 255) repeated over 3 channels (either may be NULL)
  * Bit-exact with PIL for the same coefficients.
+ * Refused (HIFIHR_EINVAL, nothing launched): B / H / W <= 0, H * W >= 2^24 (the kernels index a plane with 32-bit integers scaled by
+ * 16.16 terms; hifihr_freihand_batch and _batch_step refuse the same), idx_d / coef_fix_d NULL, both outputs NULL, an output given
+ * without its source.
  * ---------------------------------------------------------------------------------------------- */
 int hifihr_freihand_augment(const uint32_t* img_rgbx_d, const uint8_t* mask_d, const int* idx_d, const int* coef_fix_d, int B, int H,
                             int W, float* out_img_d, float* out_mask_d, void* stream);
@@ -909,7 +956,10 @@ int hifihr_freihand_augment(const uint32_t* img_rgbx_d, const uint8_t* mask_d, c
  * Cache (device): Ks_d[n][3][3], joints_d[n][J][3], verts_d[n][V][3], scales_d[n].
  * packed_d[25 B] int32, ONE host-to-device copy per batch: idx[B], coef_fix[B][6], post_rot_trans[B][3][3] (float bits),
  * rot_mat[B][3][3] (float bits).  Every output may be NULL.  Outputs: out_Ks[B][3][3], out_Ps[B][3][4], out_joints[B][J][3],
- * out_verts[B][V][3], out_j2d[B][J][2], out_scales[B], out_idxs[B] (int64), out_segm[B][H][W] (int64). */
+ * out_verts[B][V][3], out_j2d[B][J][2], out_scales[B], out_idxs[B] (int64), out_segm[B][H][W] (int64).
+ * J = 0 / V = 0 are accepted (joints_d / verts_d may then be NULL).  Refused (HIFIHR_EINVAL, nothing launched or written), by this entry
+ * and by hifihr_freihand_batch_step: B / H / W <= 0, H * W >= 2^24, J / V < 0, NULL img / mask / Ks / scales / packed, J > 0 without
+ * joints_d, V > 0 without verts_d. */
 int hifihr_freihand_batch(const uint32_t* img_rgbx_d, const uint8_t* mask_d, const float* Ks_d, const float* joints_d, const float* verts_d,
                           const float* scales_d, int J, int V, const int* packed_d, int B, int H, int W, float* out_img_d,
                           float* out_mask_d, long long* out_segm_d, float* out_Ks_d, float* out_Ps_d, float* out_joints_d,
@@ -918,7 +968,8 @@ int hifihr_freihand_batch(const uint32_t* img_rgbx_d, const uint8_t* mask_d, con
  * (reference train_hrnet.py:62-68: root_xyz = joints[:, ROOT]; joints -= root; verts -= root;  models_res_nimble.py:184-186,228-235:
  * the NDC camera terms of PerspectiveCameras(focal_length=-fcl, principal_point=prp)):
  *   out_root[B][3] = joints[:, root_id] (root_id < 0: zeros), out_joints_rel[B][J][3], out_verts_rel[B][V][3],
- *   out_cam_ndc[B][4] = (-2 fx / s, -2 fy / s, 1 - 2 cx / s, 1 - 2 cy / s) with s = image_size, from out_Ks.  Any may be NULL. */
+ *   out_cam_ndc[B][4] = (-2 fx / s, -2 fy / s, 1 - 2 cx / s, 1 - 2 cy / s) with s = image_size, from out_Ks.  Any may be NULL.
+ * The ten outputs shared with hifihr_freihand_batch are the same bits.  Also refused: root_id >= J, image_size <= 0 or NaN. */
 int hifihr_freihand_batch_step(const uint32_t* img_rgbx_d, const uint8_t* mask_d, const float* Ks_d, const float* joints_d,
                                const float* verts_d, const float* scales_d, int J, int V, const int* packed_d, int B, int H, int W,
                                float* out_img_d, float* out_mask_d, long long* out_segm_d, float* out_Ks_d, float* out_Ps_d,
@@ -939,7 +990,15 @@ int hifihr_freihand_batch_step(const uint32_t* img_rgbx_d, const uint8_t* mask_d
  *   out_K_d[B][3][3] = T . S . K (`K_crop`, :1206-1210), out_uv21_d[B][21][2] = (uv21 - centre) * scale + S / 2 (`uv21_crop`, :1186-1188),
  *   out_xyz21_d[B][21][3] = xyz21[idx].  Any output may be NULL.  Pixels bit-exact with Pillow (tests/golden/ho3d_path.npz).
  * ws_d: hifihr_ho3d_workspace_bytes(B, out_size) bytes of scratch (any contents).
+ * Bit-exact for every box up to HIFIHR_HO3D_MAX_WINDOW = 800 pixels on an edge at every out_size in 1 .. 256, whatever the number of
+ * filter taps that takes (800 -> 16: 200 per output pixel and axis; the workspace is sized for it).  800 is the most ho3d_crop_windows can
+ * produce at any inp_res (640 / 0.8).  The boxes live in device memory, so the entry cannot refuse one: a box that is longer than
+ * that on either edge, EMPTY or INVERTED (x1 <= x0 or y1 <= y0; Pillow raises) gives that sample's out_img_d and out_mask_d as all
+ * zeros; the small outputs do not depend on the box.  hifihr_amd.data.HO3DDeviceCache.batch raises on the host for such a window.
+ * Refused (HIFIHR_EINVAL, nothing launched or written): B / FH / FW <= 0, out_size outside 1 .. 256, packed_d or ws_d NULL, ws_bytes
+ * below hifihr_ho3d_workspace_bytes(B, out_size) (which returns 0 for a refused B / out_size), an output given without its source.
  * ---------------------------------------------------------------------------------------------- */
+#define HIFIHR_HO3D_MAX_WINDOW 800
 size_t hifihr_ho3d_workspace_bytes(int B, int out_size);
 int hifihr_ho3d_batch(const uint32_t* img_rgbx_d, const uint8_t* hand_mask_d, const float* Ks_d, const float* uv21_d, const float* xyz21_d,
                       int FH, int FW, const int* packed_d, int B, int out_size, void* ws_d, size_t ws_bytes, float* out_img_d,

@@ -42,8 +42,10 @@ def _bicubic(x: float) -> float:
 FILTERS = {"bilinear": (_bilinear, 1.0), "bicubic": (_bicubic, 2.0)}
 
 
-def precompute_coeffs(in_size: int, in0: float, in1: float, out_size: int, name: str):
-    """Resample.c precompute_coeffs + normalize_coeffs_8bpc -> (ksize, bounds [out, 2] = (xmin, count), kk [out, ksize] int32)."""
+def precompute_coeffs(in_size: int, in0: float, in1: float, out_size: int, name: str, max_taps: int | None = None):
+    """Resample.c precompute_coeffs + normalize_coeffs_8bpc -> (ksize, bounds [out, 2] = (xmin, count), kk [out, ksize] int32).
+    max_taps: NOT Pillow -- a table cut to that many taps per output element (the rest dropped before the normalisation), which is what
+    a fixed-width table does; the tests use it to show that their images expose a dropped tap."""
     filt, fsupport = FILTERS[name]
     scale = (in1 - in0) / out_size
     filterscale = scale if scale >= 1.0 else 1.0
@@ -61,6 +63,8 @@ def precompute_coeffs(in_size: int, in0: float, in1: float, out_size: int, name:
         if xmax > in_size:
             xmax = in_size
         xmax -= xmin
+        if max_taps is not None:
+            xmax = min(xmax, max_taps)
         k = np.zeros(ksize, np.float64)
         ww = 0.0
         for x in range(xmax):
@@ -81,7 +85,7 @@ def _clip8(v: np.ndarray) -> np.ndarray:
     return np.clip(v >> PRECISION_BITS, 0, 255).astype(np.uint8)
 
 
-def pil_resize_u8(img: np.ndarray, out_h: int, out_w: int, name: str) -> np.ndarray:
+def pil_resize_u8(img: np.ndarray, out_h: int, out_w: int, name: str, max_taps: int | None = None) -> np.ndarray:
     """Image.resize((out_w, out_h), filter) of an 8-bit image [h, w] or [h, w, c]; equal sizes: a copy (Image.resize returns self.copy())."""
     squeeze = img.ndim == 2
     a = img[:, :, None] if squeeze else img
@@ -90,7 +94,7 @@ def pil_resize_u8(img: np.ndarray, out_h: int, out_w: int, name: str) -> np.ndar
         return img.copy()
     src = a.astype(np.int64)
     if w != out_w:                                             # horizontal pass
-        _, bounds, kk = precompute_coeffs(w, 0.0, float(w), out_w, name)
+        _, bounds, kk = precompute_coeffs(w, 0.0, float(w), out_w, name, max_taps)
         tmp = np.empty((h, out_w, c), np.uint8)
         for xx in range(out_w):
             x0, n = bounds[xx]
@@ -98,7 +102,7 @@ def pil_resize_u8(img: np.ndarray, out_h: int, out_w: int, name: str) -> np.ndar
             tmp[:, xx, :] = _clip8(acc)
         src = tmp.astype(np.int64)
     if h != out_h:                                             # vertical pass (on the uint8 result of the horizontal one)
-        _, bounds, kk = precompute_coeffs(h, 0.0, float(h), out_h, name)
+        _, bounds, kk = precompute_coeffs(h, 0.0, float(h), out_h, name, max_taps)
         out = np.empty((out_h, src.shape[1], c), np.uint8)
         for yy in range(out_h):
             y0, n = bounds[yy]

@@ -27,8 +27,9 @@ def rodrigues(theta: torch.Tensor) -> torch.Tensor:
 
 
 def lbs_forward(v_template, shapedirs, j_regressor, weights, parents, theta, beta):
-    """theta [B,J,3], beta [B,S] -> verts [B,V,3], posed joints [B,J,3] (my_mano.py:386-451 with th_pose_map dropped)."""
-    v_template, shapedirs, j_regressor, weights = (torch.as_tensor(a, dtype=torch.float32) for a in (v_template, shapedirs, j_regressor, weights))
+    """theta [B,J,3], beta [B,S] -> verts [B,V,3], posed joints [B,J,3] (my_mano.py:386-451 with th_pose_map dropped); computed in
+    theta's dtype (float64 inputs give the float64 reference of the contract tests)."""
+    v_template, shapedirs, j_regressor, weights = (torch.as_tensor(a, dtype=theta.dtype) for a in (v_template, shapedirs, j_regressor, weights))
     B, J = theta.shape[0], theta.shape[1]
     v_shaped = v_template.unsqueeze(0) + torch.einsum("vck,bk->bvc", shapedirs, beta)
     joints = torch.einsum("jv,bvc->bjc", j_regressor, v_shaped)

@@ -4169,3 +4169,1660 @@ class gemm_route:
             _os.environ.pop(k, None)
             if v is not None:
                 _os.environ[k] = v
+
+
+# ------------------------------------------------------------------------------------------------
+# The tail contract: the entries behind the network's heads -- Procrustes (csrc/eval.hip), the two data paths (csrc/augment.hip), Adam
+# (csrc/adam.hip), texture PCA (csrc/texpca.hip), the fused losses (csrc/losses.hip), MANO / LBS (csrc/mano_lbs.hip, csrc/lbs.hip) -- on
+# the lists of tests/test_hostsim_tail_contract.py (the GPU half: tests/test_gpu_tail.py, tests/test_gpu_mano.py), in the layer contract's
+# form: refused with HIFIHR_EINVAL, nothing launched, nothing written -- or a float64 reference inside guard bands, a second call on the
+# same buffers (identical bits where include/hifihr.h says deterministic), accumulate / overwrite as the header states them, every
+# optional pointer NULL at least once.  Pixels, gathers, masks and integer outputs: bit for bit.
+# ------------------------------------------------------------------------------------------------
+TAIL_CONTRACT_ENTRIES = ("procrustes_error", "ho3d_batch", "freihand_augment", "freihand_batch", "freihand_batch_step", "adam_step", "adam_step_dyn",
+                         "adam_step_counted", "texture_pca_fwd", "texture_pca_bwd", "geom_loss_fwd", "geom_loss_bwd", "joint_terms_fwd", "joint_terms_bwd",
+                         "photo_loss_fwd", "photo_loss_bwd", "sil_post", "loss_total_fwd", "loss_total_bwd", "light_split_fwd", "light_split_bwd",
+                         "mano_lbs_fwd", "mano_lbs_bwd", "mano_joints_fwd", "mano_joints_bwd", "mano_full_fwd", "mano_full_bwd", "lbs_fwd", "lbs_bwd")
+# kind: (c, cap) as in LAYER_CONTRACT_C: c = 4 x the worst err / (sqrt(L) max|ref| + cond) of the float64 references run in float32 (plain fp32
+# torch on the CPU) over the lists of tests/test_hostsim_tail_contract.py, printed by tools/layer_contract_c.py.  The older cases' tolerances
+# are absolute or mixed, so they are applied as such (TAIL_LEGACY below, never exceeded); cap repeats their relative part where they have one.
+TAIL_CONTRACT_C = {
+    # kind: (c, cap)                   fp32 torch's worst ratio x 4; the quantities and L
+    "adam_p": (1.7e-7, 1e-5),          # 4.22e-08 x 4   parameters after a step, L = 1                     (adam_case rtol 1e-5, with its 2e-6: adam_passes)
+    "adam_m": (3.3e-7, 3.3e-7),        # 8.22e-08 x 4   exp_avg, L = 1                                     (no older case looks at the moments)
+    "adam_v": (3.8e-7, 3.8e-7),        # 9.48e-08 x 4   exp_avg_sq, L = 1
+    "tex_fwd": (1.7e-7, 1e-5),         # 4.18e-08 x 4   tex, L = K + 1                                     (texture_pca_case 1e-5)
+    "tex_bwd": (1.7e-7, 2e-5),         # 4.04e-08 x 4   dcoef, L = n                                       (texture_pca_case 2e-5 max(1, sqrt(n / 4096)))
+    "geom_out": (1.8e-7, 2e-5),        # 4.31e-08 x 4   each of the five terms, L = its element count      (geom_loss_case 2e-5)
+    "geom_grad": (4.5e-7, 2e-5),       # 1.10e-07 x 4   gj / gshape / gpose (L = 1), gv (L = 1 + edges at the vertex)   (geom_loss_case 2e-5)
+    "photo_out": (7.3e-8, 3e-5),       # 1.82e-08 x 4   texture, mrgb, sil, mean difference, L = B 3 H W (sil: B H W)   (photo_loss_case 3e-5)
+    "photo_img": (1.5e-9, 1e-6),       # 3.72e-10 x 4   re_img_m, L = 1: exact wherever alpha > 0          (photo_loss_case 1e-6 absolute)
+    "photo_grad": (4.3e-7, 2e-5),      # 1.07e-07 x 4   grad_rgba, L = 1                                   (photo_loss_case 2e-5)
+    "joint_out": (8.8e-8, 2e-5),       # 2.19e-08 x 4   joint_2d, bone_direc, bone_direc_3d, L = their element counts   (joint_terms_case 2e-5)
+    "joint_grad": (8.6e-7, 1e-5),      # 2.13e-07 x 4   g_j2d / g_joints per sample, L = 6 (the wrist's five bones and the base term)   (joint_terms_case 1e-5)
+    "total": (7.2e-8, 1e-6),           # 1.79e-08 x 4   the sum of the selected terms, L = their number, cond = sum |term|   (loss_total_case 1e-6)
+    "mano_v": (1.3e-6, 5e-5),          # 3.21e-07 x 4   verts / jtr / verts_cam, L = 16 joints' transforms  (mano_*_case 5e-6 absolute on ~0.1: TAIL_LEGACY)
+    "mano_j": (2.3e-8, 2e-5),          # 5.55e-09 x 4   joints_rel / verts_rel / root, L = 778              (mano_joints_case 2e-6 absolute)
+    "mano_g": (2.9e-7, 3e-4),          # 7.08e-08 x 4   gpose / gbeta, L = 778                              (mano_*_case 3e-4 of the largest gradient)
+    "mano_gv": (9.2e-8, 2e-4),         # 2.29e-08 x 4   gverts of the regression, L = 22                    (mano_joints_case 2e-4 absolute)
+    "lbs_v": (7.1e-7, 2e-5),           # 1.75e-07 x 4   verts / posed joints, L = J                         (lbs_case 2e-6 max(1, max|ref| / 0.1))
+    "lbs_g": (1.4e-7, 2e-4),           # 3.36e-08 x 4   gtheta / gbeta / the scratch, L = V                 (lbs_case 2e-4)
+}
+TAIL_CONTRACT_KINDS = tuple(TAIL_CONTRACT_C)
+LAYER_CONTRACT_C.update(TAIL_CONTRACT_C)
+_CANARY[torch.int64] = -1234567890123
+_POISON[torch.int64] = 0x7FFFFFFFFFFFFFF0
+TAIL_LAUNCHED = set()                 # kernels the emulator launched under the tail cases (the coverage test reads it)
+
+
+def _tail_drain(lib, device):
+    """What the emulator launched since the last look (None on a GPU: the product library keeps no log)."""
+    if device != "cpu":
+        return None
+    names = [k.replace(" ", "") for k in launch_log(lib)]
+    TAIL_LAUNCHED.update(names)
+    return names
+
+
+def _tail_refuses(entry, lib, device, call, guards, what):
+    """HIFIHR_EINVAL, every output and guard untouched, nothing launched."""
+    _tail_drain(lib, device)
+    _refuses(entry, call, guards, f"{entry}: {what}")
+    left = _tail_drain(lib, device)
+    assert not left, f"{entry}: {what}: refused but launched {left}"
+
+
+def _raw(lib, name, *args):
+    """The C entry itself (the wrappers of hifihr_amd._lib derive sizes from tensor shapes; refused sizes need them spelled out)."""
+    lib.check(getattr(lib.c, name)(*args), name)
+
+
+def _vp(t):
+    import ctypes
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def _tail_ratio(entry, err, bound):
+    _layer_log(entry, True, (err / bound) if bound > 0 else (0.0 if err == 0 else float("inf")))
+
+
+# ---- Procrustes (csrc/eval.hip) ------------------------------------------------------------------------------------------------------
+# float64 inside, fp32 out: aligned within 2^-23 max|ref aligned| of the sample (twice the storage rounding), the per-point distances
+# | aligned_n - gt_n | within the same (a distance moves by at most sqrt(3) x the largest component error, sqrt(3) 2^-24 < 2^-23), err_sum
+# within 2^-23 ref + floor.  Floor: 4 x the largest difference, over the emulator list, between two float64 evaluations of the reference
+# (numpy svd of M against the eigen route of M^T M completed by cross products; tools/layer_contract_c.py prints both figures): 7.28e-12,
+# met on points of 1e3 units -- and, since such a difference grows with the size of the data, never more than 4 x the largest difference
+# relative to N max|gt| (2.52e-16) times the sample's own N max|gt|: 1e-15 of the summed magnitudes for a hand in metres.
+PROCRUSTES_FLOOR = 3.0e-11            # 7.28e-12 x 4
+PROCRUSTES_FLOOR_REL = 1.1e-15        # 2.52e-16 x 4
+PROCRUSTES_UNIQUE = 1e-12             # smallest / largest singular value of the reference below which R is not unique (include/hifihr.h)
+PROCRUSTES_FAMILIES = ("generic", "similar", "reflect", "gt_planar", "gt_planar_fp32", "gt_thin_1e-2", "gt_thin_1e-4", "gt_thin_1e-6",
+                       "gt_thin_1e-8", "gt_line", "gt_point", "pred_planar", "pred_line", "pred_point", "both_planar", "both_line_planar",
+                       "both_point", "offset100", "extent1e-3", "extent1e3")
+
+
+def procrustes_contract_expect(B, N):
+    return B > 0 and N > 0
+
+
+def procrustes_contract_inputs(family, B, N, seed):
+    """(pred, gt) fp32 [B, N, 3]; points of 0.05 units (a hand in metres) unless the family says otherwise."""
+    rng = np.random.default_rng(seed)
+    ext = 0.05
+    generic = lambda: rng.normal(0, ext, (B, N, 3))
+    line = lambda: rng.integers(-50, 51, (B, N, 1)) / 256.0 * (np.array([1.0, 2.0, -1.0]) / 8)        # exact in fp32: exactly collinear
+    point = lambda: np.broadcast_to(np.array([0.1, -0.2, 0.6]), (B, N, 3)).copy()
+
+    def planar(t=0.0):
+        x = generic()
+        x[..., 2] = t * rng.normal(0, ext, (B, N))
+        return x
+    gt, pred = generic(), generic() + rng.normal(0, 0.1, (B, 1, 3))
+    if family in ("similar", "reflect"):
+        q = np.stack([np.linalg.qr(rng.normal(size=(3, 3)))[0] for _ in range(B)])
+        for b in range(B):
+            if (np.linalg.det(q[b]) < 0) != (family == "reflect"):
+                q[b, :, 0] *= -1
+        pred = 1.7 * gt @ q.transpose(0, 2, 1) + rng.normal(0, 0.1, (B, 1, 3))
+    elif family == "gt_planar":
+        gt = planar()
+    elif family == "gt_planar_fp32":                                     # one depth, stored in fp32: planar to an ulp
+        z = np.float32(0.6)
+        gt[..., 2] = np.stack([np.nextafter(z, np.float32(-1)), z, np.nextafter(z, np.float32(2))]).astype(np.float64)[rng.integers(0, 3, (B, N))]
+    elif family.startswith("gt_thin_"):
+        gt = planar(float(family[8:]))
+    elif family == "gt_line":
+        gt = line()
+    elif family == "gt_point":
+        gt = point()
+    elif family == "pred_planar":
+        pred = planar() + 0.3
+    elif family == "pred_line":
+        pred = line() + 0.25
+    elif family == "pred_point":
+        pred = point()
+    elif family == "both_planar":
+        gt, pred = planar(), 2.0 * planar() + 0.3
+    elif family == "both_line_planar":
+        gt, pred = line(), planar()
+    elif family == "both_point":
+        gt, pred = point(), point() * 0.5
+    elif family == "offset100":
+        gt, pred = gt + 100.0, pred + 100.0
+    elif family.startswith("extent"):
+        gt, pred = gt * float(family[6:]) / ext, pred * float(family[6:]) / ext
+    else:
+        assert family == "generic", family
+    return torch.from_numpy(pred.astype(np.float32)), torch.from_numpy(gt.astype(np.float32))
+
+
+def _polar_by_eigen(M):
+    """The orthogonal polar factor and the singular values of a 3x3 M by the eigen route: V from M^T M, the two leading left vectors from
+    M V, the missing direction(s) completed by cross products (float64 numpy; the second evaluation behind PROCRUSTES_FLOOR)."""
+    lam, V = np.linalg.eigh(M.T @ M)
+    V = V[:, ::-1]
+    W = M @ V
+    w = np.linalg.norm(W, axis=0)
+    if not w[0] > 0:
+        return np.eye(3), w
+    u1 = W[:, 0] / w[0]
+    if w[1] > 1e-14 * w[0]:
+        u2 = W[:, 1] - (W[:, 1] @ u1) * u1
+    else:
+        u2 = np.eye(3)[int(np.abs(u1).argmin())]
+        u2 = u2 - (u2 @ u1) * u1
+    u2 = u2 / np.linalg.norm(u2)
+    u3 = np.cross(u1, u2)
+    if w[2] > 1e-14 * w[0] and w[1] > 1e-14 * w[0]:
+        u3 = u3 if W[:, 2] @ u3 >= 0 else -u3
+    return np.stack([u1, u2, u3], 1) @ V.T, w
+
+
+def procrustes_contract_ref(pred, gt, route="svd", drop_point=None):
+    """align_w_scale (reference utils/train_utils.py:267-290 around scipy.linalg.orthogonal_procrustes) restated in float64 numpy.
+    -> aligned [B, N, 3], dist [B, N], err_sum [B], unique [B] (R is determined: the smallest singular value of M above 1e-12 of the
+    largest).  drop_point: err_sum without that point's distance (the detection check)."""
+    P, G = pred.double().numpy(), gt.double().numpy()
+    aligned, unique = np.empty_like(P), np.empty(P.shape[0], bool)
+    for b in range(P.shape[0]):
+        t1, t2 = G[b].mean(0), P[b].mean(0)
+        A, Bm = G[b] - t1, P[b] - t2
+        s1 = np.linalg.norm(A) + 1e-8
+        A = A / s1
+        s2 = np.linalg.norm(Bm) + 1e-8
+        Bm = Bm / s2
+        M = A.T @ Bm                                                    # orthogonal_procrustes(A, Bm): u w vt = svd((Bm^T A)^T), R = u vt
+        if route == "svd":
+            u, w, vt = np.linalg.svd(M)
+            R = u @ vt
+        else:
+            R, w = _polar_by_eigen(M)
+        aligned[b] = (Bm @ R.T) * w.sum() * s1 + t1
+        unique[b] = bool(w.max() > 0 and w.min() > PROCRUSTES_UNIQUE * w.max())
+    dist = np.linalg.norm(aligned - G, axis=2)
+    keep = np.ones(P.shape[1], bool)
+    if drop_point is not None:
+        keep[drop_point] = False
+    return {"aligned": aligned, "dist": dist, "err_sum": dist[:, keep].sum(1), "unique": unique}
+
+
+def procrustes_err_bound(ref_err, N, gt_max):
+    return 2.0 ** -23 * float(ref_err) + min(PROCRUSTES_FLOOR, PROCRUSTES_FLOOR_REL * N * float(gt_max))
+
+
+def procrustes_err_passes(got, ref_err, N, gt_max):
+    return all(abs(float(g) - float(r)) <= procrustes_err_bound(r, N, m) for g, r, m in zip(got, ref_err, gt_max))
+
+
+def procrustes_contract_case(lib, device, B, N, family, seed=0):
+    from hifihr_amd._lib import _fp
+    e, what = "procrustes_error", f"procrustes {(B, N, family)}"
+    Bs, Ns = max(B, 1), max(N, 1)
+    pred, gt = procrustes_contract_inputs(family, Bs, Ns, seed)
+    G = Guards(device)
+    p, g, al, err = G.inp(pred), G.inp(gt), G.out(Bs, Ns, 3), G.out(Bs)
+    if not procrustes_contract_expect(B, N):
+        _tail_refuses(e, lib, device, lambda: _raw(lib, "hifihr_procrustes_error", _fp(p), _fp(g), B, N, _fp(al), _fp(err), None), G, what)
+        return False
+    for k, args in enumerate(((None, g, err), (p, None, err), (p, g, None))):
+        _tail_refuses(e, lib, device, lambda: _raw(lib, "hifihr_procrustes_error", _fp(args[0]), _fp(args[1]), B, N, _fp(al), _fp(args[2]), None),
+                      G, f"{what} NULL argument {k}")
+    ref = procrustes_contract_ref(pred, gt)
+    lib.procrustes_error(p, g, al, err)
+    G.intact(what)
+    got_al, got_err = al.cpu().double().numpy(), err.cpu().double().numpy()
+    assert np.isfinite(got_al).all() and np.isfinite(got_err).all(), f"{what}: not finite"
+    for b in range(B):
+        tol = 2.0 ** -23 * float(np.abs(ref["aligned"][b]).max())
+        if ref["unique"][b]:
+            d = float(np.abs(got_al[b] - ref["aligned"][b]).max())
+            _tail_ratio(e, d, tol)
+            assert d <= tol, f"{what} sample {b}: aligned off by {d:.3e}, bound {tol:.3e}"
+        d = float(np.abs(np.linalg.norm(got_al[b] - gt[b].double().numpy(), axis=1) - ref["dist"][b]).max())
+        _tail_ratio(e, d, tol)
+        assert d <= tol, f"{what} sample {b}: per-point distances off by {d:.3e}, bound {tol:.3e}"
+        d, bound = abs(got_err[b] - ref["err_sum"][b]), procrustes_err_bound(ref["err_sum"][b], N, gt[b].abs().max())
+        _tail_ratio(e, d, bound)
+        assert d <= bound, f"{what} sample {b}: err_sum {got_err[b]!r} vs {ref['err_sum'][b]!r}, bound {bound:.3e}"
+    first = (al.clone(), err.clone())
+    lib.procrustes_error(p, g, al, err)                                 # deterministic: the same bits again
+    _layer_equal(e, al, first[0], f"{what}: aligned, second call")
+    _layer_equal(e, err, first[1], f"{what}: err_sum, second call")
+    err2 = G.out(B)
+    lib.procrustes_error(p, g, None, err2)                              # aligned NULL: the same err_sum bits
+    _layer_equal(e, err2, first[1], f"{what}: err_sum without aligned")
+    G.intact(what)
+    _tail_drain(lib, device)
+    return True
+
+
+# ---- HO-3D crop + resize (csrc/augment.hip) ------------------------------------------------------------------------------------------
+HO3D_MAX_WINDOW = 800                 # HIFIHR_HO3D_MAX_WINDOW (include/hifihr.h)
+
+
+def ho3d_contract_frames(n, FH, FW):
+    """Frames and hand masks that make a dropped filter tap visible: a ramp, a one-pixel checker (every resampled value sits at 127.5, the
+    mask's rounding threshold) crossed with coarse blocks, and isolated bright / dark pixels -- not noise, whose outermost taps average out."""
+    y, x = np.mgrid[:FH, :FW]
+    frames = np.zeros((n, FH, FW, 4), np.uint8)
+    masks = np.zeros((n, FH, FW), np.uint8)
+    for k in range(n):
+        spots = ((x * 7 + y * 13 + k * 5) % 37 == 0)
+        frames[k, :, :, 0] = (x + 3 * k) * 255 // max(FW + 3 * k - 1, 1)
+        frames[k, :, :, 1] = (((x + y + k) & 1) ^ ((x // 9 + y // 5) & 1)) * 255
+        frames[k, :, :, 2] = np.where(spots, 255, (y * 40 // max(FH, 1)))
+        frames[k, :, :, 3] = 77                                          # the X byte must not reach an output
+        masks[k] = ((((x + y + k) & 1) ^ ((x // 7 + y // 11) & 1)) ^ spots) * 255
+    return frames, masks
+
+
+def ho3d_contract_expect(FH, FW, out_size, boxes, mode="ok"):
+    return mode == "ok" and len(boxes) > 0 and FH > 0 and FW > 0 and 0 < out_size <= 256
+
+
+def ho3d_contract_ref(frames, masks, idx, boxes, out_size, max_taps=None):
+    """Pillow's crop + resize (oracle/ho3d_oracle.py, no tap limit unless max_taps cuts the tables) per sample -> img u8 [B, S, S, 3],
+    mask u8 [B, S, S]; a box that is empty, inverted or above HO3D_MAX_WINDOW on an edge: zeros (include/hifihr.h)."""
+    from oracle import ho3d_oracle as ho
+    S = out_size
+    img, msk = np.zeros((len(boxes), S, S, 3), np.uint8), np.zeros((len(boxes), S, S), np.uint8)
+    for b, (x0, y0, x1, y1) in enumerate(boxes):
+        if x1 - x0 <= 0 or y1 - y0 <= 0 or max(x1 - x0, y1 - y0) > HO3D_MAX_WINDOW:
+            continue
+        img[b] = ho.pil_resize_u8(ho.pil_crop_u8(frames[idx[b], :, :, :3], (x0, y0, x1, y1)), S, S, "bilinear", max_taps)
+        msk[b] = ho.pil_resize_u8(ho.pil_crop_u8(masks[idx[b]], (x0, y0, x1, y1)), S, S, "bicubic", max_taps)
+    return img, msk
+
+
+def ho3d_taps_needed(boxes, out_size):
+    """The most taps any output element of the case takes, per filter: (bilinear, bicubic), counted on Pillow's own tables."""
+    from oracle import ho3d_oracle as ho
+    need = [0, 0]
+    for x0, y0, x1, y1 in boxes:
+        if min(x1 - x0, y1 - y0) <= 0 or max(x1 - x0, y1 - y0) > HO3D_MAX_WINDOW:
+            continue
+        for k, name in enumerate(("bilinear", "bicubic")):
+            for edge in {x1 - x0, y1 - y0} - {out_size}:
+                need[k] = max(need[k], int(ho.precompute_coeffs(edge, 0.0, float(edge), out_size, name)[1][:, 1].max()))
+    return tuple(need)
+
+
+def ho3d_pixels_match(got_img, got_mask, ref_img, ref_mask):
+    """The comparator (the detection check feeds it a reference made with cut tables): u8 / 255 and round(u8 / 255), bit for bit."""
+    want_i = torch.from_numpy(ref_img).permute(0, 3, 1, 2).float().div(255)
+    want_m = torch.round(torch.from_numpy(ref_mask).float().div(255)).unsqueeze(1)
+    return torch.equal(got_img.cpu(), want_i), torch.equal(got_mask.cpu(), want_m)
+
+
+def ho3d_contract_case(lib, device, FH, FW, out_size, boxes, mode="ok", seed=0):
+    """mode: "ok", or what is wrong with the call -- "short_ws", "no_<source>" (an output given without its source); B = len(boxes)."""
+    from oracle import ho3d_oracle as ho
+    e, what = "ho3d_batch", f"ho3d {(FH, FW, out_size, boxes, mode)}"
+    rng = np.random.default_rng(seed)
+    B, S, n = len(boxes), out_size, 3
+    Bs, Ss = max(B, 1), min(max(S, 1), 256)
+    frames, masks = ho3d_contract_frames(n, max(FH, 1), max(FW, 1))
+    idx = [(2 * b + 1) % n for b in range(Bs)]                             # batch order != cache order
+    bx = np.asarray(list(boxes) if B else [(0, 0, 4, 4)], np.int32).reshape(Bs, 4)
+    center = rng.uniform(50, 400, (Bs, 2)).astype(np.float32)
+    scale = rng.uniform(0.3, 5.0, Bs).astype(np.float32)
+    packed = np.concatenate([np.asarray(idx, np.int32), bx.reshape(-1), np.concatenate([center, scale[:, None]], 1).reshape(-1).view(np.int32)])
+    Ks = (np.tile(np.array([[600.0, 0, 320], [0, 610.0, 240], [0, 0, 1]], np.float32), (n, 1, 1)) + rng.normal(0, 1, (n, 3, 3))).astype(np.float32)
+    uv, xyz = rng.uniform(0, 640, (n, 21, 2)).astype(np.float32), rng.normal(size=(n, 21, 3)).astype(np.float32)
+    G = Guards(device)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+    fr = G.inp(t(frames).view(torch.int32).reshape(n, max(FH, 1), max(FW, 1)))
+    mk, Kd, uvd, xyzd, pk = G.inp(t(masks)), G.inp(t(Ks)), G.inp(t(uv)), G.inp(t(xyz)), G.inp(t(packed))
+    nws = lib.ho3d_workspace_bytes(Bs, Ss)
+    assert nws > 0 and nws % 4 == 0, what
+    assert lib.ho3d_workspace_bytes(B, S) == (nws if B > 0 and 0 < S <= 256 else 0), f"{what}: hifihr_ho3d_workspace_bytes"
+    ws = G.out(nws // 4, dtype=torch.int32)
+    ws_guard = G.outs.pop()                                                  # scratch: "any contents", only its surroundings are watched
+    out = lambda: {"img_crop": G.out(Bs, 3, Ss, Ss), "hand_mask_crop": G.out(Bs, 1, Ss, Ss), "K_crop": G.out(Bs, 3, 3), "uv21_crop": G.out(Bs, 21, 2),
+                   "xyz21": G.out(Bs, 21, 3)}
+    o = out()
+    names = ("img_crop", "hand_mask_crop", "K_crop", "uv21_crop", "xyz21")
+
+    def call(o, src=(fr, mk, Kd, uvd, xyzd), ws_bytes=nws, ws_t=ws, packed_t=pk):
+        from hifihr_amd._lib import _fp, _ip
+        import ctypes
+        _raw(lib, "hifihr_ho3d_batch", _vp(src[0]), _vp(src[1]), _fp(src[2]), _fp(src[3]), _fp(src[4]), FH, FW, _ip(packed_t), B, S, _vp(ws_t),
+             ctypes.c_size_t(ws_bytes), *[_fp(o.get(k)) for k in names], None)
+    if not ho3d_contract_expect(FH, FW, S, boxes, mode):
+        G.outs.append(ws_guard)                                               # a refused call leaves the scratch alone too
+        if mode == "short_ws":
+            _tail_refuses(e, lib, device, lambda: call(o, ws_bytes=nws - 4), G, what)
+        elif mode.startswith("no_"):
+            k = names.index(mode[3:])
+            _tail_refuses(e, lib, device, lambda: call(o, src=tuple(None if i == k else s for i, s in enumerate((fr, mk, Kd, uvd, xyzd)))), G, what)
+        elif mode == "no packed":
+            _tail_refuses(e, lib, device, lambda: call(o, packed_t=None), G, what)
+        elif mode == "no ws":
+            _tail_refuses(e, lib, device, lambda: call(o, ws_t=None), G, what)
+        else:
+            _tail_refuses(e, lib, device, lambda: call(o), G, what)
+        return False
+    ref_img, ref_mask = ho3d_contract_ref(frames, masks, idx, boxes, S)
+    call(o)
+    G.intact(what)
+    whole, lo, hi, canary = ws_guard
+    assert bool((whole[:lo] == canary).all()) and bool((whole[hi:] == canary).all()), f"{what}: wrote outside the workspace"
+    ok_i, ok_m = ho3d_pixels_match(o["img_crop"], o["hand_mask_crop"], ref_img, ref_mask)
+    _layer_log(e, True, 0.0)
+    assert ok_i, f"{what}: frame crop differs from Pillow in {int((o['img_crop'].cpu() != torch.from_numpy(ref_img).permute(0, 3, 1, 2).float().div(255)).sum())} values"
+    assert ok_m, f"{what}: mask crop differs from Pillow in {int((o['hand_mask_crop'].cpu()[:, 0] != torch.round(torch.from_numpy(ref_mask).float().div(255))).sum())} pixels"
+    for b in range(B):                                                       # the rules of ho3d_batch_case
+        uvc, Kc = ho.crop_targets(uv[idx[b]], Ks[idx[b]], {"crop_center": center[b], "scale": scale[b]}, S)
+        assert torch.equal(o["uv21_crop"][b].cpu(), torch.from_numpy(uvc)), f"{what}: uv21_crop {b}"
+        np.testing.assert_allclose(o["K_crop"][b].cpu().numpy(), Kc, rtol=1e-6, atol=1e-4)
+        assert torch.equal(o["xyz21"][b].cpu(), torch.from_numpy(xyz[idx[b]])), f"{what}: xyz21 {b}"
+    first = {k: v.clone() for k, v in o.items()}
+    call(o)                                                                  # again, on the scratch the first call left
+    for k in names:
+        _layer_equal(e, o[k], first[k], f"{what}: {k}, second call")
+    for k in names:                                                          # each output NULL: the others are the same bits
+        o2 = out()
+        o2[k] = None
+        call(o2)
+        for k2 in names:
+            if k2 != k:
+                _layer_equal(e, o2[k2], first[k2], f"{what}: {k2} with {k} NULL")
+    G.intact(what)
+    _tail_drain(lib, device)
+    return True
+
+
+# ---- FreiHAND warp and batch assembly (csrc/augment.hip) -----------------------------------------------------------------------------
+# name -> the six AFFINE coefficients (a b c; d e f) of Image.transform, output pixel -> input pixel, for an H x W image
+FREIHAND_MAPS = {
+    "identity": lambda H, W: (1.0, 0.0, 0.0, 0.0, 1.0, 0.0),
+    "rotation": lambda H, W: (np.cos(0.5), -np.sin(0.5), W / 2 - np.cos(0.5) * W / 2 + np.sin(0.5) * H / 2,
+                              np.sin(0.5), np.cos(0.5), H / 2 - np.sin(0.5) * W / 2 - np.cos(0.5) * H / 2),
+    "flip": lambda H, W: (-1.0, 0.0, float(W), 0.0, 1.0, 0.0),
+    "half": lambda H, W: (2.0, 0.0, 0.0, 0.0, 2.0, 0.0),                       # a 0.5x scale of the picture
+    "triple": lambda H, W: (1 / 3, 0.0, 0.0, 0.0, 1 / 3, 0.0),                 # a 3x scale
+    "away": lambda H, W: (1.0, 0.0, W + 5.0, 0.0, 1.0, 0.0),                   # a shift that leaves the image
+    "subpixel": lambda H, W: (1.0, 0.0, -0.5, 0.0, 1.0, 0.0),
+}
+
+
+def pil_affine_fixed(coefs):
+    """Pillow's six 16.16 integers of (a, b, c, d, e, f) (libImaging/Geometry.c affine_fixed; hifihr_amd.data.pil_affine_fixed_terms)."""
+    import math
+    a, b, c, d, e, f = (float(v) for v in coefs)
+    fix = lambda v: int(math.floor(v * 65536.0 + 0.5))
+    return [fix(a), fix(b), fix(c + a * 0.5 + b * 0.5), fix(d), fix(e), fix(f + d * 0.5 + e * 0.5)]
+
+
+def pil_affine_nearest_ref(src, idx, fixed):
+    """Pillow's fixed-point nearest-neighbour walk from the six integers, restated in numpy: src [n, H, W(, C)] -> [B, H, W(, C)], zero fill."""
+    H, W = src.shape[1:3]
+    x, y = np.arange(W, dtype=np.int64)[None, :], np.arange(H, dtype=np.int64)[:, None]
+    out = np.zeros((len(idx),) + src.shape[1:], src.dtype)
+    for b, c in enumerate(np.asarray(fixed, np.int64)):
+        xs, ys = c[2] + x * c[0] + y * c[1], c[5] + x * c[3] + y * c[4]
+        assert max(int(np.abs(xs).max()), int(np.abs(ys).max())) < 2 ** 31, "the walk leaves 32-bit integers"
+        xin, yin = xs >> 16, ys >> 16
+        inside = (xin >= 0) & (xin < W) & (yin >= 0) & (yin < H)
+        px = src[idx[b], yin.clip(0, H - 1), xin.clip(0, W - 1)]
+        out[b] = np.where(inside.reshape(inside.shape + (1,) * (px.ndim - 2)), px, 0)
+    return out
+
+
+def freihand_contract_case(lib, device, H, W, J, V, seed=0):
+    """hifihr_freihand_augment, _batch and _batch_step on every map of FREIHAND_MAPS at once (B = 7 samples gathered from a cache of 3)."""
+    from hifihr_amd._lib import _fp, _ip
+    what = f"freihand {(H, W, J, V)}"
+    rng = np.random.default_rng(seed)
+    n, B = 3, len(FREIHAND_MAPS)
+    rgbx = rng.integers(0, 256, (n, H, W, 4), dtype=np.uint8)
+    mk = rng.choice(np.array([0, 127, 128, 255], np.uint8), (n, H, W))                 # both sides of round(u8 / 255)
+    idx = rng.integers(0, n, B).astype(np.int32)
+    fixed = np.asarray([pil_affine_fixed(m(H, W)) for m in FREIHAND_MAPS.values()], np.int32)
+    Ks = (np.tile(np.array([[400.0, 0, 112], [0, 410.0, 108], [0, 0, 1]], np.float32), (n, 1, 1)) + rng.normal(0, 1, (n, 3, 3))).astype(np.float32)
+    joints = (rng.normal(0, 0.05, (n, J, 3)) + np.array([0, 0, 0.6])).astype(np.float32)
+    verts = (rng.normal(0, 0.05, (n, V, 3)) + np.array([0, 0, 0.6])).astype(np.float32)
+    scales = rng.random(n).astype(np.float32)
+    ang = rng.uniform(-np.pi, np.pi, B)
+    rmat = np.zeros((B, 3, 3), np.float32)
+    rmat[:, 0, 0] = np.cos(ang); rmat[:, 0, 1] = -np.sin(ang); rmat[:, 1, 0] = np.sin(ang); rmat[:, 1, 1] = np.cos(ang); rmat[:, 2, 2] = 1
+    post = (np.tile(np.eye(3, dtype=np.float32), (B, 1, 1)) + rng.normal(0, 0.1, (B, 3, 3))).astype(np.float32)
+    post[:, 2] = (0, 0, 1)
+    packed = np.concatenate([idx, fixed.reshape(-1), post.reshape(-1).view(np.int32), rmat.reshape(-1).view(np.int32)])
+    # references: pixels bit for bit; the small tensors in float64 under freihand_batch_case's tolerances
+    want_img = torch.from_numpy(pil_affine_nearest_ref(rgbx[..., :3], idx, fixed)).permute(0, 3, 1, 2).float().div(255)
+    want_m1 = torch.round(torch.from_numpy(pil_affine_nearest_ref(mk, idx, fixed)).float().div(255))
+    want_mask = want_m1.unsqueeze(1).repeat(1, 3, 1, 1)
+    il = idx.astype(np.int64)
+    wK = post.astype(np.float64) @ Ks[il].astype(np.float64)
+    rot = lambda pts: pts[il].astype(np.float64) @ rmat.astype(np.float64).transpose(0, 2, 1)
+    wj, wv = rot(joints), rot(verts)
+    uvw = wj @ wK.transpose(0, 2, 1)
+    wj2d = uvw[..., :2] / uvw[..., 2:3]
+    close = lambda a, b, tol=2e-6: a.numel() == 0 or float((a.cpu().double() - torch.from_numpy(np.ascontiguousarray(b))).abs().max()) <= tol * max(1.0, float(np.abs(b).max()))
+    G = Guards(device)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+    cache = G.inp(t(rgbx).view(torch.int32).reshape(n, H, W))
+    mkd, Kd, jd, vd, sd, pk, idxd, fxd = (G.inp(t(a)) for a in (mk, Ks, joints, verts, scales, packed, idx, fixed))
+
+    # ---- hifihr_freihand_augment ----
+    e = "freihand_augment"
+    aug = lambda img, m, ix, cf, b, h, w, oi, om: _raw(lib, "hifihr_freihand_augment", _vp(img), _vp(m), _ip(ix), _ip(cf), b, h, w, _fp(oi), _fp(om), None)
+    oi, om = G.out(B, 3, H, W), G.out(B, 3, H, W)
+    aug(cache, mkd, idxd, fxd, B, H, W, oi, om)
+    _layer_equal(e, oi, want_img, f"{what}: {e} image")
+    _layer_equal(e, om, want_mask, f"{what}: {e} mask")
+    aug(cache, mkd, idxd, fxd, B, H, W, oi, om)
+    _layer_equal(e, oi, want_img, f"{what}: {e} image, second call")
+    oi2, om2 = G.out(B, 3, H, W, offset_floats=1), G.out(B, 3, H, W, offset_floats=1)          # off 16-byte alignment: the one-pixel kernel
+    aug(cache, mkd, idxd, fxd, B, H, W, oi2, om2)
+    _layer_equal(e, oi2, want_img, f"{what}: {e} image, unaligned")
+    _layer_equal(e, om2, want_mask, f"{what}: {e} mask, unaligned")
+    oi3, om3 = G.out(B, 3, H, W), G.out(B, 3, H, W)
+    aug(cache, None, idxd, fxd, B, H, W, oi3, None)                                            # either output NULL, with its source
+    aug(None, mkd, idxd, fxd, B, H, W, None, om3)
+    _layer_equal(e, oi3, want_img, f"{what}: {e} image alone")
+    _layer_equal(e, om3, want_mask, f"{what}: {e} mask alone")
+    G.intact(what)
+    for why, call in (("no output", lambda: aug(cache, mkd, idxd, fxd, B, H, W, None, None)),
+                      ("image without its source", lambda: aug(None, mkd, idxd, fxd, B, H, W, oi, om)),
+                      ("mask without its source", lambda: aug(cache, None, idxd, fxd, B, H, W, oi, om)),
+                      ("idx NULL", lambda: aug(cache, mkd, None, fxd, B, H, W, oi, om)), ("coef NULL", lambda: aug(cache, mkd, idxd, None, B, H, W, oi, om)),
+                      ("B = 0", lambda: aug(cache, mkd, idxd, fxd, 0, H, W, oi, om)), ("H = 0", lambda: aug(cache, mkd, idxd, fxd, B, 0, W, oi, om)),
+                      ("H W = 2^24", lambda: aug(cache, mkd, idxd, fxd, B, 4096, 4096, oi, om))):
+        _tail_refuses(e, lib, device, call, G, f"{what}: {why}")
+
+    # ---- hifihr_freihand_batch ----
+    e = "freihand_batch"
+    names = ("imgs", "masks", "segms_gt", "Ks", "Ps", "joints", "verts", "j2d_gt", "scales", "idxs")
+    mk_out = lambda: {"imgs": G.out(B, 3, H, W), "masks": G.out(B, 3, H, W), "segms_gt": G.out(B, H, W, dtype=torch.int64), "Ks": G.out(B, 3, 3),
+                      "Ps": G.out(B, 3, 4), "joints": G.out(B, J, 3), "verts": G.out(B, V, 3), "j2d_gt": G.out(B, J, 2), "scales": G.out(B),
+                      "idxs": G.out(B, dtype=torch.int64)}
+
+    def batch(o, src=None, b=B, h=H, w=W, j=J, v=V, step=None, sx=None):
+        s_ = dict(img=cache, mask=mkd, Ks=Kd, joints=jd, verts=vd, scales=sd, packed=pk)
+        s_.update(src or {})
+        head = [_vp(s_["img"]), _vp(s_["mask"]), _fp(s_["Ks"]), _fp(s_["joints"]), _fp(s_["verts"]), _fp(s_["scales"]), j, v, _ip(s_["packed"]), b, h, w]
+        outs = [_fp(o.get("imgs")), _fp(o.get("masks")), _vp(o.get("segms_gt"))] + [_fp(o.get(k)) for k in names[3:9]] + [_vp(o.get("idxs"))]
+        if step is None:
+            _raw(lib, "hifihr_freihand_batch", *head, *outs, None)
+        else:
+            sx = sx or {}
+            _raw(lib, "hifihr_freihand_batch_step", *head, *outs, int(step[0]), float(step[1]),
+                 *[_fp(sx.get(k)) for k in ("root_xyz", "joints_rel", "verts_rel", "cam_ndc")], None)
+
+    def check_batch(o, tag):
+        for k, want in (("imgs", want_img), ("masks", want_mask), ("segms_gt", want_m1.long()), ("idxs", torch.from_numpy(il))):
+            if o.get(k) is not None:
+                _layer_equal(e, o[k], want, f"{what}: {tag} {k}")
+        if o.get("scales") is not None:
+            _layer_equal(e, o["scales"], torch.from_numpy(scales[il]), f"{what}: {tag} scales")
+        assert o.get("Ks") is None or close(o["Ks"], wK), f"{what}: {tag} Ks"
+        assert o.get("joints") is None or close(o["joints"], wj), f"{what}: {tag} joints"
+        assert o.get("verts") is None or close(o["verts"], wv), f"{what}: {tag} verts"
+        assert o.get("j2d_gt") is None or close(o["j2d_gt"], wj2d, 1e-5), f"{what}: {tag} j2d_gt"
+        if o.get("Ps") is not None:
+            assert close(o["Ps"][:, :, :3], wK) and float(o["Ps"][:, :, 3].abs().max()) == 0.0, f"{what}: {tag} Ps"
+            assert o.get("Ks") is None or torch.equal(o["Ps"][:, :, :3], o["Ks"]), f"{what}: {tag} Ps != [Ks | 0]"
+    o = mk_out()
+    batch(o)
+    check_batch(o, e)
+    G.intact(what)
+    first = {k: v.clone() for k, v in o.items()}
+    batch(o)
+    for k in names:
+        _layer_equal(e, o[k], first[k], f"{what}: {e} {k}, second call")
+    for k in names:                                                      # each output NULL: the others are the same bits
+        o2 = mk_out()
+        o2[k] = None
+        batch(o2)
+        for k2 in names:
+            if k2 != k:
+                _layer_equal(e, o2[k2], first[k2], f"{what}: {e} {k2} with {k} NULL")
+    G.intact(what)
+    refused = [("img NULL", dict(src={"img": None})), ("mask NULL", dict(src={"mask": None})), ("Ks NULL", dict(src={"Ks": None})),
+               ("scales NULL", dict(src={"scales": None})), ("packed NULL", dict(src={"packed": None})), ("B = 0", dict(b=0)), ("W = 0", dict(w=0)),
+               ("J < 0", dict(j=-1)), ("V < 0", dict(v=-1)), ("H W = 2^24", dict(h=4096, w=4096))]
+    refused += [("joints NULL", dict(src={"joints": None}))] if J > 0 else []
+    refused += [("verts NULL", dict(src={"verts": None}))] if V > 0 else []
+    for why, kw in refused:
+        _tail_refuses(e, lib, device, lambda: batch(o, **kw), G, f"{what}: {why}")
+
+    # ---- hifihr_freihand_batch_step ----
+    e = "freihand_batch_step"
+    xnames = ("root_xyz", "joints_rel", "verts_rel", "cam_ndc")
+    mk_x = lambda: {"root_xyz": G.out(B, 1, 3), "joints_rel": G.out(B, J, 3), "verts_rel": G.out(B, V, 3), "cam_ndc": G.out(B, 4)}
+    size = float(max(H, W))
+    for root_id in sorted({-1, 0, J - 1} & set(range(-1, J))):
+        o3, x = mk_out(), mk_x()
+        batch(o3, step=(root_id, size), sx=x)
+        for k in names:
+            _layer_equal(e, o3[k], first[k], f"{what}: {e} root {root_id} {k}")
+        root = first["joints"][:, root_id:root_id + 1] if root_id >= 0 else torch.zeros(B, 1, 3, device=device)
+        _layer_equal(e, x["root_xyz"], root, f"{what}: {e} root {root_id} root_xyz")
+        _layer_equal(e, x["joints_rel"], first["joints"] - root, f"{what}: {e} root {root_id} joints_rel")
+        _layer_equal(e, x["verts_rel"], first["verts"] - root, f"{what}: {e} root {root_id} verts_rel")
+        K = first["Ks"].cpu().double()
+        cam = torch.stack([-2 * K[:, 0, 0] / size, -2 * K[:, 1, 1] / size, 1 - 2 * K[:, 0, 2] / size, 1 - 2 * K[:, 1, 2] / size], 1)
+        assert close(x["cam_ndc"], cam.numpy(), 1e-6), f"{what}: {e} cam_ndc"
+        firstx = {k: v.clone() for k, v in x.items()}
+        for k in xnames:
+            x2 = mk_x()
+            x2[k] = None
+            batch(mk_out(), step=(root_id, size), sx=x2)
+            for k2 in xnames:
+                if k2 != k:
+                    _layer_equal(e, x2[k2], firstx[k2], f"{what}: {e} {k2} with {k} NULL")
+    G.intact(what)
+    x = mk_x()
+    for why, kw in (("root_id = J", dict(step=(J, size))), ("image_size 0", dict(step=(-1, 0.0))), ("image_size < 0", dict(step=(-1, -4.0))),
+                    ("image_size NaN", dict(step=(-1, float("nan")))), ("H W = 2^24", dict(step=(-1, size), h=4096, w=4096)), ("B = 0", dict(step=(-1, size), b=0)),
+                    ("mask NULL", dict(step=(-1, size), src={"mask": None}))):
+        _tail_refuses(e, lib, device, lambda: batch(o, sx=x, **kw), G, f"{what}: {why}")
+    _tail_drain(lib, device)
+    return True
+
+
+# ---- Adam (csrc/adam.hip) ------------------------------------------------------------------------------------------------------------
+ADAM_BETAS, ADAM_EPS, ADAM_LR = (0.9, 0.999), 1e-8, 1e-3
+
+
+def adam_contract_ref(p, g, m, v, step, wd, grad_scale, dt=torch.float64, drop=None):
+    """One torch.optim.Adam step (coupled weight decay) in `dt`, the scalars of the update in float64 as the launcher forms them.
+    drop: that element's gradient is left out (the detection check).  -> (p, m, v)"""
+    b1, b2 = ADAM_BETAS
+    p, g, m, v = (t.to(dt) for t in (p, g, m, v))
+    f = lambda x: torch.tensor(x, dtype=torch.float32).to(dt)                 # the entry takes its scalars as fp32
+    gr = g * f(grad_scale) + f(wd) * p
+    if drop is not None:
+        gr[drop] = 0
+    m = f(b1) * m + (1 - f(b1)) * gr
+    v = f(b2) * v + (1 - f(b2)) * gr * gr
+    b1d, b2d, lrd = (float(torch.tensor(x, dtype=torch.float32)) for x in (b1, b2, ADAM_LR))
+    step_size, inv = lrd / (1 - b1d ** step), 1 / (1 - b2d ** step) ** 0.5
+    if dt == torch.float32:
+        step_size, inv = float(torch.tensor(step_size, dtype=dt)), float(torch.tensor(inv, dtype=dt))
+    p = p - step_size * (m / (v.sqrt() * inv + f(ADAM_EPS)))
+    return p, m, v
+
+
+def adam_passes(kind, got, ref):
+    """The comparator: layer_bound, and for the parameters never above adam_case's 2e-6 + 1e-5 |p| per element."""
+    d = (got.detach().cpu().double() - ref).abs()
+    if bool(torch.isnan(d).any()):
+        return False, float("nan"), 0.0
+    bound = torch.full_like(ref, layer_bound(kind, ref, 1))
+    if kind == "adam_p":
+        bound = torch.minimum(bound, 2e-6 + 1e-5 * ref.abs())
+    worst = int((d / bound.clamp_min(1e-300)).argmax()) if d.numel() else 0
+    return bool((d <= bound).all()), float(d.reshape(-1)[worst]) if d.numel() else 0.0, float(bound.reshape(-1)[worst]) if d.numel() else 0.0
+
+
+def _adam_close(entry, kind, got, ref, what):
+    ok, err, bound = adam_passes(kind, got, ref)
+    _tail_ratio(entry, err, bound)
+    assert ok, f"{what}: {kind} err {err:.3e} vs bound {bound:.3e}"
+
+
+def adam_contract_inputs(n, seed, steps=3):
+    gen = torch.Generator().manual_seed(seed)
+    return {"p": torch.randn(n, generator=gen), "g": [torch.randn(n, generator=gen) for _ in range(steps)],
+            "m": torch.randn(n, generator=gen) * 0.1, "v": torch.rand(n, generator=gen) * 0.01}
+
+
+def adam_contract_case(lib, device, n, wd, grad_scale, seed=0):
+    """hifihr_adam_step, _dyn and _counted on one trajectory: steps 1 - 3 from zero moments, a step at t = 1000 from given moments, an all-zero
+    gradient on zero moments; every step against the float64 update continued from the entry's own previous fp32 state."""
+    import struct
+    from hifihr_amd._lib import _fp
+    what = f"adam {(n, wd, grad_scale)}"
+    b1, b2 = ADAM_BETAS
+    inp = adam_contract_inputs(n, seed)
+    G = Guards(device)
+    zero = torch.zeros(n)
+
+    def buffers(p, m, v, off=0):
+        out = []
+        for t in (p, m, v):
+            b = G.out(n, offset_floats=off)
+            b.copy_(t)
+            out.append(b)
+        return out
+
+    def state_at(done_steps, off=0):
+        st = G.out(48, dtype=torch.uint8, offset_floats=off)
+        st.copy_(lib.adam_state_image(ADAM_LR, b1, b2, done_steps))
+        return st
+
+    def dyn_at(step):
+        b1d, b2d, lrd = (float(torch.tensor(x, dtype=torch.float32)) for x in (b1, b2, ADAM_LR))
+        return G.inp(torch.tensor([lrd / (1 - b1d ** step), 1.0 / (1 - b2d ** step) ** 0.5], dtype=torch.float32))
+
+    def run(entry, bufs, g, step, st=None, count=n):
+        p, m, v = bufs
+        if entry == "adam_step":
+            _raw(lib, "hifihr_adam_step", _fp(p), _fp(g), _fp(m), _fp(v), count, grad_scale, ADAM_LR, b1, b2, ADAM_EPS, wd, step, None)
+        elif entry == "adam_step_dyn":
+            dyn = dyn_at(step)                                           # (kept alive across the call)
+            _raw(lib, "hifihr_adam_step_dyn", _fp(p), _fp(g), _fp(m), _fp(v), count, grad_scale, b1, b2, ADAM_EPS, wd, _fp(dyn), None)
+        else:
+            _raw(lib, "hifihr_adam_step_counted", _fp(p), _fp(g), _fp(m), _fp(v), count, grad_scale, ADAM_EPS, wd, _vp(st), None)
+
+    def read_state(st):
+        return struct.unpack("<dddddii", bytes(st.cpu().numpy().tobytes()))
+
+    for entry in ("adam_step", "adam_step_dyn", "adam_step_counted"):
+        # steps 1 - 3 from zero moments
+        bufs, st = buffers(inp["p"], zero, zero), state_at(0)
+        for s in (1, 2, 3):
+            before = [b.cpu().clone() for b in bufs]
+            gd = G.inp(inp["g"][s - 1])
+            ref = adam_contract_ref(before[0], inp["g"][s - 1], before[1], before[2], s, wd, grad_scale)
+            run(entry, bufs, gd, s, st)
+            for kind, got, r in zip(("adam_p", "adam_m", "adam_v"), bufs, ref):
+                _adam_close(entry, kind, got, r, f"{what}: {entry} step {s}")
+            if s == 2:                                                  # deterministic: the same step from the same state, the same bits
+                again, st2 = buffers(*before), state_at(1)
+                run(entry, again, gd, s, st2)
+                for a, b_ in zip(again, bufs):
+                    _layer_equal(entry, a, b_, f"{what}: {entry} step 2 repeated")
+        if entry == "adam_step_counted":
+            lr_d, b1_d, b2_d, p1, p2, step_d, done_d = read_state(st)
+            assert (lr_d, b1_d, b2_d, step_d, done_d) == (ADAM_LR, b1, b2, 3, 0), f"{what}: state {(lr_d, b1_d, b2_d, step_d, done_d)}"
+            assert abs(p1 - b1 ** 3) <= 1e-14 and abs(p2 - b2 ** 3) <= 1e-14, f"{what}: running products"
+        # a step at t = 1000 from given moments
+        bufs, st = buffers(inp["p"], inp["m"], inp["v"]), state_at(999)
+        ref = adam_contract_ref(inp["p"], inp["g"][0], inp["m"], inp["v"], 1000, wd, grad_scale)
+        run(entry, bufs, G.inp(inp["g"][0]), 1000, st)
+        for kind, got, r in zip(("adam_p", "adam_m", "adam_v"), bufs, ref):
+            _adam_close(entry, kind, got, r, f"{what}: {entry} step 1000")
+        if entry == "adam_step_counted":
+            _, _, _, p1, p2, step_d, done_d = read_state(st)
+            assert (step_d, done_d) == (1000, 0) and abs(p1 - b1 ** 1000) <= 1e-14 and abs(p2 - b2 ** 1000) <= 1e-14, f"{what}: state after step 1000"
+        # an all-zero gradient on zero moments: 0 / (0 + eps) = 0
+        bufs, st = buffers(inp["p"], zero, zero), state_at(0)
+        run(entry, bufs, G.inp(zero), 1, st)
+        if wd == 0:
+            _layer_equal(entry, bufs[0], inp["p"], f"{what}: {entry} zero gradient, parameters")
+            assert float(bufs[1].abs().max()) == 0.0 and float(bufs[2].abs().max()) == 0.0, f"{what}: {entry} zero gradient, moments"
+        else:
+            ref = adam_contract_ref(inp["p"], zero, zero, zero, 1, wd, grad_scale)
+            for kind, got, r in zip(("adam_p", "adam_m", "adam_v"), bufs, ref):
+                _adam_close(entry, kind, got, r, f"{what}: {entry} zero gradient")
+        G.intact(what)
+        # n = 0: accepted, not a step -- nothing launched, nothing written, the counter stays
+        bufs, st, gd = buffers(inp["p"], inp["m"], inp["v"]), state_at(5), G.inp(inp["g"][0])
+        before, st_before = [b.clone() for b in bufs], st.clone()
+        _tail_drain(lib, device)
+        run(entry, bufs, gd, 6, st, count=0)
+        left = _tail_drain(lib, device)
+        assert not left, f"{what}: {entry} with n = 0 launched {left}"
+        assert all(torch.equal(a, b_) for a, b_ in zip(bufs, before)) and torch.equal(st, st_before), f"{what}: {entry} with n = 0 wrote"
+        _layer_log(entry, True, 0.0)
+        # refused: a NULL, a buffer one float off 16-byte alignment, the state off 8-byte alignment, step < 1
+        for k in range(4):
+            args = bufs[:1] + [gd] + bufs[1:]
+            args[k] = None
+            _tail_refuses(entry, lib, device, lambda: run(entry, (args[0], args[2], args[3]), args[1], 6, st), G, f"{what}: NULL buffer {k}")
+            off = buffers(inp["p"], inp["m"], inp["v"], off=1)
+            args = bufs[:1] + [gd] + bufs[1:]
+            args[k] = off[0] if k != 1 else G.inp(inp["g"][0], offset_floats=1)
+            _tail_refuses(entry, lib, device, lambda: run(entry, (args[0], args[2], args[3]), args[1], 6, st), G, f"{what}: buffer {k} off alignment")
+        if entry == "adam_step":
+            for bad in (0, -1):
+                _tail_refuses(entry, lib, device, lambda: run(entry, bufs, gd, bad), G, f"{what}: step {bad}")
+        elif entry == "adam_step_counted":
+            _tail_refuses(entry, lib, device, lambda: run(entry, bufs, gd, 6, None), G, f"{what}: state NULL")
+            st_off = state_at(5, off=4)
+            _tail_refuses(entry, lib, device, lambda: run(entry, bufs, gd, 6, st_off), G, f"{what}: state off 8-byte alignment")
+        else:
+            _tail_refuses(entry, lib, device, lambda: _raw(lib, "hifihr_adam_step_dyn", _fp(bufs[0]), _fp(gd), _fp(bufs[1]), _fp(bufs[2]), n, grad_scale,
+                                                           b1, b2, ADAM_EPS, wd, None, None), G, f"{what}: dyn NULL")
+    _tail_drain(lib, device)
+    return True
+
+
+# ---- bounds of the float families ------------------------------------------------------------------------------------------------------
+# kind -> the absolute tolerance the family's older case in this file gives a quantity `ref` of reduction length L (never exceeded)
+TAIL_LEGACY = {
+    "tex_fwd": lambda ref, L: 1e-5 * max(1.0, float(ref.abs().max())),                               # texture_pca_case
+    "tex_bwd": lambda ref, L: 2e-5 * float(ref.abs().max()) * max(1.0, (L / 4096) ** 0.5),           # texture_pca_case (L = n)
+    "geom_out": lambda ref, L: 2e-5 * float(ref.abs().max()) + 1e-7,                                 # geom_loss_case, per term
+    "geom_grad": lambda ref, L: 2e-5 * float(ref.abs().max()) + 1e-9,
+    "photo_out": lambda ref, L: 3e-5 * float(ref.abs().max()) + 1e-9,                                # photo_loss_case, per term
+    "photo_img": lambda ref, L: 1e-6,
+    "photo_grad": lambda ref, L: 2e-5 * float(ref.abs().max()) + 1e-12,
+    "joint_out": lambda ref, L: 2e-5 * max(1.0, float(ref.abs().max())),                             # joint_terms_case, per term
+    "joint_grad": lambda ref, L: 1e-5 * float(ref.abs().max()) + 1e-9,
+    "total": lambda ref, L: 1e-6 * max(1.0, float(ref.abs().max())),                                 # loss_total_case
+}
+
+
+def tail_bound(kind, ref, L, cond=0.0):
+    """layer_bound, never above the older case's tolerance for the same quantity; c cond on top (what a prefilled accumulator or a
+    cancellation inside the operation costs: layer_bound's docstring)."""
+    b = layer_bound(kind, ref, L)
+    if kind in TAIL_LEGACY and ref.numel():
+        b = min(b, TAIL_LEGACY[kind](ref, L))
+    return b + LAYER_CONTRACT_C[kind][0] * float(cond)
+
+
+def tail_passes(kind, got, ref, L, cond=0.0):
+    return layer_err(got, ref) <= tail_bound(kind, ref, L, cond)
+
+
+def _tail_close(entry, kind, got, ref, L, what, cond=0.0):
+    err, bound = layer_err(got, ref), tail_bound(kind, ref, L, cond)
+    _tail_ratio(entry, err, bound)
+    assert err <= bound, f"{what}: err {err:.3e} vs bound {bound:.3e} (kind {kind}, max|ref| {float(ref.abs().max()) if ref.numel() else 0:.3e}, L {L})"
+
+
+# ---- texture PCA (csrc/texpca.hip) -----------------------------------------------------------------------------------------------------
+def texpca_contract_expect(B, K, n):
+    return B > 0 and 1 <= K <= 32 and n >= 4 and n % 4 == 0
+
+
+def texpca_contract_inputs(B, K, n, seed):
+    gen = torch.Generator().manual_seed(seed)
+    return {"coef": torch.randn(B, K, generator=gen), "basis": torch.randn(K, n, generator=gen) * 0.1, "mean": torch.rand(n, generator=gen),
+            "g": torch.randn(B, n, generator=gen), "prefill": torch.randn(B, K, generator=gen)}
+
+
+def texpca_contract_ref(inp, with_mean, dt=torch.float64, drop_row=None):
+    """tex = mean + coef basis (L = K + 1), dcoef = g basis^T (L = n); drop_row: tex without that basis row."""
+    coef, basis, g = inp["coef"].to(dt), inp["basis"].to(dt), inp["g"].to(dt)
+    if drop_row is not None:
+        basis = basis.clone()
+        basis[drop_row] = 0
+    tex = coef @ basis + (inp["mean"].to(dt) if with_mean else 0.0)
+    return {"tex": ("tex_fwd", coef.shape[1] + 1, tex), "dcoef": ("tex_bwd", basis.shape[1], g @ inp["basis"].to(dt).t())}
+
+
+def texpca_contract_case(lib, device, B, K, n, with_mean=True, seed=0):
+    from hifihr_amd._lib import _fp
+    import ctypes
+    what = f"texpca {(B, K, n, with_mean)}"
+    Bs, Ks, ns = max(B, 1), min(max(K, 1), 33), max(n, 4)
+    inp = texpca_contract_inputs(Bs, Ks, ns, seed)
+    G = Guards(device)
+    coef, basis, mean, g = G.inp(inp["coef"]), G.inp(inp["basis"]), G.inp(inp["mean"]), G.inp(inp["g"])
+    tex, dcoef = G.out(Bs, ns), G.out(Bs, Ks)
+    fwd = lambda c=coef, bs=basis, m=mean, o=tex: _raw(lib, "hifihr_texture_pca_fwd", _fp(c), _fp(bs), _fp(m), B, K, ctypes.c_long(n), _fp(o), None)
+    bwd = lambda gg=g, bs=basis, o=dcoef: _raw(lib, "hifihr_texture_pca_bwd", _fp(gg), _fp(bs), B, K, ctypes.c_long(n), _fp(o), None)
+    if not texpca_contract_expect(B, K, n):
+        _tail_refuses("texture_pca_fwd", lib, device, fwd, G, what)
+        _tail_refuses("texture_pca_bwd", lib, device, bwd, G, what)
+        return False
+    ref = texpca_contract_ref(inp, with_mean)
+    fwd(m=mean if with_mean else None)
+    _close_tail = lambda e, name, got, tag, cond=0.0: _tail_close(e, ref[name][0], got, ref[name][2], ref[name][1], f"{what}: {e} {name} {tag}", cond)
+    _close_tail("texture_pca_fwd", "tex", tex, "")
+    first = tex.clone()
+    fwd(m=mean if with_mean else None)
+    _layer_equal("texture_pca_fwd", tex, first, f"{what}: tex, second call")                  # (no atomics in the forward)
+    dcoef.copy_(inp["prefill"])                                                               # "+=": onto what the buffer holds
+    bwd()
+    pre = float(inp["prefill"].abs().max())
+    _tail_close("texture_pca_bwd", "tex_bwd", dcoef.cpu().double() - inp["prefill"].double(), ref["dcoef"][2], n, f"{what}: dcoef onto a prefill", pre)
+    bwd()                                                                                     # float atomics: the second sum inside the bound
+    _tail_close("texture_pca_bwd", "tex_bwd", (dcoef.cpu().double() - inp["prefill"].double()) / 2, ref["dcoef"][2], n, f"{what}: dcoef, second call", pre)
+    dcoef.zero_()
+    bwd()
+    _close_tail("texture_pca_bwd", "dcoef", dcoef, "from zero")
+    G.intact(what)
+    for k, call in enumerate((lambda: fwd(c=None), lambda: fwd(bs=None), lambda: fwd(o=None))):
+        _tail_refuses("texture_pca_fwd", lib, device, call, G, f"{what}: NULL argument {k}")
+    for k, call in enumerate((lambda: bwd(gg=None), lambda: bwd(bs=None), lambda: bwd(o=None))):
+        _tail_refuses("texture_pca_bwd", lib, device, call, G, f"{what}: NULL argument {k}")
+    _tail_drain(lib, device)
+    return True
+
+
+# ---- the small entries: loss total, light split (csrc/losses.hip) --------------------------------------------------------------------
+def loss_total_contract_case(lib, device, counts, lengths=None, mode="ok", seed=0):
+    """counts: leading entries summed per part (len = nparts); lengths: the vectors' full lengths (default 64)."""
+    from hifihr_amd._lib import _fp, _c_float_p
+    import ctypes
+    nparts = len(counts)
+    lengths = list(lengths) if lengths is not None else [64] * nparts
+    what = f"loss_total {(tuple(counts), tuple(lengths), mode)}"
+    gen = torch.Generator().manual_seed(seed)
+    G = Guards(device)
+    alloc = [max(l, c, 1) for l, c in zip(lengths, counts)] or [1]
+    parts = [G.inp(torch.randn(a, generator=gen)) for a in alloc]
+    grads = [G.out(a, fill=9.0) for a in alloc]
+    total, gt = G.out(1), G.inp(torch.tensor([1.75]))
+    arr = lambda ts: (_c_float_p * max(len(ts), 1))(*[_fp(t) for t in ts])
+    ints = lambda v: (ctypes.c_int * max(len(v), 1))(*[int(x) for x in v])
+    fwd = lambda ps=parts, tot=total, np_=nparts: _raw(lib, "hifihr_loss_total_fwd", arr(ps), ints(counts), np_, _fp(tot), None)
+    bwd = lambda gs=grads, g=gt, np_=nparts: _raw(lib, "hifihr_loss_total_bwd", _fp(g), arr(gs), ints(counts), ints(lengths), np_, None)
+    ok_f = 1 <= nparts <= 4 and all(0 <= c <= 64 for c in counts)
+    ok_b = ok_f and all(c <= l <= 64 for c, l in zip(counts, lengths))
+    if mode != "ok" or not ok_f:
+        _tail_refuses("loss_total_fwd", lib, device, (lambda: fwd(ps=[None] + parts[1:])) if mode == "null" else (lambda: fwd(tot=None)) if mode == "null_total" else fwd, G, what)
+    else:
+        fwd()
+        want = torch.tensor([sum(float(p[:c].double().sum()) for p, c in zip(parts, counts))], dtype=torch.float64)
+        _tail_close("loss_total_fwd", "total", total, want, sum(counts), f"{what}: total",
+                    sum(float(p[:c].abs().sum()) for p, c in zip(parts, counts)))                      # (a sum of signed terms)
+        if sum(counts) == 1:
+            _layer_equal("loss_total_fwd", total, [p for p, c in zip(parts, counts) if c][0][:1], f"{what}: a single term")
+        first = total.clone()
+        fwd()
+        _layer_equal("loss_total_fwd", total, first, f"{what}: second call")
+    if mode != "ok" or not ok_b:
+        _tail_refuses("loss_total_bwd", lib, device, (lambda: bwd(gs=[None] + grads[1:])) if mode == "null" else (lambda: bwd(g=None)) if mode == "null_total" else bwd, G, what)
+    else:
+        bwd()
+        for gr, c, l in zip(grads, counts, lengths):
+            want = torch.cat([torch.full((c,), 1.75), torch.zeros(l - c), torch.full((gr.numel() - l,), 9.0)])
+            _layer_equal("loss_total_bwd", gr, want, f"{what}: gradient")
+    G.intact(what)
+    _tail_drain(lib, device)
+    return mode == "ok" and ok_b
+
+
+def light_split_contract_case(lib, device, B, seed=0):
+    """hifihr_light_split_fwd / _bwd inside guards: light_split_case's bit-exact rules (clamp ends, a NaN colour, each gradient NULL)."""
+    from hifihr_amd._lib import _fp
+    what = f"light_split {B}"
+    Bs = max(B, 1)
+    gen = torch.Generator().manual_seed(seed)
+    l = torch.randn(Bs, 6, generator=gen) * 1.5
+    l[0, 0] = 1.0; l[min(1, Bs - 1), 1] = -1.0
+    l[Bs - 1, 2] = float("nan")
+    gc, gd = torch.randn(Bs, 3, generator=gen), torch.randn(Bs, 3, generator=gen)
+    lr = l.clone().requires_grad_(True)
+    c, dd = torch.nn.functional.hardtanh(lr[:, :3]), lr[:, 3:]
+    ((c * gc).sum() + (dd * gd).sum()).backward()
+    G = Guards(device)
+    ld, gcd, gdd = G.inp(l), G.inp(gc), G.inp(gd)
+    oc, od, gl = G.out(Bs, 3), G.out(Bs, 3), G.out(Bs, 6)
+    fwd = lambda a=ld, b=oc, c_=od: _raw(lib, "hifihr_light_split_fwd", _fp(a), B, _fp(b), _fp(c_), None)
+    bwd = lambda a=ld, b=gcd, c_=gdd, o=gl: _raw(lib, "hifihr_light_split_bwd", _fp(a), _fp(b), _fp(c_), B, _fp(o), None)
+    if B <= 0:
+        _tail_refuses("light_split_fwd", lib, device, fwd, G, what)
+        _tail_refuses("light_split_bwd", lib, device, bwd, G, what)
+        return False
+    # (the refused calls first: the forward's NaN colour would make every later bit comparison of its buffer fail)
+    for k, call in enumerate((lambda: fwd(a=None), lambda: fwd(b=None), lambda: fwd(c_=None))):
+        _tail_refuses("light_split_fwd", lib, device, call, G, f"{what}: NULL argument {k}")
+    for k, call in enumerate((lambda: bwd(a=None), lambda: bwd(o=None))):
+        _tail_refuses("light_split_bwd", lib, device, call, G, f"{what}: NULL argument {k}")
+    same = lambda a, b: bool(((a.cpu() == b) | (a.cpu().isnan() & b.isnan())).all())
+    fwd()
+    _layer_log("light_split_fwd", True)
+    assert same(oc, c.detach()) and bool(oc.cpu()[B - 1, 2].isnan()) and torch.equal(od.cpu(), dd.detach().contiguous()), f"{what}: forward"
+    bwd()
+    _layer_log("light_split_bwd", True)
+    assert same(gl, lr.grad) and float(gl.cpu()[B - 1, 2]) == float(gc[B - 1, 2]), f"{what}: backward"
+    bwd(b=None)
+    assert float(gl.cpu()[:, :3].abs().max()) == 0.0 and torch.equal(gl.cpu()[:, 3:], gd), f"{what}: gcolors NULL"
+    bwd(c_=None)
+    assert float(gl.cpu()[:, 3:].abs().max()) == 0.0 and same(gl[:, :3], lr.grad[:, :3]), f"{what}: gdirections NULL"
+    G.intact(what)
+    _tail_drain(lib, device)
+    return True
+
+
+# ---- photometric terms (csrc/losses.hip) -----------------------------------------------------------------------------------------------
+PHOTO_LAMBDAS = (0.005, 0.005, 0.1)               # l_tex, l_mrgb, l_sil
+
+
+def photo_contract_expect(B, H, W):
+    return B > 0 and H > 0 and W > 0 and (H * W) % 4 == 0
+
+
+def photo_contract_inputs(B, H, W, seg_kind, seed, nan_alpha=False):
+    """alpha > 0, = 0 and < 0 inside every image; seg in {0, 1} or, seg_kind "ints", in 0 .. 3."""
+    gen = torch.Generator().manual_seed(seed)
+    rgba = torch.rand(B, 4, H, W, generator=gen)
+    cls = torch.arange(B * H * W).reshape(B, H, W) % 3
+    cls = cls.reshape(B, -1)[:, torch.randperm(H * W, generator=gen)].reshape(B, H, W) if H * W > 3 else cls
+    rgba[:, 3] = torch.where(cls == 0, rgba[:, 3], torch.where(cls == 1, torch.zeros(B, H, W), -rgba[:, 3] - 0.1))
+    if nan_alpha:
+        rgba[B - 1, 3, H - 1, W - 1] = float("nan")
+    imgs = torch.rand(B, 3, H, W, generator=gen)
+    seg = torch.randint(0, 4 if seg_kind == "ints" else 2, (B, H, W), generator=gen)
+    return {"rgba": rgba, "imgs": imgs, "seg": seg, "g_re": torch.randn(B, 3, H, W, generator=gen) * 1e-6, "gout": torch.tensor([0.8, 1.7, 0.0, 0.0])}
+
+
+def photo_contract_ref(inp, dt=torch.float64, drop_quad=False):
+    """losses.py:355-378 + the `sil` term.  drop_quad: the sums without the last four pixels of the last image."""
+    rgba, imgs, seg = inp["rgba"].to(dt), inp["imgs"].to(dt), inp["seg"].to(dt)
+    B, _, H, W = rgba.shape
+    al = rgba[:, 3:4]
+    re_sil = torch.where(al > 0, torch.full_like(al, 255.0), al)
+    re_m = rgba[:, :3] * (re_sil / 255.0)
+    mk = seg.unsqueeze(1) * imgs
+    keep = torch.ones(B, 1, H * W, dtype=dt)
+    if drop_quad:
+        keep[B - 1, 0, -4:] = 0
+    keep = keep.reshape(B, 1, H, W)
+    n3, n1 = B * 3 * H * W, B * H * W
+    l_tex, l_mrgb, l_sil = (float(torch.tensor(v, dtype=torch.float32)) for v in PHOTO_LAMBDAS)
+    sr, sm = (re_m * keep).sum(), (mk * keep).sum()
+    dm = sr / n3 - sm / n3
+    cancel = float(sr.abs() + sm.abs()) / n3
+    return {"re_m": ("photo_img", 1, re_m), "mk": mk,
+            "tex": ("photo_out", n3, (l_tex * ((re_m - mk).abs() * keep).sum() / n3).reshape(1)),
+            "mrgb": ("photo_out", n3, (l_mrgb * dm * dm).reshape(1), l_mrgb * 2 * abs(float(dm)) * cancel),
+            "sil": ("photo_out", n1, (l_sil * ((re_sil - seg.unsqueeze(1)).abs() * keep).sum() / n1).reshape(1)),
+            "dm": ("photo_out", n3, dm.reshape(1), cancel), "re_sil": re_sil}
+
+
+def photo_contract_bwd_ref(inp, re_m, mk, fwd_out, with_g, with_gout, dt=torch.float64, drop_quad=False):
+    """grad_rgba from the entry's own forward tensors (re_m, mask_rgbs, out[3]), as the entry reads them."""
+    rgba = inp["rgba"].to(dt)
+    B, _, H, W = rgba.shape
+    n3 = B * 3 * H * W
+    l_tex, l_mrgb, _ = (float(torch.tensor(v, dtype=torch.float32)) for v in PHOTO_LAMBDAS)
+    al = rgba[:, 3:4]
+    sc = torch.where(al > 0, torch.ones_like(al), al / 255.0)
+    gout = inp["gout"].to(dt) if with_gout else torch.zeros(4, dtype=dt)
+    kt, km = gout[0] * l_tex / n3, gout[1] * l_mrgb * 2 * fwd_out.to(dt)[3] / n3
+    g = (inp["g_re"].to(dt) if with_g else 0.0) + kt * torch.sign(re_m.to(dt) - mk.to(dt)) + km
+    if drop_quad:
+        g = g.clone()
+        g.reshape(B, 3, -1)[B - 1, :, -4:] = 0
+    return ("photo_grad", 1, torch.cat([g * sc, torch.zeros_like(al)], 1))
+
+
+def photo_contract_case(lib, device, B, H, W, seg_kind="binary", seed=0):
+    from hifihr_amd._lib import _fp
+    what = f"photo {(B, H, W, seg_kind)}"
+    Bs, Hs, Ws = max(B, 1), max(H, 1), max(W, 1)
+    if (Hs * Ws) % 4:
+        Hs, Ws = Hs, Ws + (4 - Ws % 4) if Hs % 2 else Ws + Ws % 2
+    nan_case = seg_kind == "nan"
+    inp = photo_contract_inputs(Bs, Hs, Ws, seg_kind, seed, nan_alpha=nan_case)
+    G = Guards(device)
+    rd, idd, sd, gre, gout = G.inp(inp["rgba"]), G.inp(inp["imgs"]), G.inp(inp["seg"]), G.inp(inp["g_re"]), G.inp(inp["gout"])
+    npart = lib.photo_loss_partial_floats()
+    assert npart > 0
+    re_m, mk, out, grad = G.out(Bs, 3, Hs, Ws), G.out(Bs, 3, Hs, Ws), G.out(4), G.out(Bs, 4, Hs, Ws)
+    partial = G.out(npart)
+    scratch = G.outs.pop()                                                # scratch: only its surroundings are watched
+    rs, mrgbs = G.out(Bs, 1, Hs, Ws), G.out(Bs, 3, Hs, Ws)
+    l = PHOTO_LAMBDAS
+    fwd = lambda a=rd, b=idd, c=sd, o1=re_m, o2=mk, p=partial, o=out: _raw(lib, "hifihr_photo_loss_fwd", _fp(a), _fp(b), _vp(c), B, H, W, l[0], l[1], l[2],
+                                                                            _fp(o1), _fp(o2), _fp(p), _fp(o), None)
+    bwd = lambda a=rd, r=re_m, m=mk, g=gre, go=gout, fo=out, o=grad: _raw(lib, "hifihr_photo_loss_bwd", _fp(a), _fp(r), _fp(m), _fp(g), _fp(go), _fp(fo),
+                                                                           B, H, W, l[0], l[1], _fp(o), None)
+    post = lambda a=rd, b=idd, o1=rs, o2=mrgbs: _raw(lib, "hifihr_sil_post", _fp(a), _fp(b), B, H, W, _fp(o1), _fp(o2), None)
+    if not photo_contract_expect(B, H, W):
+        G.outs.append(scratch)
+        _tail_refuses("photo_loss_fwd", lib, device, fwd, G, what)
+        _tail_refuses("photo_loss_bwd", lib, device, bwd, G, what)
+        _tail_refuses("sil_post", lib, device, post, G, what)
+        return False
+    # refused calls first (NaN outputs of the NaN case would defeat the bit comparison of the buffers afterwards)
+    G.outs.append(scratch)
+    for k, call in enumerate((lambda: fwd(a=None), lambda: fwd(b=None), lambda: fwd(c=None), lambda: fwd(o1=None), lambda: fwd(o2=None),
+                              lambda: fwd(p=None), lambda: fwd(o=None))):
+        _tail_refuses("photo_loss_fwd", lib, device, call, G, f"{what}: NULL argument {k}")
+    for k, call in enumerate((lambda: bwd(a=None), lambda: bwd(r=None), lambda: bwd(m=None), lambda: bwd(fo=None), lambda: bwd(o=None))):
+        _tail_refuses("photo_loss_bwd", lib, device, call, G, f"{what}: NULL argument {k}")
+    for k, call in enumerate((lambda: post(a=None), lambda: post(o1=None), lambda: post(b=None))):
+        _tail_refuses("sil_post", lib, device, call, G, f"{what}: NULL argument {k}")
+    G.outs.pop()
+    ref = photo_contract_ref(inp)
+    fwd()
+    e = "photo_loss_fwd"
+    nanpix = torch.zeros(Bs, 1, Hs, Ws, dtype=torch.bool)
+    if nan_case:                                                          # pinned: NaN alpha -> NaN re_img_m at that pixel, NaN in all four terms
+        nanpix[B - 1, 0, H - 1, W - 1] = True
+        assert bool(re_m.cpu().isnan().eq(nanpix.expand(-1, 3, -1, -1)).all()), f"{what}: NaN alpha must reach re_img_m at its pixel only"
+        assert bool(out.cpu().isnan().all()), f"{what}: NaN alpha must reach every term, got {out.cpu()}"
+        _layer_log(e, True)
+    else:
+        _tail_close(e, "photo_img", re_m, ref["re_m"][2], 1, f"{what}: re_img_m")
+        for k, name in enumerate(("tex", "mrgb", "sil", "dm")):
+            q = ref[name]
+            _tail_close(e, q[0], out[k:k + 1], q[2], q[1], f"{what}: out[{k}] ({name})", q[3] if len(q) > 3 else 0.0)
+    _layer_equal(e, mk, ref["mk"].float(), f"{what}: mask_rgbs")
+    first = (re_m.clone(), mk.clone(), out.clone())
+    fwd()                                                                 # deterministic (fixed summation order)
+    same = lambda a, b: bool(((a == b) | (a.isnan() & b.isnan())).all())
+    assert same(re_m, first[0]) and same(mk, first[1]) and same(out, first[2]), f"{what}: forward, second call"
+    e = "photo_loss_bwd"
+    for with_g, with_gout in ((True, True), (False, True), (True, False)):
+        grad.fill_(7.0)                                                   # overwritten, not accumulated
+        bwd(g=gre if with_g else None, go=gout if with_gout else None)
+        gc = grad.cpu()
+        assert float(gc[:, 3].abs().max()) == 0.0, f"{what}: the alpha channel of the gradient must be exact zeros"
+        if nan_case:                                                      # pinned: out[3] is NaN, so is every rgb gradient (0 x NaN with gout NULL)
+            assert bool(gc[:, :3].isnan().all()), f"{what}: NaN alpha, rgb gradient"
+            _layer_log(e, True)
+            continue
+        q = photo_contract_bwd_ref(inp, first[0].cpu(), first[1].cpu(), first[2].cpu(), with_g, with_gout)
+        _tail_close(e, q[0], grad, q[2], q[1], f"{what}: grad_rgba (g_re_img {with_g}, gout {with_gout})")
+        if with_g and with_gout:
+            g1 = grad.clone()
+            bwd()
+            _layer_equal(e, grad, g1, f"{what}: backward, second call")
+    e = "sil_post"
+    post()
+    want_sil = ref["re_sil"].float()
+    assert same(rs.cpu(), want_sil) and bool(rs.cpu().isnan().eq(nanpix).all()), f"{what}: re_sil"
+    _layer_equal(e, mrgbs, (inp["imgs"] * (inp["rgba"][:, 3:4] > 0).float()), f"{what}: maskRGBs")
+    rs2 = G.out(Bs, 1, Hs, Ws)
+    post(b=None, o1=rs2, o2=None)                                         # mask_rgbs NULL (imgs not needed then)
+    assert same(rs2.cpu(), want_sil), f"{what}: re_sil with mask_rgbs NULL"
+    _layer_log(e, True)
+    G.intact(what)
+    whole, lo, hi, canary = scratch
+    assert bool((whole[:lo] == canary).all()) and bool((whole[hi:] == canary).all()), f"{what}: wrote outside the partial sums"
+    _tail_drain(lib, device)
+    return True
+
+
+# ---- joint terms (csrc/losses.hip) -----------------------------------------------------------------------------------------------------
+JOINT_LAMBDAS = (0.7, 1.3, 2.1)
+_BONE_PARENT = [0, 1, 2, 3, 0, 5, 6, 7, 0, 9, 10, 11, 0, 13, 14, 15, 0, 17, 18, 19]
+_BONE_CHILD = list(range(1, 21))
+
+
+def joint_contract_expect(B, J, use2, use3):
+    return B > 0 and J == 21 and (use2 or use3)
+
+
+def joint_contract_inputs(B, special, seed, J=21):
+    gen = torch.Generator().manual_seed(seed)
+    j2d, j2d_gt = torch.rand(B, J, 2, generator=gen) * 224, torch.rand(B, J, 2, generator=gen) * 224
+    j3d, j3d_gt = torch.randn(B, J, 3, generator=gen) * 0.05, torch.randn(B, J, 3, generator=gen) * 0.05
+    if special == "identical":
+        j2d, j3d = j2d_gt.clone(), j3d_gt.clone()
+    elif special == "zero_bones" and J == 21:                             # sample 0: bone 3 (3 -> 4) of zero length in pred, bone 7 (7 -> 8) in gt
+        j2d[0, 4], j3d[0, 4] = j2d[0, 3], j3d[0, 3]
+        j2d_gt[0, 8], j3d_gt[0, 8] = j2d_gt[0, 7], j3d_gt[0, 7]
+    return {"j2d": j2d, "j2d_gt": j2d_gt, "j3d": j3d, "j3d_gt": j3d_gt, "gout": torch.tensor([0.9, -1.1, 0.6])}
+
+
+def joint_contract_ref(inp, mse, use2, use3, dt=torch.float64, drop_bone=None):
+    """joint_2d, bone_direc, bone_direc_3d (losses.py:267-282, utils/losses_util.py:217-283 with confidence 1) and the gradient of
+    sum_k gout[k] out[k] in closed form: d |vn - vgn|^2 / dv = 2 / (|v| + eps) (dn - vn (dn . v) / |v|), the second term taken as zero at
+    |v| = 0 (autograd: NaN).  drop_bone: without that bone of the last sample."""
+    lam = [float(torch.tensor(v, dtype=torch.float32)) for v in JOINT_LAMBDAS]
+    gout = inp["gout"].to(dt)
+    par, chi = torch.tensor(_BONE_PARENT), torch.tensor(_BONE_CHILD)
+    B = inp["j2d"].shape[0]
+    out, grads = [torch.zeros(1, dtype=dt)] * 3, {}
+
+    def bones(j, jg, k):
+        v, vg = j[:, chi] - j[:, par], jg[:, chi] - jg[:, par]
+        n = v.pow(2).sum(2, keepdim=True).sqrt()
+        il = 1 / (n + 1e-4)
+        vn = v * il
+        dn = vn - vg * (1 / (vg.pow(2).sum(2, keepdim=True).sqrt() + 1e-4))        # (the same form on both sides: an identical pair gives exactly 0)
+        keep = torch.ones(B, 20, 1, dtype=dt)
+        if drop_bone is not None:
+            keep[B - 1, drop_bone] = 0
+        term = lam[k] * (dn.pow(2).sum(2, keepdim=True) * keep).sum() / (B * 20)
+        radial = torch.where(n > 0, (dn * vn).sum(2, keepdim=True) * v / n.clamp_min(1e-300), torch.zeros_like(v))
+        gv = 2 * gout[k] * lam[k] / (B * 20) * il * (dn - radial) * keep
+        g = torch.zeros_like(j)
+        g.index_add_(1, chi, gv)
+        g.index_add_(1, par, -gv)
+        return term.reshape(1), g
+    if use2:
+        j, jg = inp["j2d"].to(dt), inp["j2d_gt"].to(dt)
+        d = jg - j
+        out[0] = (lam[0] * ((d * d) if mse else d.abs()).mean()).reshape(1)
+        out[1], g = bones(j, jg, 1)
+        grads["g2"] = g - gout[0] * lam[0] / d.numel() * ((2 * d) if mse else torch.sign(d))
+    if use3:
+        out[2], grads["g3"] = bones(inp["j3d"].to(dt), inp["j3d_gt"].to(dt), 2)
+    return out, grads
+
+
+def joint_contract_case(lib, device, B, mse, use2=True, use3=True, special="random", J=21, seed=0):
+    from hifihr_amd._lib import _fp
+    import ctypes
+    what = f"joint_terms {(B, mse, use2, use3, special, J)}"
+    Bs = max(B, 1)
+    inp = joint_contract_inputs(Bs, special, seed, J)
+    G = Guards(device)
+    a2 = (G.inp(inp["j2d"]), G.inp(inp["j2d_gt"]))
+    a3 = (G.inp(inp["j3d"]), G.inp(inp["j3d_gt"]))
+    gout, out, g2, g3 = G.inp(inp["gout"]), G.out(3), G.out(Bs, J, 2), G.out(Bs, J, 3)
+    lam = (ctypes.c_float * 3)(*JOINT_LAMBDAS)
+    N = lambda t, use: t if use else None
+    fwd = lambda p2=N(a2[0], use2), q2=N(a2[1], use2), p3=N(a3[0], use3), q3=N(a3[1], use3), o=out, lm=lam: _raw(
+        lib, "hifihr_joint_terms_fwd", _fp(p2), _fp(q2), _fp(p3), _fp(q3), B, J, int(mse), lm, _fp(o), None)
+    bwd = lambda p2=N(a2[0], use2), q2=N(a2[1], use2), p3=N(a3[0], use3), q3=N(a3[1], use3), go=gout, o2=N(g2, use2), o3=N(g3, use3), lm=lam: _raw(
+        lib, "hifihr_joint_terms_bwd", _fp(p2), _fp(q2), _fp(p3), _fp(q3), B, J, int(mse), lm, _fp(go), _fp(o2), _fp(o3), None)
+    if not joint_contract_expect(B, J, use2, use3):
+        _tail_refuses("joint_terms_fwd", lib, device, fwd, G, what)
+        _tail_refuses("joint_terms_bwd", lib, device, (lambda: bwd(o2=g2, o3=g3)) if not (use2 or use3) and B > 0 and J == 21 else bwd, G, what)
+        return False
+    ref, gref = joint_contract_ref(inp, mse, use2, use3)
+    fwd()
+    Ls = (B * 21 * 2, B * 20 * 2, B * 20 * 3)
+    for k in range(3):
+        _tail_close("joint_terms_fwd", "joint_out", out[k:k + 1], ref[k], Ls[k], f"{what}: out[{k}]")
+        if not (use2, use2, use3)[k]:
+            assert float(out[k]) == 0.0, f"{what}: a term without inputs must be exactly 0"
+    first = out.clone()
+    fwd()
+    _layer_equal("joint_terms_fwd", out, first, f"{what}: second call")
+    bwd()
+    for use, got, name in ((use2, g2, "g2"), (use3, g3, "g3")):           # per sample: a zero-length bone's 1 / eps must not hide the others
+        for b in range(B if use else 0):
+            _tail_close("joint_terms_bwd", "joint_grad", got[b], gref[name][b], 6, f"{what}: {name}, sample {b}")
+    firsts = (g2.clone(), g3.clone())
+    bwd()
+    _layer_equal("joint_terms_bwd", g2, firsts[0], f"{what}: g_j2d, second call")
+    _layer_equal("joint_terms_bwd", g3, firsts[1], f"{what}: g_joints, second call")
+    if use2 and use3:                                                     # each gradient NULL: the other is the same bits
+        h2, h3 = G.out(Bs, J, 2), G.out(Bs, J, 3)
+        bwd(o2=h2, o3=None)
+        bwd(o2=None, o3=h3)
+        _layer_equal("joint_terms_bwd", h2, firsts[0], f"{what}: g_j2d alone")
+        _layer_equal("joint_terms_bwd", h3, firsts[1], f"{what}: g_joints alone")
+    G.intact(what)
+    if use2:
+        _tail_refuses("joint_terms_fwd", lib, device, lambda: fwd(q2=None), G, f"{what}: j2d without its gt")
+        _tail_refuses("joint_terms_bwd", lib, device, lambda: bwd(q2=None), G, f"{what}: j2d without its gt")
+    else:
+        _tail_refuses("joint_terms_bwd", lib, device, lambda: bwd(o2=g2), G, f"{what}: g_j2d without j2d")
+    if use3:
+        _tail_refuses("joint_terms_fwd", lib, device, lambda: fwd(q3=None), G, f"{what}: joints without their gt")
+        _tail_refuses("joint_terms_bwd", lib, device, lambda: bwd(q3=None), G, f"{what}: joints without their gt")
+    else:
+        _tail_refuses("joint_terms_bwd", lib, device, lambda: bwd(o3=g3), G, f"{what}: g_joints without joints")
+    _tail_refuses("joint_terms_fwd", lib, device, lambda: fwd(o=None), G, f"{what}: out NULL")
+    _tail_refuses("joint_terms_fwd", lib, device, lambda: fwd(lm=None), G, f"{what}: lambda NULL")
+    _tail_refuses("joint_terms_bwd", lib, device, lambda: bwd(go=None), G, f"{what}: gout NULL")
+    _tail_refuses("joint_terms_bwd", lib, device, lambda: bwd(lm=None), G, f"{what}: lambda NULL")
+    _tail_drain(lib, device)
+    return True
+
+
+# ---- geometry terms (csrc/losses.hip) ----------------------------------------------------------------------------------------------------
+GEOM_LAMBDAS = (1e4, 1e4, 1e2, 0.25, 0.5)
+
+
+def geom_contract_expect(B, J, V, F, NS, NP):
+    return B > 0 and J > 0 and V > 0 and F >= 0 and NS >= 0 and NP >= 0
+
+
+def geom_contract_inputs(B, J, V, F, NS, NP, special, seed):
+    """special: "random"; "identical" (pred = gt: sign(0) = 0 everywhere); "zero_edges" (face 0 has a zero-length PREDICTED edge, face 1 a
+    zero-length GT edge).  The last vertex is in no face whenever V > 3."""
+    gen = torch.Generator().manual_seed(seed)
+    rnd = lambda *s: torch.randn(*s, generator=gen)
+    inp = {"joints": rnd(B, J, 3) * 0.05, "joints_gt": rnd(B, J, 3) * 0.05, "verts": rnd(B, V, 3) * 0.05, "verts_gt": rnd(B, V, 3) * 0.05,
+           "shape": rnd(B, NS), "pose": rnd(B, NP), "gout": torch.tensor([0.7, 1.3, 0.9, 1.1, 0.6])}
+    Vf = V - 1 if V > 3 else V
+    inp["faces"] = torch.stack([torch.randperm(Vf, generator=gen)[:3] for _ in range(F)]).int() if F > 0 and V >= 3 else None
+    if special == "identical":
+        inp["joints"], inp["verts"] = inp["joints_gt"].clone(), inp["verts_gt"].clone()
+    elif special == "zero_edges" and inp["faces"] is not None and F >= 2 and V >= 7:
+        inp["faces"][0] = torch.tensor([0, 1, 2], dtype=torch.int32)
+        inp["faces"][1] = torch.tensor([3, 4, 5], dtype=torch.int32)
+        inp["verts"][:, 1] = inp["verts"][:, 0]
+        inp["verts_gt"][:, 4] = inp["verts_gt"][:, 3]
+    return inp
+
+
+def geom_contract_ref(inp, mse, dt=torch.float64, drop_vertex=None, drop_face=None):
+    """The five terms and their gradients in closed form (autograd gives NaN at a zero-length predicted edge; the kernel -- and this
+    reference -- give that edge no gradient).  -> out: five (kind, L, value); grads: gj, gv, gs, gp as (kind, L, tensor)."""
+    lam = [float(torch.tensor(v, dtype=torch.float32)) for v in GEOM_LAMBDAS]
+    gout = inp["gout"].to(dt)
+    j, jg, v, vg, sh, po = (inp[k].to(dt) for k in ("joints", "joints_gt", "verts", "verts_gt", "shape", "pose"))
+    B, J, V, NS, NP = j.shape[0], j.shape[1], v.shape[1], sh.shape[1], po.shape[1]
+    faces = inp["faces"].long() if inp["faces"] is not None else None
+    F = 0 if faces is None else faces.shape[0]
+    base = (lambda d: d * d) if mse else (lambda d: d.abs())
+    bgrad = (lambda d: 2 * d) if mse else torch.sign
+    vkeep = torch.ones(1, V, 1, dtype=dt)
+    if drop_vertex is not None:
+        vkeep[0, drop_vertex] = 0
+    out = [("geom_out", B * J * 3, (lam[0] * base(j - jg).sum() / (B * J * 3)).reshape(1)),
+           ("geom_out", B * V * 3, (lam[1] * (base(v - vg) * vkeep).sum() / (B * V * 3)).reshape(1))]
+    gv = gout[1] * lam[1] / (B * V * 3) * bgrad(v - vg) * vkeep
+    valence = torch.zeros(V)
+    if F:
+        fkeep = torch.ones(F, dtype=dt)
+        if drop_face is not None:
+            fkeep[drop_face] = 0
+        e = torch.zeros((), dtype=dt)
+        ce = gout[2] * lam[2] / (B * F * 3)
+        for a, b in ((0, 1), (0, 2), (1, 2)):
+            ia, ib = faces[:, a], faces[:, b]
+            dp, dg = v[:, ia] - v[:, ib], vg[:, ia] - vg[:, ib]
+            lp, lg = dp.pow(2).sum(2).sqrt(), dg.pow(2).sum(2).sqrt()
+            e = e + ((lp - lg).abs() * fkeep).sum()
+            k = torch.where(lp > 0, ce * torch.sign(lp - lg) / lp.clamp_min(1e-300), torch.zeros_like(lp)) * fkeep
+            gv = gv.index_add(1, ia, k.unsqueeze(2) * dp).index_add(1, ib, -k.unsqueeze(2) * dp)
+            valence.index_add_(0, ia, torch.ones(F)).index_add_(0, ib, torch.ones(F))
+        out.append(("geom_out", B * F * 3, (lam[2] * e / (B * F * 3)).reshape(1)))
+    else:
+        out.append(("geom_out", 1, torch.zeros(1, dtype=dt)))
+    out.append(("geom_out", B * NS, (lam[3] * sh.pow(2).sum() / (B * NS)).reshape(1) if NS else torch.zeros(1, dtype=dt)))
+    out.append(("geom_out", B * NP, (lam[4] * po.pow(2).sum() / (B * NP)).reshape(1) if NP else torch.zeros(1, dtype=dt)))
+    grads = {"gj": ("geom_grad", 1, gout[0] * lam[0] / (B * J * 3) * bgrad(j - jg)), "gv": ("geom_grad", 1 + int(valence.max()), gv),
+             "gs": ("geom_grad", 1, gout[3] * lam[3] * 2 / (B * max(NS, 1)) * sh), "gp": ("geom_grad", 1, gout[4] * lam[4] * 2 / (B * max(NP, 1)) * po)}
+    return out, grads
+
+
+def geom_contract_case(lib, device, B, J, V, F, NS, NP, mse, special="random", seed=0):
+    from hifihr_amd._lib import _fp, _ip
+    import ctypes
+    what = f"geom_loss {(B, J, V, F, NS, NP, mse, special)}"
+    Bs, Js, Vs = max(B, 1), max(J, 1), max(V, 1)
+    inp = geom_contract_inputs(Bs, Js, Vs, F, NS, NP, special, seed)
+    Fe = 0 if inp["faces"] is None else F
+    G = Guards(device)
+    d = {k: G.inp(inp[k]) for k in ("joints", "joints_gt", "verts", "verts_gt", "shape", "pose", "faces", "gout")}
+    off = idx = None
+    if Fe:
+        o_, i_ = vertex_face_csr(inp["faces"].numpy(), Vs)
+        off, idx = G.inp(torch.from_numpy(o_)), G.inp(torch.from_numpy(i_))
+    partial, out = G.out(Bs * 5), G.out(5)
+    scratch = G.outs.pop(-2)                                               # partial: scratch, only its surroundings are watched
+    gj, gv, gs, gp = G.out(Bs, Js, 3), G.out(Bs, Vs, 3), G.out(Bs, NS), G.out(Bs, NP)
+    lam = (ctypes.c_float * 5)(*GEOM_LAMBDAS)
+    nn = lambda t, n: t if n > 0 else None                                # (an empty tensor's pointer is no use: NULL where the count is 0)
+
+    def fwd(B_=B, J_=J, V_=V, F_=Fe, NS_=NS, NP_=NP, lm=lam, **kw):
+        a = dict(d, partial=partial, out=out)
+        a.update(kw)
+        _raw(lib, "hifihr_geom_loss_fwd", _fp(a["joints"]), _fp(a["joints_gt"]), _fp(a["verts"]), _fp(a["verts_gt"]), _fp(nn(a["shape"], NS_)),
+             _fp(nn(a["pose"], NP_)), _ip(a["faces"]), B_, J_, V_, F_, NS_, NP_, int(mse), lm, _fp(a["partial"]), _fp(a["out"]), None)
+
+    def bwd(B_=B, J_=J, V_=V, F_=Fe, NS_=NS, NP_=NP, lm=lam, **kw):
+        a = dict(d, off=off, idx=idx, gj=gj, gv=gv, gs=nn(gs, NS), gp=nn(gp, NP))
+        a.update(kw)
+        _raw(lib, "hifihr_geom_loss_bwd", _fp(a["joints"]), _fp(a["joints_gt"]), _fp(a["verts"]), _fp(a["verts_gt"]), _fp(nn(a["shape"], NS_)),
+             _fp(nn(a["pose"], NP_)), _ip(a["faces"]), _ip(a["off"]), _ip(a["idx"]), B_, J_, V_, F_, NS_, NP_, int(mse), lm, _fp(a["gout"]),
+             _fp(a["gj"]), _fp(a["gv"]), _fp(a["gs"]), _fp(a["gp"]), None)
+    if not geom_contract_expect(B, J, V, F, NS, NP):
+        G.outs.append(scratch)
+        _tail_refuses("geom_loss_fwd", lib, device, fwd, G, what)
+        _tail_refuses("geom_loss_bwd", lib, device, bwd, G, what)
+        return False
+    ref, gref = geom_contract_ref(inp, mse)
+    fwd()
+    for k in range(5):
+        _tail_close("geom_loss_fwd", ref[k][0], out[k:k + 1], ref[k][2], ref[k][1], f"{what}: out[{k}]")
+    for k, cnt in ((2, Fe), (3, NS), (4, NP)):
+        assert cnt > 0 or float(out[k]) == 0.0, f"{what}: a term with count 0 must be exactly 0, out[{k}] = {float(out[k])}"
+    first = out.clone()
+    fwd()
+    _layer_equal("geom_loss_fwd", out, first, f"{what}: second call")
+    bwd()
+    got = {"gj": gj, "gv": gv, "gs": gs, "gp": gp}
+    for name in ("gj", "gv", "gs", "gp"):
+        q = gref[name]
+        _tail_close("geom_loss_bwd", q[0], got[name], q[2], q[1], f"{what}: {name}")
+    firsts = {k: v.clone() for k, v in got.items()}
+    bwd()
+    for name in got:
+        _layer_equal("geom_loss_bwd", got[name], firsts[name], f"{what}: {name}, second call")
+    for name in ("gj", "gv", "gs", "gp"):                                   # each gradient NULL: the others are the same bits
+        fresh = {"gj": G.out(Bs, Js, 3), "gv": G.out(Bs, Vs, 3), "gs": nn(G.out(Bs, NS), NS), "gp": nn(G.out(Bs, NP), NP)}
+        fresh[name] = None
+        bwd(**fresh)
+        for other in got:
+            if other != name and fresh[other] is not None:
+                _layer_equal("geom_loss_bwd", fresh[other], firsts[other], f"{what}: {other} with {name} NULL")
+    G.intact(what)
+    whole, lo, hi, canary = scratch
+    assert bool((whole[:lo] == canary).all()) and bool((whole[hi:] == canary).all()), f"{what}: wrote outside the partial sums"
+    G.outs.append(scratch)
+    bad = [("joints NULL", dict(joints=None)), ("joints_gt NULL", dict(joints_gt=None)), ("verts NULL", dict(verts=None)), ("verts_gt NULL", dict(verts_gt=None)),
+           ("lambda NULL", dict(lm=None)), ("F < 0", dict(F_=-1)), ("NS < 0", dict(NS_=-1)), ("NP < 0", dict(NP_=-1))]
+    bad += [("faces NULL", dict(faces=None))] if Fe else [("F > 0 without faces", dict(F_=3, faces=None))]
+    bad += [("shape NULL", dict(shape=None))] if NS else [("NS > 0 without shape", dict(NS_=4, shape=None))]
+    bad += [("pose NULL", dict(pose=None))] if NP else [("NP > 0 without pose", dict(NP_=4, pose=None))]
+    for why, kw in bad:
+        _tail_refuses("geom_loss_fwd", lib, device, lambda: fwd(**kw), G, f"{what}: {why}")
+        _tail_refuses("geom_loss_bwd", lib, device, lambda: bwd(**kw), G, f"{what}: {why}")
+    _tail_refuses("geom_loss_fwd", lib, device, lambda: fwd(partial=None), G, f"{what}: partial NULL")
+    _tail_refuses("geom_loss_fwd", lib, device, lambda: fwd(out=None), G, f"{what}: out NULL")
+    _tail_refuses("geom_loss_bwd", lib, device, lambda: bwd(gout=None), G, f"{what}: gout NULL")
+    if Fe:
+        _tail_refuses("geom_loss_bwd", lib, device, lambda: bwd(off=None), G, f"{what}: no vertex -> face offsets")
+        _tail_refuses("geom_loss_bwd", lib, device, lambda: bwd(idx=None), G, f"{what}: no vertex -> face table")
+    _tail_drain(lib, device)
+    return True
+
+
+# ---- MANO layer, joint regression, the fused form (csrc/mano_lbs.hip) -------------------------------------------------------------------
+TAIL_LEGACY.update({
+    "mano_v": lambda ref, L: 5e-6,                                        # mano_fwd_bwd_case / mano_full_case: absolute, metres
+    "mano_j": lambda ref, L: 2e-6,                                        # mano_joints_case
+    "mano_g": lambda ref, L: 3e-4 * float(ref.abs().max()),               # mano_fwd_bwd_case / mano_full_case: of the largest gradient
+    "mano_gv": lambda ref, L: 2e-4,                                       # mano_joints_case
+    "lbs_v": lambda ref, L: 2e-6 * max(1.0, float(ref.abs().max()) / 0.1),           # lbs_case
+    "lbs_g": lambda ref, L: 2e-4 * float(ref.abs().max()),
+})
+MANO_POSE_FAMILIES = ("zero", "1e-7", "1e-4", "0.6", "3.0", "root0", "rootpi")
+
+
+def mano_contract_inputs(B, family, seed):
+    gen = torch.Generator().manual_seed(seed)
+    rnd = lambda *s: torch.randn(*s, generator=gen)
+    scale = {"zero": 0.0, "root0": 0.6, "rootpi": 0.6}.get(family)
+    pose = rnd(B, 48) * (float(family) if scale is None else scale)
+    if family == "root0":
+        pose[:, :3] = 0.0                                                 # the root rotation exactly 0
+    elif family == "rootpi":
+        pose[:, :3] = 0.0
+        pose[torch.arange(B), torch.arange(B) % 3] = float(np.float32(np.pi))          # exactly pi about an axis
+    return {"pose": pose, "beta": rnd(B, 10) * 0.7, "root_xyz": rnd(B, 3) * 0.3, "wv": rnd(B, 778, 3), "wj": rnd(B, 21, 3), "wc": rnd(B, 778, 3),
+            "wr": rnd(B, 3), "wv2": rnd(B, 778, 3), "wj2": rnd(B, 21, 3), "ap": rnd(B, 48), "ab": rnd(B, 10)}
+
+
+def mano_layer_ref(tables, inp, dt=torch.float64, drop_vertex=None):
+    """ManoLayer.forward and, per incoming gradient, d/d(pose, beta): {"v": of sum(verts wv), "j": of sum(jtr wj)} (linear: a NULL
+    gradient leaves its part out).  drop_vertex: that vertex's gverts left out."""
+    pose, beta = inp["pose"].to(dt).requires_grad_(True), inp["beta"].to(dt).requires_grad_(True)
+    verts, jtr, _ = mo.mano_forward(tables, pose, beta, dtype=dt)
+    wv = inp["wv"].to(dt).clone()
+    if drop_vertex is not None:
+        wv[:, drop_vertex] = 0
+    g = {k: torch.autograd.grad(t, (pose, beta), retain_graph=True) for k, t in (("v", (verts * wv).sum()), ("j", (jtr * inp["wj"].to(dt)).sum()))}
+    return verts.detach(), jtr.detach(), g
+
+
+def mano_joints_ref(tables, verts, inp, root_id, dt=torch.float64, drop_vertex=None):
+    """xyz_from_vertice + the root-relative step on `verts`, and per incoming gradient d/dverts: "j", "v", "r"."""
+    v = verts.to(dt).clone().requires_grad_(True)
+    vin = v
+    if drop_vertex is not None:
+        m = torch.ones(1, 778, 1, dtype=dt)
+        m[0, drop_vertex] = 0
+        vin = v * m
+    j = mo.xyz_from_vertice(tables, vin, dtype=dt)
+    if root_id >= 0:
+        jr, vr, root = mo.root_relative(j, v, root_id)
+    else:
+        jr, vr, root = j, v, torch.zeros(v.shape[0], 1, 3, dtype=dt)
+    terms = {"j": (jr * inp["wj2"].to(dt)).sum(), "v": (vr * inp["wv2"].to(dt)).sum(), "r": (root.reshape(-1, 3) * inp["wr"].to(dt)).sum()}
+    g = {k: (torch.autograd.grad(t, v, retain_graph=True)[0] if t.requires_grad else torch.zeros_like(v)) for k, t in terms.items()}
+    return jr.detach(), vr.detach(), root.detach().reshape(-1, 3), g
+
+
+def mano_full_ref(tables, inp, root_id, dt=torch.float64):
+    """The chain layer -> regression -> root-relative -> + root_xyz and, per incoming gradient, d/d(pose, beta): "j", "v", "c", "r"."""
+    pose, beta = inp["pose"].to(dt).requires_grad_(True), inp["beta"].to(dt).requires_grad_(True)
+    verts, _, _ = mo.mano_forward(tables, pose, beta, dtype=dt)
+    j = mo.xyz_from_vertice(tables, verts, dtype=dt)
+    if root_id >= 0:
+        jr, vr, root = mo.root_relative(j, verts, root_id)
+    else:
+        jr, vr, root = j, verts, torch.zeros(verts.shape[0], 1, 3, dtype=dt)
+    vc = vr + inp["root_xyz"].to(dt).unsqueeze(1)
+    terms = {"j": (jr * inp["wj2"].to(dt)).sum(), "v": (vr * inp["wv2"].to(dt)).sum(), "c": (vc * inp["wc"].to(dt)).sum(),
+             "r": (root.reshape(-1, 3) * inp["wr"].to(dt)).sum()}
+    zero = (torch.zeros_like(pose), torch.zeros_like(beta))
+    g = {k: (torch.autograd.grad(t, (pose, beta), retain_graph=True) if t.requires_grad else zero) for k, t in terms.items()}
+    return {"verts": verts.detach(), "jr": jr.detach(), "vr": vr.detach(), "vc": vc.detach(), "root": root.detach().reshape(-1, 3)}, g
+
+
+def mano_contract_case(lib, device, tables, B, family, root_id, seed=0):
+    """All six hifihr_mano_* compute entries on one (batch, pose family, root) -- see the section header for the contract."""
+    from hifihr_amd._lib import _fp
+    what = f"mano {(B, family, root_id)}"
+    Bs = max(B, 1)
+    inp = mano_contract_inputs(Bs, family, seed)
+    G = Guards(device)
+    d = {k: G.inp(v) for k, v in inp.items()}
+    h = lib.mano_create(tables)
+    NV = 778
+    try:
+        lfwd = lambda pose=d["pose"], beta=d["beta"], verts=None, jtr=None, saved=None, hh=h, B_=B: _raw(
+            lib, "hifihr_mano_lbs_fwd", hh, _fp(pose), _fp(beta), B_, _fp(verts), _fp(jtr), _fp(saved), None)
+        lbwd = lambda pose=d["pose"], beta=d["beta"], saved=None, gv=d["wv"], gj=d["wj"], gp=None, gb=None, hh=h, B_=B: _raw(
+            lib, "hifihr_mano_lbs_bwd", hh, _fp(pose), _fp(beta), _fp(saved), _fp(gv), _fp(gj), B_, _fp(gp), _fp(gb), None)
+        jfwd = lambda verts=None, jr=None, vr=None, root=None, rid=root_id, hh=h, B_=B: _raw(
+            lib, "hifihr_mano_joints_fwd", hh, _fp(verts), B_, rid, _fp(jr), _fp(vr), _fp(root), None)
+        jbwd = lambda gj=d["wj2"], gv=d["wv2"], gr=d["wr"], out=None, rid=root_id, hh=h, B_=B: _raw(
+            lib, "hifihr_mano_joints_bwd", hh, _fp(gj), _fp(gv), _fp(gr), B_, rid, _fp(out), None)
+        ffwd = lambda pose=d["pose"], beta=d["beta"], rxyz=d["root_xyz"], verts=None, jr=None, vr=None, vc=None, root=None, saved=None, rid=root_id, hh=h, B_=B: _raw(
+            lib, "hifihr_mano_full_fwd", hh, _fp(pose), _fp(beta), B_, rid, _fp(rxyz), _fp(verts), _fp(jr), _fp(vr), _fp(vc), _fp(root), _fp(saved), None)
+        fbwd = lambda pose=d["pose"], beta=d["beta"], saved=None, gj=d["wj2"], gv=d["wv2"], gc=d["wc"], gr=d["wr"], ap=None, ab=None, gp=None, gb=None, rid=root_id, hh=h, B_=B: _raw(
+            lib, "hifihr_mano_full_bwd", hh, _fp(pose), _fp(beta), _fp(saved), _fp(gj), _fp(gv), _fp(gc), _fp(gr), _fp(ap), _fp(ab), B_, rid, _fp(gp), _fp(gb), None)
+        V3 = lambda: G.out(Bs, NV, 3)
+        verts, jtr, saved, gp, gb = V3(), G.out(Bs, 21, 3), V3(), G.out(Bs, 48), G.out(Bs, 10)
+        jr, vr, root, gverts = G.out(Bs, 21, 3), V3(), G.out(Bs, 3), V3()
+        if B < 0 or root_id >= 21:
+            _tail_refuses("mano_full_fwd", lib, device, lambda: ffwd(verts=verts, jr=jr, vr=vr, saved=saved), G, what)
+            _tail_refuses("mano_full_bwd", lib, device, lambda: fbwd(saved=saved, gp=gp, gb=gb), G, what)
+            _tail_refuses("mano_joints_fwd", lib, device, lambda: jfwd(verts=d["wv"], jr=jr, vr=vr, root=root), G, what)
+            _tail_refuses("mano_joints_bwd", lib, device, lambda: jbwd(out=gverts), G, what)
+            if B < 0:
+                _tail_refuses("mano_lbs_fwd", lib, device, lambda: lfwd(verts=verts, jtr=jtr, saved=saved), G, what)
+                _tail_refuses("mano_lbs_bwd", lib, device, lambda: lbwd(saved=saved, gp=gp, gb=gb), G, what)
+            return False
+        if B == 0:                                                        # accepted; writes nothing, launches nothing
+            _tail_drain(lib, device)
+            before = [w.clone() for w in G.wholes()]
+            for e, call in (("mano_lbs_fwd", lambda: lfwd(verts=verts, jtr=jtr, saved=saved)), ("mano_lbs_bwd", lambda: lbwd(saved=saved, gp=gp, gb=gb)),
+                            ("mano_joints_fwd", lambda: jfwd(verts=d["wv"], jr=jr, vr=vr, root=root)), ("mano_joints_bwd", lambda: jbwd(out=gverts)),
+                            ("mano_full_fwd", lambda: ffwd(verts=verts, jr=jr, vr=vr, saved=saved)), ("mano_full_bwd", lambda: fbwd(saved=saved, gp=gp, gb=gb))):
+                call()
+                _layer_log(e, True)
+            assert not _tail_drain(lib, device), f"{what}: B = 0 launched a kernel"
+            assert all(torch.equal(a, b) for a, b in zip(G.wholes(), before)), f"{what}: B = 0 wrote"
+            return True
+        # ---- the layer ----
+        rv, rj, rg = mano_layer_ref(tables, inp)
+        lfwd(verts=verts, jtr=jtr, saved=saved)
+        _tail_close("mano_lbs_fwd", "mano_v", verts, rv, 16, f"{what}: verts")
+        _tail_close("mano_lbs_fwd", "mano_v", jtr, rj, 16, f"{what}: jtr")
+        first = (verts.clone(), jtr.clone(), saved.clone())
+        lfwd(verts=verts, jtr=jtr, saved=saved)
+        for a, b, n in zip((verts, jtr, saved), first, ("verts", "jtr", "saved")):
+            _layer_equal("mano_lbs_fwd", a, b, f"{what}: {n}, second call")
+        v2, j2 = V3(), G.out(Bs, 21, 3)
+        lfwd(verts=v2, jtr=None, saved=None)                              # jtr / saved NULL
+        _layer_equal("mano_lbs_fwd", v2, first[0], f"{what}: verts with jtr and saved NULL")
+        lbwd(saved=saved, gp=gp, gb=gb)
+        _tail_close("mano_lbs_bwd", "mano_g", gp, rg["v"][0] + rg["j"][0], NV, f"{what}: gpose")
+        _tail_close("mano_lbs_bwd", "mano_g", gb, rg["v"][1] + rg["j"][1], NV, f"{what}: gbeta")
+        g1 = (gp.clone(), gb.clone())
+        lbwd(saved=saved, gp=gp, gb=gb)                                   # overwritten, deterministic
+        _layer_equal("mano_lbs_bwd", gp, g1[0], f"{what}: gpose, second call")
+        _layer_equal("mano_lbs_bwd", gb, g1[1], f"{what}: gbeta, second call")
+        for null, keep in (("gv", "j"), ("gj", "v")):
+            gp2, gb2 = G.out(Bs, 48), G.out(Bs, 10)
+            lbwd(saved=saved, gp=gp2, gb=gb2, **{null: None})
+            _tail_close("mano_lbs_bwd", "mano_g", gp2, rg[keep][0], NV, f"{what}: gpose with {null} NULL")
+            _tail_close("mano_lbs_bwd", "mano_g", gb2, rg[keep][1], NV, f"{what}: gbeta with {null} NULL")
+        # ---- regression + root-relative step, on the layer's own vertices ----
+        qjr, qvr, qroot, qg = mano_joints_ref(tables, first[0].cpu(), inp, root_id)
+        jfwd(verts=verts, jr=jr, vr=vr, root=root)
+        for got, ref_, n in ((jr, qjr, "joints_rel"), (vr, qvr, "verts_rel"), (root, qroot, "root")):
+            _tail_close("mano_joints_fwd", "mano_j", got, ref_, NV, f"{what}: {n}")
+        two = (jr.clone(), vr.clone(), root.clone())
+        alias, jr2 = V3(), G.out(Bs, 21, 3)
+        alias.copy_(verts)
+        jfwd(verts=alias, jr=jr2, vr=alias, root=None)                    # verts_rel aliasing verts; root NULL
+        _layer_equal("mano_joints_fwd", alias, two[1], f"{what}: verts_rel written over verts")
+        _layer_equal("mano_joints_fwd", jr2, two[0], f"{what}: joints_rel, aliased call")
+        jr3 = G.out(Bs, 21, 3)
+        jfwd(verts=verts, jr=jr3, vr=None, root=None)                     # verts_rel NULL
+        _layer_equal("mano_joints_fwd", jr3, two[0], f"{what}: joints_rel with verts_rel NULL")
+        jbwd(out=gverts)
+        _tail_close("mano_joints_bwd", "mano_gv", gverts, qg["j"] + qg["v"] + qg["r"], 22, f"{what}: gverts")
+        gv1 = gverts.clone()
+        jbwd(out=gverts)
+        _layer_equal("mano_joints_bwd", gverts, gv1, f"{what}: gverts, second call")
+        for null, keep in (("gj", "vr"), ("gv", "jr"), ("gr", "jv")):
+            gv2 = V3()
+            jbwd(out=gv2, **{null: None})
+            _tail_close("mano_joints_bwd", "mano_gv", gv2, sum(qg[k] for k in keep), 22, f"{what}: gverts with {null} NULL")
+        # ---- the fused form: bit for bit the two-call form ----
+        fr, fg = mano_full_ref(tables, inp, root_id)
+        o = {"verts": V3(), "jr": G.out(Bs, 21, 3), "vr": V3(), "vc": V3(), "root": G.out(Bs, 3), "saved": V3()}
+        ffwd(**o)
+        for k, want in (("verts", first[0]), ("saved", first[2]), ("jr", two[0]), ("vr", two[1]), ("root", two[2])):
+            _layer_equal("mano_full_fwd", o[k], want, f"{what}: fused {k} against the two-call form")
+        _tail_close("mano_full_fwd", "mano_v", o["vc"], fr["vc"], 16, f"{what}: verts_cam")
+        _tail_close("mano_full_fwd", "mano_v", o["vr"], fr["vr"], 16, f"{what}: verts_rel against the chain")
+        o2 = {"verts": V3(), "jr": G.out(Bs, 21, 3), "vr": V3(), "vc": V3()}
+        ffwd(rxyz=None, **o2)                                             # root_xyz / root / saved NULL: verts_cam = verts_rel
+        _layer_equal("mano_full_fwd", o2["vc"], two[1], f"{what}: verts_cam with root_xyz NULL")
+        _layer_equal("mano_full_fwd", o2["jr"], two[0], f"{what}: joints_rel with root and saved NULL")
+        o3 = {"verts": V3(), "jr": G.out(Bs, 21, 3), "vr": V3()}
+        ffwd(**o3)                                                        # verts_cam NULL
+        _layer_equal("mano_full_fwd", o3["vr"], two[1], f"{what}: verts_rel with verts_cam NULL")
+        fbwd(saved=saved, gp=gp, gb=gb)
+        tot = lambda keys, i: sum(fg[k][i] for k in keys)
+        _tail_close("mano_full_bwd", "mano_g", gp, tot("jvcr", 0), NV, f"{what}: fused gpose")
+        _tail_close("mano_full_bwd", "mano_g", gb, tot("jvcr", 1), NV, f"{what}: fused gbeta")
+        f1 = (gp.clone(), gb.clone())
+        fbwd(saved=saved, gp=gp, gb=gb)
+        _layer_equal("mano_full_bwd", gp, f1[0], f"{what}: fused gpose, second call")
+        _layer_equal("mano_full_bwd", gb, f1[1], f"{what}: fused gbeta, second call")
+        for null, keep in (("gj", "vcr"), ("gv", "jcr"), ("gc", "jvr"), ("gr", "jvc")):
+            gp2, gb2 = G.out(Bs, 48), G.out(Bs, 10)
+            fbwd(saved=saved, gp=gp2, gb=gb2, **{null: None})
+            _tail_close("mano_full_bwd", "mano_g", gp2, tot(keep, 0), NV, f"{what}: fused gpose with {null} NULL")
+            _tail_close("mano_full_bwd", "mano_g", gb2, tot(keep, 1), NV, f"{what}: fused gbeta with {null} NULL")
+        gp3, gb3 = G.out(Bs, 48), G.out(Bs, 10)
+        fbwd(saved=saved, gp=gp3, gb=gb3, ap=d["ap"], ab=d["ab"])          # gpose_add / gbeta_add: one fp32 addition on top
+        _layer_equal("mano_full_bwd", gp3, f1[0].cpu() + inp["ap"], f"{what}: gpose_add")
+        _layer_equal("mano_full_bwd", gb3, f1[1].cpu() + inp["ab"], f"{what}: gbeta_add")
+        G.intact(what)
+        # ---- refused: NULLs ----
+        for e, calls in (("mano_lbs_fwd", (lambda: lfwd(verts=verts, jtr=jtr, hh=None), lambda: lfwd(pose=None, verts=verts), lambda: lfwd(beta=None, verts=verts), lambda: lfwd())),
+                         ("mano_lbs_bwd", (lambda: lbwd(saved=saved, gp=gp, gb=gb, hh=None), lambda: lbwd(pose=None, saved=saved, gp=gp, gb=gb), lambda: lbwd(beta=None, saved=saved, gp=gp, gb=gb),
+                                           lambda: lbwd(gp=gp, gb=gb), lambda: lbwd(saved=saved, gb=gb), lambda: lbwd(saved=saved, gp=gp))),
+                         ("mano_joints_fwd", (lambda: jfwd(verts=verts, jr=jr, hh=None), lambda: jfwd(jr=jr), lambda: jfwd(verts=verts))),
+                         ("mano_joints_bwd", (lambda: jbwd(out=gverts, hh=None), lambda: jbwd())),
+                         ("mano_full_fwd", (lambda: ffwd(verts=verts, jr=jr, vr=vr, hh=None), lambda: ffwd(pose=None, verts=verts, jr=jr, vr=vr), lambda: ffwd(beta=None, verts=verts, jr=jr, vr=vr),
+                                            lambda: ffwd(jr=jr, vr=vr), lambda: ffwd(verts=verts, vr=vr), lambda: ffwd(verts=verts, jr=jr))),
+                         ("mano_full_bwd", (lambda: fbwd(saved=saved, gp=gp, gb=gb, hh=None), lambda: fbwd(pose=None, saved=saved, gp=gp, gb=gb), lambda: fbwd(beta=None, saved=saved, gp=gp, gb=gb),
+                                            lambda: fbwd(gp=gp, gb=gb), lambda: fbwd(saved=saved, gb=gb), lambda: fbwd(saved=saved, gp=gp)))):
+            for k, call in enumerate(calls):
+                _tail_refuses(e, lib, device, call, G, f"{what}: NULL argument {k}")
+        _tail_drain(lib, device)
+        return True
+    finally:
+        lib.mano_destroy(h)
+
+
+# ---- generic linear-blend skinning (csrc/lbs.hip) ---------------------------------------------------------------------------------------
+def lbs_contract_inputs(tabs, B, seed):
+    vt, sd, jr, w, parents = tabs
+    V, J, S = vt.shape[0], w.shape[1], sd.shape[2]
+    gen = torch.Generator().manual_seed(seed)
+    theta = torch.randn(B, J, 3, generator=gen) * 0.6
+    theta[0, min(1, J - 1)] = 0.0                                         # one joint's rotation exactly 0
+    theta[B - 1, min(2, J - 1) if B == 1 else 0] = torch.randn(3, generator=gen) * 1e-7          # and one at 1e-7
+    return {"theta": theta, "beta": torch.randn(B, S, generator=gen), "wv": torch.randn(B, V, 3, generator=gen), "wj": torch.randn(B, J, 3, generator=gen),
+            "prefill": torch.randn(B, S, generator=gen)}
+
+
+def lbs_contract_ref(tabs, inp, dt=torch.float64, drop_vertex=None):
+    """oracle/lbs_oracle.py in `dt`: verts, posed joints, per incoming gradient d/d(theta, beta) ("v", "j"), and what the backward leaves in
+    its scratch: gA[b][j] = sum_v w_vj gverts_v [v_shaped_v; 1]^T (3 x 4, row-major)."""
+    from oracle import lbs_oracle as lo
+    vt, sd, jr, w, parents = tabs
+    th, be = inp["theta"].to(dt).requires_grad_(True), inp["beta"].to(dt).requires_grad_(True)
+    rv, rj = lo.lbs_forward(vt, sd, jr, w, parents, th, be)
+    wv = inp["wv"].to(dt).clone()
+    if drop_vertex is not None:
+        wv[:, drop_vertex] = 0
+    zero = lambda t: torch.zeros_like(t)
+    g = {}
+    for k, term in (("v", (rv * wv).sum()), ("j", (rj * inp["wj"].to(dt)).sum())):
+        gt = torch.autograd.grad(term, (th, be), retain_graph=True, allow_unused=True)
+        g[k] = (gt[0] if gt[0] is not None else zero(th), gt[1] if gt[1] is not None else zero(be))
+    vs = torch.as_tensor(vt, dtype=dt).unsqueeze(0) + torch.einsum("vck,bk->bvc", torch.as_tensor(sd, dtype=dt), be.detach())
+    vs1 = torch.cat([vs, torch.ones_like(vs[..., :1])], 2)
+    gA = torch.einsum("vj,bvr,bvc->bjrc", torch.as_tensor(w, dtype=dt), wv, vs1).reshape(wv.shape[0], -1, 12)
+    return rv.detach(), rj.detach(), g, gA
+
+
+def lbs_contract_case(lib, device, V, J, S, B, seed=0):
+    from hifihr_amd._lib import _fp
+    what = f"lbs {(V, J, S, B)}"
+    tabs = random_lbs_tables(V, J, S, seed)
+    Bs = max(B, 1)
+    inp = lbs_contract_inputs(tabs, Bs, seed)
+    G = Guards(device)
+    d = {k: G.inp(v) for k, v in inp.items()}
+    nn = lambda t: t if S > 0 else None
+    h = lib.lbs_create(*tabs)
+    try:
+        verts, joints, scratch, gth, gbe = G.out(Bs, V, 3), G.out(Bs, J, 3), G.out(Bs, J, 12, fill=0.0), G.out(Bs, J, 3), G.out(Bs, S)
+        fwd = lambda theta=d["theta"], beta=nn(d["beta"]), v=verts, j=joints, hh=h, B_=B: _raw(lib, "hifihr_lbs_fwd", hh, _fp(theta), _fp(beta), B_, _fp(v), _fp(j), None)
+        bwd = lambda theta=d["theta"], beta=nn(d["beta"]), gv=d["wv"], gj=d["wj"], sc=scratch, gt=gth, gb=nn(gbe), hh=h, B_=B: _raw(
+            lib, "hifihr_lbs_bwd", hh, _fp(theta), _fp(beta), _fp(gv), _fp(gj), B_, _fp(sc), _fp(gt), _fp(gb), None)
+        if B < 0:
+            _tail_refuses("lbs_fwd", lib, device, fwd, G, what)
+            _tail_refuses("lbs_bwd", lib, device, bwd, G, what)
+            return False
+        if B == 0:
+            _tail_drain(lib, device)
+            before = [w_.clone() for w_ in G.wholes()]
+            fwd()
+            bwd()
+            _layer_log("lbs_fwd", True)
+            _layer_log("lbs_bwd", True)
+            assert not _tail_drain(lib, device) and all(torch.equal(a, b) for a, b in zip(G.wholes(), before)), f"{what}: B = 0 launched or wrote"
+            return True
+        rv, rj, rg, rA = lbs_contract_ref(tabs, inp)
+        depth = J                                                         # a chain of up to J transforms in front of a vertex
+        fwd()
+        _tail_close("lbs_fwd", "lbs_v", verts, rv, depth, f"{what}: verts")
+        _tail_close("lbs_fwd", "lbs_v", joints, rj, depth, f"{what}: joints")
+        v1 = verts.clone()
+        v2 = G.out(Bs, V, 3)
+        fwd(v=v2, j=None)                                                 # joints NULL
+        _layer_equal("lbs_fwd", v2, v1, f"{what}: verts with joints NULL")
+        for rep in range(2):                                              # float atomics: each run inside the bound
+            scratch.zero_()
+            if S:
+                gbe.copy_(inp["prefill"])                                 # gbeta is ACCUMULATED: onto what the buffer holds
+            bwd()
+            _tail_close("lbs_bwd", "lbs_g", gth, rg["v"][0] + rg["j"][0], V, f"{what}: gtheta (run {rep})")
+            if S:
+                _tail_close("lbs_bwd", "lbs_g", gbe.cpu().double() - inp["prefill"].double(), rg["v"][1] + rg["j"][1], V, f"{what}: gbeta (run {rep})",
+                            float(inp["prefill"].abs().max()))
+            _tail_close("lbs_bwd", "lbs_g", scratch, rA, V, f"{what}: scratch = d(sum gverts verts) / dA (run {rep})")
+        scratch.zero_()
+        gth2, gbe2 = G.out(Bs, J, 3), G.out(Bs, S, fill=0.0)
+        bwd(gj=None, gt=gth2, gb=nn(gbe2))                                # gjoints NULL
+        _tail_close("lbs_bwd", "lbs_g", gth2, rg["v"][0], V, f"{what}: gtheta with gjoints NULL")
+        if S:
+            _tail_close("lbs_bwd", "lbs_g", gbe2, rg["v"][1], V, f"{what}: gbeta with gjoints NULL")
+        G.intact(what)
+        bad_f = [lambda: fwd(hh=None), lambda: fwd(theta=None), lambda: fwd(v=None)] + ([lambda: fwd(beta=None)] if S else [])
+        bad_b = [lambda: bwd(hh=None), lambda: bwd(theta=None), lambda: bwd(gv=None), lambda: bwd(sc=None), lambda: bwd(gt=None)]
+        bad_b += [lambda: bwd(beta=None), lambda: bwd(gb=None)] if S else []
+        for k, call in enumerate(bad_f):
+            _tail_refuses("lbs_fwd", lib, device, call, G, f"{what}: NULL argument {k}")
+        for k, call in enumerate(bad_b):
+            _tail_refuses("lbs_bwd", lib, device, call, G, f"{what}: NULL argument {k}")
+        _tail_drain(lib, device)
+        return True
+    finally:
+        lib.lbs_destroy(h)

@@ -53,3 +53,27 @@ def test_mano_bwd_is_deterministic(lib, synth_tables):
         outs.append((gp.clone(), gb.clone()))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     lib.mano_destroy(h)
+
+
+# ---- the tail contract on the GPU: the emulator's MANO / LBS lists (tests/test_hostsim_tail_contract.py) and a training-sized batch ----------------
+from test_hostsim_tail_contract import LBS_CASES, MANO_CASES, tail_runners  # noqa: E402
+
+_TAIL = tail_runners("cuda")
+MANO_CASES_GPU = [("dense", 33, "0.6", 9)]
+LBS_CASES_GPU = [(5990, 20, 20, 4)]
+
+
+@pytest.fixture(scope="module")
+def tail_tally():
+    yield None
+    kc.layer_contract_report("the MANO / LBS entries on the GPU", ("mano_", "lbs_"))
+
+
+@pytest.mark.parametrize("case", MANO_CASES + MANO_CASES_GPU, ids=lambda g: "-".join(map(str, g)))
+def test_mano_contract_every_entry_on_every_pose_family(lib, tail_tally, case):
+    assert _TAIL["mano"](lib, case) == (case[1] >= 0 and case[3] < 21)
+
+
+@pytest.mark.parametrize("case", LBS_CASES + LBS_CASES_GPU, ids=lambda g: "-".join(map(str, g)))
+def test_lbs_contract_on_every_table_size(lib, tail_tally, case):
+    assert _TAIL["lbs"](lib, case) == (case[3] >= 0)

@@ -425,3 +425,91 @@ def test_linear_contract_on_every_shape(lib, linear_tally, geo):
 @pytest.mark.parametrize("members", LINEAR_GROUPS + LINEAR_GROUPS_GPU, ids=lambda ms: f"{len(ms)}x" + "_".join(map(str, ms[0])))
 def test_linear_group_contract(lib, linear_tally, members):
     assert kc.linear_group_contract_case(lib, "cuda", list(members), seed=len(members)) == (len(members) <= kc.LINEAR_MAX_GROUP and all(m[3] < 2 for m in members))
+
+
+# ---- the tail contract on the GPU: the emulator's lists (tests/test_hostsim_tail_contract.py) and the sizes that wrap a grid cap ----------------
+from test_hostsim_tail_contract import (ADAM_CASES, FREIHAND_GEOMS, GEOM_CASES, HO3D_CASES, JOINT_CASES, LIGHT_CASES, PHOTO_CASES,  # noqa: E402
+                                        PROCRUSTES_CASES, TEXPCA_GEOMS, TOTAL_CASES, tail_runners)
+
+_TAIL = tail_runners("cuda")
+_tid = lambda g: "-".join(str(v).replace(" ", "") for v in g)[:80] if isinstance(g, tuple) else str(g)
+PROCRUSTES_CASES_GPU = [(32, 778, "gt_planar"), (32, 21, "gt_thin_1e-6")]
+HO3D_CASES_GPU = [(480, 640, 224, ((-80, -160, 720, 640), (0, 0, 640, 480), (300, 200, 350, 250)), "ok")]      # the production maximum: 800 -> 224
+ADAM_CASES_GPU = [(2097152 + 5, 0.01, 0.5)]                                # 2048 workgroups x 256 x 4: the grid-stride loop wraps
+TEXPCA_GEOMS_GPU = [(1, 2, 4 * (256 * 4096 + 1), True),                    # wraps the forward's 4096-workgroup cap
+                    (9, 3, 4 * (256 * 512 + 1), False)]                    # the backward's 512-workgroup cap, batch tiles halved
+PHOTO_CASES_GPU = [(9, 256, 256, "binary")]                                # wraps the 512-workgroup cap
+GEOM_CASES_GPU = [(32, 21, 778, 1538, 10, 48, False, "zero_edges")]
+JOINT_CASES_GPU = [(130, False, True, True, "zero_bones", 21)]
+
+
+@pytest.fixture(scope="module")
+def tail_tally():
+    yield None
+    kc.layer_contract_report("the tail entries on the GPU", kc.TAIL_CONTRACT_ENTRIES)
+
+
+@pytest.mark.parametrize("case", PROCRUSTES_CASES + PROCRUSTES_CASES_GPU, ids=_tid)
+def test_procrustes_contract_on_every_point_set(lib, tail_tally, case):
+    assert _TAIL["procrustes"](lib, case) == kc.procrustes_contract_expect(*case[:2])
+
+
+@pytest.mark.parametrize("case", HO3D_CASES + HO3D_CASES_GPU, ids=_tid)
+def test_ho3d_contract_on_every_window(lib, tail_tally, case):
+    assert _TAIL["ho3d"](lib, case) == kc.ho3d_contract_expect(*case)
+
+
+@pytest.mark.parametrize("case", FREIHAND_GEOMS, ids=_tid)
+def test_freihand_contract_every_entry_on_every_map(lib, tail_tally, case):
+    assert _TAIL["freihand"](lib, case)
+
+
+@pytest.mark.parametrize("case", ADAM_CASES + ADAM_CASES_GPU, ids=_tid)
+def test_adam_contract_every_entry_on_one_trajectory(lib, tail_tally, case):
+    assert _TAIL["adam"](lib, case)
+
+
+@pytest.mark.parametrize("case", TEXPCA_GEOMS + TEXPCA_GEOMS_GPU, ids=_tid)
+def test_texture_pca_contract_on_every_geometry(lib, tail_tally, case):
+    assert _TAIL["texpca"](lib, case) == kc.texpca_contract_expect(*case[:3])
+
+
+@pytest.mark.parametrize("case", GEOM_CASES + GEOM_CASES_GPU, ids=_tid)
+def test_geometry_terms_contract_on_every_geometry(lib, tail_tally, case):
+    assert _TAIL["geom"](lib, case) == kc.geom_contract_expect(*case[:6])
+
+
+@pytest.mark.parametrize("case", JOINT_CASES + JOINT_CASES_GPU, ids=_tid)
+def test_joint_terms_contract_on_every_batch(lib, tail_tally, case):
+    assert _TAIL["joint"](lib, case) == kc.joint_contract_expect(case[0], case[5], case[2], case[3])
+
+
+@pytest.mark.parametrize("case", PHOTO_CASES + PHOTO_CASES_GPU, ids=_tid)
+def test_photometric_terms_contract_on_every_image_size(lib, tail_tally, case):
+    assert _TAIL["photo"](lib, case) == kc.photo_contract_expect(*case[:3])
+
+
+@pytest.mark.parametrize("case", TOTAL_CASES, ids=_tid)
+def test_loss_total_contract_on_every_part_list(lib, tail_tally, case):
+    _TAIL["total"](lib, case)
+
+
+@pytest.mark.parametrize("case", LIGHT_CASES, ids=_tid)
+def test_light_split_contract_on_every_batch(lib, tail_tally, case):
+    assert _TAIL["light"](lib, case) == (case > 0)
+
+
+def test_ho3d_device_cache_refuses_a_window_the_kernel_would_zero():
+    """hifihr_ho3d_batch cannot refuse a crop box (the boxes live in device memory): HO3DDeviceCache.batch raises on the host for a window
+    above HIFIHR_HO3D_MAX_WINDOW or an empty one, and takes the largest window ho3d_crop_windows can make (640 / 0.8 = 800 pixels)."""
+    from hifihr_amd.data import HO3D_MAX_WINDOW, HO3DDeviceCache
+    assert HO3D_MAX_WINDOW == kc.HO3D_MAX_WINDOW
+    rng = np.random.default_rng(0)
+    n = 2
+    K = np.tile(np.array([[600.0, 0, 320], [0, 600.0, 240], [0, 0, 1]], np.float32), (n, 1, 1))
+    xyz = np.tile(np.array([0.0, 0.0, 0.6], np.float32), (n, 21, 1)) + rng.normal(0, 0.3, (n, 21, 3)).astype(np.float32) * np.array([1, 1, 0.01], np.float32)
+    cache = HO3DDeviceCache(rng.integers(0, 256, (n, 480, 640, 3), dtype=np.uint8), rng.integers(0, 2, (n, 480, 640), dtype=np.uint8) * 255, K, xyz, inp_res=64)
+    out = cache.batch([0, 1], center_noise=np.zeros((2, 2), np.float32), scale_noise=np.full(2, 0.8, np.float32))          # the smallest scale the reference draws
+    assert out["img_crop"].shape == (2, 3, 64, 64) and bool(torch.isfinite(out["img_crop"]).all())
+    with pytest.raises(ValueError, match="800"):
+        cache.batch([0, 1], center_noise=np.zeros((2, 2), np.float32), scale_noise=np.full(2, 0.5, np.float32))

@@ -260,7 +260,8 @@ def test_no_bound_is_looser_than_the_family_case_it_replaces():
               "mm_dp": 1e-4, "dw_fwd": 2e-5, "dw_pre": 3e-5, "dw_dgrad": 2e-5, "dw_wgrad": 1e-4, "dw_wgrad_pre": 2e-4, "se_pool": 1e-5,
               "se_y": 3e-5, "se_mlp": 2e-5, "se_grad": 3e-4, "ssim_val": 2e-6, "ssim_part": 2e-6, "ssim_map": 2.1e-3, "ssim_grad": 2e-4}      # (no older case asserts on the SSIM maps)
     # (the kinds of the GEMM contract live in the same table: tests/test_hostsim_gemm_contract.py holds them to their own older cases)
-    assert set(legacy) == set(kc.LAYER_CONTRACT_C) - set(kc.GEMM_CONTRACT_KINDS) - set(kc.WINO_CONTRACT_KINDS)
+    # (so do the kinds of the tail contract: tests/test_hostsim_tail_contract.py holds them to kc.TAIL_LEGACY)
+    assert set(legacy) == set(kc.LAYER_CONTRACT_C) - set(kc.GEMM_CONTRACT_KINDS) - set(kc.WINO_CONTRACT_KINDS) - set(kc.TAIL_CONTRACT_KINDS)
     for kind in legacy:
         c, cap = kc.LAYER_CONTRACT_C[kind]
         assert 0 < c <= cap <= legacy[kind], kind
@@ -289,7 +290,7 @@ def test_the_lists_reach_every_instantiation_and_both_answers(hostsim_lib):
         assert {kc.se_contract_expect(*g)[e] for g in SE_GEOMS} == {True, False}, e
     assert {bool(_DONE[("drop", g)]) for g in DROP_GEOMS} == {True, False}
     for e, row in kc.LAYER_CONTRACT_LOG.items():
-        if e.startswith(kc.GEMM_CONTRACT_ENTRIES):          # (the GEMM contract logs into the same table: tests/test_hostsim_gemm_contract.py asks this of its own entries)
+        if e.startswith(kc.GEMM_CONTRACT_ENTRIES) or e in kc.TAIL_CONTRACT_ENTRIES:          # (the GEMM and tail contracts log into the same table and ask this of their own entries)
             continue
         assert row[0] > 0 and (row[1] > 0 or e in ("ssim_bwd", "ssim_bwd_scaled")), f"{e}: accepted {row[0]}, refused {row[1]} calls"
     # the classes the lists exist for

@@ -145,8 +145,18 @@ def gemm_contract():
         kc.linear_group_contract_case(lib, "cpu", list(ms), seed=len(ms))
 
 
+def tail_contract():
+    """Every entry of the tail contract -- Procrustes, the HO-3D and FreiHAND data paths, Adam, texture PCA, the fused losses, MANO and generic
+    skinning -- on the lists of tests/test_hostsim_tail_contract.py (refused calls included)."""
+    import test_hostsim_tail_contract as tl
+    runners = tl.tail_runners("cpu")
+    for family, cases in tl.LISTS.items():
+        for c in cases:
+            runners[family](lib, c)
+
+
 GROUPS = {"conv": conv, "render": render, "wino": wino, "round5": round5, "round6": round6, "contract": contract, "lpips": lpips,
-          "gemm_contract": gemm_contract}
+          "gemm_contract": gemm_contract, "tail_contract": tail_contract}
 for g in (sys.argv[1:] or list(GROUPS)):
     GROUPS[g]()
     print(f"asan: {g} clean", flush=True)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Where the constants of tests/kernel_cases.py LAYER_CONTRACT_C / LAYER_CONTRACT_FLOOR come from: the layer contract's float64 references run
-in float32 -- plain fp32 PyTorch on the CPU -- over the emulator geometry lists of tests/test_hostsim_layer_contract.py, compared with the same
+in float32 -- plain fp32 PyTorch on the CPU -- over the emulator geometry lists of tests/test_hostsim_layer_contract.py (and, for the kinds of the GEMM and tail
+contracts, of tests/test_hostsim_gemm_contract.py / tests/test_hostsim_tail_contract.py), compared with the same
 references in float64.  Per kind it prints the worst  err / (sqrt(L) max|ref| + cond)  (c is 4 times that) and, over the comparisons whose
 reference is zero to rounding, the worst absolute error (the floor is 4 times that).  No kernel runs.
 
@@ -35,6 +36,100 @@ def both(ref64, ref32, names, where):
     for n in names:
         q = ref64[n]
         note(q[0], ref32[n][2], q[2], q[1], q[3] if len(q) > 3 else 0.0, f"{where} {n}")
+
+
+def tail():
+    """The kinds of the tail contract (tests/test_hostsim_tail_contract.py): every float64 reference of kernel_cases' "The tail contract" run
+    in float32 on the same lists; and the Procrustes floor, the largest difference between two float64 routes to the same err_sum."""
+    import numpy as np
+    import test_hostsim_tail_contract as tl
+    q = lambda kind, a, b, L, cond=0.0, where="": note(kind, a, b, L, cond, where)
+    for n, wd, gs in tl.ADAM_CASES:
+        inp = kc.adam_contract_inputs(n, n)
+        zero = torch.zeros(n)
+        for step, m, v in ((1, zero, zero), (2, inp["m"], inp["v"]), (3, inp["m"], inp["v"]), (1000, inp["m"], inp["v"])):
+            r64, r32 = (kc.adam_contract_ref(inp["p"], inp["g"][0], m, v, step, wd, gs, dt=dt) for dt in (F64, F32))
+            for kind, a, b in zip(("adam_p", "adam_m", "adam_v"), r32, r64):
+                q(kind, a, b, 1, where=f"adam {(n, wd, gs)} step {step}")
+    for g in tl.TEXPCA_GEOMS:
+        if kc.texpca_contract_expect(*g[:3]):
+            inp = kc.texpca_contract_inputs(*g[:3], sum(g[:3]))
+            both(kc.texpca_contract_ref(inp, g[3]), kc.texpca_contract_ref(inp, g[3], dt=F32), ("tex", "dcoef"), f"texpca {g}")
+    for g in tl.GEOM_CASES:
+        if kc.geom_contract_expect(*g[:6]):
+            inp = kc.geom_contract_inputs(*g[:6], g[7], sum(g[:6]))
+            (o64, g64), (o32, g32) = kc.geom_contract_ref(inp, g[6]), kc.geom_contract_ref(inp, g[6], dt=F32)
+            for k in range(5):
+                q("geom_out", o32[k][2], o64[k][2], o64[k][1], where=f"geom {g} out[{k}]")
+            for n_ in g64:
+                q("geom_grad", g32[n_][2], g64[n_][2], g64[n_][1], where=f"geom {g} {n_}")
+    for g in tl.JOINT_CASES:
+        if kc.joint_contract_expect(g[0], g[5], g[2], g[3]):
+            inp = kc.joint_contract_inputs(g[0], g[4], g[0])
+            (o64, g64), (o32, g32) = kc.joint_contract_ref(inp, g[1], g[2], g[3]), kc.joint_contract_ref(inp, g[1], g[2], g[3], dt=F32)
+            for k, L in enumerate((g[0] * 42, g[0] * 40, g[0] * 60)):
+                q("joint_out", o32[k], o64[k], L, where=f"joint {g} out[{k}]")
+            for n_ in g64:
+                for b in range(g[0]):                                       # (per sample, as the case compares)
+                    q("joint_grad", g32[n_][b], g64[n_][b], 6, where=f"joint {g} {n_} sample {b}")
+    for g in tl.PHOTO_CASES:
+        if kc.photo_contract_expect(*g[:3]) and g[3] != "nan":
+            inp = kc.photo_contract_inputs(*g[:3], g[3], sum(g[:3]))
+            r64, r32 = kc.photo_contract_ref(inp), kc.photo_contract_ref(inp, dt=F32)
+            both(r64, r32, ("re_m", "tex", "mrgb", "sil", "dm"), f"photo {g}")
+            out32 = torch.cat([r32[k][2] for k in ("tex", "mrgb", "sil", "dm")])          # the backward starts from the fp32 forward's tensors
+            b64 = kc.photo_contract_bwd_ref(inp, r32["re_m"][2], r32["mk"], out32, True, True)
+            b32 = kc.photo_contract_bwd_ref(inp, r32["re_m"][2], r32["mk"], out32, True, True, dt=F32)
+            q("photo_grad", b32[2], b64[2], 1, where=f"photo {g} grad")
+    for counts, lengths, mode in tl.TOTAL_CASES:
+        if mode == "ok" and 1 <= len(counts) <= 4 and all(0 <= c <= 64 for c in counts) and sum(counts):
+            gen = torch.Generator().manual_seed(len(counts))
+            parts = [torch.randn(max(c, 1), generator=gen)[:c] for c in counts]
+            s32 = torch.zeros(())
+            for p in parts:
+                for x in p:
+                    s32 = s32 + x
+            q("total", s32.reshape(1), sum(p.double().sum() for p in parts).reshape(1), sum(counts), sum(float(p.abs().sum()) for p in parts), f"total {counts}")
+    for name, B, family, root_id in tl.MANO_CASES:
+        if B > 0 and root_id < 21:
+            t, inp = tl.tail_tables(name), kc.mano_contract_inputs(B, family, 5 + B)
+            (v64, j64, g64), (v32, j32, g32) = kc.mano_layer_ref(t, inp), kc.mano_layer_ref(t, inp, dt=F32)
+            w = f"mano {(name, B, family, root_id)}"
+            q("mano_v", v32, v64, 16, where=w + " verts")
+            q("mano_v", j32, j64, 16, where=w + " jtr")
+            for i in (0, 1):
+                q("mano_g", g32["v"][i] + g32["j"][i], g64["v"][i] + g64["j"][i], 778, where=w + " layer grad")
+            a64, a32 = kc.mano_joints_ref(t, v32, inp, root_id), kc.mano_joints_ref(t, v32, inp, root_id, dt=F32)
+            for i in range(3):
+                q("mano_j", a32[i], a64[i], 778, where=w + " joints")
+            q("mano_gv", sum(a32[3].values()), sum(a64[3].values()), 22, where=w + " gverts")
+            (f64_, fg64), (f32_, fg32) = kc.mano_full_ref(t, inp, root_id), kc.mano_full_ref(t, inp, root_id, dt=F32)
+            q("mano_v", f32_["vc"], f64_["vc"], 16, where=w + " verts_cam")
+            for i in (0, 1):
+                q("mano_g", sum(fg32[k][i] for k in fg32), sum(fg64[k][i] for k in fg64), 778, where=w + " fused grad")
+    for V, J, S, B in tl.LBS_CASES:
+        if B > 0:
+            tabs = kc.random_lbs_tables(V, J, S, V + J + S + B)
+            inp = kc.lbs_contract_inputs(tabs, B, V + J + S + B)
+            r64, r32 = kc.lbs_contract_ref(tabs, inp), kc.lbs_contract_ref(tabs, inp, dt=F32)
+            w = f"lbs {(V, J, S, B)}"
+            q("lbs_v", r32[0], r64[0], J, where=w + " verts")
+            q("lbs_v", r32[1], r64[1], J, where=w + " joints")
+            for i in (0, 1):
+                if r64[2]["v"][i].numel():
+                    q("lbs_g", r32[2]["v"][i] + r32[2]["j"][i], r64[2]["v"][i] + r64[2]["j"][i], V, where=w + " grad")
+            q("lbs_g", r32[3], r64[3], V, where=w + " scratch")
+    worst, rel, at = 0.0, 0.0, ""
+    for B, N, family in tl.PROCRUSTES_CASES:
+        if kc.procrustes_contract_expect(B, N):
+            pred, gt = kc.procrustes_contract_inputs(family, B, N, N + len(family))
+            a, b = kc.procrustes_contract_ref(pred, gt)["err_sum"], kc.procrustes_contract_ref(pred, gt, route="eigen")["err_sum"]
+            d = float(np.abs(a - b).max())
+            if d > worst:
+                worst, at = d, f"{(B, N, family)} (err_sum {float(a.max()):.3e})"
+            rel = max(rel, float((np.abs(a - b) / (N * np.abs(gt.double().numpy()).max((1, 2)))).max()))
+    print(f"Procrustes: two float64 routes to err_sum differ by at most {worst:.3e} at {at}; x 4 = {4 * worst:.2e} (table floor {kc.PROCRUSTES_FLOOR:.2e});"
+          f" relative to N max|gt|: {rel:.3e}, x 4 = {4 * rel:.2e} (table {kc.PROCRUSTES_FLOOR_REL:.2e})")
 
 
 def main():
@@ -144,6 +239,7 @@ def main():
                 r = kc.LAYER_CONTRACT_LOG[e][2]
                 if r > RATIO.get(kind, (0.0, ""))[0]:
                     RATIO[kind] = (r, f"wino {g} (fp32 product, emulator)")
+    tail()
     print(f"{'kind':14s} {'fp32 torch ratio':>17s} {'x 4':>10s} {'table c':>10s} {'cap':>8s}   worst at")
     for kind, (c, cap) in kc.LAYER_CONTRACT_C.items():
         r, where = RATIO.get(kind, (0.0, "-"))
