@@ -147,15 +147,8 @@ class HifihrLib:
         c.hifihr_sil_post.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, _c_float_p, _c_float_p, c_void_p]
         c.hifihr_linear_fwd.argtypes = [_c_float_p] * 3 + [c_int] * 4 + [_c_float_p] * 2 + [c_float, c_float] + [_c_float_p] * 6 + [c_void_p]
         c.hifihr_linear_bwd.argtypes = [_c_float_p] * 4 + [c_int] * 4 + [_c_float_p] * 10 + [c_void_p]
-        c.hifihr_wino_gemm_workspace_bytes.argtypes = [c_int] * 5
-        c.hifihr_wino_gemm_workspace_bytes.restype = c_size_t
-        c.hifihr_wino_weight_transform.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_void_p]
-        c.hifihr_wino_input_transform.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_int, c_void_p]
-        c.hifihr_wino_gemm.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]
-        c.hifihr_wino_output_transform.argtypes = [_c_float_p] * 3 + [c_int] * 4 + [c_void_p]
         c.hifihr_linear_fwd_group.argtypes = [POINTER(_LinearDesc), c_int, c_void_p]
         c.hifihr_linear_bwd_group.argtypes = [POINTER(_LinearDesc), c_int, c_void_p]
-        c.hifihr_wino_input_dy_transform.argtypes = [_c_float_p] * 3 + [c_int] * 4 + [c_void_p]
         c.hifihr_conv2d_bwd_data_pre.argtypes = [_c_float_p] * 3 + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]
         c.hifihr_conv2d_bwd_data_pre_res.argtypes = [_c_float_p] * 4 + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]
         c.hifihr_conv2d_bwd_data_pre_plus1x1.argtypes = [_c_float_p] * 5 + [c_int] * 9 + [c_void_p]
@@ -179,8 +172,6 @@ class HifihrLib:
         c.hifihr_loss_total_fwd.argtypes = [POINTER(_c_float_p), POINTER(c_int), c_int, _c_float_p, c_void_p]
         c.hifihr_loss_total_bwd.argtypes = [_c_float_p, POINTER(_c_float_p), POINTER(c_int), POINTER(c_int), c_int, c_void_p]
         c.hifihr_procrustes_error.argtypes = [_c_float_p, _c_float_p, c_int, c_int, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_wino_output_transform_act.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino_dy_transform.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_int, c_void_p]
         c.hifihr_wino_wgrad_gemm.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
         c.hifihr_wino_dw_transform.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_void_p]
         c.hifihr_weight_transpose.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_void_p]
@@ -197,13 +188,13 @@ class HifihrLib:
         c.hifihr_comm_broadcast_f32.argtypes = [c_void_p, _c_float_p, c_size_t, c_int, c_void_p]
         c.hifihr_comm_destroy.argtypes = [c_void_p]
         c.hifihr_wino_tile.argtypes = [c_int] * 5
-        c.hifihr_wino_gemm_workspace_bytes_m.argtypes = [c_int] * 6
-        c.hifihr_wino_gemm_workspace_bytes_m.restype = c_size_t
-        c.hifihr_wino_weight_transform_m.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_int, c_void_p]
-        c.hifihr_wino_input_transform_m.argtypes = [_c_float_p, _c_float_p] + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino_gemm_m.argtypes = [_c_float_p] * 3 + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]
-        c.hifihr_wino_output_transform_m.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino_output_transform_act_m.argtypes = [_c_float_p] * 3 + [c_int] * 6 + [c_void_p]
+        c.hifihr_wino_gemm_workspace_bytes.argtypes = [c_int] * 6
+        c.hifihr_wino_gemm_workspace_bytes.restype = c_size_t
+        c.hifihr_wino_weight_transform.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_int, c_void_p]
+        c.hifihr_wino_input_transform.argtypes = [_c_float_p, _c_float_p] + [c_int] * 5 + [c_void_p]
+        c.hifihr_wino_gemm.argtypes = [_c_float_p] * 3 + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]
+        c.hifihr_wino_output_transform.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
+        c.hifihr_wino_output_transform_act.argtypes = [_c_float_p] * 3 + [c_int] * 6 + [c_void_p]
         c.hifihr_conv3x3_c64_wino_supported.argtypes = [c_int] * 5
         c.hifihr_conv3x3_c64_wino.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
         c.hifihr_conv3x3_c64_wino_res.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
@@ -218,19 +209,15 @@ class HifihrLib:
         c.hifihr_bn_bwd_apply.argtypes = [_c_float_p] * 5 + [c_long, c_int] + [_c_float_p] * 4 + [c_void_p]
         c.hifihr_joint_terms_fwd.argtypes = [_c_float_p] * 4 + [c_int] * 3 + [POINTER(c_float), _c_float_p, c_void_p]
         c.hifihr_joint_terms_bwd.argtypes = [_c_float_p] * 4 + [c_int] * 3 + [POINTER(c_float)] + [_c_float_p] * 3 + [c_void_p]
-        c.hifihr_wino_dy_transform_m.argtypes = [_c_float_p] * 2 + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino_input_dy_transform_m.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino_wgrad_parts_m.argtypes = [c_int] * 6
-        c.hifihr_wino_wgrad_gemm_parts_m.argtypes = [_c_float_p] * 3 + [c_int] * 7 + [c_void_p]
-        c.hifihr_wino_dw_transform_parts_m.argtypes = [_c_float_p, c_int, _c_float_p, c_int, c_int, c_int, c_void_p]
-        c.hifihr_bgemm_describe.argtypes = [c_int] * 4 + [ctypes.c_char_p, c_int]
-        c.hifihr_bgemm_describe_batch.argtypes = [c_int] * 5 + [ctypes.c_char_p, c_int]
+        c.hifihr_wino_dy_transform.argtypes = [_c_float_p] * 2 + [c_int] * 5 + [c_void_p]
+        c.hifihr_wino_input_dy_transform.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
+        c.hifihr_wino_wgrad_parts.argtypes = [c_int] * 6
+        c.hifihr_wino_wgrad_gemm_parts.argtypes = [_c_float_p] * 3 + [c_int] * 7 + [c_void_p]
+        c.hifihr_wino_dw_transform_parts.argtypes = [_c_float_p, c_int, _c_float_p, c_int, c_int, c_int, c_void_p]
+        c.hifihr_bgemm_describe.argtypes = [c_int] * 5 + [ctypes.c_char_p, c_int]
         c.hifihr_conv2d_describe.argtypes = [c_int] * 10 + [ctypes.c_char_p, c_int]
         c.hifihr_bgemm_tn_parts.argtypes = [c_int] * 4
         c.hifihr_bgemm_tn.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino_wgrad_parts.argtypes = [c_int] * 5
-        c.hifihr_wino_wgrad_gemm_parts.argtypes = [_c_float_p] * 3 + [c_int] * 6 + [c_void_p]
-        c.hifihr_wino_dw_transform_parts.argtypes = [_c_float_p, c_int, _c_float_p, c_int, c_int, c_void_p]
         c.hifihr_wino4_dw_transform_multi.argtypes = [c_void_p, c_int, c_void_p]
         c.hifihr_se_pool.argtypes = [_c_float_p, c_int, c_int, c_int, _c_float_p, c_void_p]
         c.hifihr_se_scale.argtypes = [_c_float_p, _c_float_p, _c_float_p, c_float, c_int, c_int, c_int, _c_float_p, c_void_p]
@@ -252,7 +239,7 @@ class HifihrLib:
         c.hifihr_maxpool2d_fwd_flat.argtypes = [_c_float_p] + [c_int] * 7 + [_c_float_p, c_void_p, c_void_p]
         c.hifihr_maxpool2d_bwd_flat.argtypes = [_c_float_p, c_void_p] + [c_int] * 7 + [_c_float_p, c_void_p]
         c.hifihr_maxpool2d_bwd_relu.argtypes = [_c_float_p, c_void_p, _c_float_p] + [c_int] * 7 + [_c_float_p, c_void_p]
-        c.hifihr_wino_output_transform_mask_m.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
+        c.hifihr_wino_output_transform_mask.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
         c.hifihr_adam_step.argtypes = [_c_float_p, _c_float_p, _c_float_p, _c_float_p, c_size_t, c_float, c_float, c_float,
                                        c_float, c_float, c_float, c_int, c_void_p]
         c.hifihr_adam_state_bytes.restype = c_size_t
@@ -528,7 +515,7 @@ class HifihrLib:
         return int(self.c.hifihr_wino_tile(N, H, W, C, K))
 
     def wino_gemm_workspace_bytes(self, N, H, W, C, K, m=2):
-        return int(self.c.hifihr_wino_gemm_workspace_bytes_m(N, H, W, C, K, m))
+        return int(self.c.hifihr_wino_gemm_workspace_bytes(N, H, W, C, K, m))
 
     def wino4_bwd_gemm_pair_supported(self, N, H, W, C, K):
         key = (N, H, W, C, K)
@@ -543,10 +530,10 @@ class HifihrLib:
                                                      _stream_of(V2)), "hifihr_wino4_bwd_gemm_pair")
 
     def wino_weight_transform(self, w, U, K, C, flip, m=2):
-        self.check(self.c.hifihr_wino_weight_transform_m(_fp(w), _fp(U), K, C, int(flip), m, _stream_of(w)), "hifihr_wino_weight_transform")
+        self.check(self.c.hifihr_wino_weight_transform(_fp(w), _fp(U), K, C, int(flip), m, _stream_of(w)), "hifihr_wino_weight_transform")
 
     def wino_input_transform(self, x, V, N, H, W, C, m=2):
-        self.check(self.c.hifihr_wino_input_transform_m(_fp(x), _fp(V), N, H, W, C, m, _stream_of(x)), "hifihr_wino_input_transform")
+        self.check(self.c.hifihr_wino_input_transform(_fp(x), _fp(V), N, H, W, C, m, _stream_of(x)), "hifihr_wino_input_transform")
 
     def zero_page_ready(self, device=None):
         """The 256 zero bytes the halo / Winograd kernels read out-of-image pixels from exist on `device` (allocated at the first call
@@ -624,10 +611,10 @@ class HifihrLib:
                                               _fp(dgamma_acc), _fp(dbeta_acc), _stream_of(g)), "hifihr_bn_bwd_apply")
 
     def wino_gemm(self, V, U, M, N, H, W, C, K, ws=None, m=2):
-        self.check(self.c.hifihr_wino_gemm_m(_fp(V), _fp(U), _fp(M), N, H, W, C, K, m, *self._ws(ws), _stream_of(V)), "hifihr_wino_gemm")
+        self.check(self.c.hifihr_wino_gemm(_fp(V), _fp(U), _fp(M), N, H, W, C, K, m, *self._ws(ws), _stream_of(V)), "hifihr_wino_gemm")
 
     def wino_input_dy_transform(self, dy, V, Yt, N, H, W, K, m=2):
-        self.check(self.c.hifihr_wino_input_dy_transform_m(_fp(dy), _fp(V), _fp(Yt), N, H, W, K, m, _stream_of(dy)), "hifihr_wino_input_dy_transform")
+        self.check(self.c.hifihr_wino_input_dy_transform(_fp(dy), _fp(V), _fp(Yt), N, H, W, K, m, _stream_of(dy)), "hifihr_wino_input_dy_transform")
 
     def conv2d_bwd_data_pre(self, dy, wt, dx, N, H, W, C, K, R, S, stride, pad, ws=None):
         wsp, wsb = self._ws(ws)
@@ -721,18 +708,18 @@ class HifihrLib:
     def wino_output_transform(self, M, y, stats, N, H, W, K, bias=None, act=0, m=2, mask=None):
         if mask is not None:
             assert stats is None and bias is None and not act and m == 4
-            self.check(self.c.hifihr_wino_output_transform_mask_m(_fp(M), _fp(y), _fp(mask), N, H, W, K, m, _stream_of(M)),
-                       "hifihr_wino_output_transform_mask_m")
+            self.check(self.c.hifihr_wino_output_transform_mask(_fp(M), _fp(y), _fp(mask), N, H, W, K, m, _stream_of(M)),
+                       "hifihr_wino_output_transform_mask")
             return
         if bias is not None or act:
             assert stats is None
-            self.check(self.c.hifihr_wino_output_transform_act_m(_fp(M), _fp(y), _fp(bias), act, N, H, W, K, m, _stream_of(M)),
+            self.check(self.c.hifihr_wino_output_transform_act(_fp(M), _fp(y), _fp(bias), act, N, H, W, K, m, _stream_of(M)),
                        "hifihr_wino_output_transform_act")
             return
-        self.check(self.c.hifihr_wino_output_transform_m(_fp(M), _fp(y), _fp(stats), N, H, W, K, m, _stream_of(M)), "hifihr_wino_output_transform")
+        self.check(self.c.hifihr_wino_output_transform(_fp(M), _fp(y), _fp(stats), N, H, W, K, m, _stream_of(M)), "hifihr_wino_output_transform")
 
     def wino_dy_transform(self, dy, Y, N, H, W, K, m=2):
-        self.check(self.c.hifihr_wino_dy_transform_m(_fp(dy), _fp(Y), N, H, W, K, m, _stream_of(dy)), "hifihr_wino_dy_transform")
+        self.check(self.c.hifihr_wino_dy_transform(_fp(dy), _fp(Y), N, H, W, K, m, _stream_of(dy)), "hifihr_wino_dy_transform")
 
     def wino_wgrad_gemm(self, V, Y, dU_zeroed, N, H, W, C, K):
         self.check(self.c.hifihr_wino_wgrad_gemm(_fp(V), _fp(Y), _fp(dU_zeroed), N, H, W, C, K, _stream_of(V)), "hifihr_wino_wgrad_gemm")
@@ -779,7 +766,7 @@ class HifihrLib:
 
     def bgemm_describe(self, tn, M, N, K, batch=16):
         buf = ctypes.create_string_buffer(96)
-        self.check(self.c.hifihr_bgemm_describe_batch(int(bool(tn)), M, N, K, batch, buf, 96), "hifihr_bgemm_describe_batch")
+        self.check(self.c.hifihr_bgemm_describe(int(bool(tn)), M, N, K, batch, buf, 96), "hifihr_bgemm_describe")
         return buf.value.decode()
 
     def bgemm_tn_parts(self, M, N, T, batch):
@@ -789,10 +776,10 @@ class HifihrLib:
         self.check(self.c.hifihr_bgemm_tn(_fp(A), _fp(B), _fp(Cparts), M, N, T, batch, parts, _stream_of(A)), "hifihr_bgemm_tn")
 
     def wino_wgrad_parts(self, N, H, W, C, K, m=2):
-        return int(self.c.hifihr_wino_wgrad_parts_m(N, H, W, C, K, m))
+        return int(self.c.hifihr_wino_wgrad_parts(N, H, W, C, K, m))
 
     def wino_wgrad_gemm_parts(self, V, Y, dU_parts, N, H, W, C, K, parts, m=2):
-        self.check(self.c.hifihr_wino_wgrad_gemm_parts_m(_fp(V), _fp(Y), _fp(dU_parts), N, H, W, C, K, parts, m, _stream_of(V)),
+        self.check(self.c.hifihr_wino_wgrad_gemm_parts(_fp(V), _fp(Y), _fp(dU_parts), N, H, W, C, K, parts, m, _stream_of(V)),
                    "hifihr_wino_wgrad_gemm_parts")
 
     def wino4_dw_transform_multi(self, jobs):
@@ -806,7 +793,7 @@ class HifihrLib:
                    "hifihr_wino4_dw_transform_multi")
 
     def wino_dw_transform_parts(self, dU_parts, parts, dw_acc, K, C, m=2):
-        self.check(self.c.hifihr_wino_dw_transform_parts_m(_fp(dU_parts), parts, _fp(dw_acc), K, C, m, _stream_of(dU_parts)),
+        self.check(self.c.hifihr_wino_dw_transform_parts(_fp(dU_parts), parts, _fp(dw_acc), K, C, m, _stream_of(dU_parts)),
                    "hifihr_wino_dw_transform_parts")
 
     def weight_transpose(self, w, wt, K, RS, C):

@@ -72,7 +72,7 @@ int upload_i(DevBuf& b, const std::vector<int>& h) {
 
 extern "C" {
 
-int hifihr_version(void) { return 1; }
+int hifihr_version(void) { return 2; }
 const char* hifihr_last_error(void) { return g_err; }
 
 int hifihr_device_count(void) {
@@ -440,36 +440,42 @@ static int conv_dims_ok(int N, int H, int W, int C, int K, int R, int S, int str
          (W + 2 * pad - S) >= 0;
 }
 
+// forward geometry of a convolution x[N][H][W][C] -> y[N][OH][OW][K], and the geometry of its backward-data (dy[N][OH][OW][K] -> dx[N][H][W][C])
+static hifihr::ConvGeom conv_geom(int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
+  return hifihr::ConvGeom{N, H, W, C, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, K, R, S, stride, pad, 0};
+}
+static hifihr::ConvGeom conv_dgrad_geom(int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
+  const hifihr::ConvGeom f = conv_geom(N, H, W, C, K, R, S, stride, pad);
+  return hifihr::ConvGeom{N, f.OH, f.OW, K, H, W, C, R, S, stride, pad, 1};
+}
+
 size_t hifihr_conv2d_workspace_bytes(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int bwd_data) {
   if (!conv_dims_ok(N, H, W, C, K, R, S, stride, pad)) return 0;
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
-  const hifihr::ConvGeom f{N, H, W, C, OH, OW, K, R, S, stride, pad, 0};
-  const hifihr::ConvGeom b{N, OH, OW, K, H, W, C, R, S, stride, pad, 1};
-  return hifihr::conv_sk_workspace_bytes(bwd_data ? b : f);
+  return hifihr::conv_sk_workspace_bytes(bwd_data ? conv_dgrad_geom(N, H, W, C, K, R, S, stride, pad) : conv_geom(N, H, W, C, K, R, S, stride, pad));
 }
 
 int hifihr_conv2d_fwd(const float* x, const float* w, const float* bias, int act, float* y, int N, int H, int W, int C, int K, int R,
                       int S, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
   if (!x || !w || !y || !conv_dims_ok(N, H, W, C, K, R, S, stride, pad) || C % 4 || act < 0 || act > 1)
     return fail(HIFIHR_EINVAL, "hifihr_conv2d_fwd: bad argument (C must be a multiple of 4; act 0/1)");
-  hifihr::ConvGeom g{N, H, W, C, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, K, R, S, stride, pad, 0, act};
+  hifihr::ConvGeom g = conv_geom(N, H, W, C, K, R, S, stride, pad);
+  g.relu = act;
   HIP_TRY(hifihr::launch_conv_igemm(g, x, w, bias, y, nullptr, ws, ws_bytes, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 
 int hifihr_conv2d_describe(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dgrad, char* out, int cap) {
   if (!out || cap < 24 || !conv_dims_ok(N, H, W, C, K, R, S, stride, pad)) return fail(HIFIHR_EINVAL, "hifihr_conv2d_describe: bad argument");
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
-  if (dgrad == 1) hifihr::conv_describe(hifihr::ConvGeom{N, OH, OW, K, H, W, C, R, S, stride, pad, 1}, out, cap);
-  else if (dgrad == 2) hifihr::conv_wgrad_describe(hifihr::ConvGeom{N, H, W, C, OH, OW, K, R, S, stride, pad, 0}, out, cap);
-  else hifihr::conv_describe(hifihr::ConvGeom{N, H, W, C, OH, OW, K, R, S, stride, pad, 0}, out, cap);
+  if (dgrad == 1) hifihr::conv_describe(conv_dgrad_geom(N, H, W, C, K, R, S, stride, pad), out, cap);
+  else if (dgrad == 2) hifihr::conv_wgrad_describe(conv_geom(N, H, W, C, K, R, S, stride, pad), out, cap);
+  else hifihr::conv_describe(conv_geom(N, H, W, C, K, R, S, stride, pad), out, cap);
   return HIFIHR_OK;
 }
 
 static bool pair_geoms(int N, int H, int W, int C, int stride, int K1, int R1, int pad1, int K2, int R2, int pad2, hifihr::ConvGeom* g1, hifihr::ConvGeom* g2) {
   if (!conv_dims_ok(N, H, W, C, K1, R1, R1, stride, pad1) || !conv_dims_ok(N, H, W, C, K2, R2, R2, stride, pad2) || C % 4) return false;
-  *g1 = hifihr::ConvGeom{N, H, W, C, (H + 2 * pad1 - R1) / stride + 1, (W + 2 * pad1 - R1) / stride + 1, K1, R1, R1, stride, pad1, 0};
-  *g2 = hifihr::ConvGeom{N, H, W, C, (H + 2 * pad2 - R2) / stride + 1, (W + 2 * pad2 - R2) / stride + 1, K2, R2, R2, stride, pad2, 0};
+  *g1 = conv_geom(N, H, W, C, K1, R1, R1, stride, pad1);
+  *g2 = conv_geom(N, H, W, C, K2, R2, R2, stride, pad2);
   return true;
 }
 int hifihr_conv2d_fwd_bnstats_pair_supported(int N, int H, int W, int C, int stride, int K1, int R1, int pad1, int K2, int R2, int pad2) {
@@ -493,7 +499,7 @@ int hifihr_conv2d_fwd_bnstats(const float* x, const float* w, float* y, float* s
                               int S, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
   if (!x || !w || !y || !stats || !conv_dims_ok(N, H, W, C, K, R, S, stride, pad) || C % 4)
     return fail(HIFIHR_EINVAL, "hifihr_conv2d_fwd_bnstats: bad argument (C must be a multiple of 4)");
-  hifihr::ConvGeom g{N, H, W, C, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, K, R, S, stride, pad, 0};
+  const hifihr::ConvGeom g = conv_geom(N, H, W, C, K, R, S, stride, pad);
   HIP_TRY(hifihr::launch_conv_igemm(g, x, w, nullptr, y, stats, ws, ws_bytes, (hipStream_t)stream));
   return HIFIHR_OK;
 }
@@ -502,10 +508,8 @@ int hifihr_conv2d_bwd_data(const float* dy, const float* w, float* dx, float* wt
                            int R, int S, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
   if (!dy || !w || !dx || !wt_scratch || !conv_dims_ok(N, H, W, C, K, R, S, stride, pad) || K % 4 || (K % 16 && stride != 1))
     return fail(HIFIHR_EINVAL, "hifihr_conv2d_bwd_data: bad argument (K % 4 == 0; K % 16 == 0 when stride > 1)");
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
   HIP_TRY(hifihr::launch_weight_transpose(w, wt_scratch, K, R * S, C, (hipStream_t)stream));
-  hifihr::ConvGeom g{N, OH, OW, K, H, W, C, R, S, stride, pad, 1};
-  HIP_TRY(hifihr::launch_conv_igemm(g, dy, wt_scratch, nullptr, dx, nullptr, ws, ws_bytes, (hipStream_t)stream));
+  HIP_TRY(hifihr::launch_conv_igemm(conv_dgrad_geom(N, H, W, C, K, R, S, stride, pad), dy, wt_scratch, nullptr, dx, nullptr, ws, ws_bytes, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 
@@ -513,9 +517,7 @@ int hifihr_conv2d_bwd_data_pre(const float* dy, const float* wt, float* dx, int 
                                int pad, void* ws, size_t ws_bytes, void* stream) {
   if (!dy || !wt || !dx || !conv_dims_ok(N, H, W, C, K, R, S, stride, pad) || K % 4 || (K % 16 && stride != 1))
     return fail(HIFIHR_EINVAL, "hifihr_conv2d_bwd_data_pre: bad argument (K % 4 == 0; K % 16 == 0 when stride > 1)");
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
-  hifihr::ConvGeom g{N, OH, OW, K, H, W, C, R, S, stride, pad, 1};
-  HIP_TRY(hifihr::launch_conv_igemm(g, dy, wt, nullptr, dx, nullptr, ws, ws_bytes, (hipStream_t)stream));
+  HIP_TRY(hifihr::launch_conv_igemm(conv_dgrad_geom(N, H, W, C, K, R, S, stride, pad), dy, wt, nullptr, dx, nullptr, ws, ws_bytes, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 
@@ -523,8 +525,7 @@ int hifihr_conv2d_bwd_data_pre_res(const float* dy, const float* wt, const float
                                    int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
   if (!dy || !wt || !dx || !res || !conv_dims_ok(N, H, W, C, K, R, S, stride, pad) || K % 4 || (K % 16 && stride != 1))
     return fail(HIFIHR_EINVAL, "hifihr_conv2d_bwd_data_pre_res: bad argument (K % 4 == 0; K % 16 == 0 when stride > 1)");
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
-  hifihr::ConvGeom g{N, OH, OW, K, H, W, C, R, S, stride, pad, 1};
+  hifihr::ConvGeom g = conv_dgrad_geom(N, H, W, C, K, R, S, stride, pad);
   g.residual = res;
   HIP_TRY(hifihr::launch_conv_igemm(g, dy, wt, nullptr, dx, nullptr, ws, ws_bytes, (hipStream_t)stream));
   return HIFIHR_OK;
@@ -536,9 +537,9 @@ int hifihr_conv2d_bwd_data_pre_plus1x1_supported(int N, int H, int W, int C, int
   // row and column, pad % stride (csrc/conv.hip make_plan), then lie inside the filter, so the class has row AND column taps -- the kernel
   // puts the extra tap behind the class's last tap row, and with row taps but no column taps it would run as an ordinary tap
   if (!conv_dims_ok(N, H, W, C, K, R, S, stride, pad) || stride < 2 || K % 16 || C % 4 || R * S > 62 || pad >= R || pad >= S) return 0;
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
-  if (OH != (H - 1) / stride + 1 || OW != (W - 1) / stride + 1) return 0;
-  if ((long)N * OH * OW * K >= (1L << 30) || (long)C * R * S * K >= (1L << 30)) return 0;
+  const hifihr::ConvGeom f = conv_geom(N, H, W, C, K, R, S, stride, pad);
+  if (f.OH != (H - 1) / stride + 1 || f.OW != (W - 1) / stride + 1) return 0;
+  if ((long)N * f.OH * f.OW * K >= (1L << 30) || (long)C * R * S * K >= (1L << 30)) return 0;
   static const int on = [] { const char* e = getenv("HIFIHR_DGRAD_PLUS1X1"); return e ? atoi(e) : 1; }();
   return on;
 }
@@ -547,8 +548,7 @@ int hifihr_conv2d_bwd_data_pre_plus1x1(const float* dy, const float* wt, const f
                                        int K, int R, int S, int stride, int pad, void* stream) {
   if (!dy || !wt || !dy2 || !wt2 || !dx || !hifihr_conv2d_bwd_data_pre_plus1x1_supported(N, H, W, C, K, R, S, stride, pad))
     return fail(HIFIHR_EINVAL, "hifihr_conv2d_bwd_data_pre_plus1x1: bad argument (see hifihr_conv2d_bwd_data_pre_plus1x1_supported)");
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
-  hifihr::ConvGeom g{N, OH, OW, K, H, W, C, R, S, stride, pad, 1};
+  hifihr::ConvGeom g = conv_dgrad_geom(N, H, W, C, K, R, S, stride, pad);
   g.src2 = dy2; g.wgt2 = wt2;
   HIP_TRY(hifihr::launch_conv_igemm(g, dy, wt, nullptr, dx, nullptr, nullptr, 0, (hipStream_t)stream));
   return HIFIHR_OK;
@@ -556,7 +556,7 @@ int hifihr_conv2d_bwd_data_pre_plus1x1(const float* dy, const float* wt, const f
 
 int hifihr_conv2d_bwd_weight_plus1x1_supported(int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
   if (!conv_dims_ok(N, H, W, C, K, R, S, stride, pad) || C % 4 || K % 4) return 0;
-  hifihr::ConvGeom g{N, H, W, C, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, K, R, S, stride, pad, 0};
+  const hifihr::ConvGeom g = conv_geom(N, H, W, C, K, R, S, stride, pad);
   return hifihr::conv_wgrad_plus1x1_supported(g) ? 1 : 0;
 }
 
@@ -564,7 +564,7 @@ int hifihr_conv2d_bwd_weight_plus1x1(const float* x, const float* dy, float* dw,
                                      int R, int S, int stride, int pad, void* stream) {
   if (!x || !dy || !dw || !dy2 || !dw2 || !hifihr_conv2d_bwd_weight_plus1x1_supported(N, H, W, C, K, R, S, stride, pad))
     return fail(HIFIHR_EINVAL, "hifihr_conv2d_bwd_weight_plus1x1: bad argument (see hifihr_conv2d_bwd_weight_plus1x1_supported)");
-  hifihr::ConvGeom g{N, H, W, C, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, K, R, S, stride, pad, 0};
+  const hifihr::ConvGeom g = conv_geom(N, H, W, C, K, R, S, stride, pad);
   HIP_TRY(hifihr::launch_conv_wgrad_plus1x1(g, x, dy, dw, dy2, dw2, (hipStream_t)stream));
   return HIFIHR_OK;
 }
@@ -583,7 +583,7 @@ int hifihr_conv2d_bwd_weight(const float* x, const float* dy, float* dw, int N, 
 
 size_t hifihr_conv2d_wgrad_workspace_bytes(int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
   if (!conv_dims_ok(N, H, W, C, K, R, S, stride, pad) || C % 4 || K % 4) return 0;
-  hifihr::ConvGeom g{N, H, W, C, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, K, R, S, stride, pad, 0};
+  const hifihr::ConvGeom g = conv_geom(N, H, W, C, K, R, S, stride, pad);
   return hifihr::conv_wgrad_workspace_bytes(g);
 }
 
@@ -591,14 +591,14 @@ int hifihr_conv2d_bwd_weight_ws(const float* x, const float* dy, float* dw, int 
                                 int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
   if (!x || !dy || !dw || !conv_dims_ok(N, H, W, C, K, R, S, stride, pad) || C % 4 || K % 4)
     return fail(HIFIHR_EINVAL, "hifihr_conv2d_bwd_weight: bad argument (C and K must be multiples of 4)");
-  hifihr::ConvGeom g{N, H, W, C, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, K, R, S, stride, pad, 0};
+  const hifihr::ConvGeom g = conv_geom(N, H, W, C, K, R, S, stride, pad);
   HIP_TRY(hifihr::launch_conv_wgrad(g, x, dy, dw, ws, ws ? ws_bytes : 0, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 
 int hifihr_conv2d_bwd_weight_c3_supported(int N, int H, int W, int K, int R, int S, int stride, int pad) {
   if (!conv_dims_ok(N, H, W, 4, K, R, S, stride, pad) || K % 4) return 0;
-  hifihr::ConvGeom g{N, H, W, 4, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, K, R, S, stride, pad, 0};
+  const hifihr::ConvGeom g = conv_geom(N, H, W, 4, K, R, S, stride, pad);
   return hifihr::conv_wgrad_c3_supported(g) ? 1 : 0;
 }
 
@@ -607,7 +607,7 @@ int hifihr_conv2d_bwd_weight_c3(const float* x4, const float* dy, float* dw3, in
   if (!x4 || !dy || !dw3 || !ws || !hifihr_conv2d_bwd_weight_c3_supported(N, H, W, K, R, S, stride, pad))
     return fail(HIFIHR_EINVAL, "hifihr_conv2d_bwd_weight_c3: only the 7x7 / stride 2 / 64-filter stem on NHWC4 images, with the workspace of "
                                "hifihr_conv2d_wgrad_workspace_bytes (ask hifihr_conv2d_bwd_weight_c3_supported)");
-  hifihr::ConvGeom g{N, H, W, 4, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, K, R, S, stride, pad, 0};
+  const hifihr::ConvGeom g = conv_geom(N, H, W, 4, K, R, S, stride, pad);
   HIP_TRY(hifihr::launch_conv_wgrad_c3(g, x4, dy, dw3, ws, ws_bytes, (hipStream_t)stream));
   return HIFIHR_OK;
 }
@@ -1128,59 +1128,6 @@ int hifihr_weight_transpose(const float* w, float* wt, int K, int RS, int C, voi
   return HIFIHR_OK;
 }
 
-/* ---- Winograd F(2x2, 3x3) ---- */
-static hifihr::ConvGeom wino_gemm_geom(long T, int C, int K) {
-  hifihr::ConvGeom g{1, (int)T, 1, C, (int)T, 1, K, 1, 1, 1, 0, 0, 0, 16, T * (long)C, (long)K * C, T * (long)K};
-  return g;
-}
-
-// HIFIHR_BGEMM=0 keeps the Winograd products on round 1's gather kernels (conv.hip); tuning / A-B runs only
-static bool use_bgemm() {
-  const char* e = getenv("HIFIHR_BGEMM");
-  return e == nullptr || atoi(e) != 0;
-}
-
-// Output-tile edge of the Winograd algorithm a layer of this geometry runs: 4 = F(4x4, 3x3) (csrc/wino4.hip: 36 positions, 4x fewer
-// multiplications than direct) where the batched GEMMs of csrc/gemm.hip take the shape in both directions, else 2 = F(2x2, 3x3).
-// HIFIHR_WINO_M=2 keeps every layer on F(2x2, 3x3).
-static int wino_m(int N, int H, int W, int C, int K) {
-  static const int pref = [] { const char* e = getenv("HIFIHR_WINO_M"); return e ? atoi(e) : 4; }();
-  if (pref != 4 || !use_bgemm() || H < 4 || W < 4) return 2;
-  const long T4 = hifihr::wino4_tiles(N, H, W);
-  if (T4 >= (1L << 30)) return 2;
-  // forward (V U^T: rows T4, N = K, reduction C), backward-data (roles of C and K swapped), backward-weight (slabs of Y'^T V)
-  if (!hifihr::bgemm_nt_supported((int)T4, K, C) || !hifihr::bgemm_nt_supported((int)T4, C, K) || !hifihr::bgemm_tn_supported(K, C, (int)T4)) return 2;
-  return 4;
-}
-// one rule for every _m entry: the output-tile edge is 2 (F(2x2, 3x3)) or 4 (F(4x4, 3x3)); anything else is refused, the queries answer 0
-static bool wino_m_ok(int m) { return m == 2 || m == 4; }
-static long wino_T(int m, int N, int H, int W) { return m == 4 ? hifihr::wino4_tiles(N, H, W) : (long)N * ((H + m - 1) / m) * ((W + m - 1) / m); }
-
-long hifihr_wino_tiles(int N, int H, int W, int m) { return (N > 0 && H > 0 && W > 0 && (m == 2 || m == 4)) ? wino_T(m, N, H, W) : 0; }
-long hifihr_wino_tiles_computed(int N, int H, int W, int m) {
-  if (!(N > 0 && H > 0 && W > 0 && (m == 2 || m == 4))) return 0;
-  return m == 4 ? hifihr::wino4_tiles_real(N, H, W) : wino_T(m, N, H, W);
-}
-
-int hifihr_wino_tile(int N, int H, int W, int C, int K) {
-  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return 2;
-  return wino_m(N, H, W, C, K);
-}
-
-size_t hifihr_wino_gemm_workspace_bytes_m(int N, int H, int W, int C, int K, int m) {
-  if (!wino_m_ok(m) || N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return 0;
-  if (m == 4) return hifihr::bgemm_nt_workspace_bytes((int)wino_T(4, N, H, W), K, C, 36);
-  return hifihr_wino_gemm_workspace_bytes(N, H, W, C, K);
-}
-
-size_t hifihr_wino_gemm_workspace_bytes(int N, int H, int W, int C, int K) {
-  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return 0;
-  const long T = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
-  if (use_bgemm() && T < (1L << 30) && hifihr::bgemm_nt_supported((int)T, K, C))
-    return hifihr::bgemm_nt_workspace_bytes((int)T, K, C, 16);       // the persistent (balanced) kernel's slabs + flags, or 0
-  return hifihr::conv_sk_workspace_bytes(wino_gemm_geom(T, C, K));
-}
-
 size_t hifihr_bgemm_nt_workspace_bytes(int M, int N, int K, int batch) { return hifihr::bgemm_nt_workspace_bytes(M, N, K, batch); }
 
 int hifihr_bgemm_nt(const float* A, const float* B, float* C, int M, int N, int K, int batch, void* ws, size_t ws_bytes, void* stream) {
@@ -1192,15 +1139,8 @@ int hifihr_bgemm_nt(const float* A, const float* B, float* C, int M, int N, int 
   return HIFIHR_OK;
 }
 
-int hifihr_bgemm_describe(int tn, int M, int N, int K, char* out, int cap) {
-  if (!out || cap < 8) return fail(HIFIHR_EINVAL, "hifihr_bgemm_describe: bad argument");
-  if (tn ? !hifihr::bgemm_tn_supported(M, N, K) : !hifihr::bgemm_nt_supported(M, N, K)) { out[0] = 0; return HIFIHR_OK; }
-  hifihr::bgemm_describe(tn, M, N, K, out, cap);
-  return HIFIHR_OK;
-}
-
-int hifihr_bgemm_describe_batch(int tn, int M, int N, int K, int batch, char* out, int cap) {
-  if (!out || cap < 8 || batch <= 0) return fail(HIFIHR_EINVAL, "hifihr_bgemm_describe_batch: bad argument");
+int hifihr_bgemm_describe(int tn, int M, int N, int K, int batch, char* out, int cap) {
+  if (!out || cap < 8 || batch <= 0) return fail(HIFIHR_EINVAL, "hifihr_bgemm_describe: bad argument");
   if (tn ? !hifihr::bgemm_tn_supported(M, N, K) : !hifihr::bgemm_nt_supported(M, N, K)) { out[0] = 0; return HIFIHR_OK; }
   hifihr::bgemm_describe_batch(tn, M, N, K, batch, out, cap);
   return HIFIHR_OK;
@@ -1220,47 +1160,162 @@ int hifihr_bgemm_tn(const float* A, const float* B, float* C_parts, int M, int N
   return HIFIHR_OK;
 }
 
-int hifihr_wino_wgrad_parts_m(int N, int H, int W, int C, int K, int m) {
-  if (!wino_m_ok(m) || N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || !use_bgemm()) return 0;
-  if (m == 4) {
-    const long T4 = wino_T(4, N, H, W);
-    return (T4 < (1L << 30) && hifihr::bgemm_tn_supported(K, C, (int)T4)) ? hifihr::bgemm_tn_parts(K, C, (int)T4, 36) : 0;
+/* ---- Winograd F(m x m, 3x3), m = 2 or 4: one entry per operation, the tile edge picks launch_wino_* (csrc/wino.hip) or launch_wino4_*
+ * (csrc/wino4.hip) ---- */
+static hifihr::ConvGeom wino_gemm_geom(long T, int C, int K) {
+  hifihr::ConvGeom g{1, (int)T, 1, C, (int)T, 1, K, 1, 1, 1, 0, 0, 0, 16, T * (long)C, (long)K * C, T * (long)K};
+  return g;
+}
+
+// HIFIHR_BGEMM=0 keeps the Winograd products on round 1's gather kernels (conv.hip); tuning / A-B runs only
+static bool use_bgemm() {
+  const char* e = getenv("HIFIHR_BGEMM");
+  return e == nullptr || atoi(e) != 0;
+}
+
+// one rule for every entry: the output-tile edge is 2 (F(2x2, 3x3)) or 4 (F(4x4, 3x3)); anything else is refused, the queries answer 0
+static bool wino_m_ok(int m) { return m == 2 || m == 4; }
+
+// The shape of a layer in the transform domain; every query and every product launch of the family reads it.
+struct WinoPlan {
+  int m, P;      // output-tile edge and positions (m + 2)^2: the batch of the products
+  long T, Tr;    // tiles = rows per position the buffers hold, and the rows of them the products compute (Tr <= T; m = 4 mosaics: the count
+                 // before its rounding, the rows behind it are zeros in V / Y' and unread in M)
+  bool ok;       // m is 2 or 4 and N, H, W > 0 (else T = Tr = 0)
+};
+static WinoPlan wino_plan(int N, int H, int W, int m) {
+  WinoPlan p{m, (m + 2) * (m + 2), 0, 0, wino_m_ok(m) && N > 0 && H > 0 && W > 0};
+  if (!p.ok) return p;
+  p.T = m == 4 ? hifihr::wino4_tiles(N, H, W) : (long)N * ((H + 1) / 2) * ((W + 1) / 2);
+  p.Tr = m == 4 ? hifihr::wino4_tiles_real(N, H, W) : p.T;
+  return p;
+}
+// the NT product [P][T][red] . [P][n][red]^T of this layer is csrc/gemm.hip's (forward: n = K, red = C; backward-data: n = C, red = K).
+// Its launches also need bgemm_nt_fits32 and say so in a text of their own.
+static bool wino_nt_ok(const WinoPlan& p, int n, int red) { return p.ok && p.T < (1L << 30) && hifihr::bgemm_nt_supported((int)p.T, n, red); }
+// the TN product Y'[P][T][K]^T . V[P][T][C] (backward-weight) is csrc/gemm.hip's, and the slabs it then writes (0: it is not)
+static bool wino_tn_ok(const WinoPlan& p, int C, int K) { return p.ok && p.T < (1L << 30) && hifihr::bgemm_tn_supported(K, C, (int)p.T); }
+static int wino_tn_parts(const WinoPlan& p, int C, int K) { return wino_tn_ok(p, C, K) ? hifihr::bgemm_tn_parts(K, C, (int)p.T, p.P) : 0; }
+
+// Output-tile edge of the Winograd algorithm a layer of this geometry runs: 4 = F(4x4, 3x3) (csrc/wino4.hip: 36 positions, 4x fewer
+// multiplications than direct) where the batched GEMMs of csrc/gemm.hip take the shape in both directions, else 2 = F(2x2, 3x3).
+// HIFIHR_WINO_M=2 keeps every layer on F(2x2, 3x3).
+static int wino_m(int N, int H, int W, int C, int K) {
+  static const int pref = [] { const char* e = getenv("HIFIHR_WINO_M"); return e ? atoi(e) : 4; }();
+  if (pref != 4 || !use_bgemm() || H < 4 || W < 4) return 2;
+  const WinoPlan p = wino_plan(N, H, W, 4);
+  // forward (V U^T: rows T, N = K, reduction C), backward-data (roles of C and K swapped), backward-weight (slabs of Y'^T V)
+  return (wino_nt_ok(p, K, C) && wino_nt_ok(p, C, K) && wino_tn_ok(p, C, K)) ? 4 : 2;
+}
+
+int hifihr_wino_tile(int N, int H, int W, int C, int K) {
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return 2;
+  return wino_m(N, H, W, C, K);
+}
+
+long hifihr_wino_tiles(int N, int H, int W, int m) { return wino_plan(N, H, W, m).T; }
+long hifihr_wino_tiles_computed(int N, int H, int W, int m) { return wino_plan(N, H, W, m).Tr; }
+
+size_t hifihr_wino_gemm_workspace_bytes(int N, int H, int W, int C, int K, int m) {
+  const WinoPlan p = wino_plan(N, H, W, m);
+  if (!p.ok || C <= 0 || K <= 0) return 0;
+  if (m == 4 || (use_bgemm() && wino_nt_ok(p, K, C)))
+    return hifihr::bgemm_nt_workspace_bytes((int)p.T, K, C, p.P);       // the persistent (balanced) kernel's slabs + flags, or 0
+  return hifihr::conv_sk_workspace_bytes(wino_gemm_geom(p.T, C, K));
+}
+
+int hifihr_wino_wgrad_parts(int N, int H, int W, int C, int K, int m) {
+  return use_bgemm() ? wino_tn_parts(wino_plan(N, H, W, m), C, K) : 0;
+}
+
+int hifihr_wino_weight_transform(const float* w, float* U, int K, int C, int flip, int m, void* stream) {
+  if (!w || !U || K <= 0 || C < 4 || C % 4 != 0 || !wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_weight_transform: bad argument (C % 4 == 0)");
+  if (m == 4) HIP_TRY(hifihr::launch_wino4_weight_transform(w, U, K, C, flip ? 1 : 0, (hipStream_t)stream));
+  else HIP_TRY(hifihr::launch_wino_weight_transform(w, U, K, C, flip ? 1 : 0, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_wino_input_transform(const float* x, float* V, int N, int H, int W, int C, int m, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_input_transform: m must be 2 or 4");
+  if (!x || !V || N <= 0 || H <= 0 || W <= 0 || C < 4 || C % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_input_transform: bad argument");
+  if (m == 4) HIP_TRY(hifihr::launch_wino4_input_transform(x, V, nullptr, N, H, W, C, (hipStream_t)stream));
+  else HIP_TRY(hifihr::launch_wino_input_transform(x, V, nullptr, N, H, W, C, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_wino_input_dy_transform(const float* dy, float* V, float* Yt, int N, int H, int W, int K, int m, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_input_dy_transform: m must be 2 or 4");
+  if (!dy || !V || !Yt || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0)
+    return fail(HIFIHR_EINVAL, "hifihr_wino_input_dy_transform: bad argument");
+  if (m == 4) HIP_TRY(hifihr::launch_wino4_input_transform(dy, V, Yt, N, H, W, K, (hipStream_t)stream));
+  else HIP_TRY(hifihr::launch_wino_input_transform(dy, V, Yt, N, H, W, K, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_wino_dy_transform(const float* dy, float* Y, int N, int H, int W, int K, int m, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_dy_transform: m must be 2 or 4");
+  if (!dy || !Y || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_dy_transform: bad argument");
+  if (m == 4) HIP_TRY(hifihr::launch_wino4_dy_transform(dy, Y, N, H, W, K, (hipStream_t)stream));
+  else HIP_TRY(hifihr::launch_wino_dy_transform(dy, Y, N, H, W, K, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+// m = 4: csrc/gemm.hip's product or refused.  m = 2: csrc/gemm.hip's where it takes the shape, else the gather kernel of csrc/conv.hip
+int hifihr_wino_gemm(const float* V, const float* U, float* M, int N, int H, int W, int C, int K, int m, void* ws, size_t ws_bytes, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: m must be 2 or 4");
+  const WinoPlan p = wino_plan(N, H, W, m);
+  const bool args = V && U && M && p.ok, nt = wino_nt_ok(p, K, C);
+  if (m == 4 && !(args && nt)) return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: bad argument (F(4x4, 3x3) needs C % 32 == 0, K % 64 == 0)");
+  if (m == 2 && !(args && C >= 32 && C % 32 == 0 && K >= 4 && K % 4 == 0))
+    return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: bad argument (C % 32 == 0, K % 4 == 0)");
+  if (m == 4 || (use_bgemm() && nt)) {
+    if (!hifihr::bgemm_nt_fits32(p.T, K, C)) return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: T * C and K * C must stay below 2^31 elements");
+    HIP_TRY(hifihr::launch_bgemm_nt(V, U, M, (int)p.Tr, K, C, p.P, ws, ws_bytes, (hipStream_t)stream, nullptr, (int)p.T));
+    return HIFIHR_OK;
   }
-  return hifihr_wino_wgrad_parts(N, H, W, C, K);
+  HIP_TRY(hifihr::launch_conv_igemm(wino_gemm_geom(p.T, C, K), V, U, nullptr, M, nullptr, ws, ws_bytes, (hipStream_t)stream));
+  return HIFIHR_OK;
 }
 
-int hifihr_wino_wgrad_parts(int N, int H, int W, int C, int K) {
-  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || !use_bgemm()) return 0;
-  const long T = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
-  if (T >= (1L << 30) || !hifihr::bgemm_tn_supported(K, C, (int)T)) return 0;
-  return hifihr::bgemm_tn_parts(K, C, (int)T, 16);
+int hifihr_wino_output_transform(const float* M, float* y, float* stats, int N, int H, int W, int K, int m, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform: m must be 2 or 4");
+  if (!M || !y || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform: bad argument");
+  if (m == 4) HIP_TRY(hifihr::launch_wino4_output_transform(M, y, stats, nullptr, 0, nullptr, N, H, W, K, (hipStream_t)stream));
+  else HIP_TRY(hifihr::launch_wino_output_transform(M, y, stats, nullptr, 0, N, H, W, K, (hipStream_t)stream));
+  return HIFIHR_OK;
 }
 
-int hifihr_wino_wgrad_gemm_parts_m(const float* V, const float* Y, float* dU_parts, int N, int H, int W, int C, int K, int parts, int m, void* stream) {
+int hifihr_wino_output_transform_act(const float* M, float* y, const float* bias, int act, int N, int H, int W, int K, int m, void* stream) {
+  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_act: m must be 2 or 4");
+  if (!M || !y || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0 || act < 0 || act > 1)
+    return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_act: bad argument");
+  if (m == 4) HIP_TRY(hifihr::launch_wino4_output_transform(M, y, nullptr, bias, act, nullptr, N, H, W, K, (hipStream_t)stream));
+  else HIP_TRY(hifihr::launch_wino_output_transform(M, y, nullptr, bias, act, N, H, W, K, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_wino_output_transform_mask(const float* M, float* y, const float* mask, int N, int H, int W, int K, int m, void* stream) {
+  if (m != 4) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_mask: the F(4x4, 3x3) pipeline only (m == 4)");
+  if (!M || !y || !mask || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0)
+    return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_mask: bad argument");
+  HIP_TRY(hifihr::launch_wino4_output_transform(M, y, nullptr, nullptr, 0, mask, N, H, W, K, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_wino_wgrad_gemm_parts(const float* V, const float* Y, float* dU_parts, int N, int H, int W, int C, int K, int parts, int m, void* stream) {
   if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_wgrad_gemm_parts: m must be 2 or 4");
-  if (m != 4) return hifihr_wino_wgrad_gemm_parts(V, Y, dU_parts, N, H, W, C, K, parts, stream);
   if (!V || !Y || !dU_parts || N <= 0 || H <= 0 || W <= 0 || parts <= 0)
     return fail(HIFIHR_EINVAL, "hifihr_wino_wgrad_gemm_parts: bad argument");
-  const long T4 = wino_T(4, N, H, W);
-  if (T4 >= (1L << 30) || !hifihr::bgemm_tn_supported(K, C, (int)T4) || parts != hifihr::bgemm_tn_parts(K, C, (int)T4, 36))
-    return fail(HIFIHR_EINVAL, "hifihr_wino_wgrad_gemm_parts: parts must be hifihr_wino_wgrad_parts_m(N, H, W, C, K, 4) > 0");
+  const WinoPlan p = wino_plan(N, H, W, m);
+  if (parts != wino_tn_parts(p, C, K))
+    return fail(HIFIHR_EINVAL, "hifihr_wino_wgrad_gemm_parts: parts must be hifihr_wino_wgrad_parts(N, H, W, C, K, m) > 0");
   // (the rows behind the last tile mosaic are zero in V and Y: the row-share kernel skips their k-steps)
-  HIP_TRY(hifihr::launch_bgemm_tn(Y, V, dU_parts, K, C, (int)T4, 36, parts, (hipStream_t)stream, (int)hifihr::wino4_tiles_real(N, H, W)));
+  HIP_TRY(hifihr::launch_bgemm_tn(Y, V, dU_parts, K, C, (int)p.T, p.P, parts, (hipStream_t)stream, (int)p.Tr));
   return HIFIHR_OK;
 }
 
-int hifihr_wino_wgrad_gemm_parts(const float* V, const float* Y, float* dU_parts, int N, int H, int W, int C, int K, int parts, void* stream) {
-  if (!V || !Y || !dU_parts || N <= 0 || H <= 0 || W <= 0 || parts <= 0)
-    return fail(HIFIHR_EINVAL, "hifihr_wino_wgrad_gemm_parts: bad argument");
-  const long T = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
-  if (T >= (1L << 30) || !hifihr::bgemm_tn_supported(K, C, (int)T) || parts != hifihr::bgemm_tn_parts(K, C, (int)T, 16))
-    return fail(HIFIHR_EINVAL, "hifihr_wino_wgrad_gemm_parts: parts must be hifihr_wino_wgrad_parts(N, H, W, C, K) > 0");
-  HIP_TRY(hifihr::launch_bgemm_tn(Y, V, dU_parts, K, C, (int)T, 16, parts, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_dw_transform_parts_m(const float* dU_parts, int parts, float* dw_acc, int K, int C, int m, void* stream) {
-  if (!dU_parts || !dw_acc || parts <= 0 || K <= 0 || C < 4 || C % 4 != 0 || (m != 2 && m != 4))
+int hifihr_wino_dw_transform_parts(const float* dU_parts, int parts, float* dw_acc, int K, int C, int m, void* stream) {
+  if (!dU_parts || !dw_acc || parts <= 0 || K <= 0 || C < 4 || C % 4 != 0 || !wino_m_ok(m))
     return fail(HIFIHR_EINVAL, "hifihr_wino_dw_transform_parts: bad argument");
   if (m == 4) HIP_TRY(hifihr::launch_wino4_dw_transform_parts(dU_parts, parts, dw_acc, K, C, (hipStream_t)stream));
   else HIP_TRY(hifihr::launch_wino_dw_transform_parts(dU_parts, parts, dw_acc, K, C, (hipStream_t)stream));
@@ -1277,79 +1332,82 @@ int hifihr_wino4_dw_transform_multi(const hifihr_wino_dw_job* jobs, int njobs, v
   return HIFIHR_OK;
 }
 
-int hifihr_wino_dw_transform_parts(const float* dU_parts, int parts, float* dw_acc, int K, int C, void* stream) {
-  return hifihr_wino_dw_transform_parts_m(dU_parts, parts, dw_acc, K, C, 2, stream);
-}
-
-int hifihr_wino_weight_transform_m(const float* w, float* U, int K, int C, int flip, int m, void* stream) {
-  if (!w || !U || K <= 0 || C < 4 || C % 4 != 0 || (m != 2 && m != 4)) return fail(HIFIHR_EINVAL, "hifihr_wino_weight_transform: bad argument (C % 4 == 0)");
-  if (m == 4) HIP_TRY(hifihr::launch_wino4_weight_transform(w, U, K, C, flip ? 1 : 0, (hipStream_t)stream));
-  else HIP_TRY(hifihr::launch_wino_weight_transform(w, U, K, C, flip ? 1 : 0, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_weight_transform(const float* w, float* U, int K, int C, int flip, void* stream) {
-  return hifihr_wino_weight_transform_m(w, U, K, C, flip, 2, stream);
-}
-
-int hifihr_wino_input_transform_m(const float* x, float* V, int N, int H, int W, int C, int m, void* stream) {
-  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_input_transform: m must be 2 or 4");
-  if (m != 4) return hifihr_wino_input_transform(x, V, N, H, W, C, stream);
-  if (!x || !V || N <= 0 || H <= 0 || W <= 0 || C < 4 || C % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_input_transform: bad argument");
-  HIP_TRY(hifihr::launch_wino4_input_transform(x, V, nullptr, N, H, W, C, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_gemm_m(const float* V, const float* U, float* M, int N, int H, int W, int C, int K, int m, void* ws, size_t ws_bytes, void* stream) {
-  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: m must be 2 or 4");
-  if (m != 4) return hifihr_wino_gemm(V, U, M, N, H, W, C, K, ws, ws_bytes, stream);
-  const long T4 = (N > 0 && H > 0 && W > 0) ? wino_T(4, N, H, W) : 0;
-  if (!V || !U || !M || T4 <= 0 || T4 >= (1L << 30) || !hifihr::bgemm_nt_supported((int)T4, K, C))
-    return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: bad argument (F(4x4, 3x3) needs C % 32 == 0, K % 64 == 0)");
-  if (!hifihr::bgemm_nt_fits32(T4, K, C)) return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: T * C and K * C must stay below 2^31 elements");
-  const long Tr = hifihr::wino4_tiles_real(N, H, W);       // mosaic tiles: the rows behind the last mosaic are padding (zeros in V, unread in M)
-  HIP_TRY(hifihr::launch_bgemm_nt(V, U, M, (int)(Tr < T4 ? Tr : T4), K, C, 36, ws, ws_bytes, (hipStream_t)stream, nullptr, (int)T4));
-  return HIFIHR_OK;
-}
-
 int hifihr_wino4_bwd_gemm_pair_supported(int N, int H, int W, int C, int K) {
-  const long T4 = (N > 0 && H > 0 && W > 0) ? wino_T(4, N, H, W) : 0;
-  if (T4 <= 0 || T4 >= (1L << 30) || C <= 0 || K <= 0 || !hifihr::bgemm_nt_supported((int)T4, C, K) || !hifihr::bgemm_tn_supported(K, C, (int)T4)) return 0;
-  const long Tr = hifihr::wino4_tiles_real(N, H, W);
-  return hifihr::bgemm_nt_tn_pair_supported((int)(Tr < T4 ? Tr : T4), (int)T4, C, K, 36, K, C, (int)T4, 36, hifihr::bgemm_tn_parts(K, C, (int)T4, 36)) ? 1 : 0;
+  const WinoPlan p = wino_plan(N, H, W, 4);
+  if (!wino_nt_ok(p, C, K) || !wino_tn_ok(p, C, K)) return 0;
+  return hifihr::bgemm_nt_tn_pair_supported((int)p.Tr, (int)p.T, C, K, 36, K, C, (int)p.T, 36, wino_tn_parts(p, C, K)) ? 1 : 0;
 }
 
 int hifihr_wino4_bwd_gemm_pair(const float* V2, const float* U2, float* M2, const float* Vx, const float* Yt, float* dU_parts, int N, int H,
                                int W, int C, int K, int parts, void* stream) {
-  const long T4 = (N > 0 && H > 0 && W > 0) ? wino_T(4, N, H, W) : 0;
-  if (!V2 || !U2 || !M2 || !Vx || !Yt || !dU_parts || T4 <= 0 || T4 >= (1L << 30) || parts <= 0 || !hifihr::bgemm_nt_supported((int)T4, C, K) ||
-      !hifihr::bgemm_tn_supported(K, C, (int)T4) || parts != hifihr::bgemm_tn_parts(K, C, (int)T4, 36))
-    return fail(HIFIHR_EINVAL, "hifihr_wino4_bwd_gemm_pair: bad argument (C, K % 64 == 0; parts = hifihr_wino_wgrad_parts_m(N, H, W, C, K, 4))");
-  if (!hifihr::bgemm_nt_fits32(T4, C, K)) return fail(HIFIHR_EINVAL, "hifihr_wino4_bwd_gemm_pair: T * K and C * K must stay below 2^31 elements");
-  const long Tr = hifihr::wino4_tiles_real(N, H, W);
-  const hipError_t e = hifihr::launch_bgemm_nt_tn_pair(V2, U2, M2, (int)(Tr < T4 ? Tr : T4), (int)T4, C, K, 36, Yt, Vx, dU_parts, K, C, (int)T4, 36,
-                                                       parts, (hipStream_t)stream, (int)(Tr < T4 ? Tr : T4));
+  const WinoPlan p = wino_plan(N, H, W, 4);
+  if (!V2 || !U2 || !M2 || !Vx || !Yt || !dU_parts || parts <= 0 || !wino_nt_ok(p, C, K) || parts != wino_tn_parts(p, C, K))
+    return fail(HIFIHR_EINVAL, "hifihr_wino4_bwd_gemm_pair: bad argument (C, K % 64 == 0; parts = hifihr_wino_wgrad_parts(N, H, W, C, K, 4))");
+  if (!hifihr::bgemm_nt_fits32(p.T, C, K)) return fail(HIFIHR_EINVAL, "hifihr_wino4_bwd_gemm_pair: T * K and C * K must stay below 2^31 elements");
+  const int T = (int)p.T, Tr = (int)p.Tr;
+  const hipError_t e = hifihr::launch_bgemm_nt_tn_pair(V2, U2, M2, Tr, T, C, K, 36, Yt, Vx, dU_parts, K, C, T, 36, parts, (hipStream_t)stream, Tr);
   if (e == hipSuccess) return HIFIHR_OK;
   if (e != hipErrorNotSupported) HIP_TRY(e);
-  // not a pair of row-share products: the two launches of hifihr_wino_gemm_m (with C and K exchanged) / hifihr_wino_wgrad_gemm_parts_m
-  HIP_TRY(hifihr::launch_bgemm_nt(V2, U2, M2, (int)(Tr < T4 ? Tr : T4), C, K, 36, nullptr, 0, (hipStream_t)stream, nullptr, (int)T4));
-  HIP_TRY(hifihr::launch_bgemm_tn(Yt, Vx, dU_parts, K, C, (int)T4, 36, parts, (hipStream_t)stream, (int)(Tr < T4 ? Tr : T4)));
+  // not a pair of row-share products: the two launches of hifihr_wino_gemm (with C and K exchanged) / hifihr_wino_wgrad_gemm_parts
+  HIP_TRY(hifihr::launch_bgemm_nt(V2, U2, M2, Tr, C, K, 36, nullptr, 0, (hipStream_t)stream, nullptr, T));
+  HIP_TRY(hifihr::launch_bgemm_tn(Yt, Vx, dU_parts, K, C, T, 36, parts, (hipStream_t)stream, Tr));
   return HIFIHR_OK;
 }
 
-int hifihr_wino_dy_transform_m(const float* dy, float* Y, int N, int H, int W, int K, int m, void* stream) {
-  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_dy_transform: m must be 2 or 4");
-  if (m != 4) return hifihr_wino_dy_transform(dy, Y, N, H, W, K, stream);
-  if (!dy || !Y || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_dy_transform: bad argument");
-  HIP_TRY(hifihr::launch_wino4_dy_transform(dy, Y, N, H, W, K, (hipStream_t)stream));
+// the F(2x2, 3x3) backward-weight for shapes hifihr_wino_wgrad_parts answers 0 for: atomics into a zeroed dU, then its transform
+int hifihr_wino_wgrad_gemm(const float* V, const float* Y, float* dU_zeroed, int N, int H, int W, int C, int K, void* stream) {
+  const WinoPlan p = wino_plan(N, H, W, 2);
+  if (!V || !Y || !dU_zeroed || !p.ok || C < 4 || C % 4 != 0 || K < 4 || K % 4 != 0)
+    return fail(HIFIHR_EINVAL, "hifihr_wino_wgrad_gemm: bad argument (C % 4 == 0, K % 4 == 0)");
+  HIP_TRY(hifihr::launch_conv_wgrad(wino_gemm_geom(p.T, C, K), V, Y, dU_zeroed, nullptr, 0, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 
-int hifihr_wino_output_transform_m(const float* M, float* y, float* stats, int N, int H, int W, int K, int m, void* stream) {
-  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform: m must be 2 or 4");
-  if (m != 4) return hifihr_wino_output_transform(M, y, stats, N, H, W, K, stream);
-  if (!M || !y || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform: bad argument");
-  HIP_TRY(hifihr::launch_wino4_output_transform(M, y, stats, nullptr, 0, nullptr, N, H, W, K, (hipStream_t)stream));
+int hifihr_wino_dw_transform(float* dU, float* dw_acc, int K, int C, int clear_du, void* stream) {
+  if (!dU || !dw_acc || K <= 0 || C < 4 || C % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_dw_transform: bad argument");
+  HIP_TRY(hifihr::launch_wino_dw_transform(dU, dw_acc, K, C, clear_du ? 1 : 0, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_wino_bn_input_supported(int C, int m) { return (m == 4 && hifihr::wino4_bn_supported(C)) ? 1 : 0; }
+
+int hifihr_wino_bn_input_transform(const float* x, float* stats, const float* gamma, const float* beta, const float* residual, float* out,
+                                   float* V, int N, int H, int W, int C, int m, float eps, float momentum, float* save_mean,
+                                   float* save_invstd, float* running_mean, float* running_var, void* stream) {
+  if (!x || !stats || !gamma || !beta || !V || !save_mean || !save_invstd || N <= 0 || H <= 0 || W <= 0 || ((residual == nullptr) != (out == nullptr)))
+    return fail(HIFIHR_EINVAL, "hifihr_wino_bn_input_transform: bad argument");
+  if (!hifihr_wino_bn_input_supported(C, m)) return fail(HIFIHR_EINVAL, "hifihr_wino_bn_input_transform: needs m = 4 and C % 4 == 0, C <= 512");
+  HIP_TRY(hifihr::launch_wino4_bn_input_transform(x, stats, gamma, beta, residual, out, V, N, H, W, C, eps, momentum, save_mean, save_invstd,
+                                                  running_mean, running_var, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_wino_output_transform_bnred(const float* Mm, const float* x, const float* out, const float* gadd, const float* save_mean,
+                                       const float* save_invstd, const float* gamma, const float* beta, float* red, float* g, int N, int H, int W,
+                                       int C, int m, void* stream) {
+  if (!Mm || !x || !save_mean || !save_invstd || !gamma || !beta || !red || !g || N <= 0 || H <= 0 || W <= 0)
+    return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_bnred: bad argument");
+  if (!hifihr_wino_bn_input_supported(C, m)) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_bnred: needs m = 4 and C % 4 == 0, C <= 512");
+  HIP_TRY(hifihr::launch_wino4_output_transform_bnred(Mm, x, out, gadd, save_mean, save_invstd, gamma, beta, red, g, N, H, W, C, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_wino_bn_bwd_dual_transform(const float* g, const float* y, const float* save_mean, const float* save_invstd, const float* gamma,
+                                      float* red, float* V, float* Yt, int N, int H, int W, int K, int m, float* dgamma_acc, float* dbeta_acc,
+                                      void* stream) {
+  if (!g || !y || !save_mean || !save_invstd || !gamma || !red || !V || !Yt || N <= 0 || H <= 0 || W <= 0)
+    return fail(HIFIHR_EINVAL, "hifihr_wino_bn_bwd_dual_transform: bad argument");
+  if (!hifihr_wino_bn_input_supported(K, m)) return fail(HIFIHR_EINVAL, "hifihr_wino_bn_bwd_dual_transform: needs m = 4 and K % 4 == 0, K <= 512");
+  HIP_TRY(hifihr::launch_wino4_bn_bwd_dual_transform(g, y, save_mean, save_invstd, gamma, red, V, Yt, N, H, W, K, dgamma_acc, dbeta_acc,
+                                                     (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_bn_bwd_apply(const float* g, const float* x, const float* save_mean, const float* save_invstd, const float* gamma, long M, int C,
+                        float* red, float* dx, float* dgamma_acc, float* dbeta_acc, void* stream) {
+  if (!g || !x || !save_mean || !save_invstd || !gamma || !red || !dx || M <= 0 || C < 4 || C % 4 != 0 || C > 512)
+    return fail(HIFIHR_EINVAL, "hifihr_bn_bwd_apply: bad argument (C % 4 == 0, C <= 512)");
+  HIP_TRY(hifihr::launch_bn_bwd_apply(g, x, save_mean, save_invstd, gamma, M, C, red, dx, dgamma_acc, dbeta_acc, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 
@@ -1404,119 +1462,6 @@ int hifihr_conv_halo_wgrad_reduce_multi(const hifihr_halo_reduce_job* jobs, int 
   return HIFIHR_OK;
 }
 
-int hifihr_wino_bn_input_supported(int C, int m) { return (m == 4 && hifihr::wino4_bn_supported(C)) ? 1 : 0; }
-
-int hifihr_wino_bn_input_transform(const float* x, float* stats, const float* gamma, const float* beta, const float* residual, float* out,
-                                   float* V, int N, int H, int W, int C, int m, float eps, float momentum, float* save_mean,
-                                   float* save_invstd, float* running_mean, float* running_var, void* stream) {
-  if (!x || !stats || !gamma || !beta || !V || !save_mean || !save_invstd || N <= 0 || H <= 0 || W <= 0 || ((residual == nullptr) != (out == nullptr)))
-    return fail(HIFIHR_EINVAL, "hifihr_wino_bn_input_transform: bad argument");
-  if (!hifihr_wino_bn_input_supported(C, m)) return fail(HIFIHR_EINVAL, "hifihr_wino_bn_input_transform: needs m = 4 and C % 4 == 0, C <= 512");
-  HIP_TRY(hifihr::launch_wino4_bn_input_transform(x, stats, gamma, beta, residual, out, V, N, H, W, C, eps, momentum, save_mean, save_invstd,
-                                                  running_mean, running_var, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_output_transform_bnred(const float* Mm, const float* x, const float* out, const float* gadd, const float* save_mean,
-                                       const float* save_invstd, const float* gamma, const float* beta, float* red, float* g, int N, int H, int W,
-                                       int C, int m, void* stream) {
-  if (!Mm || !x || !save_mean || !save_invstd || !gamma || !beta || !red || !g || N <= 0 || H <= 0 || W <= 0)
-    return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_bnred: bad argument");
-  if (!hifihr_wino_bn_input_supported(C, m)) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_bnred: needs m = 4 and C % 4 == 0, C <= 512");
-  HIP_TRY(hifihr::launch_wino4_output_transform_bnred(Mm, x, out, gadd, save_mean, save_invstd, gamma, beta, red, g, N, H, W, C, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_bn_bwd_dual_transform(const float* g, const float* y, const float* save_mean, const float* save_invstd, const float* gamma,
-                                      float* red, float* V, float* Yt, int N, int H, int W, int K, int m, float* dgamma_acc, float* dbeta_acc,
-                                      void* stream) {
-  if (!g || !y || !save_mean || !save_invstd || !gamma || !red || !V || !Yt || N <= 0 || H <= 0 || W <= 0)
-    return fail(HIFIHR_EINVAL, "hifihr_wino_bn_bwd_dual_transform: bad argument");
-  if (!hifihr_wino_bn_input_supported(K, m)) return fail(HIFIHR_EINVAL, "hifihr_wino_bn_bwd_dual_transform: needs m = 4 and K % 4 == 0, K <= 512");
-  HIP_TRY(hifihr::launch_wino4_bn_bwd_dual_transform(g, y, save_mean, save_invstd, gamma, red, V, Yt, N, H, W, K, dgamma_acc, dbeta_acc,
-                                                     (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_bn_bwd_apply(const float* g, const float* x, const float* save_mean, const float* save_invstd, const float* gamma, long M, int C,
-                        float* red, float* dx, float* dgamma_acc, float* dbeta_acc, void* stream) {
-  if (!g || !x || !save_mean || !save_invstd || !gamma || !red || !dx || M <= 0 || C < 4 || C % 4 != 0 || C > 512)
-    return fail(HIFIHR_EINVAL, "hifihr_bn_bwd_apply: bad argument (C % 4 == 0, C <= 512)");
-  HIP_TRY(hifihr::launch_bn_bwd_apply(g, x, save_mean, save_invstd, gamma, M, C, red, dx, dgamma_acc, dbeta_acc, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_input_dy_transform_m(const float* dy, float* V, float* Yt, int N, int H, int W, int K, int m, void* stream) {
-  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_input_dy_transform: m must be 2 or 4");
-  if (m != 4) return hifihr_wino_input_dy_transform(dy, V, Yt, N, H, W, K, stream);
-  if (!dy || !V || !Yt || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0)
-    return fail(HIFIHR_EINVAL, "hifihr_wino_input_dy_transform: bad argument");
-  HIP_TRY(hifihr::launch_wino4_input_transform(dy, V, Yt, N, H, W, K, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_output_transform_act_m(const float* M, float* y, const float* bias, int act, int N, int H, int W, int K, int m, void* stream) {
-  if (!wino_m_ok(m)) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_act: m must be 2 or 4");
-  if (m != 4) return hifihr_wino_output_transform_act(M, y, bias, act, N, H, W, K, stream);
-  if (!M || !y || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0 || act < 0 || act > 1)
-    return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_act: bad argument");
-  HIP_TRY(hifihr::launch_wino4_output_transform(M, y, nullptr, bias, act, nullptr, N, H, W, K, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_output_transform_mask_m(const float* M, float* y, const float* mask, int N, int H, int W, int K, int m, void* stream) {
-  if (m != 4) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_mask_m: the F(4x4, 3x3) pipeline only (m == 4)");
-  if (!M || !y || !mask || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0)
-    return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_mask_m: bad argument");
-  HIP_TRY(hifihr::launch_wino4_output_transform(M, y, nullptr, nullptr, 0, mask, N, H, W, K, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_input_transform(const float* x, float* V, int N, int H, int W, int C, void* stream) {
-  if (!x || !V || N <= 0 || H <= 0 || W <= 0 || C < 4 || C % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_input_transform: bad argument");
-  HIP_TRY(hifihr::launch_wino_input_transform(x, V, nullptr, N, H, W, C, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_gemm(const float* V, const float* U, float* M, int N, int H, int W, int C, int K, void* ws, size_t ws_bytes, void* stream) {
-  if (!V || !U || !M || N <= 0 || H <= 0 || W <= 0 || C < 32 || C % 32 != 0 || K < 4 || K % 4 != 0)
-    return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: bad argument (C % 32 == 0, K % 4 == 0)");
-  const long T = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
-  if (use_bgemm() && T < (1L << 30) && hifihr::bgemm_nt_supported((int)T, K, C)) {
-    if (!hifihr::bgemm_nt_fits32(T, K, C)) return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: T * C and K * C must stay below 2^31 elements");
-    HIP_TRY(hifihr::launch_bgemm_nt(V, U, M, (int)T, K, C, 16, ws, ws_bytes, (hipStream_t)stream));
-    return HIFIHR_OK;
-  }
-  HIP_TRY(hifihr::launch_conv_igemm(wino_gemm_geom(T, C, K), V, U, nullptr, M, nullptr, ws, ws_bytes, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_dy_transform(const float* dy, float* Y, int N, int H, int W, int K, void* stream) {
-  if (!dy || !Y || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_dy_transform: bad argument");
-  HIP_TRY(hifihr::launch_wino_dy_transform(dy, Y, N, H, W, K, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_wgrad_gemm(const float* V, const float* Y, float* dU_zeroed, int N, int H, int W, int C, int K, void* stream) {
-  if (!V || !Y || !dU_zeroed || N <= 0 || H <= 0 || W <= 0 || C < 4 || C % 4 != 0 || K < 4 || K % 4 != 0)
-    return fail(HIFIHR_EINVAL, "hifihr_wino_wgrad_gemm: bad argument (C % 4 == 0, K % 4 == 0)");
-  const long T = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
-  HIP_TRY(hifihr::launch_conv_wgrad(wino_gemm_geom(T, C, K), V, Y, dU_zeroed, nullptr, 0, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_dw_transform(float* dU, float* dw_acc, int K, int C, int clear_du, void* stream) {
-  if (!dU || !dw_acc || K <= 0 || C < 4 || C % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_dw_transform: bad argument");
-  HIP_TRY(hifihr::launch_wino_dw_transform(dU, dw_acc, K, C, clear_du ? 1 : 0, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_output_transform(const float* M, float* y, float* stats, int N, int H, int W, int K, void* stream) {
-  if (!M || !y || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0) return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform: bad argument");
-  HIP_TRY(hifihr::launch_wino_output_transform(M, y, stats, nullptr, 0, N, H, W, K, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
 int hifihr_freihand_augment(const uint32_t* img_rgbx, const uint8_t* mask, const int* idx, const int* coef_fix, int B, int H, int W,
                             float* out_img, float* out_mask, void* stream) {
   if (!idx || !coef_fix || (!out_img && !out_mask) || (out_img && !img_rgbx) || (out_mask && !mask) || B <= 0 || H <= 0 || W <= 0 ||
@@ -1554,13 +1499,6 @@ int hifihr_freihand_batch_step(const uint32_t* img_rgbx, const uint8_t* mask, co
   return HIFIHR_OK;
 }
 
-int hifihr_wino_input_dy_transform(const float* dy, float* V, float* Yt, int N, int H, int W, int K, void* stream) {
-  if (!dy || !V || !Yt || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0)
-    return fail(HIFIHR_EINVAL, "hifihr_wino_input_dy_transform: bad argument");
-  HIP_TRY(hifihr::launch_wino_input_transform(dy, V, Yt, N, H, W, K, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
 int hifihr_procrustes_error(const float* pred, const float* gt, int B, int N, float* aligned, float* err_sum, void* stream) {
   if (!pred || !gt || !err_sum || B <= 0 || N <= 0) return fail(HIFIHR_EINVAL, "hifihr_procrustes_error: bad argument");
   HIP_TRY(hifihr::launch_procrustes(pred, gt, B, N, aligned, err_sum, (hipStream_t)stream));
@@ -1579,13 +1517,6 @@ int hifihr_ho3d_batch(const uint32_t* img_rgbx, const uint8_t* hand_mask, const 
     return fail(HIFIHR_EINVAL, "hifihr_ho3d_batch: bad argument (out_size <= 256, workspace of hifihr_ho3d_workspace_bytes)");
   HIP_TRY(hifihr::launch_ho3d_batch(img_rgbx, hand_mask, Ks, uv21, xyz21, FH, FW, packed, B, out_size, ws, out_img, out_mask, out_K, out_uv21,
                                     out_xyz21, (hipStream_t)stream));
-  return HIFIHR_OK;
-}
-
-int hifihr_wino_output_transform_act(const float* M, float* y, const float* bias, int act, int N, int H, int W, int K, void* stream) {
-  if (!M || !y || N <= 0 || H <= 0 || W <= 0 || K < 4 || K % 4 != 0 || act < 0 || act > 1)
-    return fail(HIFIHR_EINVAL, "hifihr_wino_output_transform_act: bad argument");
-  HIP_TRY(hifihr::launch_wino_output_transform(M, y, nullptr, bias, act, N, H, W, K, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 

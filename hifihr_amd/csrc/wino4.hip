@@ -317,7 +317,7 @@ __global__ __launch_bounds__(192) void wino4_dw_transform_parts_wide_kernel(cons
 
 // The weight-gradient transforms of SEVERAL layers in ONE launch (round 6).  dw is needed by the optimizer only, so a step may collect the
 // (slabs, target) pairs of its F(4x4) layers during backward and run them all here, right before Adam: ten 5-11 us launches that sat
-// between the backward products at 3.9 TB/s (each a prologue and two or three trips of loads: hifihr_wino_dw_transform_parts_m) become
+// between the backward products at 3.9 TB/s (each a prologue and two or three trips of loads: hifihr_wino_dw_transform_parts) become
 // one stream over the same 298 MB.  The jobs travel BY VALUE in the kernel arguments (no device table: nothing to upload, nothing a
 // captured graph could find stale); job j owns workgroups [wg0_j, wg0_{j+1}); layers of <= 8 192 items keep the wide form above.
 struct DwJob {

@@ -637,7 +637,7 @@ _WEIGHT_PREP = _WeightPrep()
 
 
 class _DeferredDw:
-    """The F(4x4) weight-gradient transforms (dw += G^T dU G, hifihr_wino_dw_transform_parts_m) of a step's layers, collected during
+    """The F(4x4) weight-gradient transforms (dw += G^T dU G, hifihr_wino_dw_transform_parts) of a step's layers, collected during
     backward and run as ONE launch when the `prepared_weights()` scope closes -- the weight gradients are read by the optimizer only,
     and ten 5-11 us launches between the backward products (3.9 TB/s each) stream better as one (hifihr_wino4_dw_transform_multi).
     A layer defers only when (a) a scope is open, (b) its gradient is accumulated straight into the flat gradient buffer (nothing is

@@ -30,6 +30,7 @@ extern "C" {
 #define HIFIHR_MANO_NF 1538
 #define HIFIHR_MANO_NJ 16
 
+/* 2: every Winograd entry takes the tile edge m under its plain name (the `_m` twins of version 1 are gone) and hifihr_bgemm_describe the batch */
 int hifihr_version(void);
 const char* hifihr_last_error(void);
 /* number of HIP devices visible to the library (<=0: the library cannot be used for compute) */
@@ -304,50 +305,37 @@ int hifihr_conv2d_bwd_weight_ws(const float* x_d, const float* dy_d, float* dw_a
 int hifihr_conv2d_bwd_weight_c3_supported(int N, int H, int W, int K, int R, int S, int stride, int pad);
 int hifihr_conv2d_bwd_weight_c3(const float* x4_d, const float* dy_d, float* dw3_d, int N, int H, int W, int K, int R, int S, int stride,
                                 int pad, void* ws_d, size_t ws_bytes, void* stream);
-/* Winograd F(2x2, 3x3) path for stride-1, pad-1 3x3 convolutions with many channels (ResNet-18 layers 3-4): 2.25x fewer
- * multiplications than the direct kernel, same results up to a few ulp.  Forward:
- *   hifihr_wino_weight_transform(w[K][3][3][C], U[16][K][C], K, C, flip = 0)
- *   hifihr_wino_input_transform (x[N][H][W][C], V[16][T][C]),  T = N * ceil(H/2) * ceil(W/2)
- *   hifihr_wino_gemm            (V, U, M[16][T][K])  -- 16 GEMMs on the MFMA kernel; ws as for hifihr_conv2d_fwd
- *   hifihr_wino_output_transform(M, y[N][H][W][K], stats_d or NULL)   -- stats_d: batch-norm slot buffer (zero on entry)
+/* Winograd F(m x m, 3x3) for stride-1, pad-1 3x3 convolutions with many channels; m is the output-tile edge, 2 (csrc/wino.hip) or 4
+ * (csrc/wino4.hip), P = (m + 2)^2 the positions of a tile (16 / 36) and T = hifihr_wino_tiles(N, H, W, m) the tiles.  2.25x (m = 2) / 4x
+ * (m = 4) fewer multiplications than the direct kernel, results within 1e-5 of it (ResNet-18 layers 2-4, VGG19).  Forward:
+ *   hifihr_wino_weight_transform(w[K][3][3][C], U[P][K][C], K, C, flip = 0, m)
+ *   hifihr_wino_input_transform (x[N][H][W][C], V[P][T][C], ..., m)
+ *   hifihr_wino_gemm            (V, U, M[P][T][K], ..., m)  -- P GEMMs on the matrix cores; ws of hifihr_wino_gemm_workspace_bytes or NULL
+ *   hifihr_wino_output_transform(M, y[N][H][W][K], stats_d or NULL, ..., m)   -- stats_d: batch-norm slot buffer (zero on entry)
  * Backward-data is the same sequence on dy with the weights of the transposed, 180-degree rotated filter:
- *   weight_transform(wt[C][3][3][K] (= the [C][R][S][K] transpose hifihr_conv2d_bwd_data also builds), U[16][C][K], C, K, flip = 1).
- * Backward-weight: dU[16][K][C] (ZERO on entry) += the 16 batched reductions over the tiles of
- *   Y'[16][T][K] = hifihr_wino_dy_transform(dy)  and  V[16][T][C] (the forward's input transform of x), then
- *   hifihr_wino_dw_transform: dw[K][3][3][C] += G^T dU G  (accumulates, like hifihr_conv2d_bwd_weight). */
-size_t hifihr_wino_gemm_workspace_bytes(int N, int H, int W, int C, int K);
-int hifihr_wino_dy_transform(const float* dy_d, float* yt_d, int N, int H, int W, int K, void* stream);
-int hifihr_wino_wgrad_gemm(const float* v_d, const float* yt_d, float* du_zeroed_d, int N, int H, int W, int C, int K, void* stream);
-int hifihr_wino_dw_transform(float* du_d, float* dw_acc_d, int K, int C, int clear_du /* 1: leave du_d all zero (self-cleaning) */,
-                             void* stream);
-int hifihr_wino_weight_transform(const float* w_d, float* u_d, int K, int C, int flip, void* stream);
-int hifihr_wino_input_transform(const float* x_d, float* v_d, int N, int H, int W, int C, void* stream);
-int hifihr_wino_gemm(const float* v_d, const float* u_d, float* m_d, int N, int H, int W, int C, int K, void* ws_d, size_t ws_bytes,
-                     void* stream);
-int hifihr_wino_output_transform(const float* m_d, float* y_d, float* stats_d /* or NULL */, int N, int H, int W, int K, void* stream);
-/* Backward of a Winograd layer reads dy twice (input transform for backward-data, hifihr_wino_dy_transform for backward-weight);
- * this does both from one read: v_d[16][T][K] = B^T d B of the padded 4x4 patches, yt_d[16][T][K] = A dy A^T of their central 2x2. */
-int hifihr_wino_input_dy_transform(const float* dy_d, float* v_d, float* yt_d, int N, int H, int W, int K, void* stream);
-/* Output transform with the act epilogue of hifihr_conv2d_fwd: y = act(A^T m A + bias[K] (or NULL)), act 0 = none, 1 = ReLU
- * (VGG19 layers of the perceptual loss, reference utils/perceptual_loss.py:27-36). */
-int hifihr_wino_output_transform_act(const float* m_d, float* y_d, const float* bias_d /* or NULL */, int act, int N, int H, int W,
-                                     int K, void* stream);
-/* Winograd F(4x4, 3x3) (csrc/wino4.hip): the same pipeline with 4x4 output tiles -- 36 positions, T = N * ceil(H/4) * ceil(W/4), 4x fewer
- * multiplications than the direct convolution (F(2x2, 3x3): 2.25x), results within 1e-5 of it.  Every entry point above has an `_m`
- * form that takes the tile edge m (2 or 4; the plain names are m = 2; ANY other m is refused with HIFIHR_EINVAL by every _m entry, and the
- * _m queries -- hifihr_wino_tiles, _tiles_computed, _gemm_workspace_bytes_m, _wgrad_parts_m -- answer 0 for it: no entry falls back to
- * F(2x2, 3x3) on an m it does not know); all calls of one layer must use the same m, and buffers are sized
- * with P = (m + 2)^2 positions: U[P][K][C], V[P][T][C], M[P][T][K], Y'[P][T][K], du_parts[parts][P][K][C].
+ *   weight_transform(wt[C][3][3][K] (= the [C][R][S][K] transpose hifihr_conv2d_bwd_data also builds), U'[P][C][K], C, K, flip = 1, m).
+ * Backward-weight, from Y'[P][T][K] = hifihr_wino_dy_transform(dy) and V[P][T][C] (the forward's input transform of x): with
+ *   parts = hifihr_wino_wgrad_parts(N, H, W, C, K, m) > 0 (the product is csrc/gemm.hip's: C % 64 == 0, K % 64 == 0)
+ *     hifihr_wino_wgrad_gemm_parts(V, Y', du_parts[parts][P][K][C], ..., parts, m)  then
+ *     hifihr_wino_dw_transform_parts: dw[K][3][3][C] += G^T (sum of the slabs) G   -- nothing zero-initialised, bit-reproducible;
+ *   with parts == 0, at m = 2 only: hifihr_wino_wgrad_gemm: dU[16][K][C] (ZERO on entry) += the 16 reductions over the tiles (atomics), then
+ *     hifihr_wino_dw_transform: dw[K][3][3][C] += G^T dU G  (accumulates, like hifihr_conv2d_bwd_weight).
+ * All calls of one layer must use the same m, and every buffer is sized with its P and T.  ANY m other than 2 or 4 is refused with
+ * HIFIHR_EINVAL by every entry that takes m, and the queries -- hifihr_wino_tiles, _tiles_computed, _gemm_workspace_bytes, _wgrad_parts --
+ * answer 0 for it: no entry falls back to F(2x2, 3x3) on an m it does not know.
  * The transforms of both tile edges take ANY N, H, W > 0 -- images smaller than one tile included (H or W of 1, 2, 3 at m = 4: the tile is
  * zero-padded like any ragged last tile) -- and any C resp. K that is a multiple of 4; the weight and dw transforms any K > 0.  They write every
  * row t < hifihr_wino_tiles_computed of V / Y' and ZEROS into the rows behind it (the padding of the mosaic form); the output transforms read
- * rows t < hifihr_wino_tiles_computed of M only, and the products may leave the rows of M behind it unwritten.  act of the _act forms is 0 or 1.
- * The products on csrc/gemm.hip (hifihr_wino_gemm[_m], hifihr_wino4_bwd_gemm_pair) refuse, like hifihr_bgemm_nt, operands of 2^31 elements or
- * more per position (T * C, T * K, K * C) with HIFIHR_EINVAL.
+ * rows t < hifihr_wino_tiles_computed of M only, and the products may leave the rows of M behind it unwritten.  act of the _act form is 0 or 1.
+ * hifihr_wino_gemm: at m = 4 the product is csrc/gemm.hip's or refused (C % 32 == 0, K % 64 == 0); at m = 2 it needs C % 32 == 0 and
+ * K % 4 == 0 and runs on csrc/gemm.hip where that takes the shape (K % 64 == 0), else on the gather kernel of csrc/conv.hip (ws then as for
+ * hifihr_conv2d_fwd).  The products on csrc/gemm.hip (hifihr_wino_gemm, hifihr_wino4_bwd_gemm_pair) refuse, like hifihr_bgemm_nt, operands of
+ * 2^31 elements or more per position (T * C, T * K, K * C) with HIFIHR_EINVAL.
  * (tests/test_hostsim_gemm_contract.py holds every entry to this, around a float64 product, against float64 conv2d.)
  * hifihr_wino_tile(N, H, W, C, K) returns the m this library prefers for a layer: 4 where the batched GEMMs of csrc/gemm.hip take the
  * shape in all three directions (C % 64 == 0, K % 64 == 0, H, W >= 4), else 2.  m = 4 has the slab form of backward-weight only
- * (hifihr_wino_wgrad_parts_m > 0).  The per-step weight re-layout (hifihr_weight_prep) has job kinds 3 / 4 for U[36][K][C] / U'[36][C][K]. */
+ * (hifihr_wino_wgrad_parts > 0).  The per-step weight re-layout (hifihr_weight_prep) has job kinds 1 / 2 for U[16][K][C] / U'[16][C][K] and
+ * 3 / 4 for U[36][K][C] / U'[36][C][K]. */
 int hifihr_wino_tile(int N, int H, int W, int C, int K);
 /* T, the tiles (rows per position of V / M / Y') a layer has at tile edge m: N * ceil(H / m) * ceil(W / m) -- or, at m = 4 on square maps
  * with H % 4 in {1, 2} and N % 16 == 0, the tiles of the 4 x 4-image MOSAICS the transforms cut (16 images share one map with single
@@ -356,23 +344,35 @@ int hifihr_wino_tile(int N, int H, int W, int C, int K);
 long hifihr_wino_tiles(int N, int H, int W, int m);
 /* ... and the rows of them the forward / backward-data products actually compute (the mosaic count before the rounding; else the same). */
 long hifihr_wino_tiles_computed(int N, int H, int W, int m);
-size_t hifihr_wino_gemm_workspace_bytes_m(int N, int H, int W, int C, int K, int m);
-int hifihr_wino_weight_transform_m(const float* w_d, float* u_d, int K, int C, int flip, int m, void* stream);
-int hifihr_wino_input_transform_m(const float* x_d, float* v_d, int N, int H, int W, int C, int m, void* stream);
-int hifihr_wino_gemm_m(const float* v_d, const float* u_d, float* m_d, int N, int H, int W, int C, int K, int m, void* ws_d, size_t ws_bytes,
-                       void* stream);
-int hifihr_wino_output_transform_m(const float* m_d, float* y_d, float* stats_d /* or NULL */, int N, int H, int W, int K, int m, void* stream);
-int hifihr_wino_output_transform_act_m(const float* m_d, float* y_d, const float* bias_d /* or NULL */, int act, int N, int H, int W, int K,
-                                       int m, void* stream);
+size_t hifihr_wino_gemm_workspace_bytes(int N, int H, int W, int C, int K, int m);
+int hifihr_wino_wgrad_parts(int N, int H, int W, int C, int K, int m);
+int hifihr_wino_weight_transform(const float* w_d, float* u_d, int K, int C, int flip, int m, void* stream);
+int hifihr_wino_input_transform(const float* x_d, float* v_d, int N, int H, int W, int C, int m, void* stream);
+int hifihr_wino_dy_transform(const float* dy_d, float* yt_d, int N, int H, int W, int K, int m, void* stream);
+/* Backward of a Winograd layer reads dy twice (input transform for backward-data, hifihr_wino_dy_transform for backward-weight);
+ * this does both from one read: v_d[P][T][K] = B^T d B of the padded (m + 2)^2 patches, yt_d[P][T][K] = A dy A^T of their central m x m. */
+int hifihr_wino_input_dy_transform(const float* dy_d, float* v_d, float* yt_d, int N, int H, int W, int K, int m, void* stream);
+int hifihr_wino_gemm(const float* v_d, const float* u_d, float* m_d, int N, int H, int W, int C, int K, int m, void* ws_d, size_t ws_bytes,
+                     void* stream);
+int hifihr_wino_output_transform(const float* m_d, float* y_d, float* stats_d /* or NULL */, int N, int H, int W, int K, int m, void* stream);
+/* Output transform with the act epilogue of hifihr_conv2d_fwd: y = act(A^T m A + bias[K] (or NULL)), act 0 = none, 1 = ReLU
+ * (VGG19 layers of the perceptual loss, reference utils/perceptual_loss.py:27-36). */
+int hifihr_wino_output_transform_act(const float* m_d, float* y_d, const float* bias_d /* or NULL */, int act, int N, int H, int W, int K,
+                                     int m, void* stream);
 /* Output transform of a BACKWARD-DATA product whose layer input was a ReLU's output (VGG19 conv + ReLU -> conv): y_d = mask_d > 0 ? A^T m A : 0
  * with mask_d[N][H][W][K] = that ReLU output (the layer's saved input) -- the ReLU's backward where its gradient is produced, instead of a
  * hifihr_bias_relu_bwd pass in front of the previous layer's backward.  m == 4 only. */
-int hifihr_wino_output_transform_mask_m(const float* m_d, float* y_d, const float* mask_d, int N, int H, int W, int K, int m, void* stream);
-int hifihr_wino_dy_transform_m(const float* dy_d, float* yt_d, int N, int H, int W, int K, int m, void* stream);
+int hifihr_wino_output_transform_mask(const float* m_d, float* y_d, const float* mask_d, int N, int H, int W, int K, int m, void* stream);
+int hifihr_wino_wgrad_gemm_parts(const float* v_d, const float* yt_d, float* du_parts_d, int N, int H, int W, int C, int K, int parts, int m,
+                                 void* stream);
+int hifihr_wino_dw_transform_parts(const float* du_parts_d, int parts, float* dw_acc_d, int K, int C, int m, void* stream);
+int hifihr_wino_wgrad_gemm(const float* v_d, const float* yt_d, float* du_zeroed_d, int N, int H, int W, int C, int K, void* stream);
+int hifihr_wino_dw_transform(float* du_d, float* dw_acc_d, int K, int C, int clear_du /* 1: leave du_d all zero (self-cleaning) */,
+                             void* stream);
 /* 3x3 / stride 1 / pad 1 convolution with 64 input and 64 output channels as Winograd F(2x2, 3x3) in ONE launch, the transforms in
  * registers and nothing of the transform domain in HBM (round 3, csrc/conv_halo.hip: conv_wino2_kernel) -- ResNet layer 1 (reference
  * network/res_encoder.py:364-373 -> torchvision BasicBlock conv1 / conv2 of layer1) and VGG19 conv1_2 of the perceptual loss (reference
- * utils/perceptual_loss.py:27-36).  u_d = U[16][64][64]: hifihr_wino_weight_transform(w, u, 64, 64, 0) or hifihr_weight_prep kind 1 for
+ * utils/perceptual_loss.py:27-36).  u_d = U[16][64][64]: hifihr_wino_weight_transform(w, u, 64, 64, 0, 2) or hifihr_weight_prep kind 1 for
  * the forward; kind 2 (the transposed, rotated filter) with x_d = dy gives backward-data.  bias_d / relu: epilogue (VGG19); stats_d: the
  * forward statistics slots of the batch norm that follows (hifihr_bn_stats_floats(64) floats, zeroed) or NULL.  H even, W even and >= 14
  * (hifihr_conv3x3_c64_wino_supported); results within 1e-5 (relative to the output scale) of the direct convolution. */
@@ -413,7 +413,7 @@ int hifihr_conv_halo_wgrad_reduce_multi(const hifihr_halo_reduce_job* jobs /* ho
 /* Batch-norm fused into the F(4x4, 3x3) input transform (round 3, csrc/wino4_bn.hip).  For a BatchNorm2d whose consumer is a Winograd
  * convolution (reference BasicBlock: conv1 -> bn1 -> relu -> conv2; bn2 -> += identity -> relu -> the next block's conv1,
  * network/res_encoder.py:364-373 + vendored utils/Freihand_GNN_mano/network/resnet.py) this ONE launch replaces hifihr_bn_act_fwd followed by
- * hifihr_wino_input_transform_m: x_d is the RAW output of the previous convolution, stats_d its batch statistics (consumed: zero on
+ * hifihr_wino_input_transform: x_d is the RAW output of the previous convolution, stats_d its batch statistics (consumed: zero on
  * return, as in hifihr_bn_act_fwd, same save_mean / save_invstd / running-statistics semantics); the activation a = relu(bn(x) + residual?)
  * is formed on the fly and only V = B^T a B is written.  With residual_d, out_d (same shape as x) receives a as well -- the next block's
  * identity branch reads it; without, both are NULL and a is never stored (the backward recomputes the ReLU mask from x, as
@@ -427,7 +427,7 @@ int hifihr_wino_bn_input_transform(const float* x_d, float* stats_d, const float
  *     = d loss / d a; in its epilogue + gadd_d (the gradient that reached the block output through the next block's identity
  *     branch, or NULL), the ReLU mask (out_d > 0 when the forward added a residual, else recomputed from x_d), g_d = the masked
  *     gradient written once, and the batch-norm backward REDUCTION (sum g, sum g xhat) added into red_d (hifihr_bn_stats_floats(C)
- *     floats, all zero on entry).  Replaces hifihr_wino_output_transform_m + the autograd add + the reduction half of hifihr_bn_act_bwd.
+ *     floats, all zero on entry).  Replaces hifihr_wino_output_transform + the autograd add + the reduction half of hifihr_bn_act_bwd.
  *   then EITHER hifihr_bn_bwd_apply: the apply half of hifihr_bn_act_bwd on (g_d, red_d): dx, dgamma_acc += , dbeta_acc +=, red_d zeroed;
  *   OR, when the batch-norm's input was itself produced by a Winograd convolution, hifihr_wino_bn_bwd_dual_transform in THAT
  *     convolution's backward: dy = gamma invstd (g - mean g - xhat mean(g xhat)) is evaluated on the fly and only V' = B^T dy B and
@@ -442,24 +442,19 @@ int hifihr_wino_bn_bwd_dual_transform(const float* g_d, const float* y_d, const 
                                       float* dgamma_acc_d, float* dbeta_acc_d, void* stream);
 int hifihr_bn_bwd_apply(const float* g_d, const float* x_d, const float* save_mean_d, const float* save_invstd_d, const float* gamma_d, long M,
                         int C, float* red_d, float* dx_d, float* dgamma_acc_d, float* dbeta_acc_d, void* stream);
-int hifihr_wino_input_dy_transform_m(const float* dy_d, float* v_d, float* yt_d, int N, int H, int W, int K, int m, void* stream);
-int hifihr_wino_wgrad_parts_m(int N, int H, int W, int C, int K, int m);
-int hifihr_wino_wgrad_gemm_parts_m(const float* v_d, const float* yt_d, float* du_parts_d, int N, int H, int W, int C, int K, int parts, int m,
-                                   void* stream);
 /* The two products of a Winograd F(4x4, 3x3) layer's backward that do not depend on each other, in ONE launch (round 5):
- *   backward-data   M2[36][T][C] = V2[36][T][K] . U2[36][C][K]^T      (= hifihr_wino_gemm_m(V2, U2, M2, N, H, W, K, C, 4, ...))
- *   backward-weight dU_parts     = Yt[36][T][K]^T . Vx[36][T][C]      (= hifihr_wino_wgrad_gemm_parts_m(Vx, Yt, dU_parts, ..., parts, 4))
+ *   backward-data   M2[36][T][C] = V2[36][T][K] . U2[36][C][K]^T      (= hifihr_wino_gemm(V2, U2, M2, N, H, W, K, C, 4, ...))
+ *   backward-weight dU_parts     = Yt[36][T][K]^T . Vx[36][T][C]      (= hifihr_wino_wgrad_gemm_parts(Vx, Yt, dU_parts, ..., parts, 4))
  * with V2 / Yt the two transforms of dy and Vx the forward's transformed input (the layer maps C -> K channels).  Workgroups of one
  * launch split between the two (a short launch of these kernels is shaped by its start and its end); falls back to the two launches
  * for shapes that are not on the row-share kernels.  Results identical to the separate calls. */
 int hifihr_wino4_bwd_gemm_pair_supported(int N, int H, int W, int C, int K);   /* 1: the call below pairs; 0: it makes the two launches */
 int hifihr_wino4_bwd_gemm_pair(const float* V2_d, const float* U2_d, float* M2_d, const float* Vx_d, const float* Yt_d, float* dU_parts_d,
                                int N, int H, int W, int C, int K, int parts, void* stream);
-int hifihr_wino_dw_transform_parts_m(const float* du_parts_d, int parts, float* dw_acc_d, int K, int C, int m, void* stream);
 /* The same F(4x4, 3x3) weight-gradient transform (m = 4) for SEVERAL layers in one launch: dw_acc_d[K][3][3][C] += G^T (sum of the `parts`
  * slabs du_parts_d[parts][36][K][C]) G per job, jobs independent of each other.  `jobs` is a HOST array (its pointers are device pointers);
  * the entries travel in the kernel arguments, so nothing is uploaded and a captured launch keeps them.  Results identical to one
- * hifihr_wino_dw_transform_parts_m(..., 4, ...) call per job.  A training step whose weight gradients are only read by the optimizer
+ * hifihr_wino_dw_transform_parts(..., 4, ...) call per job.  A training step whose weight gradients are only read by the optimizer
  * collects its layers' jobs during backward and makes this one call in front of the optimizer (reference train_hrnet.py:104-105). */
 typedef struct hifihr_wino_dw_job {
   const float* du_parts_d;
@@ -469,7 +464,7 @@ typedef struct hifihr_wino_dw_job {
 int hifihr_wino4_dw_transform_multi(const hifihr_wino_dw_job* jobs, int njobs, void* stream);
 /* Batched fp32 GEMM on the f32 matrix cores (csrc/gemm.hip): the plain products a Winograd layer consists of -- the GEMM half of
  * the vendor-library call behind one conv2d of the reference (network/res_encoder.py:364-373).  hifihr_wino_gemm dispatches here
- * when the shape allows (C % 32 == 0, K % 64 == 0; hifihr_wino_gemm_workspace_bytes then returns 0).
+ * when the shape allows (C % 32 == 0, K % 64 == 0).
  *   hifihr_bgemm_nt: c[b][M][N] = a[b][M][K] . b[b][N][K]^T          (K % 32 == 0, N % 64 == 0, any M); with a workspace of
  *                    hifihr_bgemm_nt_workspace_bytes (zero-initialised once, handed back all zero) large shapes run on the persistent,
  *                    balanced kernel (one workgroup per CU, stream-K shares), else one workgroup per tile
@@ -485,23 +480,15 @@ int hifihr_wino4_dw_transform_multi(const hifihr_wino_dw_job* jobs, int njobs, v
  *   - hifihr_bgemm_nt_workspace_bytes answers 0 for a shape that needs no workspace or that hifihr_bgemm_nt refuses.  A workspace that is
  *     NULL or smaller than that is not an error: the product runs with one workgroup per tile and the workspace is not touched.
  *   - hifihr_bgemm_nt writes every element of c once and reads nothing of it; operands are read inside a[b][M][K] / b[b][N][K] only.
- *   - hifihr_bgemm_describe[_batch]: out non-null, cap >= 8, batch > 0, else HIFIHR_EINVAL; "" for a shape the product entries refuse.
- *   - two calls on the same operands give the same bits (no atomics; the stream-K kernel hands its tiles over in a fixed order).
- * Winograd backward-weight on it: parts = hifihr_wino_wgrad_parts(N, H, W, C, K) (0: shape unsupported, use hifihr_wino_wgrad_gemm),
- *   hifihr_wino_wgrad_gemm_parts(V, Y', du_parts[parts][16][K][C])  then
- *   hifihr_wino_dw_transform_parts: dw[K][3][3][C] += G^T (sum of the slabs) G   -- nothing zero-initialised, bit-reproducible. */
+ *   - hifihr_bgemm_describe: out non-null, cap >= 8, batch > 0, else HIFIHR_EINVAL; "" for a shape the product entries refuse.
+ *   - two calls on the same operands give the same bits (no atomics; the stream-K kernel hands its tiles over in a fixed order). */
 size_t hifihr_bgemm_nt_workspace_bytes(int M, int N, int K, int batch);
 int hifihr_bgemm_nt(const float* a_d, const float* b_d, float* c_d, int M, int N, int K, int batch,
                     void* ws_d /* zero-initialised, self-cleaning; or NULL */, size_t ws_bytes, void* stream);
 int hifihr_bgemm_tn_parts(int M, int N, int T, int batch);
 /* Name of the kernel instantiation a shape runs on, as a profiler lists it ("" when the shape is not supported): measurement only. */
-int hifihr_bgemm_describe(int tn, int M, int N, int K_or_T, char* out, int cap);                       /* batch = 16 */
-int hifihr_bgemm_describe_batch(int tn, int M, int N, int K_or_T, int batch, char* out, int cap);
+int hifihr_bgemm_describe(int tn, int M, int N, int K_or_T, int batch, char* out, int cap);
 int hifihr_bgemm_tn(const float* a_d, const float* b_d, float* c_parts_d, int M, int N, int T, int batch, int parts, void* stream);
-int hifihr_wino_wgrad_parts(int N, int H, int W, int C, int K);
-int hifihr_wino_wgrad_gemm_parts(const float* v_d, const float* yt_d, float* du_parts_d, int N, int H, int W, int C, int K, int parts,
-                                 void* stream);
-int hifihr_wino_dw_transform_parts(const float* du_parts_d, int parts, float* dw_acc_d, int K, int C, void* stream);
 /* [K][RS][C] -> [C][RS][K] (the transpose backward-data consumes).  K, RS, C > 0 (any values: no multiple is required), non-null pointers,
  * else HIFIHR_EINVAL; every element of wt_d is written once. */
 int hifihr_weight_transpose(const float* w_d, float* wt_d, int K, int RS, int C, void* stream);

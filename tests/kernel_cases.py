@@ -1576,7 +1576,7 @@ def se_case(lib, device, B, H, W, C, SQ, seed=0):
 # ------------------------------------------------------------------------------------------------
 def wino4_dw_multi_case(lib, device, seed=0):
     """hifihr_wino4_dw_transform_multi: the F(4x4) weight-gradient transforms of several layers in one launch == one
-    hifihr_wino_dw_transform_parts_m(..., 4) call per layer, bit for bit (same per-item arithmetic, slabs in slab order) -- wide-form layers
+    hifihr_wino_dw_transform_parts(..., 4) call per layer, bit for bit (same per-item arithmetic, slabs in slab order) -- wide-form layers
     (<= 8 192 items), item-per-thread layers, 1 .. 7 slabs, a layer whose item count is not a multiple of the workgroup's, accumulation
     into non-zero targets; more jobs than one launch's argument block holds (24)."""
     gen = torch.Generator().manual_seed(seed)
@@ -2144,7 +2144,7 @@ def bn_large_mean_case(lib, device, producer, seed=0, mean=50.0, std=0.1):
 # batch-norm fused into the Winograd F(4x4, 3x3) input transform (csrc/wino4_bn.hip) vs the two separate launches
 # ------------------------------------------------------------------------------------------------
 def wino_bn_input_case(lib, device, N, H, W, C, residual, seed=0):
-    """hifihr_wino_bn_input_transform == hifihr_bn_act_fwd (ReLU, optional residual) followed by hifihr_wino_input_transform_m, bit for bit
+    """hifihr_wino_bn_input_transform == hifihr_bn_act_fwd (ReLU, optional residual) followed by hifihr_wino_input_transform, bit for bit
     (same scale / shift / residual / ReLU expression, same transform), and both against torch: V through the known input transform of a
     torch-computed activation."""
     import torch.nn.functional as F
@@ -2186,8 +2186,8 @@ def wino_bn_input_case(lib, device, N, H, W, C, residual, seed=0):
 
 def wino_bn_bwd_case(lib, device, N, H, W, C, residual, addend, seed=0):
     """The backward of the batch-norm / Winograd fusion (csrc/wino4_bn.hip) against the launches it replaces:
-      hifihr_wino_output_transform_bnred + hifihr_bn_bwd_apply  ==  hifihr_wino_output_transform_m (+ add) + hifihr_bn_act_bwd
-      hifihr_wino_bn_bwd_dual_transform                         ==  hifihr_bn_bwd_apply + hifihr_wino_input_dy_transform_m   (bit for bit)"""
+      hifihr_wino_output_transform_bnred + hifihr_bn_bwd_apply  ==  hifihr_wino_output_transform (+ add) + hifihr_bn_act_bwd
+      hifihr_wino_bn_bwd_dual_transform                         ==  hifihr_bn_bwd_apply + hifihr_wino_input_dy_transform   (bit for bit)"""
     gen = torch.Generator().manual_seed(seed)
     d = lambda t: t.to(device).contiguous()
     M = N * H * W
@@ -3741,7 +3741,7 @@ def _wino_fused_and_refused(lib, G, ent, what, N, H, W, C, K, m, P, T, w, wt, U,
     """hifihr_weight_prep against the separate launches (bit for bit) and the refusals of the entries the chain only ever accepts."""
     from hifihr_amd._lib import _stream_of
     import ctypes
-    # the per-step re-layout in one launch: transpose, U and U' of this layer == hifihr_weight_transpose / hifihr_wino_weight_transform_m
+    # the per-step re-layout in one launch: transpose, U and U' of this layer == hifihr_weight_transpose / hifihr_wino_weight_transform
     kinds = (0, 1, 2) if m == 2 else (0, 3, 4)
     dsts = [G.out(C, 9, K), G.out(P, K, C), G.out(P, C, K)]
     table = lib.prep_jobs([(w, d, K, C, 9, k) for d, k in zip(dsts, kinds)], w.device)
@@ -3775,7 +3775,7 @@ def _wino_fused_and_refused(lib, G, ent, what, N, H, W, C, K, m, P, T, w, wt, U,
         parts = lib.wino_wgrad_parts(N, H, W, C, K, 4)
         can = C % 64 == 0 and K % 64 == 0
         assert not lib.wino4_bwd_gemm_pair_supported(N, H, W, C, K) or (can and parts > 0), f"{what}: pair predicate on channels the products refuse"
-        assert can == (parts > 0), f"{what}: hifihr_wino_wgrad_parts_m {parts}"
+        assert can == (parts > 0), f"{what}: hifihr_wino_wgrad_parts {parts}"
         M2, dUq = G.out(P, T, C), G.out(max(parts, 1) + 1, P, K, C)
         bad = [(V2, U2, M2, V, Yt, dUq, parts + 1), (V2, U2, M2, V, Yt, dUq, 0)] + ([] if can else [(V2, U2, M2, V, Yt, dUq, 1)])
         bad += [(None, U2, M2, V, Yt, dUq, max(parts, 1)), (V2, U2, None, V, Yt, dUq, max(parts, 1)), (V2, U2, M2, V, Yt, None, max(parts, 1))]

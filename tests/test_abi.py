@@ -24,7 +24,7 @@ def test_header_symbols_are_exported():
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/hifihr.h but not exported"
     lib.hifihr_version.restype = ctypes.c_int
-    assert lib.hifihr_version() >= 1
+    assert lib.hifihr_version() >= 2
 
 
 def test_python_binding_covers_the_header():

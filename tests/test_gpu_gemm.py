@@ -67,7 +67,7 @@ def test_bgemm_tn_row_shares(lib, M, N, T, batch):
 
 
 # ---- the GEMM contract (tests/kernel_cases.py "The GEMM contract"): the emulator's lists (tests/test_hostsim_gemm_contract.py) plus the few
-# larger shapes whose 256-workgroup plan reaches what the small shapes reach on the emulator's 4 -- chosen with hifihr_bgemm_describe_batch
+# larger shapes whose 256-workgroup plan reaches what the small shapes reach on the emulator's 4 -- chosen with hifihr_bgemm_describe
 # at 256 compute units: no small shape takes the stream-K kernel, the single-slab or T-split TN row-share kernel or shares above the minimum there.
 from kernel_cases import (GEMM_ROUTES as ROUTES, NT_SHAPES, TN_SHAPES, TRANSPOSE_SHAPES, WINO_BN_GEOMS, WINO_GEOMS,  # noqa: E402
                           gemm_route as _route)
@@ -115,7 +115,7 @@ def test_weight_transpose_contract_on_every_shape(lib, gemm_tally, geo):
 
 
 def test_the_gemm_contract_shapes_reach_every_kernel_on_this_device(lib):
-    """What hifihr_bgemm_describe_batch / _tn_parts / _nt_workspace_bytes name for the lists on THIS device's compute units: the larger
+    """What hifihr_bgemm_describe / _tn_parts / _nt_workspace_bytes name for the lists on THIS device's compute units: the larger
     shapes name what they were chosen for, and the lists together name every kernel of the family."""
     named = set()
     for g, kernel in NT_SHAPES_GPU:

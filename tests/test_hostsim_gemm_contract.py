@@ -3,7 +3,7 @@ hostsim emulator, in the form of tests/test_hostsim_layer_contract.py: fixed sha
 boundary; an entry either refuses (HIFIHR_EINVAL, outputs untouched) or matches a float64 reference inside NaN / canary guard bands, twice
 on the same workspace with identical bits (tests/kernel_cases.py, "The GEMM contract").  The routing switches (HIFIHR_GEMM_*) are set per
 case so that the lists reach every kernel of the family on the emulator's 4 compute units; the coverage test at the end fails when an edit
-stops reaching one, or when hifihr_bgemm_describe_batch names another kernel than the one that ran.  The GPU half runs the same lists, and
+stops reaching one, or when hifihr_bgemm_describe names another kernel than the one that ran.  The GPU half runs the same lists, and
 a few larger shapes, in tests/test_gpu_gemm.py and tests/test_gpu_tail.py."""
 import pytest
 import torch
@@ -46,7 +46,7 @@ def tally():
 
 
 def nt_kernel_expected(lib, g):
-    """The kernel an accepted NT case must run on: what hifihr_bgemm_describe_batch names -- except the stream-K plan without (enough of) its
+    """The kernel an accepted NT case must run on: what hifihr_bgemm_describe names -- except the stream-K plan without (enough of) its
     workspace, which include/hifihr.h sends to one workgroup per tile (the wave-specialised kernel with the same loader waves)."""
     M, N, K, batch, route, ws = g
     with _route(route):
@@ -90,7 +90,7 @@ def test_bgemm_nt_on_every_shape(hostsim_lib, tally, geo):
     accepted, nb = _run(hostsim_lib, "nt", geo)
     assert accepted == kc.bgemm_nt_expect(*geo[:4])
     if accepted:
-        assert LAUNCHED[("nt", geo)] == {nt_kernel_expected(hostsim_lib, geo)}, "hifihr_bgemm_describe_batch names another kernel than the one that ran"
+        assert LAUNCHED[("nt", geo)] == {nt_kernel_expected(hostsim_lib, geo)}, "hifihr_bgemm_describe names another kernel than the one that ran"
     else:
         assert not LAUNCHED[("nt", geo)], "a refused call launched a kernel"
 
@@ -102,7 +102,7 @@ def test_bgemm_tn_on_every_shape(hostsim_lib, tally, geo):
     if parts:
         with _route(geo[4]):
             name = hostsim_lib.bgemm_describe(True, *geo[:4]).replace(" ", "")
-        assert LAUNCHED[("tn", geo)] == {name}, "hifihr_bgemm_describe_batch names another kernel than the one that ran"
+        assert LAUNCHED[("tn", geo)] == {name}, "hifihr_bgemm_describe names another kernel than the one that ran"
     else:
         assert not LAUNCHED[("tn", geo)], "a refused call launched a kernel"
 
