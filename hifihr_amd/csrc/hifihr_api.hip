@@ -266,9 +266,9 @@ int hifihr_mano_joints_bwd(const hifihr_mano_t* h, const float* gjoints_rel, con
 int hifihr_renderer_create(hifihr_renderer_t** out, const int32_t* faces, int V, int F, int image_size, int aa,
                            const float* ambient3, const float* mat_diffuse3, const float* specular3, float shininess,
                            const float* background3) {
-  if (!out || !faces || V <= 0 || F <= 0 || image_size <= 0 || aa < 1 || aa > 3 || !ambient3 || !mat_diffuse3 || !specular3 ||
-      !background3)
-    return fail(HIFIHR_EINVAL, "hifihr_renderer_create: bad argument");
+  if (!out || !faces || V <= 0 || F <= 0 || image_size <= 0 || image_size > hifihr::kRenderMaxImage || aa < 1 || aa > 3 || !ambient3 ||
+      !mat_diffuse3 || !specular3 || !background3)
+    return fail(HIFIHR_EINVAL, "hifihr_renderer_create: bad argument (1 <= image_size <= 720, 1 <= aa <= 3)");
   std::vector<int> fv(faces, faces + (size_t)F * 3), off(V + 1, 0), idx((size_t)F * 3);
   for (int i = 0; i < F * 3; ++i) {
     if (fv[i] < 0 || fv[i] >= V) return fail(HIFIHR_EINVAL, "hifihr_renderer_create: face index out of range");

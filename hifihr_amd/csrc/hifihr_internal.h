@@ -69,6 +69,7 @@ hipError_t launch_lbs_bwd(const LbsDev& t, const float* theta, const float* beta
                           float* gA_zeroed, float* gtheta, float* gbeta_zeroed, hipStream_t st);
 
 // Renderer handle contents (device pointers + constants); passed to kernels by value.
+constexpr int kRenderMaxImage = 720;  // largest image_size a renderer is created for (derived next to f3_supported in csrc/render.hip)
 struct RenderDev {
   int V, F, H, aa;
   const int* faces;    // [F][3]

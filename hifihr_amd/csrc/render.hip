@@ -103,6 +103,13 @@ static inline size_t f3_part_bytes(const RenderDev& r, int B) {
   return (size_t)(kF3CtlInts + B) * 4 + (size_t)kF3Classes * f3_queue_cap(r, B) * sizeof(int2) + (size_t)B * kF3SplitSlots * 4 +
          (size_t)B * kF3SplitSlots * sw2 * 8 + 256;
 }
+// Largest image edge a forward can be launched for (hifihr_renderer_create refuses more; include/hifihr.h states it).  The third form's item
+// code holds 64 x 64 tiles of 8 pixels: H <= 512 (f3_supported).  Above that the second form runs on the same 8-pixel grid, and
+// render_bin_kernel asks for 2 tiles^2 ints of dynamic LDS next to 40 bytes of static (s_last, f3_sched_image's counters): a launch may
+// request 64 KiB in all without a function attribute, so tiles^2 <= (65536 - 40) / 8 = 8187, tiles <= 90, H <= 720.  (Fwd2Lds does not
+// grow with H; the tile kernels' grids -- B tiles^2 workgroups, B (H / 16)^2 for the backward -- stay far below the grid limits.)
+static_assert(kRenderMaxImage == 720 && 2 * ((kRenderMaxImage + 7) / 8) * ((kRenderMaxImage + 7) / 8) * sizeof(int) + 40 <= 65536 &&
+              2 * ((kRenderMaxImage + 8) / 8) * ((kRenderMaxImage + 8) / 8) * sizeof(int) + 40 > 65536, "render_bin_kernel's LDS request");
 static inline bool f3_supported(const RenderDev& r, int B) {
   return r.H <= 512 && B < (1 << 14) && render_tile() == 8;         // 64 x 64 tiles and the batch index fit the item code
 }
@@ -181,8 +188,9 @@ __device__ __forceinline__ void f3_sched_image(const RenderDev& r, int* __restri
 
 #if defined(HIFIHR_HOSTSIM)
 #define HIFIHR_R_WAIT_VMEM() ((void)0)
-// emulator builds only: how many split-tile merges / resolves by the last arriver / background strips ran (tests assert that the
-// small test images reach every path of render_fwd3_kernel)
+// emulator builds only: how many split-tile merges / resolves by the last arriver / background strips / items that walk more than one pass
+// of CAP faces WITHOUT a merge slot (f3_sched_image ran out of kF3SplitSlots) ran (tests assert that the small test images reach every
+// path of render_fwd3_kernel)
 static int g_f3_dbg[4];
 extern "C" void hifihr_hostsim_render_fwd3_counts(int* out4, int reset) {
   for (int i = 0; i < 4; ++i) { out4[i] = g_f3_dbg[i]; if (reset) g_f3_dbg[i] = 0; }
@@ -877,6 +885,7 @@ __global__ __launch_bounds__(kF2Threads) void render_fwd3_kernel(RenderDev r, co
     const int nlist = tile_cnt[tile];
     const int* flist = tile_list + tile * r.F;
     const int lo = (int)((long)nlist * part / P), hi = (int)((long)nlist * (part + 1) / P);
+    if (P == 1 && hi - lo > CAP) { F3_DBG(3) }
     R2_T0
     for (int e = tid; e < 2 * SW; e += kF2Threads) {
       const int idx = e < SW ? e : e - SW;

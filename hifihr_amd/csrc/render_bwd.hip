@@ -14,6 +14,18 @@ namespace hifihr {
 // four workgroups per CU, 37 KB to zero and to scan per tile, and no LDS path at all for a 5 990-vertex skin, whose gradients went
 // out as one global float atomic per lane per value -- 64 rows per wave instruction, ~0.08 TB/s).  A vertex that finds the table
 // full (a tile with more distinct vertices than slots) falls back to global atomics for that record.
+#if defined(HIFIHR_HOSTSIM)
+// emulator builds only: vertex records / texels that found their LDS table full and went out as global atomics (tests assert that their
+// lists reach both overflow paths)
+static int g_rbwd_dbg[2];
+extern "C" void hifihr_hostsim_render_bwd_counts(int* out2, int reset) {
+  for (int i = 0; i < 2; ++i) { out2[i] = g_rbwd_dbg[i]; if (reset) g_rbwd_dbg[i] = 0; }
+}
+#define RBWD_DBG(i) __atomic_fetch_add(&g_rbwd_dbg[i], 1, __ATOMIC_RELAXED);
+#else
+#define RBWD_DBG(i)
+#endif
+
 template <int HT>
 struct BwdAcc {
   int keys[HT];
@@ -43,6 +55,7 @@ __device__ __forceinline__ void flush_face(BwdAcc<HT>& A, float* __restrict__ gg
         if (v != 0.f) atomicAdd(&A.rec[s][c], v);  // (all of these LDS atomics together: ~50 of the launch's ~140 us -- measured by compiling them out)
       }
     } else {
+      RBWD_DBG(0)
       float* dst = gglobal + (size_t)idx[k] * 12;
 #pragma unroll
       for (int c = 0; c < 12; ++c) {
@@ -83,6 +96,7 @@ __device__ __forceinline__ void flush_texel(TexAcc<TT>& A, float* __restrict__ g
 #pragma unroll
     for (int c = 0; c < 3; ++c) atomicAdd(&A.rec[s][c], v[c]);
   } else {
+    RBWD_DBG(1)
 #pragma unroll
     for (int c = 0; c < 3; ++c) atomicAdd(gm + (size_t)texel * 3 + c, v[c]);
   }

@@ -145,7 +145,26 @@ int hifihr_lbs_bwd(const hifihr_lbs_t* h, const float* theta_d, const float* bet
  * ---------------------------------------------------------------------------------------------- */
 typedef struct hifihr_renderer hifihr_renderer_t;
 
-/* faces_h[F][3] int32 (host); image_size = output edge H (224), aa = samples per pixel edge (3; 1..3 supported);
+/* Refused / accepted, for every entry of this block (tests/test_hostsim_render_contract.py walks each of them):
+ *   Refused (HIFIHR_EINVAL, nothing launched, nothing written): a NULL handle or a NULL among the pointers an entry lists -- every one of
+ *   them except gvcolors_d of render_bwd and gmaps_acc_d of render_bwd_uv (NULL = that gradient is not wanted) and the two reserved texel
+ *   scratch arguments; B < 0; TH < 1 or TW < 1; render_fwd_uv / render_bwd_uv on a renderer without UV tables (before a successful
+ *   hifihr_renderer_set_uv).  hifihr_renderer_create: V, F or image_size <= 0, image_size > 720, aa outside 1 .. 3, a face index outside
+ *   0 .. V - 1, a NULL among out, faces_h and the four colour pointers (*out is left as it was).  hifihr_renderer_set_uv: n_uv <= 0, an
+ *   index outside 0 .. n_uv - 1, a NULL pointer (the renderer keeps the tables it had).  hifihr_renderer_set_light_mode: a mode other than 0, 1.
+ *   Accepted: B == 0 is a no-op -- nothing launched, no output and no byte of the workspace touched.  hifihr_render_workspace_bytes(NULL, .)
+ *   and (h, B < 0) return 0; the size never decreases with B.  hifihr_render_uv_scratch_bytes is 0.  hifihr_renderer_destroy(NULL) does nothing.
+ *   The image-size limit: image_size <= 720.  Up to 512 the forward runs persistent workgroups on a queue whose item code holds 64 x 64
+ *   tiles of 8 pixels; above it one workgroup per tile, and the binning kernel's 2 ceil(image_size / 8)^2 ints of dynamic LDS must fit the
+ *   64 KiB a launch may request without a function attribute: 90 x 90 tiles (csrc/render.hip, next to f3_supported).
+ *   Precondition, NOT checked: every vertex is finite and none has Z == 0 (the projection divides by Z).  Vertices behind the camera plane
+ *   (Z < 0) are inside the contract: a face that straddles the plane is rasterised per sample (pz >= 0), one wholly behind it is dropped.
+ *   A NaN, an Inf or a zero Z in verts_d gives unspecified pixels and gradients (never an out-of-range access: tile and pixel ranges come
+ *   from comparisons against the grid, a texel index from a coordinate clamped to the map first; no unclamped float becomes an index).
+ *   A pixel without a covered sample holds the sum of aa^2 background samples over aa^2 (the background colour to rounding; exactly it for
+ *   colours whose multiples are exact, 1.0 among them); alpha is exactly hits / aa^2. */
+
+/* faces_h[F][3] int32 (host); image_size = output edge H (224; 1 .. 720), aa = samples per pixel edge (3; 1..3 supported);
  * ambient3 = materials.ambient * lights.ambient, mat_diffuse3 = materials.diffuse,
  * specular3 = materials.specular * lights.specular, background3 = BlendParams.background_color. */
 int hifihr_renderer_create(hifihr_renderer_t** out, const int32_t* faces_h, int V, int F, int image_size, int aa,
@@ -171,7 +190,8 @@ int hifihr_render_fwd(const hifihr_renderer_t* h, const float* verts_d, const fl
                       int32_t* face_id_d, void* workspace_d, void* stream);
 
 /* grad_rgba_d[B][4][H][H] (the coverage channel carries no gradient, as in the reference: SURVEY.md F7) ->
- * gverts_d[B][V][3], gvcolors_d[B][V][3] (may be NULL), glight_color_d[B][3], glight_dir_d[B][3]; all overwritten.
+ * gverts_d[B][V][3], gvcolors_d[B][V][3] (may be NULL; per image also when the forward's colours were shared), glight_color_d[B][3],
+ * glight_dir_d[B][3]; all overwritten.
  * Uses float atomics: results are reproducible to rounding, not bitwise. */
 int hifihr_render_bwd(const hifihr_renderer_t* h, const float* verts_d, const float* cam_d, const float* light_color_d,
                       const float* light_dir_d, const int32_t* face_id_d, const float* grad_rgba_d, int B,

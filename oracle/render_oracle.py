@@ -72,14 +72,20 @@ def project_ndc(verts, cam):
     return torch.stack([(X * fx + Z * px) / Z, (Y * fy + Z * py) / Z, Z], dim=-1)
 
 
-def vertex_normals(verts, faces):
+def vertex_normals(verts, faces, skip=None):
     """Meshes.verts_normals_packed [recalled]: area-weighted sum of cross(v2-v1, v0-v1) over incident faces,
-    then F.normalize(eps=1e-6).  verts [B,V,3], faces LongTensor [F,3]."""
+    then F.normalize(eps=1e-6).  verts [B,V,3], faces LongTensor [F,3].  skip = (face, corner): that one face is left out of the sum of
+    its corner's vertex (the contract tests' "one contribution removed")."""
     v0, v1, v2 = verts[:, faces[:, 0]], verts[:, faces[:, 1]], verts[:, faces[:, 2]]
     fn = torch.cross(v2 - v1, v0 - v1, dim=-1)
     n = torch.zeros_like(verts)
     for k in range(3):
-        n = n.index_add(1, faces[:, k], fn)
+        fk = fn
+        if skip is not None and skip[1] == k:
+            keep = torch.ones(faces.shape[0], dtype=verts.dtype)
+            keep[skip[0]] = 0
+            fk = fn * keep.view(1, -1, 1)
+        n = n.index_add(1, faces[:, k], fk)
     return F.normalize(n, eps=1e-6, dim=-1)
 
 
@@ -141,31 +147,41 @@ def _interp(attr, faces, idx, bary):
     return (bary.unsqueeze(-1) * g).sum(-2)
 
 
-def sample_textures_uv(maps, faces_uvs, verts_uvs, idx, bary):
+def sample_textures_uv(maps, faces_uvs, verts_uvs, idx, bary, aux=None):
     """TexturesUV.sample_textures [recalled, PyTorch3D renderer/mesh/textures.py]: pixel uv = barycentric interpolation of the face's three
     uv coordinates; the maps are flipped vertically and sampled with F.grid_sample(2 uv - 1, bilinear, align_corners=True, padding border).
     maps [B,TH,TW,3], faces_uvs Long [F,3], verts_uvs [n,2], idx Long [B,S,S] (clamped face index), bary [B,S,S,3] -> [B,S,S,3]."""
     fu = verts_uvs[faces_uvs]                                   # [F,3,2]
     uv = (bary.unsqueeze(-1) * fu[idx]).sum(-2)                  # [B,S,S,2]
+    if aux is not None:
+        aux["uv"] = uv.detach()
     tex = torch.flip(maps.permute(0, 3, 1, 2), [2])
     return F.grid_sample(tex, uv * 2.0 - 1.0, mode="bilinear", align_corners=True, padding_mode="border").permute(0, 2, 3, 1)
 
 
-def render(verts, vcolors, cam, light_color, light_dir, faces, image_size=224, aa=3, consts=ShadeConsts(), point_lights=False, textures_uv=None):
-    """verts [B,V,3] (view space), vcolors [B,V,3] (TexturesVertex stand-in), cam [B,4], light_color/dir [B,3],
-    faces LongTensor [F,3].  -> rgba [B,4,H,H] after the aa x aa average pool, pix_to_face [B,S,S] (numpy)."""
+def render(verts, vcolors, cam, light_color, light_dir, faces, image_size=224, aa=3, consts=ShadeConsts(), point_lights=False, textures_uv=None,
+           p2f=None, sample_weight=None, normal_skip=None, aux=None):
+    """verts [B,V,3] (view space), vcolors [B,V,3] (TexturesVertex stand-in; [V,3] = shared by the batch), cam [B,4], light_color/dir [B,3],
+    faces LongTensor [F,3].  -> rgba [B,4,H,H] after the aa x aa average pool, pix_to_face [B,S,S] (numpy).
+    p2f [B,S,S] int32: IMPOSED visibility instead of the rasteriser's (the float64 reference of the contract tests shades the float32
+    run's winners: the discontinuity stays a bit-exact float32 target, everything behind it gets a float64 answer).  sample_weight [B,S,S]
+    multiplies every sample's rgba before the pool and normal_skip goes to vertex_normals (one contribution removed; None = the
+    reference's own arithmetic).  aux: a dict that receives, per sample, the quantities whose sign or integer part switches a branch of the
+    shading ("cosang", the specular lobe's "d", "uv"), and "hit"."""
     faces = torch.as_tensor(faces).long()
     S = image_size * aa
+    if vcolors is not None and vcolors.dim() == 2:
+        vcolors = vcolors.unsqueeze(0).expand(verts.shape[0], -1, -1)
     vndc = project_ndc(verts, cam)
-    p2f_np, _, _ = rasterize(vndc, faces, S)
+    p2f_np = np.ascontiguousarray(p2f, dtype=np.int32) if p2f is not None else rasterize(vndc, faces, S)[0]
     p2f = torch.from_numpy(p2f_np)
     bary, hit, idx = differentiable_bary(vndc, faces, p2f)
-    normals = vertex_normals(verts, faces)
+    normals = vertex_normals(verts, faces, normal_skip)
     P = _interp(verts, faces, idx, bary)
     N = _interp(normals, faces, idx, bary)
     if textures_uv is not None:                                  # (maps [B,TH,TW,3], faces_uvs [F,3], verts_uvs [n,2]); vcolors unused
         maps, faces_uvs, verts_uvs = textures_uv
-        T = sample_textures_uv(maps, torch.as_tensor(faces_uvs).long(), verts_uvs, idx, bary)
+        T = sample_textures_uv(maps, torch.as_tensor(faces_uvs).long(), verts_uvs, idx, bary, aux)
     else:
         T = _interp(vcolors, faces, idx, bary)
     dt = verts.dtype
@@ -184,11 +200,16 @@ def render(verts, vcolors, cam, light_color, light_dir, faces, image_size=224, a
     vh = F.normalize(-P, p=2, dim=-1, eps=1e-6)                         # camera centre = origin
     refl = -ld + 2 * (cosang[..., None] * nh)
     alpha = F.relu((vh * refl).sum(-1)) * mask
+    if aux is not None:
+        aux.update(cosang=cosang.detach(), d=(vh * refl).sum(-1).detach(), hit=hit)
     spec = sp * torch.pow(alpha, consts.shininess)[..., None]
     colors = (amb + md * diffuse) * T + spec
     bg = torch.tensor(consts.background, dtype=dt).view(1, 1, 1, 3)
     rgb = torch.where(hit.unsqueeze(-1), colors, bg.expand_as(colors))   # hard_rgb_blend
-    rgba = torch.cat([rgb, hit.to(dt).unsqueeze(-1)], dim=-1).permute(0, 3, 1, 2)
+    rgba = torch.cat([rgb, hit.to(dt).unsqueeze(-1)], dim=-1)
+    if sample_weight is not None:
+        rgba = rgba * sample_weight.to(dt).unsqueeze(-1)
+    rgba = rgba.permute(0, 3, 1, 2)
     rgba = F.avg_pool2d(rgba, kernel_size=aa, stride=aa)                # models_res_nimble.py:210-211
     return rgba, p2f_np
 

@@ -5826,3 +5826,678 @@ def lbs_contract_case(lib, device, V, J, S, B, seed=0):
         return True
     finally:
         lib.lbs_destroy(h)
+
+
+# ------------------------------------------------------------------------------------------------
+# The renderer contract: the ten hifihr_render* entries (csrc/render.hip, csrc/render_bwd.hip) on the lists of
+# tests/test_hostsim_render_contract.py (the GPU half: tests/test_gpu_render.py), in the tail contract's form.  A case is
+# (scene, V/F source[/options], B, image_size, aa, mode); mode: "vc" batched vertex colours, "shared" [V][3] colours, "uv" TexturesUV,
+# "point" point lights.  Options after "/" in the source: "mat" non-default materials and background, "tex384" a 384 x 384 texture (more
+# texels per backward tile than TexAcc holds), "dim" the second image lit at 1 / 100 of the first with no ambient or specular term and the upstream gradient of sum(rgb^2) / 2, "small" a mesh of a few
+# pixels, "poseN" the N-th pose after the one the case's shape gives (render_contract_admits decides when a case needs another).
+#   * face ids: bit for bit those of oracle/raster_oracle.c on the float32 projection (the discontinuity stays a float32 target);
+#   * everything behind them -- pixels and all gradients -- against render_oracle.render in FLOAT64 with those ids imposed (p2f=), per
+#     image and per quantity:  err <= min(c (sqrt(L) + K), cap) max|ref of that image|,  L the number of summed terms (aa^2 for a pixel,
+#     the largest number of samples feeding one vertex / one texel / the light for a gradient), K the conditioning of the image's worst
+#     winning face taken from the float64 reference (render_contract_cond); cap = what render_case / render_uv_case accept;
+#   * alpha = hits / aa^2 exactly; a pixel without a hit = the sum of aa^2 background samples over aa^2, exactly; a second forward gives
+#     the same bits, a second backward on the same workspace the first one's values to rounding (float atomics);
+#   * outputs prefilled with NaN, canaries around every output and behind the render_workspace_bytes(h, B) bytes of workspace.
+# No NaN / Inf / Z == 0 vertex goes in (include/hifihr.h: outside the contract).
+# ------------------------------------------------------------------------------------------------
+RENDER_CONTRACT_ENTRIES = ("renderer_create", "renderer_set_light_mode", "renderer_set_uv", "renderer_destroy", "render_workspace_bytes",
+                           "render_uv_scratch_bytes", "render_fwd", "render_bwd", "render_fwd_uv", "render_bwd_uv")
+RENDER_MAX_IMAGE = 720                # include/hifihr.h: the largest image_size hifihr_renderer_create accepts
+# kind: (c, cap) as in LAYER_CONTRACT_C: c = 4 x the worst err / ((sqrt(L) + K) max|ref|) of render_contract_ref run in float32 (plain fp32
+# torch on the CPU) against its float64 run over RENDER_CASES of tests/test_hostsim_render_contract.py (tools/render_contract_c.py prints
+# them); cap = the tolerance render_case / render_uv_case use for the same quantity, relative to max|ref| (pixels: 2e-5 absolute on
+# values of the order of 1).
+RENDER_CONTRACT_C = {
+    "render_rgb": (5.1e-7, 2e-5),     # 1.27e-07 x 4      rgb, L = aa^2                                    (render_case atol 2e-5)
+    #                                                     (+ render_device_allowance on the GPU: the approximate reciprocals of its forward)
+    "render_gv": (1.7e-6, 2e-3),      # 4.20e-07 x 4      gverts, L = samples on the faces of one vertex     (render_case 2e-3)
+    "render_gc": (3.4e-7, 2e-3),      # 8.47e-08 x 4      gvcolors, same L                                   (render_case 2e-3)
+    "render_gmap": (1.7e-6, 3e-3),    # 4.14e-07 x 4      gmaps, L = samples with a tap on one texel         (render_uv_case 3e-3)
+    "render_glc": (2.7e-6, 2e-3),     # 6.85e-07 x 4      glight_color, L = covered samples of the image     (render_case 2e-3)
+    "render_gld": (2.0e-6, 2e-3),     # 4.89e-07 x 4      glight_dir, same L                                 (render_case 2e-3)
+}
+RENDER_CONTRACT_KINDS = tuple(RENDER_CONTRACT_C)
+LAYER_CONTRACT_C.update(RENDER_CONTRACT_C)
+RENDER_LAUNCHED = set()               # kernels the emulator launched under the renderer cases (the reach test reads it)
+RENDER_COUNTS = {"merges": 0, "resolves": 0, "strips": 0, "slotless": 0, "vertex_overflow": 0, "texel_overflow": 0}
+RENDER_NONDEFAULT = dict(ambient=(0.3, 0.5, 0.25), mat_diffuse=(0.9, 0.6, 0.7), specular=(0.1, 0.04, 0.2), shininess=12.0,
+                         background=(0.3, 0.75, 0.1))
+RENDER_DIM = dict(ambient=(0.0, 0.0, 0.0), mat_diffuse=(0.8, 0.8, 0.8), specular=(0.0, 0.0, 0.0), shininess=30.0, background=(0.0, 0.0, 0.0))
+_RENDER_MEMO = {}
+
+
+def _render_drain(lib, device):
+    """Launch log and path counters of the emulator since the last look, added to RENDER_LAUNCHED / RENDER_COUNTS (nothing on a GPU)."""
+    if device != "cpu":
+        return None
+    import ctypes
+    names = [k.replace(" ", "") for k in launch_log(lib)]
+    RENDER_LAUNCHED.update(names)
+    f4, b2 = (ctypes.c_int * 4)(), (ctypes.c_int * 2)()
+    lib.c.hifihr_hostsim_render_fwd3_counts(f4, 1)
+    lib.c.hifihr_hostsim_render_bwd_counts(b2, 1)
+    for k, v in zip(RENDER_COUNTS, list(f4) + list(b2)):
+        RENDER_COUNTS[k] += v
+    return names
+
+
+def _render_refuses(entry, lib, device, call, guards, what):
+    """HIFIHR_EINVAL, every output and guard untouched, nothing launched."""
+    _render_drain(lib, device)
+    _refuses(entry, call, guards, f"{entry}: {what}")
+    left = _render_drain(lib, device)
+    assert not left, f"{entry}: {what}: refused but launched {left}"
+
+
+def icosahedron():
+    """12 vertices on the unit sphere, 20 faces."""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = np.array([(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1),
+                  (-t, 0, -1), (-t, 0, 1)], dtype=np.float32)
+    f = np.array([(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+                  (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)], dtype=np.int32)
+    return v / np.linalg.norm(v[0]), f
+
+
+def _render_tables():
+    if "tables" not in _RENDER_MEMO:
+        from hifihr_amd.mano_tables import synthetic_mano_tables
+        _RENDER_MEMO["tables"] = synthetic_mano_tables(0)
+    return _RENDER_MEMO["tables"]
+
+
+def render_contract_inputs(case):
+    """The inputs of one case, float32, and the float32 oracle's face ids for them ("p2f"); memoised: the runner, the detection test and
+    the measurement share them."""
+    if case in _RENDER_MEMO:
+        return _RENDER_MEMO[case]
+    from oracle import render_oracle as ro
+    scene, src, B, H, aa, mode = case
+    src, *opts = src.split("/")
+    seed = 1000 + 7 * H + 3 * aa + B + len(scene) + sum(int(o[4:]) for o in opts if o.startswith("pose"))
+    gen = torch.Generator().manual_seed(seed)
+    hv, _, cam, lc, ld = make_render_inputs(_render_tables(), B, seed, H)
+    centre = hv.mean(1, keepdim=True)                                     # [B,1,3]: in front of the camera, z in 0.6 .. 0.8
+    fx = cam[:, 0].view(B, 1)
+    if src == "mano":
+        verts, faces = hv, np.asarray(_render_tables().faces, dtype=np.int32)
+    elif src == "ico":
+        iv, faces = icosahedron()
+        verts = torch.from_numpy(iv)[None] * (0.006 if "small" in opts else 0.07) + centre
+    elif src == "skin":
+        mv, faces = nimble_sized_mesh(B, seed)
+        verts = mv + centre
+    elif src == "one":
+        faces = np.array([[0, 1, 2]], dtype=np.int32)
+        verts = torch.tensor([[-0.08, -0.05, 0.0], [0.09, -0.04, 0.05], [0.0, 0.1, -0.03]])[None] * (0.1 if "small" in opts else 1.0) + centre
+    elif src == "quads96":
+        # 96 quads, each larger than the image, at distinct depths and with their own small tilt (the planes cross: the winner changes
+        # from sample to sample); quads 11 and 51 are copies of 10 and 50: coplanar at identical z, the lower face index wins
+        Q = 96
+        corners = torch.tensor([[-1.0, -1.0], [1.0, -1.0], [1.0, 1.0], [-1.0, 1.0]])
+        order = torch.randperm(Q, generator=gen).float()
+        order[[10, 50]] = 0.0                                             # (the copied quads in front: their ties decide samples)
+        z = 0.5 + 0.004 * order
+        tilt = 0.05 * (torch.rand(Q, 4, generator=gen) - 0.5)
+        tilt[50] = -tilt[10]
+        zq = z.view(Q, 1) + tilt
+        xy = corners.view(1, 4, 2) * (0.4 + 0.04 * torch.rand(Q, 4, 2, generator=gen)) * zq.view(Q, 4, 1)      # (no two diagonals coincide)
+        quad = torch.cat([xy, zq.view(Q, 4, 1)], -1)
+        quad[11], quad[51] = quad[10], quad[50]
+        verts = quad.reshape(1, 4 * Q, 3).repeat(B, 1, 1)
+        base = 4 * np.arange(Q, dtype=np.int32)[:, None]
+        faces = np.concatenate([base + np.array([[0, 1, 2]]), base + np.array([[0, 2, 3]])], 1).reshape(-1, 3).astype(np.int32)
+        cam = cam.clone(); cam[:, 2:] = 0.0
+    elif src == "tris":
+        # large triangles with one or two vertices BEHIND the camera plane (Z negative and finite, never 0: NDC coordinates huge but
+        # finite; per sample pz >= 0 decides), next to one wholly in front
+        # (without clipping, the interpolated depth is z0 z1 z2 / denom: ONE vertex behind the camera makes it negative wherever the
+        # corrected barycentrics are positive -- faces 0 and 3 cover nothing, after the full arithmetic on every sample of their boxes --
+        # and with TWO behind the covered samples are those of the NDC bounding box in the cone beyond the front vertex: face 1 is laid
+        # out in NDC with that vertex inside the image; face 3's vertex at Z = -1e-3 projects hundreds of image widths away)
+        ndcz = torch.tensor([[[-0.8, -0.7, 0.8], [0.8, 0.9, 0.8], [0.1, -0.1, -0.5]],
+                             [[0.1, -0.1, 0.6], [-0.9, -0.8, -0.3], [0.9, 0.9, -0.5]]])
+        cam = cam.clone(); cam[:, 2:] = 0.0
+        laid = torch.stack([ndcz[..., 0].view(1, 2, 3) * ndcz[..., 2] / cam[:, 0].view(B, 1, 1), ndcz[..., 1].view(1, 2, 3) * ndcz[..., 2] / cam[:, 1].view(B, 1, 1),
+                            ndcz[..., 2].view(1, 2, 3).expand(B, -1, -1)], -1)
+        tri = torch.tensor([[[-0.25, -0.1, 1.0], [0.2, -0.15, 1.1], [0.05, 0.2, 0.9]],
+                            [[0.1, 0.1, 0.7], [-0.15, 0.12, 0.75], [0.0, -0.1, -1e-3]]])
+        verts = torch.cat([laid.reshape(B, 6, 3), tri.reshape(1, 6, 3).repeat(B, 1, 1)], 1)
+        verts = verts * (1.0 + 0.1 * torch.arange(B, dtype=torch.float32).view(B, 1, 1))
+        faces = np.arange(12, dtype=np.int32).reshape(4, 3)
+    elif src == "odd":
+        # f1 shares all three vertices with f0 (a tie at every sample: f0 wins); f3 repeats a vertex and f4 is collinear (zero area);
+        # vertex 9 belongs to no face (zero normal sum: normalize's epsilon path, zero gradient)
+        verts = torch.tensor([[-0.1, -0.08, 0.0], [0.1, -0.07, 0.02], [0.0, 0.1, -0.02], [-0.05, -0.1, 0.05], [0.12, 0.0, 0.06],
+                              [-0.08, 0.09, 0.04], [-0.1, 0.0, -0.05], [0.0, 0.0, -0.05], [0.1, 0.0, -0.05], [0.02, 0.03, -0.1]])[None] + centre
+        faces = np.array([[0, 1, 2], [0, 1, 2], [3, 4, 5], [3, 3, 4], [6, 7, 8]], dtype=np.int32)
+    elif src == "confetti196":
+        # 14 x 14 disjoint small triangles (V = 3 F = 588 > the 512 slots of BwdAcc) inside ONE 16 x 16-pixel backward tile; inradius
+        # 0.034 NDC > half the diagonal of a sample cell at S = 48 (0.0295): every triangle covers at least one sample
+        n = 14
+        c = (torch.arange(n, dtype=torch.float32) + 0.5) / n * 2 - 1
+        cy, cx = torch.meshgrid(c, c, indexing="ij")
+        ang = torch.rand(n * n, 1, generator=gen) * 6.2832 + torch.tensor([[0.0, 2.0944, 4.1888]])
+        ndc = torch.stack([cx.reshape(-1, 1) + 0.068 * torch.cos(ang), cy.reshape(-1, 1) + 0.068 * torch.sin(ang)], -1)     # [F,3,2]
+        zz = 0.6 + 0.2 * torch.rand(n * n, 3, generator=gen)
+        cam = cam.clone(); cam[:, 2:] = 0.0
+        v1 = torch.cat([ndc * zz.unsqueeze(-1), zz.unsqueeze(-1)], -1).reshape(1, 3 * n * n, 3).repeat(B, 1, 1)
+        verts = torch.cat([v1[..., :1] / cam[:, 0].view(B, 1, 1), v1[..., 1:2] / cam[:, 1].view(B, 1, 1), v1[..., 2:]], -1)
+        faces = np.arange(3 * n * n, dtype=np.int32).reshape(-1, 3)
+    else:
+        raise ValueError(src)
+    verts = verts.expand(B, -1, -1).clone() if verts.shape[0] != B else verts.clone()
+    if scene == "offscreen":
+        # image k: across the left / right / top / bottom border, wholly outside, the principal point far off-centre (the mesh moved with it,
+        # half an image off); an NDC shift of s is a move of s Z / fx in view space
+        shifts = [(1.0, 0.0), (-1.0, 0.0), (0.0, 1.0), (0.0, -1.0), (4.0, 0.3), (0.5, -0.4)]
+        cam = cam.clone()
+        for b in range(B):
+            sx, sy = shifts[b % 6]
+            if b % 6 == 5:
+                cam[b, 2], cam[b, 3] = 1.7, -1.3
+            zc = float(centre[b, 0, 2])
+            verts[b, :, 0] += (sx - float(cam[b, 2]) * (b % 6 == 5)) * zc / float(cam[b, 0])
+            verts[b, :, 1] += (sy - float(cam[b, 3]) * (b % 6 == 5)) * zc / float(cam[b, 1])
+    V = verts.shape[1]
+    if scene == "degenerate":
+        ld = ld.clone(); ld[0] = 0.0                                      # a zero light direction
+        lc = lc.clone(); lc[0] = torch.tensor([-1.0, 1.0, 1.0])          # the ends of the hardtanh range
+        if B > 1:
+            lc[1] = torch.tensor([1.0, -1.0, -1.0])
+    consts = dict(ambient=(0.5, 0.5, 0.5), mat_diffuse=(0.8, 0.8, 0.8), specular=(0.04, 0.04, 0.04), shininess=30.0, background=(1.0, 1.0, 1.0))
+    if "mat" in opts:
+        consts = dict(RENDER_NONDEFAULT)
+    if "dim" in opts:
+        consts = dict(RENDER_DIM)
+        lc = lc.abs() + 0.2
+        lc[1] = lc[0] * 0.01
+        ld = ld.clone(); ld[1] = ld[0]
+        verts[1] = verts[0]
+        cam = cam.clone(); cam[1] = cam[0]
+    if mode == "point":
+        lc = torch.full((B, 3), 0.3)
+        ld = torch.tensor([[0.0, 1.0, 0.0]]).repeat(B, 1)
+        if B > 1:
+            ld[1] = torch.tensor([0.1, -0.2, 0.3])
+    inp = {"case": case, "verts": verts.contiguous(), "faces": faces, "V": V, "F": len(faces), "cam": cam.contiguous(), "lc": lc.contiguous(),
+           "ld": ld.contiguous(), "consts": consts, "point": mode == "point", "uv": None, "vcol": None, "B": B, "H": H, "aa": aa}
+    if mode == "uv":
+        TH, TW = (384, 384) if "tex384" in opts else (24, 40)
+        fu, vu = synthetic_uv_tables(faces, V, seed)
+        # a smooth image (a skin texture is one): under a coarse raster a random texture is noise -- one sliver's barycentrics, off by
+        # 1e-5, move its sample across texels that differ by 1 -- and no float32 evaluation is within 2e-5 of the float64 pixel there
+        yy, xx = torch.meshgrid(torch.arange(TH) / TH, torch.arange(TW) / TW, indexing="ij")
+        ph = torch.rand(B, 1, 1, 3, generator=gen) * 6.2832
+        fr = torch.tensor([5.0, 3.0, 4.0]).view(1, 1, 1, 3)
+        maps = 0.5 + 0.4 * torch.sin(fr * xx[None, :, :, None] + (8.0 - fr) * yy[None, :, :, None] + ph)
+        inp["uv"] = (fu, vu, maps.contiguous())
+    else:
+        inp["vcol"] = 0.3 + 0.6 * torch.rand(*((V, 3) if mode == "shared" else (B, V, 3)), generator=gen)
+    w = torch.randn(B, 4, H, H, generator=gen)
+    if "dim" in opts:
+        w[1] = w[0]
+    inp["w"] = w
+    vndc = ro.project_ndc(inp["verts"], inp["cam"])
+    assert bool(torch.isfinite(vndc).all()) and bool(torch.isfinite(inp["verts"]).all())
+    inp["p2f"] = ro.rasterize(vndc, torch.as_tensor(faces).long(), H * aa)[0]
+    if "dim" in opts:                                                     # the gradient of sum(rgb^2) / 2: 1e-4 of the first image's in the second
+        r32, _ = ro.render(inp["verts"], inp["vcol"], inp["cam"], inp["lc"], inp["ld"], torch.as_tensor(faces).long(), image_size=H, aa=aa,
+                           consts=ro.ShadeConsts(**consts), p2f=inp["p2f"])
+        w = r32.clone()
+        w[:, 3] = 0
+        inp["w"] = w
+    inp["w"] = (w * render_kink_free(inp).view(B, 1, H, H)).contiguous()
+    _RENDER_MEMO[case] = inp
+    return inp
+
+
+RENDER_KINK_MARGIN = (1e-4, 1e-2)      # |cosang|, |d| of the unit vectors; distance of a texel coordinate from an integer
+
+
+def render_kink_free(inp):
+    """[B,H,H] 0 / 1: pixels that take an upstream gradient.  The shading has kinks -- relu(cosang), the specular lobe's relu(d) under its
+    cosang > 0 mask, the bilinear quad floor(ix), floor(iy) and the border clamp of the texture -- where the VALUE is continuous and the
+    GRADIENT jumps: a sample within rounding of one takes either side in float32, and no float32 evaluation, torch's included, can be held
+    to the float64 gradient there (as for visibility, which the imposed face ids take out).  A pixel with a covered sample inside
+    RENDER_KINK_MARGIN of a kink, judged on the float64 reference, gets no upstream gradient; its pixel VALUE is compared like every other."""
+    from oracle import render_oracle as ro
+    B, H, aa, dt = inp["B"], inp["H"], inp["aa"], torch.float64
+    aux = {}
+    tuv = None if inp["uv"] is None else (inp["uv"][2].to(dt), torch.from_numpy(inp["uv"][0]).long(), torch.from_numpy(inp["uv"][1]).to(dt))
+    vc = None if inp["vcol"] is None else inp["vcol"].to(dt)
+    ro.render(inp["verts"].to(dt), vc, inp["cam"].to(dt), inp["lc"].to(dt), inp["ld"].to(dt), torch.as_tensor(inp["faces"]).long(), image_size=H,
+              aa=aa, consts=ro.ShadeConsts(**inp["consts"]), point_lights=inp["point"], textures_uv=tuv, p2f=inp["p2f"], aux=aux)
+    m_cos, m_tex = RENDER_KINK_MARGIN
+    near = (aux["cosang"].abs() < m_cos) | ((aux["cosang"] > 0) & (aux["d"].abs() < m_cos))
+    if tuv is not None:
+        TH, TW = tuv[0].shape[1], tuv[0].shape[2]
+        for k, T in ((0, TW), (1, TH)):
+            t = aux["uv"][..., k] * (T - 1)
+            near = near | ((t - t.round()).abs() < m_tex) | (t < m_tex) | (t > T - 1 - m_tex)
+    near = near & aux["hit"]
+    return 1.0 - near.view(B, H, aa, H, aa).any(4).any(2).float()
+
+
+def render_drop_choice(inp, ref):
+    """The contributions the detection test removes: the covered sample of the LAST image that has one whose pixel carries the largest
+    upstream gradient, and the first corner of the face it shows."""
+    hit = inp["p2f"] >= 0
+    if not hit.any():
+        return None
+    b = max(k for k in range(inp["B"]) if hit[k].any())
+    aa = inp["aa"]
+    wpix = inp["w"][b, :3].abs().sum(0).numpy().repeat(aa, 0).repeat(aa, 1)
+    y, x = np.unravel_index(int(np.argmax(np.where(hit[b], wpix, -1.0))), hit[b].shape)
+    return b, int(y), int(x), int(inp["p2f"][b, y, x])
+
+
+def render_contract_ref(inp, dt=torch.float64, drop=None):
+    """The checked quantities, per image, of render_oracle.render run in `dt` on the float32 run's face ids: "rgb" [B,3,H,H], "alpha",
+    "gverts", "gvcolors" (vertex colours) or "gmaps" (UV), "glight_color", "glight_dir" for the loss sum(rgba * w).
+    drop removes ONE contribution (render_drop_choice gives b, y, x, f):
+      ("sample", b, y, x)   that sample from its pixel's aa x aa block -- and with it from every gradient sum it feeds;
+      ("normal", f, k)      face f from the normal sum of its corner k's vertex;
+      ("tap", b, y, x)      the largest of that sample's bilinear taps from the texture gradient."""
+    from oracle import render_oracle as ro
+    B, H, aa = inp["B"], inp["H"], inp["aa"]
+    leaf = lambda t: t.to(dt).clone().requires_grad_(True)
+    v, lc, ld = leaf(inp["verts"]), leaf(inp["lc"]), leaf(inp["ld"])
+    faces = torch.as_tensor(inp["faces"]).long()
+    consts = ro.ShadeConsts(**inp["consts"])
+    sw = skip = None
+    if drop is not None and drop[0] == "sample":
+        sw = torch.ones(B, H * aa, H * aa, dtype=dt)
+        sw[drop[1], drop[2], drop[3]] = 0
+    if drop is not None and drop[0] == "normal":
+        skip = (drop[1], drop[2])
+    if inp["uv"] is not None:
+        tex = leaf(inp["uv"][2])
+        tuv = (tex, torch.from_numpy(inp["uv"][0]).long(), torch.from_numpy(inp["uv"][1]).to(dt))
+        rgba, _ = ro.render(v, None, inp["cam"].to(dt), lc, ld, faces, image_size=H, aa=aa, consts=consts, textures_uv=tuv, p2f=inp["p2f"],
+                            sample_weight=sw, normal_skip=skip)
+    else:
+        vc = inp["vcol"] if inp["vcol"].dim() == 3 else inp["vcol"].unsqueeze(0).expand(B, -1, -1)
+        tex = leaf(vc)
+        rgba, _ = ro.render(v, tex, inp["cam"].to(dt), lc, ld, faces, image_size=H, aa=aa, consts=consts, point_lights=inp["point"],
+                            p2f=inp["p2f"], sample_weight=sw, normal_skip=skip)
+    (rgba * inp["w"].to(dt)).sum().backward()
+    z = lambda t: t.grad.detach() if t.grad is not None else torch.zeros_like(t)
+    out = {"rgb": rgba.detach()[:, :3], "alpha": rgba.detach()[:, 3], "gverts": z(v), "glight_color": z(lc),
+           "glight_dir": torch.zeros_like(ld) if inp["point"] else z(ld)}
+    out["gmaps" if inp["uv"] is not None else "gvcolors"] = z(tex)
+    if drop is not None and drop[0] == "tap":
+        one = torch.zeros(B, H * aa, H * aa, dtype=dt)
+        one[drop[1], drop[2], drop[3]] = 1
+        t2 = leaf(inp["uv"][2])
+        r2, _ = ro.render(inp["verts"].to(dt), None, inp["cam"].to(dt), inp["lc"].to(dt), inp["ld"].to(dt), faces, image_size=H, aa=aa, consts=consts,
+                          textures_uv=(t2, tuv[1], tuv[2]), p2f=inp["p2f"], sample_weight=one)
+        (r2 * inp["w"].to(dt)).sum().backward()
+        g1 = t2.grad[drop[1]]                                             # the sample's (up to) four taps
+        ty, tx = np.unravel_index(int(g1.abs().sum(-1).argmax()), g1.shape[:2])
+        out["gmaps"] = out["gmaps"].clone()
+        out["gmaps"][drop[1], ty, tx] -= g1[ty, tx]
+    return out
+
+
+def render_contract_cond(inp):
+    """Per image: (L of a vertex gradient, L of a light gradient, L of a texel gradient, K).  L: the largest number of samples on the faces
+    of one vertex / covered samples of the image / samples with a bilinear tap on one texel.  K: the conditioning of the barycentrics of the
+    image's worst WINNING face, from the float64 reference: max(1, |x|, |y|) (dx + dy) / |area| of its NDC coordinates, bounding box and
+    edge-function area (float32 holds a projected vertex to 2^-24 of its coordinate; the barycentrics move by that over the triangle's
+    height, area / extent: about 2 / extent for a well-shaped face, large for a sliver) times the largest sum |bary_k| of a covered sample (1 in front of the camera; the perspective correction cancels when a
+    vertex lies behind it), times -- TexturesUV -- 1 + (T - 1) max |step between neighbouring texels|, what an error of uv is worth in
+    the texel.  0 where nothing is covered."""
+    from oracle import render_oracle as ro
+    faces = torch.as_tensor(inp["faces"]).long()
+    vndc = ro.project_ndc(inp["verts"].double(), inp["cam"].double())
+    p2f = torch.from_numpy(inp["p2f"])
+    bary, hit, idx = ro.differentiable_bary(vndc, faces, p2f)
+    out = []
+    for b in range(inp["B"]):
+        ids = inp["p2f"][b][inp["p2f"][b] >= 0]
+        if ids.size == 0:
+            out.append((1, 1, 1, 0.0))
+            continue
+        cnt_f = np.bincount(ids, minlength=inp["F"])
+        cnt_v = np.zeros(inp["V"], dtype=np.int64)
+        for k in range(3):
+            np.add.at(cnt_v, inp["faces"][:, k], cnt_f)
+        win = torch.from_numpy(np.unique(ids)).long()
+        fv = vndc[b][faces[win]]                                           # [n,3,3]
+        ext = (fv[..., 0].amax(1) - fv[..., 0].amin(1)) + (fv[..., 1].amax(1) - fv[..., 1].amin(1))
+        area = ro._edge(fv[:, 2, 0], fv[:, 2, 1], fv[:, 0, 0], fv[:, 0, 1], fv[:, 1, 0], fv[:, 1, 1]).abs()
+        cmax = fv[..., :2].abs().amax((1, 2)).clamp(min=1.0)
+        K = float((cmax * ext / area).max()) * float(bary[b][hit[b]].abs().sum(-1).max())
+        Lt = 1
+        if inp["uv"] is not None:
+            fu, vu, maps = inp["uv"]
+            TH, TW = maps.shape[1], maps.shape[2]
+            uv = (bary[b][hit[b]].unsqueeze(-1) * torch.from_numpy(vu).double()[torch.from_numpy(fu).long()][idx[b][hit[b]]]).sum(-2)
+            ix = (uv[:, 0] * (TW - 1)).clamp(0, TW - 1); iy = (uv[:, 1] * (TH - 1)).clamp(0, TH - 1)
+            x0, y0 = ix.floor().long(), iy.floor().long()
+            x1, y1 = (x0 + 1).clamp(max=TW - 1), (y0 + 1).clamp(max=TH - 1)
+            taps = torch.stack([y0 * TW + x0, y0 * TW + x1, y1 * TW + x0, y1 * TW + x1], 1)
+            Lt = int(torch.bincount(taps.reshape(-1), minlength=TH * TW).max())
+            # the texel moves with uv at (T - 1) x the step between neighbouring texels: an error of the barycentrics is worth that much more
+            m = maps[b].double()
+            K *= 1.0 + max(float((m[:, 1:] - m[:, :-1]).abs().max()) * (TW - 1), float((m[1:] - m[:-1]).abs().max()) * (TH - 1))
+        out.append((max(1, int(cnt_v.max())), int(ids.size), Lt, K))
+    return out
+
+
+def render_contract_ref_once(case):
+    """(float64 reference, conditioning) of a case: computed once, shared by the runner and the detection tests, left unchanged."""
+    key = ("ref", case)
+    if key not in _RENDER_MEMO:
+        inp = render_contract_inputs(case)
+        _RENDER_MEMO[key] = (render_contract_ref(inp), render_contract_cond(inp))
+    return _RENDER_MEMO[key]
+
+
+def render_bound(kind, ref, L, K, approx=0.0):
+    """min(c (sqrt(L) + K) + approx, cap) max|ref|: layer_bound with cond = K max|ref|, and never above the older case's tolerance.
+    approx: render_device_allowance (the device's forward only)."""
+    c, cap = LAYER_CONTRACT_C[kind]
+    scale = float(ref.abs().max()) if ref.numel() else 0.0
+    return min(layer_bound(kind, ref, L, K * scale) + approx * scale, cap * scale)
+
+
+def render_device_allowance(inp, device):
+    """What the DEVICE build's forward may add to the emulator's error, relative to max|rgb| -- not measured on the kernel: from the
+    documented accuracy of the instructions shade_fwd_fast and resolve_shade2 use where the emulator divides and takes square roots
+    exactly.  V_RCP_F32 and V_RSQ_F32 are accurate to 1 ulp (2^-23 relative; CDNA ISA guide).  Along one sample: rcp(area) and rcp(denom)
+    put 2 ulp on the barycentrics and so on P, N and the texel; rsq on the normal, the view vector and -- point lights -- the light
+    vector put 1 ulp on each unit vector.  Diffuse term: texel (2) x cosang (2 + 1 + 1) = 6 ulp of (ambient + diffuse) texel <= max|rgb|.
+    Specular term: d = view . reflection carries the same 6 ulp, the power multiplies a relative error by the shininess: 6 s ulp of
+    specular d^s <= max(specular)."""
+    if device == "cpu":
+        return 0.0
+    return 2.0 ** -23 * (6.0 + 6.0 * inp["consts"]["shininess"] * max(inp["consts"]["specular"]))
+
+
+def render_passes(kind, got, ref, L, K):
+    return layer_err(got, ref) <= render_bound(kind, ref, L, K)
+
+
+def _render_close(entry, kind, got, ref, L, K, what, approx=0.0):
+    err, bound = layer_err(got, ref), render_bound(kind, ref, L, K, approx)
+    _tail_ratio(entry, err, bound)
+    assert err <= bound, f"{what}: err {err:.3e} vs bound {bound:.3e} (kind {kind}, max|ref| {float(ref.abs().max()):.3e}, L {L}, K {K:.3g})"
+
+
+def render_quantities(inp):
+    """(name of the reference's quantity, kind, which L of render_contract_cond) of the backward."""
+    tex = ("gmaps", "render_gmap", 2) if inp["uv"] is not None else ("gvcolors", "render_gc", 0)
+    return [("gverts", "render_gv", 0), tex, ("glight_color", "render_glc", 1), ("glight_dir", "render_gld", 1)]
+
+
+def render_legacy_passes(got, ref, tol=2e-3):
+    """render_case's criterion: ONE maximum over the batch and all elements."""
+    return float((got - ref).abs().max()) / (float(ref.abs().max()) + 1e-12) < tol
+
+
+def render_contract_float32_errors(case):
+    """[(image, kind, L, K, err, max|ref|)] of the reference run in float32 (plain torch on the CPU) against its float64 run; once per
+    case: the measurement of RENDER_CONTRACT_C and the admission of a case share it."""
+    key = ("f32", case)
+    if key not in _RENDER_MEMO:
+        inp = render_contract_inputs(case)
+        (r64, cond), r32 = render_contract_ref_once(case), render_contract_ref(inp, torch.float32)
+        rows = []
+        for b in range(inp["B"]):
+            for name, kind, L in [("rgb", "render_rgb", inp["aa"] ** 2)] + [(n, k, cond[b][i]) for n, k, i in render_quantities(inp)]:
+                scale = float(r64[name][b].abs().max())
+                if scale > 0:
+                    rows.append((b, kind, L, cond[b][3], layer_err(r32[name][b], r64[name][b]), scale))
+        _RENDER_MEMO[key] = rows
+    return _RENDER_MEMO[key]
+
+
+def render_contract_measure(cases):
+    """The float32 run of the reference against its float64 run: kind -> worst err / ((sqrt(L) + K) max|ref|) (x 4 = RENDER_CONTRACT_C)."""
+    worst = {k: 0.0 for k in RENDER_CONTRACT_KINDS}
+    for case in cases:
+        for b, kind, L, K, err, scale in render_contract_float32_errors(case):
+            worst[kind] = max(worst[kind], err / ((L ** 0.5 + K) * scale))
+    return worst
+
+
+RENDER_ADMIT = 0.5                     # the share of a cap the float32 run of the reference may use up on a case of the lists
+
+
+def render_contract_admits(case):
+    """What keeps a case OUT of the lists: [(image, kind, err / max|ref|, cap)] where the reference's own float32 run is further than
+    RENDER_ADMIT x cap from its float64 run.  The caps are the older cases' tolerances and do not grow with the conditioning: on a pose
+    whose winning sliver costs plain float32 arithmetic most of a cap, a correct float32 kernel that merely rounds elsewhere -- another
+    summation order, a reciprocal for a division -- cannot be held to it, and a failure there says nothing about the kernel.  Two float32
+    evaluations with independent rounding are up to twice one's error apart, hence the half.  Decided on the reference alone, never on a
+    kernel's output; such a case takes its next pose ("poseN")."""
+    return [(b, kind, err / scale, LAYER_CONTRACT_C[kind][1]) for b, kind, L, K, err, scale in render_contract_float32_errors(case)
+            if err > RENDER_ADMIT * LAYER_CONTRACT_C[kind][1] * scale]
+
+
+def render_contract_case(lib, device, case):
+    """One accepted case through create / set_light_mode / set_uv / workspace_bytes / fwd / bwd / destroy (module comment above)."""
+    inp = render_contract_inputs(case)
+    ref, cond = render_contract_ref_once(case)
+    B, H, aa, V, F_ = inp["B"], inp["H"], inp["aa"], inp["V"], inp["F"]
+    S, uv, what = H * aa, inp["uv"] is not None, str(case)
+    fwd_e, bwd_e = ("render_fwd_uv", "render_bwd_uv") if uv else ("render_fwd", "render_bwd")
+    _render_drain(lib, device)
+    h = lib.renderer_create(inp["faces"], V, image_size=H, aa=aa, **inp["consts"])
+    _layer_log("renderer_create", True)
+    try:
+        lib.renderer_set_light_mode(h, inp["point"])
+        _layer_log("renderer_set_light_mode", True)
+        assert lib.render_uv_scratch_bytes(h, B) == 0
+        _layer_log("render_uv_scratch_bytes", True)
+        if uv:
+            lib.renderer_set_uv(h, inp["uv"][0], inp["uv"][1])
+            _layer_log("renderer_set_uv", True)
+        nws = lib.render_workspace_bytes(h, B)
+        assert nws > 0 and lib.render_workspace_bytes(h, B + 1) >= nws >= lib.render_workspace_bytes(h, max(B - 1, 0))
+        _layer_log("render_workspace_bytes", True)
+        G = Guards(device)
+        ws = G.out(nws, dtype=torch.uint8, fill=0xFF)
+        dv, dcam, dlc, dld, dw = (G.inp(inp[k]) for k in ("verts", "cam", "lc", "ld", "w"))
+        dtex = G.inp(inp["uv"][2] if uv else inp["vcol"])
+        rgba = [G.out(B, 4, H, H, fill=float("nan")) for _ in range(2)]
+        fid = [G.out(B, S, S, dtype=torch.int32, fill=_POISON[torch.int32]) for _ in range(2)]
+
+        def fwd(k):
+            if uv:
+                lib.render_fwd_uv(h, dv, dtex, dcam, dlc, dld, rgba[k], fid[k], None, ws)
+            else:
+                lib.render_fwd(h, dv, dtex, dcam, dlc, dld, rgba[k], fid[k], ws)
+            G.intact(f"{what}: forward {k}")
+
+        fwd(0)
+        got_fid = fid[0].cpu().numpy()
+        assert np.array_equal(got_fid, inp["p2f"]), f"{what}: {int((got_fid != inp['p2f']).sum())} face ids differ from the float32 oracle's"
+        _layer_log(fwd_e, True, 0.0)
+        got = rgba[0].cpu()
+        hits = torch.from_numpy((inp["p2f"] >= 0).reshape(B, H, aa, H, aa).sum((2, 4)).astype(np.float32))
+        assert torch.equal(got[:, 3], hits / np.float32(aa * aa)), f"{what}: alpha is not the hit fraction"
+        bgsum = np.zeros(3, dtype=np.float32)
+        for _ in range(aa * aa):
+            bgsum = bgsum + np.asarray(inp["consts"]["background"], dtype=np.float32)
+        bgpix = torch.from_numpy(bgsum / np.float32(aa * aa))
+        empty = hits == 0
+        assert bool((got[:, :3].permute(0, 2, 3, 1)[empty] == bgpix).all()), f"{what}: a pixel without a hit is not the background"
+        for b in range(B):
+            _render_close(fwd_e, "render_rgb", got[b, :3], ref["rgb"][b], aa * aa, cond[b][3], f"{what}: rgb of image {b}",
+                          render_device_allowance(inp, device))
+        fwd(1)
+        assert torch.equal(fid[1], fid[0]) and torch.equal(rgba[1].view(torch.int32), rgba[0].view(torch.int32)), f"{what}: a second forward differs"
+        _layer_log(fwd_e, True, 0.0)
+
+        tshape = tuple(inp["uv"][2].shape) if uv else (B, V, 3)
+        first = None
+        for rep in range(2):                                              # the second run finds the accumulators dirty (render_ws_mark_clean)
+            gv, glc, gld = G.out(B, V, 3, fill=float("nan")), G.out(B, 3, fill=float("nan")), G.out(B, 3, fill=float("nan"))
+            gt = G.out(*tshape, fill=0.0 if uv else float("nan"))         # gmaps is ACCUMULATED onto the caller's zeros
+            if uv:
+                lib.render_bwd_uv(h, dv, dtex, dcam, dlc, dld, fid[0], dw, None, None, gv, gt, glc, gld, ws)
+            else:
+                lib.render_bwd(h, dv, dcam, dlc, dld, fid[0], dw, gv, gt, glc, gld, ws)
+            G.intact(f"{what}: backward {rep}")
+            outs = {"gverts": gv, "gmaps" if uv else "gvcolors": gt, "glight_color": glc, "glight_dir": gld}
+            for b in range(B):
+                for name, kind, li in render_quantities(inp):
+                    _render_close(bwd_e, kind, outs[name][b], ref[name][b], cond[b][li], cond[b][3], f"{what}: {name} of image {b} (run {rep})")
+            if inp["point"]:
+                assert float(gld.abs().max()) == 0.0, f"{what}: point lights: glight_dir is not zero"
+            if first is None:
+                first = {k: t.cpu().clone() for k, t in outs.items()}
+            else:
+                for k, t in outs.items():
+                    for b in range(B):
+                        scale = float(first[k][b].abs().max())
+                        assert float((t[b].cpu() - first[k][b]).abs().max()) <= 1e-5 * scale, f"{what}: second backward on one workspace: {k} of image {b} differs"
+        if not uv:                                                        # gvcolors NULL: the other gradients as before
+            gv2, glc2, gld2 = G.out(B, V, 3, fill=float("nan")), G.out(B, 3, fill=float("nan")), G.out(B, 3, fill=float("nan"))
+            lib.render_bwd(h, dv, dcam, dlc, dld, fid[0], dw, gv2, None, glc2, gld2, ws)
+            G.intact(f"{what}: backward without gvcolors")
+            for b in range(B):
+                _render_close(bwd_e, "render_gv", gv2[b], ref["gverts"][b], cond[b][0], cond[b][3], f"{what}: gverts of image {b} with gvcolors NULL")
+        _render_drain(lib, device)
+        return True
+    finally:
+        lib.renderer_destroy(h)
+        _layer_log("renderer_destroy", True)
+
+
+def render_refusal_case(lib, device, entry):
+    """Every refused call of one entry -- HIFIHR_EINVAL, outputs and guards untouched, nothing launched -- and its accepted edge calls
+    (B == 0: a no-op; the byte queries).  True when the entry has refused calls at all."""
+    import ctypes
+    case = ("refusals", "ico", 2, 8, 2, "uv")
+    inp = render_contract_inputs(case)
+    B, H, aa, V, F_ = inp["B"], inp["H"], inp["aa"], inp["V"], inp["F"]
+    S = H * aa
+    fu, vu, maps = inp["uv"]
+    TH, TW = maps.shape[1], maps.shape[2]
+    c_int, c_float, vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+    np_p = lambda a: vp(a.ctypes.data) if a is not None else vp(0)
+    faces = np.ascontiguousarray(inp["faces"], dtype=np.int32)
+    mats = {k: np.asarray(inp["consts"][k], dtype=np.float32) for k in ("ambient", "mat_diffuse", "specular", "background")}
+    G = Guards(device)
+    _render_drain(lib, device)
+
+    def _raw(lib_, name, *a):                                             # (the argument types hifihr_amd._lib declared: cast the pointers to them)
+        fn = getattr(lib_.c, name)
+        a = [ctypes.cast(x, t) if isinstance(x, vp) and t is not None and t is not vp and hasattr(t, "contents") else x
+             for x, t in zip(a, fn.argtypes or [None] * len(a))]
+        lib_.check(fn(*a), name)
+
+    def create(out="ok", faces_=faces, V_=V, F2=F_, H_=H, aa_=aa, null=None):
+        hh = vp(0)
+        m = {k: (None if k == null else v) for k, v in mats.items()}
+        try:
+            _raw(lib, "hifihr_renderer_create", ctypes.byref(hh) if out is not None else vp(0), np_p(faces_), c_int(V_), c_int(F2), c_int(H_), c_int(aa_),
+                 np_p(m["ambient"]), np_p(m["mat_diffuse"]), np_p(m["specular"]), c_float(30.0), np_p(m["background"]))
+        finally:
+            assert hh.value is None or out == "made", "a refused hifihr_renderer_create left a handle"
+        return hh
+
+    if entry == "renderer_create":
+        bad_lo, bad_hi = faces.copy(), faces.copy()
+        bad_lo[3, 1], bad_hi[F_ - 1, 2] = -1, V
+        calls = [("out NULL", lambda: create(out=None)), ("faces NULL", lambda: create(faces_=None)), ("V = 0", lambda: create(V_=0)),
+                 ("V = -1", lambda: create(V_=-1)), ("F = 0", lambda: create(F2=0)), ("F = -1", lambda: create(F2=-1)),
+                 ("image_size = 0", lambda: create(H_=0)), ("image_size = -1", lambda: create(H_=-1)),
+                 (f"image_size = {RENDER_MAX_IMAGE + 1}", lambda: create(H_=RENDER_MAX_IMAGE + 1)), ("aa = 0", lambda: create(aa_=0)),
+                 ("aa = 4", lambda: create(aa_=4)), ("a face index of -1", lambda: create(faces_=bad_lo)), ("a face index of V", lambda: create(faces_=bad_hi))]
+        calls += [(f"{k} NULL", lambda k=k: create(null=k)) for k in mats]
+        for name, call in calls:
+            _render_refuses(entry, lib, device, call, G, name)
+        hh = create(out="made", H_=RENDER_MAX_IMAGE)                      # the limit itself is accepted (no launch here)
+        assert hh.value is not None and lib.render_workspace_bytes(hh, 1) > 0
+        lib.renderer_destroy(hh)
+        _layer_log(entry, True)
+        return True
+    h = lib.renderer_create(faces, V, image_size=H, aa=aa, **inp["consts"])
+    try:
+        if entry == "renderer_set_light_mode":
+            for name, call in [("h NULL", lambda: _raw(lib, "hifihr_renderer_set_light_mode", vp(0), c_int(1))),
+                               ("mode 2", lambda: _raw(lib, "hifihr_renderer_set_light_mode", h, c_int(2))),
+                               ("mode -1", lambda: _raw(lib, "hifihr_renderer_set_light_mode", h, c_int(-1)))]:
+                _render_refuses(entry, lib, device, call, G, name)
+            return True
+        if entry == "renderer_set_uv":
+            lo, hi = fu.copy(), fu.copy()
+            lo[0, 0], hi[F_ - 1, 2] = -1, len(vu)
+            set_uv = lambda hh=h, f=fu, v=vu, n=len(vu): _raw(lib, "hifihr_renderer_set_uv", hh, np_p(f), np_p(v), c_int(n))
+            for name, call in [("h NULL", lambda: set_uv(hh=vp(0))), ("faces_uvs NULL", lambda: set_uv(f=None)), ("verts_uvs NULL", lambda: set_uv(v=None)),
+                               ("n_uv = 0", lambda: set_uv(n=0)), ("n_uv = -1", lambda: set_uv(n=-1)), ("an index of -1", lambda: set_uv(f=lo)),
+                               ("an index of n_uv", lambda: set_uv(f=hi))]:
+                _render_refuses(entry, lib, device, call, G, name)
+            # a refused set_uv leaves the renderer without tables: the UV forward is still refused
+            return True
+        if entry in ("renderer_destroy", "render_workspace_bytes", "render_uv_scratch_bytes"):
+            lib.c.hifihr_render_workspace_bytes.restype = ctypes.c_size_t
+            assert lib.c.hifihr_render_workspace_bytes(vp(0), c_int(2)) == 0 and lib.render_workspace_bytes(h, -1) == 0
+            sizes = [lib.render_workspace_bytes(h, b) for b in range(6)]
+            assert sizes == sorted(sizes) and sizes[1] > 0, sizes
+            assert lib.render_uv_scratch_bytes(h, B) == 0 and lib.render_uv_scratch_bytes(h, 0) == 0
+            assert lib.c.hifihr_renderer_destroy(vp(0)) == 0              # nothing to destroy: accepted
+            assert not _render_drain(lib, device)
+            _layer_log(entry, True)
+            return False
+        uvm = entry.endswith("_uv")
+        bwd = "bwd" in entry
+        ws = G.out(lib.render_workspace_bytes(h, B), dtype=torch.uint8)
+        dv, dcam, dlc, dld, dw, dmaps = (G.inp(t) for t in (inp["verts"], inp["cam"], inp["lc"], inp["ld"], inp["w"], maps))
+        dcol = G.inp(0.5 * torch.ones(B, V, 3))
+        rgba, fid = G.out(B, 4, H, H), G.out(B, S, S, dtype=torch.int32)
+        gv, gt, glc, gld = G.out(B, V, 3), G.out(*(maps.shape if uvm else (B, V, 3))), G.out(B, 3), G.out(B, 3)
+        fid_in = G.inp(torch.from_numpy(inp["p2f"]))
+        if entry == "render_fwd":
+            names = ["h", "verts", "vcolors", "cam", "light_color", "light_dir", "rgba", "face_id", "workspace"]
+            args = lambda B_=B: [h, _vp(dv), _vp(dcol), c_int(1), _vp(dcam), _vp(dlc), _vp(dld), c_int(B_), _vp(rgba), _vp(fid), _vp(ws), vp(0)]
+            ptrs = [0, 1, 2, 4, 5, 6, 8, 9, 10]
+        elif entry == "render_bwd":
+            names = ["h", "verts", "cam", "light_color", "light_dir", "face_id", "grad_rgba", "gverts", "glight_color", "glight_dir", "workspace"]
+            args = lambda B_=B: [h, _vp(dv), _vp(dcam), _vp(dlc), _vp(dld), _vp(fid_in), _vp(dw), c_int(B_), _vp(gv), _vp(gt), _vp(glc), _vp(gld), _vp(ws), vp(0)]
+            ptrs = [0, 1, 2, 3, 4, 5, 6, 8, 10, 11, 12]
+        elif entry == "render_fwd_uv":
+            names = ["h", "verts", "maps", "cam", "light_color", "light_dir", "rgba", "face_id", "workspace"]
+            args = lambda B_=B, th=TH, tw=TW: [h, _vp(dv), _vp(dmaps), c_int(th), c_int(tw), _vp(dcam), _vp(dlc), _vp(dld), c_int(B_), _vp(rgba), _vp(fid),
+                                               vp(0), _vp(ws), vp(0)]
+            ptrs = [0, 1, 2, 5, 6, 7, 9, 10, 12]
+        else:
+            names = ["h", "verts", "maps", "cam", "light_color", "light_dir", "face_id", "grad_rgba", "gverts", "glight_color", "glight_dir", "workspace"]
+            args = lambda B_=B, th=TH, tw=TW: [h, _vp(dv), _vp(dmaps), c_int(th), c_int(tw), _vp(dcam), _vp(dlc), _vp(dld), _vp(fid_in), _vp(dw), c_int(B_),
+                                               vp(0), vp(0), _vp(gv), _vp(gt), _vp(glc), _vp(gld), _vp(ws), vp(0)]
+            ptrs = [0, 1, 2, 5, 6, 7, 8, 9, 13, 15, 16, 17]
+        assert len(names) == len(ptrs)
+
+        def call(null=None, **kw):
+            a = args(**kw)
+            if null is not None:
+                a[null] = vp(0)
+            _raw(lib, "hifihr_" + entry, *a)
+
+        if uvm:                                                          # no UV tables yet: refused whatever else is right
+            _render_refuses(entry, lib, device, call, G, "before hifihr_renderer_set_uv")
+            lib.renderer_set_uv(h, fu, vu)
+            _render_refuses(entry, lib, device, lambda: call(th=0), G, "TH = 0")
+            _render_refuses(entry, lib, device, lambda: call(tw=0), G, "TW = 0")
+            _render_refuses(entry, lib, device, lambda: call(th=-1), G, "TH = -1")
+        for name, k in zip(names, ptrs):
+            _render_refuses(entry, lib, device, lambda k=k: call(null=k), G, f"{name} NULL")
+        _render_refuses(entry, lib, device, lambda: call(B_=-1), G, "B = -1")
+        before = [t.clone() for t in G.wholes()]
+        call(B_=0)                                                        # accepted: a no-op
+        assert all(torch.equal(a, b2) for a, b2 in zip(G.wholes(), before)), f"{entry}: B = 0 wrote something"
+        assert not _render_drain(lib, device), f"{entry}: B = 0 launched something"
+        _layer_log(entry, True)
+        return True
+    finally:
+        lib.renderer_destroy(h)

@@ -96,3 +96,31 @@ def test_render_textures_uv_texel_table_overflow(lib, synth_tables):
     """A texture fine enough that a 16 x 16-pixel tile of the backward touches more distinct texels than its LDS table holds (2 048 slots:
     csrc/render_bwd.hip TexAcc): the texels that find the table full go out as global atomics -- same gradients either way."""
     kc.render_uv_case(lib, synth_tables, "cuda", B=2, seed=131, image_size=224, aa=3, TH=512, TW=512, rgb_atol=1e-4)
+
+
+# ---- the renderer contract (tests/kernel_cases.py, "The renderer contract"): the emulator's lists through the same runners, and the shapes
+# ---- only a GPU reaches in seconds
+import test_hostsim_render_contract as rc
+
+GPU_RENDER_CASES = rc.RENDER_CASES + [
+    ("sheets", "quads96", 1, 128, 3, "vc"),                      # merge buffers of 24 x 24 samples, slot-less tiles in two passes
+    ("hand", "mano", 1, 520, 1, "vc"),                           # H > 512: the second forward form in production
+    ("limit", "ico", 1, kc.RENDER_MAX_IMAGE, 1, "vc"),           # the largest image a renderer is created for: 90 x 90 tiles in the binning kernel's LDS
+]
+_GPU_RUNNERS = rc.render_runners("cuda")
+
+
+@pytest.fixture(scope="module")
+def render_tally():
+    yield None
+    kc.layer_contract_report("the renderer entries on the GPU", kc.RENDER_CONTRACT_ENTRIES)
+
+
+@pytest.mark.parametrize("case", GPU_RENDER_CASES, ids=rc._ids)
+def test_render_contract_on_every_scene_size_and_mode(lib, render_tally, case):
+    assert _GPU_RUNNERS["render"](lib, case)
+
+
+@pytest.mark.parametrize("entry", kc.RENDER_CONTRACT_ENTRIES)
+def test_render_contract_every_entry_refuses_and_touches_nothing(lib, render_tally, entry):
+    assert _GPU_RUNNERS["refuse"](lib, entry) == (entry not in ("renderer_destroy", "render_workspace_bytes", "render_uv_scratch_bytes"))

@@ -261,7 +261,9 @@ def test_no_bound_is_looser_than_the_family_case_it_replaces():
               "se_y": 3e-5, "se_mlp": 2e-5, "se_grad": 3e-4, "ssim_val": 2e-6, "ssim_part": 2e-6, "ssim_map": 2.1e-3, "ssim_grad": 2e-4}      # (no older case asserts on the SSIM maps)
     # (the kinds of the GEMM contract live in the same table: tests/test_hostsim_gemm_contract.py holds them to their own older cases)
     # (so do the kinds of the tail contract: tests/test_hostsim_tail_contract.py holds them to kc.TAIL_LEGACY)
-    assert set(legacy) == set(kc.LAYER_CONTRACT_C) - set(kc.GEMM_CONTRACT_KINDS) - set(kc.WINO_CONTRACT_KINDS) - set(kc.TAIL_CONTRACT_KINDS)
+    # (and those of the renderer contract: tests/test_hostsim_render_contract.py holds them to render_case / render_uv_case)
+    assert set(legacy) == (set(kc.LAYER_CONTRACT_C) - set(kc.GEMM_CONTRACT_KINDS) - set(kc.WINO_CONTRACT_KINDS) - set(kc.TAIL_CONTRACT_KINDS) -
+                           set(kc.RENDER_CONTRACT_KINDS))
     for kind in legacy:
         c, cap = kc.LAYER_CONTRACT_C[kind]
         assert 0 < c <= cap <= legacy[kind], kind
