@@ -58,6 +58,11 @@ def _np_fp(a):
     return a, a.ctypes.data_as(_c_float_p)
 
 
+def _np_f64(a):
+    import numpy as np
+    return np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+
+
 class HifihrLib:
     def __init__(self, path: str = LIB_PATH):
         if not os.path.exists(path):
@@ -172,6 +177,9 @@ class HifihrLib:
         c.hifihr_loss_total_fwd.argtypes = [POINTER(_c_float_p), POINTER(c_int), c_int, _c_float_p, c_void_p]
         c.hifihr_loss_total_bwd.argtypes = [_c_float_p, POINTER(_c_float_p), POINTER(c_int), POINTER(c_int), c_int, c_void_p]
         c.hifihr_procrustes_error.argtypes = [_c_float_p, _c_float_p, c_int, c_int, _c_float_p, _c_float_p, c_void_p]
+        c.hifihr_point_error_hist.argtypes = [_c_float_p, _c_float_p, c_void_p, c_int, c_int, POINTER(ctypes.c_double), c_int, _c_int_p, c_void_p,
+                                              c_void_p]
+        c.hifihr_fscore_counts.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, POINTER(ctypes.c_double), c_int, _c_int_p, c_void_p]
         c.hifihr_wino_wgrad_gemm.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
         c.hifihr_wino_dw_transform.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_void_p]
         c.hifihr_weight_transpose.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_void_p]
@@ -704,6 +712,22 @@ class HifihrLib:
         B, N = pred.shape[0], pred.shape[1]
         self.check(self.c.hifihr_procrustes_error(_fp(pred), _fp(gt), B, N, _fp(aligned), _fp(err_sum), _stream_of(pred)),
                    "hifihr_procrustes_error")
+
+    def point_error_hist(self, pred, gt, vis, thresholds, hist, sum_d):
+        """pred / gt fp32 [n,K,3], vis uint8 [n,K] or None, thresholds: T host float64 values; hist int32 [K,T+1], sum_d float64 [K]."""
+        thr, n, K = _np_f64(thresholds), pred.shape[0], pred.shape[1]
+        assert vis is None or (vis.dtype == torch.uint8 and vis.is_contiguous() and tuple(vis.shape) == (n, K))
+        assert sum_d.dtype == torch.float64 and sum_d.is_contiguous() and tuple(hist.shape) == (K, len(thr) + 1) and tuple(sum_d.shape) == (K,)
+        self.check(self.c.hifihr_point_error_hist(_fp(pred), _fp(gt), c_void_p(vis.data_ptr()) if vis is not None else None, n, K,
+                                                  thr.ctypes.data_as(POINTER(ctypes.c_double)), len(thr), _ip(hist), c_void_p(sum_d.data_ptr()),
+                                                  _stream_of(pred)), "hifihr_point_error_hist")
+
+    def fscore_counts(self, pred, gt, thresholds, counts):
+        """pred fp32 [B,Np,3], gt fp32 [B,Ng,3], thresholds: T host float64 values; counts int32 [B,2,T]."""
+        thr, B = _np_f64(thresholds), pred.shape[0]
+        assert gt.shape[0] == B and tuple(counts.shape) == (B, 2, len(thr))
+        self.check(self.c.hifihr_fscore_counts(_fp(pred), _fp(gt), B, pred.shape[1], gt.shape[1], thr.ctypes.data_as(POINTER(ctypes.c_double)),
+                                               len(thr), _ip(counts), _stream_of(pred)), "hifihr_fscore_counts")
 
     def wino_output_transform(self, M, y, stats, N, H, W, K, bias=None, act=0, m=2, mask=None):
         if mask is not None:

@@ -10,6 +10,8 @@
 // fp64 arrays); the points are read as fp32, 12 bytes per point per set: the kernel is HBM / latency bound and tiny.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+
 #include "hifihr_internal.h"
 
 namespace hifihr {
@@ -167,6 +169,132 @@ __global__ __launch_bounds__(kThreads) void procrustes_kernel(const float* __res
 hipError_t launch_procrustes(const float* pred, const float* gt, int B, int N, float* aligned, float* err_sum, hipStream_t st) {
   if (B <= 0 || N <= 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(procrustes_kernel, dim3(B), dim3(kThreads), 0, st, pred, gt, N, aligned, err_sum);
+  return hipGetLastError();
+}
+
+// ---- benchmark metrics: the counts behind the FreiHAND benchmark's PCK / AUC and F-score (reference utils/fh_utils.py:719-815
+// EvalUtil; the benchmark's calculate_fscore).  The device counts, the host (hifihr_amd/evaluate.py) turns counts into curves.
+
+namespace {
+
+constexpr int kHistKp = 4;            // adjacent keypoints per workgroup: 48 contiguous bytes of every sample row
+static_assert(kThreads % kHistKp == 0 && (kHistKp & (kHistKp - 1)) == 0, "a thread keeps one keypoint; the tree sum keeps the classes apart");
+constexpr int kFsQ = 64;              // queries per workgroup: one per lane, every wave searches a quarter of each tile
+constexpr int kFsWaves = kThreads / 64;
+constexpr int kFsTile = 512;          // searched points staged per pass, as doubles: 12 KiB of LDS
+static_assert(kFsTile % kFsWaves == 0, "every wave takes the same share of a tile");
+
+}  // namespace
+
+// One workgroup per kHistKp adjacent keypoints; thread t keeps keypoint t % kHistKp and walks the samples t / kHistKp, + kThreads / kHistKp, ...
+// The bins are LDS integers (atomic adds of integers: the same bits in any order), the distance sum is a per-thread chain then a fixed tree.
+__global__ __launch_bounds__(kThreads) void point_error_hist_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                                   const unsigned char* __restrict__ vis, int n, int K, HistThresholds thr,
+                                                                   int T, int* __restrict__ hist, double* __restrict__ sum) {
+  __shared__ double red[kThreads];
+  __shared__ double sThr[kHistMaxT];
+  __shared__ int sBin[kHistKp * (kHistMaxT + 1)];
+  const int tid = threadIdx.x, j = tid % kHistKp, k0 = blockIdx.x * kHistKp, k = k0 + j;
+  for (int i = tid; i < kHistKp * (T + 1); i += kThreads) sBin[i] = 0;
+  for (int t = tid; t < T; t += kThreads) sThr[t] = thr.v[t];
+  __syncthreads();
+  double acc = 0.0;
+  if (k < K)
+    for (int s = tid / kHistKp; s < n; s += kThreads / kHistKp) {
+      const size_t at = (size_t)s * K + k;
+      if (vis != nullptr && vis[at] == 0) continue;
+      const double dx = (double)pred[at * 3] - (double)gt[at * 3], dy = (double)pred[at * 3 + 1] - (double)gt[at * 3 + 1],
+                   dz = (double)pred[at * 3 + 2] - (double)gt[at * 3 + 2];
+      const double d = sqrt(dx * dx + dy * dy + dz * dz);
+      int lo = 0, hi = T;                                // first t with d <= thr[t]; T when there is none (d beyond the last, or not a number)
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (d <= sThr[mid]) hi = mid; else lo = mid + 1;
+      }
+      atomicAdd(&sBin[j * (T + 1) + lo], 1);
+      acc += d;
+    }
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = kThreads / 2; s >= kHistKp; s >>= 1) {    // s is a multiple of kHistKp: a keypoint's partial sums only meet each other
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid < kHistKp && k0 + tid < K) sum[k0 + tid] = red[tid];
+  for (int i = tid; i < kHistKp * (T + 1); i += kThreads)
+    if (k0 + i / (T + 1) < K) hist[(size_t)k0 * (T + 1) + i] = sBin[i];
+}
+
+// Nearest neighbour of kFsQ queries in the other set of their sample, both directions in one launch: blockIdx.x = (sample, direction, chunk).
+// The searched set passes through LDS in tiles of kFsTile points (widened to double once); lane l of every wave keeps query l and
+// scans its wave's share of the tile -- all lanes read the same LDS address, a broadcast --, the four partial minima meet in LDS.
+// min d^2 does not depend on the order of the search, the counts are integer atomics: the same bits on every call.
+__global__ __launch_bounds__(kThreads) void fscore_counts_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int Np, int Ng,
+                                                                int chunks, FscoreThresholds thr, int T, int* __restrict__ counts) {
+  __shared__ double sP[kFsTile * 3];
+  __shared__ double sMin[kFsWaves][kFsQ];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int chunk = blockIdx.x % chunks, dir = (blockIdx.x / chunks) & 1, b = blockIdx.x / (2 * chunks);
+  const int Nq = dir == 0 ? Np : Ng, Ns = dir == 0 ? Ng : Np;
+  if (chunk * kFsQ >= Nq) return;                        // the shorter direction has fewer chunks (uniform over the workgroup)
+  const float* Q = (dir == 0 ? pred : gt) + (size_t)b * Nq * 3;
+  const float* S = (dir == 0 ? gt : pred) + (size_t)b * Ns * 3;
+  const int q = chunk * kFsQ + lane;
+  const bool live = q < Nq;
+  const double qx = live ? (double)Q[(size_t)q * 3] : 0.0, qy = live ? (double)Q[(size_t)q * 3 + 1] : 0.0,
+               qz = live ? (double)Q[(size_t)q * 3 + 2] : 0.0;
+  double best = INFINITY;
+  for (int base = 0; base < Ns; base += kFsTile) {
+    const int cnt = Ns - base < kFsTile ? Ns - base : kFsTile;
+    __syncthreads();
+    for (int i = tid; i < cnt * 3; i += kThreads) sP[i] = (double)S[(size_t)base * 3 + i];
+    __syncthreads();
+    const int per = kFsTile / kFsWaves, lo = wave * per, hi = lo + per < cnt ? lo + per : cnt;
+    for (int p = lo; p < hi; ++p) {
+      const double dx = qx - sP[p * 3], dy = qy - sP[p * 3 + 1], dz = qz - sP[p * 3 + 2];
+      const double d2 = dx * dx + dy * dy + dz * dz;
+      best = d2 < best ? d2 : best;                      // a distance that is not a number never wins
+    }
+  }
+  sMin[wave][lane] = best;
+  __syncthreads();
+  if (wave != 0) return;
+  for (int w = 1; w < kFsWaves; ++w) best = sMin[w][lane] < best ? sMin[w][lane] : best;
+  const double d = sqrt(best);
+  for (int t = 0; t < T; ++t) {
+    const unsigned long long m = __ballot(live && d < thr.v[t]);
+    if (lane == 0 && m != 0ull) atomicAdd(&counts[((size_t)b * 2 + dir) * T + t], __popcll(m));
+  }
+}
+
+bool thresholds_ok(const double* thr, int T, bool positive) {
+  if (thr == nullptr || T <= 0) return false;
+  for (int t = 0; t < T; ++t) {
+    if (!std::isfinite(thr[t])) return false;
+    if (positive ? !(thr[t] > 0.0) : (t > 0 && !(thr[t] > thr[t - 1]))) return false;
+  }
+  return true;
+}
+
+hipError_t launch_point_error_hist(const float* pred, const float* gt, const unsigned char* vis, int n, int K, const double* thr_h, int T,
+                                   int* hist, double* sum, hipStream_t st) {
+  if (n <= 0 || K <= 0 || T > kHistMaxT || !thresholds_ok(thr_h, T, false)) return hipErrorInvalidValue;
+  HistThresholds thr;
+  for (int t = 0; t < kHistMaxT; ++t) thr.v[t] = t < T ? thr_h[t] : 0.0;
+  hipLaunchKernelGGL(point_error_hist_kernel, dim3((K + kHistKp - 1) / kHistKp), dim3(kThreads), 0, st, pred, gt, vis, n, K, thr, T, hist, sum);
+  return hipGetLastError();
+}
+
+hipError_t launch_fscore_counts(const float* pred, const float* gt, int B, int Np, int Ng, const double* thr_h, int T, int* counts,
+                                hipStream_t st) {
+  if (B <= 0 || Np <= 0 || Ng <= 0 || T > kFscoreMaxT || !thresholds_ok(thr_h, T, true)) return hipErrorInvalidValue;
+  const int chunks = ((Np > Ng ? Np : Ng) + kFsQ - 1) / kFsQ;
+  if ((long long)B * 2 * chunks > 0x7fffffffLL) return hipErrorInvalidValue;
+  FscoreThresholds thr;
+  for (int t = 0; t < kFscoreMaxT; ++t) thr.v[t] = t < T ? thr_h[t] : 0.0;
+  hipError_t e = hipMemsetAsync(counts, 0, sizeof(int) * (size_t)B * 2 * T, st);      // the workgroups of a sample add into its row
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(fscore_counts_kernel, dim3((unsigned)(B * 2 * chunks)), dim3(kThreads), 0, st, pred, gt, Np, Ng, chunks, thr, T, counts);
   return hipGetLastError();
 }
 

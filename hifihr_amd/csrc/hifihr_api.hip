@@ -1505,6 +1505,25 @@ int hifihr_procrustes_error(const float* pred, const float* gt, int B, int N, fl
   return HIFIHR_OK;
 }
 
+int hifihr_point_error_hist(const float* pred, const float* gt, const uint8_t* vis, int n, int K, const double* thr, int T, int32_t* hist,
+                            double* sum, void* stream) {
+  if (!pred || !gt || !thr || !hist || !sum || n <= 0 || K <= 0 || T <= 0 || T > hifihr::kHistMaxT)
+    return fail(HIFIHR_EINVAL, "hifihr_point_error_hist: bad argument (1 <= T <= %d)", hifihr::kHistMaxT);
+  if (!hifihr::thresholds_ok(thr, T, false))
+    return fail(HIFIHR_EINVAL, "hifihr_point_error_hist: the thresholds must be finite and strictly increasing");
+  HIP_TRY(hifihr::launch_point_error_hist(pred, gt, vis, n, K, thr, T, hist, sum, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_fscore_counts(const float* pred, const float* gt, int B, int Np, int Ng, const double* thr, int T, int32_t* counts, void* stream) {
+  if (!pred || !gt || !thr || !counts || B <= 0 || Np <= 0 || Ng <= 0 || T <= 0 || T > hifihr::kFscoreMaxT ||
+      (long long)B * 2 * (((Np > Ng ? Np : Ng) + 63) / 64) > 0x7fffffffLL)
+    return fail(HIFIHR_EINVAL, "hifihr_fscore_counts: bad argument (1 <= T <= %d)", hifihr::kFscoreMaxT);
+  if (!hifihr::thresholds_ok(thr, T, true)) return fail(HIFIHR_EINVAL, "hifihr_fscore_counts: the thresholds must be finite and > 0");
+  HIP_TRY(hifihr::launch_fscore_counts(pred, gt, B, Np, Ng, thr, T, counts, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
 size_t hifihr_ho3d_workspace_bytes(int B, int out_size) {
   return (B > 0 && out_size > 0 && out_size <= 256) ? hifihr::ho3d_workspace_bytes(B, out_size) : 0;
 }

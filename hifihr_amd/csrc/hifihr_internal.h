@@ -409,6 +409,15 @@ hipError_t launch_ho3d_batch(const uint32_t* img, const uint8_t* mask, const flo
                              const int* packed, int B, int out_size, void* ws, float* out_img, float* out_mask, float* out_K,
                              float* out_uv, float* out_xyz, hipStream_t st);
 hipError_t launch_procrustes(const float* pred, const float* gt, int B, int N, float* aligned, float* err_sum, hipStream_t st);
+// benchmark metrics (eval.hip): the thresholds travel by value as kernel arguments, validated on the host
+constexpr int kHistMaxT = 128, kFscoreMaxT = 8;
+struct HistThresholds { double v[kHistMaxT]; };
+struct FscoreThresholds { double v[kFscoreMaxT]; };
+bool thresholds_ok(const double* thr_h, int T, bool positive);       // finite; positive, or else strictly increasing
+hipError_t launch_point_error_hist(const float* pred, const float* gt, const unsigned char* vis, int n, int K, const double* thr_h, int T,
+                                   int* hist, double* sum, hipStream_t st);
+hipError_t launch_fscore_counts(const float* pred, const float* gt, int B, int Np, int Ng, const double* thr_h, int T, int* counts,
+                                hipStream_t st);
 hipError_t launch_wino_output_transform(const float* Mm, float* y, float* stats, const float* bias, int relu, int N, int H, int W, int K,
                                         hipStream_t st);
 hipError_t launch_wino_dy_transform(const float* dy, float* Y, int N, int H, int W, int K, hipStream_t st);

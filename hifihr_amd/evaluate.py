@@ -4,9 +4,16 @@ device (csrc/eval.hip) instead of a per-sample numpy / scipy loop.  SURVEY.md se
 
 LPIPS (train_hrnet.py:156-158) is opt-in: `Evaluator(lpips_fn=hifihr_amd.lpips.LPIPS(...))` -- the AlexNet metric on this package's
 kernels, with weights loaded by `load_state_dict_lpips` (train_hrnet.py --lpips_weights) or, without any, seeded ones.  With no
-`lpips_fn` it is reported as None.  Parity with the `lpips` package and with the real weights is unpinned: neither is available here."""
+`lpips_fn` it is reported as None.  Parity with the `lpips` package and with the real weights is unpinned: neither is available here.
+
+The FreiHAND benchmark's other `scores.txt` keys -- PCK / AUC of joints and mesh, aligned and not (reference utils/fh_utils.py:719-815
+EvalUtil, instantiated at train_hrnet.py:25,43) and F@5 mm / F@15 mm -- come from `pck_auc`, `fscore` and `Evaluator(benchmark=True)`:
+the device counts (csrc/eval.hip: one launch per metric), the host turns the integer counts into curves in float64.  PCK / AUC are pinned
+to the reference's EvalUtil (tests/golden/benchmark_metrics.npz); the F-score has no counterpart in the reference tree and neither the
+benchmark's eval.py nor open3d is available here: its parity with the benchmark's script is unpinned (tests/benchmark_ref.py restates it)."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -36,11 +43,73 @@ def aligned_error(pred, gt):
     return err / pred.shape[1]
 
 
+BENCHMARK_KEYS = ("xyz_mean3d", "xyz_auc3d", "xyz_al_mean3d", "xyz_al_auc3d", "mesh_mean3d", "mesh_auc3d", "mesh_al_mean3d", "mesh_al_auc3d",
+                  "f_score_5", "f_score_15", "f_al_score_5", "f_al_score_15")
+_trapezoid = getattr(np, "trapezoid", None) or np.trapz
+
+
+def point_error_counts(pred, gt, vis, thresholds):
+    """hifihr_point_error_hist: (hist int32 [K, T+1], sum float64 [K]) on the device, no host sync.  pred / gt [n,K,3]; vis [n,K] or None."""
+    require_cuda(pred, gt)
+    pred, gt = pred.float().contiguous(), gt.float().contiguous()
+    assert pred.shape == gt.shape and pred.dim() == 3 and pred.shape[2] == 3, (pred.shape, gt.shape)
+    if vis is not None:
+        require_cuda(vis)
+        vis = (vis != 0).to(torch.uint8).contiguous()
+    hist = torch.empty(pred.shape[1], len(thresholds) + 1, dtype=torch.int32, device=pred.device)
+    sums = torch.empty(pred.shape[1], dtype=torch.float64, device=pred.device)
+    get_lib().point_error_hist(pred, gt, vis, thresholds, hist, sums)
+    return hist, sums
+
+
+def pck_measures(hist, sums, thresholds):
+    """EvalUtil.get_measures (utils/fh_utils.py:774-815) from the per-keypoint counts, float64 numpy on the host: hist [K, T+1] (the last
+    column = beyond the last threshold), sums [K] the distance sums.  Keypoints without a visible sample are skipped, as the reference
+    `continue`s; mean / auc / pck_curve are averages over the others."""
+    hist, sums, thr = np.asarray(hist, np.int64), np.asarray(sums, np.float64), np.asarray(thresholds, np.float64)
+    visible = hist.sum(1)
+    keep = visible > 0
+    if not keep.any():
+        nan = float("nan")
+        return {"mean": nan, "auc": nan, "pck_curve": np.full(len(thr), nan), "thresholds": thr}
+    pck = np.cumsum(hist[keep, :-1], 1).astype(np.float64) / visible[keep, None].astype(np.float64)
+    norm = _trapezoid(np.ones_like(thr), thr)
+    auc = np.array([_trapezoid(row, thr) / norm for row in pck])
+    return {"mean": float(np.mean(sums[keep] / visible[keep])), "auc": float(np.mean(auc)), "pck_curve": np.mean(pck, 0), "thresholds": thr}
+
+
+def pck_auc(pred, gt, vis=None, val_min=0.0, val_max=0.05, steps=100):
+    """EvalUtil.feed + get_measures(val_min, val_max, steps) for pred / gt [n,K,3] (vis [n,K]: which keypoints count): a dict with the
+    mean end-point error, the area under the PCK curve, the curve and its thresholds.  The median is not computed."""
+    thr = np.linspace(val_min, val_max, steps)
+    hist, sums = point_error_counts(pred, gt, vis, thr)
+    return pck_measures(hist.cpu().numpy(), sums.cpu().numpy(), thr)
+
+
+def fscore(pred, gt, thresholds=(0.005, 0.015)):
+    """The benchmark's calculate_fscore for every sample and threshold: pred [B,Np,3], gt [B,Ng,3] -> (F, precision, recall), float64
+    [B,T] on the device.  precision = share of predicted points whose nearest ground-truth point is closer than the threshold (strictly),
+    recall = the same from ground truth to prediction, F = 2 P R / (P + R), 0 where P + R = 0."""
+    require_cuda(pred, gt)
+    pred, gt = pred.float().contiguous(), gt.float().contiguous()
+    assert pred.dim() == 3 and gt.dim() == 3 and pred.shape[0] == gt.shape[0] and pred.shape[2] == 3 and gt.shape[2] == 3, (pred.shape, gt.shape)
+    counts = torch.empty(pred.shape[0], 2, len(thresholds), dtype=torch.int32, device=pred.device)
+    get_lib().fscore_counts(pred, gt, thresholds, counts)
+    return fscore_from_counts(counts, pred.shape[1], gt.shape[1])
+
+
+def fscore_from_counts(counts, Np, Ng):
+    P, R = counts[:, 0].double() / Np, counts[:, 1].double() / Ng
+    S = P + R
+    return torch.where(S > 0, 2 * P * R / torch.where(S > 0, S, torch.ones_like(S)), torch.zeros_like(S)), P, R
+
+
 class Evaluator:
     """Accumulates what the evaluation loop keeps (train_hrnet.py:119-161) and reduces it as :216-272 does."""
 
-    def __init__(self, ssim_fn=None, lpips_fn=None):
+    def __init__(self, ssim_fn=None, lpips_fn=None, benchmark=False):
         self.xyz_pred, self.verts_pred, self.texture = [], [], []
+        self.benchmark = bool(benchmark)          # summary() adds BENCHMARK_KEYS when ground truth is given
         if ssim_fn is None:
             from . import ops
             ssim_fn = ops.ssim
@@ -79,19 +148,61 @@ class Evaluator:
             json.dump([xyz, verts], fo)
         return len(xyz), len(verts)
 
-    def summary(self, xyz_gt=None, verts_gt=None):
+    def summary(self, xyz_gt=None, verts_gt=None, root_id=None):
         """xyz_gt [n,21,3] / verts_gt [n,778,3]: evaluation_xyz.json / evaluation_verts.json.  Returns a dict with
         'pose_3d' / 'vert_3d' (MPJPE / MPVPE in the inputs' unit, metres in FreiHAND; the reference prints x100 = cm) and
-        the batch-averaged texture metrics."""
-        out = {}
-        if xyz_gt is not None:
-            pred = torch.cat(self.xyz_pred)
-            out["pose_3d"] = float(aligned_error(pred, torch.as_tensor(xyz_gt, dtype=torch.float32).to(pred.device)).mean())
-        if verts_gt is not None:
-            pred = torch.cat(self.verts_pred)
-            out["vert_3d"] = float(aligned_error(pred, torch.as_tensor(verts_gt, dtype=torch.float32).to(pred.device)).mean())
+        the batch-averaged texture metrics.  An Evaluator(benchmark=True) adds BENCHMARK_KEYS for the ground truth it is given (the
+        FreiHAND benchmark's scores.txt names: *_mean3d in the inputs' unit, *_auc3d over 0..0.05 in 100 steps, F at 0.005 / 0.015); the
+        `_al_` forms are taken on the fp32 output of align_w_scale.  root_id: the ground truth is made relative to its joint `root_id`
+        before the un-aligned forms (the predictions are root-relative already); None takes it as given."""
+        out, bench = {}, []
+        dev = lambda a, like: torch.as_tensor(a, dtype=torch.float32).to(like.device)
+        root = None
+        if self.benchmark and root_id is not None and (xyz_gt is not None or verts_gt is not None):
+            if xyz_gt is None:
+                raise ValueError("root_id needs xyz_gt: the root is a ground-truth joint")
+            root = dev(xyz_gt, (self.xyz_pred or self.verts_pred)[0])[:, int(root_id):int(root_id) + 1]
+        for name, gt, preds in (("xyz", xyz_gt, self.xyz_pred), ("mesh", verts_gt, self.verts_pred)):
+            if gt is None:
+                continue
+            pred = torch.cat(preds)
+            gt = dev(gt, pred)
+            if self.benchmark:
+                aligned, err = align_w_scale(gt, pred, return_error=True)           # the same err bits as aligned_error
+                bench.append((name, pred, gt if root is None else gt - root, aligned, gt))
+            else:
+                err = aligned_error(pred, gt)
+            out["pose_3d" if name == "xyz" else "vert_3d"] = float(err.mean())
+        if bench:
+            out.update(self._benchmark_summary(bench))
         if self.texture:
             for k in self.texture[0]:
                 out[k] = float(torch.stack([r[k] for r in self.texture]).mean())
             out.setdefault("lpips", None)
         return out
+
+    @staticmethod
+    def _benchmark_summary(bench):
+        """bench: (name, pred, gt for the un-aligned forms, aligned pred, gt) per point set.  Everything is counted on the device and
+        comes to the host in ONE copy; the curves are host float64."""
+        thr = np.linspace(0.0, 0.05, 100)
+        parts, plan = [], []
+        for name, pred, gt_rel, aligned, gt in bench:
+            for tag, p, g in ((name, pred, gt_rel), (name + "_al", aligned, gt)):
+                hist, sums = point_error_counts(p, g, None, thr)
+                parts += [hist.double().reshape(-1), sums]
+                plan.append(("pck", tag, hist.shape))
+                if name == "mesh":
+                    parts.append(fscore(p, g, (0.005, 0.015))[0].mean(0))
+                    plan.append(("f", "f_al_score_" if tag.endswith("_al") else "f_score_", None))
+        flat, at, out = torch.cat(parts).cpu().numpy(), 0, {}
+        for kind, tag, shape in plan:
+            if kind == "pck":
+                K, W = shape
+                m = pck_measures(np.rint(flat[at:at + K * W]).astype(np.int64).reshape(K, W), flat[at + K * W:at + K * W + K], thr)
+                out[tag + "_mean3d"], out[tag + "_auc3d"] = m["mean"], m["auc"]
+                at += K * W + K
+            else:
+                out[tag + "5"], out[tag + "15"] = float(flat[at]), float(flat[at + 1])
+                at += 2
+        return {k: out[k] for k in BENCHMARK_KEYS if k in out}

@@ -19,6 +19,7 @@ _DEFAULTS = dict(
     lambda_percep=1e-5, lambda_ssim_tex=0.001, lambda_scale=100.0, lambda_mscale=0.1, lambda_laplacian=0.1,
     ROOT=9, ROOT_NIMBLE=11,
     lpips_weights=None,    # [path, ...]: AlexNet + lin weights for the evaluation pass's LPIPS (hifihr_amd/lpips.py); None = LPIPS not reported
+    benchmark_metrics=True,    # the evaluation pass also reports the FreiHAND benchmark's PCK / AUC and F-score keys (hifihr_amd/evaluate.py)
 )
 
 # lambda values of reference config/FreiHAND/full_rhd_freihand.json, used by the

@@ -939,6 +939,40 @@ int hifihr_procrustes_error(const float* pred_d, const float* gt_d, int B, int N
                             float* err_sum_d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Benchmark metrics: the counts behind the FreiHAND benchmark's PCK / AUC (reference utils/fh_utils.py:719-815, EvalUtil) and
+ * F-score (the benchmark's calculate_fscore).  The device counts; hifihr_amd/evaluate.py (pck_auc, fscore) turns the counts into
+ * curves, areas and scores in float64 on the host.
+ *
+ * hifihr_point_error_hist: per-keypoint histogram of d = || pred - gt ||_2 over the visible samples, one launch.
+ *   pred_d / gt_d [n][K][3] fp32;  vis_d [n][K] uint8 (non-zero = visible) or NULL = all visible;
+ *   thr_h[T]: HOST array of doubles, finite and strictly increasing, 1 <= T <= 128; it is copied into the kernel's arguments (the
+ *   caller may free it on return) and never re-derived on the device -- the thresholds compared are the caller's bits.
+ *   hist_d[K][T + 1] int32: hist[k][t] = #{ thr[t-1] < d <= thr[t] } (thr[-1] = -inf), hist[k][T] = #{ d > thr[T-1] or d not a number };
+ *     the comparison is <=, as in EvalUtil._get_pck: pck[k][t] = sum(hist[k][0..t]) / sum(hist[k][0..T]).
+ *   sum_d[K] double = sum of d over the visible samples of the keypoint (not a number when one d is).
+ *   d is the fp64 square root of (dx dx + dy dy) + dz dz, the differences taken in fp64 from the widened fp32 coordinates (exact).
+ * Every element of hist_d and sum_d is written (a keypoint without a visible sample: zeros); the caller clears nothing.
+ * Deterministic: a second call gives the same bits, sum_d included (a fixed summation order).
+ * Refused (HIFIHR_EINVAL, nothing launched or written): pred_d / gt_d / thr_h / hist_d / sum_d NULL, n / K / T <= 0, T > 128, a
+ * threshold that is not finite or not greater than its predecessor.
+ *
+ * hifihr_fscore_counts: two-sided nearest-neighbour counts between the point sets of each sample, one memset and one launch.
+ *   pred_d [B][Np][3], gt_d [B][Ng][3] fp32 (any Np, Ng: the searched set passes through LDS in tiles);
+ *   thr_h[T]: HOST array of doubles, finite and > 0 (any order), 1 <= T <= 8, copied like the above;
+ *   counts_d[B][2][T] int32: counts[b][0][t] = #{ predicted points whose nearest ground-truth point is at distance < thr[t] }
+ *     (the precision numerator, of Np), counts[b][1][t] = the same from ground truth to prediction (the recall numerator, of Ng).
+ *   The comparison is sqrt(min d^2) < thr, STRICT, as in calculate_fscore; d^2 = (dx dx + dy dy) + dz dz in fp64 as above.
+ *   A pair whose d^2 is not a number is skipped; a point all of whose pairs are is not counted.
+ * Every element of counts_d is written; deterministic (integer sums, a minimum).
+ * Refused (HIFIHR_EINVAL, nothing launched or written): pred_d / gt_d / thr_h / counts_d NULL, B / Np / Ng / T <= 0, T > 8, a threshold
+ * that is not finite or not > 0, 2 B ceil(max(Np, Ng) / 64) >= 2^31 (the grid).
+ * ---------------------------------------------------------------------------------------------- */
+int hifihr_point_error_hist(const float* pred_d, const float* gt_d, const uint8_t* vis_d /* or NULL */, int n, int K, const double* thr_h,
+                            int T, int32_t* hist_d, double* sum_d, void* stream);
+int hifihr_fscore_counts(const float* pred_d, const float* gt_d, int B, int Np, int Ng, const double* thr_h, int T, int32_t* counts_d,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * FreiHAND training augmentation: gathers B samples from a uint8 dataset cache resident in
  * device memory and applies the reference's nearest-neighbour affine warp (reference data/dataset.py:223-270,
  * utils/handutils.py:48-60 = PIL Image.transform(AFFINE), zero fill) + to_tensor (+ torch.round for masks).

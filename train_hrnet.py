@@ -236,13 +236,14 @@ def make_evaluator(args, device):
     """Evaluator of the evaluation pass; with --lpips_weights it also reports LPIPS (the module is built and loaded once per device)."""
     from hifihr_amd.evaluate import Evaluator
     paths = getattr(args, "lpips_weights", None)
+    bench = bool(getattr(args, "benchmark_metrics", True))          # the FreiHAND benchmark's PCK / AUC and F-score keys
     if not paths:
-        return Evaluator()
+        return Evaluator(benchmark=bench)
     key = (str(device), tuple(paths))
     if key not in _LPIPS:
         from hifihr_amd.lpips import LPIPS, load_lpips_weights
         _LPIPS[key] = load_lpips_weights(LPIPS(net="alex"), *paths).to(device)
-    return Evaluator(lpips_fn=_LPIPS[key])
+    return Evaluator(lpips_fn=_LPIPS[key], benchmark=bench)
 
 
 def run_evaluation_ho3d(model, cache, args, device, epoch):
@@ -278,7 +279,13 @@ def run_evaluation(model, cache, arrays, args, device):
             out = model("FreiHand", False, ex["imgs"], Ks=ex["Ps"], root_xyz=root)
             ev.collect(out, ex, "FreiHand", render=args.render)
     model.train()
-    return ev.summary(arrays["joints"], arrays["verts"])
+    return ev.summary(arrays["joints"], arrays["verts"], root_id=args.ROOT)
+
+
+def benchmark_report(summary):
+    """The twelve values of the FreiHAND benchmark's scores.txt, under its names (those the summary holds)."""
+    from hifihr_amd.evaluate import BENCHMARK_KEYS
+    return "\n".join(f"{k}: {summary[k]:.6f}" for k in BENCHMARK_KEYS if k in summary)
 
 
 def main(argv=None):
@@ -339,7 +346,10 @@ def main(argv=None):
     say(f"[train_hrnet] {cache.n} training samples resident on {device}; world {world}; encoder {args.pretrain}; losses {args.losses}")
 
     if "evaluation" in args.mode:
-        say("[train_hrnet] evaluation:", run_evaluation(model, eval_cache or cache, eval_arrays or train_arrays, args, device))
+        summary = run_evaluation(model, eval_cache or cache, eval_arrays or train_arrays, args, device)
+        say("[train_hrnet] evaluation:", summary)
+        if getattr(args, "benchmark_metrics", True):
+            say("[train_hrnet] benchmark scores:\n" + benchmark_report(summary))
         return 0
 
     B = args.train_batch
