@@ -262,6 +262,14 @@ class HifihrLib:
                                         _c_float_p, _c_int_p, c_void_p, c_void_p]
         c.hifihr_render_bwd.argtypes = [c_void_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_int_p, _c_float_p, c_int,
                                         _c_float_p, _c_float_p, _c_float_p, _c_float_p, c_void_p, c_void_p]
+        c.hifihr_soft_sil_workspace_bytes.argtypes = [c_void_p, c_int]
+        c.hifihr_soft_sil_workspace_bytes.restype = c_size_t
+        c.hifihr_soft_sil_fwd.argtypes = [c_void_p, _c_float_p, _c_float_p, c_int, c_float, c_float, _c_float_p, _c_float_p, c_void_p, c_void_p]
+        c.hifihr_soft_sil_bwd.argtypes = [c_void_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, c_int, c_float, c_float, _c_float_p, c_void_p,
+                                          c_void_p]
+        c.hifihr_soft_sil_loss_fwd.argtypes = [_c_float_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, _c_float_p, c_void_p]
+        c.hifihr_soft_sil_loss_bwd.argtypes = [_c_float_p, c_void_p, c_int, c_void_p, _c_float_p, c_int, c_int, c_float, c_float, _c_float_p,
+                                               c_void_p]
         c.hifihr_renderer_set_uv.argtypes = [c_void_p, _c_int_p, _c_float_p, c_int]
         c.hifihr_render_uv_scratch_bytes.argtypes = [c_void_p, c_int]
         c.hifihr_render_uv_scratch_bytes.restype = c_size_t
@@ -1080,6 +1088,39 @@ class HifihrLib:
         self.check(self.c.hifihr_render_bwd(h, _fp(verts), _fp(cam), _fp(light_color), _fp(light_dir), _ip(face_id),
                                             _fp(grad_rgba), B, _fp(gverts), _fp(gvcolors), _fp(glc), _fp(gld),
                                             c_void_p(ws.data_ptr()), _stream_of(verts)), "hifihr_render_bwd")
+
+    # ---- soft silhouette (csrc/soft_sil.hip) ------------------------------
+    def soft_sil_workspace_bytes(self, h, B) -> int:
+        return int(self.c.hifihr_soft_sil_workspace_bytes(h, int(B)))
+
+    def soft_sil_fwd(self, h, verts, cam, sigma, blur_radius, alpha, neglog, ws):
+        self.check(self.c.hifihr_soft_sil_fwd(h, _fp(verts), _fp(cam), verts.shape[0], c_float(sigma), c_float(blur_radius), _fp(alpha),
+                                              _fp(neglog), c_void_p(ws.data_ptr()), _stream_of(verts)), "hifihr_soft_sil_fwd")
+
+    def soft_sil_bwd(self, h, verts, cam, neglog, galpha, sigma, blur_radius, gverts, ws):
+        self.check(self.c.hifihr_soft_sil_bwd(h, _fp(verts), _fp(cam), _fp(neglog), _fp(galpha), verts.shape[0], c_float(sigma),
+                                              c_float(blur_radius), _fp(gverts), c_void_p(ws.data_ptr()), _stream_of(verts)),
+                   "hifihr_soft_sil_bwd")
+
+    @staticmethod
+    def _mask_arg(mask):
+        assert mask.dtype in (torch.float32, torch.int64) and mask.is_contiguous(), (mask.dtype, mask.stride())
+        return c_void_p(mask.data_ptr()), int(mask.dtype == torch.int64)
+
+    def soft_sil_loss_fwd(self, alpha, mask, lam_sil, lam_iou, sums, out):
+        """alpha [B, ...]; mask of the same element count, float32 or int64; sums float64 [B, 3]; out float32 [2] (include/hifihr.h)."""
+        B = alpha.shape[0]
+        assert sums.dtype == torch.float64 and sums.is_contiguous() and mask.numel() == alpha.numel()
+        mp, kind = self._mask_arg(mask)
+        self.check(self.c.hifihr_soft_sil_loss_fwd(_fp(alpha), mp, kind, B, alpha.numel() // max(B, 1), c_float(lam_sil), c_float(lam_iou),
+                                                   c_void_p(sums.data_ptr()), _fp(out), _stream_of(alpha)), "hifihr_soft_sil_loss_fwd")
+
+    def soft_sil_loss_bwd(self, alpha, mask, sums, gout, lam_sil, lam_iou, galpha):
+        B = alpha.shape[0]
+        mp, kind = self._mask_arg(mask)
+        self.check(self.c.hifihr_soft_sil_loss_bwd(_fp(alpha), mp, kind, c_void_p(sums.data_ptr()), _fp(gout), B, alpha.numel() // max(B, 1),
+                                                   c_float(lam_sil), c_float(lam_iou), _fp(galpha), _stream_of(alpha)),
+                   "hifihr_soft_sil_loss_bwd")
 
 
 _LIB = None

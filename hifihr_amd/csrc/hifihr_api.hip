@@ -2,6 +2,7 @@
 // kernel launches on the caller's stream.  No allocation and no synchronisation in compute calls.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -398,6 +399,53 @@ int hifihr_render_bwd(const hifihr_renderer_t* h, const float* verts, const floa
   if (B == 0) return HIFIHR_OK;
   HIP_TRY(hifihr::launch_render_bwd(h->dev, verts, cam, light_color, light_dir, face_id, grad_rgba, B, gverts, gvcolors,
                                     glight_color, glight_dir, ws, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+size_t hifihr_soft_sil_workspace_bytes(const hifihr_renderer_t* h, int B) {
+  if (!h || B < 0) return 0;
+  return hifihr::soft_sil_workspace_bytes(h->dev, B);
+}
+
+namespace {
+bool soft_sil_params_ok(float sigma, float blur_radius) {
+  return std::isfinite(sigma) && sigma > 0.f && std::isfinite(blur_radius) && blur_radius >= 0.f;
+}
+}  // namespace
+
+int hifihr_soft_sil_fwd(const hifihr_renderer_t* h, const float* verts, const float* cam, int B, float sigma, float blur_radius,
+                        float* alpha, float* neglog, void* ws, void* stream) {
+  if (!h || !verts || !cam || !alpha || !neglog || !ws || B < 0 || !soft_sil_params_ok(sigma, blur_radius))
+    return fail(HIFIHR_EINVAL, "hifihr_soft_sil_fwd: bad argument (sigma finite and > 0, blur_radius finite and >= 0)");
+  if (B == 0) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_soft_sil_fwd(h->dev, verts, cam, B, sigma, blur_radius, alpha, neglog, ws, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_soft_sil_bwd(const hifihr_renderer_t* h, const float* verts, const float* cam, const float* neglog, const float* galpha, int B,
+                        float sigma, float blur_radius, float* gverts, void* ws, void* stream) {
+  if (!h || !verts || !cam || !neglog || !galpha || !gverts || !ws || B < 0 || !soft_sil_params_ok(sigma, blur_radius))
+    return fail(HIFIHR_EINVAL, "hifihr_soft_sil_bwd: bad argument (sigma finite and > 0, blur_radius finite and >= 0)");
+  if (B == 0) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_soft_sil_bwd(h->dev, verts, cam, neglog, galpha, B, sigma, blur_radius, gverts, ws, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_soft_sil_loss_fwd(const float* alpha, const void* mask, int mask_i64, int B, int HW, float lam_sil, float lam_iou, double* sums,
+                             float* out, void* stream) {
+  if (!alpha || !mask || !sums || !out || B < 0 || HW <= 0 || mask_i64 < 0 || mask_i64 > 1)
+    return fail(HIFIHR_EINVAL, "hifihr_soft_sil_loss_fwd: bad argument");
+  if (B == 0) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_soft_sil_loss_fwd(alpha, mask, mask_i64, B, HW, lam_sil, lam_iou, sums, out, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_soft_sil_loss_bwd(const float* alpha, const void* mask, int mask_i64, const double* sums, const float* gout, int B, int HW,
+                             float lam_sil, float lam_iou, float* galpha, void* stream) {
+  if (!alpha || !mask || !sums || !gout || !galpha || B < 0 || B > 65535 || HW <= 0 || mask_i64 < 0 || mask_i64 > 1)
+    return fail(HIFIHR_EINVAL, "hifihr_soft_sil_loss_bwd: bad argument (B <= 65535)");
+  if (B == 0) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_soft_sil_loss_bwd(alpha, mask, mask_i64, sums, gout, B, HW, lam_sil, lam_iou, galpha, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 

@@ -96,6 +96,17 @@ hipError_t launch_render_bwd(const RenderDev& r, const float* verts, const float
                              const float* light_dir, const int* face_id, const float* grad_rgba, int B, float* gverts,
                              float* gvcolors, float* glight_color, float* glight_dir, void* ws, hipStream_t st, const TexUvPass* uv = nullptr);
 
+// Soft silhouette of the mesh at the output resolution and its two losses (csrc/soft_sil.hip); the renderer handle's faces, V, F and H
+size_t soft_sil_workspace_bytes(const RenderDev& r, int B);
+hipError_t launch_soft_sil_fwd(const RenderDev& r, const float* verts, const float* cam, int B, float sigma, float blur, float* alpha,
+                               float* neglog, void* ws, hipStream_t st);
+hipError_t launch_soft_sil_bwd(const RenderDev& r, const float* verts, const float* cam, const float* neglog, const float* galpha, int B,
+                               float sigma, float blur, float* gverts, void* ws, hipStream_t st);
+hipError_t launch_soft_sil_loss_fwd(const float* alpha, const void* mask, int mask_i64, int B, int HW, float lam_s, float lam_i, double* sums,
+                                    float* out, hipStream_t st);
+hipError_t launch_soft_sil_loss_bwd(const float* alpha, const void* mask, int mask_i64, const double* sums, const float* gout, int B, int HW,
+                                    float lam_s, float lam_i, float* galpha, hipStream_t st);
+
 // Implicit-GEMM convolution geometry.  src [N][IH][IW][IC] is gathered, dst [N][OH][OW][OC] is written.
 // forward: src = x, dst = y (ih = oh*stride - pad + r); dgrad = 1: src = dy, dst = dx (ih = (oh + pad - r)/stride).
 struct ConvGeom {

@@ -3,7 +3,8 @@
 
 ONE path: the step's terms run as fused HIP kernels -- SSIM (csrc/ssim.hip), the photometric block and the joint / vertex /
 edge-length / shape / pose terms (csrc/losses.hip: two launches per group instead of ~250 ATen launches) -- on GPU tensors; a CPU
-tensor raises (no fallback).  joint_2d / bone_direc / bone_direc_3d: one more kernel pair (round 3).  The rarely used terms (mscale, scale,
+tensor raises (no fallback).  joint_2d / bone_direc / bone_direc_3d: one more kernel pair (round 3).  sil_soft / iou_soft (not in the
+reference: `sil` and `iou` on the model's opt-in differentiable silhouette, outputs['re_sil_soft']): one kernel pair (csrc/soft_sil.hip).  The rarely used terms (mscale, scale,
 iou, mtex and the self-supervised `*_self` terms) are a handful of torch ops on the same GPU tensors.  The torch restatement of the whole function that the tests
 compare against is oracle/loss_oracle.py (pinned by the reference's own LossFunction.__call__, tests/golden/loss_dict.npz).
 """
@@ -176,6 +177,18 @@ class LossFunction:
                 outputs["re_img"] * seg + examples["imgs"] * (1 - seg), examples["imgs"])
         if "iou" in loss_used:
             loss_dic["iou"] = args.lambda_iou * iou(outputs["re_sil"], examples["segms_gt"].unsqueeze(1).float())
+        if "sil_soft" in loss_used or "iou_soft" in loss_used:
+            # the two terms of the differentiable silhouette, one kernel pair (csrc/soft_sil.hip); a term that is not requested has weight 0
+            assert "re_sil_soft" in outputs, ("the loss terms 'sil_soft' / 'iou_soft' need outputs['re_sil_soft']: build the model with "
+                                              "Model(..., soft_silhouette=True) (options: soft_silhouette)")
+            names = [k for k in ("sil_soft", "iou_soft") if k in loss_used]
+            vec = ops.soft_sil_losses(outputs["re_sil_soft"], examples["segms_gt"],
+                                      args.lambda_silhouette_soft if "sil_soft" in loss_used else 0.0,
+                                      args.lambda_iou_soft if "iou_soft" in loss_used else 0.0)
+            for k, v in zip(("sil_soft", "iou_soft"), vec.unbind(0)):
+                if k in loss_used:
+                    loss_dic[k] = v
+            self._total_parts.append((vec, 2, names))
         if "mtex" in loss_used and outputs.get("texture_params") is not None:
             loss_dic["mtex"] = args.lambda_tex_reg * F.mse_loss(outputs["texture_params"], torch.zeros_like(outputs["texture_params"]))
         return loss_dic

@@ -101,8 +101,11 @@ class MyNIMBLELayer(nn.Module):
 class Model(nn.Module):
     def __init__(self, ifRender, device, if_4c, hand_model, use_mean_shape, pretrain, root_id=9, root_id_nimble=11,
                  ifLight=True, mano_tables: ManoTables | None = None, image_size=224, aa_factor=3, texture_stand_in=0,
-                 nimble_tables: NimbleTables | None = None, conv_precision="fast"):
-        """conv_precision: "fast" (default) -- the encoder's stride-1 3x3 convolutions run as Winograd F(4x4, 3x3) / F(2x2, 3x3); "reference"
+                 nimble_tables: NimbleTables | None = None, conv_precision="fast", soft_silhouette=False, soft_sil_sigma=1e-4):
+        """soft_silhouette: with ifRender, the outputs also carry 're_sil_soft' [B, 1, H, H], a differentiable coverage of the same mesh and
+        camera the hard render sees (ops.soft_silhouette with sigma = soft_sil_sigma; the terms "sil_soft" / "iou_soft" of LossFunction
+        read it).  Off (default): the outputs and the launches are exactly those without the option.
+        conv_precision: "fast" (default) -- the encoder's stride-1 3x3 convolutions run as Winograd F(4x4, 3x3) / F(2x2, 3x3); "reference"
         -- on the direct kernels, whose outputs round like a plain fp32 convolution: features within 5e-6 of the reference's instead of
         1.3e-5, for ~50 % more time per step.  The trunk's GRADIENT error against the reference (~1e-2 of a gradient's maximum on the
         batch-of-8 fixture: ReLU sign flips) does not shrink with it (README "Precision of the default dispatch").  Per model, not per process."""
@@ -137,6 +140,7 @@ class Model(nn.Module):
                                         ifRender=ifRender, use_mean_shape=use_mean_shape)
         self.register_buffer("mano_face", self._mano_face_i32.unsqueeze(0).to(torch.int16), persistent=False)
         self.ifRender, self.ifLight, self.aa_factor, self.image_size = ifRender, ifLight, aa_factor, image_size
+        self.soft_silhouette, self.soft_sil_sigma = bool(soft_silhouette), float(soft_sil_sigma)
         if ifRender:
             # Materials(diffuse .8, specular .2, shininess 30) + DirectionalLights defaults (ambient .5, specular .2)
             if not ifLight:
@@ -248,6 +252,8 @@ class Model(nn.Module):
             outputs["re_sil"], outputs["maskRGBs"] = ops.sil_post(rgba, images)          # :219-220, one launch
             outputs["face_id"] = face_id
             outputs["skin_verts"] = verts_cam
+            if self.soft_silhouette:
+                outputs["re_sil_soft"] = ops.soft_silhouette(self.renderer_p3d, verts_cam, cam, self.soft_sil_sigma)
         outputs["mano_faces"] = self.mano_face.expand(images.shape[0], -1, -1)           # a view (the reference repeats)
         outputs["_faces_i32"] = self._mano_face_i32
         return outputs
@@ -276,6 +282,8 @@ class Model(nn.Module):
             outputs["re_img"], outputs["_rgba"] = rgba[:, :3], rgba
             outputs["re_sil"], outputs["maskRGBs"] = ops.sil_post(rgba, images)
             outputs["face_id"], outputs["skin_verts"] = face_id, verts_cam
+            if self.soft_silhouette:
+                outputs["re_sil_soft"] = ops.soft_silhouette(self.renderer_p3d, verts_cam, cam, self.soft_sil_sigma)
         outputs["mano_faces"] = self.mano_face.expand(B, -1, -1)
         outputs["_faces_i32"] = self._mano_face_i32
         return outputs

@@ -4,6 +4,7 @@ Every op here runs ONLY on the GPU through libhifihr.so; a CPU tensor raises (th
 """
 from __future__ import annotations
 
+import math
 import os
 import threading
 
@@ -346,6 +347,78 @@ def render(handle: RendererHandle, verts, vcolors, cam, light_color, light_dir):
     """renderer_p3d(meshes, cameras, lights) + avg_pool2d(aa) (models_res_nimble.py:208-211).
     -> rgba [B,4,H,H], face_id int32 [B,H*aa,H*aa]."""
     return _Render.apply(handle, verts, vcolors, cam, light_color, light_dir)
+
+
+SOFT_SIL_SIGMA = 1e-4               # BlendParams.sigma of PyTorch3D's soft silhouette recipe [recalled]
+
+
+def soft_sil_default_blur(sigma):
+    """RasterizationSettings.blur_radius of the same recipe: log(1 / 1e-4 - 1) * sigma (compared with SQUARED distances)."""
+    return math.log(1.0 / 1e-4 - 1.0) * float(sigma)
+
+
+class _SoftSilhouette(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, handle, verts, cam, sigma, blur_radius):
+        require_cuda(verts, cam)
+        verts, cam = verts.contiguous(), cam.contiguous()
+        B, H = verts.shape[0], handle.H
+        alpha = torch.empty(B, 1, H, H, device=verts.device)
+        neglog = torch.empty(B, H, H, device=verts.device)
+        ws = torch.empty(handle.lib.soft_sil_workspace_bytes(handle.h, B), dtype=torch.uint8, device=verts.device)
+        PROFILE.bracket("soft_sil_fwd", lambda: handle.lib.soft_sil_fwd(handle.h, verts, cam, sigma, blur_radius, alpha, neglog, ws))
+        ctx.handle, ctx.params = handle, (sigma, blur_radius)
+        ctx.save_for_backward(verts, cam, neglog)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, galpha):
+        verts, cam, neglog = ctx.saved_tensors
+        handle = ctx.handle
+        gverts = torch.empty_like(verts)
+        ws = torch.empty(handle.lib.soft_sil_workspace_bytes(handle.h, verts.shape[0]), dtype=torch.uint8, device=verts.device)
+        g = galpha.contiguous()
+        PROFILE.bracket("soft_sil_bwd", lambda: handle.lib.soft_sil_bwd(handle.h, verts, cam, neglog, g, ctx.params[0], ctx.params[1], gverts, ws))
+        return None, gverts, None, None, None
+
+
+def soft_silhouette(handle: RendererHandle, verts, cam, sigma=SOFT_SIL_SIGMA, blur_radius=None):
+    """A differentiable coverage of the mesh at the renderer's OUTPUT resolution, [B, 1, H, H] in [0, 1]: PyTorch3D's
+    rasterize_meshes(blur_radius > 0) + sigmoid_alpha_blend [recalled] without a faces_per_pixel cap (include/hifihr.h "Soft silhouette").
+    verts [B, V, 3] and cam [B, 4] as for render(); the gradient goes to verts.  blur_radius=None: log(1 / 1e-4 - 1) * sigma."""
+    sigma = float(sigma)
+    blur_radius = soft_sil_default_blur(sigma) if blur_radius is None else float(blur_radius)
+    return _SoftSilhouette.apply(handle, verts, cam, sigma, blur_radius)
+
+
+class _SoftSilLosses(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, alpha, mask, lam_sil, lam_iou):
+        require_cuda(alpha, mask)
+        alpha = alpha.contiguous()
+        mask = mask.contiguous() if mask.dtype in (torch.float32, torch.int64) else mask.float().contiguous()
+        assert mask.numel() == alpha.numel(), (alpha.shape, mask.shape)
+        sums = torch.empty(alpha.shape[0], 3, dtype=torch.float64, device=alpha.device)
+        out = torch.empty(2, device=alpha.device)
+        PROFILE.bracket("soft_sil_loss_fwd", lambda: get_lib().soft_sil_loss_fwd(alpha, mask, lam_sil, lam_iou, sums, out))
+        ctx.save_for_backward(alpha, mask, sums)
+        ctx.lams = (lam_sil, lam_iou)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        alpha, mask, sums = ctx.saved_tensors
+        galpha = torch.empty_like(alpha)
+        g = gout.contiguous()
+        PROFILE.bracket("soft_sil_loss_bwd", lambda: get_lib().soft_sil_loss_bwd(alpha, mask, sums, g, ctx.lams[0], ctx.lams[1], galpha))
+        return galpha, None, None, None
+
+
+def soft_sil_losses(alpha, segms_gt, lam_sil, lam_iou):
+    """[2] = (lam_sil * F.l1_loss(alpha, M), lam_iou * (1 - mean IoU)) of a soft silhouette alpha [B, 1, H, W] against the mask segms_gt
+    [B, H, W] (float32 or int64), M = the mask as float: one kernel pair (csrc/soft_sil.hip).  The IoU is losses.iou's formula, without an
+    epsilon: an image with an empty mask and zero alpha gives NaN.  A weight of exactly 0 gives that term as 0."""
+    return _SoftSilLosses.apply(alpha, segms_gt, float(lam_sil), float(lam_iou))
 
 
 # ------------------------------------------------------------------------------------------------

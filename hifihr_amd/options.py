@@ -20,6 +20,9 @@ _DEFAULTS = dict(
     ROOT=9, ROOT_NIMBLE=11,
     lpips_weights=None,    # [path, ...]: AlexNet + lin weights for the evaluation pass's LPIPS (hifihr_amd/lpips.py); None = LPIPS not reported
     benchmark_metrics=True,    # the evaluation pass also reports the FreiHAND benchmark's PCK / AUC and F-score keys (hifihr_amd/evaluate.py)
+    # opt-in differentiable silhouette (hifihr_amd/ops.py soft_silhouette; the loss names "sil_soft" / "iou_soft" switch it on as well).
+    # The two weights are the defaults of their hard counterparts lambda_silhouette / lambda_iou: starting points, not tuned values
+    soft_silhouette=False, soft_sil_sigma=1e-4, lambda_silhouette_soft=0.005, lambda_iou_soft=1e-3,
 )
 
 # lambda values of reference config/FreiHAND/full_rhd_freihand.json, used by the

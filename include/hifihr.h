@@ -189,7 +189,8 @@ int hifihr_render_fwd(const hifihr_renderer_t* h, const float* verts_d, const fl
                       const float* cam_d, const float* light_color_d, const float* light_dir_d, int B, float* rgba_d,
                       int32_t* face_id_d, void* workspace_d, void* stream);
 
-/* grad_rgba_d[B][4][H][H] (the coverage channel carries no gradient, as in the reference: SURVEY.md F7) ->
+/* grad_rgba_d[B][4][H][H] (the coverage channel carries no gradient, as in the reference: SURVEY.md F7; the differentiable
+ * coverage is hifihr_soft_sil_fwd below) ->
  * gverts_d[B][V][3], gvcolors_d[B][V][3] (may be NULL; per image also when the forward's colours were shared), glight_color_d[B][3],
  * glight_dir_d[B][3]; all overwritten.
  * Uses float atomics: results are reproducible to rounding, not bitwise. */
@@ -213,6 +214,60 @@ int hifihr_render_bwd_uv(const hifihr_renderer_t* h, const float* verts_d, const
                          const float* light_color_d, const float* light_dir_d, const int32_t* face_id_d, const float* grad_rgba_d, int B,
                          const float* texels_scratch_d, float* gtexels_scratch_d, float* gverts_d, float* gmaps_acc_d,
                          float* glight_color_d, float* glight_dir_d, void* ws_d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Soft silhouette (csrc/soft_sil.hip): a differentiable coverage of the mesh at the OUTPUT resolution, next to the hard renderer whose
+ * coverage channel carries no gradient.  Semantics of PyTorch3D's rasterize_meshes(blur_radius > 0) + sigmoid_alpha_blend
+ * (SoftSilhouetteShader) [recalled: parity is unpinned, like the rest of that boundary].  The entries reuse the renderer handle's faces, V,
+ * F and image_size H; aa is ignored (one sample per pixel centre).  Per image b and pixel (yi, xi):
+ *   vertices    xn = (X fx + Z px) / Z, yn = (Y fy + Z py) / Z with cam_d[B][4] = (fx, fy, px, py) as for hifihr_render_fwd
+ *   centre      (pix_to_ndc(H - 1 - xi, H), pix_to_ndc(H - 1 - yi, H))
+ *   per face    area = edge_fn(v2, v0, v1); inside = the three edge functions over area are all > 0; dist = min over the three edges of
+ *               the SQUARED distance from the centre to the segment (t clamped to [0, 1]); d = inside ? -dist : dist
+ *   a face participates iff its three vertices have Z > 0, |area| > 1e-8 and (inside || dist < blur_radius) -- blur_radius is compared
+ *               with the squared distance, as in PyTorch3D
+ *   S = sum over participating faces, in face-index order, of softplus(-d / sigma);   alpha = 1 - exp(-S)
+ * (= 1 - prod (1 - sigmoid(-d_f / sigma)); a pixel without a participating face is exactly 0).  Defaults of the Python surface:
+ * sigma = 1e-4, blur_radius = log(1 / 1e-4 - 1) sigma.
+ * Two departures from PyTorch3D: no faces_per_pixel cap (equal whenever K >= the number of participating faces); a face with a vertex at or
+ * behind the camera plane (Z <= 0) is left out (PyTorch3D projects such a vertex through the division).
+ * Gradient: to verts_d only (cam_d gets none, as in the renderer's Python wrapper); participation, inside, the nearest edge and the clamp
+ * are piecewise constant choices.
+ *
+ * Refused (HIFIHR_EINVAL, nothing launched, nothing written): a NULL handle or pointer; B < 0; sigma not finite or <= 0; blur_radius not
+ *   finite or < 0; the loss entries: HW <= 0, mask_i64 outside {0, 1}, and hifihr_soft_sil_loss_bwd B > 65535.
+ * Accepted: B == 0 is a no-op (nothing launched, nothing written).  hifihr_soft_sil_workspace_bytes(NULL, .) and (h, B < 0) return 0; the
+ *   size never decreases with B.
+ * Precondition, NOT checked (as for the renderer): every vertex is finite and none has Z == 0.  A NaN, an Inf or a zero Z gives
+ *   unspecified pixels and gradients, never an out-of-range access: every index comes from the face table or from integer arithmetic on
+ *   the grid, no float becomes an index.
+ * Overwritten / accumulated: hifihr_soft_sil_fwd writes EVERY element of alpha_d[B][H][H] and neglog_d[B][H][H] (= S; the backward reads
+ *   S because 1 - alpha has no precision left near full coverage).  hifihr_soft_sil_bwd OVERWRITES gverts_d[B][V][3] (a vertex no
+ *   participating face references gets 0); it zeroes its NDC-gradient accumulators inside ws_d itself and depends on nothing a forward
+ *   left there, so any ws_d of hifihr_soft_sil_workspace_bytes(h, B) bytes serves either call.  Pixels whose galpha_d is 0 or whose
+ *   exp(-S) is 0 are skipped.
+ * Repeatable: alpha_d and neglog_d have the same bits on every call (faces are listed per tile in face order by a ballot prefix, no raced
+ *   counter).  gverts_d is summed with float atomics (one per component, face corner and tile, after an on-chip sum over the tile's
+ *   pixels): reproducible to rounding, not bitwise -- as for hifihr_render_bwd.
+ * ws_d: hifihr_soft_sil_workspace_bytes(h, B) bytes, 16-byte aligned (it is written as float4 records; NOT checked).
+ * No allocation and no synchronisation inside: the entries can be captured into a hipGraph. */
+size_t hifihr_soft_sil_workspace_bytes(const hifihr_renderer_t* h, int B);
+int hifihr_soft_sil_fwd(const hifihr_renderer_t* h, const float* verts_d, const float* cam_d, int B, float sigma, float blur_radius,
+                        float* alpha_d, float* neglog_d, void* ws_d, void* stream);
+int hifihr_soft_sil_bwd(const hifihr_renderer_t* h, const float* verts_d, const float* cam_d, const float* neglog_d, const float* galpha_d,
+                        int B, float sigma, float blur_radius, float* gverts_d, void* ws_d, void* stream);
+/* The two losses of the soft silhouette in one kernel pair.  alpha_d[B][HW]; mask_d[B][HW] = segms_gt, float32 (mask_i64 = 0) or int64
+ * (mask_i64 = 1), M = its value as float.  Per image, in a fixed order and in fp64, one workgroup and no atomics:
+ *   sums_d[B][3] = (sum |A - M|, I = sum A M, sum (A + M));
+ * a finish step writes out_d[2] = (lam_sil mean |A - M|, lam_iou (1 - mean_b I_b / U_b)), U_b = sum (A + M) - I_b: F.l1_loss and the
+ * formula of hifihr_amd.losses.iou, with NO epsilon -- an image with U_b = 0 (empty mask, zero alpha) gives NaN, exactly as `iou` does.
+ * A term whose weight is exactly 0 is written as 0 (and gets no gradient) whatever its value would be.  out_d and sums_d are overwritten
+ * and have the same bits on every call.  hifihr_soft_sil_loss_bwd: one elementwise launch that OVERWRITES galpha_d[B][HW] from the two
+ * upstream scalars gout_d[2] and sums_d (the mask gets no gradient; d|A - M| / dA = 0 where A == M). */
+int hifihr_soft_sil_loss_fwd(const float* alpha_d, const void* mask_d, int mask_i64, int B, int HW, float lam_sil, float lam_iou,
+                             double* sums_d, float* out_d, void* stream);
+int hifihr_soft_sil_loss_bwd(const float* alpha_d, const void* mask_d, int mask_i64, const double* sums_d, const float* gout_d, int B, int HW,
+                             float lam_sil, float lam_iou, float* galpha_d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Texture-PCA decode (csrc/texpca.hip): tex[b][n] = mean[n] (or 0 when NULL) + sum_k coef[b][k] basis[k][n], K <= 32, n % 4 == 0.

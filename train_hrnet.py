@@ -58,8 +58,17 @@ def parse(argv=None):
                     help="report LPIPS(net='alex') beside PSNR / SSIM in the evaluation pass (reference train_hrnet.py:158,563): one or two torch "
                          "files -- torchvision's alexnet state dict and the lpips package's alex.pth, or the package's full LPIPS state dict "
                          "(hifihr_amd/lpips.py: load_state_dict_lpips).  Without it LPIPS is not reported.")
+    ap.add_argument("--soft_silhouette", action="store_true",
+                    help="the model also emits outputs['re_sil_soft'], a differentiable silhouette (options: soft_silhouette, soft_sil_sigma); "
+                         "the loss names 'sil_soft' / 'iou_soft' switch it on by themselves")
     ap.add_argument("--override", default=None, help='JSON object of option overrides, e.g. \'{"total_epochs": 2}\'')
     return ap.parse_args(argv)
+
+
+def soft_silhouette_kwargs(args):
+    """Model(...)'s soft-silhouette options: on when asked for, or when a loss term that reads outputs['re_sil_soft'] is requested."""
+    on = bool(getattr(args, "soft_silhouette", False)) or any(k in args.losses for k in ("sil_soft", "iou_soft"))
+    return dict(soft_silhouette=on, soft_sil_sigma=float(getattr(args, "soft_sil_sigma", 1e-4)))
 
 
 def build_args(cli):
@@ -75,6 +84,8 @@ def build_args(cli):
     args.state_output = os.path.join(args.base_out_path, "model")       # options/train_options.py:208-220
     args.pred_output = os.path.join(args.base_out_path, "json")         # :214 (the pred.json dumps)
     args.texture_stand_in = 0
+    if getattr(cli, "soft_silhouette", False):
+        args.soft_silhouette = True
     if cli.lpips_weights:
         args.lpips_weights = list(cli.lpips_weights)
     elif isinstance(getattr(args, "lpips_weights", None), str):        # a JSON may name one file
@@ -318,7 +329,7 @@ def main(argv=None):
     model = Model(ifRender=args.render, device=device, if_4c=args.four_channel, hand_model=args.hand_model,
                   use_mean_shape=args.use_mean_shape, pretrain=args.pretrain, root_id=args.ROOT, root_id_nimble=args.ROOT_NIMBLE,
                   ifLight=args.light_estimation, mano_tables=tables, texture_stand_in=args.texture_stand_in,
-                  nimble_tables=nimble_tables).to(device).train()
+                  nimble_tables=nimble_tables, **soft_silhouette_kwargs(args)).to(device).train()
     frozen = freeze_model_modules(model, args)          # only_train_regressor / only_train_texture (train_hrnet.py:566)
     if frozen:
         say("[train_hrnet] frozen:", ", ".join(frozen))
