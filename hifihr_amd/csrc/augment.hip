@@ -101,9 +101,8 @@ __global__ __launch_bounds__(256) void freihand_augment4_kernel(const uint32_t* 
 
 static void launch_augment_planes(const uint32_t* img, const uint8_t* mask, const int* idx, const int* coef, int B, int H, int W, float* out_img,
                                   float* out_mask, long long* out_segm, hipStream_t st) {
-  static const int vec = [] { const char* e = getenv("HIFIHR_AUGMENT_VEC4"); return e ? atoi(e) : 1; }();
   const bool aligned = ((reinterpret_cast<uintptr_t>(out_img) | reinterpret_cast<uintptr_t>(out_mask) | reinterpret_cast<uintptr_t>(out_segm)) & 15) == 0;
-  if (vec && W % 4 == 0 && aligned)
+  if (W % 4 == 0 && aligned)
     hipLaunchKernelGGL(freihand_augment4_kernel, dim3((H * (W / 4) + 255) / 256, B), dim3(256), 0, st, img, mask, idx, coef, H, W, out_img, out_mask,
                        out_segm);
   else

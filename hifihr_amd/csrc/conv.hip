@@ -123,11 +123,7 @@ __device__ __forceinline__ GatherPlan make_plan(const ConvGeom& g, int cls) {
 #define HIFIHR_WAVES_PER_EU(n)
 #define HIFIHR_WAIT_VMEM() ((void)0)
 #else
-#if defined(HIFIHR_CONV_NO_CAP)       /* tuning builds (tools/build_conv_probes.sh) */
-#define HIFIHR_WAVES_PER_EU(n)
-#else
 #define HIFIHR_WAVES_PER_EU(n) __attribute__((amdgpu_waves_per_eu(n)))
-#endif
 // Wait until this wave's outstanding vector-memory operations (here: its device-scope atomic adds, which execute at the
 // memory side) have been acknowledged.  NOT __threadfence(): an agent-scope fence also writes back and invalidates this
 // XCD's L2 (buffer_wbl2 / buffer_inv sc1), which nothing here needs -- the hand-off below consists of atomics only -- and
@@ -721,63 +717,47 @@ __global__ __launch_bounds__(256) void image_to_nhwc4_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-template <int BM, int BN>
+// Measured on MI355X at B = 32 (tools/time_conv.py, round 1): the 64x64 tile wins on every ResNet-18 layer (7 resident workgroups per CU
+// hide the per-chunk barrier); the gather that takes any channel count (the 4-channel stem) runs 128x64.
 static void launch_igemm_tile(const ConvGeom& g, long Mmax, int classes, bool generic, int bk, const float* src, const float* wgt,
                               const float* bias, float* dst, float* stats, hipStream_t st) {
+  const int BM = generic ? 128 : 64, BN = 64;
   const dim3 grid((unsigned)((Mmax + BM - 1) / BM), (g.OC + BN - 1) / BN, g.batch > 1 ? g.batch : classes);
   const SkArgs none{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, nullptr, nullptr};
   if (generic)
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, true, 16, false>), grid, dim3(256), 0, st, g, src, wgt, bias, dst, stats, none);
+    hipLaunchKernelGGL((conv_igemm_kernel<128, 64, true, 16, false>), grid, dim3(256), 0, st, g, src, wgt, bias, dst, stats, none);
   else if (bk == 32)
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, false, 32, false>), grid, dim3(256), 0, st, g, src, wgt, bias, dst, stats, none);
+    hipLaunchKernelGGL((conv_igemm_kernel<64, 64, false, 32, false>), grid, dim3(256), 0, st, g, src, wgt, bias, dst, stats, none);
   else
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, false, 16, false>), grid, dim3(256), 0, st, g, src, wgt, bias, dst, stats, none);
+    hipLaunchKernelGGL((conv_igemm_kernel<64, 64, false, 16, false>), grid, dim3(256), 0, st, g, src, wgt, bias, dst, stats, none);
 }
 
 // ---- balanced schedule (one gather class, source channels % 32 == 0) ----
 constexpr int kSkMinChunks = 16;         // K chunks per tile below which splitting is not worth a workspace round trip
-
-// variant of the persistent kernel: tile, K-chunk depth and the number of workgroups that are resident per CU
-struct SkVariant {
-  int bm, bn, bk, occ;
-};
-static SkVariant sk_variant() {
-  // 0: 64x64 BK32 (36.9 KB LDS, <= 128 VGPRs: 4 per CU).  Others are tuning experiments (HIFIHR_CONV_SK_VARIANT).
-  static const SkVariant v[] = {{64, 64, 32, 4}, {128, 64, 16, 3}, {128, 64, 32, 2}, {128, 128, 16, 2}};
-  int i = 0;
-  if (const char* e = getenv("HIFIHR_CONV_SK_VARIANT")) i = atoi(e);
-  if (i < 0 || i > 3) i = 0;
-  SkVariant r = v[i];
-  if (const char* e = getenv("HIFIHR_CONV_SK_OCC")) r.occ = atoi(e) > 0 ? atoi(e) : r.occ;
-  return r;
-}
+// the persistent kernel: 64x64 tile, K chunks of 32 (36.9 KB LDS, <= 128 VGPRs), 4 workgroups resident per CU
+constexpr int kSkBM = 64, kSkBN = 64, kSkBK = 32, kSkOcc = 4;
 
 struct SkPlan {
   bool use;
   int tiles_x, tiles, nch, wgs, per;
-  SkVariant v;
 };
 
 static SkPlan sk_plan(const ConvGeom& g) {
-  SkPlan p{false, 0, 0, 0, 0, 0, sk_variant()};
-  if (const char* e = getenv("HIFIHR_CONV_SK")) { if (atoi(e) == 0) return p; }
+  SkPlan p{false, 0, 0, 0, 0, 0};
   const bool one_class = !g.dgrad || g.stride == 1;
   if (!one_class || g.IC % 32 != 0) return p;
   const long M = (long)g.N * g.OH * g.OW;
-  p.tiles_x = (int)((M + p.v.bm - 1) / p.v.bm);
-  p.tiles = p.tiles_x * ((g.OC + p.v.bn - 1) / p.v.bn) * (g.batch > 1 ? g.batch : 1);
-  p.nch = g.R * g.S * (g.IC / p.v.bk);
-  const int slots = device_cus() * p.v.occ;
-  int minch = kSkMinChunks;
-  if (const char* e = getenv("HIFIHR_CONV_SK_MINCH")) minch = atoi(e);
+  p.tiles_x = (int)((M + kSkBM - 1) / kSkBM);
+  p.tiles = p.tiles_x * ((g.OC + kSkBN - 1) / kSkBN) * (g.batch > 1 ? g.batch : 1);
+  p.nch = g.R * g.S * (g.IC / kSkBK);
+  const int slots = device_cus() * kSkOcc;
   // (fewer tiles than a quarter of the slots stay data-parallel: the balanced schedule for EfficientNet's 7 x 7 / 14 x 14 pointwise layers --
-  //  37-150 tiles -- measured 34.04 vs 33.82 ms per config-3 step, HIFIHR_CONV_SK_TILEDIV=32: the workspace round trip costs more than the
+  //  37-150 tiles -- measured 34.04 ms per config-3 step with the bound at a 32nd against 33.82: the workspace round trip costs more than the
   //  idle CUs; those products are bound by each workgroup streaming the whole weight panel for 16-64 rows)
-  static const int min_tile_div = [] { const char* e = getenv("HIFIHR_CONV_SK_TILEDIV"); return e && atoi(e) > 0 ? atoi(e) : 4; }();
-  if (p.nch * p.v.bk < minch * 32 || p.tiles < slots / min_tile_div) return p;
+  if (p.nch * kSkBK < kSkMinChunks * 32 || p.tiles < slots / 4) return p;
   // rounds the data-parallel grid costs vs the balanced share: only switch when > 5 % is on the table
   const double dp = (double)((p.tiles + slots - 1) / slots), sk = (double)p.tiles / slots;
-  if (dp < 1.05 * sk && p.v.bm == 64) return p;
+  if (dp < 1.05 * sk) return p;
   const long total = (long)p.tiles * p.nch;
   p.per = (int)((total + slots - 1) / slots);
   p.wgs = (int)((total + p.per - 1) / p.per);
@@ -786,11 +766,10 @@ static SkPlan sk_plan(const ConvGeom& g) {
 }
 
 static size_t sk_bytes(const SkPlan& p) {
-  return p.use ? (size_t)((p.tiles * sizeof(unsigned) + 255) / 256 * 256) + (size_t)p.tiles * p.v.bm * p.v.bn * sizeof(float) : 0;
+  return p.use ? (size_t)((p.tiles * sizeof(unsigned) + 255) / 256 * 256) + (size_t)p.tiles * kSkBM * kSkBN * sizeof(float) : 0;
 }
 size_t conv_sk_workspace_bytes(const ConvGeom& g) { return sk_bytes(sk_plan(g)); }
 
-template <int BM, int BN, int BK>
 static void launch_sk(const SkPlan& p, const ConvGeom& g, const float* src, const float* wgt, float* dst, float* stats, void* sk_ws,
                       hipStream_t st) {
   const size_t cnt_bytes = (p.tiles * sizeof(unsigned) + 255) / 256 * 256;
@@ -798,10 +777,9 @@ static void launch_sk(const SkPlan& p, const ConvGeom& g, const float* src, cons
   SkArgs a{p.tiles_x, p.tiles / nb / p.tiles_x, p.nch, p.per, p.tiles * p.nch, 0, 0, 0, 0, p.tiles / nb,
            reinterpret_cast<float*>(static_cast<char*>(sk_ws) + cnt_bytes), static_cast<unsigned*>(sk_ws)};
   int wgs = p.wgs;
-  const int slots = device_cus() * p.v.occ;
+  const int slots = device_cus() * kSkOcc;
   // measured (tools/time_conv_sk.py): +1.5 % on the 144-chunk layer-4 shapes, -9 % on 36-chunk layer 2 (short tails): long K only
-  bool inphase = p.tiles % 8 == 0 && slots % 8 == 0 && p.tiles <= slots && (p.nch >= 100 || device_cus() < 16);
-  if (const char* e = getenv("HIFIHR_CONV_SK_INPHASE")) inphase = inphase && atoi(e) != 0;
+  const bool inphase = p.tiles % 8 == 0 && slots % 8 == 0 && p.tiles <= slots && (p.nch >= 100 || device_cus() < 16);
   if (inphase) {
     const int Tx = p.tiles / 8, Gx = slots / 8;
     int S = (int)(((long)Tx * p.nch + Gx - 1) / Gx);
@@ -813,7 +791,7 @@ static void launch_sk(const SkPlan& p, const ConvGeom& g, const float* src, cons
     a.tper = (S < p.nch && ntail > 0) ? (int)(((long)Tx * (p.nch - S) + ntail - 1) / ntail) : 1;
     wgs = slots;
   }
-  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, false, BK, true>), dim3(wgs), dim3(256), 0, st, g, src, wgt, nullptr, dst, stats, a);
+  hipLaunchKernelGGL((conv_igemm_kernel<kSkBM, kSkBN, false, kSkBK, true>), dim3(wgs), dim3(256), 0, st, g, src, wgt, nullptr, dst, stats, a);
 }
 
 // 3x3 / stride 1 / pad 1 onto FOUR output channels: the backward-data of a network's first layer on an NHWC4 image (VGG19 conv1_1 of the
@@ -995,8 +973,7 @@ __global__ __launch_bounds__(256) void conv3x3_oc4_tile_kernel(const float* __re
 }
 
 static bool conv_oc4_supported(const ConvGeom& g, const float* bias, const float* stats) {
-  static const int on = [] { const char* e = getenv("HIFIHR_CONV_OC4"); return e ? atoi(e) : 1; }();
-  return on && g.OC == 4 && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && (g.IC == 64 || g.IC == 32) && g.batch <= 1 && !g.relu &&
+  return g.OC == 4 && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && (g.IC == 64 || g.IC == 32) && g.batch <= 1 && !g.relu &&
          bias == nullptr && stats == nullptr && g.IH == g.OH && g.IW == g.OW;
 }
 
@@ -1004,7 +981,7 @@ static bool conv_oc4_supported(const ConvGeom& g, const float* bias, const float
 // conv1 / conv3 of a bottleneck block): it runs on the kernels of csrc/gemm.hip, 2-3x faster there than as an implicit GEMM with one tap
 // (tools/time_conv1x1.py).  HIFIHR_CONV1X1_GEMM=0 keeps the implicit-GEMM kernels (A/B timing).
 bool conv_is_gemm(const ConvGeom& g) {
-  static const int on = [] { const char* e = getenv("HIFIHR_CONV1X1_GEMM"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("HIFIHR_CONV1X1_GEMM", 1);
   const long M = (long)g.N * g.OH * g.OW;
   return on && g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && g.batch <= 1 && g.OH == g.IH && g.OW == g.IW &&
          M * (g.IC > g.OC ? g.IC : g.OC) < (1L << 31) &&
@@ -1052,8 +1029,8 @@ struct ConvPlan {
   ConvKernel kernel;
   NtPlan nt;               // gemm
   SkPlan sk;               // sk
-  int tile, bk, classes;   // tiled: 0: 128x128, 1: 128x64, 2: 64x64; K-chunk depth; parity classes of a strided backward-data
-  bool generic;            // tiled: the gather that takes any channel count
+  int bk, classes;         // tiled: K-chunk depth; parity classes of a strided backward-data
+  bool generic;            // tiled: the gather that takes any channel count (128x64 tile; 64x64 otherwise)
   long Mmax;               // tiled: rows of the largest class
 };
 static ConvPlan plan_conv(const ConvGeom& g, const float* bias, const float* stats, size_t ws_bytes, bool zero_page) {
@@ -1066,8 +1043,7 @@ static ConvPlan plan_conv(const ConvGeom& g, const float* bias, const float* sta
   if (g.src2 != nullptr && (!g.dgrad || g.stride < 2 || g.wgt2 == nullptr || g.batch > 1 || g.IC % 16 != 0 || g.R * g.S > 62)) return p;
   if (res && !g.dgrad) return p;
   p.err = hipSuccess;
-  static const int oc4_tiled = [] { const char* e = getenv("HIFIHR_OC4_TILE"); return e ? atoi(e) : 1; }();
-  if (!res && conv_oc4_supported(g, bias, stats)) { p.kernel = (g.IC == 64 && oc4_tiled) ? ConvKernel::oc4_tile : ConvKernel::oc4; return p; }
+  if (!res && conv_oc4_supported(g, bias, stats)) { p.kernel = g.IC == 64 ? ConvKernel::oc4_tile : ConvKernel::oc4; return p; }
   // (the GEMM kernels have no activation epilogue: a fused ReLU keeps the implicit-GEMM kernel; the statistics of a batch-norm consumer
   // come out of the row-share kernel's epilogue)
   if (!res && conv_is_gemm(g) && bias == nullptr && !g.relu && (stats == nullptr || bgemm_nt_stats_supported(g.OC))) {
@@ -1080,17 +1056,12 @@ static ConvPlan plan_conv(const ConvGeom& g, const float* bias, const float* sta
   if (zero_page && conv_stem_supported(g, bias)) { p.kernel = ConvKernel::stem; return p; }
   p.generic = (g.IC % 16) != 0 || g.R * g.S > 62;   // (62 tap bits + the row bit + the "no tap" bit of the gather's mask)
   p.bk = (g.IC % 32 == 0) ? 32 : 16;
-  if (const char* e = getenv("HIFIHR_CONV_BK")) p.bk = (atoi(e) == 32 && g.IC % 32 == 0) ? 32 : 16;   // tuning override
   p.classes = g.dgrad ? g.stride * g.stride : 1;
   // strided dgrad needs source channels % 16 == 0
   if ((p.generic && g.dgrad && g.stride != 1) || (g.batch > 1 && (p.classes != 1 || bias != nullptr || stats != nullptr))) { p.err = hipErrorInvalidValue; return p; }
   const int st_ = g.dgrad ? g.stride : 1;
   p.Mmax = (long)g.N * ((g.OH + st_ - 1) / st_) * ((g.OW + st_ - 1) / st_);
-  // Measured on MI355X at B = 32 (tools/time_conv.py, round 1): the 64x64 tile wins on every ResNet-18 layer (7 resident workgroups per CU
-  // hide the per-chunk barrier), except the 4-channel stem.  HIFIHR_CONV_TILE: tuning / diagnostic override
-  p.tile = p.generic ? 1 : 2;
-  if (const char* e = getenv("HIFIHR_CONV_TILE")) p.tile = atoi(e);
-  if (ws_bytes > 0 && p.tile == 2 && p.bk == 32 && bias == nullptr && g.src2 == nullptr) {
+  if (ws_bytes > 0 && !p.generic && p.bk == 32 && bias == nullptr && g.src2 == nullptr) {
     p.sk = sk_plan(g);
     if (p.sk.use && ws_bytes >= sk_bytes(p.sk)) p.kernel = ConvKernel::sk;
   }
@@ -1119,12 +1090,11 @@ hipError_t launch_conv_igemm(const ConvGeom& g, const float* src, const float* w
   switch (p.kernel) {
     case ConvKernel::oc4_tile:
     case ConvKernel::oc4: {
-      // 16 x 8-pixel tiles, two workgroups per CU; 16 x 16-pixel tiles, grid-stride (the filter goes to LDS once per workgroup)
+      // 64 channels: 16 x 8-pixel tiles, two workgroups per CU; 32 channels: 16 x 16-pixel tiles, grid-stride (the filter goes to LDS once per workgroup)
       const bool t = p.kernel == ConvKernel::oc4_tile;
       long blocks = (long)g.N * ((g.OH + (t ? 7 : 15)) / (t ? 8 : 16)) * ((g.OW + 15) / 16);
       if (blocks > (long)device_cus() * (t ? 2 : 16)) blocks = (long)device_cus() * (t ? 2 : 16);
       if (t) hipLaunchKernelGGL(conv3x3_oc4_tile_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, st, src, wgt, dst, g.N, g.OH, g.OW, sign);
-      else if (g.IC == 64) hipLaunchKernelGGL(conv3x3_oc4_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, st, src, wgt, dst, g.N, g.OH, g.OW, sign);
       else hipLaunchKernelGGL(conv3x3_oc4_kernel<32>, dim3((unsigned)blocks), dim3(256), 0, st, src, wgt, dst, g.N, g.OH, g.OW, sign);
       break;
     }
@@ -1133,15 +1103,10 @@ hipError_t launch_conv_igemm(const ConvGeom& g, const float* src, const float* w
     case ConvKernel::rows: return launch_conv_rows(g, src, wgt, dst, stats, zeros, st);
     case ConvKernel::stem: return launch_conv_stem(g, src, wgt, dst, stats, zeros, st);
     case ConvKernel::sk:
-      if (p.sk.v.bm == 64) launch_sk<64, 64, 32>(p.sk, g, src, wgt, dst, stats, sk_ws, st);
-      else if (p.sk.v.bn == 128) launch_sk<128, 128, 16>(p.sk, g, src, wgt, dst, stats, sk_ws, st);
-      else if (p.sk.v.bk == 16) launch_sk<128, 64, 16>(p.sk, g, src, wgt, dst, stats, sk_ws, st);
-      else launch_sk<128, 64, 32>(p.sk, g, src, wgt, dst, stats, sk_ws, st);
+      launch_sk(p.sk, g, src, wgt, dst, stats, sk_ws, st);
       break;
     case ConvKernel::tiled:
-      if (p.tile == 0) launch_igemm_tile<128, 128>(g, p.Mmax, p.classes, p.generic, p.bk, src, wgt, bias, dst, stats, st);
-      else if (p.tile == 1) launch_igemm_tile<128, 64>(g, p.Mmax, p.classes, p.generic, p.bk, src, wgt, bias, dst, stats, st);
-      else launch_igemm_tile<64, 64>(g, p.Mmax, p.classes, p.generic, p.bk, src, wgt, bias, dst, stats, st);
+      launch_igemm_tile(g, p.Mmax, p.classes, p.generic, p.bk, src, wgt, bias, dst, stats, st);
   }
   return hipGetLastError();
 }
@@ -1156,8 +1121,6 @@ static void launch_wgrad_tile(const ConvGeom& g, int Q, long M, int slots, const
   // tiles * splits workgroups: stay at or just below the resident slots so that every CU gets the same number (the
   // dispatcher spreads a grid evenly; 1152 workgroups on 1024 slots cost five rounds on some CUs: tools/conv_quant_probe.py)
   int splits = slots / tiles;
-  if (const char* e = getenv("HIFIHR_WGRAD_SPLITS")) splits = atoi(e);
-  if (const char* e = getenv("HIFIHR_WGRAD_MAXSPLIT")) { if (splits > atoi(e)) splits = atoi(e); }
   if (splits > nch / 4) splits = nch / 4;
   if (splits < 1) splits = 1;
   const int cps = (nch + splits - 1) / splits;
@@ -1175,20 +1138,16 @@ struct WgradPlan {
   WgradKernel kernel;
   size_t ws_bytes;         // scratch the kernel wants (tiled: none)
   int parts;               // gemm: row slabs
-  int bm, bn, bkw, slots;  // tiled: tile, K-chunk depth, resident workgroups to fill
+  int bm, slots;           // tiled: the square tile's side (128 or 64), resident workgroups to fill
 };
 static WgradPlan plan_wgrad(const ConvGeom& g, size_t ws_bytes) {
   WgradPlan p{};
-  // 0: 128x128 (4 resident per CU), 1: 64x128, n >= 2: 64x64 with n workgroups per CU.  Measured at B = 32 (tools/time_wgrad.py):
+  // 128x128 (4 resident per CU) or 64x64 (8 per CU), K chunks of 16.  Measured at B = 32 (tools/time_wgrad.py):
   // the atomic epilogue moves (workgroups x tile bytes), so below 512 output channels the 64x64 tile (a quarter of the atomic
   // volume, 8 per CU) wins by 5-15 %; the 29.6 GFLOP layer-4 shapes keep the 128x128 tile (100 vs 81 TF).
   // (every plan carries the tile: the slab kernels hand a launch they cannot set up inside a stream capture to the atomics kernel)
-  int tile = (g.OC % 128 == 0 && g.OC >= 512) ? 0 : 8;
-  if (const char* e = getenv("HIFIHR_WGRAD_TILE")) tile = atoi(e);
-  p.bkw = 16;
-  if (const char* e = getenv("HIFIHR_WGRAD_BK")) p.bkw = (atoi(e) == 32 && tile != 1) ? 32 : 16;
-  p.bm = tile == 0 ? 128 : 64; p.bn = (tile == 0 || tile == 1) ? 128 : 64;
-  p.slots = device_cus() * (tile == 0 ? (p.bkw == 32 ? 2 : 4) : (tile == 1 || tile == 2) ? 4 : tile);
+  p.bm = (g.OC % 128 == 0 && g.OC >= 512) ? 128 : 64;
+  p.slots = device_cus() * (p.bm == 128 ? 4 : 8);
   const int M = (int)((long)g.N * g.OH * g.OW);
   // a 64 x 256 filter is only four 64x64 tiles: 128 row slabs of it (71 us at 32 x 56 x 56) lose to conv_wgrad_kernel's atomics (55 us)
   if (conv_is_gemm(g) && (long)g.OC * g.IC >= 32768 && bgemm_tn_supported(g.OC, g.IC, M)) {
@@ -1211,7 +1170,7 @@ void conv_wgrad_describe(const ConvGeom& g, char* out, int cap) {      // with t
 // dw += the weight gradient of the strided convolution g, dw2 += the weight gradient of the 1x1 / same stride / pad 0 convolution of the same
 // input with the same output channels, in ONE launch of conv_wgrad_kernel (see its header)
 bool conv_wgrad_plus1x1_supported(const ConvGeom& g) {
-  static const int on = [] { const char* e = getenv("HIFIHR_WGRAD_PLUS1X1"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("HIFIHR_WGRAD_PLUS1X1", 1);
   return on && !g.dgrad && g.stride >= 2 && g.pad < g.R && g.pad < g.S && g.batch <= 1 && g.IC % 4 == 0 && g.OC % 4 == 0 &&
          g.OH == (g.IH - 1) / g.stride + 1 && g.OW == (g.IW - 1) / g.stride + 1 && plan_wgrad(g, SIZE_MAX).kernel == WgradKernel::tiled;
 }
@@ -1249,10 +1208,7 @@ hipError_t launch_conv_wgrad(const ConvGeom& g, const float* x, const float* dy,
   if (p.kernel == WgradKernel::halo) e = launch_conv_halo_wgrad(g, x, dy, dw, slabs, st);
   if (p.kernel == WgradKernel::stem) e = launch_conv_stem_wgrad(g, x, dy, dw, slabs, st);
   if (e != hipErrorNotReady) return e;
-  if (p.bm == 128 && p.bkw == 32) launch_wgrad_tile<128, 128, 32>(g, Q, M, p.slots, x, dy, dw, st);
-  else if (p.bm == 128) launch_wgrad_tile<128, 128, 16>(g, Q, M, p.slots, x, dy, dw, st);
-  else if (p.bn == 128) launch_wgrad_tile<64, 128, 16>(g, Q, M, p.slots, x, dy, dw, st);
-  else if (p.bkw == 32) launch_wgrad_tile<64, 64, 32>(g, Q, M, p.slots, x, dy, dw, st);
+  if (p.bm == 128) launch_wgrad_tile<128, 128, 16>(g, Q, M, p.slots, x, dy, dw, st);
   else launch_wgrad_tile<64, 64, 16>(g, Q, M, p.slots, x, dy, dw, st);
   return hipGetLastError();
 }

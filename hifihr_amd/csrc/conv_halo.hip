@@ -62,15 +62,13 @@ struct HaloArgs {
 struct Tile { int n, x0, y0, rows; };
 
 // rows of the tile that starts at strip `cur` of a share ending at `end`; the tile itself (strips are ordered (n, column tile, y))
-// `lead`: the row limit of the share's FIRST tile (strip `first`), kTH elsewhere -- odd workgroups of conv_wino2_kernel start with a 4-row
-// tile so that the tile ends (output bursts) of neighbouring workgroups do not coincide
-__device__ __forceinline__ int tile_rows(int H, int cur, int end, int first = -1, int lead = kTH) {
-  return min(min(cur == first ? lead : kTH, H - cur % H), end - cur);
+__device__ __forceinline__ int tile_rows(int H, int cur, int end) {
+  return min(min(kTH, H - cur % H), end - cur);
 }
-__device__ __forceinline__ Tile tile_of(int H, int ctiles, int cur, int end, int first = -1, int lead = kTH) {
+__device__ __forceinline__ Tile tile_of(int H, int ctiles, int cur, int end) {
   const int col = cur / H, y = cur - col * H;
   const int n = col / ctiles, ct = col - n * ctiles;
-  return Tile{n, ct * kTW, y, min(min(cur == first ? lead : kTH, H - y), end - cur)};
+  return Tile{n, ct * kTW, y, min(min(kTH, H - y), end - cur)};
 }
 
 // the tile that starts at strip `cur` of a share ending at `end`
@@ -86,19 +84,9 @@ __device__ __forceinline__ Tile tile_at(const HaloArgs& a, int cur, int end) {
 // HIFIHR_HALO_STAMP (diagnostic build, tools/build_halo_probe.sh + tools/halo_stamp.py): MFMA wave 0 of every workgroup adds to
 // g_halo_stamp [0] cycles inside the chunk loops, [1] 100 MHz ticks of the same spans, [2] chunks, [3] cycles at the per-chunk
 // barrier, [4] workgroups, [5] cycles kernel entry -> exit, [6] cycles in the epilogues, [7] loader wave 0: cycles waiting on vmcnt
-// HIFIHR_HALO_ABLATE (timing experiments only, results are wrong): 1 = no loader waves and no barriers (the MFMA waves' own
-// instruction stream alone), 2 = also no LDS reads (MFMA only), 3 = loaders and barriers kept, LDS reads removed
-#ifndef HIFIHR_HALO_ABLATE
-#define HIFIHR_HALO_ABLATE 0
-#endif
 #if defined(HIFIHR_HALO_STAMP)
 __device__ unsigned long long g_halo_stamp[8];
 #define HALO_T() __builtin_amdgcn_s_memtime()
-#endif
-#if HIFIHR_HALO_ABLATE == 1 || HIFIHR_HALO_ABLATE == 2
-#define HALO_BARRIER() ((void)0)
-#else
-#define HALO_BARRIER() HIFIHR_RAW_BARRIER()
 #endif
 
 // EPI: the epilogue adds a bias, applies ReLU and masks a ragged last column tile (the perceptual loss's VGG19 conv1_2; any W % 14 != 0).
@@ -121,7 +109,6 @@ __global__ __launch_bounds__(256 + 64 * kNL) void conv_halo_kernel(HaloArgs a) {
   const int ntaps = ntiles * kTaps;                          // iterations of this workgroup: one per (tile, tap)
 
   if (wave >= 4) {
-    if (HIFIHR_HALO_ABLATE == 1 || HIFIHR_HALO_ABLATE == 2) return;
     // ---------------- loader ----------------
     const int l = wave - 4;
     HIFIHR_SET_LOADER_PRIO();
@@ -231,7 +218,7 @@ __global__ __launch_bounds__(256 + 64 * kNL) void conv_halo_kernel(HaloArgs a) {
   float ssum[4] = {0.f, 0.f, 0.f, 0.f}, ssq[4] = {0.f, 0.f, 0.f, 0.f}, sk[4] = {0.f, 0.f, 0.f, 0.f};
   int sn = 0;
 
-  HALO_BARRIER();                                            // barrier -1
+  HIFIHR_RAW_BARRIER();                                      // barrier -1
   int cur = s_lo, gt = 0;
   // one tile with NB MFMA row blocks (7: up to 8 rows, 4: up to 4 rows = 56 pixels)
   auto run_tile = [&](auto nbc, const Tile& t, int hbuf) {
@@ -239,15 +226,6 @@ __global__ __launch_bounds__(256 + 64 * kNL) void conv_halo_kernel(HaloArgs a) {
     float fm[2][NB][4], fn[2][4];
     // fragments of quarter qd = 2 * (channel half) + h (16 input channels) of tap `tap` of this tile; weights of global tap gtt
     auto read_q = [&](int gtt, int tap, int qd, int slot) {
-      if (HIFIHR_HALO_ABLATE >= 2) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          HIFIHR_TOUCH(fn[slot][k]);
-#pragma unroll
-          for (int j = 0; j < NB; ++j) HIFIHR_TOUCH(fm[slot][j][k]);
-        }
-        return;
-      }
       const int tr = tap / 3, ts = tap - 3 * tr;
       const int toff = (1 + a.sign * (tr - 1)) * kHP + (1 + a.sign * (ts - 1));
       const int hu = hbuf * (kHalo * 4) + toff * (kPixF * 4) + qd * 64;                               // (uniform)
@@ -309,7 +287,7 @@ __global__ __launch_bounds__(256 + 64 * kNL) void conv_halo_kernel(HaloArgs a) {
       HIFIHR_TOUCH(acc[0][0]);
       const unsigned long long b0 = HALO_T();
 #endif
-      HALO_BARRIER();                                        // barrier gt
+      HIFIHR_RAW_BARRIER();                                  // barrier gt
 #if defined(HIFIHR_HALO_STAMP)
       st_bar += HALO_T() - b0;
 #endif
@@ -399,7 +377,7 @@ __global__ __launch_bounds__(256 + 64 * kNL) void conv_halo_kernel(HaloArgs a) {
 // weight stages wait for the stores to RETIRE (~2 us each): 700-1 300 cycles at every barrier, 57 us; (2) two loader + two output waves:
 // a wave issues one LDS-DMA instruction per ~200 cycles, so 16 pieces per loader wave and stage take 3 500 cycles: 65 us (108 when the
 // unrolled loader spilled: a scratch reload in a loader costs microseconds); (3) four accumulator chains instead of two, scheduler hints
-// removed: +-0; (4) odd workgroups starting with a 4-row tile so that tile ends do not coincide (HIFIHR_W2_STAGGER): +-0 at B = 32, 18 -> 22 us at
+// removed: +-0; (4) odd workgroups starting with a 4-row tile so that tile ends do not coincide: +-0 at B = 32, 18 -> 22 us at
 // B = 8 -- the epilogue's cost is the issue of its 8 stores per lane, not a burst on the fabric.  profiles/r03_time_conv_wino2.txt, r03_wino2_stamps.txt.
 // ------------------------------------------------------------------------------------------------
 namespace {
@@ -443,9 +421,6 @@ __device__ __forceinline__ float comp(const F4& a, int k) { return k < 2 ? a.lo[
 #ifndef HIFIHR_W2_ABLATE
 #define HIFIHR_W2_ABLATE 0
 #endif
-#ifndef HIFIHR_W2_STAGGER
-#define HIFIHR_W2_STAGGER 0
-#endif
 // STATS: the batch-norm statistics epilogue of the forward (24 registers of shifted sums) is compiled in -- the kernel sits at the 256-register
 // limit of its 512-thread workgroup, and backward-data launches do without them
 // (the body, so that conv_c64_bwd_pair_kernel can run it on a SHARE of a launch's workgroups: bid of nblk)
@@ -462,8 +437,7 @@ __device__ __forceinline__ void wino2_body(const Wino2Args& a, float* __restrict
   const int s_lo = wg * a.per, s_hi = min(s_lo + a.per, a.total);
   if (s_lo >= s_hi) return;                                  // (uniform)
   int ntiles = 0;
-  const int lead = HIFIHR_W2_STAGGER && (wg & 1) ? 4 : kTH;
-  for (int cur = s_lo; cur < s_hi; cur += tile_rows(a.H, cur, s_hi, s_lo, lead)) ++ntiles;
+  for (int cur = s_lo; cur < s_hi; cur += tile_rows(a.H, cur, s_hi)) ++ntiles;
   const int nst = ntiles * kW2Stages;                        // iterations of this workgroup: one per (tile, stage)
 
   if (wave >= 4) {
@@ -503,7 +477,7 @@ __device__ __forceinline__ void wino2_body(const Wino2Args& a, float* __restrict
     };
     const int nh = (kHaloPieces - l + kNL - 1) / kNL;
     int cur = s_lo;
-    Tile t = tile_of(a.H, a.ctiles, cur, s_hi, s_lo, lead);
+    Tile t = tile_of(a.H, a.ctiles, cur, s_hi);
 #pragma unroll
     for (int i = 0; i < kHaloPer; ++i)
       if (i < nh) issue_h1(t, 0, i);
@@ -515,7 +489,7 @@ __device__ __forceinline__ void wino2_body(const Wino2Args& a, float* __restrict
       cur += t.rows;
       const bool more = ti + 1 < ntiles;
       Tile nt = t;
-      if (more) nt = tile_of(a.H, a.ctiles, cur, s_hi, s_lo, lead);
+      if (more) nt = tile_of(a.H, a.ctiles, cur, s_hi);
       const int nbuf = (ti + 1) & 1;
 #pragma unroll
       for (int s = 0; s < kW2Stages; ++s, ++gs) {
@@ -714,7 +688,7 @@ __device__ __forceinline__ void wino2_body(const Wino2Args& a, float* __restrict
 #endif
   };
   for (int ti = 0; ti < ntiles; ++ti) {
-    const Tile t = tile_of(a.H, a.ctiles, cur, s_hi, s_lo, lead);
+    const Tile t = tile_of(a.H, a.ctiles, cur, s_hi);
     cur += t.rows;
     if (t.rows > 4) run_tile(std::integral_constant<int, 2>{}, t, ti & 1);
     else run_tile(std::integral_constant<int, 1>{}, t, ti & 1);
@@ -1389,7 +1363,7 @@ const float* conv_halo_zero_page(hipStream_t st) {
 }
 
 bool conv_halo_supported(const ConvGeom& g, const float* bias) {
-  static const int on = [] { const char* e = getenv("HIFIHR_CONV_HALO"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("HIFIHR_CONV_HALO", 1);
   return on && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.IC == 64 && g.OC == 64 && g.batch <= 1 &&
          !((g.relu || bias != nullptr) && g.dgrad) && g.IH == g.OH && g.IW == g.OW && g.OW >= kTW &&
          (long)g.N * g.OH * g.OW * 64 < (1L << 31);
@@ -1423,10 +1397,7 @@ static float* halo_wgrad_scratch(hipStream_t st, size_t bytes) {
   return d.buf[d.used++];
 }
 
-bool conv_stem_wgrad_supported(const ConvGeom& g) {
-  static const int on = [] { const char* e = getenv("HIFIHR_CONV_STEM_WGRAD"); return e ? atoi(e) : 1; }();
-  return on && conv_stem_supported(g, nullptr);
-}
+bool conv_stem_wgrad_supported(const ConvGeom& g) { return conv_stem_supported(g, nullptr); }
 
 size_t conv_stem_wgrad_slab_bytes() { return (size_t)device_cus() * 64 * 196 * sizeof(float); }
 
@@ -1450,7 +1421,7 @@ hipError_t launch_conv_stem_wgrad(const ConvGeom& g, const float* x, const float
 }
 
 bool conv_halo_wgrad_supported(const ConvGeom& g) {
-  static const int on = [] { const char* e = getenv("HIFIHR_CONV_HALO_WGRAD"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("HIFIHR_CONV_HALO_WGRAD", 1);
   return on && conv_halo_supported(g, nullptr) && !g.dgrad && g.OW % kTW == 0;      // (the dy tiles of the weight gradient are not masked)
 }
 
@@ -1476,7 +1447,7 @@ hipError_t launch_conv_halo_wgrad(const ConvGeom& g, const float* x, const float
 }
 
 bool conv_stem_supported(const ConvGeom& g, const float* bias) {
-  static const int on = [] { const char* e = getenv("HIFIHR_CONV_STEM"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("HIFIHR_CONV_STEM", 1);
   return on && !g.dgrad && g.R == 7 && g.S == 7 && g.stride == 2 && g.pad == 3 && g.IC == 4 && g.OC == 64 && g.batch <= 1 && !g.relu &&
          bias == nullptr && g.OW % kTW == 0 && (long)g.N * g.OH * g.OW * 64 < (1L << 31);
 }
@@ -1516,7 +1487,7 @@ hipError_t launch_conv_halo(const ConvGeom& g, const float* src, const float* wg
 // conv_wino2_kernel: the 64 -> 64 stride-1 3x3 layers with even H and W (ResNet layer 1 at 56 x 56, VGG19 conv1_2 at 224 x 224 and, with a ragged
 // last column tile, at 512 x 512 = 36 x 14 + 8)
 bool conv_wino2_supported(int N, int H, int W, int C, int K) {
-  static const int on = [] { const char* e = getenv("HIFIHR_CONV_WINO2"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("HIFIHR_CONV_WINO2", 1);
   return on && C == 64 && K == 64 && N > 0 && H >= 2 && H % 2 == 0 && W >= kTW && W % 2 == 0 && (long)N * H * W * 64 < (1L << 31);
 }
 
@@ -1548,9 +1519,9 @@ hipError_t launch_conv_wino2(const float* src, const float* U, const float* bias
 // Data gradient + weight gradient of one 64 -> 64 3x3 stride-1 layer in ONE launch (conv_c64_bwd_pair_kernel), then the slab reduction.
 //   dx = conv(dy, U_bwd) [+ res]      (launch_conv_wino2's arguments: U_bwd = the Winograd-domain filters of the transposed convolution)
 //   dw += sum_p dy[p] x[p + tap]      (launch_conv_halo_wgrad's)
-// The workgroups are split in proportion to the two kernels' measured times at the config batch (HIFIHR_C64_PAIR_DGRAD_PCT, default 44).
+// The workgroups are split in proportion to the two kernels' measured times at the config batch: 44 % to the data gradient.
 bool conv_c64_bwd_pair_supported(int N, int H, int W) {
-  static const int on = [] { const char* e = getenv("HIFIHR_C64_PAIR"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("HIFIHR_C64_PAIR", 1);
   ConvGeom g{};
   g.N = N; g.IH = H; g.IW = W; g.IC = 64; g.OC = 64; g.R = 3; g.S = 3; g.stride = 1; g.pad = 1; g.OH = H; g.OW = W; g.dgrad = 0; g.batch = 1;
   return on && conv_wino2_supported(N, H, W, 64, 64) && conv_halo_wgrad_supported(g) && device_cus() >= 2;
@@ -1575,9 +1546,8 @@ hipError_t launch_conv_c64_bwd_pair(const float* dy, const float* U_bwd, const f
   if (!conv_c64_bwd_pair_supported(N, H, W)) return hipErrorInvalidValue;
   const float* zeros = conv_halo_zero_page(st);
   if (zeros == nullptr) return hipErrorNotReady;
-  static const int pct = [] { const char* e = getenv("HIFIHR_C64_PAIR_DGRAD_PCT"); int v = e ? atoi(e) : 44; return v < 5 ? 5 : (v > 95 ? 95 : v); }();
   const int cus = device_cus();
-  int ga = (cus * pct + 50) / 100;
+  int ga = (cus * 44 + 50) / 100;
   if (ga < 1) ga = 1;
   if (ga > cus - 1) ga = cus - 1;
   int gb = cus - ga;

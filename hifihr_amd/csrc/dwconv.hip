@@ -114,8 +114,7 @@ __global__ __launch_bounds__(256) void dwconv_fwd_kernel(DwGeom g, const float* 
   if (cok) {
     for (long pb = (long)blockIdx.x * 16 + pl; pb < nb; pb += (long)gridDim.x * 16) {
       int owb, oh, n;
-      if (g.vorder) { oh = (int)(pb % g.OH); const long q = pb / g.OH; owb = (int)(q % OWB); n = (int)(q / OWB); }
-      else { owb = (int)(pb % OWB); const long q = pb / OWB; oh = (int)(q % g.OH); n = (int)(q / g.OH); }
+      owb = (int)(pb % OWB); const long q = pb / OWB; oh = (int)(q % g.OH); n = (int)(q / g.OH);
       const int ow0 = owb * kPW;
       float4 acc[kPW];
 #pragma unroll
@@ -214,8 +213,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_data_kernel(DwGeom g, const fl
   const bool odd = ((g.pl - (K - 1)) & 1) != 0;      // parity of base (iw0 is a multiple of 4); uniform
   for (long pb = (long)blockIdx.x * 16 + pl; pb < nb; pb += (long)gridDim.x * 16) {
     int iwb, ih, n;
-    if (g.vorder) { ih = (int)(pb % g.H); const long q = pb / g.H; iwb = (int)(q % WB); n = (int)(q / WB); }
-    else { iwb = (int)(pb % WB); const long q = pb / WB; ih = (int)(q % g.H); n = (int)(q / g.H); }
+    iwb = (int)(pb % WB); const long q = pb / WB; ih = (int)(q % g.H); n = (int)(q / g.H);
     if (S == 1 || !odd) dgrad_block<K, S, 0>(g, dy, wl, cl, n, ih, iwb * kPW, c, dx);
     else dgrad_block<K, S, 1>(g, dy, wl, cl, n, ih, iwb * kPW, c, dx);
   }
@@ -240,8 +238,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_weight_kernel(DwGeom g, const 
   if (cok) {
     for (long pb = (long)blockIdx.x * 16 + pl; pb < nb; pb += (long)gridDim.x * 16) {
       int owb, oh, n;
-      if (g.vorder) { oh = (int)(pb % g.OH); const long q = pb / g.OH; owb = (int)(q % OWB); n = (int)(q / OWB); }
-      else { owb = (int)(pb % OWB); const long q = pb / OWB; oh = (int)(q % g.OH); n = (int)(q / g.OH); }
+      owb = (int)(pb % OWB); const long q = pb / OWB; oh = (int)(q % g.OH); n = (int)(q / g.OH);
       const int ow0 = owb * kPW;
       float4 d[kPW];
       {
@@ -292,10 +289,6 @@ __global__ __launch_bounds__(256) void dwconv_bwd_weight_kernel(DwGeom g, const 
   }
 }
 
-static int dw_vorder() {
-  static const int v = [] { const char* e = getenv("HIFIHR_DW_VORDER"); return e ? atoi(e) : 0; }();
-  return v;
-}
 static unsigned dw_grid_x(long nb, long cap) {
   long b = (nb + 15) / 16;
   if (b > cap) b = cap;
@@ -320,37 +313,27 @@ static unsigned dw_grid_x(long nb, long cap) {
     else return hipErrorInvalidValue;                                                                                 \
   } while (0)
 
-hipError_t launch_dwconv_fwd(const DwGeom& g_in, const float* x, const float* w, float* y, float* stats, hipStream_t st, const float* pre_mean,
+hipError_t launch_dwconv_fwd(const DwGeom& g, const float* x, const float* w, float* y, float* stats, hipStream_t st, const float* pre_mean,
                              const float* pre_invstd, const float* pre_gamma, const float* pre_beta) {
-  DwGeom g = g_in;
-  g.vorder = dw_vorder();
   const long nb = (long)g.N * g.OH * ((g.OW + kPW - 1) / kPW);
   // with statistics every workgroup ends with 128 float atomics: bound (workgroups x channels) like bn.hip does
-  static const long cap_stats = [] { const char* e = getenv("HIFIHR_DW_FWD_CAP"); return e && atol(e) > 0 ? atol(e) : 256L; }();
-  static const long cap_plain = [] { const char* e = getenv("HIFIHR_DW_CAP"); return e && atol(e) > 0 ? atol(e) : 2048L; }();
-  const dim3 grid(dw_grid_x(nb, stats != nullptr ? cap_stats : cap_plain), (g.C + 63) / 64);
+  const dim3 grid(dw_grid_x(nb, stats != nullptr ? 256L : 2048L), (g.C + 63) / 64);
   const DwPre pre{pre_mean, pre_invstd, pre_gamma, pre_beta};
   if (pre_mean != nullptr) { HIFIHR_DW_DISPATCH_PRE(dwconv_fwd_kernel, true, grid, g, x, w, y, stats, pre); }
   else { HIFIHR_DW_DISPATCH_PRE(dwconv_fwd_kernel, false, grid, g, x, w, y, stats, pre); }
   return hipGetLastError();
 }
-hipError_t launch_dwconv_bwd_data(const DwGeom& g_in, const float* dy, const float* w, float* dx, hipStream_t st) {
-  DwGeom g = g_in;
-  g.vorder = dw_vorder();
+hipError_t launch_dwconv_bwd_data(const DwGeom& g, const float* dy, const float* w, float* dx, hipStream_t st) {
   const long nb = (long)g.N * g.H * ((g.W + kPW - 1) / kPW);
-  static const long cap_plain = [] { const char* e = getenv("HIFIHR_DW_CAP"); return e && atol(e) > 0 ? atol(e) : 2048L; }();
-  const dim3 grid(dw_grid_x(nb, cap_plain), (g.C + 63) / 64);
+  const dim3 grid(dw_grid_x(nb, 2048L), (g.C + 63) / 64);
   HIFIHR_DW_DISPATCH(dwconv_bwd_data_kernel, grid, g, dy, w, dx);
   return hipGetLastError();
 }
-hipError_t launch_dwconv_bwd_weight(const DwGeom& g_in, const float* x, const float* dy, float* dw, hipStream_t st, const float* pre_mean,
+hipError_t launch_dwconv_bwd_weight(const DwGeom& g, const float* x, const float* dy, float* dw, hipStream_t st, const float* pre_mean,
                                     const float* pre_invstd, const float* pre_gamma, const float* pre_beta) {
-  DwGeom g = g_in;
-  g.vorder = dw_vorder();
   const long nb = (long)g.N * g.OH * ((g.OW + kPW - 1) / kPW);
   // every workgroup ends with k*k x 64 atomics: give each pixel lane ~8 steps before that, between 8 and 128 workgroups per block
   long gx = nb / (16 * 8);
-  if (const char* e = getenv("HIFIHR_DW_WGRAD_STEPS")) gx = nb / (16 * (atoi(e) > 0 ? atoi(e) : 8));
   if (gx < 8) gx = 8;
   if (gx > 128) gx = 128;
   const dim3 grid((unsigned)gx, (g.C + 63) / 64);

@@ -1541,10 +1541,6 @@ __global__ __launch_bounds__(512) void bgemm_nt_tn_pair_kernel(BgemmArgs a, long
 // workspace and slab-count queries and the pair launch all read the plan.
 // ------------------------------------------------------------------------------------------------
 constexpr int kUnset = -(1 << 30);
-static int env_int(const char* name, int unset) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : unset;
-}
 // HIFIHR_GEMM_CUS (tests: the emulator reports 4 compute units, and the XCD-coherent TN schedule needs a multiple of 8 workgroups)
 static int gemm_cus() {
   const int v = env_int("HIFIHR_GEMM_CUS", 0);
@@ -1552,12 +1548,10 @@ static int gemm_cus() {
 }
 struct GemmEnv {
   // read once per process, all of them at the first call of gemm_env() (a switch set after a process's first GEMM is not seen, even where
-  // the feature it governs has not run yet): HIFIHR_GEMM_ROWS=0 (NT products on the older kernels), _RAGGED (0: no ragged N / K on the row-share kernel, 2: every
-  // shape it can take), _TN_ROWS=0 (the per-tile TN kernels), _TN_SPLIT=0 (no T-split), _TN_COHERENT=0 (contiguous shares), _TN_SKIP=0 (walk
-  // the zero rows behind a tile mosaic), _PAIR=0 (two launches), _PAIR_NT_WEIGHT (percent), _PAIR_MAX_GFLOP, HIFIHR_CONV_ROWS (2: every
+  // the feature it governs has not run yet): HIFIHR_GEMM_ROWS=0 (NT products on the older kernels), _TN_ROWS=0 (the per-tile TN kernels), _TN_SPLIT=0 (no T-split), _TN_COHERENT=0 (contiguous shares), _TN_SKIP=0 (walk
+  // the zero rows behind a tile mosaic), _PAIR=0 (two launches), HIFIHR_CONV_ROWS (2: every
   // shape), HIFIHR_CONV_ROWS_PAIR=0 (two launches)
-  int rows, ragged, tn_rows, tn_split, tn_coherent, tn_skip, pair, pair_nt_weight, conv_rows, conv_rows_pair;
-  double pair_max_gflop;
+  int rows, tn_rows, tn_split, tn_coherent, tn_skip, pair, conv_rows, conv_rows_pair;
   // re-read on every call (the tuning scripts and the tests change them inside one process): HIFIHR_GEMM_CUS, _WS (loader waves of the
   // wave-specialised kernels, 0: the 4-wave kernels), _SK=0 (never the persistent stream-K kernel), _NT_TILE / _TN_TILE (1000 bm + bn)
   // and _TN_PARTS (slabs of the per-tile TN kernels), whose presence alone switches the row-share kernels off (kUnset: not there)
@@ -1568,13 +1562,10 @@ struct GemmEnv {
 static GemmEnv gemm_env() {
   static const GemmEnv once = [] {
     GemmEnv e{};
-    e.rows = env_int("HIFIHR_GEMM_ROWS", 1); e.ragged = env_int("HIFIHR_GEMM_RAGGED", 1);
+    e.rows = env_int("HIFIHR_GEMM_ROWS", 1);
     e.tn_rows = env_int("HIFIHR_GEMM_TN_ROWS", 1); e.tn_split = env_int("HIFIHR_GEMM_TN_SPLIT", 1);
     e.tn_coherent = env_int("HIFIHR_GEMM_TN_COHERENT", 1); e.tn_skip = env_int("HIFIHR_GEMM_TN_SKIP", 1);
-    e.pair = env_int("HIFIHR_GEMM_PAIR", 1); e.pair_nt_weight = env_int("HIFIHR_GEMM_PAIR_NT_WEIGHT", 100);
-    if (e.pair_nt_weight <= 0) e.pair_nt_weight = 100;
-    const char* g = getenv("HIFIHR_GEMM_PAIR_MAX_GFLOP");
-    e.pair_max_gflop = (g && atof(g) > 0) ? atof(g) : 12.0;
+    e.pair = env_int("HIFIHR_GEMM_PAIR", 1);
     e.conv_rows = env_int("HIFIHR_CONV_ROWS", 1); e.conv_rows_pair = env_int("HIFIHR_CONV_ROWS_PAIR", 1);
     return e;
   }();
@@ -1638,13 +1629,12 @@ bool bgemm_nt_supported(int M, int N, int K) { return M > 0 && K >= 32 && K % 32
 bool bgemm_tn_supported(int M, int N, int T) { return T > 0 && M >= 64 && M % 64 == 0 && N >= 64 && N % 64 == 0; }
 
 // ragged N / K on the row-share kernel (EfficientNet's 1x1 convolutions).  Measured at batch 48 against conv_igemm_kernel
-// (tools/time_conv1x1.py with EFFNET=1, HIFIHR_GEMM_RAGGED=0 for the other side): a wash on most shapes -- these products are 20-50 us
+// (tools/time_conv1x1.py with EFFNET=1): a wash on most shapes -- these products are 20-50 us
 // launches on 2 352-9 408 rows, bounded by their size, and the implicit GEMM's 64-column tiles waste less of a 136- or 232-wide output --
 // a win where the 128-column tiles are >= 90 % full and the reduction is long (1392 -> 384: 45 -> 35 us, 232 -> 1392: 28.5 -> 25.7), a loss
 // below (32 -> 192: 45 -> 54, 576 -> 136: 30 -> 35).  Hence: tiles >= 90 % full and K >= 128.
 static bool nt_ragged(const GemmEnv& e, int M, int N, int K) {
-  if (!e.ragged || !e.rows_on() || M <= 0 || N < 96 || N % 4 != 0 || K < 16 || K % 4 != 0 || (N % 128 == 0 && K % 32 == 0)) return false;
-  if (e.ragged >= 2) return true;
+  if (!e.rows_on() || M <= 0 || N < 96 || N % 4 != 0 || K < 16 || K % 4 != 0 || (N % 128 == 0 && K % 32 == 0)) return false;
   return K >= 128 && 10L * N >= 9L * ((N + 127) / 128 * 128);
 }
 bool bgemm_nt_ragged_supported(int M, int N, int K) { return nt_ragged(gemm_env(), M, N, K); }
@@ -1942,8 +1932,8 @@ hipError_t launch_bgemm_tn(const float* A, const float* B, float* Cparts, int M,
 
 // The pair launch (bgemm_nt_tn_pair_kernel): C[p][m][n] = sum_k A[p][m][k] B[p][n][k] (plain row-share form: N % 128 == 0, K % 32 == 0) AND
 // C2parts = A2^T . B2 (row-share TN form, one slab or the T-split) in ONE launch.  hipErrorNotSupported: one of the two is not on its
-// row-share kernel (the caller then launches them separately).  The CUs are divided in proportion to the products' flops, the NT side
-// weighted by HIFIHR_GEMM_PAIR_NT_WEIGHT / 100 (default 100; measured on the ResNet-18 step: 70 -> 5.33 ms, 85 -> 5.21, 100 -> 5.17, 110 -> 5.22, 130 -> 5.50; separate launches 5.27).
+// row-share kernel (the caller then launches them separately).  The CUs are divided in proportion to the products' flops (weighting the
+// NT side, measured on the ResNet-18 step: x0.70 -> 5.33 ms, x0.85 -> 5.21, x1.00 -> 5.17, x1.10 -> 5.22, x1.30 -> 5.50; separate launches 5.27: unweighted).
 static bool pair_plans(const GemmEnv& e, int M, int M_alloc, int N, int K, int batch, int M2, int N2, int T2, int batch2, int parts2, NtPlan* nt) {
   *nt = plan_nt(e, M, M_alloc, N, K, batch, false);
   if (!e.pair || !nt->ok || nt->kernel != NtKernel::rows || !nt_fits32(*nt)) return false;
@@ -1952,7 +1942,7 @@ static bool pair_plans(const GemmEnv& e, int M, int M_alloc, int N, int K, int b
   if (tn.kernel != TnKernel::rows || tn.parts != parts2) return false;
   // Long products gain nothing from sharing a launch (their ends are a small part of them): VGG19's layers at 112 x 112 / 56 x 56 (22-44
   // GFLOP each) measured 33.71 ms/step apart against 33.75 paired (config 3); the ResNet layers (1.9-8.5 GFLOP) 5.25 -> 5.16 ms/step.
-  return 2.0 * batch * (double)M * N * K <= e.pair_max_gflop * 1e9;
+  return 2.0 * batch * (double)M * N * K <= 12.0 * 1e9;
 }
 bool bgemm_nt_tn_pair_supported(int M, int M_alloc, int N, int K, int batch, int M2, int N2, int T2, int batch2, int parts2) {
   NtPlan nt;
@@ -1966,7 +1956,7 @@ hipError_t launch_bgemm_nt_tn_pair(const float* A, const float* B, float* C, int
   if (!pair_plans(e, M, M_alloc, N, K, batch, M2, N2, T2, batch2, parts2, &nt)) return hipErrorNotSupported;
   if (T2_valid < 0 || T2_valid > T2) return hipErrorInvalidValue;
   const int T2w = (e.tn_skip && T2_valid > 0 && T2_valid < T2) ? (T2_valid + 3) / 4 * 4 : T2;      // rows whose k-steps run (the split of the CUs follows the work)
-  const double fa = 2.0 * batch * (double)M * N * K * (e.pair_nt_weight / 100.0), fb = 2.0 * batch2 * (double)M2 * N2 * T2w;
+  const double fa = 2.0 * batch * (double)M * N * K, fb = 2.0 * batch2 * (double)M2 * N2 * T2w;
   int ga = (int)(e.cus * fa / (fa + fb) + 0.5);
   if (ga < 8) ga = 8;
   if (ga > e.cus - 8) ga = e.cus - 8;

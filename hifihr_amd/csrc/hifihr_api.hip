@@ -588,7 +588,7 @@ int hifihr_conv2d_bwd_data_pre_plus1x1_supported(int N, int H, int W, int C, int
   const hifihr::ConvGeom f = conv_geom(N, H, W, C, K, R, S, stride, pad);
   if (f.OH != (H - 1) / stride + 1 || f.OW != (W - 1) / stride + 1) return 0;
   if ((long)N * f.OH * f.OW * K >= (1L << 30) || (long)C * R * S * K >= (1L << 30)) return 0;
-  static const int on = [] { const char* e = getenv("HIFIHR_DGRAD_PLUS1X1"); return e ? atoi(e) : 1; }();
+  static const int on = hifihr::env_int("HIFIHR_DGRAD_PLUS1X1", 1);
   return on;
 }
 
@@ -1215,12 +1215,6 @@ static hifihr::ConvGeom wino_gemm_geom(long T, int C, int K) {
   return g;
 }
 
-// HIFIHR_BGEMM=0 keeps the Winograd products on round 1's gather kernels (conv.hip); tuning / A-B runs only
-static bool use_bgemm() {
-  const char* e = getenv("HIFIHR_BGEMM");
-  return e == nullptr || atoi(e) != 0;
-}
-
 // one rule for every entry: the output-tile edge is 2 (F(2x2, 3x3)) or 4 (F(4x4, 3x3)); anything else is refused, the queries answer 0
 static bool wino_m_ok(int m) { return m == 2 || m == 4; }
 
@@ -1249,8 +1243,8 @@ static int wino_tn_parts(const WinoPlan& p, int C, int K) { return wino_tn_ok(p,
 // multiplications than direct) where the batched GEMMs of csrc/gemm.hip take the shape in both directions, else 2 = F(2x2, 3x3).
 // HIFIHR_WINO_M=2 keeps every layer on F(2x2, 3x3).
 static int wino_m(int N, int H, int W, int C, int K) {
-  static const int pref = [] { const char* e = getenv("HIFIHR_WINO_M"); return e ? atoi(e) : 4; }();
-  if (pref != 4 || !use_bgemm() || H < 4 || W < 4) return 2;
+  static const int pref = hifihr::env_int("HIFIHR_WINO_M", 4);
+  if (pref != 4 || H < 4 || W < 4) return 2;
   const WinoPlan p = wino_plan(N, H, W, 4);
   // forward (V U^T: rows T, N = K, reduction C), backward-data (roles of C and K swapped), backward-weight (slabs of Y'^T V)
   return (wino_nt_ok(p, K, C) && wino_nt_ok(p, C, K) && wino_tn_ok(p, C, K)) ? 4 : 2;
@@ -1267,13 +1261,13 @@ long hifihr_wino_tiles_computed(int N, int H, int W, int m) { return wino_plan(N
 size_t hifihr_wino_gemm_workspace_bytes(int N, int H, int W, int C, int K, int m) {
   const WinoPlan p = wino_plan(N, H, W, m);
   if (!p.ok || C <= 0 || K <= 0) return 0;
-  if (m == 4 || (use_bgemm() && wino_nt_ok(p, K, C)))
+  if (m == 4 || wino_nt_ok(p, K, C))
     return hifihr::bgemm_nt_workspace_bytes((int)p.T, K, C, p.P);       // the persistent (balanced) kernel's slabs + flags, or 0
   return hifihr::conv_sk_workspace_bytes(wino_gemm_geom(p.T, C, K));
 }
 
 int hifihr_wino_wgrad_parts(int N, int H, int W, int C, int K, int m) {
-  return use_bgemm() ? wino_tn_parts(wino_plan(N, H, W, m), C, K) : 0;
+  return wino_tn_parts(wino_plan(N, H, W, m), C, K);
 }
 
 int hifihr_wino_weight_transform(const float* w, float* U, int K, int C, int flip, int m, void* stream) {
@@ -1316,7 +1310,7 @@ int hifihr_wino_gemm(const float* V, const float* U, float* M, int N, int H, int
   if (m == 4 && !(args && nt)) return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: bad argument (F(4x4, 3x3) needs C % 32 == 0, K % 64 == 0)");
   if (m == 2 && !(args && C >= 32 && C % 32 == 0 && K >= 4 && K % 4 == 0))
     return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: bad argument (C % 32 == 0, K % 4 == 0)");
-  if (m == 4 || (use_bgemm() && nt)) {
+  if (m == 4 || nt) {
     if (!hifihr::bgemm_nt_fits32(p.T, K, C)) return fail(HIFIHR_EINVAL, "hifihr_wino_gemm: T * C and K * C must stay below 2^31 elements");
     HIP_TRY(hifihr::launch_bgemm_nt(V, U, M, (int)p.Tr, K, C, p.P, ws, ws_bytes, (hipStream_t)stream, nullptr, (int)p.T));
     return HIFIHR_OK;

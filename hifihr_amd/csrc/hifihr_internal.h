@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
 #include <stdint.h>
 
 #include "render_math.h"
@@ -19,6 +20,13 @@ inline int device_cus() {
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
   }
   return cus > 0 ? cus : 256;
+}
+
+// The one reader of the library's runtime switches (docs/SWITCHES.md lists them all): the value of the environment variable, `unset` without it.
+// A call site that wants the value cached at first use keeps it in a function-local static; a bare call re-reads it every time.
+static inline int env_int(const char* name, int unset) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : unset;
 }
 
 constexpr int kNVP = 800;   // padded vertex count of the SoA MANO tables (rows are 16-byte aligned)
@@ -286,9 +294,9 @@ hipError_t launch_ssim_finish(const float* partial, int count, float scale, floa
 // depthwise convolution geometry: x[N][H][W][C] -> y[N][OH][OW][C], k x k taps, padding top/left = pt/pl
 struct DwGeom {
   int N, H, W, C, OH, OW, K, stride, pt, pl;
-  int vorder = 0;      // 1 (HIFIHR_DW_VORDER=1): pixel blocks numbered row-fastest -- the 16 pixel lanes of a workgroup are 16 consecutive ROWS of one
-                       // 4-pixel column block, whose windows share K - 1 of K input rows in L1.  Measured per EfficientNet-b3 step (tools/time_dwconv.py):
-                       // forward 940 -> 913 us, backward-data 750 -> 732, backward-weight 1 306 -> 1 506; single shapes +-25 % either way: off
+  // (pixel blocks are numbered column-fastest.  Row-fastest -- the 16 pixel lanes of a workgroup on 16 consecutive ROWS of one 4-pixel column
+  // block, whose windows share K - 1 of K input rows in L1 -- measured per EfficientNet-b3 step (tools/time_dwconv.py): forward 940 -> 913 us,
+  // backward-data 750 -> 732, backward-weight 1 306 -> 1 506; single shapes +-25 % either way: not kept)
 };
 // pre_* (all four or none): x is the raw output of the preceding convolution; swish(batch_norm(x)) is applied as it is loaded
 hipError_t launch_dwconv_fwd(const DwGeom& g, const float* x, const float* w, float* y, float* stats, hipStream_t st,

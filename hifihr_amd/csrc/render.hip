@@ -121,8 +121,7 @@ static inline F3Ws f3_carve(const RenderDev& r, int B, void* ws) {
   // parts hold -- cutting a list finer than it must be multiplies the exact sample tests.  On the MANO mesh (41 faces per covered tile on
   // average, a few tiles of 300-600) parts of 128 shorten the launch's tail; on a dense skin (11 976 faces: hundreds per tile everywhere)
   // they made the launch 18 % longer than one workgroup per tile (838 vs 710 us at B = 48): the target grows with the mesh.
-  static const int forced = [] { const char* e = getenv("HIFIHR_RENDER_PART"); return e ? atoi(e) : 0; }();
-  w.part_faces = forced > 0 ? forced : (r.F <= 2048 ? kF3Cap : (r.F <= 8192 ? 2 * kF3Cap : 4 * kF3Cap));
+  w.part_faces = r.F <= 2048 ? kF3Cap : (r.F <= 8192 ? 2 * kF3Cap : 4 * kF3Cap);
   w.cap = (int)f3_queue_cap(r, B);
   const size_t sw2 = (size_t)(8 * r.aa) * (8 * r.aa);
   w.gz = reinterpret_cast<unsigned long long*>(p); p += (size_t)B * kF3SplitSlots * sw2 * 8;
@@ -316,11 +315,7 @@ __shared__ unsigned long long s_r2_acc[8];          // thread 0's phase sums of 
 #define R2_T0
 #define R2_STAMP(i)
 #endif
-#if defined(HIFIHR_R2_NOSTORE)
-#define R2_STORE(...) if (r.H < 0) { __VA_ARGS__; }
-#else
 #define R2_STORE(...) __VA_ARGS__
-#endif
 constexpr int kF2Threads = 256;
 constexpr int kF2Cap = 256;          // faces per pass
 constexpr int kQCap = 1024;          // survivor queue entries: a round appends at most 256
@@ -681,28 +676,18 @@ __global__ __launch_bounds__(kF2Threads) void render_fwd2_kernel(RenderDev r, co
                                                                  const float* __restrict__ light_color, const float* __restrict__ light_dir,
                                                                  float* __restrict__ rgba, int* __restrict__ face_id,
                                                                  const int* __restrict__ tile_cnt, const int* __restrict__ tile_list,
-                                                                 TexUvDev tuv, int nB, int xcd_map) {
+                                                                 TexUvDev tuv) {
   HIP_DYNAMIC_SHARED(float4, smem_raw)
   Fwd2Lds<AA, TILE>& L = *reinterpret_cast<Fwd2Lds<AA, TILE>*>(smem_raw);
   constexpr int SW = TILE * AA;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int H = r.H, S = H * AA;
   const int tiles = (H + TILE - 1) / TILE;
-  // 1-D grid, XCD-aware: workgroups are dealt round-robin over the 8 XCDs (id % 8), so image b = 8 g + (id % 8): all tiles of an image
-  // run on ONE XCD and its face records / tile lists (0.3 MB + 0.1 MB per image) stay in that XCD's 4 MB L2 -- with blockIdx.z = image
-  // every XCD touched every image (9.4 MB of records at B = 32) and the gathers were served from the Infinity Cache under load
-  // (staging 12.5 us, shading 21 us per tile: tools/render_stamp2.py)
-  int b, tix, tiy;
-  if (xcd_map) {
-    const int bid = blockIdx.x, xcd = bid & 7, jj = bid >> 3;
-    b = (jj / (tiles * tiles)) * 8 + xcd;
-    if (b >= nB) return;
-    tix = (jj % (tiles * tiles)) % tiles; tiy = (jj % (tiles * tiles)) / tiles;
-  } else {
-    const int bid = blockIdx.x;
-    b = bid / (tiles * tiles);
-    tix = (bid % (tiles * tiles)) % tiles; tiy = (bid % (tiles * tiles)) / tiles;
-  }
+  // 1-D grid, image-major: the tiles of an image are consecutive workgroups.  (Dealing the images to the 8 XCDs by id % 8, so that an
+  // image's face records and tile lists stay in one XCD's L2, was tried and not kept: docs/HISTORY.md, retired switches.)
+  const int bid = blockIdx.x;
+  const int b = bid / (tiles * tiles);
+  const int tix = (bid % (tiles * tiles)) % tiles, tiy = (bid % (tiles * tiles)) / tiles;
   const int ox = tix * TILE, oy = tiy * TILE;
   const int cols = min(TILE, H - ox), rows = min(TILE, H - oy);
   const size_t tile = ((size_t)b * tiles + tiy) * tiles + tix;
@@ -844,7 +829,7 @@ __device__ __forceinline__ void f3_fill_strip(const RenderDev& r, const int* __r
 
 // CAP: faces per rasterisation pass.  128 for hand-sized meshes (41 faces per covered tile on the MANO mesh: one pass nearly everywhere, 36 KB of
 // LDS, four workgroups per CU); 256 for dense skins (hundreds of faces per tile everywhere: the per-pass chain of barriers, scans and queue
-// rounds is what a tile costs there, and half the passes beat a fourth workgroup per CU -- HIFIHR_RENDER_CAP forces either).
+// rounds is what a tile costs there, and half the passes beat a fourth workgroup per CU).
 template <int AA, bool UV, int CAP>
 __global__ __launch_bounds__(kF2Threads) void render_fwd3_kernel(RenderDev r, const float4* __restrict__ frec,
                                                                  const float* __restrict__ light_color, const float* __restrict__ light_dir,
@@ -1022,24 +1007,20 @@ hipError_t launch_render_fwd(const RenderDev& r, const float* verts, const float
   const int te = render_tile();
   carve(r, B, ws, &vndc, &vpos, &vnrm, &vcol, &gvrec, &tile_cnt, &tile_list, te);
   const int tiles = (r.H + te - 1) / te;
-  static const int use3 = [] { const char* e = getenv("HIFIHR_RENDER_FWD3"); return e ? atoi(e) : 1; }();     // 0: the second form (A/B)
-  const bool f3 = use3 != 0 && f3_supported(r, B);
+  const bool f3 = f3_supported(r, B);      // the third form wherever its item code fits; else the second
   const F3Ws w3 = f3_carve(r, B, ws);
   hipLaunchKernelGGL(render_vertex_kernel, dim3((r.V + 255) / 256, B), dim3(256), 0, st, r, verts, vcolors, vcol_bstride, cam,
                      vndc, vpos, vnrm, vcol, tile_cnt, tiles * tiles, f3 ? w3.ctl : nullptr, gvrec, light_records(r, B, ws));
   render_ws_mark_clean(ws, true);
   const dim3 bgrid((r.F + kBinFaces - 1) / kBinFaces, B);
-  static const int xm = [] { const char* e = getenv("HIFIHR_RENDER_XCD"); return e ? atoi(e) : 0; }();      // A/B: images pinned to XCDs
-  const dim3 grid1((unsigned)((xm ? 8 * ((B + 7) / 8) : B) * tiles * tiles));
+  const dim3 grid1((unsigned)(B * tiles * tiles));
   float4* frec = face_records(r, B, ws);
   const TexUvDev td = uv != nullptr ? TexUvDev{uv->faces_uvs, uv->verts_uvs, uv->maps, nullptr, uv->TH, uv->TW} : TexUvDev{};
   if (f3) {
     const int cus = device_cus();
-    static const int per_cu = [] { const char* e = getenv("HIFIHR_RENDER_WGS"); const int v = e ? atoi(e) : 16; return v > 0 ? v : 16; }();
-    const dim3 grid3((unsigned)(cus * per_cu));
-    static const int cap_forced = [] { const char* e = getenv("HIFIHR_RENDER_CAP"); return e ? atoi(e) : 0; }();
-    const int cap3 = cap_forced == 128 || cap_forced == 256 ? cap_forced : (r.F > 2048 ? 256 : kF3Cap);
-#define HIFIHR_RENDER_FWD3(AA_)                                                                                                          \
+    const dim3 grid3((unsigned)(cus * 16));
+    const int cap3 = r.F > 2048 ? 256 : kF3Cap;
+#define HIFIHR_LAUNCH_FWD3(AA_)                                                                                                          \
     {                                                                                                                                   \
       hipLaunchKernelGGL((render_bin_kernel<AA_, 8>), bgrid, dim3(4 * kBinFaces), (size_t)2 * tiles * tiles * sizeof(int), st, r, vndc,   \
                          vpos, vnrm, vcol, frec, tile_cnt, tile_list, w3, 1);                                                           \
@@ -1057,12 +1038,12 @@ hipError_t launch_render_fwd(const RenderDev& r, const float* verts, const float
                            light_color, light_dir, rgba, face_id, tile_cnt, tile_list, td, B, w3);                                      \
     }
     switch (r.aa) {
-      case 1: HIFIHR_RENDER_FWD3(1) break;
-      case 2: HIFIHR_RENDER_FWD3(2) break;
-      case 3: HIFIHR_RENDER_FWD3(3) break;
+      case 1: HIFIHR_LAUNCH_FWD3(1) break;
+      case 2: HIFIHR_LAUNCH_FWD3(2) break;
+      case 3: HIFIHR_LAUNCH_FWD3(3) break;
       default: return hipErrorInvalidValue;
     }
-#undef HIFIHR_RENDER_FWD3
+#undef HIFIHR_LAUNCH_FWD3
     return hipGetLastError();
   }
 #define HIFIHR_RENDER_FWD2(AA_, T_)                                                                                                      \
@@ -1071,10 +1052,10 @@ hipError_t launch_render_fwd(const RenderDev& r, const float* verts, const float
                        vpos, vnrm, vcol, frec, tile_cnt, tile_list, w3, 0);                                                             \
     if (uv != nullptr)                                                                                                                  \
       hipLaunchKernelGGL((render_fwd2_kernel<AA_, T_, true>), grid1, dim3(kF2Threads), sizeof(Fwd2Lds<AA_, T_>), st, r, frec, light_color, \
-                         light_dir, rgba, face_id, tile_cnt, tile_list, td, B, xm);                                                     \
+                         light_dir, rgba, face_id, tile_cnt, tile_list, td);                                                     \
     else                                                                                                                                \
       hipLaunchKernelGGL((render_fwd2_kernel<AA_, T_, false>), grid1, dim3(kF2Threads), sizeof(Fwd2Lds<AA_, T_>), st, r, frec,           \
-                         light_color, light_dir, rgba, face_id, tile_cnt, tile_list, td, B, xm);                                        \
+                         light_color, light_dir, rgba, face_id, tile_cnt, tile_list, td);                                        \
   }
 #define HIFIHR_RENDER_FWD(AA_) if (te == 8) HIFIHR_RENDER_FWD2(AA_, 8) else HIFIHR_RENDER_FWD2(AA_, 16)
   switch (r.aa) {

@@ -285,11 +285,10 @@ __global__ __launch_bounds__(256) void render_bwd_kernel(RenderDev r, const floa
         for (int j = 0; j < AA; ++j) sample(i, j, fid_px[(size_t)i * S + j]);
     } else {                                                  // (vertex colours: 198 registers unrolled, 188 rolled -- two workgroups per CU either
                                                               //  way, and rolled measured 165 -> 176 us at B = 32)
-#if !defined(HIFIHR_RBWD_SCAN_ORDER)
       // Round 6: the pixel's samples are walked in FACE order (keys (face, sample index) through an odd-even transposition network in
       // registers): a pixel that an edge crosses reads A A B / A B B / B B B in scan order -- four runs, i.e. three in-loop flushes into the
       // tile's vertex table and three reloads of twelve face records, each executed under divergence -- and two runs when sorted.  Entry point
-      // at B = 32: 163 -> 145 us (timing-only builds without the in-loop flushes: 114).  -DHIFIHR_RBWD_SCAN_ORDER: the scan order (A/B builds).
+      // at B = 32: 163 -> 145 us (timing-only builds without the in-loop flushes: 114).
       constexpr int NS = AA * AA;
       unsigned key[NS];
 #pragma unroll
@@ -307,12 +306,6 @@ __global__ __launch_bounds__(256) void render_bwd_kernel(RenderDev r, const floa
         const int idx = (int)(key[t] & 15u);
         sample(idx / AA, idx - (idx / AA) * AA, fk == 0x0FFFFFFFu ? -1 : (int)fk);
       }
-#else
-#pragma unroll
-      for (int i = 0; i < AA; ++i)
-#pragma unroll
-        for (int j = 0; j < AA; ++j) sample(i, j, fid[i * AA + j]);
-#endif
     }
   }
   // The last run of every lane is flushed HERE, at a wave-uniform point -- and that is where the LDS atomics met 64 ways: the lanes of a

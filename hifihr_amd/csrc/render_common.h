@@ -118,7 +118,7 @@ void render_ws_mark_clean(void* ws, bool clean);
 bool render_ws_take_clean(void* ws);
 
 static inline int render_tile() {                // tile edge of the forward (8: see render_fwd2_kernel; HIFIHR_RENDER_TILE=16 for the A/B)
-  static const int v = [] { const char* e = getenv("HIFIHR_RENDER_TILE"); return (e && atoi(e) == 16) ? 16 : 8; }();
+  static const int v = env_int("HIFIHR_RENDER_TILE", 8) == 16 ? 16 : 8;
   return v;
 }
 static inline size_t list_part_bytes(const RenderDev& r, int B) {

@@ -228,8 +228,7 @@ int ssim_tile_edge() { return kST; }
 
 // vector staging: whole float4 groups inside or outside the image, planes 16-byte aligned (plane stride H * W floats with W % 4 == 0)
 static bool ssim_vec_ok(int W, const float* a, const float* b, const float* c) {
-  static const int on = [] { const char* e = getenv("HIFIHR_SSIM_VEC"); return e ? atoi(e) : 1; }();
-  return on && W % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+  return W % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
 }
 
 hipError_t launch_ssim_finish(const float* partial, int count, float scale, float offset, float* out, hipStream_t st) {

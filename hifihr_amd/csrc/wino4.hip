@@ -357,7 +357,7 @@ hipError_t launch_wino4_weight_transform(const float* w, float* U, int K, int C,
 
 // the tile geometry of a layer: every launcher of the F(4x4, 3x3) pipeline and the products' row count come through here
 TileGeo wino4_geo(int N, int H, int W) {
-  static const int on = [] { const char* e = getenv("HIFIHR_WINO_MOSAIC"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("HIFIHR_WINO_MOSAIC", 1);
   return make_tile_geo(N, H, W, on != 0);
 }
 long wino4_tiles(int N, int H, int W) { return (long)tile_count(wino4_geo(N, H, W)); }
@@ -421,7 +421,7 @@ hipError_t launch_wino4_dw_transform_multi(const WinoDwJob* jobs, int njobs, hip
 hipError_t launch_wino4_dw_transform_parts(const float* dU_parts, int parts, float* dw, int K, int C, hipStream_t st) {
   if (C % 4 != 0 || parts < 1) return hipErrorInvalidValue;
   const size_t total = (size_t)K * (C / 4);
-  static const int wide_on = [] { const char* e = getenv("HIFIHR_WINO_DW_WIDE"); return e ? atoi(e) : 1; }();
+  static const int wide_on = env_int("HIFIHR_WINO_DW_WIDE", 1);
   if (wide_on && total <= 8192)
     hipLaunchKernelGGL(wino4_dw_transform_parts_wide_kernel, dim3((unsigned)((total + 31) / 32)), dim3(192), 0, st, dU_parts, parts, dw, K, C);
   else

@@ -352,14 +352,8 @@ static unsigned wbn_grid(size_t total) {
   return (unsigned)b;
 }
 
-// one channel per thread instead of four while the four-channel form would not even give every SIMD two waves (HIFIHR_WINO_VEC=4 / 1
-// force a form: A/B)
-static bool wbn_scalar(size_t items_v4) {
-  static const int force = [] { const char* e = getenv("HIFIHR_WINO_VEC"); return e ? atoi(e) : 0; }();
-  if (force == 1) return true;
-  if (force == 4) return false;
-  return items_v4 < (size_t)256 * 2048;
-}
+// one channel per thread instead of four while the four-channel form would not even give every SIMD two waves
+static bool wbn_scalar(size_t items_v4) { return items_v4 < (size_t)256 * 2048; }
 
 bool wino4_bn_supported(int C) { return C >= 4 && C % 4 == 0 && C <= kWbnMaxC; }
 
@@ -369,14 +363,12 @@ hipError_t launch_wino4_bn_input_transform(const float* x, float* stats, const f
   if (!wino4_bn_supported(C) || ((res == nullptr) != (out == nullptr))) return hipErrorInvalidValue;
   const TileGeo geo = wino4_geo(N, H, W);
   const size_t total = tile_count(geo) * (C / 4);
-  static const int in_scalar = [] { const char* e = getenv("HIFIHR_WINO_IN_VEC"); return e ? atoi(e) : 0; }();   // 1: one channel per thread; 4: four (A/B)
-  const bool scalar = in_scalar == 1;      // (measured: no gain -- 18.3 / 13.6 / 19.6 us against 16.2 / 13.1 / 17.2 at four channels per thread)
-#define HIFIHR_WBN_IN2(R_, T_, M_, TOT_)                                                                                                       \
-  hipLaunchKernelGGL((wino4_bn_input_transform_kernel<R_, T_, M_>), dim3(wbn_grid(TOT_)), dim3(256), 0, st, x, stats, gamma, beta, res, out, V, \
+  // always four channels per thread (one per thread measured no gain: 18.3 / 13.6 / 19.6 us against 16.2 / 13.1 / 17.2)
+#define HIFIHR_WBN_IN2(R_, M_)                                                                                                                 \
+  hipLaunchKernelGGL((wino4_bn_input_transform_kernel<R_, V4, M_>), dim3(wbn_grid(total)), dim3(256), 0, st, x, stats, gamma, beta, res, out, V, \
                      geo, C, eps, momentum, save_mean, save_invstd, running_mean, running_var)
-#define HIFIHR_WBN_IN(R_, T_, TOT_) { if (geo.G) HIFIHR_WBN_IN2(R_, T_, true, TOT_); else HIFIHR_WBN_IN2(R_, T_, false, TOT_); }
-  if (res != nullptr) { if (scalar) HIFIHR_WBN_IN(true, float, total * 4) else HIFIHR_WBN_IN(true, V4, total) }
-  else { if (scalar) HIFIHR_WBN_IN(false, float, total * 4) else HIFIHR_WBN_IN(false, V4, total) }
+#define HIFIHR_WBN_IN(R_) { if (geo.G) HIFIHR_WBN_IN2(R_, true); else HIFIHR_WBN_IN2(R_, false); }
+  if (res != nullptr) HIFIHR_WBN_IN(true) else HIFIHR_WBN_IN(false)
 #undef HIFIHR_WBN_IN
 #undef HIFIHR_WBN_IN2
   return hipGetLastError();

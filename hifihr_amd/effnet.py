@@ -16,7 +16,6 @@ oracle/torch_modules.EfficientNetB3Ref (pinned by the reference's own network/ef
 from __future__ import annotations
 
 import math
-import os
 
 import torch
 import torch.nn as nn
@@ -66,13 +65,13 @@ def b3_block_table():
     return out
 
 
-# bn0 + swish inside the depthwise kernels' loads (ops._BNSwishDwConv; built and parity-tested in round 5) is OFF by default: MEASURED
+# bn0 + swish stay a launch of their own, the activated tensor materialised.  Applying them inside the depthwise kernels' loads (the
+# hifihr_dwconv_bnswish_* entries; built and parity-tested in round 5) MEASURED
 # slower (profiles/r05_time_dw_bnswish.txt, batch 48: forward 1 542 -> 1 623 us per step, backward-weight 1 033 -> 3 089 us; config 3
 # 34.45 -> 36.80 ms/step).  The streaming depthwise kernels load every input element 1.7-10 x (the window overlap) and each load then
 # pays a v_exp + v_rcp: they turn from L1-bound into VALU-bound, and the weight gradient -- which needs the ACTIVATED tensor again --
 # pays it a second time.  What would work is a depthwise kernel that stages an input tile in LDS (each element activated once) for
-# forward and weight gradient both; not built.  HIFIHR_EFFNET_FUSE_BN0=1 turns the fused path on.
-_FUSE_BN0 = os.environ.get("HIFIHR_EFFNET_FUSE_BN0", "0") != "0"
+# forward and weight gradient both; not built.
 
 
 class SqueezeExciteConv(nn.Conv2d):
@@ -158,32 +157,16 @@ class MBConvBlock(nn.Module):
     def forward(self, inputs, drop_connect_rate=None):
         x = inputs
         from . import ops
-        fused_expand = None
-        if self.expand != 1 and _FUSE_BN0 and self._bn0.training and x.is_cuda:
-            # (HIFIHR_EFFNET_FUSE_BN0=0: bn0 + swish as a launch of its own, the activated tensor materialised)
-            skip = self.stride == 1 and self.cin == self.cout
-            if skip and inputs.requires_grad and torch.is_grad_enabled() and os.environ.get("HIFIHR_EFFNET_FORK", "1") != "0":
-                e, st0, inputs = self._expand_conv(x, want_stats=True, fork=True)
-            else:
-                e, st0 = self._expand_conv(x, want_stats=True)
-            fused_expand = (e, st0)
-        elif self.expand != 1:
+        if self.expand != 1:
             # (the skip connection's gradient joins the expand convolution's backward-data launch -- which then runs on conv_igemm_kernel,
             #  the only epilogue that adds one, instead of the row-share GEMM: config 3 35.09 / 35.14 -> 35.05 / 35.06 ms/step and 19 launches
-            #  fewer; HIFIHR_EFFNET_FORK=0 leaves the sum to autograd)
+            #  fewer than leaving the sum to autograd)
             skip = self.stride == 1 and self.cin == self.cout
-            if skip and inputs.requires_grad and torch.is_grad_enabled() and os.environ.get("HIFIHR_EFFNET_FORK", "1") != "0":
+            if skip and inputs.requires_grad and torch.is_grad_enabled():
                 x, inputs = _conv_bn_swish(self._expand_conv, self._bn0, x, fork=True)
             else:
                 x = _conv_bn_swish(self._expand_conv, self._bn0, x)
-        if fused_expand is not None:
-            # expand convolution -> [bn0 + swish applied inside the depthwise kernel's loads] -> depthwise convolution (ops._BNSwishDwConv)
-            e, st0 = fused_expand
-            dwc = self._depthwise_conv
-            y, st = ops.bn_swish_dwconv(e, st0, self._bn0, dwc.weight, dwc.stride, dwc.pad4, want_stats=True)
-            x = ops.bn_act(y, st, self._bn1, None, "swish")
-        else:
-            x = _conv_bn_swish(self._depthwise_conv, self._bn1, x)         # statistics from the depthwise kernel's epilogue
+        x = _conv_bn_swish(self._depthwise_conv, self._bn1, x)             # statistics from the depthwise kernel's epilogue
         x = ops.squeeze_excite(x, self._se_reduce, self._se_expand)        # pool + 2 small linears + scale, fused
         x = _conv_bn_swish(self._project_conv, self._bn2, x, act=False)
         if self.stride == 1 and self.cin == self.cout:

@@ -112,7 +112,7 @@ class LossFunction:
         parts = getattr(self, "_total_parts", [])
         covered = [k for _, _, names in parts for k in names]
         if (parts and len(parts) <= 4 and sorted(covered) == sorted(losses) and all(p.is_cuda for p, _, _ in parts)
-                and all(loss_dic.get(k) is not None for k in losses) and os.environ.get("HIFIHR_LOSS_TOTAL", "1") != "0"):
+                and all(loss_dic.get(k) is not None for k in losses)):
             return ops.loss_total([(p, n) for p, n, _ in parts])
         terms = [loss_dic[k] for k in losses]
         return terms[0] if len(terms) == 1 else torch.stack(terms).sum()      # 2 launches instead of a chain of adds

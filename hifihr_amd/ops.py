@@ -462,7 +462,7 @@ class side_branch:
     on what the main stream does next overlaps with it -- forward AND backward, because autograd runs a node's backward on the stream of its
     forward; inside a captured step the two become parallel branches of the hipGraph.  Measured (round 5, B = 32): the light estimator
     beside the hand encoder / MANO chain 5.38 -> 5.32 ms/step.  One stream per (device, name), created once.
-    `enabled=False` (or HIFIHR_BRANCHES=0) makes the block run inline."""
+    `enabled=False` makes the block run inline."""
     _streams = {}
     _home = {}          # (device, name) -> the stream the branch last forked from (the step's own stream)
     _pending = set()    # branches entered since the last join_pending(): their BACKWARD may still be running on the side stream
@@ -525,7 +525,7 @@ class side_branch:
         side_branch._pending.clear()
 
 
-_BRANCHES = os.environ.get("HIFIHR_BRANCHES", "1") != "0"
+_BRANCHES = True       # (module attribute: the end-to-end test compares a step with the branches inline against the default)
 _STEM_REDUCE_Y = os.environ.get("HIFIHR_STEM_REDUCE_Y", "1") != "0"       # the stem's batch-norm backward reduction over the pooled grid
 _GEMM_PAIR = os.environ.get("HIFIHR_GEMM_PAIR", "1") != "0"
 # the same for the 64 -> 64 layers (ResNet layer 1): Winograd F(2x2) data gradient + pixel-reduction weight gradient in one launch
@@ -629,10 +629,10 @@ def _wino_ok(C, K, R, S, stride, pad, allowed=None):
     if not (R == 3 and S == 3 and stride == 1 and pad == 1 and C % 32 == 0 and K % 32 == 0):
         return False
     # both sides >= 128 channels -- or (round 4) 64 on one side and >= 128 on the other: VGG19's conv2_1 (64 -> 128 at 112 x 112, three
-    # launches of 858 us on the implicit GEMM per config-3 step; HIFIHR_WINO_MIXED=0 keeps it there).  64 -> 64 is conv_wino2_kernel's.
+    # launches of 858 us on the implicit GEMM per config-3 step).  64 -> 64 is conv_wino2_kernel's.
     if C >= 128 and K >= 128:
         return True
-    return min(C, K) >= 64 and max(C, K) >= 128 and os.environ.get("HIFIHR_WINO_MIXED", "1") != "0"
+    return min(C, K) >= 64 and max(C, K) >= 128
 
 
 def _wino2_fused_ok(lib, N, H, W, C, K, R, S, stride, pad, allowed=None, device=None):
@@ -837,7 +837,7 @@ class prepared_weights:
     exit (before the optimizer runs)."""
 
     def __init__(self, async_wgrad=False):
-        self.async_wgrad = bool(async_wgrad) and os.environ.get("HIFIHR_ASYNC_WGRAD", "1") != "0"
+        self.async_wgrad = bool(async_wgrad)
 
     def __enter__(self):
         # branches left over from a forward outside any scope (evaluation): joined now -- or, when this scope opens inside a capture, dropped
@@ -846,13 +846,12 @@ class prepared_weights:
             side_branch._pending.clear()
         else:
             side_branch.join_pending()
-        if os.environ.get("HIFIHR_WEIGHT_PREP", "1") != "0":
-            _WEIGHT_PREP.begin()
+        _WEIGHT_PREP.begin()
         _DEFER_DW.clear()
         _DEFER_DW.active = True
         # not inside a hipGraph capture: forked branches of a replayed graph ran SLOWER here (8.03 vs 7.74 ms/step) while the same
         # fork in the eager step gains (7.69 vs 7.83)
-        _ASYNC_WGRAD.active = self.async_wgrad and (not torch.cuda.is_current_stream_capturing() or os.environ.get("HIFIHR_ASYNC_WGRAD_GRAPH") == "1")
+        _ASYNC_WGRAD.active = self.async_wgrad and not torch.cuda.is_current_stream_capturing()
         return self
 
     def __exit__(self, *exc):
@@ -2094,7 +2093,7 @@ def _se_w2t(w2):
 
 class _SqueezeExcite(torch.autograd.Function):
     """Pooling -> the two layers in ONE launch (csrc/se.hip se_mlp_fwd_kernel) -> scaling: 3 launches forward, 4 backward, no fills (round
-    3: 5 + 7 with the layers on the head kernels; HIFIHR_SE_FUSED=0 keeps that form for the A/B)."""
+    3: 5 + 7 with the layers on the head kernels, the form that still takes the shapes se_mlp_supported refuses)."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2):
@@ -2104,7 +2103,7 @@ class _SqueezeExcite(torch.autograd.Function):
         B, C, H, W = x.shape
         HW, SQ = H * W, w1.shape[0]
         dev = x.device
-        fused = _SE_FUSED and lib.se_mlp_supported(C, SQ)
+        fused = lib.se_mlp_supported(C, SQ)
         ctx.fused = fused
         h1, z1, gate = torch.empty(B, SQ, device=dev), torch.empty(B, SQ, device=dev), torch.empty(B, C, device=dev)
         if fused:
@@ -2160,9 +2159,6 @@ class _SqueezeExcite(torch.autograd.Function):
             if r is None:
                 _grad_ready(p)
         return dx, rets[0], rets[1], rets[2], rets[3]
-
-
-_SE_FUSED = os.environ.get("HIFIHR_SE_FUSED", "1") != "0"
 
 
 class _DropConnectAdd(torch.autograd.Function):
@@ -2478,76 +2474,6 @@ class _DwConv(torch.autograd.Function):
             if dw is None:
                 _grad_ready(p)
         return dx, dw, None, None, None
-
-
-class _BNSwishDwConv(torch.autograd.Function):
-    """depthwise_conv(swish(bn(e))) of an MBConv block (reference network/efficientnet_pt/model.py:73-80) WITHOUT the activated tensor:
-    e = the expand convolution's raw output and `stats` its slot buffer.  Forward: hifihr_bn_finalize_fwd (one tiny launch: mean / invstd,
-    running statistics) + hifihr_dwconv2d_fwd_bnswish (batch-norm + swish applied as the rows are loaded).  Backward: the weight gradient
-    from e the same way; d a = dwconv_bwd_data(gy); then the ordinary fused batch-norm backward with act = swish on (d a, e), which
-    recomputes the activation's derivative from e.  Against `bn_act` + `dwconv2d`: one pass over the block's largest tensor less in
-    forward (read e + write a: 2.4 GB per EfficientNet-b3 step at batch 48) and that tensor is never allocated."""
-
-    @staticmethod
-    def forward(ctx, e, stats, gamma, beta, eps, momentum, running_mean, running_var, w, stride, pad4, want_stats):
-        require_cuda(e, stats, gamma, beta, w)
-        lib = get_lib()
-        e = e.contiguous(memory_format=_CL)
-        w = w.contiguous()
-        N, C, H, W = e.shape
-        K = w.shape[-1]
-        pl, pr, pt, pb = pad4
-        OH, OW = (H + pt + pb - K) // stride + 1, (W + pl + pr - K) // stride + 1
-        save_mean, save_invstd = torch.empty(C, device=e.device), torch.empty(C, device=e.device)
-        PROFILE.bracket("bn_fwd", lambda: lib.bn_finalize_fwd(stats, N * H * W, C, eps, momentum, save_mean, save_invstd, running_mean, running_var))
-        _ZERO_POOL.release(stats)                 # consumed and zeroed
-        y = torch.empty((N, C, OH, OW), device=e.device, dtype=torch.float32, memory_format=_CL)
-        ystats = _ZERO_POOL.acquire(lib.bn_stats_floats(C), e.device) if want_stats else None
-        geom = (N, H, W, C, OH, OW, K, stride, pt, pl)
-        PROFILE.bracket("dwconv_fwd", lambda: lib.dwconv2d_fwd_bnswish(e, save_mean, save_invstd, gamma, beta, w, y, *geom, stats=ystats))
-        ctx.geom, ctx.M, ctx.C = geom, N * H * W, C
-        ctx.save_for_backward(e, w, gamma, beta, save_mean, save_invstd)
-        ctx.w_param, ctx.gamma_param, ctx.beta_param = w, gamma, beta
-        ctx.set_materialize_grads(False)
-        if want_stats:
-            ctx.mark_non_differentiable(ystats)
-            return y, ystats
-        return y
-
-    @staticmethod
-    def backward(ctx, gy, _gstats=None):
-        if gy is None:
-            return (None,) * 12
-        e, w, gamma, beta, save_mean, save_invstd = ctx.saved_tensors
-        lib = get_lib()
-        gy = gy.contiguous(memory_format=_CL)
-        dw = None
-        if ctx.needs_input_grad[8]:
-            p = ctx.w_param
-            tgt, dw = _grad_target(p, w, torch.contiguous_format)
-            PROFILE.bracket("dwconv_wgrad", lambda: lib.dwconv2d_bwd_weight_bnswish(e, save_mean, save_invstd, gamma, beta, gy, tgt, *ctx.geom))
-            if dw is None:
-                _grad_ready(p)
-        da = torch.empty_like(e, memory_format=_CL)
-        PROFILE.bracket("dwconv_dgrad", lambda: lib.dwconv2d_bwd_data(gy, w, da, *ctx.geom))
-        de = torch.empty_like(e, memory_format=_CL)
-        red = _ZERO_POOL.acquire(lib.bn_stats_floats(ctx.C), e.device)
-        dg_t, dg_ret = _grad_target(ctx.gamma_param, gamma)
-        db_t, db_ret = _grad_target(ctx.beta_param, beta)
-        PROFILE.bracket("bn_bwd", lambda: lib.bn_act_bwd(da, None, e, save_mean, save_invstd, gamma, beta, 2, ctx.M, ctx.C, red, de, None, dg_t, db_t))
-        _ZERO_POOL.release(red)
-        if dg_ret is None:
-            _grad_ready(ctx.gamma_param)
-        if db_ret is None:
-            _grad_ready(ctx.beta_param)
-        return de, None, dg_ret, db_ret, None, None, None, None, dw, None, None, None
-
-
-def bn_swish_dwconv(e, stats, bn: torch.nn.BatchNorm2d, w, stride, pad4, want_stats=False):
-    """dwconv2d(bn_act(e, stats, bn, None, "swish"), w, stride, pad4, want_stats) in training mode, without the activated tensor."""
-    assert bn.training and stats is not None
-    return _BNSwishDwConv.apply(e, stats, bn.weight, bn.bias, float(bn.eps), float(bn.momentum), bn.running_mean, bn.running_var, w, stride,
-                                tuple(pad4), want_stats)
 
 
 def dwconv2d(x, w, stride, pad4, want_stats=False):

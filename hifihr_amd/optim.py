@@ -9,8 +9,6 @@ Semantics: torch.optim.Adam as configured at reference train_hrnet.py:546-551.
 """
 from __future__ import annotations
 
-import os
-
 import torch
 
 from ._lib import get_lib, require_cuda
@@ -74,13 +72,10 @@ class FusedAdam(torch.optim.Optimizer):
         self._lib = None
         # graph mode: the step counter and the learning rate live in device memory (hifihr_adam_step_counted: the kernel derives the bias
         # corrections and advances the counter itself), uploaded by prepare_step() only when the host's view of them changed -- a scheduler
-        # step, a restored checkpoint.  HIFIHR_ADAM_COUNTED=0: the two per-step scalars uploaded before every replay (hifihr_adam_step_dyn).
+        # step, a restored checkpoint.
         self.graph_mode = False
-        self._counted = os.environ.get("HIFIHR_ADAM_COUNTED", "1") != "0"
         self._state = None                  # device image of (lr, betas, step)
         self._state_sig = None              # (lr, betas, completed steps) the device holds
-        self._dyn = None
-        self._dyn_host = None
         self._prepared = False              # prepare_step() ran and the launch / replay it announced has not been noted yet
 
     @property
@@ -94,26 +89,17 @@ class FusedAdam(torch.optim.Optimizer):
         self._state_sig = None
         self._prepared = False
 
-    _RING = 32        # pinned staging slots for the per-step scalars
-
     def enable_graph_mode(self):
         """The device-side state is allocated ONCE per optimizer: a graph captured after an earlier enable_graph_mode() has the
         buffers' addresses baked in, and a second call (a re-capture after a lambda schedule fired) must not free them under it."""
         self.graph_mode = True
         self._prepared = False
         self._state_sig = None
-        if self._counted and self.flatp.flat.is_cuda:
-            if self._lib is None:
-                self._lib = get_lib()
-            if self._state is None:
-                self._state = torch.zeros(int(self._lib.c.hifihr_adam_state_bytes()), dtype=torch.uint8, device=self.flatp.flat.device)
-        else:
-            self._counted = False
-        if self._dyn is None:
-            self._dyn = torch.zeros(2, device=self.flatp.flat.device)
-            cuda = self.flatp.flat.is_cuda
-            self._dyn_host = torch.zeros(self._RING, 2).pin_memory() if cuda else torch.zeros(self._RING, 2)
-            self._dyn_events = [None] * self._RING
+        require_cuda(self.flatp.flat)
+        if self._lib is None:
+            self._lib = get_lib()
+        if self._state is None:
+            self._state = torch.zeros(int(self._lib.c.hifihr_adam_state_bytes()), dtype=torch.uint8, device=self.flatp.flat.device)
 
     def disable_graph_mode(self):
         """Back to the eager step (scalars passed by value, step counter advanced by step())."""
@@ -129,10 +115,8 @@ class FusedAdam(torch.optim.Optimizer):
         self._prepared = False
 
     def prepare_step(self):
-        """Graph mode: advance the step counter and upload {lr/(1-b1^t), 1/sqrt(1-b2^t)}; call before each replay.
-        The asynchronous copy reads a pinned host slot when the GPU gets to it, possibly many host steps later: every step
-        writes a slot of its own (ring), and a slot is rewritten only after the copy that read it has completed (event) --
-        a single staging buffer let a pending copy pick up a LATER step's scalars when the host ran ahead."""
+        """Graph mode: advance the step counter; call before each replay.  The device advances its own counter, so the state image
+        (lr, betas, completed steps) is uploaded only when what the device holds is not what this step needs."""
         g = self.param_groups[0]
         if self._prepared:                  # the step announced last time was never enqueued
             self._step_count -= 1
@@ -140,24 +124,10 @@ class FusedAdam(torch.optim.Optimizer):
         self._prepared = True
         self._step_count += 1
         b1, b2 = g["betas"]
-        if self._counted:
-            # the device advances its own counter: upload only when what it holds is not what this step needs
-            want = (float(g["lr"]), float(b1), float(b2), self._step_count - 1)
-            if self._state_sig != want:
-                self._state.copy_(self._lib.adam_state_image(*want))        # (pageable source: a blocking, stream-ordered copy; rare)
-            self._state_sig = (want[0], want[1], want[2], self._step_count)     # after the replay that follows
-            return
-        slot = self.step_count % self._RING
-        ev = self._dyn_events[slot]
-        if ev is not None:
-            ev.synchronize()
-        self._dyn_host[slot, 0] = g["lr"] / (1.0 - b1 ** self.step_count)
-        self._dyn_host[slot, 1] = 1.0 / (1.0 - b2 ** self.step_count) ** 0.5
-        self._dyn.copy_(self._dyn_host[slot], non_blocking=True)
-        if self._dyn.is_cuda:
-            ev = self._dyn_events[slot] or torch.cuda.Event()
-            ev.record()
-            self._dyn_events[slot] = ev
+        want = (float(g["lr"]), float(b1), float(b2), self._step_count - 1)
+        if self._state_sig != want:
+            self._state.copy_(self._lib.adam_state_image(*want))        # (pageable source: a blocking, stream-ordered copy; rare)
+        self._state_sig = (want[0], want[1], want[2], self._step_count)     # after the replay that follows
 
     def zero_grad(self, set_to_none: bool = False):
         self.flatp.zero_grad()
@@ -175,13 +145,8 @@ class FusedAdam(torch.optim.Optimizer):
                     raise RuntimeError("FusedAdam.step() in graph mode without prepare_step(): the device-side step counter / the uploaded "
                                        "bias corrections would be those of the previous step")
                 self._prepared = False
-        if self.graph_mode and self._counted:
             self._lib.adam_step_counted(self.flatp.flat, self.flatp.grad, self.exp_avg, self.exp_avg_sq, self.grad_scale, g["eps"],
                                         g["weight_decay"], self._state)
-            return
-        if self.graph_mode:
-            self._lib.adam_step_dyn(self.flatp.flat, self.flatp.grad, self.exp_avg, self.exp_avg_sq, self.grad_scale,
-                                    g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self._dyn)
             return
         self._step_count += 1
         from .ops import PROFILE

@@ -19,9 +19,9 @@ for i in range(2):
     l, d = train_step(model, LossFunction(), opt, ex, args)
     print("eager", i, float(l), bool(torch.isfinite(flat.flat).all()))
 g = GraphedTrainStep(model, LossFunction(), opt, ex, args, warmup=2)
-print("after capture: params finite", bool(torch.isfinite(flat.flat).all()), "dyn", g.opt._dyn.tolist(), "grad finite", bool(torch.isfinite(flat.grad).all()))
+print("after capture: params finite", bool(torch.isfinite(flat.flat).all()), "state", g.opt._state_sig, "grad finite", bool(torch.isfinite(flat.grad).all()))
 for i in range(3):
     l, d = g()
     torch.cuda.synchronize()
     print("replay", i, float(l), {k: float(v) for k, v in d.items() if k != "loss"}, "params finite", bool(torch.isfinite(flat.flat).all()),
-          "grad finite", bool(torch.isfinite(flat.grad).all()), "dyn", g.opt._dyn.tolist())
+          "grad finite", bool(torch.isfinite(flat.grad).all()), "state", g.opt._state_sig)

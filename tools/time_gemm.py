@@ -1,5 +1,5 @@
 """csrc/gemm.hip (hand-written batched f32 GEMM, 16x16x4 MFMA) on the Winograd GEMM shapes of the ResNet-18 step (B = 32):
-tile / split variants vs round 1's gather kernels (HIFIHR_BGEMM=0) and vs the vendor library (torch.bmm), which is only the
+tile / split variants vs the vendor library (torch.bmm), which is only the
 yardstick here -- the product path no longer calls it."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -32,12 +32,7 @@ for H, C, K in shapes:
     gf = 2.0 * 16 * T * C * K / 1e9
     ref = torch.bmm(V, U.transpose(1, 2))
     t_bmm = timeit(lambda: torch.bmm(V, U.transpose(1, 2), out=M))
-    setenv("HIFIHR_BGEMM", 0)
-    nb = lib.wino_gemm_workspace_bytes(B, H, H, C, K)
-    ws = torch.zeros(nb // 4 + 64, device="cuda") if nb else None
-    t_old = timeit(lambda: lib.wino_gemm(V, U, M, B, H, H, C, K, ws=ws))
-    setenv("HIFIHR_BGEMM", None)
-    line = f"T={T:5d} C={C:3d} K={K:3d} {gf:5.1f} GF | bmm {t_bmm:6.1f} us ({gf / t_bmm * 1e3:5.1f} TF) | r1 kernel {t_old:6.1f} |"
+    line = f"T={T:5d} C={C:3d} K={K:3d} {gf:5.1f} GF | bmm {t_bmm:6.1f} us ({gf / t_bmm * 1e3:5.1f} TF) |"
     for tile, ws_, sk in ((128128, 4, 1), (128128, 2, 1), (128128, 4, 0), (128128, 2, 0), (128128, 0, 0), (64064, 0, 0)):
         setenv("HIFIHR_GEMM_NT_TILE", tile); setenv("HIFIHR_GEMM_WS", ws_); setenv("HIFIHR_GEMM_SK", sk)
         nbk = lib.wino_gemm_workspace_bytes(B, H, H, C, K)
