@@ -253,6 +253,13 @@ class HifihrLib:
         c.hifihr_adam_state_bytes.restype = c_size_t
         c.hifihr_adam_state_bytes.argtypes = []
         c.hifihr_adam_step_counted.argtypes = [_c_float_p, _c_float_p, _c_float_p, _c_float_p, c_size_t, c_float, c_float, c_float, c_void_p, c_void_p]
+        c.hifihr_grad_guard_bytes.restype = c_size_t
+        c.hifihr_grad_guard_bytes.argtypes = []
+        c.hifihr_grad_norm_workspace_bytes.restype = c_size_t
+        c.hifihr_grad_norm_workspace_bytes.argtypes = [c_size_t]
+        c.hifihr_grad_norm.argtypes = [_c_float_p, c_size_t, c_float, c_float, c_void_p, c_void_p, c_void_p]
+        c.hifihr_adam_step_guarded.argtypes = [_c_float_p, _c_float_p, _c_float_p, _c_float_p, c_size_t, c_float, c_float, c_float, c_float,
+                                               c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]
         c.hifihr_adam_step_dyn.argtypes = [_c_float_p, _c_float_p, _c_float_p, _c_float_p, c_size_t, c_float, c_float, c_float,
                                            c_float, c_float, _c_float_p, c_void_p]
         c.hifihr_renderer_destroy.argtypes = [c_void_p]
@@ -1023,6 +1030,39 @@ class HifihrLib:
         self.check(self.c.hifihr_adam_step_dyn(_fp(p), _fp(g), _fp(m), _fp(v), c_size_t(n), c_float(grad_scale), c_float(beta1),
                                                c_float(beta2), c_float(eps), c_float(weight_decay), _fp(dyn), _stream_of(p)),
                    "hifihr_adam_step_dyn")
+
+    # ---- gradient guard (include/hifihr.h: hifihr_grad_norm / hifihr_adam_step_guarded) ----
+    def grad_guard_alloc(self, n, device):
+        """(guard block, workspace) for a flat gradient of n floats: uint8 tensors, the guard block zeroed once as the header asks."""
+        guard = torch.zeros(int(self.c.hifihr_grad_guard_bytes()), dtype=torch.uint8, device=device)
+        ws = torch.zeros(int(self.c.hifihr_grad_norm_workspace_bytes(c_size_t(n))), dtype=torch.uint8, device=device)
+        return guard, ws
+
+    def grad_norm(self, g, grad_scale, max_norm, guard, ws):
+        n = g.numel()
+        assert guard.dtype == torch.uint8 and guard.numel() == int(self.c.hifihr_grad_guard_bytes()) and guard.device == g.device
+        assert ws.dtype == torch.uint8 and ws.numel() >= int(self.c.hifihr_grad_norm_workspace_bytes(c_size_t(n))) and ws.device == g.device
+        self.check(self.c.hifihr_grad_norm(_fp(g), c_size_t(n), c_float(grad_scale), c_float(max_norm), c_void_p(guard.data_ptr()),
+                                           c_void_p(ws.data_ptr()), _stream_of(g)), "hifihr_grad_norm")
+
+    def adam_step_guarded(self, p, g, m, v, grad_scale, lr, beta1, beta2, eps, weight_decay, step, state, guard):
+        """state None: the host-scalar form (lr, betas, step as hifihr_adam_step); a state tensor: the counted form (they are ignored)."""
+        n = p.numel()
+        assert g.numel() == n and m.numel() == n and v.numel() == n
+        assert guard.dtype == torch.uint8 and guard.numel() == int(self.c.hifihr_grad_guard_bytes()) and guard.device == p.device
+        if state is not None:
+            assert state.dtype == torch.uint8 and state.numel() == int(self.c.hifihr_adam_state_bytes()) and state.device == p.device
+        self.check(self.c.hifihr_adam_step_guarded(_fp(p), _fp(g), _fp(m), _fp(v), c_size_t(n), c_float(grad_scale), c_float(lr),
+                                                   c_float(beta1), c_float(beta2), c_float(eps), c_float(weight_decay), int(step),
+                                                   c_void_p(state.data_ptr()) if state is not None else c_void_p(0),
+                                                   c_void_p(guard.data_ptr()), _stream_of(p)), "hifihr_adam_step_guarded")
+
+    @staticmethod
+    def grad_guard_unpack(raw):
+        """The 32 bytes of the guard block (include/hifihr.h) as a dict: norm, clip_coef, finite, steps, clipped, skipped."""
+        import struct
+        norm, coef, finite, steps, clipped, skipped, _ = struct.unpack("<dfiiiii", bytes(raw))
+        return {"norm": norm, "clip_coef": coef, "finite": bool(finite), "steps": steps, "clipped": clipped, "skipped": skipped}
 
     # ---- renderer ----------------------------------------------------
     def renderer_create(self, faces, V, image_size=224, aa=3, ambient=(0.5, 0.5, 0.5), mat_diffuse=(0.8, 0.8, 0.8),

@@ -483,6 +483,35 @@ int hifihr_adam_step_dyn(float* params, const float* grads, float* exp_avg, floa
   return HIFIHR_OK;
 }
 
+size_t hifihr_grad_guard_bytes(void) { return hifihr::grad_guard_bytes(); }
+size_t hifihr_grad_norm_workspace_bytes(size_t n) { return hifihr::grad_norm_workspace_bytes(n); }
+
+int hifihr_grad_norm(const float* grads, size_t n, float grad_scale, float max_norm, void* guard_d, void* ws_d, void* stream) {
+  if (!grads || !guard_d || !ws_d) return fail(HIFIHR_EINVAL, "hifihr_grad_norm: bad argument");
+  if (((uintptr_t)grads & 15) || (((uintptr_t)guard_d | (uintptr_t)ws_d) & 7))
+    return fail(HIFIHR_EINVAL, "hifihr_grad_norm: grads_d must be 16-byte aligned, guard_d and ws_d 8-byte");
+  if (!(max_norm > 0.f) || !std::isfinite(grad_scale))          // (max_norm NaN fails the comparison; +inf passes: guard only)
+    return fail(HIFIHR_EINVAL, "hifihr_grad_norm: max_norm must be > 0 (+inf allowed) and grad_scale finite");
+  if (n == 0) return HIFIHR_OK;                  // not a step: the counters stay
+  HIP_TRY(hifihr::launch_grad_norm(grads, n, grad_scale, max_norm, guard_d, ws_d, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, float grad_scale, float lr,
+                             float beta1, float beta2, float eps, float weight_decay, int step, void* state_d, const void* guard_d,
+                             void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !guard_d || (!state_d && step < 1))
+    return fail(HIFIHR_EINVAL, "hifihr_adam_step_guarded: bad argument");
+  if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) ||
+      (((uintptr_t)state_d | (uintptr_t)guard_d) & 7))
+    return fail(HIFIHR_EINVAL, "hifihr_adam_step_guarded: buffers must be 16-byte aligned (the state and the guard block: 8)");
+  if (!std::isfinite(grad_scale)) return fail(HIFIHR_EINVAL, "hifihr_adam_step_guarded: grad_scale must be finite");
+  if (n == 0) return HIFIHR_OK;                  // as the unguarded entries: nothing launched, the counter stays
+  HIP_TRY(hifihr::launch_adam_guarded(params, grads, exp_avg, exp_avg_sq, n, grad_scale, lr, beta1, beta2, eps, weight_decay, step, state_d,
+                                      guard_d, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
 static int conv_dims_ok(int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
   return N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && S > 0 && stride > 0 && pad >= 0 && (H + 2 * pad - R) >= 0 &&
          (W + 2 * pad - S) >= 0;

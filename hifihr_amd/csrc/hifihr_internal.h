@@ -537,6 +537,12 @@ hipError_t launch_adam_counted(float* p, const float* g, float* m, float* v, siz
                                void* state, hipStream_t st);
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, size_t n, float grad_scale, float lr, float beta1,
                        float beta2, float eps, float weight_decay, int step, const float* dyn, hipStream_t st);
+// the gradient guard (csrc/adam.hip): norm pass + finish into the 32-byte guard block, and the Adam launch that reads it
+size_t grad_guard_bytes();
+size_t grad_norm_workspace_bytes(size_t n);
+hipError_t launch_grad_norm(const float* g, size_t n, float grad_scale, float max_norm, void* guard, void* ws, hipStream_t st);
+hipError_t launch_adam_guarded(float* p, const float* g, float* m, float* v, size_t n, float grad_scale, float lr, float beta1, float beta2,
+                               float eps, float weight_decay, int step, void* state, const void* guard, hipStream_t st);
 
 // joint_2d / bone_direc / bone_direc_3d of LossFunction (csrc/losses.hip): J = 21; either the 2-D or the 3-D pair may be NULL
 hipError_t launch_joint_terms_fwd(const float* j2d, const float* j2d_gt, const float* j3d, const float* j3d_gt, int B, int J, int mse,

@@ -62,7 +62,18 @@ class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam semantics on a FlatParams (one kernel launch per step).  Subclasses Optimizer so that
     torch.optim.lr_scheduler.MultiStepLR (train_hrnet.py:551) drives param_groups[0]['lr'] unchanged."""
 
-    def __init__(self, flat: FlatParams, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
+    def __init__(self, flat: FlatParams, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, max_grad_norm=None):
+        """max_grad_norm (None = off: exactly the unguarded launches): a float > 0 turns the gradient guard on -- step() first takes the
+        global L2 norm of grad_scale * flat.grad on the device (hifihr_grad_norm), then runs the Adam launch that reads the clip
+        coefficient min(1, max_grad_norm / (norm + 1e-6)) and the finite flag from device memory (hifihr_adam_step_guarded).  A gradient
+        with a NaN / inf in it leaves parameters and moments untouched; the step still counts (include/hifihr.h).  float('inf') = guard
+        only.  Nothing is read back, so a captured step keeps replaying; grad_stats() reads the block for a log line."""
+        if max_grad_norm is not None:
+            ok = isinstance(max_grad_norm, (int, float)) and not isinstance(max_grad_norm, bool) and max_grad_norm > 0     # (NaN fails >)
+            if not ok:
+                raise ValueError(f"max_grad_norm must be None (off) or a number > 0 (inf = guard only), got {max_grad_norm!r}")
+            max_grad_norm = float(max_grad_norm)
+        self.max_grad_norm = max_grad_norm
         self.flatp = flat
         super().__init__([flat.flat], dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.exp_avg = torch.zeros_like(flat.flat)
@@ -77,6 +88,12 @@ class FusedAdam(torch.optim.Optimizer):
         self._state = None                  # device image of (lr, betas, step)
         self._state_sig = None              # (lr, betas, completed steps) the device holds
         self._prepared = False              # prepare_step() ran and the launch / replay it announced has not been noted yet
+        # gradient guard: the 32-byte block and the norm pass's workspace, allocated ONCE -- captured graphs have their addresses baked in.
+        # The counters in the block are not persisted (state_dict() and the .t7 files do not change).
+        self._guard = self._guard_ws = None
+        if max_grad_norm is not None:
+            self._lib = get_lib()
+            self._guard, self._guard_ws = self._lib.grad_guard_alloc(flat.flat.numel(), flat.flat.device)
 
     @property
     def step_count(self):
@@ -145,14 +162,41 @@ class FusedAdam(torch.optim.Optimizer):
                     raise RuntimeError("FusedAdam.step() in graph mode without prepare_step(): the device-side step counter / the uploaded "
                                        "bias corrections would be those of the previous step")
                 self._prepared = False
+            if self.max_grad_norm is not None:
+                self._lib.grad_norm(self.flatp.grad, self.grad_scale, self.max_grad_norm, self._guard, self._guard_ws)
+                self._lib.adam_step_guarded(self.flatp.flat, self.flatp.grad, self.exp_avg, self.exp_avg_sq, self.grad_scale, 0.0, 0.0, 0.0,
+                                            g["eps"], g["weight_decay"], 0, self._state, self._guard)
+                return
             self._lib.adam_step_counted(self.flatp.flat, self.flatp.grad, self.exp_avg, self.exp_avg_sq, self.grad_scale, g["eps"],
                                         g["weight_decay"], self._state)
             return
         self._step_count += 1
         from .ops import PROFILE
+        if self.max_grad_norm is not None:
+            def guarded():
+                self._lib.grad_norm(self.flatp.grad, self.grad_scale, self.max_grad_norm, self._guard, self._guard_ws)
+                self._lib.adam_step_guarded(self.flatp.flat, self.flatp.grad, self.exp_avg, self.exp_avg_sq, self.grad_scale, g["lr"],
+                                            g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.step_count, None, self._guard)
+            PROFILE.bracket("adam", guarded)
+            return
         PROFILE.bracket("adam", lambda: self._lib.adam_step(self.flatp.flat, self.flatp.grad, self.exp_avg, self.exp_avg_sq,
                                                             self.grad_scale, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
                                                             g["weight_decay"], self.step_count))
+
+    def grad_stats(self):
+        """The guard block as a dict -- norm, clip_coef, finite (of the last step), steps, clipped, skipped (since construction): one
+        32-byte copy that SYNCHRONISES, meant for a log line.  None when the guard is off."""
+        if self._guard is None:
+            return None
+        return self._lib.grad_guard_unpack(self._guard.cpu().numpy().tobytes())
+
+    def guard_snapshot(self):
+        """The guard block for a later guard_restore() (the warm-up of a captured step must not show in a run's counters)."""
+        return None if self._guard is None else self._guard.clone()
+
+    def guard_restore(self, snap):
+        if snap is not None:
+            self._guard.copy_(snap)
 
     def state_dict(self):
         return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,

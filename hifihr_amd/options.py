@@ -23,6 +23,9 @@ _DEFAULTS = dict(
     # opt-in differentiable silhouette (hifihr_amd/ops.py soft_silhouette; the loss names "sil_soft" / "iou_soft" switch it on as well).
     # The two weights are the defaults of their hard counterparts lambda_silhouette / lambda_iou: starting points, not tuned values
     soft_silhouette=False, soft_sil_sigma=1e-4, lambda_silhouette_soft=0.005, lambda_iou_soft=1e-3,
+    # opt-in gradient guard of the fused Adam step (hifihr_amd/optim.py FusedAdam(max_grad_norm=...)): the global L2 norm the gradient is
+    # clipped to, and a step whose gradient holds a NaN / inf is skipped.  0 = off; inf = the skip alone
+    max_grad_norm=0.0,
 )
 
 # lambda values of reference config/FreiHAND/full_rhd_freihand.json, used by the

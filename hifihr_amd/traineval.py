@@ -230,10 +230,11 @@ class GraphedTrainStep:
         split = reducer is not None
         # Warm-up and capture must leave the training state exactly as they found it (the warm-up runs real steps on one batch;
         # a re-capture happens whenever a lambda schedule fires): parameters, Adam moments, step counter and every module buffer
-        # (batch-norm running statistics) are snapshotted here and restored below.
+        # (batch-norm running statistics) are snapshotted here and restored below -- and the gradient guard's counters, so that a
+        # re-capture does not add its warm-up steps to a run's totals.
         flat = optimizer.flatp
         snap = (flat.flat.clone(), optimizer.exp_avg.clone(), optimizer.exp_avg_sq.clone(), optimizer.step_count,
-                [b.clone() for b in model.buffers()])
+                [b.clone() for b in model.buffers()], optimizer.guard_snapshot())
         if split:
             reducer.pause_hooks(True)                           # the graph must not contain (or trigger) collectives
         else:
@@ -278,11 +279,12 @@ class GraphedTrainStep:
         self._restore(snap)
 
     def _restore(self, snap):
-        flat_w, m, v, step, bufs = snap
+        flat_w, m, v, step, bufs, guard = snap
         with torch.no_grad():
             self.opt.flatp.flat.copy_(flat_w)
             self.opt.exp_avg.copy_(m)
             self.opt.exp_avg_sq.copy_(v)
+            self.opt.guard_restore(guard)
             for b, s in zip(self.model.buffers(), bufs):
                 b.copy_(s)
         self.opt.step_count = step
@@ -348,7 +350,7 @@ class SegmentedGraphedTrainStep:
         self.ranges = [(hi4, n), (lo4, hi4), (lo3, hi3), (0, lo3)]
         assert 0 < lo3 <= hi3 == lo4 <= hi4 <= n, (lo3, hi3, lo4, hi4, n)
         snap = (flat.flat.clone(), optimizer.exp_avg.clone(), optimizer.exp_avg_sq.clone(), optimizer.step_count,
-                [b.clone() for b in model.buffers()])
+                [b.clone() for b in model.buffers()], optimizer.guard_snapshot())
         reducer.pause_hooks(True)
         self._enc = enc
         self._scope = None

@@ -333,6 +333,41 @@ int hifihr_adam_step_dyn(float* params_d, const float* grads_d, float* exp_avg_d
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Gradient guard for the fused Adam step: global L2 norm clipping and a skip on a non-finite gradient, all on the device (nothing is
+ * read back, both calls can be captured in a hipGraph).  Where torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) and a
+ * skip-on-overflow step would sit in front of optimizer.step(), reference train_hrnet.py:111-113.
+ *   hifihr_grad_norm(grads_d, n, grad_scale, max_norm, guard_d, ws_d): two launches -- per-workgroup sums of g_i^2 (squares and sums in
+ *     double: a finite fp32 gradient never overflows them) into ws_d, then one workgroup that folds them and writes guard_d.  Every
+ *     summation order is fixed: the same input gives the same bits.
+ *   hifihr_adam_step_guarded(..., state_d, guard_d): the Adam update of hifihr_adam_step (state_d NULL: lr, beta*, step from the host) or
+ *     of hifihr_adam_step_counted (state_d given: lr, beta1, beta2 and step are ignored), reading {coef, finite} from guard_d.
+ * guard_d: hifihr_grad_guard_bytes() = 32 bytes, 8-byte aligned, zeroed ONCE by the caller:
+ *   f64 norm      sqrt(sum (grad_scale g_i)^2) of the last norm pass (alignment padding inside grads_d must be zero)
+ *   f32 coef      min(1, max_norm / (norm + 1e-6)) as clip_grad_norm_ forms it; exactly 1.0f for max_norm = +inf; 0 when not finite
+ *   i32 finite    1 when the sum of squares is finite, 0 when any element is NaN or +-inf
+ *   i32 steps, i32 clipped (coef < 1), i32 skipped (not finite): running counts, advanced by every norm pass
+ *   i32 padding
+ * ws_d: hifihr_grad_norm_workspace_bytes(n) bytes, 8-byte aligned, contents irrelevant.
+ * finite:     the update runs with grad_scale * coef (one f32 product) in the place of grad_scale; weight decay is added after, as in
+ *             the unguarded entries.  coef == 1.0f gives the bits of hifihr_adam_step / hifihr_adam_step_counted on the same inputs.
+ * not finite: the step is SKIPPED -- params, exp_avg and exp_avg_sq keep their bits, no weight decay -- but it still COUNTS: the counted
+ *             state's step and running products advance exactly as in hifihr_adam_step_counted, and a host-scalar caller keeps
+ *             incrementing `step`.  (torch.cuda.amp.GradScaler does not count a skipped step; here the host never reads the flag back,
+ *             so lr schedule, checkpoint step and data-parallel ranks stay aligned.  The price is a bias correction one step ahead.)
+ * Data parallel: call hifihr_grad_norm after the all-reduce with the same grad_scale the Adam call gets; every rank sees the same bits.
+ * Refused (HIFIHR_EINVAL, nothing launched or written): a NULL pointer (state_d excepted: it selects the form); grads_d (and for the
+ * step the other three buffers) not 16-byte aligned; guard_d, ws_d or state_d not 8-byte aligned; max_norm NaN or <= 0 (+inf is
+ * accepted: guard only); a non-finite grad_scale; step < 1 when state_d is NULL.
+ * n = 0 is accepted by both and is NOT a step: nothing is launched, nothing written, no counter moves.
+ * ---------------------------------------------------------------------------------------------- */
+size_t hifihr_grad_guard_bytes(void);
+size_t hifihr_grad_norm_workspace_bytes(size_t n);
+int hifihr_grad_norm(const float* grads_d, size_t n, float grad_scale, float max_norm, void* guard_d, void* ws_d, void* stream);
+int hifihr_adam_step_guarded(float* params_d, const float* grads_d, float* exp_avg_d, float* exp_avg_sq_d, size_t n, float grad_scale,
+                             float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* state_d,
+                             const void* guard_d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * NHWC fp32 convolution on the f32 matrix cores (implicit GEMM, exact fp32 accumulate).
  * Replaces the cuDNN/MIOpen dispatches of the encoder's nn.Conv2d layers (forward, backward-data,
  * backward-weight): reference network/res_encoder.py:364-373 (ResNet trunk built at :345-362).

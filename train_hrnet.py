@@ -61,6 +61,9 @@ def parse(argv=None):
     ap.add_argument("--soft_silhouette", action="store_true",
                     help="the model also emits outputs['re_sil_soft'], a differentiable silhouette (options: soft_silhouette, soft_sil_sigma); "
                          "the loss names 'sil_soft' / 'iou_soft' switch it on by themselves")
+    ap.add_argument("--max_grad_norm", type=float, default=None, metavar="X",
+                    help="gradient guard of the optimizer step (options: max_grad_norm): clip the global L2 norm of the gradient to X and skip a "
+                         "step whose gradient holds a NaN / inf, all on the device; 'inf' = the skip alone, 0 = off (the default)")
     ap.add_argument("--override", default=None, help='JSON object of option overrides, e.g. \'{"total_epochs": 2}\'')
     return ap.parse_args(argv)
 
@@ -69,6 +72,19 @@ def soft_silhouette_kwargs(args):
     """Model(...)'s soft-silhouette options: on when asked for, or when a loss term that reads outputs['re_sil_soft'] is requested."""
     on = bool(getattr(args, "soft_silhouette", False)) or any(k in args.losses for k in ("sil_soft", "iou_soft"))
     return dict(soft_silhouette=on, soft_sil_sigma=float(getattr(args, "soft_sil_sigma", 1e-4)))
+
+
+def optimizer_max_grad_norm(args):
+    """FusedAdam's max_grad_norm from the options: 0 (or a missing key) is off."""
+    x = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
+    return x if x != 0.0 else None
+
+
+def grad_guard_log(stats):
+    """What the training loops append to their log line: FusedAdam.grad_stats() (None: the guard is off)."""
+    if stats is None:
+        return ""
+    return f" gnorm={stats['norm']:.3e} clipped={stats['clipped']}/{stats['steps']} skipped={stats['skipped']}"
 
 
 def build_args(cli):
@@ -86,6 +102,8 @@ def build_args(cli):
     args.texture_stand_in = 0
     if getattr(cli, "soft_silhouette", False):
         args.soft_silhouette = True
+    if getattr(cli, "max_grad_norm", None) is not None:
+        args.max_grad_norm = float(cli.max_grad_norm)
     if cli.lpips_weights:
         args.lpips_weights = list(cli.lpips_weights)
     elif isinstance(getattr(args, "lpips_weights", None), str):        # a JSON may name one file
@@ -199,7 +217,8 @@ def train_ho3d(cli, args, model, loss_func, opt, sched, reducer, current_epoch, 
                 dt, t_last = time.perf_counter() - t_last, time.perf_counter()
                 n_it = cli.print_freq if it % cli.print_freq == 0 else it % cli.print_freq
                 terms = " ".join(f"{k}={float(dic[k].detach()):.4g}" for k in args.losses)
-                say(f"[train_hrnet] epoch {epoch + current_epoch} it {it} loss {float(loss.detach()):.5f} ({terms}) {n_it * per_step / dt:.0f} img/s")
+                say(f"[train_hrnet] epoch {epoch + current_epoch} it {it} loss {float(loss.detach()):.5f} ({terms}) {n_it * per_step / dt:.0f} img/s"
+                    + grad_guard_log(opt.grad_stats()))
             if cli.max_iters and it >= cli.max_iters:
                 break
         if (epoch + current_epoch) % args.save_interval == 0 or (cli.max_iters and it >= cli.max_iters):
@@ -337,7 +356,8 @@ def main(argv=None):
     hdist.broadcast_params(flat)
     reducer = hdist.GradReducer(flat, num_buckets=4)
     wd = 0.01 if args.optimizer == "AdamW" else 0.0                   # train_hrnet.py:549-550: "AdamW" is Adam with L2 0.01
-    opt = FusedAdam(flat, lr=args.init_lr, betas=(0.9, 0.999), weight_decay=wd, grad_scale=reducer.grad_scale)
+    opt = FusedAdam(flat, lr=args.init_lr, betas=(0.9, 0.999), weight_decay=wd, grad_scale=reducer.grad_scale,
+                    max_grad_norm=optimizer_max_grad_norm(args))
     sched = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=args.lr_steps, gamma=args.lr_gamma)
     model, current_epoch, opt, sched = load_model(model, opt, sched, args)
     if args.force_init_lr > 0:
@@ -409,7 +429,8 @@ def main(argv=None):
                 t_last = time.perf_counter()
                 n_it = cli.print_freq if it % cli.print_freq == 0 else it % cli.print_freq
                 terms = " ".join(f"{k}={float(dic[k].detach()):.4g}" for k in args.losses)
-                say(f"[train_hrnet] epoch {epoch + current_epoch} it {it} loss {float(loss.detach()):.5f} ({terms}) {n_it * per_step / dt:.0f} img/s")
+                say(f"[train_hrnet] epoch {epoch + current_epoch} it {it} loss {float(loss.detach()):.5f} ({terms}) {n_it * per_step / dt:.0f} img/s"
+                    + grad_guard_log(opt.grad_stats()))
             if cli.max_iters and it >= cli.max_iters:
                 break
         if (epoch + current_epoch) % args.save_interval == 0 or (cli.max_iters and it >= cli.max_iters):
