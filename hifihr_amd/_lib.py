@@ -277,6 +277,14 @@ class HifihrLib:
         c.hifihr_soft_sil_loss_fwd.argtypes = [_c_float_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, _c_float_p, c_void_p]
         c.hifihr_soft_sil_loss_bwd.argtypes = [_c_float_p, c_void_p, c_int, c_void_p, _c_float_p, c_int, c_int, c_float, c_float, _c_float_p,
                                                c_void_p]
+        c.hifihr_mesh_topology_create.argtypes = [_c_int_p, c_int, c_int]
+        c.hifihr_mesh_topology_create.restype = c_void_p
+        c.hifihr_mesh_topology_destroy.argtypes = [c_void_p]
+        c.hifihr_mesh_topology_counts.argtypes = [c_void_p, _c_int_p, _c_int_p, _c_int_p]
+        c.hifihr_mesh_reg_partial_floats.argtypes = [c_void_p, c_int]
+        c.hifihr_mesh_reg_partial_floats.restype = c_size_t
+        c.hifihr_mesh_reg_fwd.argtypes = [c_void_p, _c_float_p, c_int, c_float, c_float, _c_float_p, _c_float_p, _c_float_p, c_void_p]
+        c.hifihr_mesh_reg_bwd.argtypes = [c_void_p, _c_float_p, _c_float_p, _c_float_p, c_int, c_float, c_float, _c_float_p, c_void_p]
         c.hifihr_renderer_set_uv.argtypes = [c_void_p, _c_int_p, _c_float_p, c_int]
         c.hifihr_render_uv_scratch_bytes.argtypes = [c_void_p, c_int]
         c.hifihr_render_uv_scratch_bytes.restype = c_size_t
@@ -1161,6 +1169,38 @@ class HifihrLib:
         self.check(self.c.hifihr_soft_sil_loss_bwd(_fp(alpha), mp, kind, c_void_p(sums.data_ptr()), _fp(gout), B, alpha.numel() // max(B, 1),
                                                    c_float(lam_sil), c_float(lam_iou), _fp(galpha), _stream_of(alpha)),
                    "hifihr_soft_sil_loss_bwd")
+
+    # ---- mesh regularisers (csrc/mesh_reg.hip) ----------------------------
+    def mesh_topology_create(self, faces, V) -> c_void_p:
+        """faces [F, 3] (host); raises when the library refuses them (include/hifihr.h "Mesh regularisers")."""
+        import numpy as np
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        assert f.ndim == 2 and f.shape[1] == 3, f.shape
+        h = self.c.hifihr_mesh_topology_create(f.ctypes.data_as(_c_int_p), int(f.shape[0]), int(V))
+        if not h:
+            raise HifihrError(f"hifihr_mesh_topology_create failed: {self.c.hifihr_last_error().decode()}")
+        return c_void_p(h)
+
+    def mesh_topology_destroy(self, h):
+        self.c.hifihr_mesh_topology_destroy(h)
+
+    def mesh_topology_counts(self, h):
+        """-> (V, E, Q)"""
+        v, e, q = c_int32(), c_int32(), c_int32()
+        self.check(self.c.hifihr_mesh_topology_counts(h, ctypes.byref(v), ctypes.byref(e), ctypes.byref(q)), "hifihr_mesh_topology_counts")
+        return v.value, e.value, q.value
+
+    def mesh_reg_partial_floats(self, h, B) -> int:
+        return int(self.c.hifihr_mesh_reg_partial_floats(h, int(B)))
+
+    def mesh_reg_fwd(self, h, verts, lam_lap, lam_nc, unit, partial, out):
+        """verts, unit [B, V, 3]; partial [mesh_reg_partial_floats(h, B)]; out [2]"""
+        self.check(self.c.hifihr_mesh_reg_fwd(h, _fp(verts), verts.shape[0], c_float(lam_lap), c_float(lam_nc), _fp(unit), _fp(partial),
+                                              _fp(out), _stream_of(verts)), "hifihr_mesh_reg_fwd")
+
+    def mesh_reg_bwd(self, h, verts, unit, gout, lam_lap, lam_nc, gverts):
+        self.check(self.c.hifihr_mesh_reg_bwd(h, _fp(verts), _fp(unit), _fp(gout), verts.shape[0], c_float(lam_lap), c_float(lam_nc),
+                                              _fp(gverts), _stream_of(verts)), "hifihr_mesh_reg_bwd")
 
 
 _LIB = None

@@ -2,6 +2,8 @@
 // kernel launches on the caller's stream.  No allocation and no synchronisation in compute calls.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -61,6 +63,11 @@ struct hifihr_renderer {
   DevBuf faces_uvs, verts_uvs;       // TexturesUV tables (hifihr_renderer_set_uv), empty otherwise
   int n_uv = 0;
   hifihr::RenderDev dev;
+};
+
+struct hifihr_mesh_topology {
+  DevBuf nbr_off, nbr_idx, deg, quads, vq_off, vq_idx;
+  hifihr::MeshTopoDev dev;
 };
 
 namespace {
@@ -446,6 +453,121 @@ int hifihr_soft_sil_loss_bwd(const float* alpha, const void* mask, int mask_i64,
     return fail(HIFIHR_EINVAL, "hifihr_soft_sil_loss_bwd: bad argument (B <= 65535)");
   if (B == 0) return HIFIHR_OK;
   HIP_TRY(hifihr::launch_soft_sil_loss_bwd(alpha, mask, mask_i64, sums, gout, B, HW, lam_sil, lam_iou, galpha, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+hifihr_mesh_topology_t* hifihr_mesh_topology_create(const int32_t* faces, int F, int V) {
+  if (!faces || F <= 0 || V <= 0) {
+    fail(HIFIHR_EINVAL, "hifihr_mesh_topology_create: bad argument (faces, F > 0, V > 0)");
+    return nullptr;
+  }
+  // one record per face side: (lower vertex, higher vertex, face, opposite vertex), sorted by edge and then by face
+  std::vector<std::array<int, 4>> sides;
+  sides.reserve((size_t)F * 3);
+  for (int f = 0; f < F; ++f) {
+    const int v[3] = {faces[3 * (size_t)f], faces[3 * (size_t)f + 1], faces[3 * (size_t)f + 2]};
+    for (int k = 0; k < 3; ++k)
+      if (v[k] < 0 || v[k] >= V) {
+        fail(HIFIHR_EINVAL, "hifihr_mesh_topology_create: face %d has an index outside [0, %d)", f, V);
+        return nullptr;
+      }
+    if (v[0] == v[1] || v[1] == v[2] || v[0] == v[2]) {
+      fail(HIFIHR_EINVAL, "hifihr_mesh_topology_create: face %d repeats a vertex", f);
+      return nullptr;
+    }
+    for (int k = 0; k < 3; ++k) {
+      const int i = v[k], j = v[(k + 1) % 3], o = v[(k + 2) % 3];
+      sides.push_back({std::min(i, j), std::max(i, j), f, o});
+    }
+  }
+  std::sort(sides.begin(), sides.end());
+  std::vector<int> off(V + 1, 0), quads;
+  std::vector<std::array<int, 2>> edges;
+  for (size_t s = 0; s < sides.size();) {
+    size_t t = s;
+    while (t < sides.size() && sides[t][0] == sides[s][0] && sides[t][1] == sides[s][1]) ++t;
+    edges.push_back({sides[s][0], sides[s][1]});
+    for (size_t a = s; a < t; ++a)
+      for (size_t b = a + 1; b < t; ++b) {
+        if (quads.size() / 4 + 1 >= ((size_t)1 << 29)) {
+          fail(HIFIHR_EINVAL, "hifihr_mesh_topology_create: too many face pairs on shared edges (4 Q >= 2^31)");
+          return nullptr;
+        }
+        quads.insert(quads.end(), {sides[s][0], sides[s][1], sides[a][3], sides[b][3]});
+      }
+    s = t;
+  }
+  const int E = (int)edges.size(), Q = (int)(quads.size() / 4);
+  for (const auto& e : edges) { off[e[0] + 1]++; off[e[1] + 1]++; }
+  for (int v = 0; v < V; ++v) off[v + 1] += off[v];
+  // the edges are sorted by (lower, higher): a vertex receives its lower neighbours first, ascending, then its higher ones, ascending
+  std::vector<int> idx((size_t)2 * E), cur(off.begin(), off.end() - 1);
+  for (const auto& e : edges) idx[cur[e[1]]++] = e[0];
+  for (const auto& e : edges) idx[cur[e[0]]++] = e[1];
+  std::vector<float> deg((size_t)V);
+  for (int v = 0; v < V; ++v) deg[v] = (float)(off[v + 1] - off[v]);
+  std::vector<int> qoff(V + 1, 0), qidx((size_t)4 * Q);
+  for (int x : quads) qoff[x + 1]++;
+  for (int v = 0; v < V; ++v) qoff[v + 1] += qoff[v];
+  std::vector<int> qcur(qoff.begin(), qoff.end() - 1);
+  for (int q = 0; q < Q; ++q)            // ascending quad order within a vertex => a fixed summation order in the backward
+    for (int r = 0; r < 4; ++r) qidx[qcur[quads[4 * (size_t)q + r]]++] = q * 4 + r;
+  hifihr_mesh_topology* h = new (std::nothrow) hifihr_mesh_topology();
+  if (!h) {
+    fail(HIFIHR_ENOMEM, "hifihr_mesh_topology_create: out of host memory");
+    return nullptr;
+  }
+  if (upload_i(h->nbr_off, off) || upload_i(h->nbr_idx, idx) || upload(h->deg, deg) || upload_i(h->quads, quads) ||
+      upload_i(h->vq_off, qoff) || upload_i(h->vq_idx, qidx)) {
+    delete h;
+    return nullptr;
+  }
+  hifihr::MeshTopoDev& d = h->dev;
+  d.V = V; d.E = E; d.Q = Q;
+  d.nbr_off = (const int*)h->nbr_off.p; d.nbr_idx = (const int*)h->nbr_idx.p; d.deg = (const float*)h->deg.p;
+  d.quads = (const int*)h->quads.p; d.vq_off = (const int*)h->vq_off.p; d.vq_idx = (const int*)h->vq_idx.p;
+  return h;
+}
+
+int hifihr_mesh_topology_destroy(hifihr_mesh_topology_t* h) {
+  delete h;
+  return HIFIHR_OK;
+}
+
+int hifihr_mesh_topology_counts(const hifihr_mesh_topology_t* h, int* V, int* E, int* Q) {
+  if (!h) return fail(HIFIHR_EINVAL, "hifihr_mesh_topology_counts: null handle");
+  if (V) *V = h->dev.V;
+  if (E) *E = h->dev.E;
+  if (Q) *Q = h->dev.Q;
+  return HIFIHR_OK;
+}
+
+size_t hifihr_mesh_reg_partial_floats(const hifihr_mesh_topology_t* h, int B) {
+  if (!h || B < 0) return 0;
+  return (size_t)B * hifihr::mesh_reg_blocks(h->dev) * 2;
+}
+
+namespace {
+bool mesh_reg_args_ok(const hifihr_mesh_topology_t* h, int B, float lam_lap, float lam_nc) {
+  return h && B >= 0 && (long long)B * h->dev.V * 3 < (1LL << 31) && std::isfinite(lam_lap) && std::isfinite(lam_nc);
+}
+}  // namespace
+
+int hifihr_mesh_reg_fwd(const hifihr_mesh_topology_t* h, const float* verts, int B, float lam_lap, float lam_nc, float* unit, float* partial,
+                        float* out, void* stream) {
+  if (!verts || !unit || !partial || !out || !mesh_reg_args_ok(h, B, lam_lap, lam_nc))
+    return fail(HIFIHR_EINVAL, "hifihr_mesh_reg_fwd: bad argument (B >= 0, B V 3 < 2^31, finite weights)");
+  if (B == 0) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_mesh_reg_fwd(h->dev, verts, B, lam_lap, lam_nc, unit, partial, out, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_mesh_reg_bwd(const hifihr_mesh_topology_t* h, const float* verts, const float* unit, const float* gout, int B, float lam_lap,
+                        float lam_nc, float* gverts, void* stream) {
+  if (!verts || !unit || !gout || !gverts || !mesh_reg_args_ok(h, B, lam_lap, lam_nc))
+    return fail(HIFIHR_EINVAL, "hifihr_mesh_reg_bwd: bad argument (B >= 0, B V 3 < 2^31, finite weights)");
+  if (B == 0) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_mesh_reg_bwd(h->dev, verts, unit, gout, B, lam_lap, lam_nc, gverts, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 

@@ -349,6 +349,20 @@ struct LossTotalGrads { float* g[kLossTotalParts]; int n[kLossTotalParts]; int l
 hipError_t launch_loss_total_fwd(const LossTotalParts& p, float* total, hipStream_t st);
 hipError_t launch_loss_total_bwd(const float* gtotal, const LossTotalGrads& q, hipStream_t st);
 
+// mesh regularisers (mesh_reg.hip): triangle (uniform Laplacian) and normal_consistency.  Every table is built and checked once by
+// hifihr_mesh_topology_create: nbr_off [V+1] / nbr_idx [2E] = ascending neighbours of every vertex, deg [V] = the neighbour count as a float (0 for an
+// isolated vertex), quads [Q][4] = (v0, v1, a, b), vq_off [V+1] / vq_idx [4Q] = vertex -> (quad * 4 + role) in ascending quad order
+struct MeshTopoDev {
+  const int *nbr_off, *nbr_idx, *quads, *vq_off, *vq_idx;
+  const float* deg;
+  int V, E, Q;
+};
+int mesh_reg_blocks(const MeshTopoDev& t);        // workgroups per sample of the forward: partial holds B * blocks * 2 floats
+hipError_t launch_mesh_reg_fwd(const MeshTopoDev& t, const float* verts, int B, float lam_lap, float lam_nc, float* unit, float* partial,
+                               float* out, hipStream_t st);
+hipError_t launch_mesh_reg_bwd(const MeshTopoDev& t, const float* verts, const float* unit, const float* gout, int B, float lam_lap,
+                               float lam_nc, float* gverts, hipStream_t st);
+
 // small-batch fully connected layer (mlp.hip): y[B][O] = act(BN1d?(x[B][I] W[O][I]^T + b)); gamma == nullptr: no batch-norm
 // sigmoid(z) for the swish / sigmoid activations of EfficientNet (batch-norm + swish passes, squeeze-excite gates): v_exp_f32 of z log2(e) and
 // v_rcp_f32 -- ~4 instructions where expf + an IEEE division are ~30, and the swish passes of csrc/bn.hip were bound by exactly those

@@ -139,6 +139,9 @@ class Model(nn.Module):
         self.hand_encoder = HandEncoder(hand_model=hand_model, ncomps=self.ncomps, in_dim=self.features_dim,
                                         ifRender=ifRender, use_mean_shape=use_mean_shape)
         self.register_buffer("mano_face", self._mano_face_i32.unsqueeze(0).to(torch.int16), persistent=False)
+        # the tables of the loss terms "triangle" / "normal_consistency" (ops.mesh_regularizers): built here, once -- creation allocates and
+        # copies, which a captured step must not do
+        self._mesh_topo = ops.MeshTopology(self._mano_face_i32, 778)
         self.ifRender, self.ifLight, self.aa_factor, self.image_size = ifRender, ifLight, aa_factor, image_size
         self.soft_silhouette, self.soft_sil_sigma = bool(soft_silhouette), float(soft_sil_sigma)
         if ifRender:
@@ -256,6 +259,7 @@ class Model(nn.Module):
                 outputs["re_sil_soft"] = ops.soft_silhouette(self.renderer_p3d, verts_cam, cam, self.soft_sil_sigma)
         outputs["mano_faces"] = self.mano_face.expand(images.shape[0], -1, -1)           # a view (the reference repeats)
         outputs["_faces_i32"] = self._mano_face_i32
+        outputs["_mesh_topo"] = self._mesh_topo
         return outputs
 
     def _nimble_tail(self, dat_name, mode_train, images, outputs, light_params, Ks, root_xyz):
@@ -286,4 +290,5 @@ class Model(nn.Module):
                 outputs["re_sil_soft"] = ops.soft_silhouette(self.renderer_p3d, verts_cam, cam, self.soft_sil_sigma)
         outputs["mano_faces"] = self.mano_face.expand(B, -1, -1)
         outputs["_faces_i32"] = self._mano_face_i32
+        outputs["_mesh_topo"] = self._mesh_topo
         return outputs

@@ -421,6 +421,71 @@ def soft_sil_losses(alpha, segms_gt, lam_sil, lam_iou):
     return _SoftSilLosses.apply(alpha, segms_gt, float(lam_sil), float(lam_iou))
 
 
+class MeshTopology:
+    """The tables of a triangle mesh the regularisers read (include/hifihr.h "Mesh regularisers"): neighbours, the (v0, v1, a, b) records of
+    every pair of faces on one edge, and the vertex -> record list.  Built, checked and uploaded ONCE: creation allocates and copies, so it
+    belongs outside a captured step.  faces [F, 3] (host array or tensor); raises HifihrError when the library refuses them."""
+
+    def __init__(self, faces, num_verts):
+        self.lib = get_lib()
+        if torch.is_tensor(faces):
+            faces = faces.detach().cpu().numpy()
+        self.h = self.lib.mesh_topology_create(faces, num_verts)
+        self.V, self.E, self.Q = self.lib.mesh_topology_counts(self.h)
+
+    def __del__(self):
+        try:
+            self.lib.mesh_topology_destroy(self.h)
+        except Exception:
+            pass
+
+
+MESH_REG_TERMS = ("triangle", "normal_consistency")
+_TOPO_CACHE = {}
+
+
+def mesh_topology_of(faces, V):
+    """The MeshTopology of a faces tensor [F, 3], built on first use and kept per tensor (as _vertex_face_csr keeps its table): for outputs
+    that do not come from models.Model, which builds its own at construction."""
+    require_cuda(faces)
+    key = (faces.data_ptr(), int(faces.shape[0]), int(V), str(faces.device))
+    hit = _TOPO_CACHE.get(key)
+    if hit is None:
+        hit = _TOPO_CACHE[key] = MeshTopology(faces.reshape(-1, 3), V)
+    return hit
+
+
+class _MeshReg(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, topo, verts, lam_lap, lam_nc):
+        require_cuda(verts)
+        verts = verts.contiguous().float()
+        assert verts.dim() == 3 and verts.shape[1] == topo.V and verts.shape[2] == 3, (verts.shape, topo.V)
+        lib = topo.lib
+        unit = torch.empty_like(verts)
+        partial = torch.empty(lib.mesh_reg_partial_floats(topo.h, verts.shape[0]), device=verts.device)
+        out = torch.empty(2, device=verts.device)
+        PROFILE.bracket("mesh_reg_fwd", lambda: lib.mesh_reg_fwd(topo.h, verts, lam_lap, lam_nc, unit, partial, out))
+        ctx.topo, ctx.lams = topo, (lam_lap, lam_nc)
+        ctx.save_for_backward(verts, unit)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        verts, unit = ctx.saved_tensors
+        gverts = torch.empty_like(verts)
+        g = gout.contiguous()
+        PROFILE.bracket("mesh_reg_bwd", lambda: ctx.topo.lib.mesh_reg_bwd(ctx.topo.h, verts, unit, g, ctx.lams[0], ctx.lams[1], gverts))
+        return None, gverts, None, None
+
+
+def mesh_regularizers(topo: MeshTopology, verts, lam_lap, lam_nc):
+    """[2] = (lam_lap * uniform-Laplacian smoothing, lam_nc * normal consistency) of verts [B, V, 3] on the topology `topo`: PyTorch3D's
+    mesh_laplacian_smoothing(method="uniform") and mesh_normal_consistency [recalled], as include/hifihr.h defines them; one kernel pair
+    (csrc/mesh_reg.hip), the gradient goes to verts.  A weight of exactly 0 gives that term as 0."""
+    return _MeshReg.apply(topo, verts, float(lam_lap), float(lam_nc))
+
+
 # ------------------------------------------------------------------------------------------------
 # convolution on the f32 matrix cores (tensors are logical NCHW in channels_last memory format = physical NHWC)
 # ------------------------------------------------------------------------------------------------

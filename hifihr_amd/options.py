@@ -26,6 +26,9 @@ _DEFAULTS = dict(
     # opt-in gradient guard of the fused Adam step (hifihr_amd/optim.py FusedAdam(max_grad_norm=...)): the global L2 norm the gradient is
     # clipped to, and a step whose gradient holds a NaN / inf is skipped.  0 = off; inf = the skip alone
     max_grad_norm=0.0,
+    # weight of the opt-in term "normal_consistency" (hifihr_amd/ops.py mesh_regularizers; "triangle" reads the reference's
+    # lambda_laplacian above): the weight of PyTorch3D's mesh-fitting tutorial [recalled] -- a starting point, not a tuned value
+    lambda_normal_consistency=0.01,
 )
 
 # lambda values of reference config/FreiHAND/full_rhd_freihand.json, used by the

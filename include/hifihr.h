@@ -270,6 +270,57 @@ int hifihr_soft_sil_loss_bwd(const float* alpha_d, const void* mask_d, int mask_
                              float lam_sil, float lam_iou, float* galpha_d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mesh regularisers (csrc/mesh_reg.hip): `triangle` and `normal_consistency` in one kernel pair.
+ * `triangle` replaces reference losses.py:421-429, lambda_laplacian * mesh_laplacian_smoothing(Meshes(verts, faces), method="uniform");
+ * `normal_consistency` is PyTorch3D's mesh_normal_consistency, which the reference does not use.  Both PyTorch3D functions are [recalled]:
+ * parity with PyTorch3D is unpinned, the kernels are held to the definitions below (tests/mesh_reg_ref.py restates them in float64).
+ *
+ * Topology, built once on the host from faces[F][3] and V:
+ *   edges    the unique unordered vertex pairs of the faces; E = their count
+ *   N(i)     the distinct neighbours of vertex i in ascending order; deg(i) = |N(i)|
+ *   quads    for every edge (v0 < v1): the opposite vertex of each face that contains the edge, in ascending face order; every unordered
+ *            pair (a, b) of that list, a from the lower-indexed face, is one record (v0, v1, a, b); Q = the record count.  A boundary edge
+ *            gives no record, an edge shared by three faces gives three.  Records are ordered by (v0, v1), then by the two faces.
+ * triangle, for verts[B][V][3]:
+ *   d_i = (1 / deg(i)) sum over j in N(i) of v_j  -  v_i;   deg(i) = 0: d_i = -v_i (PyTorch3D's -1 diagonal on every row [recalled])
+ *   lap = (1 / (B V)) sum_b sum_i ||d_i||_2;   out[0] = lam_lap lap;   the subgradient at d_i = 0 is 0 (as torch.norm's)
+ * normal_consistency, per quad record:
+ *   e = v1 - v0, n0 = e x (a - v0), n1 = -(e x (b - v0)), cos = n0 . n1 / (max(||n0||, 1e-8) max(||n1||, 1e-8))
+ *   nc = (1 / (B Q)) sum_b sum_q (1 - cos), 0 when Q = 0;   out[1] = lam_nc nc;   the value does not depend on face winding.
+ *   A record with a norm at or below the clamp contributes 1 - cos to the value and NO gradient (a stated piecewise choice).
+ * A weight that is exactly 0 writes 0 for its term; that term gets no gradient and its work is skipped.
+ * Gradient: to verts only.  With u_i = d_i / ||d_i|| (0 at d_i = 0):  d lap / d v_k = (1 / (B V)) (-u_k + sum over i in N(k) of u_i / deg(i))
+ * (adjacency is symmetric).  For a quad, c = cos, g0 = -(n1^ - c n0^) / ||n0|| and likewise g1 are the gradients of 1 - cos with respect
+ * to n0 and n1; for n = e x p the gradient with respect to p is g x e and with respect to e it is p x g; they are distributed onto
+ * v0, v1, a, b with the sign of n1's definition.
+ *
+ * hifihr_mesh_topology_create builds the neighbour list (compressed rows), the quad table and the vertex -> (quad, role) list, checks
+ * them and uploads them: the kernels take every index from these tables, no index is computed from a float.
+ *   Refused (NULL returned, hifihr_last_error() says why): faces_host NULL, F <= 0, V <= 0, an index outside [0, V), a face that repeats a
+ *   vertex, 4 Q >= 2^31.  A vertex that no face references is accepted (deg = 0).
+ * hifihr_mesh_topology_destroy(NULL) is accepted.  hifihr_mesh_topology_counts writes V, E, Q (each pointer may be NULL); a NULL handle is
+ *   refused.  hifihr_mesh_reg_partial_floats(NULL, .) and (h, B < 0) return 0; the size never decreases with B.
+ * Compute entries -- refused (HIFIHR_EINVAL, nothing launched, nothing written): a NULL handle or pointer, B < 0, B V 3 >= 2^31, a weight
+ *   that is not finite.  Accepted: B == 0 is a no-op (nothing launched, nothing written).
+ * Precondition, NOT checked: finite vertices.  A NaN or an Inf gives unspecified values and gradients, never an out-of-range access.
+ * Overwritten: hifihr_mesh_reg_fwd writes EVERY element of unit_d[B][V][3] (= u_i, which the backward reads; zeros when lam_lap == 0),
+ *   of partial_d[hifihr_mesh_reg_partial_floats(h, B)] and of out_d[2].  hifihr_mesh_reg_bwd OVERWRITES every element of
+ *   gverts_d[B][V][3]; it takes the gradients of the two terms as the DEVICE vector gout_d[2] and must be given the forward's weights.
+ * Repeatable: no atomics.  Per-workgroup partial sums are folded by one workgroup in a fixed order, in double; in the backward every
+ *   element has exactly one writer that sums in table order: out_d, unit_d and gverts_d have the same bits on every call.
+ * No allocation and no synchronisation inside the compute entries: they can be captured into a hipGraph (creation allocates and copies:
+ *   do it outside a capture). */
+typedef struct hifihr_mesh_topology hifihr_mesh_topology_t;
+hifihr_mesh_topology_t* hifihr_mesh_topology_create(const int32_t* faces_host, int F, int V);
+int hifihr_mesh_topology_destroy(hifihr_mesh_topology_t* h);
+int hifihr_mesh_topology_counts(const hifihr_mesh_topology_t* h, int* V, int* E, int* Q);
+size_t hifihr_mesh_reg_partial_floats(const hifihr_mesh_topology_t* h, int B);
+int hifihr_mesh_reg_fwd(const hifihr_mesh_topology_t* h, const float* verts_d, int B, float lam_lap, float lam_nc, float* unit_d,
+                        float* partial_d, float* out_d, void* stream);
+int hifihr_mesh_reg_bwd(const hifihr_mesh_topology_t* h, const float* verts_d, const float* unit_d, const float* gout_d, int B,
+                        float lam_lap, float lam_nc, float* gverts_d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Texture-PCA decode (csrc/texpca.hip): tex[b][n] = mean[n] (or 0 when NULL) + sum_k coef[b][k] basis[k][n], K <= 32, n % 4 == 0.
  * The texture half of the NIMBLE layer as the reference consumes it (models_res_nimble.py:57,133-142: texture_params [B,10] -> the
  * hand's texture).  NIMBLE's own basis is not available: the caller supplies one (n = 778 * 3 vertex

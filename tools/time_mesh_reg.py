@@ -1,0 +1,164 @@
+#!/usr/bin/env python3
+"""Time the mesh regularisers (hifihr_mesh_reg_fwd / _bwd: the loss terms "triangle" + "normal_consistency") at B = 32 on the MANO
+topology, and the captured BASELINE config-2 training step with the two terms added against the step without them -- in this tree and,
+with --parent, in a checkout of the parent commit (built: its hifihr_amd/libhifihr.so exists) in the same run.
+
+    python tools/time_mesh_reg.py [--parent PATH] [--out profiles/mesh_reg_time.txt]
+
+Kernel figures: HIP events around `--repeats` back-to-back calls after `--warmup` calls, the median of `--rounds` such windows, per call.
+Step figures: every step is captured and timed in a process of its own (the same script text in either tree, so both are measured the
+same way), HIP events around `--steps` replays, the median of `--rounds` windows, per step; the processes run one after the other, the
+whole sequence `--alternations` times.  There is no pass threshold: the file is the record."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# runs with cwd = the tree to measure; uses only what both this tree and its parent have
+STEP_SCRIPT = r"""
+import json, statistics, sys
+sys.path.insert(0, ".")
+import torch
+from hifihr_amd import options, synth
+from hifihr_amd.losses import LossFunction
+from hifihr_amd.mano_tables import synthetic_mano_tables
+from hifihr_amd.models import Model
+from hifihr_amd.optim import FlatParams, FusedAdam
+from hifihr_amd.traineval import GraphedTrainStep, data_dic
+B, extra, warmup, steps, rounds = int(sys.argv[1]), [k for k in sys.argv[2].split(",") if k], int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
+dev, tables = torch.device("cuda"), synthetic_mano_tables(0)
+torch.cuda.set_stream(torch.cuda.Stream())
+base = options.baseline_config2_args(train_batch=B)
+args = options.baseline_config2_args(train_batch=B, losses=base.losses + extra)
+torch.manual_seed(0)
+model = Model(True, dev, False, "mano", False, "res18", mano_tables=tables).to(dev).train()
+opt = FusedAdam(FlatParams(model), lr=1e-6)
+ex = data_dic(synth.make_batch(model.hand_layer.handle, model.renderer_p3d, B, device=dev), "FreiHand", "training", args, device=dev)
+g = GraphedTrainStep(model, LossFunction(), opt, ex, args, warmup=3)
+for _ in range(warmup):
+    g()
+torch.cuda.synchronize()
+out = []
+for _ in range(rounds):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        g()
+    b.record()
+    b.synchronize()
+    out.append(a.elapsed_time(b) / steps)
+print("STEP_MS " + json.dumps(out))
+"""
+
+
+def gpu_ms(fn, warmup, repeats, rounds):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(rounds):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(repeats):
+            fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) / repeats)
+    return statistics.median(out), min(out), max(out)
+
+
+def kernel_rows(cli, lines):
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    from hifihr_amd import ops
+    from hifihr_amd.mano_tables import synthetic_mano_tables
+    tables, B = synthetic_mano_tables(0), cli.batch
+    topo = ops.MeshTopology(tables.faces, 778)
+    lib = topo.lib
+    v0 = torch.as_tensor(np.asarray(tables.v_template), dtype=torch.float32)
+    verts = (v0[None] + 0.002 * torch.randn(B, 778, 3, generator=torch.Generator().manual_seed(0))).cuda().contiguous()
+    unit, gverts = torch.empty_like(verts), torch.empty_like(verts)
+    partial = torch.empty(lib.mesh_reg_partial_floats(topo.h, B), device="cuda")
+    out, gout = torch.empty(2, device="cuda"), torch.ones(2, device="cuda")
+    lines.append(f"kernels at B = {B}, MANO topology (V = {topo.V}, E = {topo.E}, Q = {topo.Q}), lam_lap = 0.1, lam_nc = 0.01")
+    rows = [("mesh_reg_fwd (vertices + quads, finish), both terms", lambda: lib.mesh_reg_fwd(topo.h, verts, 0.1, 0.01, unit, partial, out)),
+            ("mesh_reg_bwd, both terms", lambda: lib.mesh_reg_bwd(topo.h, verts, unit, gout, 0.1, 0.01, gverts)),
+            ("mesh_reg_fwd, triangle alone", lambda: lib.mesh_reg_fwd(topo.h, verts, 0.1, 0.0, unit, partial, out)),
+            ("mesh_reg_bwd, triangle alone", lambda: lib.mesh_reg_bwd(topo.h, verts, unit, gout, 0.1, 0.0, gverts)),
+            ("mesh_reg_fwd, normal_consistency alone", lambda: lib.mesh_reg_fwd(topo.h, verts, 0.0, 0.01, unit, partial, out)),
+            ("mesh_reg_bwd, normal_consistency alone", lambda: lib.mesh_reg_bwd(topo.h, verts, unit, gout, 0.0, 0.01, gverts))]
+    for name, fn in rows:
+        med, lo, hi = gpu_ms(fn, cli.warmup, cli.repeats, cli.rounds)
+        lines.append(f"  MI355X  {name:58s} {med:9.4f}  [{lo:.4f} .. {hi:.4f}]")
+    lines.append("")
+
+
+def step_ms(tree, cli, extra):
+    """One process per measurement: a fresh child (never a replaced program) that captures the step and prints its windows."""
+    r = subprocess.run([sys.executable, "-c", STEP_SCRIPT, str(cli.batch), ",".join(extra), str(cli.warmup), str(cli.steps), str(cli.rounds)],
+                       cwd=tree, capture_output=True, text=True, timeout=cli.child_timeout)
+    rows = [ln for ln in r.stdout.splitlines() if ln.startswith("STEP_MS ")]
+    if r.returncode != 0 or not rows:
+        raise RuntimeError(f"the step measurement in {tree} ended with {r.returncode}:\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}")
+    return json.loads(rows[-1][len("STEP_MS "):])
+
+
+def step_rows(cli, lines):
+    runs = [("this tree, config 2 as it is", REPO, []), ("this tree, config 2 + triangle + normal_consistency", REPO, ["triangle", "normal_consistency"])]
+    if cli.parent:
+        runs.insert(0, ("parent commit, config 2 as it is", os.path.abspath(cli.parent), []))
+    samples = {tag: [] for tag, _, _ in runs}
+    for _ in range(cli.alternations):
+        for tag, tree, extra in runs:
+            samples[tag] += step_ms(tree, cli, extra)
+    lines.append(f"captured training step, ResNet-18 + MANO + render, B = {cli.batch}: ms/step, median [min .. max] of {cli.alternations} x {cli.rounds} "
+                 f"windows of {cli.steps} replays, one process per measurement, the rows alternated")
+    med = {}
+    for tag, v in samples.items():
+        med[tag] = statistics.median(v)
+        lines.append(f"  MI355X  {tag:58s} {med[tag]:9.4f}  [{min(v):.4f} .. {max(v):.4f}]")
+    a, b = med[runs[-2][0]], med[runs[-1][0]]
+    lines.append(f"  cost of the two terms: {b - a:+.4f} ms/step ({100 * (b - a) / a:+.2f} %)")
+    if cli.parent:
+        p = med[runs[0][0]]
+        lines.append(f"  this tree without the terms against the parent commit: {a - p:+.4f} ms/step ({100 * (a - p) / p:+.2f} %)")
+    else:
+        lines.append("  (no --parent tree was given: the parent commit was not measured)")
+    lines.append("")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "mesh_reg_time.txt"))
+    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--alternations", type=int, default=2)
+    ap.add_argument("--child-timeout", type=int, default=240)
+    cli = ap.parse_args()
+    import torch
+    assert torch.cuda.is_available(), "the timings are GPU timings: no device, no figure"
+    argv = [a if not (i > 0 and sys.argv[1:][i - 1] in ("--parent", "--out")) else "<path>" for i, a in enumerate(sys.argv[1:])]
+    lines = ["mesh regularisers (triangle, normal_consistency): time per call / per step (ms), median [min .. max]",
+             "command: python tools/time_mesh_reg.py " + " ".join(argv),
+             f"device: {torch.cuda.get_device_name(0)}; warm-up {cli.warmup}, {cli.repeats} calls per window, {cli.rounds} windows", ""]
+    kernel_rows(cli, lines)
+    step_rows(cli, lines)
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(cli.out)), exist_ok=True)
+    with open(cli.out, "w") as fh:
+        fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
