@@ -142,6 +142,11 @@ class HifihrLib:
         c.hifihr_lpips_tap_partial_floats.argtypes = [c_int]
         c.hifihr_lpips_tap_partial_floats.restype = c_size_t
         c.hifihr_lpips_tap.argtypes = [_c_float_p] * 3 + [c_int] * 4 + [_c_float_p, _c_float_p, c_void_p]
+        c.hifihr_lpips_tap_bwd.argtypes = [_c_float_p] * 4 + [c_int] * 4 + [_c_float_p, c_void_p]
+        c.hifihr_lpips_tap_bwd_relu.argtypes = [_c_float_p] * 4 + [c_int] * 4 + [_c_float_p, c_void_p]
+        c.hifihr_lpips_maxpool_fwd.argtypes = [_c_float_p] + [c_int] * 4 + [_c_float_p, c_void_p]
+        c.hifihr_lpips_maxpool_bwd.argtypes = [_c_float_p, _c_float_p] + [c_int] * 4 + [_c_float_p, c_void_p]
+        c.hifihr_image_scale_to_nhwc4_bwd.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, _c_float_p, c_void_p]
         c.hifihr_geom_loss_fwd.argtypes = [_c_float_p] * 6 + [_c_int_p] + [c_int] * 7 + [_c_float_p] * 3 + [c_void_p]
         c.hifihr_geom_loss_bwd.argtypes = [_c_float_p] * 6 + [_c_int_p] * 3 + [c_int] * 7 + [_c_float_p] * 6 + [c_void_p]
         c.hifihr_photo_loss_partial_floats.argtypes = []
@@ -986,6 +991,26 @@ class HifihrLib:
         """val[b] (+)= mean over pixels of sum_c w_c (n0_c - n1_c)^2 on two channels-last maps [B][HW][C] (include/hifihr.h)."""
         self.check(self.c.hifihr_lpips_tap(_fp(f0), _fp(f1), _fp(w), B, HW, C, int(bool(accumulate)), _fp(partial), _fp(val), _stream_of(f0)),
                    "hifihr_lpips_tap")
+
+    def lpips_tap_bwd(self, f0, f1, w, gval, B, HW, C, gf0, accumulate=False, relu=False):
+        """gf0[b] (+)= gval[b] / HW * d tap / d f0 on two channels-last maps [B][HW][C]; f1 is the target (include/hifihr.h).
+        relu: f0 is a ReLU's output and the stored sum is multiplied by [f0 > 0] (hifihr_lpips_tap_bwd_relu)."""
+        fn, name = (self.c.hifihr_lpips_tap_bwd_relu, "hifihr_lpips_tap_bwd_relu") if relu else (self.c.hifihr_lpips_tap_bwd, "hifihr_lpips_tap_bwd")
+        self.check(fn(_fp(f0), _fp(f1), _fp(w), _fp(gval), B, HW, C, int(bool(accumulate)), _fp(gf0), _stream_of(f0)), name)
+
+    def lpips_maxpool_fwd(self, x, N, H, W, C, y):
+        """nn.MaxPool2d(3, 2): x[N, H, W, C] -> y[N, OH, OW, C]; tapless (the backward recomputes the winners from x)."""
+        self.check(self.c.hifihr_lpips_maxpool_fwd(_fp(x), N, H, W, C, _fp(y), _stream_of(x)), "hifihr_lpips_maxpool_fwd")
+
+    def lpips_maxpool_bwd(self, gy, x, N, H, W, C, dx):
+        """dx[N, H, W, C] (overwritten) from gy[N, OH, OW, C] and the pool's saved input x: a gather, first maximum wins."""
+        self.check(self.c.hifihr_lpips_maxpool_bwd(_fp(gy), _fp(x), N, H, W, C, _fp(dx), _stream_of(x)), "hifihr_lpips_maxpool_bwd")
+
+    def image_scale_to_nhwc4_bwd(self, g4, gimg, scale3):
+        """gimg[B, 3, H, W] = g4[B, H, W, :3] / scale[c]: the backward of image_scale_to_nhwc4."""
+        B, _, H, W = gimg.shape
+        sc = (c_float * 3)(*[float(v) for v in scale3])
+        self.check(self.c.hifihr_image_scale_to_nhwc4_bwd(_fp(g4), _fp(gimg), B, H, W, sc, _stream_of(gimg)), "hifihr_image_scale_to_nhwc4_bwd")
 
     # ---- SSIM ----------------------------------------------------------
     def ssim_partial_count(self, planes, H, W):

@@ -707,6 +707,12 @@ int hifihr_conv2d_bwd_data(const float* dy, const float* w, float* dx, float* wt
                            int R, int S, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
   if (!dy || !w || !dx || !wt_scratch || !conv_dims_ok(N, H, W, C, K, R, S, stride, pad) || K % 4 || (K % 16 && stride != 1))
     return fail(HIFIHR_EINVAL, "hifihr_conv2d_bwd_data: bad argument (K % 4 == 0; K % 16 == 0 when stride > 1)");
+  // a strided filter of more than 62 taps (the 11x11 / stride 4 AlexNet stem): the implicit-GEMM gather does not take it; a direct
+  // gather reads w itself (csrc/lpips.hip), no transpose
+  if (stride > 1 && R * S > 62 && hifihr::lpips_stem_bwd_data_supported(N, H, W, C, K, R, S, stride, pad)) {
+    HIP_TRY(hifihr::launch_lpips_stem_bwd_data(dy, w, dx, N, H, W, C, K, R, S, stride, pad, (hipStream_t)stream));
+    return HIFIHR_OK;
+  }
   HIP_TRY(hifihr::launch_weight_transpose(w, wt_scratch, K, R * S, C, (hipStream_t)stream));
   HIP_TRY(hifihr::launch_conv_igemm(conv_dgrad_geom(N, H, W, C, K, R, S, stride, pad), dy, wt_scratch, nullptr, dx, nullptr, ws, ws_bytes, (hipStream_t)stream));
   return HIFIHR_OK;
@@ -852,6 +858,45 @@ int hifihr_lpips_tap(const float* f0, const float* f1, const float* w, int B, in
   if (!f0 || !f1 || !w || !partial || !val || B <= 0 || B > 65535 || HW <= 0 || C < 4 || C % 4 != 0 || C > hifihr::lpips_tap_max_channels())
     return fail(HIFIHR_EINVAL, "hifihr_lpips_tap: bad argument (C % 4 == 0, 4 <= C <= %d; B <= 65535)", hifihr::lpips_tap_max_channels());
   HIP_TRY(hifihr::launch_lpips_tap(f0, f1, w, B, HW, C, accumulate ? 1 : 0, partial, val, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+// ---- LPIPS backward (lpips.hip): the gradient with respect to the first image ----
+static int lpips_tap_bwd_entry(const char* name, const float* f0, const float* f1, const float* w, const float* gval, int B, int HW, int C,
+                               int accumulate, int relu_mask, float* gf0, void* stream) {
+  if (!f0 || !f1 || !w || !gval || !gf0 || B <= 0 || B > 65535 || HW <= 0 || C < 4 || C % 4 != 0 || C > hifihr::lpips_tap_max_channels())
+    return fail(HIFIHR_EINVAL, "%s: bad argument (C %% 4 == 0, 4 <= C <= %d; B <= 65535)", name, hifihr::lpips_tap_max_channels());
+  HIP_TRY(hifihr::launch_lpips_tap_bwd(f0, f1, w, gval, B, HW, C, accumulate ? 1 : 0, relu_mask, gf0, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+int hifihr_lpips_tap_bwd(const float* f0, const float* f1, const float* w, const float* gval, int B, int HW, int C, int accumulate, float* gf0,
+                         void* stream) {
+  return lpips_tap_bwd_entry("hifihr_lpips_tap_bwd", f0, f1, w, gval, B, HW, C, accumulate, 0, gf0, stream);
+}
+int hifihr_lpips_tap_bwd_relu(const float* f0, const float* f1, const float* w, const float* gval, int B, int HW, int C, int accumulate, float* gf0,
+                              void* stream) {
+  return lpips_tap_bwd_entry("hifihr_lpips_tap_bwd_relu", f0, f1, w, gval, B, HW, C, accumulate, 1, gf0, stream);
+}
+
+int hifihr_lpips_maxpool_fwd(const float* x, int N, int H, int W, int C, float* y, void* stream) {
+  if (!x || !y || N <= 0 || C < 4 || C % 4 != 0 || H < 3 || W < 3)
+    return fail(HIFIHR_EINVAL, "hifihr_lpips_maxpool_fwd: bad argument (C % 4 == 0; H, W >= 3)");
+  HIP_TRY(hifihr::launch_lpips_maxpool_fwd(x, N, H, W, C, y, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_lpips_maxpool_bwd(const float* gy, const float* x, int N, int H, int W, int C, float* dx, void* stream) {
+  if (!gy || !x || !dx || N <= 0 || C < 4 || C % 4 != 0 || H < 3 || W < 3)
+    return fail(HIFIHR_EINVAL, "hifihr_lpips_maxpool_bwd: bad argument (C % 4 == 0; H, W >= 3)");
+  HIP_TRY(hifihr::launch_lpips_maxpool_bwd(gy, x, N, H, W, C, dx, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_image_scale_to_nhwc4_bwd(const float* g4, float* gimg, int B, int H, int W, const float* scale3_host, void* stream) {
+  if (!g4 || !gimg || !scale3_host || B <= 0 || H <= 0 || W <= 0) return fail(HIFIHR_EINVAL, "hifihr_image_scale_to_nhwc4_bwd: bad argument");
+  for (int c = 0; c < 3; ++c)
+    if (!(scale3_host[c] != 0.f)) return fail(HIFIHR_EINVAL, "hifihr_image_scale_to_nhwc4_bwd: scale[%d] is zero or NaN", c);
+  HIP_TRY(hifihr::launch_image_scale_to_nhwc4_bwd(g4, gimg, B, H, W, scale3_host, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 

@@ -280,6 +280,17 @@ int lpips_tap_max_channels();
 size_t lpips_tap_partial_floats(int B);
 hipError_t launch_lpips_tap(const float* f0, const float* f1, const float* w, int B, int HW, int C, int accumulate, float* partial, float* val,
                             hipStream_t st);
+// ... and their backward (gradient with respect to the first image): one tap, MaxPool2d(3, 2) with a tapless gather backward, the repack
+hipError_t launch_lpips_tap_bwd(const float* f0, const float* f1, const float* w, const float* gval, int B, int HW, int C, int accumulate,
+                                int relu_mask, float* gf0, hipStream_t st);
+hipError_t launch_lpips_maxpool_fwd(const float* x, int N, int H, int W, int C, float* y, hipStream_t st);
+hipError_t launch_lpips_maxpool_bwd(const float* gy, const float* x, int N, int H, int W, int C, float* dx, hipStream_t st);
+hipError_t launch_image_scale_to_nhwc4_bwd(const float* g4, float* gimg, int B, int H, int W, const float* scale3, hipStream_t st);
+// backward-data of a strided filter with more than 62 taps (the 11x11 / stride 4 AlexNet stem), which launch_conv_igemm does not take:
+// a direct gather from w[K][R][S][C] itself; hifihr_conv2d_bwd_data routes such a geometry here
+bool lpips_stem_bwd_data_supported(int N, int H, int W, int C, int K, int R, int S, int stride, int pad);
+hipError_t launch_lpips_stem_bwd_data(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
+                                      hipStream_t st);
 
 struct SsimWindow {
   float g[11];      // normalised 1-D gaussian (sigma 1.5), as pytorch_ssim.gaussian builds it

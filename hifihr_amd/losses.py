@@ -5,7 +5,8 @@ ONE path: the step's terms run as fused HIP kernels -- SSIM (csrc/ssim.hip), the
 edge-length / shape / pose terms (csrc/losses.hip: two launches per group instead of ~250 ATen launches) -- on GPU tensors; a CPU
 tensor raises (no fallback).  joint_2d / bone_direc / bone_direc_3d: one more kernel pair (round 3).  triangle / normal_consistency (the
 reference's uniform-Laplacian term and, not in the reference, its usual partner): one kernel pair (csrc/mesh_reg.hip).  sil_soft / iou_soft (not in the
-reference: `sil` and `iou` on the model's opt-in differentiable silhouette, outputs['re_sil_soft']): one kernel pair (csrc/soft_sil.hip).  The rarely used terms (mscale, scale,
+reference: `sil` and `iou` on the model's opt-in differentiable silhouette, outputs['re_sil_soft']): one kernel pair (csrc/soft_sil.hip).  lpips (not in the
+reference: LPIPS(alex), the evaluation pass's texture metric, as an opt-in loss): hifihr_amd/lpips.py with its HIP backward (csrc/lpips.hip).  The rarely used terms (mscale, scale,
 iou, mtex and the self-supervised `*_self` terms) are a handful of torch ops on the same GPU tensors.  The torch restatement of the whole function that the tests
 compare against is oracle/loss_oracle.py (pinned by the reference's own LossFunction.__call__, tests/golden/loss_dict.npz).
 """
@@ -24,7 +25,7 @@ _BONES = [(0, 1), (1, 2), (2, 3), (3, 4), (0, 5), (5, 6), (6, 7), (7, 8), (0, 9)
 # every name LossFunction.__call__ can produce (a name outside it in `losses` is ignored here and stops traineval's step with a KeyError)
 TERMS = ("joint_3d", "vert_3d", "edge_length", "mshape", "mpose", "joint_2d", "bone_direc", "bone_direc_3d", "mscale", "scale", "texture",
          "mrgb", "ssim_tex", "sil", "texture_self", "mrgb_self", "ssim_tex_self", "perceptual", "iou", "sil_soft", "iou_soft", "triangle",
-         "normal_consistency", "mtex")
+         "normal_consistency", "lpips", "mtex")
 
 _BONE_IDX = {}
 
@@ -66,10 +67,27 @@ _GEOM_BRANCH = os.environ.get("HIFIHR_GEOM_BRANCH", "0") != "0"
 
 
 class LossFunction:
-    def __init__(self, perceptual=None):
+    def __init__(self, perceptual=None, lpips=None):
         # PerceptualLoss instance; None = built on first use (hifihr_amd/perceptual.py: seeded torchvision-style
         # initialisation unless the caller loads VGG19 weights -- they cannot be downloaded offline)
         self.perceptual_loss = perceptual
+        # LPIPS(differentiable=True) instance of the opt-in term `lpips`; None = built on first use (args.lpips_weights when given, else the
+        # seeded weights and one warning)
+        self.lpips_loss = lpips
+
+    def _lpips_module(self, args, device):
+        if self.lpips_loss is None:
+            from .lpips import LPIPS, load_lpips_weights
+            m = LPIPS(net="alex", differentiable=True)
+            paths = getattr(args, "lpips_weights", None)
+            if paths:
+                load_lpips_weights(m, *([paths] if isinstance(paths, str) else paths))
+            else:
+                import warnings
+                warnings.warn("loss term 'lpips': no lpips_weights given -- the AlexNet trunk and the lin layers carry SEEDED random weights, "
+                              "not the calibrated metric's (hifihr_amd/lpips.py)", stacklevel=3)
+            self.lpips_loss = m.to(device)
+        return self.lpips_loss
 
     def _fused_geometry(self, examples, outputs, loss_used, args, loss_dic):
         """joint_3d / vert_3d / edge_length / mshape / mpose in one kernel pair (csrc/losses.hip)."""
@@ -181,6 +199,13 @@ class LossFunction:
             seg = examples["segms_gt"].unsqueeze(1)
             loss_dic["perceptual"] = args.lambda_percep * self.perceptual_loss(
                 outputs["re_img"] * seg + examples["imgs"] * (1 - seg), examples["imgs"])
+        if "lpips" in loss_used:
+            # not in the reference (its LPIPS is an evaluation metric): the metric the evaluation pass reports, as a loss on the composite the
+            # `perceptual` term uses; images in [0, 1] (normalize=True), the target a constant (hifihr_amd/lpips.py, differentiable=True)
+            seg = examples["segms_gt"].unsqueeze(1)
+            fn = self._lpips_module(args, outputs["re_img"].device)
+            loss_dic["lpips"] = args.lambda_lpips * fn(outputs["re_img"] * seg + examples["imgs"] * (1 - seg), examples["imgs"],
+                                                       normalize=True).mean()
         if "iou" in loss_used:
             loss_dic["iou"] = args.lambda_iou * iou(outputs["re_sil"], examples["segms_gt"].unsqueeze(1).float())
         if "sil_soft" in loss_used or "iou_soft" in loss_used:

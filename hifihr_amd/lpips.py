@@ -1,4 +1,4 @@
-"""LPIPS(net="alex"), version 0.1, forward only: the perceptual texture metric of the reference's evaluation pass
+"""LPIPS(net="alex"), version 0.1: the perceptual texture metric of the reference's evaluation pass
 (`lpips.LPIPS(net="alex")` built at reference train_hrnet.py:563, called at :158 and averaged at :259-264).
 
 Restated from the published definition (Zhang et al. 2018, the `lpips` package's v0.1 linear calibration):
@@ -18,8 +18,14 @@ difference and the pixel mean.  No ATen kernel runs between the input and the re
 The convolutions run inside ops.conv_precision(self.conv_precision): "reference" (default, the direct kernels: this is a
 metric) or "fast" (Winograd for the three 3x3 layers).
 
-Forward-only: an input that requires grad under enabled grad raises NotImplementedError (there is no backward and no silent
-fallback); a CPU tensor raises; net != "alex" raises NotImplementedError.
+Forward-only by default: an input that requires grad under enabled grad raises NotImplementedError (no silent fallback); a CPU
+tensor raises; net != "alex" raises NotImplementedError.
+
+LPIPS(differentiable=True) is the same module with a backward for the FIRST image (the opt-in loss term `lpips` of losses.py): in0 may
+require grad, in1 is the target and may not (NotImplementedError).  The value is the forward-only module's bit for bit -- ONE custom
+autograd.Function (ops._LPIPSAlex) runs the identical launches on the batch of 2N and keeps the maps; its backward slices in0's half out
+of them, so the target's half passes through no backward kernel: per layer lpips_tap_bwd (with the layer's ReLU mask in its store),
+backward-data with the frozen weights, and the tapless gather backward of the pools (csrc/lpips.hip).  Parameters stay frozen, the module stays in eval mode.
 
 Weights: `load_state_dict_lpips` takes torchvision's `alexnet().state_dict()` plus the package's `alex.pth`, or the package's
 full `LPIPS(net="alex").state_dict()`.  Neither can be downloaded here: without them the convolutions carry nn.Conv2d's default
@@ -43,8 +49,9 @@ MIN_SIZE = 31          # 31 -> 7 (stem) -> 3 (pool) -> 1 (pool): every tap keeps
 
 
 class LPIPS(nn.Module):
-    def __init__(self, net="alex", conv_precision="reference", seed=0):
+    def __init__(self, net="alex", conv_precision="reference", seed=0, differentiable=False):
         super().__init__()
+        self.differentiable = bool(differentiable)
         if net != "alex":
             raise NotImplementedError(f"LPIPS(net={net!r}): only 'alex' is built")
         if conv_precision not in ("reference", "fast"):
@@ -85,11 +92,15 @@ class LPIPS(nn.Module):
         into the scaling constants)."""
         from . import ops
         from ._lib import require_cuda
+        if self.differentiable and torch.is_grad_enabled() and in1.requires_grad:
+            raise NotImplementedError("LPIPS(differentiable=True): the second image is the target, a constant -- detach it")
         require_cuda(in0, in1)
         if retPerLayer:
             raise NotImplementedError("LPIPS: retPerLayer is not built")
-        if torch.is_grad_enabled() and (in0.requires_grad or in1.requires_grad):
-            raise NotImplementedError("LPIPS is forward-only here (a metric): call it under torch.no_grad() or on detached inputs")
+        wants_grad = torch.is_grad_enabled() and (in0.requires_grad or in1.requires_grad)
+        if wants_grad and not self.differentiable:
+            raise NotImplementedError("LPIPS is forward-only here (a metric): call it under torch.no_grad() or on detached inputs, "
+                                      "or build LPIPS(differentiable=True)")
         if in0.dim() != 4 or in0.shape != in1.shape or in0.shape[1] != 3:
             raise ValueError(f"LPIPS: two [N,3,H,W] batches of one shape, not {tuple(in0.shape)} and {tuple(in1.shape)}")
         N, _, H, W = in0.shape
@@ -98,6 +109,9 @@ class LPIPS(nn.Module):
         shift, scale = self.shift, self.scale
         if normalize:                          # (2x - 1 - shift) / scale
             shift, scale = tuple((1.0 + s) / 2.0 for s in shift), tuple(s / 2.0 for s in scale)
+        if wants_grad:                         # one autograd.Function: the same launches forward, the backward on in0's half alone
+            with ops.conv_precision(self.conv_precision):
+                return ops.lpips_alex(self, in0, in1, shift, scale).view(N, 1, 1, 1)
         with torch.no_grad(), ops.conv_precision(self.conv_precision):
             x = torch.empty((2 * N, 4, H, W), device=in0.device, dtype=torch.float32, memory_format=torch.channels_last)
             ops.image_scale_to_nhwc4(in0.detach().float(), shift, scale, out=x[:N])

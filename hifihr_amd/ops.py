@@ -2426,6 +2426,113 @@ def lpips_tap(f0, f1, w, val, accumulate):
 
 
 # ------------------------------------------------------------------------------------------------
+# LPIPS(net="alex") as a loss: LPIPS(differentiable=True) of hifihr_amd/lpips.py and the `lpips` term of hifihr_amd/losses.py.
+# ONE autograd.Function for the whole metric.  Its forward is the forward-only module's, launch for launch (both images as one batch of
+# 2N, same kernels, hence the same bits); its backward SLICES: only the first half of every saved map -- the image the gradient is for --
+# goes through a backward kernel, the target's half is read by lpips_tap_bwd as the constant f1 and by nothing else.  Per layer, last to
+# first: lpips_tap_bwd adds the tap's gradient onto the one arriving from the layer above and masks the sum with the layer's ReLU,
+# _conv_backward (backward-data on a premasked gradient, frozen weights: no weight or bias gradient) takes it to the layer's input,
+# lpips_maxpool_bwd through the pool in front.
+# ------------------------------------------------------------------------------------------------
+def lpips_maxpool_fwd(x):
+    """nn.MaxPool2d(3, 2) on channels_last activations, the pool lpips_maxpool_bwd differentiates (hifihr_lpips_maxpool_fwd: tapless)."""
+    require_cuda(x)
+    x = x.contiguous(memory_format=_CL)
+    N, C, H, W = x.shape
+    y = torch.empty((N, C, max((H - 3) // 2 + 1, 0), max((W - 3) // 2 + 1, 0)), device=x.device, memory_format=_CL)
+    PROFILE.bracket("maxpool_fwd", lambda: get_lib().lpips_maxpool_fwd(x, N, H, W, C, y))
+    return y
+
+
+def lpips_maxpool_bwd(gy, x):
+    """-> dx like x (channels_last): gy routed to each window's first maximum, recomputed from the pool's input x (a gather, no atomics)."""
+    require_cuda(gy, x)
+    N, C, H, W = x.shape
+    assert x.is_contiguous(memory_format=_CL) and gy.shape == (N, C, (H - 3) // 2 + 1, (W - 3) // 2 + 1), (x.shape, gy.shape)
+    gy = gy.contiguous(memory_format=_CL)
+    dx = torch.empty((N, C, H, W), device=x.device, dtype=torch.float32, memory_format=_CL)
+    PROFILE.bracket("maxpool_bwd", lambda: get_lib().lpips_maxpool_bwd(gy, x, N, H, W, C, dx))
+    return dx
+
+
+def lpips_tap_bwd(f0, f1, w, gval, gf0=None, relu=False):
+    """gf0 (+)= gval[b] / HW * d tap / d f0 on two channels_last maps [B,C,H,W] (f1: the target); gf0 None: a new tensor, overwritten.
+    relu: f0 is a ReLU's output; the stored sum is the gradient of the ReLU's input, (gf0 + tap gradient) * [f0 > 0]."""
+    require_cuda(f0, f1, w, gval)
+    B, C, H, W = f0.shape
+    assert f1.shape == f0.shape and f0.is_contiguous(memory_format=_CL) and f1.is_contiguous(memory_format=_CL) and w.numel() == C
+    assert gval.shape == (B,) and gval.is_contiguous()
+    acc = gf0 is not None
+    if acc:
+        assert gf0.shape == f0.shape and gf0.is_contiguous(memory_format=_CL), (gf0.shape, gf0.stride())
+    else:
+        gf0 = torch.empty((B, C, H, W), device=f0.device, dtype=torch.float32, memory_format=_CL)
+    PROFILE.bracket("lpips_tap_bwd", lambda: get_lib().lpips_tap_bwd(f0, f1, w, gval, B, H * W, C, gf0, accumulate=acc, relu=relu))
+    return gf0
+
+
+def image_scale_to_nhwc4_bwd(g4, scale3):
+    """The backward of image_scale_to_nhwc4: channels_last [B,4,H,W] -> [B,3,H,W] = g4[:, c] / scale[c]."""
+    require_cuda(g4)
+    B, _, H, W = g4.shape
+    assert g4.shape[1] == 4 and g4.is_contiguous(memory_format=_CL), (g4.shape, g4.stride())
+    gimg = torch.empty((B, 3, H, W), device=g4.device, dtype=torch.float32)
+    PROFILE.bracket("image_scale_bwd", lambda: get_lib().image_scale_to_nhwc4_bwd(g4, gimg, scale3))
+    return gimg
+
+
+class _LPIPSAlex(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, in0, in1, module, shift, scale):
+        """-> val [N].  module: a hifihr_amd.lpips.LPIPS (frozen weights); the caller holds the conv_precision scope."""
+        from .lpips import ALEX_LAYERS
+        N, _, H, W = in0.shape
+        x = torch.empty((2 * N, 4, H, W), device=in0.device, dtype=torch.float32, memory_format=_CL)
+        image_scale_to_nhwc4(in0.detach().float(), shift, scale, out=x[:N])
+        image_scale_to_nhwc4(in1.detach().float(), shift, scale, out=x[N:])
+        val = torch.empty(N, device=in0.device, dtype=torch.float32)
+        saved = []
+        for i, (m, lin, cfg) in enumerate(zip(module.convs, module.lins, ALEX_LAYERS)):
+            if cfg[7]:
+                x = lpips_maxpool_fwd(x)
+            xin = x
+            x = conv2d_bias_act(xin, module.stem_w4 if i == 0 else m.weight, m.bias, m.stride, m.pad, True)
+            lpips_tap(x[:N], x[N:], lin, val, accumulate=i > 0)
+            saved += [xin, x]
+        ctx.save_for_backward(*saved)
+        ctx.module, ctx.scale, ctx.in_dtype = module, tuple(scale), in0.dtype
+        ctx.wino_allowed = _wino_allowed()      # the backward runs outside the conv_precision scope: it follows the forward
+        return val
+
+    @staticmethod
+    def backward(ctx, gval):
+        from .lpips import ALEX_LAYERS
+        saved, module = ctx.saved_tensors, ctx.module
+        N = saved[0].shape[0] // 2
+        gval = gval.reshape(N).float().contiguous()
+        g = None
+        for i in reversed(range(len(ALEX_LAYERS))):
+            xin, y = saved[2 * i][:N], saved[2 * i + 1]
+            m = module.convs[i]
+            w = module.stem_w4 if i == 0 else m.weight
+            g = lpips_tap_bwd(y[:N], y[N:], module.lins[i], gval, g, relu=True)      # ... and through the layer's ReLU: [y > 0]
+            _, C, H, W = xin.shape
+            K, _, R, S = w.shape
+            g, _, _ = _conv_backward(g, xin, w.contiguous(memory_format=_CL), None, None, (N, H, W, C, K, R, S, m.stride, m.pad), w, m.bias,
+                                     need_x=True, need_w=False, need_b=False, relu=True, grad_premasked=True, wino_allowed=ctx.wino_allowed)
+            if ALEX_LAYERS[i][7]:
+                g = lpips_maxpool_bwd(g, saved[2 * i - 1][:N])
+        gimg = image_scale_to_nhwc4_bwd(g, ctx.scale)
+        return gimg.to(ctx.in_dtype), None, None, None, None
+
+
+def lpips_alex(module, in0, in1, shift, scale):
+    """LPIPS(alex) of (in0, in1) [N,3,H,W] with a gradient for in0 -> [N]; values bit-identical to the forward-only module's."""
+    require_cuda(in0, in1)
+    return _LPIPSAlex.apply(in0, in1, module, shift, scale)
+
+
+# ------------------------------------------------------------------------------------------------
 # fused SSIM
 # ------------------------------------------------------------------------------------------------
 def _ssim_window():

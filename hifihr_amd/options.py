@@ -18,7 +18,7 @@ _DEFAULTS = dict(
     lambda_mrgb=1e-3, lambda_iou=1e-3, lambda_bone_direc=0.1, lambda_bone_direc_3d=0.1, lambda_edge_len=0.1,
     lambda_percep=1e-5, lambda_ssim_tex=0.001, lambda_scale=100.0, lambda_mscale=0.1, lambda_laplacian=0.1,
     ROOT=9, ROOT_NIMBLE=11,
-    lpips_weights=None,    # [path, ...]: AlexNet + lin weights for the evaluation pass's LPIPS (hifihr_amd/lpips.py); None = LPIPS not reported
+    lpips_weights=None,    # [path, ...]: AlexNet + lin weights for the evaluation pass's LPIPS and the loss term "lpips" (hifihr_amd/lpips.py); None = LPIPS not reported (the loss term: seeded weights)
     benchmark_metrics=True,    # the evaluation pass also reports the FreiHAND benchmark's PCK / AUC and F-score keys (hifihr_amd/evaluate.py)
     # opt-in differentiable silhouette (hifihr_amd/ops.py soft_silhouette; the loss names "sil_soft" / "iou_soft" switch it on as well).
     # The two weights are the defaults of their hard counterparts lambda_silhouette / lambda_iou: starting points, not tuned values
@@ -29,6 +29,9 @@ _DEFAULTS = dict(
     # weight of the opt-in term "normal_consistency" (hifihr_amd/ops.py mesh_regularizers; "triangle" reads the reference's
     # lambda_laplacian above): the weight of PyTorch3D's mesh-fitting tutorial [recalled] -- a starting point, not a tuned value
     lambda_normal_consistency=0.01,
+    # weight of the opt-in term "lpips" (hifihr_amd/losses.py: LPIPS(alex) of the composite against the image, hifihr_amd/lpips.py with
+    # differentiable=True; it reads lpips_weights above): the order of lambda_texture -- a starting point, not a tuned value
+    lambda_lpips=0.01,
 )
 
 # lambda values of reference config/FreiHAND/full_rhd_freihand.json, used by the

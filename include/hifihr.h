@@ -446,7 +446,10 @@ int hifihr_bias_relu_bwd(const float* dy_d, const float* y_d, long M, int C, flo
 int hifihr_light_split_fwd(const float* lights_d, int B, float* colors_d, float* directions_d, void* stream);
 int hifihr_light_split_bwd(const float* lights_d, const float* gcolors_d, const float* gdirections_d, int B, float* glights_d,
                            void* stream);
-/* dx[N][H][W][C] (overwritten).  wt_scratch_d: K*R*S*C floats of scratch (receives the [C][R][S][K] transpose). */
+/* dx[N][H][W][C] (overwritten).  wt_scratch_d: K*R*S*C floats of scratch (receives the [C][R][S][K] transpose).
+ * A STRIDED filter of more than 62 taps onto an NHWC4 image (R * S > 62, stride > 1, C == 4, K % 16 == 0, ceil(R / stride) ceil(S / stride) K
+ * <= 1024: the 11x11 / stride 4 AlexNet stem of the `lpips` loss term) runs on a direct gather from w_d itself (csrc/lpips.hip; fixed summation order, no workspace, wt_scratch_d untouched) -- the implicit-GEMM gather
+ * holds 62 taps; the pre-transposed entries (_pre, _pre_res, _pre_plus1x1) do not serve such a filter. */
 int hifihr_conv2d_bwd_data(const float* dy_d, const float* w_d, float* dx_d, float* wt_scratch_d, int N, int H, int W, int C,
                            int K, int R, int S, int stride, int pad, void* ws_d, size_t ws_bytes, void* stream);
 /* dw[K][R][S][C] += sum over pixels (ACCUMULATES with fp32 atomics: zero it, or pass the gradient buffer). */
@@ -863,7 +866,7 @@ int hifihr_image_to_nhwc4_padded(const float* images_d, float* out_d, int B, int
                                  int pad_bottom, int pad_right, int normalize, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * LPIPS(net="alex"), version 0.1, forward only (csrc/lpips.hip).  Replaces `lpips.LPIPS(net="alex")` of the reference's
+ * LPIPS(net="alex"), version 0.1, the forward (csrc/lpips.hip; the backward follows in the next block).  Replaces `lpips.LPIPS(net="alex")` of the reference's
  * evaluation pass (built at train_hrnet.py:563, called at :158); the five convolutions of the AlexNet trunk
  * (torchvision features[0:12]) run on hifihr_conv2d_fwd with act = 1.  hifihr_amd/lpips.py is the caller.
  *
@@ -888,6 +891,51 @@ int hifihr_lpips_tap_max_channels(void);
 size_t hifihr_lpips_tap_partial_floats(int B);
 int hifihr_lpips_tap(const float* f0_d, const float* f1_d, const float* w_d, int B, int HW, int C, int accumulate, float* partial_d,
                      float* val_d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * LPIPS as a training loss: the backward of the three launches above (csrc/lpips.hip), gradient with respect to the FIRST image only --
+ * the second is the target, a constant.  Not in the reference (its LPIPS is an evaluation metric, train_hrnet.py:158,563); the callers are
+ * hifihr_amd/lpips.py LPIPS(differentiable=True) and the opt-in loss term `lpips` of hifihr_amd/losses.py.  The convolutions' backward is
+ * hifihr_conv2d_bwd_data with the frozen weights on a gradient that lpips_tap_bwd_relu has already taken through the ReLU.  Every entry: no allocation, no synchronisation (capturable into
+ * a hipGraph), no float atomics, every output element has ONE writer: the same bits on every call.
+ *
+ * lpips_tap_bwd: the gradient of one tap (hifihr_lpips_tap) with respect to f0_d; f1_d gets none.  Per pixel, eps = 1e-10:
+ *     r0 = sqrt(sum_c f0_c^2), D0 = r0 + eps (r1, D1 alike);  n = f / D;  q_c = 2 w_c (n0_c - n1_c);  t = sum_c q_c f0_c
+ *     d d / d f0_k = q_k / D0 - f0_k t / (r0 D0^2)     where r0 > 0
+ *     d d / d f0_k = q_k / D0                          where r0 == 0  -- a CONVENTION: on an all-zero pixel the second numerator is 0;
+ *                                                      torch autograd through sqrt gives NaN there
+ *     gf0_d[b][p][k] = (accumulate ? gf0_d[b][p][k] : 0) + gval_d[b] / HW * d d / d f0_k
+ *   gval_d[B]: the gradient arriving at val_d (device).  n0 - n1 is formed per channel exactly as the forward forms it: identical maps give
+ *   a gradient of exactly 0.  The pixel -> (workgroup, lane group) mapping is the forward's, a function of (HW, C) alone.
+ *   accepted:    C % 4 == 0, 4 <= C <= hifihr_lpips_tap_max_channels() (512), 1 <= B <= 65535, HW >= 1
+ *   refused:     anything else, or a NULL f0_d / f1_d / w_d / gval_d / gf0_d: HIFIHR_EINVAL, gf0_d untouched
+ *   overwritten: gf0_d with accumulate == 0; with accumulate != 0 it is read and added to (it must hold finite or intended values)
+ * lpips_tap_bwd_relu: the same call for an f0_d that is a ReLU's output (every AlexNet tap): what it stores is the gradient of the ReLU's
+ *   INPUT, gf0_d = ((accumulate ? gf0_d : 0) + gval_d[b] / HW * d d / d f0) * [f0 > 0] -- the mask covers the arriving gradient too.
+ *   Bit for bit the unmasked call's result where f0 > 0, exactly 0 elsewhere (a NaN in f0 counts as not > 0).  Same accepted / refused /
+ *   overwritten sets.  (hifihr_bias_relu_bwd serves C <= 256; the third tap has 384 channels.)
+ * lpips_maxpool_fwd / lpips_maxpool_bwd: nn.MaxPool2d(3, 2), no padding, with a backward; x[N][H][W][C] -> y[N][OH][OW][C], OH = (H - 3)/2 + 1.
+ *   TAPLESS design: the forward writes no winning-tap bytes (it is the kernel of hifihr_maxpool2d_fwd_notap); the backward recomputes each
+ *   window's winner from the saved input x_d as a gather -- an input pixel looks at the at most 2 x 2 windows that cover it and adds the
+ *   gy of those it wins, in ascending (oh, ow) order.  Tie rule = ATen's: the first maximum in row-major window order, found with the
+ *   forward's (v > m) || isnan(v) scan from the first tap (a NaN wins, the last one of a window).
+ *   accepted:    C % 4 == 0, C >= 4, H >= 3, W >= 3, N >= 1
+ *   refused:     anything else or a NULL pointer: HIFIHR_EINVAL, y_d / dx_d untouched.  hifihr_maxpool2d_fwd / _bwd / _fwd_notap keep
+ *                their own sets
+ *   overwritten: y_d; dx_d[N][H][W][C] entirely -- rows and columns that no window covers (H or W even) get exactly 0
+ * image_scale_to_nhwc4_bwd: the backward of hifihr_image_scale_to_nhwc4: gimg_d[B][3][H][W] = g4_d[B][H][W][c] / scale[c], the same
+ *   true division as the forward; the fourth plane of g4_d is ignored.  scale3_host: HOST array of 3 floats.
+ *   accepted:    B, H, W >= 1, scale[c] != 0
+ *   refused:     anything else or a NULL pointer: HIFIHR_EINVAL, gimg_d untouched
+ *   overwritten: gimg_d
+ * ---------------------------------------------------------------------------------------------- */
+int hifihr_lpips_tap_bwd(const float* f0_d, const float* f1_d, const float* w_d, const float* gval_d, int B, int HW, int C, int accumulate,
+                         float* gf0_d, void* stream);
+int hifihr_lpips_tap_bwd_relu(const float* f0_d, const float* f1_d, const float* w_d, const float* gval_d, int B, int HW, int C, int accumulate,
+                              float* gf0_d, void* stream);
+int hifihr_lpips_maxpool_fwd(const float* x_d, int N, int H, int W, int C, float* y_d, void* stream);
+int hifihr_lpips_maxpool_bwd(const float* gy_d, const float* x_d, int N, int H, int W, int C, float* dx_d, void* stream);
+int hifihr_image_scale_to_nhwc4_bwd(const float* g4_d, float* gimg_d, int B, int H, int W, const float* scale3_host, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused SSIM (11x11 gaussian window sigma 1.5, zero padding, C1 = 0.01^2, C2 = 0.03^2, mean over all elements).

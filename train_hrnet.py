@@ -57,7 +57,8 @@ def parse(argv=None):
     ap.add_argument("--lpips_weights", nargs="+", default=None, metavar="PATH",
                     help="report LPIPS(net='alex') beside PSNR / SSIM in the evaluation pass (reference train_hrnet.py:158,563): one or two torch "
                          "files -- torchvision's alexnet state dict and the lpips package's alex.pth, or the package's full LPIPS state dict "
-                         "(hifihr_amd/lpips.py: load_state_dict_lpips).  Without it LPIPS is not reported.")
+                         "(hifihr_amd/lpips.py: load_state_dict_lpips).  Without it LPIPS is not reported.  The opt-in loss term 'lpips' "
+                         "(options: lambda_lpips) reads the same files; without them it trains on seeded weights and warns.")
     ap.add_argument("--soft_silhouette", action="store_true",
                     help="the model also emits outputs['re_sil_soft'], a differentiable silhouette (options: soft_silhouette, soft_sil_sigma); "
                          "the loss names 'sil_soft' / 'iou_soft' switch it on by themselves")
