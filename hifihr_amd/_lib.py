@@ -290,6 +290,14 @@ class HifihrLib:
         c.hifihr_mesh_reg_partial_floats.restype = c_size_t
         c.hifihr_mesh_reg_fwd.argtypes = [c_void_p, _c_float_p, c_int, c_float, c_float, _c_float_p, _c_float_p, _c_float_p, c_void_p]
         c.hifihr_mesh_reg_bwd.argtypes = [c_void_p, _c_float_p, _c_float_p, _c_float_p, c_int, c_float, c_float, _c_float_p, c_void_p]
+        c.hifihr_chamfer_geometry.argtypes = [_c_int_p, _c_int_p]
+        c.hifihr_chamfer_geometry.restype = None
+        c.hifihr_chamfer_workspace_bytes.argtypes = [c_int, c_int, c_int]
+        c.hifihr_chamfer_workspace_bytes.restype = c_size_t
+        c.hifihr_chamfer_fwd.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_float, c_float, _c_int_p, _c_int_p, c_void_p, c_void_p,
+                                         c_void_p, _c_float_p, c_void_p, c_void_p]
+        c.hifihr_chamfer_bwd.argtypes = [_c_float_p, _c_float_p, _c_int_p, _c_int_p, _c_float_p, c_int, c_int, c_int, c_float, c_float,
+                                         _c_float_p, _c_float_p, c_void_p]
         c.hifihr_renderer_set_uv.argtypes = [c_void_p, _c_int_p, _c_float_p, c_int]
         c.hifihr_render_uv_scratch_bytes.argtypes = [c_void_p, c_int]
         c.hifihr_render_uv_scratch_bytes.restype = c_size_t
@@ -1226,6 +1234,32 @@ class HifihrLib:
     def mesh_reg_bwd(self, h, verts, unit, gout, lam_lap, lam_nc, gverts):
         self.check(self.c.hifihr_mesh_reg_bwd(h, _fp(verts), _fp(unit), _fp(gout), verts.shape[0], c_float(lam_lap), c_float(lam_nc),
                                               _fp(gverts), _stream_of(verts)), "hifihr_mesh_reg_bwd")
+
+    # ---- Chamfer distance (csrc/chamfer.hip) ------------------------------
+    def chamfer_geometry(self):
+        """-> (queries per workgroup, searched points per LDS pass)"""
+        q, t = c_int32(), c_int32()
+        self.c.hifihr_chamfer_geometry(ctypes.byref(q), ctypes.byref(t))
+        return q.value, t.value
+
+    def chamfer_workspace_bytes(self, B, N, M) -> int:
+        return int(self.c.hifihr_chamfer_workspace_bytes(int(B), int(N), int(M)))
+
+    def chamfer_fwd(self, x, y, w_xy, w_yx, idx_xy, idx_yx, min_xy, min_yx, sums, out, ws):
+        """x [B, N, 3], y [B, M, 3]; idx_* int32 and min_* float64 [B, N] / [B, M]; sums float64 [B, 2]; out [1]; ws: a byte tensor of
+        chamfer_workspace_bytes(B, N, M)"""
+        assert idx_xy.dtype == torch.int32 and idx_yx.dtype == torch.int32 and min_xy.dtype == torch.float64 and min_yx.dtype == torch.float64
+        assert sums.dtype == torch.float64 and all(t.is_contiguous() for t in (idx_xy, idx_yx, min_xy, min_yx, sums, ws))
+        assert ws.numel() * ws.element_size() >= self.chamfer_workspace_bytes(x.shape[0], x.shape[1], y.shape[1])
+        self.check(self.c.hifihr_chamfer_fwd(_fp(x), _fp(y), x.shape[0], x.shape[1], y.shape[1], c_float(w_xy), c_float(w_yx), _ip(idx_xy),
+                                             _ip(idx_yx), c_void_p(min_xy.data_ptr()), c_void_p(min_yx.data_ptr()), c_void_p(sums.data_ptr()),
+                                             _fp(out), c_void_p(ws.data_ptr()), _stream_of(x)), "hifihr_chamfer_fwd")
+
+    def chamfer_bwd(self, x, y, idx_xy, idx_yx, gout, w_xy, w_yx, gx, gy):
+        """gx [B, N, 3] / gy [B, M, 3] or None: the set is skipped; gout [1] on the device"""
+        self.check(self.c.hifihr_chamfer_bwd(_fp(x), _fp(y), _ip(idx_xy), _ip(idx_yx), _fp(gout), x.shape[0], x.shape[1], y.shape[1],
+                                             c_float(w_xy), c_float(w_yx), _fp(gx), _fp(gy), _stream_of(x)), "hifihr_chamfer_bwd")
+
 
 
 _LIB = None

@@ -571,6 +571,41 @@ int hifihr_mesh_reg_bwd(const hifihr_mesh_topology_t* h, const float* verts, con
   return HIFIHR_OK;
 }
 
+void hifihr_chamfer_geometry(int* queries_per_workgroup, int* tile_points) {
+  if (queries_per_workgroup) *queries_per_workgroup = hifihr::kChamferQ;
+  if (tile_points) *tile_points = hifihr::kChamferTile;
+}
+
+namespace {
+// the grid of both launches: (sample, direction, chunk) in one dimension
+bool chamfer_grid_ok(int B, int N, int M) { return (long long)B * 2 * hifihr::chamfer_chunks(N, M) <= 0x7fffffffLL; }
+}  // namespace
+
+size_t hifihr_chamfer_workspace_bytes(int B, int N, int M) {
+  if (B < 0 || N < 1 || M < 1) return 0;
+  return (size_t)B * 2 * (size_t)hifihr::chamfer_chunks(N, M) * sizeof(double);
+}
+
+int hifihr_chamfer_fwd(const float* x, const float* y, int B, int N, int M, float w_xy, float w_yx, int32_t* idx_xy, int32_t* idx_yx,
+                       double* min_xy, double* min_yx, double* sums, float* out, void* ws, void* stream) {
+  if (!x || !y || !idx_xy || !idx_yx || !min_xy || !min_yx || !sums || !out || !ws || B < 0 || N < 1 || M < 1 || !std::isfinite(w_xy) ||
+      !std::isfinite(w_yx) || !chamfer_grid_ok(B, N, M))
+    return fail(HIFIHR_EINVAL, "hifihr_chamfer_fwd: bad argument (B >= 0, N, M >= 1, finite weights, 2 B chunks < 2^31)");
+  if (B == 0) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_chamfer_fwd(x, y, B, N, M, w_xy, w_yx, idx_xy, idx_yx, min_xy, min_yx, sums, out, (double*)ws, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_chamfer_bwd(const float* x, const float* y, const int32_t* idx_xy, const int32_t* idx_yx, const float* gout, int B, int N, int M,
+                       float w_xy, float w_yx, float* gx, float* gy, void* stream) {
+  if (!x || !y || !idx_xy || !idx_yx || !gout || B < 0 || N < 1 || M < 1 || !std::isfinite(w_xy) || !std::isfinite(w_yx) ||
+      !chamfer_grid_ok(B, N, M))
+    return fail(HIFIHR_EINVAL, "hifihr_chamfer_bwd: bad argument (B >= 0, N, M >= 1, finite weights, 2 B chunks < 2^31)");
+  if (B == 0 || (!gx && !gy)) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_chamfer_bwd(x, y, idx_xy, idx_yx, gout, B, N, M, w_xy, w_yx, gx, gy, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
 int hifihr_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, float grad_scale,
                      float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream) {
   if (!params || !grads || !exp_avg || !exp_avg_sq || step < 1) return fail(HIFIHR_EINVAL, "hifihr_adam_step: bad argument");

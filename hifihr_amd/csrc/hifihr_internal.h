@@ -374,6 +374,15 @@ hipError_t launch_mesh_reg_fwd(const MeshTopoDev& t, const float* verts, int B, 
 hipError_t launch_mesh_reg_bwd(const MeshTopoDev& t, const float* verts, const float* unit, const float* gout, int B, float lam_lap,
                                float lam_nc, float* gverts, hipStream_t st);
 
+// Chamfer distance (chamfer.hip; include/hifihr.h "Chamfer distance").  kChamferQ queries per workgroup (four per lane), kChamferTile searched
+// points per LDS pass, a quarter of a tile per wave.  partial holds B * 2 * chamfer_chunks(N, M) doubles
+constexpr int kChamferQ = 256, kChamferTile = 512;
+long long chamfer_chunks(int N, int M);
+hipError_t launch_chamfer_fwd(const float* x, const float* y, int B, int N, int M, float w_xy, float w_yx, int* idx_xy, int* idx_yx,
+                              double* min_xy, double* min_yx, double* sums, float* out, double* partial, hipStream_t st);
+hipError_t launch_chamfer_bwd(const float* x, const float* y, const int* idx_xy, const int* idx_yx, const float* gout, int B, int N, int M,
+                              float w_xy, float w_yx, float* gx, float* gy, hipStream_t st);
+
 // small-batch fully connected layer (mlp.hip): y[B][O] = act(BN1d?(x[B][I] W[O][I]^T + b)); gamma == nullptr: no batch-norm
 // sigmoid(z) for the swish / sigmoid activations of EfficientNet (batch-norm + swish passes, squeeze-excite gates): v_exp_f32 of z log2(e) and
 // v_rcp_f32 -- ~4 instructions where expf + an IEEE division are ~30, and the swish passes of csrc/bn.hip were bound by exactly those

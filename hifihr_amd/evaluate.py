@@ -10,7 +10,10 @@ The FreiHAND benchmark's other `scores.txt` keys -- PCK / AUC of joints and mesh
 EvalUtil, instantiated at train_hrnet.py:25,43) and F@5 mm / F@15 mm -- come from `pck_auc`, `fscore` and `Evaluator(benchmark=True)`:
 the device counts (csrc/eval.hip: one launch per metric), the host turns the integer counts into curves in float64.  PCK / AUC are pinned
 to the reference's EvalUtil (tests/golden/benchmark_metrics.npz); the F-score has no counterpart in the reference tree and neither the
-benchmark's eval.py nor open3d is available here: its parity with the benchmark's script is unpinned (tests/benchmark_ref.py restates it)."""
+benchmark's eval.py nor open3d is available here: its parity with the benchmark's script is unpinned (tests/benchmark_ref.py restates it).
+
+The Chamfer distance, the number mesh papers report beside the F-score, is opt-in: `chamfer` and `Evaluator(chamfer=True)` (csrc/chamfer.hip,
+the kernels of the loss term of the same name; pinned to the reference's unwired ChamferLoss by tests/golden/chamfer.npz)."""
 from __future__ import annotations
 
 import numpy as np
@@ -45,6 +48,7 @@ def aligned_error(pred, gt):
 
 BENCHMARK_KEYS = ("xyz_mean3d", "xyz_auc3d", "xyz_al_mean3d", "xyz_al_auc3d", "mesh_mean3d", "mesh_auc3d", "mesh_al_mean3d", "mesh_al_auc3d",
                   "f_score_5", "f_score_15", "f_al_score_5", "f_al_score_15")
+CHAMFER_KEYS = ("mesh_chamfer", "mesh_al_chamfer")
 _trapezoid = getattr(np, "trapezoid", None) or np.trapz
 
 
@@ -104,12 +108,23 @@ def fscore_from_counts(counts, Np, Ng):
     return torch.where(S > 0, 2 * P * R / torch.where(S > 0, S, torch.ones_like(S)), torch.zeros_like(S)), P, R
 
 
+def chamfer(pred, gt):
+    """float64 [B, 2] on the device: per sample the MEAN squared distance to the nearest point of the other set, (pred -> gt, gt -> pred), in
+    the inputs' unit squared.  pred [B, Np, 3], gt [B, Ng, 3], any Np, Ng.  Their sum is the Chamfer distance of the loss term `chamfer`
+    at unit weights (ops.chamfer_distance), sample by sample."""
+    from . import ops
+    require_cuda(pred, gt)
+    assert pred.dim() == 3 and gt.dim() == 3 and pred.shape[0] == gt.shape[0] and pred.shape[2] == 3 and gt.shape[2] == 3, (pred.shape, gt.shape)
+    return ops.chamfer_sums(pred, gt) / torch.tensor([pred.shape[1], gt.shape[1]], dtype=torch.float64, device=pred.device)
+
+
 class Evaluator:
     """Accumulates what the evaluation loop keeps (train_hrnet.py:119-161) and reduces it as :216-272 does."""
 
-    def __init__(self, ssim_fn=None, lpips_fn=None, benchmark=False):
+    def __init__(self, ssim_fn=None, lpips_fn=None, benchmark=False, chamfer=False):
         self.xyz_pred, self.verts_pred, self.texture = [], [], []
         self.benchmark = bool(benchmark)          # summary() adds BENCHMARK_KEYS when ground truth is given
+        self.chamfer = bool(chamfer)              # summary() adds CHAMFER_KEYS when verts_gt is given
         if ssim_fn is None:
             from . import ops
             ssim_fn = ops.ssim
@@ -154,11 +169,13 @@ class Evaluator:
         the batch-averaged texture metrics.  An Evaluator(benchmark=True) adds BENCHMARK_KEYS for the ground truth it is given (the
         FreiHAND benchmark's scores.txt names: *_mean3d in the inputs' unit, *_auc3d over 0..0.05 in 100 steps, F at 0.005 / 0.015); the
         `_al_` forms are taken on the fp32 output of align_w_scale.  root_id: the ground truth is made relative to its joint `root_id`
-        before the un-aligned forms (the predictions are root-relative already); None takes it as given."""
+        before the un-aligned forms (the predictions are root-relative already); None takes it as given.  An Evaluator(chamfer=True)
+        adds CHAMFER_KEYS when verts_gt is given: the two directions of `chamfer` summed, averaged over the samples, in the inputs' unit
+        SQUARED; taken on the same two pairs of point sets as the F-scores."""
         out, bench = {}, []
         dev = lambda a, like: torch.as_tensor(a, dtype=torch.float32).to(like.device)
         root = None
-        if self.benchmark and root_id is not None and (xyz_gt is not None or verts_gt is not None):
+        if (self.benchmark or self.chamfer) and root_id is not None and (xyz_gt is not None or verts_gt is not None):
             if xyz_gt is None:
                 raise ValueError("root_id needs xyz_gt: the root is a ground-truth joint")
             root = dev(xyz_gt, (self.xyz_pred or self.verts_pred)[0])[:, int(root_id):int(root_id) + 1]
@@ -167,14 +184,14 @@ class Evaluator:
                 continue
             pred = torch.cat(preds)
             gt = dev(gt, pred)
-            if self.benchmark:
+            if self.benchmark or (self.chamfer and name == "mesh"):
                 aligned, err = align_w_scale(gt, pred, return_error=True)           # the same err bits as aligned_error
                 bench.append((name, pred, gt if root is None else gt - root, aligned, gt))
             else:
                 err = aligned_error(pred, gt)
             out["pose_3d" if name == "xyz" else "vert_3d"] = float(err.mean())
         if bench:
-            out.update(self._benchmark_summary(bench))
+            out.update(self._benchmark_summary(bench, benchmark=self.benchmark, with_chamfer=self.chamfer))
         if self.texture:
             for k in self.texture[0]:
                 out[k] = float(torch.stack([r[k] for r in self.texture]).mean())
@@ -182,19 +199,23 @@ class Evaluator:
         return out
 
     @staticmethod
-    def _benchmark_summary(bench):
+    def _benchmark_summary(bench, benchmark=True, with_chamfer=False):
         """bench: (name, pred, gt for the un-aligned forms, aligned pred, gt) per point set.  Everything is counted on the device and
-        comes to the host in ONE copy; the curves are host float64."""
+        comes to the host in ONE copy; the curves are host float64.  benchmark: BENCHMARK_KEYS; with_chamfer: CHAMFER_KEYS."""
         thr = np.linspace(0.0, 0.05, 100)
         parts, plan = [], []
         for name, pred, gt_rel, aligned, gt in bench:
             for tag, p, g in ((name, pred, gt_rel), (name + "_al", aligned, gt)):
-                hist, sums = point_error_counts(p, g, None, thr)
-                parts += [hist.double().reshape(-1), sums]
-                plan.append(("pck", tag, hist.shape))
-                if name == "mesh":
+                if benchmark:
+                    hist, sums = point_error_counts(p, g, None, thr)
+                    parts += [hist.double().reshape(-1), sums]
+                    plan.append(("pck", tag, hist.shape))
+                if benchmark and name == "mesh":
                     parts.append(fscore(p, g, (0.005, 0.015))[0].mean(0))
                     plan.append(("f", "f_al_score_" if tag.endswith("_al") else "f_score_", None))
+                if with_chamfer and name == "mesh":
+                    parts.append(chamfer(p, g).sum(1).mean(0, keepdim=True))
+                    plan.append(("chamfer", tag + "_chamfer", None))
         flat, at, out = torch.cat(parts).cpu().numpy(), 0, {}
         for kind, tag, shape in plan:
             if kind == "pck":
@@ -202,7 +223,10 @@ class Evaluator:
                 m = pck_measures(np.rint(flat[at:at + K * W]).astype(np.int64).reshape(K, W), flat[at + K * W:at + K * W + K], thr)
                 out[tag + "_mean3d"], out[tag + "_auc3d"] = m["mean"], m["auc"]
                 at += K * W + K
+            elif kind == "chamfer":
+                out[tag] = float(flat[at])
+                at += 1
             else:
                 out[tag + "5"], out[tag + "15"] = float(flat[at]), float(flat[at + 1])
                 at += 2
-        return {k: out[k] for k in BENCHMARK_KEYS if k in out}
+        return {k: out[k] for k in BENCHMARK_KEYS + CHAMFER_KEYS if k in out}

@@ -4,7 +4,8 @@
 ONE path: the step's terms run as fused HIP kernels -- SSIM (csrc/ssim.hip), the photometric block and the joint / vertex /
 edge-length / shape / pose terms (csrc/losses.hip: two launches per group instead of ~250 ATen launches) -- on GPU tensors; a CPU
 tensor raises (no fallback).  joint_2d / bone_direc / bone_direc_3d: one more kernel pair (round 3).  triangle / normal_consistency (the
-reference's uniform-Laplacian term and, not in the reference, its usual partner): one kernel pair (csrc/mesh_reg.hip).  sil_soft / iou_soft (not in the
+reference's uniform-Laplacian term and, not in the reference, its usual partner): one kernel pair (csrc/mesh_reg.hip).  chamfer (the reference's
+unwired ChamferLoss): one kernel pair (csrc/chamfer.hip).  sil_soft / iou_soft (not in the
 reference: `sil` and `iou` on the model's opt-in differentiable silhouette, outputs['re_sil_soft']): one kernel pair (csrc/soft_sil.hip).  lpips (not in the
 reference: LPIPS(alex), the evaluation pass's texture metric, as an opt-in loss): hifihr_amd/lpips.py with its HIP backward (csrc/lpips.hip).  The rarely used terms (mscale, scale,
 iou, mtex and the self-supervised `*_self` terms) are a handful of torch ops on the same GPU tensors.  The torch restatement of the whole function that the tests
@@ -25,7 +26,7 @@ _BONES = [(0, 1), (1, 2), (2, 3), (3, 4), (0, 5), (5, 6), (6, 7), (7, 8), (0, 9)
 # every name LossFunction.__call__ can produce (a name outside it in `losses` is ignored here and stops traineval's step with a KeyError)
 TERMS = ("joint_3d", "vert_3d", "edge_length", "mshape", "mpose", "joint_2d", "bone_direc", "bone_direc_3d", "mscale", "scale", "texture",
          "mrgb", "ssim_tex", "sil", "texture_self", "mrgb_self", "ssim_tex_self", "perceptual", "iou", "sil_soft", "iou_soft", "triangle",
-         "normal_consistency", "lpips", "mtex")
+         "normal_consistency", "lpips", "chamfer", "mtex")
 
 _BONE_IDX = {}
 
@@ -243,6 +244,21 @@ class LossFunction:
                 if k in loss_used:
                     loss_dic[k] = v
             self._total_parts.append((vec, 2, names))
+        if "chamfer" in loss_used:
+            # not wired in the reference (utils/losses_util.py:304-337 ChamferLoss is defined, its import in losses.py:7 is commented out):
+            # lambda_chamfer * (mean squared distance to the nearest point, prediction -> target + target -> prediction), one kernel pair
+            # (csrc/chamfer.hip).  It needs no correspondence, so it reaches the dense skin of the NIMBLE-shaped layer, which no other geometry
+            # term does, and it takes a point cloud of any size as the target (examples['chamfer_points'], in the root-relative frame of
+            # examples['verts'])
+            target = examples["chamfer_points"] if examples.get("chamfer_points") is not None else examples["verts"]
+            if outputs.get("chamfer_points") is not None:
+                pred = outputs["chamfer_points"]
+            elif getattr(args, "hand_model", "mano") == "nimble" and outputs.get("verts") is not None and outputs.get("_pred_root") is not None:
+                pred = outputs["verts"] - outputs["_pred_root"]             # the dense skin, root-relative like mano_verts
+            else:
+                pred = outputs["mano_verts"]
+            loss_dic["chamfer"] = ops.chamfer_distance(pred, target, args.lambda_chamfer, args.lambda_chamfer)
+            self._total_parts.append((loss_dic["chamfer"], 1, ["chamfer"]))
         if "mtex" in loss_used and outputs.get("texture_params") is not None:
             loss_dic["mtex"] = args.lambda_tex_reg * F.mse_loss(outputs["texture_params"], torch.zeros_like(outputs["texture_params"]))
         return loss_dic

@@ -272,6 +272,7 @@ class Model(nn.Module):
         outputs["joints"], outputs["mano_verts"] = joints - pred_root, outputs["mano_verts"] - pred_root
         nroot = outputs["nimble_joints"][:, 0 if eval_ho3d else self.root_id_nimble].unsqueeze(1)      # :167-172
         outputs["nimble_joints"] = outputs["nimble_joints"] - nroot
+        outputs["_pred_root"] = pred_root            # the loss term "chamfer" makes the dense skin outputs["verts"] root-relative with it
         if self.ifRender:
             cam = self.camera_from_K(Ks)
             if self.ifLight:

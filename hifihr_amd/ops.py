@@ -486,6 +486,54 @@ def mesh_regularizers(topo: MeshTopology, verts, lam_lap, lam_nc):
     return _MeshReg.apply(topo, verts, float(lam_lap), float(lam_nc))
 
 
+def _chamfer_run(x, y, w_xy, w_yx):
+    """hifihr_chamfer_fwd on x [B, N, 3], y [B, M, 3] -> (x, y as the kernel read them, idx_xy, idx_yx, min_xy, min_yx, sums, out)."""
+    require_cuda(x, y)
+    x, y = x.contiguous().float(), y.contiguous().float()
+    assert x.dim() == 3 and y.dim() == 3 and x.shape[2] == 3 and y.shape[2] == 3 and x.shape[0] == y.shape[0] and x.shape[0] > 0, (x.shape, y.shape)
+    assert x.shape[1] > 0 and y.shape[1] > 0, (x.shape, y.shape)
+    lib, dev, (B, N, _), M = get_lib(), x.device, x.shape, y.shape[1]
+    idx_xy, idx_yx = torch.empty(B, N, dtype=torch.int32, device=dev), torch.empty(B, M, dtype=torch.int32, device=dev)
+    min_xy, min_yx = torch.empty(B, N, dtype=torch.float64, device=dev), torch.empty(B, M, dtype=torch.float64, device=dev)
+    sums, out = torch.empty(B, 2, dtype=torch.float64, device=dev), torch.empty(1, device=dev)
+    ws = torch.empty(lib.chamfer_workspace_bytes(B, N, M) // 8, dtype=torch.float64, device=dev)
+    PROFILE.bracket("chamfer_fwd", lambda: lib.chamfer_fwd(x, y, w_xy, w_yx, idx_xy, idx_yx, min_xy, min_yx, sums, out, ws))
+    return x, y, idx_xy, idx_yx, min_xy, min_yx, sums, out
+
+
+class _Chamfer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, w_xy, w_yx):
+        x, y, idx_xy, idx_yx, _, _, _, out = _chamfer_run(x, y, w_xy, w_yx)
+        ctx.w = (w_xy, w_yx)
+        ctx.save_for_backward(x, y, idx_xy, idx_yx)
+        return out.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, y, idx_xy, idx_yx = ctx.saved_tensors
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+        g = gout.contiguous().float().reshape(1)
+        PROFILE.bracket("chamfer_bwd", lambda: get_lib().chamfer_bwd(x, y, idx_xy, idx_yx, g, ctx.w[0], ctx.w[1], gx, gy))
+        return gx, gy, None, None
+
+
+def chamfer_distance(x, y, w_xy=1.0, w_yx=1.0):
+    """w_xy * mean over (sample, point of x) of the squared distance to the nearest point of y + w_yx * the same from y to x, a 0-d tensor:
+    x [B, N, 3] (the prediction), y [B, M, 3] (the target), any N, M >= 1 (include/hifihr.h "Chamfer distance").  At unit weights it is
+    mean(loss_1) + mean(loss_2) of the reference's ChamferLoss()(x, y) and PyTorch3D's chamfer_distance(x, y)[0] at its defaults
+    [recalled].  Searched in fp64 with ties to the lowest index; the gradient takes the nearest neighbours as constants and goes to
+    whichever of x, y requires one.  A weight of exactly 0 drops that direction.  One kernel pair (csrc/chamfer.hip), no CPU path."""
+    return _Chamfer.apply(x, y, float(w_xy), float(w_yx))
+
+
+def chamfer_sums(x, y):
+    """float64 [B, 2]: per sample the SUMS of squared nearest-neighbour distances (x -> y, y -> x); no autograd (the evaluation metric)."""
+    with torch.no_grad():
+        return _chamfer_run(x.detach(), y.detach(), 1.0, 1.0)[6]
+
+
 # ------------------------------------------------------------------------------------------------
 # convolution on the f32 matrix cores (tensors are logical NCHW in channels_last memory format = physical NHWC)
 # ------------------------------------------------------------------------------------------------

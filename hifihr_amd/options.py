@@ -32,6 +32,10 @@ _DEFAULTS = dict(
     # weight of the opt-in term "lpips" (hifihr_amd/losses.py: LPIPS(alex) of the composite against the image, hifihr_amd/lpips.py with
     # differentiable=True; it reads lpips_weights above): the order of lambda_texture -- a starting point, not a tuned value
     lambda_lpips=0.01,
+    # weight of the opt-in term "chamfer" (hifihr_amd/ops.py chamfer_distance): the weight of PyTorch3D's mesh-fitting tutorial [recalled]
+    # -- a starting point, not a tuned value.  The term is in SQUARED metres (1 cm off is 1e-4), so a real run will need it much larger
+    lambda_chamfer=1.0,
+    chamfer_metric=False,    # the evaluation pass also reports mesh_chamfer / mesh_al_chamfer (hifihr_amd/evaluate.py Evaluator(chamfer=True))
 )
 
 # lambda values of reference config/FreiHAND/full_rhd_freihand.json, used by the

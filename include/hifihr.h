@@ -321,6 +321,46 @@ int hifihr_mesh_reg_bwd(const hifihr_mesh_topology_t* h, const float* verts_d, c
                         float lam_lap, float lam_nc, float* gverts_d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Chamfer distance (csrc/chamfer.hip): the loss term `chamfer` and the evaluation metric of the same name.  It is the reference's
+ * ChamferLoss (utils/losses_util.py:304-337, defined there and never wired: the import in losses.py:7 is commented out) with
+ * mean(loss_1) + mean(loss_2) at unit weights, pinned by tests/golden/chamfer.npz, and PyTorch3D's chamfer_distance(x, y)[0] at its
+ * defaults [recalled]: parity with PyTorch3D is unpinned.  tests/chamfer_ref.py restates the definition below in float64.
+ *
+ * Definition, per sample b, x = x_d[b] [N][3] (the prediction), y = y_d[b] [M][3] (the target), fp32 in, every operation in fp64:
+ *   d2(i, j) = (dx dx + dy dy) + dz dz,   dx = (double)x[i][0] - (double)y[j][0], ...       this order, no contraction
+ *   a[i] = the j that minimises (d2(i, j), j) lexicographically: ties go to the LOWEST index;   c[j] = the i that minimises (d2(i, j), i)
+ *   sum_xy[b] = sum_i d2(i, a[i]),   sum_yx[b] = sum_j d2(c[j], j)
+ *   value = w_xy mean_b (sum_xy[b] / N) + w_yx mean_b (sum_yx[b] / M), rounded to fp32 once
+ * A direction whose weight is exactly 0 contributes exactly 0 and gets no gradient; its index and min arrays are still written.
+ * Gradient (a and c are piecewise-constant choices), the inner sums in ascending index order, in fp64, rounded to fp32 once:
+ *   gx[i] = gout ( w_xy 2 / (B N) (x[i] - y[a[i]]) + w_yx 2 / (B M) sum over { j : c[j] == i } of (x[i] - y[j]) )
+ *   gy[j] = gout ( w_yx 2 / (B M) (y[j] - x[c[j]]) + w_xy 2 / (B N) sum over { i : a[i] == j } of (y[j] - x[i]) )
+ * The library is built with -ffp-contract=off, so d2, a and c are the bits and integers of any float64 evaluation of the same expression.
+ *
+ * hifihr_chamfer_geometry writes the kernel's two constants (either pointer may be NULL): the queries one workgroup takes and the searched
+ *   points of one LDS pass.  The four waves of a workgroup scan consecutive quarters of a pass.  For callers that size batches and for the
+ *   tests, which build their cases round these boundaries.
+ * hifihr_chamfer_workspace_bytes: the size of ws_d; 0 for B < 0 or N, M < 1; it never decreases with B.
+ * Refused (HIFIHR_EINVAL, nothing launched, nothing written): a NULL among the required pointers (every pointer except gx_d, gy_d and
+ *   stream), B < 0, N < 1, M < 1, a weight that is not finite, a grid beyond 2^31 - 1 workgroups (2 B ceil(max(N, M) / queries)).
+ * Accepted: B == 0 is a no-op; hifihr_chamfer_bwd with gx_d == gy_d == NULL is a no-op; one of them NULL skips that set.
+ * Overwritten: hifihr_chamfer_fwd writes EVERY element of idx_xy_d[B][N], idx_yx_d[B][M] (int32), min_xy_d[B][N], min_yx_d[B][M]
+ *   (double: d2 at the arg-min), sums_d[B][2] (double: sum_xy, sum_yx) and out_d[1]; ws_d is scratch.  hifihr_chamfer_bwd OVERWRITES every
+ *   element of gx_d[B][N][3] and gy_d[B][M][3]; a point that nobody chose gets its own term alone.  It takes the gradient of the value as the
+ *   DEVICE scalar gout_d[1] and must be given the forward's weights and index arrays.
+ * Repeatable: no atomics.  The search keeps (d2, index) pairs and compares them lexicographically wherever two candidates meet; partial
+ *   sums are folded in a fixed order; the backward takes its scatter term as a gather with one writer per element: the same bits on every call.
+ * Preconditions, NOT checked: finite coordinates.  A NaN or an Inf gives unspecified values, never an out-of-range access: an index starts
+ *   at 0 and is only ever replaced by a loop counter, a d2 that is not a number never wins, and the backward clamps the indices it is given.
+ * No allocation and no synchronisation inside the entries: they can be captured into a hipGraph. */
+void hifihr_chamfer_geometry(int* queries_per_workgroup, int* tile_points);
+size_t hifihr_chamfer_workspace_bytes(int B, int N, int M);
+int hifihr_chamfer_fwd(const float* x_d, const float* y_d, int B, int N, int M, float w_xy, float w_yx, int32_t* idx_xy_d, int32_t* idx_yx_d,
+                       double* min_xy_d, double* min_yx_d, double* sums_d, float* out_d, void* ws_d, void* stream);
+int hifihr_chamfer_bwd(const float* x_d, const float* y_d, const int32_t* idx_xy_d, const int32_t* idx_yx_d, const float* gout_d, int B, int N,
+                       int M, float w_xy, float w_yx, float* gx_d /* or NULL */, float* gy_d /* or NULL */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Texture-PCA decode (csrc/texpca.hip): tex[b][n] = mean[n] (or 0 when NULL) + sum_k coef[b][k] basis[k][n], K <= 32, n % 4 == 0.
  * The texture half of the NIMBLE layer as the reference consumes it (models_res_nimble.py:57,133-142: texture_params [B,10] -> the
  * hand's texture).  NIMBLE's own basis is not available: the caller supplies one (n = 778 * 3 vertex

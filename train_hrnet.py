@@ -268,13 +268,14 @@ def make_evaluator(args, device):
     from hifihr_amd.evaluate import Evaluator
     paths = getattr(args, "lpips_weights", None)
     bench = bool(getattr(args, "benchmark_metrics", True))          # the FreiHAND benchmark's PCK / AUC and F-score keys
+    cham = bool(getattr(args, "chamfer_metric", False))             # mesh_chamfer / mesh_al_chamfer beside the F-scores
     if not paths:
-        return Evaluator(benchmark=bench)
+        return Evaluator(benchmark=bench, chamfer=cham)
     key = (str(device), tuple(paths))
     if key not in _LPIPS:
         from hifihr_amd.lpips import LPIPS, load_lpips_weights
         _LPIPS[key] = load_lpips_weights(LPIPS(net="alex"), *paths).to(device)
-    return Evaluator(lpips_fn=_LPIPS[key], benchmark=bench)
+    return Evaluator(lpips_fn=_LPIPS[key], benchmark=bench, chamfer=cham)
 
 
 def run_evaluation_ho3d(model, cache, args, device, epoch):
@@ -314,9 +315,11 @@ def run_evaluation(model, cache, arrays, args, device):
 
 
 def benchmark_report(summary):
-    """The twelve values of the FreiHAND benchmark's scores.txt, under its names (those the summary holds)."""
-    from hifihr_amd.evaluate import BENCHMARK_KEYS
-    return "\n".join(f"{k}: {summary[k]:.6f}" for k in BENCHMARK_KEYS if k in summary)
+    """The twelve values of the FreiHAND benchmark's scores.txt, under its names (those the summary holds); with the option
+    chamfer_metric the two Chamfer distances (inputs' unit squared) follow the F-scores."""
+    from hifihr_amd.evaluate import BENCHMARK_KEYS, CHAMFER_KEYS
+    lines = [f"{k}: {summary[k]:.6f}" for k in BENCHMARK_KEYS if k in summary]
+    return "\n".join(lines + [f"{k}: {summary[k]:.6e}" for k in CHAMFER_KEYS if k in summary])
 
 
 def main(argv=None):
@@ -380,7 +383,7 @@ def main(argv=None):
     if "evaluation" in args.mode:
         summary = run_evaluation(model, eval_cache or cache, eval_arrays or train_arrays, args, device)
         say("[train_hrnet] evaluation:", summary)
-        if getattr(args, "benchmark_metrics", True):
+        if getattr(args, "benchmark_metrics", True) or getattr(args, "chamfer_metric", False):
             say("[train_hrnet] benchmark scores:\n" + benchmark_report(summary))
         return 0
 
