@@ -230,6 +230,7 @@ class HifihrLib:
         c.hifihr_bgemm_describe.argtypes = [c_int] * 5 + [ctypes.c_char_p, c_int]
         c.hifihr_conv2d_describe.argtypes = [c_int] * 10 + [ctypes.c_char_p, c_int]
         c.hifihr_bgemm_tn_parts.argtypes = [c_int] * 4
+        c.hifihr_bgemm_tn_coherent.argtypes = [c_int] * 4
         c.hifihr_bgemm_tn.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
         c.hifihr_wino4_dw_transform_multi.argtypes = [c_void_p, c_int, c_void_p]
         c.hifihr_se_pool.argtypes = [_c_float_p, c_int, c_int, c_int, _c_float_p, c_void_p]
@@ -831,6 +832,9 @@ class HifihrLib:
 
     def bgemm_tn_parts(self, M, N, T, batch):
         return int(self.c.hifihr_bgemm_tn_parts(M, N, T, batch))
+
+    def bgemm_tn_coherent(self, M, N, T, batch):
+        return int(self.c.hifihr_bgemm_tn_coherent(M, N, T, batch))
 
     def bgemm_tn(self, A, B, Cparts, M, N, T, batch, parts):
         self.check(self.c.hifihr_bgemm_tn(_fp(A), _fp(B), _fp(Cparts), M, N, T, batch, parts, _stream_of(A)), "hifihr_bgemm_tn")

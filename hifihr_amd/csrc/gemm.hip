@@ -1930,6 +1930,15 @@ hipError_t launch_bgemm_tn(const float* A, const float* B, float* Cparts, int M,
   return hipGetLastError();
 }
 
+// BgemmArgs::co_r of the launch above: the problems an XCD owns per round of the XCD-coherent schedule; 0: contiguous shares (another
+// kernel than the row-share one, a shape or workgroup count tn_coherent turns down, HIFIHR_GEMM_TN_COHERENT=0)
+int bgemm_tn_coherent(int M, int N, int T, int batch) {
+  const GemmEnv e = gemm_env();
+  const TnPlan p = plan_tn(e, M, N, T, batch);
+  if (!p.ok || p.kernel != TnKernel::rows) return 0;
+  return tn_rows_args(e, nullptr, nullptr, nullptr, M, N, T, batch, p.parts, 0, p.G).co_r;
+}
+
 // The pair launch (bgemm_nt_tn_pair_kernel): C[p][m][n] = sum_k A[p][m][k] B[p][n][k] (plain row-share form: N % 128 == 0, K % 32 == 0) AND
 // C2parts = A2^T . B2 (row-share TN form, one slab or the T-split) in ONE launch.  hipErrorNotSupported: one of the two is not on its
 // row-share kernel (the caller then launches them separately).  The CUs are divided in proportion to the products' flops (weighting the

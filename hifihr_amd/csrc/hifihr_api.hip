@@ -1430,6 +1430,11 @@ int hifihr_bgemm_tn_parts(int M, int N, int T, int batch) {
   return hifihr::bgemm_tn_parts(M, N, T, batch);
 }
 
+int hifihr_bgemm_tn_coherent(int M, int N, int T, int batch) {
+  if (batch <= 0 || !hifihr::bgemm_tn_supported(M, N, T)) return 0;
+  return hifihr::bgemm_tn_coherent(M, N, T, batch);
+}
+
 int hifihr_bgemm_tn(const float* A, const float* B, float* C_parts, int M, int N, int T, int batch, int parts, void* stream) {
   if (!A || !B || !C_parts || batch <= 0 || parts <= 0 || !hifihr::bgemm_tn_supported(M, N, T))
     return fail(HIFIHR_EINVAL, "hifihr_bgemm_tn: bad argument (M % 64 == 0, N % 64 == 0)");

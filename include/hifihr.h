@@ -690,6 +690,10 @@ size_t hifihr_bgemm_nt_workspace_bytes(int M, int N, int K, int batch);
 int hifihr_bgemm_nt(const float* a_d, const float* b_d, float* c_d, int M, int N, int K, int batch,
                     void* ws_d /* zero-initialised, self-cleaning; or NULL */, size_t ws_bytes, void* stream);
 int hifihr_bgemm_tn_parts(int M, int N, int T, int batch);
+/* The schedule hifihr_bgemm_tn walks this shape on, measurement only (like hifihr_bgemm_describe: the kernel's name and the results are the
+ * same either way): r > 0 -- the XCD-coherent one, an XCD owning r problems per round; 0 -- contiguous shares (a shape or a workgroup
+ * count the schedule does not fit, a kernel other than the row-share one, HIFIHR_GEMM_TN_COHERENT=0) or a shape hifihr_bgemm_tn refuses. */
+int hifihr_bgemm_tn_coherent(int M, int N, int T, int batch);
 /* Name of the kernel instantiation a shape runs on, as a profiler lists it ("" when the shape is not supported): measurement only. */
 int hifihr_bgemm_describe(int tn, int M, int N, int K_or_T, int batch, char* out, int cap);
 int hifihr_bgemm_tn(const float* a_d, const float* b_d, float* c_parts_d, int M, int N, int T, int batch, int parts, void* stream);

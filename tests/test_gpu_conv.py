@@ -874,6 +874,9 @@ DISPATCH_CASES = ["f4", "f4_async", "f4_grad_to_autograd", "f4_unprepared", "f4_
                   "bn_wino_fused_to_autograd", "bn_wino_unfused"]
 
 
+DISPATCH_RATIO = [0.0]           # the largest err / bound the dispatch cases' comparisons saw (tests/switch_arm_child.py resets and reports it)
+
+
 def _run_dispatch_case(expect, setup, monkeypatch, scope=True, async_wgrad=False, direct=False, premasked=False, tol=5e-5, wtol=1e-4, env=None):
     import contextlib
     from collections import Counter
@@ -911,6 +914,7 @@ def _run_dispatch_case(expect, setup, monkeypatch, scope=True, async_wgrad=False
 
     def close(a, b, rel, what):
         err, top = float((a.detach().cpu().double() - b.detach()).abs().max()), float(b.detach().abs().max())
+        DISPATCH_RATIO[0] = max(DISPATCH_RATIO[0], err / (rel * top + 1e-6))
         assert err <= rel * top + 1e-6, f"{what}: {err:.3e} of max {top:.3e}"
     for i, (a, b) in enumerate(zip(ours, r)):
         close(a, b, tol, f"output {i}")

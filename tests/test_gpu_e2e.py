@@ -26,6 +26,9 @@ def graded_images(imgs):
     return out.clamp_(0, 0.999999).to(imgs.device)
 
 
+ORACLE_RATIO = {}                # what: the largest err / bound of the two oracle comparisons below (tests/switch_arm_child.py reports it)
+
+
 def _setup(B, graded=False):
     from hifihr_amd import options, synth
     from hifihr_amd.mano_tables import synthetic_mano_tables
@@ -64,6 +67,7 @@ def test_train_step_losses_match_oracle():
     torch.cuda.synchronize()
     report = {k: (float(dic[k].detach()), float(rdic[k].detach())) for k in args.losses}
     print("loss terms (hip, oracle):", report)
+    ORACLE_RATIO["loss terms"] = max(abs(a - b) / (1e-4 * max(1.0, abs(b))) for a, b in report.values())
     for k, (a, b) in report.items():
         assert abs(a - b) <= 1e-4 * max(1.0, abs(b)), (k, a, b, report)
     assert abs(float(loss) - float(rloss)) <= 1e-4 * max(1.0, abs(float(rloss)))
@@ -113,6 +117,7 @@ def test_backward_chain_matches_oracle_from_features():
         scale = max(float(r.abs().max()), 1e-4 * gmax)        # pre-BatchNorm biases have an exactly-zero true gradient
         errs.append((float((g.detach().cpu() - r).abs().max()) / scale, name))
     print("worst relative gradient errors:", sorted(errs, reverse=True)[:6])
+    ORACLE_RATIO["chain gradients"] = max(errs)[0] / 5e-3
     assert max(errs)[0] < 5e-3, sorted(errs, reverse=True)[:6]
 
 

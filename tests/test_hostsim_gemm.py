@@ -100,6 +100,7 @@ def test_bgemm_tn_xcd_coherent_schedule(hostsim_lib, monkeypatch, M, N, T, batch
     import torch
     monkeypatch.setenv("HIFIHR_GEMM_CUS", str(cus))
     assert hostsim_lib.bgemm_describe(True, M, N, T, batch) == "bgemm_tn_rows_kernel"
+    assert hostsim_lib.bgemm_tn_coherent(M, N, T, batch) > 0, "this shape is meant to walk the XCD-coherent schedule"
     kc.launch_log(hostsim_lib)
     assert kc.bgemm_tn_case(hostsim_lib, "cpu", M, N, T, batch, seed=M + T + batch) == 1
     _ran_only(hostsim_lib, "bgemm_tn_rows_kernel")
@@ -108,6 +109,7 @@ def test_bgemm_tn_xcd_coherent_schedule(hostsim_lib, monkeypatch, M, N, T, batch
     c1 = torch.full((1, batch, M, N), 7.0); c0 = torch.full((1, batch, M, N), 7.0)
     hostsim_lib.bgemm_tn(a, b, c1, M, N, T, batch, 1)
     monkeypatch.setenv("HIFIHR_GEMM_CUS", "4")               # 4 workgroups: never coherent
+    assert hostsim_lib.bgemm_tn_coherent(M, N, T, batch) == 0
     hostsim_lib.bgemm_tn(a, b, c0, M, N, T, batch, 1)
     assert torch.equal(c0, c1)
 
