@@ -299,6 +299,14 @@ class HifihrLib:
                                          c_void_p, _c_float_p, c_void_p, c_void_p]
         c.hifihr_chamfer_bwd.argtypes = [_c_float_p, _c_float_p, _c_int_p, _c_int_p, _c_float_p, c_int, c_int, c_int, c_float, c_float,
                                          _c_float_p, _c_float_p, c_void_p]
+        c.hifihr_point_mesh_geometry.argtypes = [_c_int_p] * 4
+        c.hifihr_point_mesh_geometry.restype = None
+        c.hifihr_point_mesh_workspace_bytes.argtypes = [c_int] * 4
+        c.hifihr_point_mesh_workspace_bytes.restype = c_size_t
+        c.hifihr_point_mesh_fwd.argtypes = [_c_float_p, _c_float_p, _c_int_p, c_int, c_int, c_int, c_int, c_float, c_float, _c_int_p, c_void_p,
+                                            c_void_p, _c_int_p, c_void_p, c_void_p, c_void_p, _c_float_p, c_void_p, c_void_p]
+        c.hifihr_point_mesh_bwd.argtypes = [_c_float_p, _c_float_p, _c_int_p, _c_int_p, c_void_p, _c_int_p, c_void_p, _c_float_p, _c_int_p,
+                                            _c_int_p, c_int, c_int, c_int, c_int, c_float, c_float, _c_float_p, _c_float_p, c_void_p, c_void_p]
         c.hifihr_renderer_set_uv.argtypes = [c_void_p, _c_int_p, _c_float_p, c_int]
         c.hifihr_render_uv_scratch_bytes.argtypes = [c_void_p, c_int]
         c.hifihr_render_uv_scratch_bytes.restype = c_size_t
@@ -1263,6 +1271,38 @@ class HifihrLib:
         """gx [B, N, 3] / gy [B, M, 3] or None: the set is skipped; gout [1] on the device"""
         self.check(self.c.hifihr_chamfer_bwd(_fp(x), _fp(y), _ip(idx_xy), _ip(idx_yx), _fp(gout), x.shape[0], x.shape[1], y.shape[1],
                                              c_float(w_xy), c_float(w_yx), _fp(gx), _fp(gy), _stream_of(x)), "hifihr_chamfer_bwd")
+
+    # ---- point-to-mesh distance (csrc/point_mesh.hip) ------------------------
+    def point_mesh_geometry(self):
+        """-> (points per workgroup, face records per LDS pass, faces per workgroup, points per LDS pass)"""
+        g = [c_int32() for _ in range(4)]
+        self.c.hifihr_point_mesh_geometry(*[ctypes.byref(x) for x in g])
+        return tuple(x.value for x in g)
+
+    def point_mesh_workspace_bytes(self, B, N, V, F) -> int:
+        return int(self.c.hifihr_point_mesh_workspace_bytes(int(B), int(N), int(V), int(F)))
+
+    def point_mesh_fwd(self, p, v, faces, w_pf, w_fp, idx_pf, bary_pf, min_pf, idx_fp, bary_fp, min_fp, sums, out, ws):
+        """p [B, N, 3], v [B, V, 3], faces int32 [F, 3]; idx_* int32 [B, N] / [B, F], bary_* float64 [B, N, 3] / [B, F, 3], min_* float64;
+        sums float64 [B, 2]; out [1]; ws: point_mesh_workspace_bytes(B, N, V, F) bytes"""
+        B, N, V, F = p.shape[0], p.shape[1], v.shape[1], faces.shape[0]
+        dp = lambda t: c_void_p(t.data_ptr())
+        assert all(t.dtype == torch.float64 and t.is_contiguous() for t in (bary_pf, min_pf, bary_fp, min_fp, sums)) and ws.is_contiguous()
+        assert v.shape[0] == B and ws.numel() * ws.element_size() >= self.point_mesh_workspace_bytes(B, N, V, F)
+        self.check(self.c.hifihr_point_mesh_fwd(_fp(p), _fp(v), _ip(faces), B, N, V, F, c_float(w_pf), c_float(w_fp), _ip(idx_pf), dp(bary_pf),
+                                                dp(min_pf), _ip(idx_fp), dp(bary_fp), dp(min_fp), dp(sums), _fp(out), dp(ws), _stream_of(p)),
+                   "hifihr_point_mesh_fwd")
+
+    def point_mesh_bwd(self, p, v, faces, idx_pf, bary_pf, idx_fp, bary_fp, gout, v2c_off, v2c_corner, w_pf, w_fp, gp, gv, ws):
+        """gp [B, N, 3] / gv [B, V, 3] or None: that gradient is skipped; gout [1] on the device; v2c_off int32 [V + 1], v2c_corner int32
+        [3 F]: the vertex -> corner table (ops.point_mesh_tables_of)"""
+        B, N, V, F = p.shape[0], p.shape[1], v.shape[1], faces.shape[0]
+        dp = lambda t: c_void_p(t.data_ptr())
+        assert bary_pf.dtype == torch.float64 and bary_fp.dtype == torch.float64 and v2c_off.numel() == V + 1 and v2c_corner.numel() == 3 * F
+        assert ws.numel() * ws.element_size() >= self.point_mesh_workspace_bytes(B, N, V, F)
+        self.check(self.c.hifihr_point_mesh_bwd(_fp(p), _fp(v), _ip(faces), _ip(idx_pf), dp(bary_pf), _ip(idx_fp), dp(bary_fp), _fp(gout),
+                                                _ip(v2c_off), _ip(v2c_corner), B, N, V, F, c_float(w_pf), c_float(w_fp), _fp(gp), _fp(gv), dp(ws),
+                                                _stream_of(p)), "hifihr_point_mesh_bwd")
 
 
 

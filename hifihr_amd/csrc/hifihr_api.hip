@@ -606,6 +606,42 @@ int hifihr_chamfer_bwd(const float* x, const float* y, const int32_t* idx_xy, co
   return HIFIHR_OK;
 }
 
+void hifihr_point_mesh_geometry(int* points_per_wg, int* faces_per_pass, int* faces_per_wg, int* points_per_pass) {
+  if (points_per_wg) *points_per_wg = hifihr::kPointMeshPQ;
+  if (faces_per_pass) *faces_per_pass = hifihr::kPointMeshFT;
+  if (faces_per_wg) *faces_per_wg = hifihr::kPointMeshFQ;
+  if (points_per_pass) *points_per_pass = hifihr::kPointMeshPT;
+}
+
+size_t hifihr_point_mesh_workspace_bytes(int B, int N, int V, int F) {
+  if (B < 0 || N < 1 || V < 1 || F < 1) return 0;
+  return (hifihr::point_mesh_partial_doubles(B, N, F) + (size_t)B * (size_t)F * 9) * sizeof(double);
+}
+
+int hifihr_point_mesh_fwd(const float* p, const float* v, const int32_t* faces, int B, int N, int V, int F, float w_pf, float w_fp,
+                          int32_t* idx_pf, double* bary_pf, double* min_pf, int32_t* idx_fp, double* bary_fp, double* min_fp, double* sums,
+                          float* out, void* ws, void* stream) {
+  if (!p || !v || !faces || !idx_pf || !bary_pf || !min_pf || !idx_fp || !bary_fp || !min_fp || !sums || !out || !ws || B < 0 || N < 1 || V < 1 ||
+      F < 1 || !std::isfinite(w_pf) || !std::isfinite(w_fp) || !hifihr::point_mesh_grid_ok(B, N, V, F))
+    return fail(HIFIHR_EINVAL, "hifihr_point_mesh_fwd: bad argument (B >= 0, N, V, F >= 1, finite weights, every grid < 2^31)");
+  if (B == 0) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_point_mesh_fwd(p, v, faces, B, N, V, F, w_pf, w_fp, idx_pf, bary_pf, min_pf, idx_fp, bary_fp, min_fp, sums, out,
+                                        (double*)ws, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_point_mesh_bwd(const float* p, const float* v, const int32_t* faces, const int32_t* idx_pf, const double* bary_pf,
+                          const int32_t* idx_fp, const double* bary_fp, const float* gout, const int32_t* v2c_off, const int32_t* v2c_corner,
+                          int B, int N, int V, int F, float w_pf, float w_fp, float* gp, float* gv, void* ws, void* stream) {
+  if (!p || !v || !faces || !idx_pf || !bary_pf || !idx_fp || !bary_fp || !gout || !v2c_off || !v2c_corner || !ws || B < 0 || N < 1 || V < 1 ||
+      F < 1 || !std::isfinite(w_pf) || !std::isfinite(w_fp) || !hifihr::point_mesh_grid_ok(B, N, V, F))
+    return fail(HIFIHR_EINVAL, "hifihr_point_mesh_bwd: bad argument (B >= 0, N, V, F >= 1, finite weights, every grid < 2^31)");
+  if (B == 0 || (!gp && !gv)) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_point_mesh_bwd(p, v, faces, idx_pf, bary_pf, idx_fp, bary_fp, gout, v2c_off, v2c_corner, B, N, V, F, w_pf, w_fp, gp, gv,
+                                        (double*)ws, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
 int hifihr_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, float grad_scale,
                      float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream) {
   if (!params || !grads || !exp_avg || !exp_avg_sq || step < 1) return fail(HIFIHR_EINVAL, "hifihr_adam_step: bad argument");

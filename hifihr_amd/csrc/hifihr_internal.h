@@ -383,6 +383,21 @@ hipError_t launch_chamfer_fwd(const float* x, const float* y, int B, int N, int 
 hipError_t launch_chamfer_bwd(const float* x, const float* y, const int* idx_xy, const int* idx_yx, const float* gout, int B, int N, int M,
                               float w_xy, float w_yx, float* gx, float* gy, hipStream_t st);
 
+// Point-to-mesh distance (point_mesh.hip; include/hifihr.h "Point-to-mesh distance").  Points -> faces: kPointMeshPQ points per workgroup (one per
+// lane: N is a few hundred to a few thousand, so small chunks are what fills the chip; measured, profiles/point_mesh_time.txt), kPointMeshFT face
+// records per LDS pass.  Faces -> points: kPointMeshFQ faces per workgroup (two records per lane: a record is 24 VGPRs), kPointMeshPT points
+// per LDS pass.  A quarter of a pass per wave.  ws holds point_mesh_partial_doubles(B, N, F) doubles of partial sums, then the backward's
+// per-corner slab of B * F * 9 doubles
+constexpr int kPointMeshPQ = 64, kPointMeshFT = 256, kPointMeshFQ = 128, kPointMeshPT = 512;
+bool point_mesh_grid_ok(int B, int N, int V, int F);
+size_t point_mesh_partial_doubles(int B, int N, int F);
+hipError_t launch_point_mesh_fwd(const float* p, const float* v, const int* faces, int B, int N, int V, int F, float w_pf, float w_fp,
+                                 int* idx_pf, double* bary_pf, double* min_pf, int* idx_fp, double* bary_fp, double* min_fp, double* sums,
+                                 float* out, double* ws, hipStream_t st);
+hipError_t launch_point_mesh_bwd(const float* p, const float* v, const int* faces, const int* idx_pf, const double* bary_pf, const int* idx_fp,
+                                 const double* bary_fp, const float* gout, const int* v2c_off, const int* v2c_corner, int B, int N, int V, int F,
+                                 float w_pf, float w_fp, float* gp, float* gv, double* ws, hipStream_t st);
+
 // small-batch fully connected layer (mlp.hip): y[B][O] = act(BN1d?(x[B][I] W[O][I]^T + b)); gamma == nullptr: no batch-norm
 // sigmoid(z) for the swish / sigmoid activations of EfficientNet (batch-norm + swish passes, squeeze-excite gates): v_exp_f32 of z log2(e) and
 // v_rcp_f32 -- ~4 instructions where expf + an IEEE division are ~30, and the swish passes of csrc/bn.hip were bound by exactly those

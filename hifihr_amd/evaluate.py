@@ -13,7 +13,9 @@ to the reference's EvalUtil (tests/golden/benchmark_metrics.npz); the F-score ha
 benchmark's eval.py nor open3d is available here: its parity with the benchmark's script is unpinned (tests/benchmark_ref.py restates it).
 
 The Chamfer distance, the number mesh papers report beside the F-score, is opt-in: `chamfer` and `Evaluator(chamfer=True)` (csrc/chamfer.hip,
-the kernels of the loss term of the same name; pinned to the reference's unwired ChamferLoss by tests/golden/chamfer.npz)."""
+the kernels of the loss term of the same name; pinned to the reference's unwired ChamferLoss by tests/golden/chamfer.npz).  So is the mean
+squared distance from the ground-truth vertices to the predicted SURFACE: `point_to_surface` and `Evaluator(point_mesh=True)`
+(csrc/point_mesh.hip, the kernels of the loss term `point_mesh`; parity with PyTorch3D's point_mesh_face_distance is unpinned)."""
 from __future__ import annotations
 
 import numpy as np
@@ -49,6 +51,7 @@ def aligned_error(pred, gt):
 BENCHMARK_KEYS = ("xyz_mean3d", "xyz_auc3d", "xyz_al_mean3d", "xyz_al_auc3d", "mesh_mean3d", "mesh_auc3d", "mesh_al_mean3d", "mesh_al_auc3d",
                   "f_score_5", "f_score_15", "f_al_score_5", "f_al_score_15")
 CHAMFER_KEYS = ("mesh_chamfer", "mesh_al_chamfer")
+POINT_MESH_KEYS = ("mesh_p2s", "mesh_al_p2s")
 _trapezoid = getattr(np, "trapezoid", None) or np.trapz
 
 
@@ -118,13 +121,26 @@ def chamfer(pred, gt):
     return ops.chamfer_sums(pred, gt) / torch.tensor([pred.shape[1], gt.shape[1]], dtype=torch.float64, device=pred.device)
 
 
+def point_to_surface(pred_verts, faces, gt_points):
+    """float64 [B] on the device: per sample the MEAN squared distance from the ground-truth points gt_points [B, N, 3] to the closest
+    triangle of the predicted mesh (pred_verts [B, V, 3], faces [F, 3] int tensor on the device), in the inputs' unit squared.  Only that
+    direction is searched.  It is the points -> faces half of the loss term `point_mesh` (ops.point_mesh_distance), sample by sample, and
+    exactly 0 where the points lie on the surface."""
+    from . import ops
+    require_cuda(pred_verts, gt_points, faces)
+    assert pred_verts.dim() == 3 and gt_points.dim() == 3 and pred_verts.shape[0] == gt_points.shape[0], (pred_verts.shape, gt_points.shape)
+    return ops.point_mesh_sums(gt_points, pred_verts, faces, 1.0, 0.0)[:, 0] / float(gt_points.shape[1])
+
+
 class Evaluator:
     """Accumulates what the evaluation loop keeps (train_hrnet.py:119-161) and reduces it as :216-272 does."""
 
-    def __init__(self, ssim_fn=None, lpips_fn=None, benchmark=False, chamfer=False):
+    def __init__(self, ssim_fn=None, lpips_fn=None, benchmark=False, chamfer=False, point_mesh=False, faces=None):
         self.xyz_pred, self.verts_pred, self.texture = [], [], []
         self.benchmark = bool(benchmark)          # summary() adds BENCHMARK_KEYS when ground truth is given
         self.chamfer = bool(chamfer)              # summary() adds CHAMFER_KEYS when verts_gt is given
+        self.point_mesh = bool(point_mesh)        # summary() adds POINT_MESH_KEYS when verts_gt is given
+        self.faces = faces                        # the predicted mesh's faces [F, 3] on the device; else outputs['_faces_i32'] of `collect`
         if ssim_fn is None:
             from . import ops
             ssim_fn = ops.ssim
@@ -136,6 +152,8 @@ class Evaluator:
             joints = Frei2HO3D(joints) * torch.tensor([1.0, -1.0, -1.0], device=joints.device).view(1, 1, 3)
         self.xyz_pred.append(joints)
         self.verts_pred.append(outputs["mano_verts"].detach())
+        if self.point_mesh and self.faces is None:
+            self.faces = outputs.get("_faces_i32")
         if render and "re_img" in outputs:
             if dat_name == "HO3D":
                 m = (outputs["re_sil"] > 0).float()
@@ -171,11 +189,16 @@ class Evaluator:
         `_al_` forms are taken on the fp32 output of align_w_scale.  root_id: the ground truth is made relative to its joint `root_id`
         before the un-aligned forms (the predictions are root-relative already); None takes it as given.  An Evaluator(chamfer=True)
         adds CHAMFER_KEYS when verts_gt is given: the two directions of `chamfer` summed, averaged over the samples, in the inputs' unit
-        SQUARED; taken on the same two pairs of point sets as the F-scores."""
+        SQUARED; taken on the same two pairs of point sets as the F-scores.  An Evaluator(point_mesh=True) adds POINT_MESH_KEYS the same
+        way: the mean squared distance from the ground-truth vertices to the predicted SURFACE (point_to_surface), averaged over the
+        samples, un-aligned and aligned."""
         out, bench = {}, []
+        mesh_extra = self.chamfer or self.point_mesh
+        if self.point_mesh and verts_gt is not None and self.faces is None:
+            raise ValueError("Evaluator(point_mesh=True) needs the predicted mesh's faces: faces=, or outputs['_faces_i32'] at collect")
         dev = lambda a, like: torch.as_tensor(a, dtype=torch.float32).to(like.device)
         root = None
-        if (self.benchmark or self.chamfer) and root_id is not None and (xyz_gt is not None or verts_gt is not None):
+        if (self.benchmark or mesh_extra) and root_id is not None and (xyz_gt is not None or verts_gt is not None):
             if xyz_gt is None:
                 raise ValueError("root_id needs xyz_gt: the root is a ground-truth joint")
             root = dev(xyz_gt, (self.xyz_pred or self.verts_pred)[0])[:, int(root_id):int(root_id) + 1]
@@ -184,14 +207,15 @@ class Evaluator:
                 continue
             pred = torch.cat(preds)
             gt = dev(gt, pred)
-            if self.benchmark or (self.chamfer and name == "mesh"):
+            if self.benchmark or (mesh_extra and name == "mesh"):
                 aligned, err = align_w_scale(gt, pred, return_error=True)           # the same err bits as aligned_error
                 bench.append((name, pred, gt if root is None else gt - root, aligned, gt))
             else:
                 err = aligned_error(pred, gt)
             out["pose_3d" if name == "xyz" else "vert_3d"] = float(err.mean())
         if bench:
-            out.update(self._benchmark_summary(bench, benchmark=self.benchmark, with_chamfer=self.chamfer))
+            out.update(self._benchmark_summary(bench, benchmark=self.benchmark, with_chamfer=self.chamfer,
+                                               p2s_faces=self.faces if self.point_mesh else None))
         if self.texture:
             for k in self.texture[0]:
                 out[k] = float(torch.stack([r[k] for r in self.texture]).mean())
@@ -199,9 +223,10 @@ class Evaluator:
         return out
 
     @staticmethod
-    def _benchmark_summary(bench, benchmark=True, with_chamfer=False):
+    def _benchmark_summary(bench, benchmark=True, with_chamfer=False, p2s_faces=None):
         """bench: (name, pred, gt for the un-aligned forms, aligned pred, gt) per point set.  Everything is counted on the device and
-        comes to the host in ONE copy; the curves are host float64.  benchmark: BENCHMARK_KEYS; with_chamfer: CHAMFER_KEYS."""
+        comes to the host in ONE copy; the curves are host float64.  benchmark: BENCHMARK_KEYS; with_chamfer: CHAMFER_KEYS; p2s_faces
+        (the predicted mesh's faces): POINT_MESH_KEYS."""
         thr = np.linspace(0.0, 0.05, 100)
         parts, plan = [], []
         for name, pred, gt_rel, aligned, gt in bench:
@@ -216,6 +241,9 @@ class Evaluator:
                 if with_chamfer and name == "mesh":
                     parts.append(chamfer(p, g).sum(1).mean(0, keepdim=True))
                     plan.append(("chamfer", tag + "_chamfer", None))
+                if p2s_faces is not None and name == "mesh":
+                    parts.append(point_to_surface(p, p2s_faces, g).mean(0, keepdim=True))
+                    plan.append(("chamfer", tag + "_p2s", None))
         flat, at, out = torch.cat(parts).cpu().numpy(), 0, {}
         for kind, tag, shape in plan:
             if kind == "pck":
@@ -229,4 +257,4 @@ class Evaluator:
             else:
                 out[tag + "5"], out[tag + "15"] = float(flat[at]), float(flat[at + 1])
                 at += 2
-        return {k: out[k] for k in BENCHMARK_KEYS + CHAMFER_KEYS if k in out}
+        return {k: out[k] for k in BENCHMARK_KEYS + CHAMFER_KEYS + POINT_MESH_KEYS if k in out}

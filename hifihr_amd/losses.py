@@ -5,7 +5,8 @@ ONE path: the step's terms run as fused HIP kernels -- SSIM (csrc/ssim.hip), the
 edge-length / shape / pose terms (csrc/losses.hip: two launches per group instead of ~250 ATen launches) -- on GPU tensors; a CPU
 tensor raises (no fallback).  joint_2d / bone_direc / bone_direc_3d: one more kernel pair (round 3).  triangle / normal_consistency (the
 reference's uniform-Laplacian term and, not in the reference, its usual partner): one kernel pair (csrc/mesh_reg.hip).  chamfer (the reference's
-unwired ChamferLoss): one kernel pair (csrc/chamfer.hip).  sil_soft / iou_soft (not in the
+unwired ChamferLoss): one kernel pair (csrc/chamfer.hip).  point_mesh (not in the
+reference: the distance of the target points to the SURFACE of the predicted mesh): one kernel pair (csrc/point_mesh.hip).  sil_soft / iou_soft (not in the
 reference: `sil` and `iou` on the model's opt-in differentiable silhouette, outputs['re_sil_soft']): one kernel pair (csrc/soft_sil.hip).  lpips (not in the
 reference: LPIPS(alex), the evaluation pass's texture metric, as an opt-in loss): hifihr_amd/lpips.py with its HIP backward (csrc/lpips.hip).  The rarely used terms (mscale, scale,
 iou, mtex and the self-supervised `*_self` terms) are a handful of torch ops on the same GPU tensors.  The torch restatement of the whole function that the tests
@@ -26,7 +27,7 @@ _BONES = [(0, 1), (1, 2), (2, 3), (3, 4), (0, 5), (5, 6), (6, 7), (7, 8), (0, 9)
 # every name LossFunction.__call__ can produce (a name outside it in `losses` is ignored here and stops traineval's step with a KeyError)
 TERMS = ("joint_3d", "vert_3d", "edge_length", "mshape", "mpose", "joint_2d", "bone_direc", "bone_direc_3d", "mscale", "scale", "texture",
          "mrgb", "ssim_tex", "sil", "texture_self", "mrgb_self", "ssim_tex_self", "perceptual", "iou", "sil_soft", "iou_soft", "triangle",
-         "normal_consistency", "lpips", "chamfer", "mtex")
+         "normal_consistency", "lpips", "chamfer", "point_mesh", "mtex")
 
 _BONE_IDX = {}
 
@@ -259,6 +260,26 @@ class LossFunction:
                 pred = outputs["mano_verts"]
             loss_dic["chamfer"] = ops.chamfer_distance(pred, target, args.lambda_chamfer, args.lambda_chamfer)
             self._total_parts.append((loss_dic["chamfer"], 1, ["chamfer"]))
+        if "point_mesh" in loss_used:
+            # not in the reference: lambda_point_mesh * (mean squared distance of the target points to the closest TRIANGLE of the predicted
+            # mesh) + lambda_point_mesh_faces * (mean squared distance of the predicted faces to their closest target point; 0 by default: that
+            # direction is then not searched), one kernel pair (csrc/point_mesh.hip).  Zero exactly when the target points lie on the predicted
+            # surface, which `chamfer` on vertex sets of different density is not.  The target is the one of `chamfer`; the mesh is the
+            # caller's outputs['verts'] / outputs['faces'] when both are given, else the dense skin of the NIMBLE-shaped layer made
+            # root-relative, else the MANO-topology mesh
+            target = examples["chamfer_points"] if examples.get("chamfer_points") is not None else examples["verts"]
+            if outputs.get("verts") is not None and outputs.get("faces") is not None:
+                verts, faces = outputs["verts"], outputs["faces"]              # faces [F, 3], or [B, F, 3] with one topology for the batch
+                faces = faces[0] if faces.dim() == 3 else faces
+            elif (getattr(args, "hand_model", "mano") == "nimble" and outputs.get("verts") is not None and outputs.get("_pred_root") is not None
+                  and outputs.get("_skin_faces_i32") is not None):
+                verts, faces = outputs["verts"] - outputs["_pred_root"], outputs["_skin_faces_i32"]
+            else:
+                verts, faces = outputs["mano_verts"], outputs.get("_faces_i32")
+                if faces is None:
+                    faces = outputs["mano_faces"][0].int().contiguous()
+            loss_dic["point_mesh"] = ops.point_mesh_distance(target, verts, faces, args.lambda_point_mesh, args.lambda_point_mesh_faces)
+            self._total_parts.append((loss_dic["point_mesh"], 1, ["point_mesh"]))
         if "mtex" in loss_used and outputs.get("texture_params") is not None:
             loss_dic["mtex"] = args.lambda_tex_reg * F.mse_loss(outputs["texture_params"], torch.zeros_like(outputs["texture_params"]))
         return loss_dic

@@ -273,6 +273,7 @@ class Model(nn.Module):
         nroot = outputs["nimble_joints"][:, 0 if eval_ho3d else self.root_id_nimble].unsqueeze(1)      # :167-172
         outputs["nimble_joints"] = outputs["nimble_joints"] - nroot
         outputs["_pred_root"] = pred_root            # the loss term "chamfer" makes the dense skin outputs["verts"] root-relative with it
+        outputs["_skin_faces_i32"] = self.hand_layer.mesh_face[0]      # ... and "point_mesh" measures to the skin's own triangles
         if self.ifRender:
             cam = self.camera_from_K(Ks)
             if self.ifLight:

@@ -8,6 +8,7 @@ import math
 import os
 import threading
 
+import numpy as np
 import torch
 
 from ._lib import get_lib, require_cuda
@@ -532,6 +533,90 @@ def chamfer_sums(x, y):
     """float64 [B, 2]: per sample the SUMS of squared nearest-neighbour distances (x -> y, y -> x); no autograd (the evaluation metric)."""
     with torch.no_grad():
         return _chamfer_run(x.detach(), y.detach(), 1.0, 1.0)[6]
+
+
+_POINT_MESH_TABLES = {}
+
+
+def point_mesh_tables_of(faces, V):
+    """-> (faces int32 [F, 3] contiguous, v2c_off int32 [V + 1], v2c_corner int32 [3 F]) on the faces' device: the vertex -> corner table of
+    hifihr_point_mesh_bwd (include/hifihr.h "Point-to-mesh distance"), built on first use and kept per faces tensor, keyed as
+    mesh_topology_of keys its cache.  The first use copies the faces to the host, validates them (indices in [0, V), no face with a
+    repeated index) and allocates, so it belongs outside a captured step: run the loss once eagerly first, as a captured step's warm-up
+    does."""
+    require_cuda(faces)
+    assert faces.dim() == 2 and faces.shape[1] == 3 and faces.shape[0] > 0 and not faces.dtype.is_floating_point, (faces.shape, faces.dtype)
+    key = (faces.data_ptr(), int(faces.shape[0]), int(V), str(faces.device))
+    hit = _POINT_MESH_TABLES.get(key)
+    if hit is None:
+        f = faces.detach().cpu().numpy().astype(np.int64)
+        if f.min() < 0 or f.max() >= V:
+            raise ValueError(f"point_mesh: a face index outside [0, {V}) (found {int(f.min())} .. {int(f.max())})")
+        if ((f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 0] == f[:, 2])).any():
+            raise ValueError("point_mesh: a face names one vertex twice")
+        flat = f.reshape(-1)
+        off = np.zeros(V + 1, np.int64)
+        np.cumsum(np.bincount(flat, minlength=V), out=off[1:])
+        corner = np.argsort(flat, kind="stable")             # the corners 3 f + k vertex by vertex, ascending inside a vertex
+        dev = faces.device
+        hit = _POINT_MESH_TABLES[key] = (faces.to(torch.int32).contiguous(), torch.as_tensor(off.astype(np.int32)).to(dev),
+                                         torch.as_tensor(corner.astype(np.int32)).to(dev), faces)     # (keeps `faces` alive: the key is its address)
+    return hit[:3]
+
+
+def _point_mesh_run(points, verts, faces, w_pf, w_fp):
+    """hifihr_point_mesh_fwd on points [B, N, 3], verts [B, V, 3], faces [F, 3] -> a dict of what the kernel read and wrote."""
+    require_cuda(points, verts, faces)
+    p, v = points.contiguous().float(), verts.contiguous().float()
+    assert p.dim() == 3 and v.dim() == 3 and p.shape[2] == 3 and v.shape[2] == 3 and p.shape[0] == v.shape[0] and p.shape[0] > 0, (p.shape, v.shape)
+    assert p.shape[1] > 0 and v.shape[1] > 0, (p.shape, v.shape)
+    f32, off, corner = point_mesh_tables_of(faces, v.shape[1])
+    lib, dev, (B, N, _), V, F = get_lib(), p.device, p.shape, v.shape[1], f32.shape[0]
+    r = dict(p=p, v=v, faces=f32, off=off, corner=corner,
+             idx_pf=torch.empty(B, N, dtype=torch.int32, device=dev), bary_pf=torch.empty(B, N, 3, dtype=torch.float64, device=dev),
+             min_pf=torch.empty(B, N, dtype=torch.float64, device=dev), idx_fp=torch.empty(B, F, dtype=torch.int32, device=dev),
+             bary_fp=torch.empty(B, F, 3, dtype=torch.float64, device=dev), min_fp=torch.empty(B, F, dtype=torch.float64, device=dev),
+             sums=torch.empty(B, 2, dtype=torch.float64, device=dev), out=torch.empty(1, device=dev),
+             ws=torch.empty(lib.point_mesh_workspace_bytes(B, N, V, F) // 8, dtype=torch.float64, device=dev))
+    PROFILE.bracket("point_mesh_fwd", lambda: lib.point_mesh_fwd(p, v, f32, w_pf, w_fp, r["idx_pf"], r["bary_pf"], r["min_pf"], r["idx_fp"],
+                                                                 r["bary_fp"], r["min_fp"], r["sums"], r["out"], r["ws"]))
+    return r
+
+
+class _PointMesh(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, verts, faces, w_pf, w_fp):
+        r = _point_mesh_run(points, verts, faces, w_pf, w_fp)
+        ctx.w = (w_pf, w_fp)
+        ctx.save_for_backward(r["p"], r["v"], r["faces"], r["off"], r["corner"], r["idx_pf"], r["bary_pf"], r["idx_fp"], r["bary_fp"], r["ws"])
+        return r["out"].view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        p, v, faces, off, corner, idx_pf, bary_pf, idx_fp, bary_fp, ws = ctx.saved_tensors
+        gp = torch.empty_like(p) if ctx.needs_input_grad[0] else None
+        gv = torch.empty_like(v) if ctx.needs_input_grad[1] else None
+        g = gout.contiguous().float().reshape(1)
+        PROFILE.bracket("point_mesh_bwd", lambda: get_lib().point_mesh_bwd(p, v, faces, idx_pf, bary_pf, idx_fp, bary_fp, g, off, corner,
+                                                                           ctx.w[0], ctx.w[1], gp, gv, ws))
+        return gp, gv, None, None, None
+
+
+def point_mesh_distance(points, verts, faces, w_pf=1.0, w_fp=1.0):
+    """w_pf * mean over (sample, point) of the squared distance to the closest TRIANGLE of the mesh + w_fp * mean over (sample, face) of the
+    squared distance to the face's closest point, a 0-d tensor: points [B, N, 3], verts [B, V, 3], faces [F, 3] (an int tensor on the
+    device, one topology for the batch), any N, V, F >= 1 (include/hifihr.h "Point-to-mesh distance").  At unit weights it is PyTorch3D's
+    point_mesh_face_distance [recalled; parity unpinned].  Searched in fp64 with ties to the lowest index; the gradient takes the choices
+    and the barycentric weights of the closest points as constants and goes to whichever of points, verts requires one.  A weight of
+    exactly 0 drops that direction AND its search.  One kernel pair (csrc/point_mesh.hip), no CPU path."""
+    return _PointMesh.apply(points, verts, faces, float(w_pf), float(w_fp))
+
+
+def point_mesh_sums(points, verts, faces, w_pf=1.0, w_fp=1.0):
+    """float64 [B, 2]: per sample the SUMS of squared distances (points -> their closest faces, faces -> their closest points); no autograd
+    (the evaluation metric).  The weights only select: a direction of weight exactly 0 is not searched and its column is 0."""
+    with torch.no_grad():
+        return _point_mesh_run(points.detach(), verts.detach(), faces, float(w_pf), float(w_fp))["sums"]
 
 
 # ------------------------------------------------------------------------------------------------

@@ -35,6 +35,12 @@ _DEFAULTS = dict(
     # weight of the opt-in term "chamfer" (hifihr_amd/ops.py chamfer_distance): the weight of PyTorch3D's mesh-fitting tutorial [recalled]
     # -- a starting point, not a tuned value.  The term is in SQUARED metres (1 cm off is 1e-4), so a real run will need it much larger
     lambda_chamfer=1.0,
+    # weights of the opt-in term "point_mesh" (hifihr_amd/ops.py point_mesh_distance): target points -> the predicted surface, and predicted
+    # faces -> the target points.  Starting points, not tuned values; the term is in SQUARED metres like "chamfer".  The second is 0, which
+    # also skips its search: against a sparse target that direction's minimum is not zero, the very problem the term exists to avoid
+    lambda_point_mesh=1.0,
+    lambda_point_mesh_faces=0.0,
+    point_mesh_metric=False,   # the evaluation pass also reports mesh_p2s / mesh_al_p2s (hifihr_amd/evaluate.py Evaluator(point_mesh=True))
     chamfer_metric=False,    # the evaluation pass also reports mesh_chamfer / mesh_al_chamfer (hifihr_amd/evaluate.py Evaluator(chamfer=True))
 )
 

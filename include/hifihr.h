@@ -361,6 +361,78 @@ int hifihr_chamfer_bwd(const float* x_d, const float* y_d, const int32_t* idx_xy
                        int M, float w_xy, float w_yx, float* gx_d /* or NULL */, float* gy_d /* or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Point-to-mesh distance (csrc/point_mesh.hip): the loss term `point_mesh` and the evaluation metric of the same name, the squared distance
+ * between a point cloud and the SURFACE of a triangle mesh.  At unit weights it is PyTorch3D's point_mesh_face_distance [recalled]: parity
+ * with PyTorch3D is unpinned (no PyTorch3D is available here, and its min_triangle_area handling of small faces is not reproduced).
+ * tests/point_mesh_ref.py restates the definition below in float64.
+ *
+ * Definition, per sample b: points p = p_d[b] [N][3], vertices v = v_d[b] [V][3], ONE face table faces_d [F][3] for the batch, whose
+ * entries are clamped into [0, V) on load.  fp32 in, every operation in fp64, this order, no contraction; dot(x, y) = (x0 y0 + x1 y1) + x2 y2.
+ *   the record of face f = (i0, i1, i2):  a = v[i0], ab = v[i1] - a, ac = v[i2] - a, abab = dot(ab, ab), abac = dot(ab, ac), acac = dot(ac, ac)
+ *   for a point p:  ap = p - a, d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = d1 - abab, d4 = d2 - abac, d5 = d1 - abac, d6 = d2 - acac
+ *     vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, e1 = d1 - d3, e2 = d2 - d6, e3a = d4 - d3, e3b = d5 - d6, e3 = e3a + e3b,
+ *     den = (va + vb) + vc
+ *   the closest point cp(p, f) = a + (ab w1 + ac w2) of the triangle, by the region form of Ericson's closest-point-on-triangle (Real-Time
+ *   Collision Detection, 5.1.5), the FIRST region whose test holds, weights (w0, w1, w2) of (i0, i1, i2):
+ *     vertex a:  d1 <= 0 and d2 <= 0                                  (1, 0, 0)
+ *     vertex b:  d3 >= 0 and d4 <= d3                                 (0, 1, 0)
+ *     edge ab:   vc <= 0 and d1 >= 0 and d3 <= 0 and e1 > 0           (1 - q, q, 0),   q = d1 / e1
+ *     vertex c:  d6 >= 0 and d5 <= d6                                 (0, 0, 1)
+ *     edge ac:   vb <= 0 and d2 >= 0 and d6 <= 0 and e2 > 0           (1 - q, 0, q),   q = d2 / e2
+ *     edge bc:   va <= 0 and e3a >= 0 and e3b >= 0 and e3 > 0         (0, 1 - q, q),   q = e3a / e3
+ *     interior:  den > 0        q = 1 / den, w1 = clamp(vb q, 0, 1), w2 = clamp(vc q, 0, 1 - w1), w0 = (1 - w1) - w2
+ *     otherwise (not reachable in exact arithmetic): vertex a
+ *   Every denominator is guarded by its region's test, so there is no division by zero and no square root; every weight is >= 0 and they sum
+ *   to 1 within an ulp.  A zero-area face (collinear or coincident vertices) has va = vb = vc = 0 in exact arithmetic and falls to the vertex
+ *   and edge regions of the segment or point it degenerates to (an edge of length 0 is skipped by its guard): a finite distance, never a NaN.
+ *   d2(p, f) = (dx dx + dy dy) + dz dz,   dx = ap0 - (ab0 w1 + ac0 w2), ...
+ *   a[i] = the f that minimises (d2(p_i, f), f) lexicographically: ties go to the LOWEST index;  c[f] = the i that minimises (d2(p_i, f), i)
+ *   sum_pf[b] = sum_i d2(p_i, a[i]),   sum_fp[b] = sum_f d2(p_c[f], f)
+ *   value = w_pf mean_b (sum_pf[b] / N) + w_fp mean_b (sum_fp[b] / F), rounded to fp32 once
+ * A direction whose weight is exactly 0 is NOT SEARCHED: it contributes exactly 0, gets no gradient, its index, weight and minimum arrays
+ * are left untouched and its column of sums_d is written as 0.
+ * Gradient: the choices a, c and the weights are constants (exact away from the region boundaries: the envelope property of the constrained
+ * minimum).  With r(i, f) = p_i - cp computed as dx, dy, dz above from the STORED w1, w2, c_pf = w_pf 2 / (B N), c_fp = w_fp 2 / (B F), the
+ * inner sums in ascending index order, in fp64, rounded to fp32 once:
+ *   gp[i] = gout ( c_pf r(i, a[i]) + c_fp sum over { f : c[f] == i } of r(i, f) )
+ *   slab[f][k] = -( c_pf sum over { i : a[i] == f } of w_k(i) r(i, f)  +  c_fp w_k(f) r(c[f], f) )           k = 0, 1, 2: the face's corners
+ *   gv[u] = gout sum over the corners (f, k) with faces[f][k] == u, ascending in 3 f + k, of slab[f][k]
+ * The library is built with -ffp-contract=off, so d2, a, c and the weights are the bits and integers of any float64 evaluation of the same
+ * expressions (the one division per pair is IEEE-rounded).
+ *
+ * hifihr_point_mesh_geometry writes the kernels' four constants (any pointer may be NULL): the points one workgroup takes and the face
+ *   records of one LDS pass (points -> faces), the faces one workgroup takes and the points of one LDS pass (faces -> points).  The four
+ *   waves of a workgroup scan consecutive quarters of a pass.  The tests build their cases round these boundaries.
+ * hifihr_point_mesh_workspace_bytes: the size of ws_d (partial sums, then the backward's per-corner slab of B F 9 doubles); 0 for B < 0 or
+ *   N, V, F < 1; it never decreases with B.  Forward and backward take the same workspace size; the backward reads nothing the forward left.
+ * v2c_off_d [V + 1], v2c_corner_d [3 F] (int32): the vertex -> corner table, built by the host once per face table: corner 3 f + k belongs
+ *   to vertex faces[f][k]; v2c_corner lists the corners vertex by vertex, ascending inside a vertex; v2c_off[u] .. v2c_off[u + 1] is vertex
+ *   u's range.  Entries are clamped on load.
+ * Refused (HIFIHR_EINVAL, nothing launched, nothing written): a NULL among the required pointers (every pointer except gp_d, gv_d and
+ *   stream), B < 0, N < 1, V < 1, F < 1, a weight that is not finite, a grid beyond 2^31 - 1 workgroups (B (ceil(N / points per
+ *   workgroup) + ceil(F / faces per workgroup)), B ceil(max(N, V, F) / 256)).
+ * Accepted: B == 0 is a no-op; hifihr_point_mesh_bwd with gp_d == gv_d == NULL is a no-op; one of them NULL skips that gradient.
+ * Overwritten: hifihr_point_mesh_fwd writes, for every searched direction, EVERY element of idx_pf_d[B][N] / idx_fp_d[B][F] (int32),
+ *   bary_pf_d[B][N][3] / bary_fp_d[B][F][3] (double: w0, w1, w2 at the arg-min), min_pf_d[B][N] / min_fp_d[B][F] (double: d2 at the
+ *   arg-min); always sums_d[B][2] (double: sum_pf, sum_fp) and out_d[1]; ws_d is scratch.  hifihr_point_mesh_bwd OVERWRITES every element
+ *   of gp_d[B][N][3] and gv_d[B][V][3] (a vertex of no face gets 0).  It takes the gradient of the value as the DEVICE scalar gout_d[1] and
+ *   must be given the forward's weights, index and weight arrays.
+ * Repeatable: no atomics.  The search keeps (d2, index) pairs and compares them lexicographically wherever two candidates meet; partial
+ *   sums are folded in a fixed order; the backward takes both scatters as gathers with one writer per element: the same bits on every call.
+ * Preconditions, NOT checked: finite coordinates.  A NaN or an Inf gives unspecified values, never an out-of-range access: an index starts
+ *   at 0 and is only ever replaced by a loop counter, a d2 that is not a number never wins, and every index read from memory is clamped.
+ * No allocation and no synchronisation inside the entries: they can be captured into a hipGraph. */
+void hifihr_point_mesh_geometry(int* points_per_wg, int* faces_per_pass, int* faces_per_wg, int* points_per_pass);
+size_t hifihr_point_mesh_workspace_bytes(int B, int N, int V, int F);
+int hifihr_point_mesh_fwd(const float* p_d, const float* v_d, const int32_t* faces_d, int B, int N, int V, int F, float w_pf, float w_fp,
+                          int32_t* idx_pf_d, double* bary_pf_d, double* min_pf_d, int32_t* idx_fp_d, double* bary_fp_d, double* min_fp_d,
+                          double* sums_d, float* out_d, void* ws_d, void* stream);
+int hifihr_point_mesh_bwd(const float* p_d, const float* v_d, const int32_t* faces_d, const int32_t* idx_pf_d, const double* bary_pf_d,
+                          const int32_t* idx_fp_d, const double* bary_fp_d, const float* gout_d, const int32_t* v2c_off_d,
+                          const int32_t* v2c_corner_d, int B, int N, int V, int F, float w_pf, float w_fp, float* gp_d /* or NULL */,
+                          float* gv_d /* or NULL */, void* ws_d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Texture-PCA decode (csrc/texpca.hip): tex[b][n] = mean[n] (or 0 when NULL) + sum_k coef[b][k] basis[k][n], K <= 32, n % 4 == 0.
  * The texture half of the NIMBLE layer as the reference consumes it (models_res_nimble.py:57,133-142: texture_params [B,10] -> the
  * hand's texture).  NIMBLE's own basis is not available: the caller supplies one (n = 778 * 3 vertex

@@ -269,13 +269,14 @@ def make_evaluator(args, device):
     paths = getattr(args, "lpips_weights", None)
     bench = bool(getattr(args, "benchmark_metrics", True))          # the FreiHAND benchmark's PCK / AUC and F-score keys
     cham = bool(getattr(args, "chamfer_metric", False))             # mesh_chamfer / mesh_al_chamfer beside the F-scores
+    p2s = bool(getattr(args, "point_mesh_metric", False))           # mesh_p2s / mesh_al_p2s: ground-truth vertices -> the predicted surface
     if not paths:
-        return Evaluator(benchmark=bench, chamfer=cham)
+        return Evaluator(benchmark=bench, chamfer=cham, point_mesh=p2s)
     key = (str(device), tuple(paths))
     if key not in _LPIPS:
         from hifihr_amd.lpips import LPIPS, load_lpips_weights
         _LPIPS[key] = load_lpips_weights(LPIPS(net="alex"), *paths).to(device)
-    return Evaluator(lpips_fn=_LPIPS[key], benchmark=bench, chamfer=cham)
+    return Evaluator(lpips_fn=_LPIPS[key], benchmark=bench, chamfer=cham, point_mesh=p2s)
 
 
 def run_evaluation_ho3d(model, cache, args, device, epoch):
@@ -316,10 +317,11 @@ def run_evaluation(model, cache, arrays, args, device):
 
 def benchmark_report(summary):
     """The twelve values of the FreiHAND benchmark's scores.txt, under its names (those the summary holds); with the option
-    chamfer_metric the two Chamfer distances (inputs' unit squared) follow the F-scores."""
-    from hifihr_amd.evaluate import BENCHMARK_KEYS, CHAMFER_KEYS
+    chamfer_metric the two Chamfer distances (inputs' unit squared) follow the F-scores, with point_mesh_metric the two point-to-surface
+    distances after them."""
+    from hifihr_amd.evaluate import BENCHMARK_KEYS, CHAMFER_KEYS, POINT_MESH_KEYS
     lines = [f"{k}: {summary[k]:.6f}" for k in BENCHMARK_KEYS if k in summary]
-    return "\n".join(lines + [f"{k}: {summary[k]:.6e}" for k in CHAMFER_KEYS if k in summary])
+    return "\n".join(lines + [f"{k}: {summary[k]:.6e}" for k in CHAMFER_KEYS + POINT_MESH_KEYS if k in summary])
 
 
 def main(argv=None):
@@ -383,7 +385,7 @@ def main(argv=None):
     if "evaluation" in args.mode:
         summary = run_evaluation(model, eval_cache or cache, eval_arrays or train_arrays, args, device)
         say("[train_hrnet] evaluation:", summary)
-        if getattr(args, "benchmark_metrics", True) or getattr(args, "chamfer_metric", False):
+        if getattr(args, "benchmark_metrics", True) or getattr(args, "chamfer_metric", False) or getattr(args, "point_mesh_metric", False):
             say("[train_hrnet] benchmark scores:\n" + benchmark_report(summary))
         return 0
 
