@@ -283,6 +283,15 @@ class HifihrLib:
         c.hifihr_soft_sil_loss_fwd.argtypes = [_c_float_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, _c_float_p, c_void_p]
         c.hifihr_soft_sil_loss_bwd.argtypes = [_c_float_p, c_void_p, c_int, c_void_p, _c_float_p, c_int, c_int, c_float, c_float, _c_float_p,
                                                c_void_p]
+        c.hifihr_render_depth_workspace_bytes.argtypes = [c_void_p, c_int]
+        c.hifihr_render_depth_workspace_bytes.restype = c_size_t
+        c.hifihr_render_depth_fwd.argtypes = [c_void_p, _c_float_p, _c_float_p, _c_int_p, c_int, _c_float_p, _c_int_p, c_void_p]
+        c.hifihr_render_depth_bwd.argtypes = [c_void_p, _c_float_p, _c_float_p, _c_int_p, _c_float_p, _c_int_p, c_int, _c_float_p, c_void_p,
+                                              c_void_p]
+        c.hifihr_depth_loss_fwd.argtypes = [_c_float_p, _c_int_p, _c_float_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p,
+                                            _c_float_p, c_void_p]
+        c.hifihr_depth_loss_bwd.argtypes = [_c_float_p, _c_int_p, _c_float_p, c_void_p, c_int, c_void_p, _c_float_p, c_int, c_int, c_float,
+                                            c_float, _c_float_p, c_void_p]
         c.hifihr_mesh_topology_create.argtypes = [_c_int_p, c_int, c_int]
         c.hifihr_mesh_topology_create.restype = c_void_p
         c.hifihr_mesh_topology_destroy.argtypes = [c_void_p]
@@ -1214,6 +1223,43 @@ class HifihrLib:
         self.check(self.c.hifihr_soft_sil_loss_bwd(_fp(alpha), mp, kind, c_void_p(sums.data_ptr()), _fp(gout), B, alpha.numel() // max(B, 1),
                                                    c_float(lam_sil), c_float(lam_iou), _fp(galpha), _stream_of(alpha)),
                    "hifihr_soft_sil_loss_bwd")
+
+    # ---- depth map and depth loss (csrc/depth.hip) -------------------------
+    def render_depth_workspace_bytes(self, h, B) -> int:
+        return int(self.c.hifihr_render_depth_workspace_bytes(h, int(B)))
+
+    def render_depth_fwd(self, h, verts, cam, face_id, depth, hits):
+        """face_id int32 [B, S, S] as render_fwd wrote it for the same verts and cam; depth float32 [B, ..., H, H], hits int32 [B, H, H]."""
+        assert face_id.dtype == torch.int32 and hits.dtype == torch.int32 and face_id.is_contiguous()
+        self.check(self.c.hifihr_render_depth_fwd(h, _fp(verts), _fp(cam), _ip(face_id), verts.shape[0], _fp(depth), _ip(hits),
+                                                  _stream_of(verts)), "hifihr_render_depth_fwd")
+
+    def render_depth_bwd(self, h, verts, cam, face_id, gdepth, hits, gverts, ws):
+        self.check(self.c.hifihr_render_depth_bwd(h, _fp(verts), _fp(cam), _ip(face_id), _fp(gdepth), _ip(hits), verts.shape[0], _fp(gverts),
+                                                  c_void_p(ws.data_ptr()), _stream_of(verts)), "hifihr_render_depth_bwd")
+
+    def _depth_mask_arg(self, mask, n):
+        if mask is None:
+            return None, 0
+        assert mask.numel() == n, (mask.shape, n)
+        return self._mask_arg(mask)
+
+    def depth_loss_fwd(self, depth, hits, target, mask, lam, trunc, sums, out):
+        """depth [B, ...]; hits int32 and target float32 of the same element count; mask None, float32 or int64; sums float64 [B, 2];
+        out float32 [1] (include/hifihr.h "Depth map")."""
+        B = depth.shape[0]
+        assert sums.dtype == torch.float64 and sums.is_contiguous() and hits.dtype == torch.int32
+        assert hits.numel() == depth.numel() and target.numel() == depth.numel(), (depth.shape, hits.shape, target.shape)
+        mp, kind = self._depth_mask_arg(mask, depth.numel())
+        self.check(self.c.hifihr_depth_loss_fwd(_fp(depth), _ip(hits), _fp(target), mp, kind, B, depth.numel() // max(B, 1), c_float(lam),
+                                                c_float(trunc), c_void_p(sums.data_ptr()), _fp(out), _stream_of(depth)), "hifihr_depth_loss_fwd")
+
+    def depth_loss_bwd(self, depth, hits, target, mask, sums, gout, lam, trunc, gdepth):
+        B = depth.shape[0]
+        mp, kind = self._depth_mask_arg(mask, depth.numel())
+        self.check(self.c.hifihr_depth_loss_bwd(_fp(depth), _ip(hits), _fp(target), mp, kind, c_void_p(sums.data_ptr()), _fp(gout), B,
+                                                depth.numel() // max(B, 1), c_float(lam), c_float(trunc), _fp(gdepth), _stream_of(depth)),
+                   "hifihr_depth_loss_bwd")
 
     # ---- mesh regularisers (csrc/mesh_reg.hip) ----------------------------
     def mesh_topology_create(self, faces, V) -> c_void_p:

@@ -456,6 +456,52 @@ int hifihr_soft_sil_loss_bwd(const float* alpha, const void* mask, int mask_i64,
   return HIFIHR_OK;
 }
 
+size_t hifihr_render_depth_workspace_bytes(const hifihr_renderer_t* h, int B) {
+  if (!h || B < 0) return 0;
+  return hifihr::render_depth_workspace_bytes(h->dev, B);
+}
+
+int hifihr_render_depth_fwd(const hifihr_renderer_t* h, const float* verts, const float* cam, const int32_t* face_id, int B, float* depth,
+                            int32_t* hits, void* stream) {
+  if (!h || !verts || !cam || !face_id || !depth || !hits || B < 0) return fail(HIFIHR_EINVAL, "hifihr_render_depth_fwd: bad argument");
+  if (B == 0) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_render_depth_fwd(h->dev, verts, cam, face_id, B, depth, hits, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_render_depth_bwd(const hifihr_renderer_t* h, const float* verts, const float* cam, const int32_t* face_id, const float* gdepth,
+                            const int32_t* hits, int B, float* gverts, void* ws, void* stream) {
+  if (!h || !verts || !cam || !face_id || !gdepth || !hits || !gverts || !ws || B < 0)
+    return fail(HIFIHR_EINVAL, "hifihr_render_depth_bwd: bad argument");
+  if (B == 0) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_render_depth_bwd(h->dev, verts, cam, face_id, gdepth, hits, B, gverts, ws, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+namespace {
+bool depth_loss_params_ok(int mask_i64, int B, int HW, float lam, float trunc) {
+  return B >= 0 && HW > 0 && mask_i64 >= 0 && mask_i64 <= 1 && std::isfinite(lam) && std::isfinite(trunc) && trunc >= 0.f;
+}
+}  // namespace
+
+int hifihr_depth_loss_fwd(const float* depth, const int32_t* hits, const float* target, const void* mask, int mask_i64, int B, int HW, float lam,
+                          float trunc, double* sums, float* out, void* stream) {
+  if (!depth || !hits || !target || !sums || !out || !depth_loss_params_ok(mask_i64, B, HW, lam, trunc))
+    return fail(HIFIHR_EINVAL, "hifihr_depth_loss_fwd: bad argument (HW > 0, lam finite, trunc finite and >= 0, mask_i64 0 or 1)");
+  if (B == 0) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_depth_loss_fwd(depth, hits, target, mask, mask_i64, B, HW, lam, trunc, sums, out, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_depth_loss_bwd(const float* depth, const int32_t* hits, const float* target, const void* mask, int mask_i64, const double* sums,
+                          const float* gout, int B, int HW, float lam, float trunc, float* gdepth, void* stream) {
+  if (!depth || !hits || !target || !sums || !gout || !gdepth || B > 65535 || !depth_loss_params_ok(mask_i64, B, HW, lam, trunc))
+    return fail(HIFIHR_EINVAL, "hifihr_depth_loss_bwd: bad argument (B <= 65535, HW > 0, lam finite, trunc finite and >= 0, mask_i64 0 or 1)");
+  if (B == 0) return HIFIHR_OK;
+  HIP_TRY(hifihr::launch_depth_loss_bwd(depth, hits, target, mask, mask_i64, sums, gout, B, HW, lam, trunc, gdepth, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
 hifihr_mesh_topology_t* hifihr_mesh_topology_create(const int32_t* faces, int F, int V) {
   if (!faces || F <= 0 || V <= 0) {
     fail(HIFIHR_EINVAL, "hifihr_mesh_topology_create: bad argument (faces, F > 0, V > 0)");

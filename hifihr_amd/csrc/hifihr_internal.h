@@ -115,6 +115,17 @@ hipError_t launch_soft_sil_loss_fwd(const float* alpha, const void* mask, int ma
 hipError_t launch_soft_sil_loss_bwd(const float* alpha, const void* mask, int mask_i64, const double* sums, const float* gout, int B, int HW,
                                     float lam_s, float lam_i, float* galpha, hipStream_t st);
 
+// Depth map of the hard render from its face_id, and the masked depth loss (csrc/depth.hip); the renderer handle's faces, V, F, H and aa
+size_t render_depth_workspace_bytes(const RenderDev& r, int B);
+hipError_t launch_render_depth_fwd(const RenderDev& r, const float* verts, const float* cam, const int* face_id, int B, float* depth, int* hits,
+                                   hipStream_t st);
+hipError_t launch_render_depth_bwd(const RenderDev& r, const float* verts, const float* cam, const int* face_id, const float* gdepth,
+                                   const int* hits, int B, float* gverts, void* ws, hipStream_t st);
+hipError_t launch_depth_loss_fwd(const float* depth, const int* hits, const float* target, const void* mask, int mask_i64, int B, int HW, float lam,
+                                 float trunc, double* sums, float* out, hipStream_t st);
+hipError_t launch_depth_loss_bwd(const float* depth, const int* hits, const float* target, const void* mask, int mask_i64, const double* sums,
+                                 const float* gout, int B, int HW, float lam, float trunc, float* gdepth, hipStream_t st);
+
 // Implicit-GEMM convolution geometry.  src [N][IH][IW][IC] is gathered, dst [N][OH][OW][OC] is written.
 // forward: src = x, dst = y (ih = oh*stride - pad + r); dgrad = 1: src = dy, dst = dx (ih = (oh + pad - r)/stride).
 struct ConvGeom {

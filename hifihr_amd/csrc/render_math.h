@@ -156,6 +156,40 @@ HIFIHR_HD void bary_bwd(const FaceXYZ& f, float px, float py, const float* gb, f
   g[0] = gx0; g[1] = gy0; g[2] = gz0; g[3] = gx1; g[4] = gy1; g[5] = gz1; g[6] = gx2; g[7] = gy2; g[8] = gz2;
 }
 
+// Reverse mode of the depth of a covered sample, pz = b0 z0 + b1 z1 + b2 z2 with b = bary_of(f, px, py) (csrc/depth.hip): gz = d loss / d pz
+// -> g[9] as for bary_bwd, overwritten.  The z_i enter twice: as the weights' factors and through the perspective correction.  Unlike
+// bary_bwd, the max(., eps) of the denominator is a piecewise constant choice here (include/hifihr.h "Depth map"): where it clamps, the
+// denominator carries no gradient.
+HIFIHR_HD void pz_bwd(const FaceXYZ& f, float px, float py, float gz, float* g) {
+  const float area = edge_fn(f.x2, f.y2, f.x0, f.y0, f.x1, f.y1) + kRasterEps;
+  const float e0 = edge_fn(px, py, f.x1, f.y1, f.x2, f.y2);
+  const float e1 = edge_fn(px, py, f.x2, f.y2, f.x0, f.y0);
+  const float e2 = edge_fn(px, py, f.x0, f.y0, f.x1, f.y1);
+  const float w0 = e0 / area, w1 = e1 / area, w2 = e2 / area;
+  const float t0 = w0 * f.z1 * f.z2, t1 = f.z0 * w1 * f.z2, t2 = f.z0 * f.z1 * w2;
+  const float tsum = t0 + t1 + t2;
+  const float denom = fmaxf(tsum, kRasterEps);
+  const float b0 = t0 / denom, b1 = t1 / denom, b2 = t2 / denom;
+  const float gb0 = gz * f.z0, gb1 = gz * f.z1, gb2 = gz * f.z2;
+  const float gden = (tsum > kRasterEps) ? -(t0 * gb0 + t1 * gb1 + t2 * gb2) / (denom * denom) : 0.f;
+  const float gt0 = gden + gb0 / denom, gt1 = gden + gb1 / denom, gt2 = gden + gb2 / denom;
+  const float gw0 = gt0 * f.z1 * f.z2, gw1 = gt1 * f.z0 * f.z2, gw2 = gt2 * f.z0 * f.z1;
+  const float gz0 = gt1 * w1 * f.z2 + gt2 * f.z1 * w2 + gz * b0;
+  const float gz1 = gt0 * w0 * f.z2 + gt2 * f.z0 * w2 + gz * b1;
+  const float gz2 = gt0 * w0 * f.z1 + gt1 * f.z0 * w1 + gz * b2;
+  const float ge0 = gw0 / area, ge1 = gw1 / area, ge2 = gw2 / area;
+  const float garea = -(gw0 * w0 + gw1 * w1 + gw2 * w2) / area;
+  float gx0 = 0.f, gy0 = 0.f, gx1 = 0.f, gy1 = 0.f, gx2 = 0.f, gy2 = 0.f;
+  // the edge functions' derivatives as in bary_bwd
+  gx1 += ge0 * (py - f.y2); gy1 += ge0 * (f.x2 - px); gx2 += ge0 * -(py - f.y1); gy2 += ge0 * (px - f.x1);
+  gx2 += ge1 * (py - f.y0); gy2 += ge1 * (f.x0 - px); gx0 += ge1 * -(py - f.y2); gy0 += ge1 * (px - f.x2);
+  gx0 += ge2 * (py - f.y1); gy0 += ge2 * (f.x1 - px); gx1 += ge2 * -(py - f.y0); gy1 += ge2 * (px - f.x0);
+  gx0 += garea * (f.y2 - f.y1); gy0 += garea * (f.x1 - f.x2);
+  gx1 += garea * -(f.y2 - f.y0); gy1 += garea * (f.x2 - f.x0);
+  gx2 += garea * (f.y1 - f.y0); gy2 += garea * -(f.x1 - f.x0);
+  g[0] = gx0; g[1] = gy0; g[2] = gz0; g[3] = gx1; g[4] = gy1; g[5] = gz1; g[6] = gx2; g[7] = gy2; g[8] = gz2;
+}
+
 // ---- Phong shading of one covered sample (PyTorch3D phong_shading / _apply_lighting / DirectionalLights) ----
 struct ShadeConsts {       // per renderer
   float amb[3];            // materials.ambient_color * lights.ambient_color

@@ -15,7 +15,9 @@ benchmark's eval.py nor open3d is available here: its parity with the benchmark'
 The Chamfer distance, the number mesh papers report beside the F-score, is opt-in: `chamfer` and `Evaluator(chamfer=True)` (csrc/chamfer.hip,
 the kernels of the loss term of the same name; pinned to the reference's unwired ChamferLoss by tests/golden/chamfer.npz).  So is the mean
 squared distance from the ground-truth vertices to the predicted SURFACE: `point_to_surface` and `Evaluator(point_mesh=True)`
-(csrc/point_mesh.hip, the kernels of the loss term `point_mesh`; parity with PyTorch3D's point_mesh_face_distance is unpinned)."""
+(csrc/point_mesh.hip, the kernels of the loss term `point_mesh`; parity with PyTorch3D's point_mesh_face_distance is unpinned).  The
+error of the rendered depth map against a depth image, `depth_mae`, is opt-in too: `depth_error` and `Evaluator(depth=True)`
+(csrc/depth.hip, the kernel of the loss term `depth`)."""
 from __future__ import annotations
 
 import numpy as np
@@ -132,11 +134,22 @@ def point_to_surface(pred_verts, faces, gt_points):
     return ops.point_mesh_sums(gt_points, pred_verts, faces, 1.0, 0.0)[:, 0] / float(gt_points.shape[1])
 
 
+def depth_error(pred_depth, hits, gt_depth, mask=None):
+    """A float64 scalar on the device: the mean |pred_depth - gt_depth| over the valid pixels of the batch, in the inputs' unit -- a pixel is
+    valid where the mesh covers it (hits > 0), the depth image measures (gt_depth > 0) and the mask (None: everywhere) is not 0.
+    pred_depth [B, 1, H, W] and hits [B, H, W] from ops.render_depth, gt_depth [B, H, W].  It is the loss term `depth` at lambda = 1 and
+    trunc = 0 (ops.depth_loss, the same kernel); 0 when no pixel is valid."""
+    from . import ops
+    s = ops.depth_loss_sums(pred_depth, hits, gt_depth, mask).sum(0)
+    return s[0] / s[1].clamp(min=1.0)
+
+
 class Evaluator:
     """Accumulates what the evaluation loop keeps (train_hrnet.py:119-161) and reduces it as :216-272 does."""
 
-    def __init__(self, ssim_fn=None, lpips_fn=None, benchmark=False, chamfer=False, point_mesh=False, faces=None):
+    def __init__(self, ssim_fn=None, lpips_fn=None, benchmark=False, chamfer=False, point_mesh=False, faces=None, depth=False):
         self.xyz_pred, self.verts_pred, self.texture = [], [], []
+        self.depth, self.depth_sums = bool(depth), []      # summary() adds 'depth_mae' when the batches carried 're_depth' and 'depths'
         self.benchmark = bool(benchmark)          # summary() adds BENCHMARK_KEYS when ground truth is given
         self.chamfer = bool(chamfer)              # summary() adds CHAMFER_KEYS when verts_gt is given
         self.point_mesh = bool(point_mesh)        # summary() adds POINT_MESH_KEYS when verts_gt is given
@@ -154,6 +167,12 @@ class Evaluator:
         self.verts_pred.append(outputs["mano_verts"].detach())
         if self.point_mesh and self.faces is None:
             self.faces = outputs.get("_faces_i32")
+        if self.depth and render:
+            if "re_depth" not in outputs or examples.get("depths") is None:
+                raise ValueError("Evaluator(depth=True) needs outputs['re_depth'] (Model(..., render_depth=True)) and examples['depths']")
+            from . import ops
+            self.depth_sums.append(ops.depth_loss_sums(outputs["re_depth"], outputs["_re_depth_hits"], examples["depths"],
+                                                       examples.get("segms_gt")))          # [B, 2] on the device
         if render and "re_img" in outputs:
             if dat_name == "HO3D":
                 m = (outputs["re_sil"] > 0).float()
@@ -191,7 +210,8 @@ class Evaluator:
         adds CHAMFER_KEYS when verts_gt is given: the two directions of `chamfer` summed, averaged over the samples, in the inputs' unit
         SQUARED; taken on the same two pairs of point sets as the F-scores.  An Evaluator(point_mesh=True) adds POINT_MESH_KEYS the same
         way: the mean squared distance from the ground-truth vertices to the predicted SURFACE (point_to_surface), averaged over the
-        samples, un-aligned and aligned."""
+        samples, un-aligned and aligned.  An Evaluator(depth=True) adds 'depth_mae': the mean |re_depth - depths| over the valid pixels
+        of every collected batch (depth_error's definition with the mask segms_gt), in the inputs' unit."""
         out, bench = {}, []
         mesh_extra = self.chamfer or self.point_mesh
         if self.point_mesh and verts_gt is not None and self.faces is None:
@@ -220,6 +240,9 @@ class Evaluator:
             for k in self.texture[0]:
                 out[k] = float(torch.stack([r[k] for r in self.texture]).mean())
             out.setdefault("lpips", None)
+        if self.depth and self.depth_sums:
+            s = torch.cat(self.depth_sums).sum(0).tolist()
+            out["depth_mae"] = s[0] / max(s[1], 1.0)
         return out
 
     @staticmethod

@@ -6,7 +6,9 @@ edge-length / shape / pose terms (csrc/losses.hip: two launches per group instea
 tensor raises (no fallback).  joint_2d / bone_direc / bone_direc_3d: one more kernel pair (round 3).  triangle / normal_consistency (the
 reference's uniform-Laplacian term and, not in the reference, its usual partner): one kernel pair (csrc/mesh_reg.hip).  chamfer (the reference's
 unwired ChamferLoss): one kernel pair (csrc/chamfer.hip).  point_mesh (not in the
-reference: the distance of the target points to the SURFACE of the predicted mesh): one kernel pair (csrc/point_mesh.hip).  sil_soft / iou_soft (not in the
+reference: the distance of the target points to the SURFACE of the predicted mesh): one kernel pair (csrc/point_mesh.hip).  depth (declared and
+never computed in the reference: the mean |rendered depth - depth image| on the model's opt-in depth map, outputs['re_depth']): one kernel pair
+(csrc/depth.hip).  sil_soft / iou_soft (not in the
 reference: `sil` and `iou` on the model's opt-in differentiable silhouette, outputs['re_sil_soft']): one kernel pair (csrc/soft_sil.hip).  lpips (not in the
 reference: LPIPS(alex), the evaluation pass's texture metric, as an opt-in loss): hifihr_amd/lpips.py with its HIP backward (csrc/lpips.hip).  The rarely used terms (mscale, scale,
 iou, mtex and the self-supervised `*_self` terms) are a handful of torch ops on the same GPU tensors.  The torch restatement of the whole function that the tests
@@ -27,7 +29,7 @@ _BONES = [(0, 1), (1, 2), (2, 3), (3, 4), (0, 5), (5, 6), (6, 7), (7, 8), (0, 9)
 # every name LossFunction.__call__ can produce (a name outside it in `losses` is ignored here and stops traineval's step with a KeyError)
 TERMS = ("joint_3d", "vert_3d", "edge_length", "mshape", "mpose", "joint_2d", "bone_direc", "bone_direc_3d", "mscale", "scale", "texture",
          "mrgb", "ssim_tex", "sil", "texture_self", "mrgb_self", "ssim_tex_self", "perceptual", "iou", "sil_soft", "iou_soft", "triangle",
-         "normal_consistency", "lpips", "chamfer", "point_mesh", "mtex")
+         "normal_consistency", "lpips", "chamfer", "point_mesh", "depth", "mtex")
 
 _BONE_IDX = {}
 
@@ -280,6 +282,16 @@ class LossFunction:
                     faces = outputs["mano_faces"][0].int().contiguous()
             loss_dic["point_mesh"] = ops.point_mesh_distance(target, verts, faces, args.lambda_point_mesh, args.lambda_point_mesh_faces)
             self._total_parts.append((loss_dic["point_mesh"], 1, ["point_mesh"]))
+        if "depth" in loss_used:
+            # declared, never wired in the reference (options lambda_depth, the dataset's depth_crop, a mention of outputs['re_depth'] in its
+            # loss code; its model renders no depth): lambda_depth * mean |re_depth - depths| over the pixels the mesh covers, the depth image
+            # measures (> 0), the hand mask keeps and -- with depth_trunc > 0 -- that lie within depth_trunc of the target, one kernel pair
+            # (csrc/depth.hip).  Dense, absolute in Z and free of correspondences.  examples['depths'] [B, H, W] is in the unit of the vertices
+            assert "re_depth" in outputs and "_re_depth_hits" in outputs, (
+                "the loss term 'depth' needs outputs['re_depth']: build the model with Model(..., render_depth=True) (options: render_depth)")
+            loss_dic["depth"] = ops.depth_loss(outputs["re_depth"], outputs["_re_depth_hits"], examples["depths"], examples.get("segms_gt"),
+                                               args.lambda_depth, getattr(args, "depth_trunc", 0.0))
+            self._total_parts.append((loss_dic["depth"], 1, ["depth"]))
         if "mtex" in loss_used and outputs.get("texture_params") is not None:
             loss_dic["mtex"] = args.lambda_tex_reg * F.mse_loss(outputs["texture_params"], torch.zeros_like(outputs["texture_params"]))
         return loss_dic

@@ -101,10 +101,14 @@ class MyNIMBLELayer(nn.Module):
 class Model(nn.Module):
     def __init__(self, ifRender, device, if_4c, hand_model, use_mean_shape, pretrain, root_id=9, root_id_nimble=11,
                  ifLight=True, mano_tables: ManoTables | None = None, image_size=224, aa_factor=3, texture_stand_in=0,
-                 nimble_tables: NimbleTables | None = None, conv_precision="fast", soft_silhouette=False, soft_sil_sigma=1e-4):
+                 nimble_tables: NimbleTables | None = None, conv_precision="fast", soft_silhouette=False, soft_sil_sigma=1e-4,
+                 render_depth=False):
         """soft_silhouette: with ifRender, the outputs also carry 're_sil_soft' [B, 1, H, H], a differentiable coverage of the same mesh and
         camera the hard render sees (ops.soft_silhouette with sigma = soft_sil_sigma; the terms "sil_soft" / "iou_soft" of LossFunction
         read it).  Off (default): the outputs and the launches are exactly those without the option.
+        render_depth: with ifRender, the outputs also carry 're_depth' [B, 1, H, H], the depth map of the same forward's hard render
+        (ops.render_depth on its face_id: no second rasterisation; the gradient goes to the vertices), and '_re_depth_hits' [B, H, H], the
+        covered samples per pixel; the term "depth" of LossFunction reads both.  Off (default): outputs and launches are unchanged.
         conv_precision: "fast" (default) -- the encoder's stride-1 3x3 convolutions run as Winograd F(4x4, 3x3) / F(2x2, 3x3); "reference"
         -- on the direct kernels, whose outputs round like a plain fp32 convolution: features within 5e-6 of the reference's instead of
         1.3e-5, for ~50 % more time per step.  The trunk's GRADIENT error against the reference (~1e-2 of a gradient's maximum on the
@@ -144,6 +148,7 @@ class Model(nn.Module):
         self._mesh_topo = ops.MeshTopology(self._mano_face_i32, 778)
         self.ifRender, self.ifLight, self.aa_factor, self.image_size = ifRender, ifLight, aa_factor, image_size
         self.soft_silhouette, self.soft_sil_sigma = bool(soft_silhouette), float(soft_sil_sigma)
+        self.render_depth = bool(render_depth)
         if ifRender:
             # Materials(diffuse .8, specular .2, shininess 30) + DirectionalLights defaults (ambient .5, specular .2)
             if not ifLight:
@@ -257,6 +262,8 @@ class Model(nn.Module):
             outputs["skin_verts"] = verts_cam
             if self.soft_silhouette:
                 outputs["re_sil_soft"] = ops.soft_silhouette(self.renderer_p3d, verts_cam, cam, self.soft_sil_sigma)
+            if self.render_depth:
+                outputs["re_depth"], outputs["_re_depth_hits"] = ops.render_depth(self.renderer_p3d, verts_cam, cam, face_id)
         outputs["mano_faces"] = self.mano_face.expand(images.shape[0], -1, -1)           # a view (the reference repeats)
         outputs["_faces_i32"] = self._mano_face_i32
         outputs["_mesh_topo"] = self._mesh_topo
@@ -290,6 +297,8 @@ class Model(nn.Module):
             outputs["face_id"], outputs["skin_verts"] = face_id, verts_cam
             if self.soft_silhouette:
                 outputs["re_sil_soft"] = ops.soft_silhouette(self.renderer_p3d, verts_cam, cam, self.soft_sil_sigma)
+            if self.render_depth:
+                outputs["re_depth"], outputs["_re_depth_hits"] = ops.render_depth(self.renderer_p3d, verts_cam, cam, face_id)
         outputs["mano_faces"] = self.mano_face.expand(B, -1, -1)
         outputs["_faces_i32"] = self._mano_face_i32
         outputs["_mesh_topo"] = self._mesh_topo

@@ -422,6 +422,94 @@ def soft_sil_losses(alpha, segms_gt, lam_sil, lam_iou):
     return _SoftSilLosses.apply(alpha, segms_gt, float(lam_sil), float(lam_iou))
 
 
+class _RenderDepth(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, handle, verts, cam, face_id):
+        require_cuda(verts, cam, face_id)
+        verts, cam, face_id = verts.contiguous(), cam.contiguous(), face_id.contiguous()
+        B, H, S = verts.shape[0], handle.H, handle.H * handle.aa
+        assert face_id.dtype == torch.int32 and tuple(face_id.shape) == (B, S, S), (face_id.dtype, face_id.shape, (B, S, S))
+        depth = torch.empty(B, 1, H, H, device=verts.device)
+        hits = torch.empty(B, H, H, dtype=torch.int32, device=verts.device)
+        PROFILE.bracket("render_depth_fwd", lambda: handle.lib.render_depth_fwd(handle.h, verts, cam, face_id, depth, hits))
+        ctx.handle = handle
+        ctx.save_for_backward(verts, cam, face_id, hits)
+        ctx.mark_non_differentiable(hits)
+        ctx.set_materialize_grads(False)
+        return depth, hits
+
+    @staticmethod
+    def backward(ctx, gdepth, _):
+        if gdepth is None:
+            return None, None, None, None
+        verts, cam, face_id, hits = ctx.saved_tensors
+        handle = ctx.handle
+        gverts = torch.empty_like(verts)
+        ws = torch.empty(handle.lib.render_depth_workspace_bytes(handle.h, verts.shape[0]), dtype=torch.uint8, device=verts.device)
+        g = gdepth.contiguous()
+        PROFILE.bracket("render_depth_bwd", lambda: handle.lib.render_depth_bwd(handle.h, verts, cam, face_id, g, hits, gverts, ws))
+        return None, gverts, None, None
+
+
+def render_depth(handle: RendererHandle, verts, cam, face_id):
+    """The depth map of the hard render, from the face_id that render() / render_uv() returned for the SAME verts and cam: per output pixel
+    the mean perspective-correct depth of its covered samples, 0 where none is covered (include/hifihr.h "Depth map"; the background never
+    enters the average).  One pass over face_id, no second rasterisation.  -> depth [B, 1, H, H], hits int32 [B, H, H] (covered samples per
+    pixel, non-differentiable).  The gradient goes to verts."""
+    return _RenderDepth.apply(handle, verts, cam, face_id)
+
+
+class _DepthLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, hits, target, mask, lam, trunc):
+        require_cuda(depth, hits, target)
+        depth, hits = depth.contiguous(), hits.contiguous()
+        target = target.contiguous() if target.dtype == torch.float32 else target.float().contiguous()
+        if mask is not None:
+            require_cuda(mask)
+            mask = mask.contiguous() if mask.dtype in (torch.float32, torch.int64) else mask.float().contiguous()
+        sums = torch.empty(depth.shape[0], 2, dtype=torch.float64, device=depth.device)
+        out = torch.empty(1, device=depth.device)
+        PROFILE.bracket("depth_loss_fwd", lambda: get_lib().depth_loss_fwd(depth, hits, target, mask, lam, trunc, sums, out))
+        ctx.save_for_backward(depth, hits, target, sums)
+        ctx.mask, ctx.params = mask, (lam, trunc)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        depth, hits, target, sums = ctx.saved_tensors
+        gdepth = torch.empty_like(depth)
+        g = gout.contiguous()
+        PROFILE.bracket("depth_loss_bwd", lambda: get_lib().depth_loss_bwd(depth, hits, target, ctx.mask, sums, g, ctx.params[0], ctx.params[1],
+                                                                           gdepth))
+        return gdepth, None, None, None, None, None
+
+
+def depth_loss(depth, hits, target, mask=None, lam=1.0, trunc=0.0):
+    """lam * mean |depth - target| over the valid pixels of the batch, a scalar: a pixel is valid iff hits > 0 (the mesh covers it),
+    target > 0 (0 = no measurement), mask != 0 (mask None: all ones; float32 or int64 like segms_gt) and, with trunc > 0,
+    |depth - target| <= trunc (an occluder nearer than the hand is not pulled at).  depth [B, 1, H, W] and hits [B, H, W] from render_depth,
+    target [B, H, W] or [B, 1, H, W] in the unit of the vertices.  No valid pixel: exactly 0 with a zero gradient.  One kernel pair
+    (csrc/depth.hip); the gradient goes to depth."""
+    return _DepthLoss.apply(depth, hits, target, mask, float(lam), float(trunc)).reshape(())
+
+
+@torch.no_grad()
+def depth_loss_sums(depth, hits, target, mask=None, trunc=0.0):
+    """float64 [B, 2] on the device: per sample (sum of |depth - target| over the valid pixels, their count), the sums depth_loss divides
+    (the same kernel; no gradient): what an evaluation pass accumulates over batches."""
+    require_cuda(depth, hits, target)
+    depth, hits = depth.detach().contiguous(), hits.contiguous()
+    target = target.contiguous() if target.dtype == torch.float32 else target.float().contiguous()
+    if mask is not None:
+        require_cuda(mask)
+        mask = mask.contiguous() if mask.dtype in (torch.float32, torch.int64) else mask.float().contiguous()
+    sums = torch.empty(depth.shape[0], 2, dtype=torch.float64, device=depth.device)
+    out = torch.empty(1, device=depth.device)
+    PROFILE.bracket("depth_loss_fwd", lambda: get_lib().depth_loss_fwd(depth, hits, target, mask, 1.0, float(trunc), sums, out))
+    return sums
+
+
 class MeshTopology:
     """The tables of a triangle mesh the regularisers read (include/hifihr.h "Mesh regularisers"): neighbours, the (v0, v1, a, b) records of
     every pair of faces on one edge, and the vertex -> record list.  Built, checked and uploaded ONCE: creation allocates and copies, so it

@@ -40,6 +40,12 @@ _DEFAULTS = dict(
     # also skips its search: against a sparse target that direction's minimum is not zero, the very problem the term exists to avoid
     lambda_point_mesh=1.0,
     lambda_point_mesh_faces=0.0,
+    # opt-in depth map of the hard render and its loss term "depth" (hifihr_amd/ops.py render_depth / depth_loss; the loss name switches the
+    # option on as well).  lambda_depth is the reference option's own default (it declares the weight and never computes the term): a starting
+    # point, not a tuned value; the term is in metres.  depth_trunc (metres; 0 = off): pixels further than this from the depth image are left
+    # out -- a few centimetres for HO-3D, where the object occludes the hand
+    render_depth=False, lambda_depth=1.0, depth_trunc=0.0,
+    depth_metric=False,   # the evaluation pass also reports depth_mae (hifihr_amd/evaluate.py Evaluator(depth=True)); needs render_depth and batches with 'depths'
     point_mesh_metric=False,   # the evaluation pass also reports mesh_p2s / mesh_al_p2s (hifihr_amd/evaluate.py Evaluator(point_mesh=True))
     chamfer_metric=False,    # the evaluation pass also reports mesh_chamfer / mesh_al_chamfer (hifihr_amd/evaluate.py Evaluator(chamfer=True))
 )

@@ -13,8 +13,10 @@ from . import ops
 
 @torch.no_grad()
 def make_batch(mano_handle: ops.ManoLayerHandle, renderer: ops.RendererHandle, B: int, first_index: int = 0,
-               device="cuda", image_size=224, images="noise"):
+               device="cuda", image_size=224, images="noise", depth=False):
     """Deterministic in (first_index, B): sample i uses seed 1234 + first_index + i.
+    depth: the batch also carries "depths" f32[224,224] per sample, the depth map of the ground-truth mesh (ops.render_depth on the mask
+    render's face_id; 0 where the hand covers nothing), the target of the loss term "depth".  Without it the batch is unchanged.
     images: "noise" (uniform noise, unrelated to the pose: timing / parity inputs) or "render" (the posed hand, lit, over dim noise:
     an image the pose can be read from, for training runs that are expected to learn)."""
     rows = []
@@ -56,7 +58,7 @@ def make_batch(mano_handle: ops.ManoLayerHandle, renderer: ops.RendererHandle, B
                        -(Kp[:, 1, 2] - s / 2) * 2 / s], dim=-1).contiguous()
     lc = torch.zeros(B, 3, device=device); ld = torch.tensor([0.0, 0.0, -1.0], device=device).repeat(B, 1)
     col = torch.ones(778, 3, device=device)
-    rgba, _ = ops.render(renderer, verts_w.contiguous(), col, cam, lc, ld)
+    rgba, face_id = ops.render(renderer, verts_w.contiguous(), col, cam, lc, ld)
     mask = (rgba[:, 3:4] > 0).float().repeat(1, 3, 1, 1)
     gi = torch.Generator(device="cpu").manual_seed(1234 + first_index)
     imgs = torch.rand(B, 3, image_size, image_size, generator=gi)
@@ -68,10 +70,26 @@ def make_batch(mano_handle: ops.ManoLayerHandle, renderer: ops.RendererHandle, B
     elif images != "noise":
         raise ValueError(f"images={images!r}")
     scales = (joints_w[:, 9] - joints_w[:, 10]).norm(dim=-1)
-    return {
+    batch = {
         "trans_images": imgs, "trans_Ks": Kp.cpu(), "trans_joints": joints_w.cpu(), "trans_verts": verts_w.cpu(),
         "trans_masks": mask.cpu(), "scales": scales.cpu(), "idxs": torch.arange(first_index, first_index + B),
     }
+    if depth:
+        batch["depths"] = ops.render_depth(renderer, verts_w.contiguous(), cam, face_id)[0][:, 0].cpu()
+    return batch
+
+
+@torch.no_grad()
+def mesh_depths(renderer: ops.RendererHandle, verts, cam, out=None):
+    """The depth map [B, H, H] of a mesh in the camera frame (verts [B, V, 3], cam [B, 4] as for ops.render; 0 where nothing is covered):
+    a stand-in depth image made from ground-truth vertices, for data that carries none.  out: written in place (a captured step's static
+    input)."""
+    B = verts.shape[0]
+    dev = verts.device
+    _, face_id = ops.render(renderer, verts.contiguous(), torch.ones(verts.shape[1], 3, device=dev), cam.contiguous(),
+                            torch.zeros(B, 3, device=dev), torch.tensor([0.0, 0.0, -1.0], device=dev).repeat(B, 1))
+    d = ops.render_depth(renderer, verts.contiguous(), cam.contiguous(), face_id)[0][:, 0]
+    return d if out is None else out.copy_(d)
 
 
 def to_ho3d_sample(sample: dict, crop: int = 448) -> dict:
@@ -84,7 +102,7 @@ def to_ho3d_sample(sample: dict, crop: int = 448) -> dict:
     r = crop // base
     flip = torch.tensor([1.0, -1.0, -1.0])
     K, joints = sample["trans_Ks"], sample["trans_joints"]
-    return {
+    out = {
         "img_crop": sample["trans_images"].repeat_interleave(r, dim=2).repeat_interleave(r, dim=3),
         "K_crop": K * flip.view(1, 1, 3),
         "xyz21": Frei2HO3D(joints * flip.view(1, 1, 3)),
@@ -93,23 +111,29 @@ def to_ho3d_sample(sample: dict, crop: int = 448) -> dict:
         "hand_mask_crop": sample["trans_masks"],
         "idxs": sample["idxs"],
     }
+    if "depths" in sample:                 # the reference loader's key (data/dataset.py: depth_crop), at the mask's resolution, in metres
+        out["depth_crop"] = sample["depths"]
+    return out
 
 
-def make_ho3d_frames(mano_handle, renderer, n: int, first_index: int = 0, device="cuda", frame_hw=(480, 640), images="noise"):
+def make_ho3d_frames(mano_handle, renderer, n: int, first_index: int = 0, device="cuda", frame_hw=(480, 640), images="noise", depth=False):
     """Synthetic HO-3D-shaped raw frames for `data.HO3DDeviceCache`: the 224 x 224 synthetic hand of `make_batch` pasted into a 480 x 640
     frame at a per-sample offset (grey background), the intrinsics moved with it, everything in the HO-3D loader's conventions
     (reference data/dataset.py:1065-1068, 1093: `Ks = camMat . cam_extr` with the OpenGL flip, joints in the HO-3D order with y / z negated --
-    what utils/traineval_util.py:156-201 undoes).  -> images_u8 [n,480,640,3], hand_masks_u8 [n,480,640], Ks [n,3,3], xyz21 [n,21,3] (host)."""
+    what utils/traineval_util.py:156-201 undoes).  -> images_u8 [n,480,640,3], hand_masks_u8 [n,480,640], Ks [n,3,3], xyz21 [n,21,3] (host).
+    depth: also "depths" f32 [n,480,640], the hand's depth map pasted at the same offset (0 elsewhere).  `data.HO3DDeviceCache` does not
+    crop a depth frame: a caller that wants the term crops it with the boxes it uses."""
     from .traineval import Frei2HO3D
     FH, FW = frame_hw
     imgs = torch.full((n, FH, FW, 3), 96, dtype=torch.uint8)
     masks = torch.zeros(n, FH, FW, dtype=torch.uint8)
     Ks, xyz = torch.zeros(n, 3, 3), torch.zeros(n, 21, 3)
+    depths = torch.zeros(n, FH, FW) if depth else None
     flip = torch.tensor([1.0, -1.0, -1.0])
     step = 32
     for lo in range(0, n, step):
         m = min(step, n - lo)
-        b = make_batch(mano_handle, renderer, m, first_index=first_index + lo, device=device, images=images)
+        b = make_batch(mano_handle, renderer, m, first_index=first_index + lo, device=device, images=images, depth=depth)
         im = (b["trans_images"].clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu()
         mk = (b["trans_masks"][:, 0] > 0.5).to(torch.uint8).mul(255).cpu()
         K, J = b["trans_Ks"].cpu(), b["trans_joints"].cpu()
@@ -118,7 +142,12 @@ def make_ho3d_frames(mano_handle, renderer, n: int, first_index: int = 0, device
             oy = int(torch.randint(0, FH - 224 + 1, (1,), generator=g)); ox = int(torch.randint(0, FW - 224 + 1, (1,), generator=g))
             imgs[lo + i, oy:oy + 224, ox:ox + 224] = im[i]
             masks[lo + i, oy:oy + 224, ox:ox + 224] = mk[i]
+            if depth:
+                depths[lo + i, oy:oy + 224, ox:ox + 224] = b["depths"][i]
             Kf = K[i].clone(); Kf[0, 2] += ox; Kf[1, 2] += oy
             Ks[lo + i] = Kf * flip.view(1, 3)
             xyz[lo + i] = Frei2HO3D((J[i] * flip.view(1, 3)).unsqueeze(0))[0]
-    return {"images_u8": imgs, "hand_masks_u8": masks, "Ks": Ks, "xyz21": xyz}
+    frames = {"images_u8": imgs, "hand_masks_u8": masks, "Ks": Ks, "xyz21": xyz}
+    if depth:
+        frames["depths"] = depths
+    return frames

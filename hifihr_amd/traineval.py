@@ -61,6 +61,8 @@ def data_dic(sample, dat_name, set_name, args, device="cuda", image_size=224):
             ex["scales"] = to(sample["scales"].float())
         ex["idxs"] = to(sample["idxs"])
         joints, verts, masks = g("joints"), g("verts"), g("masks")
+        if sample.get("depths") is not None:          # a depth image per sample [B, H, W] in the vertices' unit (0 = no measurement): the term "depth"
+            ex["depths"] = to(sample["depths"].float())
     elif dat_name == "HO3D":
         # the reference resizes the crop to 224 (its render resolution is hard-wired to 224); `image_size` is the build-side
         # render resolution of BASELINE configs[4] (512): the photometric terms then run at that size, the encoder reads a 224 resize
@@ -73,6 +75,9 @@ def data_dic(sample, dat_name, set_name, args, device="cuda", image_size=224):
             ex["j2d_gt"] = HO3D2Frei(to(sample["uv21_crop"].float()))
         joints = HO3D2Frei(to(sample["xyz21"])) * flip.view(1, 1, 3) if "xyz21" in sample else None
         verts, masks = None, sample.get("hand_mask_crop")
+        if sample.get("depth_crop") is not None:      # the reference loader's key; nearest-neighbour like the mask (a depth image is not averaged)
+            d = to(sample["depth_crop"].float())
+            ex["depths"] = d if d.shape[-1] == image_size else F.interpolate(d.unsqueeze(1), (image_size, image_size))[:, 0]
         if masks is not None and masks.shape[-1] != image_size:             # the loader's 224 crop at a build-side render resolution
             masks = F.interpolate(to(masks), (image_size, image_size))
     elif dat_name == "RHD":

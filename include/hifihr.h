@@ -270,6 +270,66 @@ int hifihr_soft_sil_loss_bwd(const float* alpha_d, const void* mask_d, int mask_
                              float lam_sil, float lam_iou, float* galpha_d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Depth map (csrc/depth.hip): the depth image of the hard render, with a backward pass to the vertices, and a masked depth loss.  The
+ * rasteriser already finds every sample's nearest face and its perspective-correct depth; only face_id leaves it.  These entries turn
+ * that face_id into a depth map in one pass, without a second rasterisation.  They work on the renderer handle's faces, V, F, image_size
+ * H and aa; S = H aa is the edge of the sample grid.
+ *
+ * Depth map.  For image b and output pixel (y, x), over the aa x aa samples of that pixel in face_id_d[B][S][S] as hifihr_render_fwd or
+ * hifihr_render_fwd_uv wrote it for the SAME verts_d and cam_d:
+ *   a sample with face_id >= 0 is covered;
+ *   its z is the *pz of sample_face() in csrc/render_math.h for that face at that sample centre: the same fp32 expressions in the same
+ *     order that the rasteriser and oracle/raster_oracle.c use, built with -ffp-contract=off -- vertices xn = (X fx + Z px) / Z,
+ *     yn = (Y fy + Z py) / Z; divided barycentrics w_i = e_i / (area + 1e-8); perspective correction t0 = w0 z1 z2, t1 = z0 w1 z2,
+ *     t2 = z0 z1 w2, b_i = t_i / max(t0 + t1 + t2, 1e-8); pz = b0 z0 + b1 z1 + b2 z2.  This is PyTorch3D's fragments.zbuf under
+ *     perspective_correct = True [recalled; parity unpinned, like the rest of that boundary];
+ *   hits = the number of covered samples; depth_d[b][y][x] = the fp32 sum of z over the covered samples in row-major sample order,
+ *     divided by hits (one division), and exactly 0 when hits == 0; hits_d[b][y][x] = hits as int32.
+ * At aa = 1 the depth of a covered pixel therefore has the bits of the rasteriser's own zbuf.
+ * The background never enters the average.  This departs from the reference's avg_pool2d of rgba on purpose: there the background is a
+ * colour, whereas a pooled zbuf with a -1 background would mean nothing.
+ * A face_id outside 0 .. F - 1, or one whose sample sample_face() rejects (neither can come from the renderer for these inputs), counts as
+ * not covered: no index is formed from it.
+ *
+ * Depth gradient (hifihr_render_depth_bwd).  To verts_d only; cam_d gets none, as in the renderer's Python wrapper.  face_id, the
+ * max(., 1e-8) clamp of the denominator, the rasteriser's pz >= 0 / b_i > 0 tests and hits are piecewise constant choices (where the
+ * denominator clamps it carries no gradient).  A covered sample receives gdepth / hits; the gradient flows through z0 .. z2 directly
+ * and through the NDC coordinates xn, yn of the three corners.  gverts_d[B][V][3] is OVERWRITTEN; a vertex that no covered sample
+ * references gets exactly 0.  Pixels whose gdepth_d is 0 or whose hits_d is <= 0 are skipped.
+ * The form built is the atomic one: one wave per tile of 8 x 8 output pixels sums each face's nine components (NDC x, y and Z of its
+ * three corners) over the tile on chip and issues ONE float atomic per component, corner and tile into the accumulator float[B][V][3]
+ * inside ws_d, which the entry zeroes itself (any ws_d of hifihr_render_depth_workspace_bytes(h, B) bytes, 16-byte aligned, serves); a
+ * per-vertex pass applies the projection's chain rule.  depth_d and hits_d have the same bits on every call; gverts_d is reproducible
+ * to rounding, NOT bitwise -- as for hifihr_render_bwd.
+ *
+ * Loss (hifihr_depth_loss_fwd / _bwd).  d = depth_d[B][HW], hits_d[B][HW], the target D = target_d[B][HW] in fp32 where 0 (or less)
+ * means no measurement, an optional mask M = mask_d[B][HW], float32 (mask_i64 = 0) or int64 (mask_i64 = 1) as for
+ * hifihr_soft_sil_loss_fwd, NULL = all ones, and trunc >= 0.  A pixel is valid iff hits > 0 and D > 0 and M != 0 and
+ * (trunc == 0 or |d - D| <= trunc), with d - D taken in fp64 (exact).  Per image, one workgroup, a fixed order, fp64, no atomics:
+ *   sums_d[B][2] = (sum over the valid pixels of |d - D|, their count);
+ * a finish step writes out_d[1] = lam * sum_b sum_b / max(sum_b count_b, 1), the mean |d - D| over the valid pixels of the batch in the
+ * inputs' unit.  A batch without a valid pixel gives exactly 0 and a zero gradient, not NaN: frames without usable depth are ordinary in
+ * a mixed batch, and there is no reference formula to reproduce (the reference declares lambda_depth and never computes the term).
+ * sums_d and out_d are overwritten and have the same bits on every call.  hifihr_depth_loss_bwd is one elementwise launch that
+ * OVERWRITES gdepth_d[B][HW]: gout_d[0] * lam * sign(d - D) / max(sum count, 1) on the valid pixels, 0 on all others and where d == D;
+ * validity is treated as constant; the target and the mask get no gradient.
+ *
+ * Refused (HIFIHR_EINVAL, nothing launched, nothing written): a NULL handle or pointer other than mask_d; B < 0; the loss entries also
+ *   HW <= 0, lam or trunc not finite, trunc < 0, mask_i64 outside {0, 1}, and hifihr_depth_loss_bwd B > 65535.
+ * Accepted: B == 0 is a no-op.  hifihr_render_depth_workspace_bytes(NULL, .) and (h, B < 0) return 0; the size never decreases with B.
+ * Precondition, NOT checked (as for the renderer): every vertex is finite and none has Z == 0.
+ * No allocation and no synchronisation inside: the entries can be captured into a hipGraph. */
+size_t hifihr_render_depth_workspace_bytes(const hifihr_renderer_t* h, int B);
+int hifihr_render_depth_fwd(const hifihr_renderer_t* h, const float* verts_d, const float* cam_d, const int32_t* face_id_d, int B,
+                            float* depth_d, int32_t* hits_d, void* stream);
+int hifihr_render_depth_bwd(const hifihr_renderer_t* h, const float* verts_d, const float* cam_d, const int32_t* face_id_d,
+                            const float* gdepth_d, const int32_t* hits_d, int B, float* gverts_d, void* ws_d, void* stream);
+int hifihr_depth_loss_fwd(const float* depth_d, const int32_t* hits_d, const float* target_d, const void* mask_d, int mask_i64, int B, int HW,
+                          float lam, float trunc, double* sums_d, float* out_d, void* stream);
+int hifihr_depth_loss_bwd(const float* depth_d, const int32_t* hits_d, const float* target_d, const void* mask_d, int mask_i64,
+                          const double* sums_d, const float* gout_d, int B, int HW, float lam, float trunc, float* gdepth_d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Mesh regularisers (csrc/mesh_reg.hip): `triangle` and `normal_consistency` in one kernel pair.
  * `triangle` replaces reference losses.py:421-429, lambda_laplacian * mesh_laplacian_smoothing(Meshes(verts, faces), method="uniform");
  * `normal_consistency` is PyTorch3D's mesh_normal_consistency, which the reference does not use.  Both PyTorch3D functions are [recalled]:

@@ -62,6 +62,10 @@ def parse(argv=None):
     ap.add_argument("--soft_silhouette", action="store_true",
                     help="the model also emits outputs['re_sil_soft'], a differentiable silhouette (options: soft_silhouette, soft_sil_sigma); "
                          "the loss names 'sil_soft' / 'iou_soft' switch it on by themselves")
+    ap.add_argument("--render_depth", action="store_true",
+                    help="the model also emits outputs['re_depth'], the depth map of its hard render with a backward pass to the vertices "
+                         "(options: render_depth, lambda_depth, depth_trunc); the loss name 'depth' switches it on by itself, and the "
+                         "FreiHAND batches then carry the ground-truth mesh's depth map as 'depths'")
     ap.add_argument("--max_grad_norm", type=float, default=None, metavar="X",
                     help="gradient guard of the optimizer step (options: max_grad_norm): clip the global L2 norm of the gradient to X and skip a "
                          "step whose gradient holds a NaN / inf, all on the device; 'inf' = the skip alone, 0 = off (the default)")
@@ -73,6 +77,27 @@ def soft_silhouette_kwargs(args):
     """Model(...)'s soft-silhouette options: on when asked for, or when a loss term that reads outputs['re_sil_soft'] is requested."""
     on = bool(getattr(args, "soft_silhouette", False)) or any(k in args.losses for k in ("sil_soft", "iou_soft"))
     return dict(soft_silhouette=on, soft_sil_sigma=float(getattr(args, "soft_sil_sigma", 1e-4)))
+
+
+def render_depth_kwargs(args):
+    """Model(...)'s depth-map option: on when asked for, or when the loss term or the metric that reads outputs['re_depth'] is requested."""
+    return dict(render_depth=bool(getattr(args, "render_depth", False)) or "depth" in args.losses or bool(getattr(args, "depth_metric", False)))
+
+
+def wants_depths(args):
+    """The batches need examples['depths']: the loss term 'depth' or the metric depth_mae is requested."""
+    return "depth" in args.losses or bool(getattr(args, "depth_metric", False))
+
+
+def attach_mesh_depths(ex, model, static=None):
+    """examples['depths'] for a FreiHAND batch: that data path carries no depth image, so the depth map of the batch's ground-truth mesh
+    (hifihr_amd/synth.py mesh_depths: its augmented vertices through its own camera) stands in for one.  static: the captured step's
+    inputs -- the map is written into the tensor the graph reads."""
+    from hifihr_amd import synth
+    cam = ex["cam_ndc"] if "cam_ndc" in ex else model.camera_from_K(ex["Ks"])
+    out = static["depths"] if static is not None and "depths" in static else None
+    ex["depths"] = synth.mesh_depths(depth_renderer(model), ex["verts"], cam, out=out)
+    return ex
 
 
 def optimizer_max_grad_norm(args):
@@ -103,6 +128,8 @@ def build_args(cli):
     args.texture_stand_in = 0
     if getattr(cli, "soft_silhouette", False):
         args.soft_silhouette = True
+    if getattr(cli, "render_depth", False):
+        args.render_depth = True
     if getattr(cli, "max_grad_norm", None) is not None:
         args.max_grad_norm = float(cli.max_grad_norm)
     if cli.lpips_weights:
@@ -154,6 +181,9 @@ def train_ho3d(cli, args, model, loss_func, opt, sched, reducer, current_epoch, 
     from hifihr_amd.checkpoint import save_model
     from hifihr_amd.data import HO3DDeviceCache
     from hifihr_amd.traineval import GraphedTrainStep, data_dic, train_step
+    if wants_depths(args):
+        raise SystemExit("[train_hrnet] the HO-3D data path produces no examples['depths'] (decoding and cropping HO-3D depth images is not "
+                         "built): the loss term 'depth' / depth_metric run on --dataset FreiHand, or from a caller that supplies 'depths'")
     if cli.ho3d_cache:
         z = np.load(cli.ho3d_cache)
         frames = {"images_u8": z["images"], "hand_masks_u8": z["hand_masks"], "Ks": z["Ks"], "xyz21": z["xyz21"]}
@@ -263,6 +293,20 @@ def ho3d_eval_cache(cli, frames, device):
 _LPIPS = {}
 
 
+_DEPTH_RENDERER = {}
+
+
+def depth_renderer(model):
+    """The renderer the stand-in depth images are drawn with: the model's own for the MANO topology, a MANO one beside a NIMBLE-shaped
+    model (the ground truth is MANO either way); built once per model."""
+    if model.hand_model != "nimble":
+        return model.renderer_p3d
+    if id(model) not in _DEPTH_RENDERER:
+        from hifihr_amd import ops
+        _DEPTH_RENDERER[id(model)] = ops.RendererHandle(model.mano_face[0].cpu().numpy(), 778, image_size=224, aa=3)
+    return _DEPTH_RENDERER[id(model)]
+
+
 def make_evaluator(args, device):
     """Evaluator of the evaluation pass; with --lpips_weights it also reports LPIPS (the module is built and loaded once per device)."""
     from hifihr_amd.evaluate import Evaluator
@@ -270,13 +314,14 @@ def make_evaluator(args, device):
     bench = bool(getattr(args, "benchmark_metrics", True))          # the FreiHAND benchmark's PCK / AUC and F-score keys
     cham = bool(getattr(args, "chamfer_metric", False))             # mesh_chamfer / mesh_al_chamfer beside the F-scores
     p2s = bool(getattr(args, "point_mesh_metric", False))           # mesh_p2s / mesh_al_p2s: ground-truth vertices -> the predicted surface
+    dep = bool(getattr(args, "depth_metric", False))                # depth_mae: the rendered depth map against examples['depths']
     if not paths:
-        return Evaluator(benchmark=bench, chamfer=cham, point_mesh=p2s)
+        return Evaluator(benchmark=bench, chamfer=cham, point_mesh=p2s, depth=dep)
     key = (str(device), tuple(paths))
     if key not in _LPIPS:
         from hifihr_amd.lpips import LPIPS, load_lpips_weights
         _LPIPS[key] = load_lpips_weights(LPIPS(net="alex"), *paths).to(device)
-    return Evaluator(lpips_fn=_LPIPS[key], benchmark=bench, chamfer=cham, point_mesh=p2s)
+    return Evaluator(lpips_fn=_LPIPS[key], benchmark=bench, chamfer=cham, point_mesh=p2s, depth=dep)
 
 
 def run_evaluation_ho3d(model, cache, args, device, epoch):
@@ -308,6 +353,8 @@ def run_evaluation(model, cache, arrays, args, device):
         for lo in range(0, n, args.val_batch):
             idx = torch.arange(lo, min(n, lo + args.val_batch))
             ex = data_dic(cache.batch(idx, rots=np.zeros(len(idx))), "FreiHand", "training", args, device=device)
+            if wants_depths(args) and args.render:
+                attach_mesh_depths(ex, model)
             root = ex["joints"][:, args.ROOT, :].unsqueeze(1)
             out = model("FreiHand", False, ex["imgs"], Ks=ex["Ps"], root_xyz=root)
             ev.collect(out, ex, "FreiHand", render=args.render)
@@ -354,7 +401,7 @@ def main(argv=None):
     model = Model(ifRender=args.render, device=device, if_4c=args.four_channel, hand_model=args.hand_model,
                   use_mean_shape=args.use_mean_shape, pretrain=args.pretrain, root_id=args.ROOT, root_id_nimble=args.ROOT_NIMBLE,
                   ifLight=args.light_estimation, mano_tables=tables, texture_stand_in=args.texture_stand_in,
-                  nimble_tables=nimble_tables, **soft_silhouette_kwargs(args)).to(device).train()
+                  nimble_tables=nimble_tables, **soft_silhouette_kwargs(args), **render_depth_kwargs(args)).to(device).train()
     frozen = freeze_model_modules(model, args)          # only_train_regressor / only_train_texture (train_hrnet.py:566)
     if frozen:
         say("[train_hrnet] frozen:", ", ".join(frozen))
@@ -405,6 +452,8 @@ def main(argv=None):
             idx = perm[lo + rank * B: lo + (rank + 1) * B]
             # the batch is written straight into the captured step's static inputs (one staged copy + two launches)
             ex = cache.batch_examples(idx, generator=rot_gen, out=stepper.static if stepper is not None else None, root_id=args.ROOT)
+            if "depth" in args.losses:
+                attach_mesh_depths(ex, model, static=stepper.static if stepper is not None else None)
             if cli.graph and stepper is None:
                 ok = 1
                 try:
