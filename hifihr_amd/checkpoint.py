@@ -179,7 +179,12 @@ def rec_freeze(module):
 
 def freeze_model_modules(model, args):
     """utils/train_utils.py:205-240 for the sub-modules this build has.  Call BEFORE optim.FlatParams is built: frozen parameters
-    then stay out of the flat buffers, get no gradient kernels (the ops look at needs_input_grad) and no Adam update."""
+    then stay out of the flat buffers, end every step with .grad None and get no Adam update.  Backward work is skipped where a function
+    looks at needs_input_grad (the convolutions' weight / data gradients, a backward nothing upstream of needs); the batch-norm, linear
+    and squeeze-excite functions compute dgamma / dbeta / dw in their one launch whatever the flags say and the result is dropped.  Running
+    statistics below a frozen root stay bit-unchanged (momentum 0), batch statistics are still used in train mode, as in the reference.
+    Freezing a parameter AFTER FlatParams took it is refused: the next step raises a ValueError naming it (FlatParams.check_trainable).
+    tests/test_gpu_freeze.py holds all of this against float64 autograd."""
     frozen = []
     if getattr(args, "only_train_regressor", False) and hasattr(model, "light_estimator"):
         rec_freeze(model.light_estimator); frozen.append("light_estimator")

@@ -1189,8 +1189,10 @@ def _wino_conv(lib, x, w_krsc, y, stats, N, H, W, C, K, flip, keep_v=False, bias
 
 def _direct_grad(p, fmt=None):
     """p's gradient is accumulated straight into the flat gradient buffer it lives in (hifihr_amd/optim.py FlatParams); `fmt`: only
-    when that buffer has this memory format."""
-    return getattr(p, "_hifihr_direct_grad", False) and p.grad is not None and (fmt is None or p.grad.is_contiguous(memory_format=fmt))
+    when that buffer has this memory format.  Never for a parameter that does not require a gradient (frozen after FlatParams pinned its
+    .grad): the functions that compute dgamma / dbeta / dw whatever needs_input_grad says would add into a buffer Adam still reads."""
+    return (getattr(p, "_hifihr_direct_grad", False) and p.requires_grad and p.grad is not None
+            and (fmt is None or p.grad.is_contiguous(memory_format=fmt)))
 
 
 def _grad_target(p, like, fmt=None):
@@ -1884,8 +1886,10 @@ class _BNActWinoConv(torch.autograd.Function):
         if need[5] and direct_w:
             _grad_ready(w)
         # 5. the batch-norm apply: inside the producer's dual transform when x came from a fused function, else one launch here
+        # (only when the producer's backward will RUN, i.e. x requires a gradient: with everything upstream frozen autograd never calls it,
+        #  and dgamma / dbeta, the slot buffer `red` and the deferred flags would be left hanging)
         dg_ret = db_ret = None
-        if in_link is not None and _direct_grad(ctx.gamma_param) and _direct_grad(ctx.beta_param):
+        if in_link is not None and need[0] and _direct_grad(ctx.gamma_param) and _direct_grad(ctx.beta_param):
             in_link.red, in_link.save_mean, in_link.save_invstd, in_link.gamma = red, save_mean, save_invstd, gamma
             in_link.gamma_param, in_link.beta_param, in_link.g = ctx.gamma_param, ctx.beta_param, g_in
             # (the data-parallel reducer must not take autograd's "this function is done" for "dgamma / dbeta are written": dist.py)
@@ -2507,14 +2511,13 @@ class _MMPool(torch.autograd.Function):
         p, argmax, xmax, xavg = ctx.saved_tensors
         B, C, H, W = ctx.shape
         gy = gy.contiguous()
-        dx = torch.empty((B, C, H, W), device=gy.device, memory_format=_CL) if ctx.needs_input_grad[0] else None
+        # (a frozen trunk under a trainable p: the one kernel writes both, so dx goes to a buffer nobody reads)
+        dx = torch.empty((B, C, H, W), device=gy.device, memory_format=_CL)
         dp_t, dp_ret = _grad_target(ctx.p_param, p) if ctx.needs_input_grad[1] else (None, None)
-        if dx is None:
-            raise NotImplementedError("mmpool backward without an input gradient")
         PROFILE.bracket("mmpool_bwd", lambda: get_lib().mmpool_bwd(gy, p, argmax, xmax, xavg, B, H * W, C, dx, dp_t))
         if dp_t is not None and dp_ret is None:
             _grad_ready(ctx.p_param)
-        return dx, dp_ret
+        return (dx if ctx.needs_input_grad[0] else None), dp_ret
 
 
 def mmpool(x, p):

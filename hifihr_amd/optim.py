@@ -19,7 +19,9 @@ class FlatParams:
     flat gradient buffer."""
 
     def __init__(self, module: torch.nn.Module, align: int = 64):
-        self.params = [p for p in module.parameters() if p.requires_grad]
+        named = [(n, p) for n, p in module.named_parameters() if p.requires_grad]
+        self.params = [p for _, p in named]
+        self.names = [n for n, _ in named]
         dev = self.params[0].device
         self.offsets = []
         off = 0
@@ -47,6 +49,16 @@ class FlatParams:
         if init is not None:
             v.copy_(init)
         return v
+
+    def check_trainable(self):
+        """A parameter frozen AFTER it was re-homed here cannot be honoured: its slice of the flat buffers still gets the one Adam launch,
+        and the moments it has collected keep moving it even with a zero gradient.  Host-side, before any launch of a step: ValueError
+        naming the parameters (freeze with checkpoint.freeze_model_modules BEFORE building FlatParams, or rebuild FlatParams / FusedAdam)."""
+        late = [n for n, p in zip(self.names, self.params) if not p.requires_grad]
+        if late:
+            raise ValueError(f"requires_grad was turned off on {len(late)} parameter(s) that already live in a FlatParams ({', '.join(late[:8])}"
+                             f"{', ...' if len(late) > 8 else ''}): the fused Adam step would still move them.  Freeze before FlatParams is built, "
+                             f"or rebuild FlatParams and FusedAdam")
 
     def zero_grad(self):
         self.grad.zero_()

@@ -140,6 +140,9 @@ def _prime_for_capture(device):
 def forward_backward(model, loss_func, optimizer, examples, args, dat_name="FreiHand"):
     """Forward, losses, zero_grad and backward of one iteration (train_hrnet.py:50-104).  Returns (loss, loss_dic)."""
     from .ops import prepared_weights
+    flatp = getattr(optimizer, "flatp", None)
+    if flatp is not None:
+        flatp.check_trainable()              # a late freeze fails here, on the host, before the step's first launch
     # one launch re-lays every convolution weight out for this step (ops._WeightPrep); weight gradients go to a side stream
     # (ops._AsyncWgrad) unless data-parallel hooks may launch a bucket's all-reduce in the middle of backward
     dp = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
@@ -231,6 +234,7 @@ class GraphedTrainStep:
     def __init__(self, model, loss_func, optimizer, examples, args, dat_name="FreiHand", warmup=3, reducer=None):
         self.model, self.loss_func, self.opt, self.args, self.dat_name = model, loss_func, optimizer, args, dat_name
         self.reducer = reducer
+        optimizer.flatp.check_trainable()                       # (a late freeze: ValueError before graph mode, warm-up or capture begin)
         self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in examples.items()}
         split = reducer is not None
         # Warm-up and capture must leave the training state exactly as they found it (the warm-up runs real steps on one batch;
@@ -340,6 +344,7 @@ class SegmentedGraphedTrainStep:
         if enc is None or not hasattr(enc, "model") or not hasattr(enc.model, "layer3"):
             raise NotImplementedError("segmented backward is built for the ResNet trunks")
         self.model, self.loss_func, self.opt, self.args, self.dat_name, self.reducer = model, loss_func, optimizer, args, dat_name, reducer
+        optimizer.flatp.check_trainable()
         self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in examples.items()}
         flat = optimizer.flatp
         idx = {id(p): i for i, p in enumerate(flat.params)}

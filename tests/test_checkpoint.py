@@ -161,3 +161,46 @@ def test_freeze_model_modules_semantics():
     ck.rec_freeze(lone)                                    # no children: nothing is frozen
     assert lone.weight.requires_grad
     assert ck.freeze_model_modules(_Mine("res18"), argparse.Namespace()) == []
+
+
+def test_adam_state_round_trip_after_freeze():
+    """freeze_model_modules -> FlatParams -> adam_state_to_torch -> adam_state_from_torch: the trainable parameters' moments come back
+    equal, frozen parameters (and the classifier head) get no state entry, and the indices stay those of reference_param_names -- the
+    reference's optimizer is built over ALL model.parameters(), frozen ones included."""
+    torch.manual_seed(0)
+    m = _Mine("res18")
+    ck.freeze_model_modules(m, argparse.Namespace(only_train_texture=True, only_train_regressor=False))
+    flat = FlatParams(m)
+    opt = FusedAdam(flat, lr=1e-3)
+    gen = torch.Generator().manual_seed(2)
+    opt.exp_avg.copy_(torch.randn(flat.numel, generator=gen)); opt.exp_avg_sq.copy_(torch.rand(flat.numel, generator=gen))
+    opt.step_count = 3
+    names = ck.reference_param_names(m)
+    named = dict(m.named_parameters())
+    sd = ck.adam_state_to_torch(m, opt)
+    assert sd["param_groups"][0]["params"] == list(range(len(names)))
+    trainable = [i for i, n in enumerate(names) if n in named and named[n].requires_grad]
+    assert sorted(sd["state"]) == trainable and 0 < len(trainable) < len(names)
+    assert not any(names[i].startswith("base_encoder.") or names[i].startswith("hand_encoder.pose_reg.") for i in sd["state"])
+    for p, o in zip(flat.params, flat.offsets):
+        i = names.index(next(k for k, v in named.items() if v is p))
+        assert torch.equal(sd["state"][i]["exp_avg"], flat._view(opt.exp_avg, p, o)) and float(sd["state"][i]["step"]) == 3.0
+        assert sd["state"][i]["exp_avg"].shape == p.shape
+    opt2 = FusedAdam(flat, lr=5e-2)
+    ck.adam_state_from_torch(m, opt2, sd)
+    assert opt2.step_count == 3 and opt2.param_groups[0]["lr"] == 1e-3
+    for p, o in zip(flat.params, flat.offsets):                 # (the alignment gaps between the views are zeroed, not carried)
+        assert torch.equal(flat._view(opt2.exp_avg, p, o), flat._view(opt.exp_avg, p, o))
+        assert torch.equal(flat._view(opt2.exp_avg_sq, p, o), flat._view(opt.exp_avg_sq, p, o))
+    sd2 = ck.adam_state_to_torch(m, opt2)
+    assert sorted(sd2["state"]) == trainable and all(torch.equal(sd2["state"][i]["exp_avg_sq"], sd["state"][i]["exp_avg_sq"]) for i in trainable)
+
+
+def test_late_freeze_is_refused_by_flat_params():
+    """A parameter frozen after FlatParams re-homed it: check_trainable (called by every step before its first launch) names it."""
+    m = _Mine("res18")
+    flat = FlatParams(m)
+    flat.check_trainable()
+    m.hand_encoder.trans_reg[0].bias.requires_grad_(False)
+    with pytest.raises(ValueError, match=r"hand_encoder\.trans_reg\.0\.bias"):
+        flat.check_trainable()
