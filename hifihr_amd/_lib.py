@@ -4,12 +4,13 @@
 PyTorch fallback for the hot path.  `HifihrLib` itself only marshals pointers, so the test-suite can also
 point it at tests/hostsim/libhifihr_hostsim.so (the same kernel sources compiled against a HIP
 execution-model emulator) to exercise the kernels without a GPU; the package never does that.
+No signature is written down here: every `argtypes` / `restype` is read from the header (hifihr_amd/_abi.py).
 """
 from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_long, c_size_t, c_void_p
+from ctypes import POINTER, c_float, c_int, c_int32, c_long, c_size_t, c_void_p
 
 import torch  # noqa: F401  (must be imported first: the library binds to torch's libamdhip64)
 
@@ -73,256 +74,10 @@ class HifihrLib:
         self.c = ctypes.CDLL(path)
         self._zero_page = set()                # devices whose zero page exists (zero_page_ready)
         self._pair_ok = {}                     # (N, H, W, C, K) -> hifihr_wino4_bwd_gemm_pair_supported
-        c = self.c
-        c.hifihr_last_error.restype = c_char_p
-        c.hifihr_version.restype = c_int
-        c.hifihr_device_count.restype = c_int
-        c.hifihr_mano_create.argtypes = [POINTER(c_void_p)] + [_c_float_p] * 7
-        c.hifihr_mano_destroy.argtypes = [c_void_p]
-        c.hifihr_mano_lbs_fwd.argtypes = [c_void_p, _c_float_p, _c_float_p, c_int, _c_float_p, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_mano_lbs_bwd.argtypes = [c_void_p] + [_c_float_p] * 5 + [c_int, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_mano_joints_fwd.argtypes = [c_void_p, _c_float_p, c_int, c_int, _c_float_p, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_mano_joints_bwd.argtypes = [c_void_p, _c_float_p, _c_float_p, _c_float_p, c_int, c_int, _c_float_p, c_void_p]
-        c.hifihr_mano_full_fwd.argtypes = [c_void_p, _c_float_p, _c_float_p, c_int, c_int, _c_float_p] + [_c_float_p] * 6 + [c_void_p]
-        c.hifihr_mano_full_bwd.argtypes = [c_void_p] + [_c_float_p] * 9 + [c_int, c_int, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_lbs_create.argtypes = [POINTER(c_void_p), c_int, c_int, c_int] + [_c_float_p] * 4 + [_c_int_p]
-        c.hifihr_lbs_destroy.argtypes = [c_void_p]
-        c.hifihr_lbs_fwd.argtypes = [c_void_p, _c_float_p, _c_float_p, c_int, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_lbs_bwd.argtypes = [c_void_p] + [_c_float_p] * 4 + [c_int] + [_c_float_p] * 3 + [c_void_p]
-        self._bind_optional()
-
-    def _bind_optional(self):
-        c = self.c
-        c.hifihr_renderer_create.argtypes = [POINTER(c_void_p), _c_int_p, c_int, c_int, c_int, c_int, _c_float_p, _c_float_p,
-                                             _c_float_p, c_float, _c_float_p]
-        c.hifihr_ssim_partial_count.argtypes = [c_int, c_int, c_int]
-        c.hifihr_ssim_partial_count.restype = c_int
-        c.hifihr_ssim_fwd.argtypes = [_c_float_p, _c_float_p, _c_float_p, c_int, c_int, c_int, _c_float_p, _c_float_p, _c_float_p,
-                                      _c_float_p, c_void_p]
-        c.hifihr_ssim_bwd.argtypes = [_c_float_p] * 7 + [c_int, c_int, c_int, _c_float_p, c_void_p]
-        c.hifihr_ssim_bwd_scaled.argtypes = [_c_float_p] * 7 + [c_float, c_int, c_int, c_int, _c_float_p, c_void_p]
-        c.hifihr_ssim_finish.argtypes = [_c_float_p, c_int, c_float, c_float, _c_float_p, c_void_p]
-        ci = [c_int] * 9
-        c.hifihr_conv2d_fwd.argtypes = [_c_float_p] * 3 + [c_int, _c_float_p] + ci + [c_void_p, c_size_t, c_void_p]
-        c.hifihr_bias_relu_bwd.argtypes = [_c_float_p, _c_float_p, c_long, c_int, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_conv2d_workspace_bytes.argtypes = [c_int] * 10
-        c.hifihr_conv2d_workspace_bytes.restype = c_size_t
-        c.hifihr_conv2d_bwd_data.argtypes = [_c_float_p] * 4 + ci + [c_void_p, c_size_t, c_void_p]
-        c.hifihr_conv2d_fwd_bnstats.argtypes = [_c_float_p] * 4 + ci + [c_void_p, c_size_t, c_void_p]
-        c.hifihr_conv2d_fwd_bnstats_pair_supported.argtypes = [c_int] * 11
-        c.hifihr_conv2d_fwd_bnstats_pair.argtypes = [_c_float_p] * 4 + [c_int] * 3 + [_c_float_p] * 3 + [c_int] * 8 + [c_void_p]
-        for fn in (c.hifihr_dwconv2d_bwd_data, c.hifihr_dwconv2d_bwd_weight):
-            fn.argtypes = [_c_float_p] * 3 + [c_int] * 10 + [c_void_p]
-        c.hifihr_dwconv2d_fwd.argtypes = [_c_float_p] * 4 + [c_int] * 10 + [c_void_p]
-        c.hifihr_dwconv2d_fwd_bnswish.argtypes = [_c_float_p] * 8 + [c_int] * 10 + [c_void_p]
-        c.hifihr_dwconv2d_bwd_weight_bnswish.argtypes = [_c_float_p] * 7 + [c_int] * 10 + [c_void_p]
-        c.hifihr_bn_finalize_fwd.argtypes = [_c_float_p, c_long, c_int, c_float, c_float] + [_c_float_p] * 4 + [c_void_p]
-        c.hifihr_bn_stats_floats.argtypes = [c_int]
-        c.hifihr_bn_stats_floats.restype = c_int
-        c.hifihr_bn_stats.argtypes = [_c_float_p, c_long, c_int, _c_float_p, c_void_p]
-        c.hifihr_bn_act_fwd.argtypes = [_c_float_p] * 5 + [c_int, c_long, c_int, c_float, c_float] + [_c_float_p] * 5 + [c_void_p]
-        c.hifihr_bn_act_eval.argtypes = [_c_float_p] * 6 + [c_int, c_long, c_int, c_float, _c_float_p, c_void_p]
-        c.hifihr_bn_act_bwd.argtypes = [_c_float_p] * 7 + [c_int, c_long, c_int] + [_c_float_p] * 5 + [c_void_p]
-        c.hifihr_bn_relu_maxpool_supported.argtypes = [c_int] * 4
-        c.hifihr_bn_relu_maxpool_fwd.argtypes = [_c_float_p] * 4 + [c_int] * 4 + [c_float, c_float, _c_float_p, c_void_p] + [_c_float_p] * 4 + [c_void_p]
-        c.hifihr_bn_relu_maxpool_bwd.argtypes = [_c_float_p, c_void_p] + [_c_float_p] * 5 + [c_int] * 4 + [_c_float_p] * 4 + [c_void_p]
-        c.hifihr_bn_relu_maxpool_bwd_y.argtypes = [_c_float_p, _c_float_p, c_void_p] + [_c_float_p] * 5 + [c_int] * 4 + [_c_float_p] * 4 + [c_void_p]
-        c.hifihr_conv2d_bwd_weight.argtypes = [_c_float_p] * 3 + ci + [c_void_p]
-        c.hifihr_conv2d_bwd_weight_ws.argtypes = [_c_float_p] * 3 + ci + [c_void_p, c_size_t, c_void_p]
-        c.hifihr_conv2d_wgrad_workspace_bytes.argtypes = ci
-        c.hifihr_conv2d_bwd_weight_c3_supported.argtypes = [c_int] * 8
-        c.hifihr_conv2d_bwd_weight_c3.argtypes = [_c_float_p] * 3 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p]
-        c.hifihr_conv2d_wgrad_workspace_bytes.restype = c_size_t
-        c.hifihr_image_to_nhwc4.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_void_p]
-        c.hifihr_image_to_nhwc4_padded.argtypes = [_c_float_p, _c_float_p] + [c_int] * 8 + [c_void_p]
-        c.hifihr_image_scale_to_nhwc4.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_maxpool2d_fwd_notap.argtypes = [_c_float_p] + [c_int] * 7 + [_c_float_p, c_void_p]
-        c.hifihr_lpips_tap_max_channels.argtypes = []
-        c.hifihr_lpips_tap_max_channels.restype = c_int
-        c.hifihr_lpips_tap_partial_floats.argtypes = [c_int]
-        c.hifihr_lpips_tap_partial_floats.restype = c_size_t
-        c.hifihr_lpips_tap.argtypes = [_c_float_p] * 3 + [c_int] * 4 + [_c_float_p, _c_float_p, c_void_p]
-        c.hifihr_lpips_tap_bwd.argtypes = [_c_float_p] * 4 + [c_int] * 4 + [_c_float_p, c_void_p]
-        c.hifihr_lpips_tap_bwd_relu.argtypes = [_c_float_p] * 4 + [c_int] * 4 + [_c_float_p, c_void_p]
-        c.hifihr_lpips_maxpool_fwd.argtypes = [_c_float_p] + [c_int] * 4 + [_c_float_p, c_void_p]
-        c.hifihr_lpips_maxpool_bwd.argtypes = [_c_float_p, _c_float_p] + [c_int] * 4 + [_c_float_p, c_void_p]
-        c.hifihr_image_scale_to_nhwc4_bwd.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, _c_float_p, c_void_p]
-        c.hifihr_geom_loss_fwd.argtypes = [_c_float_p] * 6 + [_c_int_p] + [c_int] * 7 + [_c_float_p] * 3 + [c_void_p]
-        c.hifihr_geom_loss_bwd.argtypes = [_c_float_p] * 6 + [_c_int_p] * 3 + [c_int] * 7 + [_c_float_p] * 6 + [c_void_p]
-        c.hifihr_photo_loss_partial_floats.argtypes = []
-        c.hifihr_photo_loss_partial_floats.restype = c_int
-        c.hifihr_photo_loss_fwd.argtypes = [_c_float_p, _c_float_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float] + \
-            [_c_float_p] * 4 + [c_void_p]
-        c.hifihr_photo_loss_bwd.argtypes = [_c_float_p] * 6 + [c_int, c_int, c_int, c_float, c_float, _c_float_p, c_void_p]
-        c.hifihr_sil_post.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_linear_fwd.argtypes = [_c_float_p] * 3 + [c_int] * 4 + [_c_float_p] * 2 + [c_float, c_float] + [_c_float_p] * 6 + [c_void_p]
-        c.hifihr_linear_bwd.argtypes = [_c_float_p] * 4 + [c_int] * 4 + [_c_float_p] * 10 + [c_void_p]
-        c.hifihr_linear_fwd_group.argtypes = [POINTER(_LinearDesc), c_int, c_void_p]
-        c.hifihr_linear_bwd_group.argtypes = [POINTER(_LinearDesc), c_int, c_void_p]
-        c.hifihr_conv2d_bwd_data_pre.argtypes = [_c_float_p] * 3 + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]
-        c.hifihr_conv2d_bwd_data_pre_res.argtypes = [_c_float_p] * 4 + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]
-        c.hifihr_conv2d_bwd_data_pre_plus1x1.argtypes = [_c_float_p] * 5 + [c_int] * 9 + [c_void_p]
-        c.hifihr_conv2d_bwd_data_pre_plus1x1_supported.argtypes = [c_int] * 9
-        c.hifihr_conv2d_bwd_weight_plus1x1.argtypes = [_c_float_p] * 5 + [c_int] * 9 + [c_void_p]
-        c.hifihr_conv2d_bwd_weight_plus1x1_supported.argtypes = [c_int] * 9
-        c.hifihr_weight_prep.argtypes = [c_void_p, c_int, c_int, c_void_p]
-        c.hifihr_freihand_augment.argtypes = [c_void_p, c_void_p, _c_int_p, _c_int_p, c_int, c_int, c_int, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_ho3d_workspace_bytes.argtypes = [c_int, c_int]
-        c.hifihr_ho3d_workspace_bytes.restype = c_size_t
-        c.hifihr_ho3d_batch.argtypes = ([c_void_p, c_void_p] + [_c_float_p] * 3 + [c_int, c_int, _c_int_p, c_int, c_int, c_void_p, c_size_t] +
-                                        [_c_float_p] * 5 + [c_void_p])
-        c.hifihr_freihand_batch.argtypes = ([c_void_p, c_void_p] + [_c_float_p] * 4 + [c_int, c_int, _c_int_p, c_int, c_int, c_int, _c_float_p,
-                                            _c_float_p, c_void_p] + [_c_float_p] * 6 + [c_void_p, c_void_p])
-        c.hifihr_freihand_batch_step.argtypes = ([c_void_p, c_void_p] + [_c_float_p] * 4 + [c_int, c_int, _c_int_p, c_int, c_int, c_int, _c_float_p,
-                                                 _c_float_p, c_void_p] + [_c_float_p] * 6 + [c_void_p, c_int, c_float] + [_c_float_p] * 4 + [c_void_p])
-        c.hifihr_light_split_fwd.argtypes = [_c_float_p, c_int, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_light_split_bwd.argtypes = [_c_float_p, _c_float_p, _c_float_p, c_int, _c_float_p, c_void_p]
-        c.hifihr_wino4_bwd_gemm_pair_supported.argtypes = [c_int] * 5
-        c.hifihr_wino4_bwd_gemm_pair.argtypes = [_c_float_p] * 6 + [c_int] * 6 + [c_void_p]
-        c.hifihr_loss_total_fwd.argtypes = [POINTER(_c_float_p), POINTER(c_int), c_int, _c_float_p, c_void_p]
-        c.hifihr_loss_total_bwd.argtypes = [_c_float_p, POINTER(_c_float_p), POINTER(c_int), POINTER(c_int), c_int, c_void_p]
-        c.hifihr_procrustes_error.argtypes = [_c_float_p, _c_float_p, c_int, c_int, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_point_error_hist.argtypes = [_c_float_p, _c_float_p, c_void_p, c_int, c_int, POINTER(ctypes.c_double), c_int, _c_int_p, c_void_p,
-                                              c_void_p]
-        c.hifihr_fscore_counts.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, POINTER(ctypes.c_double), c_int, _c_int_p, c_void_p]
-        c.hifihr_wino_wgrad_gemm.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino_dw_transform.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_void_p]
-        c.hifihr_weight_transpose.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_void_p]
-        c.hifihr_bgemm_nt.argtypes = [_c_float_p] * 3 + [c_int] * 4 + [c_void_p, c_size_t, c_void_p]
-        c.hifihr_bgemm_nt_workspace_bytes.argtypes = [c_int] * 4
-        c.hifihr_bgemm_nt_workspace_bytes.restype = c_size_t
-        c.hifihr_renderer_set_light_mode.argtypes = [c_void_p, c_int]
-        c.hifihr_texture_pca_fwd.argtypes = [_c_float_p] * 3 + [c_int, c_int, c_long, _c_float_p, c_void_p]
-        c.hifihr_texture_pca_bwd.argtypes = [_c_float_p] * 2 + [c_int, c_int, c_long, _c_float_p, c_void_p]
-        c.hifihr_comm_last_error.restype = c_char_p
-        c.hifihr_comm_get_unique_id.argtypes = [c_void_p]
-        c.hifihr_comm_init.argtypes = [POINTER(c_void_p), c_int, c_int, c_void_p]
-        c.hifihr_comm_allreduce_f32.argtypes = [c_void_p, _c_float_p, c_size_t, c_void_p]
-        c.hifihr_comm_broadcast_f32.argtypes = [c_void_p, _c_float_p, c_size_t, c_int, c_void_p]
-        c.hifihr_comm_destroy.argtypes = [c_void_p]
-        c.hifihr_wino_tile.argtypes = [c_int] * 5
-        c.hifihr_wino_gemm_workspace_bytes.argtypes = [c_int] * 6
-        c.hifihr_wino_gemm_workspace_bytes.restype = c_size_t
-        c.hifihr_wino_weight_transform.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_int, c_void_p]
-        c.hifihr_wino_input_transform.argtypes = [_c_float_p, _c_float_p] + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino_gemm.argtypes = [_c_float_p] * 3 + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]
-        c.hifihr_wino_output_transform.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino_output_transform_act.argtypes = [_c_float_p] * 3 + [c_int] * 6 + [c_void_p]
-        c.hifihr_conv3x3_c64_wino_supported.argtypes = [c_int] * 5
-        c.hifihr_conv3x3_c64_wino.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
-        c.hifihr_conv3x3_c64_wino_res.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
-        c.hifihr_conv3x3_c64_bwd_pair_supported.argtypes = [c_int] * 3
-        c.hifihr_conv3x3_c64_bwd_pair.argtypes = [c_void_p] * 7 + [c_size_t] + [c_int] * 3 + [c_void_p]
-        c.hifihr_conv3x3_c64_bwd_pair_slabs.argtypes = [c_void_p] * 6 + [c_size_t] + [c_int] * 3 + [c_void_p, c_void_p]
-        c.hifihr_conv_halo_wgrad_reduce_multi.argtypes = [c_void_p, c_int, c_void_p]
-        c.hifihr_wino_bn_input_supported.argtypes = [c_int, c_int]
-        c.hifihr_wino_bn_input_transform.argtypes = [_c_float_p] * 7 + [c_int] * 5 + [c_float, c_float] + [_c_float_p] * 4 + [c_void_p]
-        c.hifihr_wino_output_transform_bnred.argtypes = [_c_float_p] * 10 + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino_bn_bwd_dual_transform.argtypes = [_c_float_p] * 8 + [c_int] * 5 + [_c_float_p] * 2 + [c_void_p]
-        c.hifihr_bn_bwd_apply.argtypes = [_c_float_p] * 5 + [c_long, c_int] + [_c_float_p] * 4 + [c_void_p]
-        c.hifihr_joint_terms_fwd.argtypes = [_c_float_p] * 4 + [c_int] * 3 + [POINTER(c_float), _c_float_p, c_void_p]
-        c.hifihr_joint_terms_bwd.argtypes = [_c_float_p] * 4 + [c_int] * 3 + [POINTER(c_float)] + [_c_float_p] * 3 + [c_void_p]
-        c.hifihr_wino_dy_transform.argtypes = [_c_float_p] * 2 + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino_input_dy_transform.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino_wgrad_parts.argtypes = [c_int] * 6
-        c.hifihr_wino_wgrad_gemm_parts.argtypes = [_c_float_p] * 3 + [c_int] * 7 + [c_void_p]
-        c.hifihr_wino_dw_transform_parts.argtypes = [_c_float_p, c_int, _c_float_p, c_int, c_int, c_int, c_void_p]
-        c.hifihr_bgemm_describe.argtypes = [c_int] * 5 + [ctypes.c_char_p, c_int]
-        c.hifihr_conv2d_describe.argtypes = [c_int] * 10 + [ctypes.c_char_p, c_int]
-        c.hifihr_bgemm_tn_parts.argtypes = [c_int] * 4
-        c.hifihr_bgemm_tn_coherent.argtypes = [c_int] * 4
-        c.hifihr_bgemm_tn.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
-        c.hifihr_wino4_dw_transform_multi.argtypes = [c_void_p, c_int, c_void_p]
-        c.hifihr_se_pool.argtypes = [_c_float_p, c_int, c_int, c_int, _c_float_p, c_void_p]
-        c.hifihr_se_scale.argtypes = [_c_float_p, _c_float_p, _c_float_p, c_float, c_int, c_int, c_int, _c_float_p, c_void_p]
-        c.hifihr_se_bwd_gate.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, _c_float_p, c_void_p]
-        c.hifihr_se_mlp_supported.argtypes = [c_int, c_int]
-        c.hifihr_wino_tiles.argtypes = [c_int] * 4
-        c.hifihr_wino_tiles.restype = c_long
-        c.hifihr_wino_tiles_computed.argtypes = [c_int] * 4
-        c.hifihr_wino_tiles_computed.restype = c_long
-        c.hifihr_zero_page_ready.argtypes = [c_void_p]
-        c.hifihr_drop_connect_add.argtypes = [_c_float_p, _c_float_p, _c_float_p, c_float, c_int, c_size_t, _c_float_p, c_void_p]
-        c.hifihr_se_mlp_fwd.argtypes = [_c_float_p] * 5 + [c_int] * 3 + [_c_float_p] * 4 + [c_void_p]
-        c.hifihr_se_mlp_bwd.argtypes = [_c_float_p] * 7 + [c_int] * 3 + [_c_float_p] * 7 + [c_void_p]
-        c.hifihr_mmpool_fwd.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, _c_float_p, _c_int_p, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_mmpool_bwd.argtypes = [_c_float_p, _c_float_p, _c_int_p, _c_float_p, _c_float_p, c_int, c_int, c_int, _c_float_p,
-                                        _c_float_p, c_void_p]
-        c.hifihr_maxpool2d_fwd.argtypes = [_c_float_p] + [c_int] * 7 + [_c_float_p, c_void_p, c_void_p]
-        c.hifihr_maxpool2d_bwd.argtypes = [_c_float_p, c_void_p] + [c_int] * 7 + [_c_float_p, c_void_p]
-        c.hifihr_maxpool2d_fwd_flat.argtypes = [_c_float_p] + [c_int] * 7 + [_c_float_p, c_void_p, c_void_p]
-        c.hifihr_maxpool2d_bwd_flat.argtypes = [_c_float_p, c_void_p] + [c_int] * 7 + [_c_float_p, c_void_p]
-        c.hifihr_maxpool2d_bwd_relu.argtypes = [_c_float_p, c_void_p, _c_float_p] + [c_int] * 7 + [_c_float_p, c_void_p]
-        c.hifihr_wino_output_transform_mask.argtypes = [_c_float_p] * 3 + [c_int] * 5 + [c_void_p]
-        c.hifihr_adam_step.argtypes = [_c_float_p, _c_float_p, _c_float_p, _c_float_p, c_size_t, c_float, c_float, c_float,
-                                       c_float, c_float, c_float, c_int, c_void_p]
-        c.hifihr_adam_state_bytes.restype = c_size_t
-        c.hifihr_adam_state_bytes.argtypes = []
-        c.hifihr_adam_step_counted.argtypes = [_c_float_p, _c_float_p, _c_float_p, _c_float_p, c_size_t, c_float, c_float, c_float, c_void_p, c_void_p]
-        c.hifihr_grad_guard_bytes.restype = c_size_t
-        c.hifihr_grad_guard_bytes.argtypes = []
-        c.hifihr_grad_norm_workspace_bytes.restype = c_size_t
-        c.hifihr_grad_norm_workspace_bytes.argtypes = [c_size_t]
-        c.hifihr_grad_norm.argtypes = [_c_float_p, c_size_t, c_float, c_float, c_void_p, c_void_p, c_void_p]
-        c.hifihr_adam_step_guarded.argtypes = [_c_float_p, _c_float_p, _c_float_p, _c_float_p, c_size_t, c_float, c_float, c_float, c_float,
-                                               c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]
-        c.hifihr_adam_step_dyn.argtypes = [_c_float_p, _c_float_p, _c_float_p, _c_float_p, c_size_t, c_float, c_float, c_float,
-                                           c_float, c_float, _c_float_p, c_void_p]
-        c.hifihr_renderer_destroy.argtypes = [c_void_p]
-        c.hifihr_render_workspace_bytes.argtypes = [c_void_p, c_int]
-        c.hifihr_render_workspace_bytes.restype = c_size_t
-        c.hifihr_render_fwd.argtypes = [c_void_p, _c_float_p, _c_float_p, c_int, _c_float_p, _c_float_p, _c_float_p, c_int,
-                                        _c_float_p, _c_int_p, c_void_p, c_void_p]
-        c.hifihr_render_bwd.argtypes = [c_void_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_int_p, _c_float_p, c_int,
-                                        _c_float_p, _c_float_p, _c_float_p, _c_float_p, c_void_p, c_void_p]
-        c.hifihr_soft_sil_workspace_bytes.argtypes = [c_void_p, c_int]
-        c.hifihr_soft_sil_workspace_bytes.restype = c_size_t
-        c.hifihr_soft_sil_fwd.argtypes = [c_void_p, _c_float_p, _c_float_p, c_int, c_float, c_float, _c_float_p, _c_float_p, c_void_p, c_void_p]
-        c.hifihr_soft_sil_bwd.argtypes = [c_void_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, c_int, c_float, c_float, _c_float_p, c_void_p,
-                                          c_void_p]
-        c.hifihr_soft_sil_loss_fwd.argtypes = [_c_float_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, _c_float_p, c_void_p]
-        c.hifihr_soft_sil_loss_bwd.argtypes = [_c_float_p, c_void_p, c_int, c_void_p, _c_float_p, c_int, c_int, c_float, c_float, _c_float_p,
-                                               c_void_p]
-        c.hifihr_render_depth_workspace_bytes.argtypes = [c_void_p, c_int]
-        c.hifihr_render_depth_workspace_bytes.restype = c_size_t
-        c.hifihr_render_depth_fwd.argtypes = [c_void_p, _c_float_p, _c_float_p, _c_int_p, c_int, _c_float_p, _c_int_p, c_void_p]
-        c.hifihr_render_depth_bwd.argtypes = [c_void_p, _c_float_p, _c_float_p, _c_int_p, _c_float_p, _c_int_p, c_int, _c_float_p, c_void_p,
-                                              c_void_p]
-        c.hifihr_depth_loss_fwd.argtypes = [_c_float_p, _c_int_p, _c_float_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p,
-                                            _c_float_p, c_void_p]
-        c.hifihr_depth_loss_bwd.argtypes = [_c_float_p, _c_int_p, _c_float_p, c_void_p, c_int, c_void_p, _c_float_p, c_int, c_int, c_float,
-                                            c_float, _c_float_p, c_void_p]
-        c.hifihr_mesh_topology_create.argtypes = [_c_int_p, c_int, c_int]
-        c.hifihr_mesh_topology_create.restype = c_void_p
-        c.hifihr_mesh_topology_destroy.argtypes = [c_void_p]
-        c.hifihr_mesh_topology_counts.argtypes = [c_void_p, _c_int_p, _c_int_p, _c_int_p]
-        c.hifihr_mesh_reg_partial_floats.argtypes = [c_void_p, c_int]
-        c.hifihr_mesh_reg_partial_floats.restype = c_size_t
-        c.hifihr_mesh_reg_fwd.argtypes = [c_void_p, _c_float_p, c_int, c_float, c_float, _c_float_p, _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_mesh_reg_bwd.argtypes = [c_void_p, _c_float_p, _c_float_p, _c_float_p, c_int, c_float, c_float, _c_float_p, c_void_p]
-        c.hifihr_chamfer_geometry.argtypes = [_c_int_p, _c_int_p]
-        c.hifihr_chamfer_geometry.restype = None
-        c.hifihr_chamfer_workspace_bytes.argtypes = [c_int, c_int, c_int]
-        c.hifihr_chamfer_workspace_bytes.restype = c_size_t
-        c.hifihr_chamfer_fwd.argtypes = [_c_float_p, _c_float_p, c_int, c_int, c_int, c_float, c_float, _c_int_p, _c_int_p, c_void_p, c_void_p,
-                                         c_void_p, _c_float_p, c_void_p, c_void_p]
-        c.hifihr_chamfer_bwd.argtypes = [_c_float_p, _c_float_p, _c_int_p, _c_int_p, _c_float_p, c_int, c_int, c_int, c_float, c_float,
-                                         _c_float_p, _c_float_p, c_void_p]
-        c.hifihr_point_mesh_geometry.argtypes = [_c_int_p] * 4
-        c.hifihr_point_mesh_geometry.restype = None
-        c.hifihr_point_mesh_workspace_bytes.argtypes = [c_int] * 4
-        c.hifihr_point_mesh_workspace_bytes.restype = c_size_t
-        c.hifihr_point_mesh_fwd.argtypes = [_c_float_p, _c_float_p, _c_int_p, c_int, c_int, c_int, c_int, c_float, c_float, _c_int_p, c_void_p,
-                                            c_void_p, _c_int_p, c_void_p, c_void_p, c_void_p, _c_float_p, c_void_p, c_void_p]
-        c.hifihr_point_mesh_bwd.argtypes = [_c_float_p, _c_float_p, _c_int_p, _c_int_p, c_void_p, _c_int_p, c_void_p, _c_float_p, _c_int_p,
-                                            _c_int_p, c_int, c_int, c_int, c_int, c_float, c_float, _c_float_p, _c_float_p, c_void_p, c_void_p]
-        c.hifihr_renderer_set_uv.argtypes = [c_void_p, _c_int_p, _c_float_p, c_int]
-        c.hifihr_render_uv_scratch_bytes.argtypes = [c_void_p, c_int]
-        c.hifihr_render_uv_scratch_bytes.restype = c_size_t
-        c.hifihr_render_fwd_uv.argtypes = [c_void_p, _c_float_p, _c_float_p, c_int, c_int, _c_float_p, _c_float_p, _c_float_p, c_int, _c_float_p,
-                                           _c_int_p, _c_float_p, c_void_p, c_void_p]
-        c.hifihr_render_bwd_uv.argtypes = [c_void_p, _c_float_p, _c_float_p, c_int, c_int, _c_float_p, _c_float_p, _c_float_p, _c_int_p, _c_float_p,
-                                           c_int] + [_c_float_p] * 6 + [c_void_p, c_void_p]
+        from ._abi import prototypes           # (imported here: _abi takes HifihrError and _LinearDesc from this module)
+        for name, (restype, argtypes, _) in prototypes().items():    # every signature is include/hifihr.h's own
+            fn = getattr(self.c, name)
+            fn.restype, fn.argtypes = restype, argtypes
 
     # ------------------------------------------------------------------
     def check(self, rc: int, what: str):
@@ -637,7 +392,7 @@ class HifihrLib:
         import ctypes
         n = ctypes.c_int(0)
         self.check(self.c.hifihr_conv3x3_c64_bwd_pair_slabs(_fp(dy), _fp(U_bwd), _fp(res), _fp(dx), _fp(x), _fp(slabs), slabs.numel() * slabs.element_size(),
-                                                            N, H, W, ctypes.cast(ctypes.pointer(n), c_void_p), _stream_of(dy)), "hifihr_conv3x3_c64_bwd_pair_slabs")
+                                                            N, H, W, ctypes.byref(n), _stream_of(dy)), "hifihr_conv3x3_c64_bwd_pair_slabs")
         return n.value
 
     def conv_halo_wgrad_reduce_multi(self, jobs):

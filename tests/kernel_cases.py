@@ -6390,10 +6390,10 @@ def render_refusal_case(lib, device, entry):
     G = Guards(device)
     _render_drain(lib, device)
 
-    def _raw(lib_, name, *a):                                             # (the argument types hifihr_amd._lib declared: cast the pointers to them)
+    def _raw(lib_, name, *a):                                             # (the argument types include/hifihr.h declares: cast the pointers to them)
         fn = getattr(lib_.c, name)
-        a = [ctypes.cast(x, t) if isinstance(x, vp) and t is not None and t is not vp and hasattr(t, "contents") else x
-             for x, t in zip(a, fn.argtypes or [None] * len(a))]
+        a = [ctypes.cast(x, t) if isinstance(x, vp) and t is not vp and hasattr(t, "contents") else x
+             for x, t in zip(a, fn.argtypes)]
         lib_.check(fn(*a), name)
 
     def create(out="ok", faces_=faces, V_=V, F2=F_, H_=H, aa_=aa, null=None):
@@ -6441,7 +6441,6 @@ def render_refusal_case(lib, device, entry):
             # a refused set_uv leaves the renderer without tables: the UV forward is still refused
             return True
         if entry in ("renderer_destroy", "render_workspace_bytes", "render_uv_scratch_bytes"):
-            lib.c.hifihr_render_workspace_bytes.restype = ctypes.c_size_t
             assert lib.c.hifihr_render_workspace_bytes(vp(0), c_int(2)) == 0 and lib.render_workspace_bytes(h, -1) == 0
             sizes = [lib.render_workspace_bytes(h, b) for b in range(6)]
             assert sizes == sorted(sizes) and sizes[1] > 0, sizes
