@@ -128,7 +128,7 @@ class FusedAdam(torch.optim.Optimizer):
         if self._lib is None:
             self._lib = get_lib()
         if self._state is None:
-            self._state = torch.zeros(int(self._lib.c.hifihr_adam_state_bytes()), dtype=torch.uint8, device=self.flatp.flat.device)
+            self._state = torch.zeros(self._lib.adam_state_bytes(), dtype=torch.uint8, device=self.flatp.flat.device)
 
     def disable_graph_mode(self):
         """Back to the eager step (scalars passed by value, step counter advanced by step())."""
