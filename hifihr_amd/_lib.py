@@ -345,6 +345,17 @@ class HifihrLib:
         self._run("hifihr_joint_terms_bwd", j2d, j2d_gt, joints, joints_gt, ref.shape[0], ref.shape[1], mse, _floats(lam3, 3), gout, g_j2d,
                   g_joints)
 
+    def open2d_terms_fwd(self, j2d, open_2dj, open_2dj_con, lam3, out):
+        """out[3] = lambda-weighted (open_2dj, open_bone_direc, open_2dj_de); open_2dj_con [B,21] or [B,21,1], contiguous."""
+        B, J = j2d.shape[0], j2d.shape[1]
+        assert open_2dj.shape == j2d.shape and open_2dj_con.numel() == B * J and open_2dj_con.is_contiguous(), (j2d.shape, open_2dj_con.shape)
+        self._run("hifihr_open2d_terms_fwd", j2d, open_2dj, open_2dj_con, B, J, _floats(lam3, 3), out)
+
+    def open2d_terms_bwd(self, j2d, open_2dj, open_2dj_con, lam3, gout, g_j2d):
+        B, J = j2d.shape[0], j2d.shape[1]
+        assert open_2dj.shape == j2d.shape and open_2dj_con.numel() == B * J and open_2dj_con.is_contiguous(), (j2d.shape, open_2dj_con.shape)
+        self._run("hifihr_open2d_terms_bwd", j2d, open_2dj, open_2dj_con, B, J, _floats(lam3, 3), gout, g_j2d)
+
     def geom_loss_fwd(self, joints, joints_gt, verts, verts_gt, shape, pose, faces, mse, lam, partial, out):
         B, J, V = joints.shape[0], joints.shape[1], verts.shape[1]
         F = 0 if faces is None else faces.shape[0]
@@ -518,6 +529,16 @@ class HifihrLib:
             return
         # + the terms every training iteration derives from the batch: root_xyz, root-relative ground truth, the NDC camera
         self._run("hifihr_freihand_batch_step", *batch, root_id, image_size or H, g("root_xyz"), g("joints_rel"), g("verts_rel"), g("cam_ndc"))
+
+    def freihand_keypoints(self, open_2dj, open_2dj_con, idx, total, j2d_gt, semi_below, out_open_2dj, out_con, out_texture_con):
+        """The detections of a batch (hifihr_freihand_keypoints): cache open_2dj [n,21,2] / open_2dj_con [n,21] or [n,21,1], idx int32 [B],
+        total [B,3,3]; j2d_gt [B,21,2] with semi_below > 0.  Outputs [B,21,2], [B,21] or [B,21,1], [B]; any may be None."""
+        n, B = open_2dj.shape[0], idx.shape[0]
+        assert open_2dj.shape[1:] == (21, 2) and open_2dj_con.numel() == n * 21 and total.numel() == 9 * B, (open_2dj.shape, open_2dj_con.shape)
+        for t, numel in ((out_open_2dj, B * 42), (out_con, B * 21), (out_texture_con, B), (j2d_gt, B * 42)):
+            assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == numel)
+        self._run("hifihr_freihand_keypoints", open_2dj, open_2dj_con, n, idx, total, j2d_gt, semi_below, B, out_open_2dj, out_con,
+                  out_texture_con)
 
     def ho3d_workspace_bytes(self, B, out_size):
         return self._call("hifihr_ho3d_workspace_bytes", B, out_size)

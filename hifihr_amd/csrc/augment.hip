@@ -201,6 +201,64 @@ __global__ __launch_bounds__(256) void freihand_batch_meta_kernel(BatchMeta m) {
   }
 }
 
+// The 2-D detections of a FreiHAND training batch (the self-supervised configs' `trans_open_2dj`, `open_2dj_con` and the `texture_con`
+// data_dic derives from them: reference data/dataset.py:196-201, 255-257; utils/traineval_util.py:55-66, 106-111), one workgroup per sample:
+//   open_2dj     = total . (x, y, 1) of the cached detections, `total` the float32 forward affine of the image warp
+//                  (handutils.transform_coords without its final truncation to integers: the sub-pixel position is kept), each
+//                  coordinate as fmaf(t0, x, fmaf(t1, y, t2))
+//   open_2dj_con = the cached confidences, bit for bit
+//   texture_con  = mean_j([min_j con > 0.1] con_j) ([idx < 32560] + 0.1), summed in joint order, from the confidences BEFORE the mix
+//   semi mix     = samples with idx % 32560 < semi_below take j2d_gt for their detections and 1 for their confidences (semi_below =
+//                  ceil(32560 semi_ratio): the same samples as `raw_idx < 32560 * semi_ratio` picks among integers)
+// An index outside the cache gives that sample zeros (the entry cannot see the indices: they live in device memory).
+struct KeypointArgs {
+  const float *det, *con;                        // cache: [n][21][2], [n][21]
+  const int* idx;                                // [B]
+  const float* total;                            // [B][3][3]
+  const float* j2d_gt;                           // [B][21][2] or NULL
+  int n, B, semi_below;
+  float *odet, *ocon, *otex;
+};
+__global__ __launch_bounds__(64) void freihand_keypoints_kernel(KeypointArgs k) {
+  __shared__ float sc[21];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int id = k.idx[b];
+  const bool ok = id >= 0 && id < k.n;
+  const bool mix = ok && k.j2d_gt != nullptr && (id % 32560) < k.semi_below;
+  if (t < 21) {
+    const float c = ok ? k.con[(size_t)id * 21 + t] : 0.f;
+    sc[t] = c;
+    float u = 0.f, v = 0.f;
+    if (mix) {
+      u = k.j2d_gt[((size_t)b * 21 + t) * 2];
+      v = k.j2d_gt[((size_t)b * 21 + t) * 2 + 1];
+    } else if (ok) {
+      const float* m = k.total + (size_t)b * 9;
+      const float x = k.det[((size_t)id * 21 + t) * 2], y = k.det[((size_t)id * 21 + t) * 2 + 1];
+      u = fmaf(m[0], x, fmaf(m[1], y, m[2]));
+      v = fmaf(m[3], x, fmaf(m[4], y, m[5]));
+    }
+    if (k.odet) { k.odet[((size_t)b * 21 + t) * 2] = u; k.odet[((size_t)b * 21 + t) * 2 + 1] = v; }
+    if (k.ocon) k.ocon[(size_t)b * 21 + t] = mix ? 1.f : c;
+  }
+  __syncthreads();
+  if (t == 0 && k.otex) {
+    float lo = sc[0], s = 0.f;
+    for (int j = 1; j < 21; ++j) lo = sc[j] < lo ? sc[j] : lo;
+    const float gate = lo > 0.1f ? 1.f : 0.f;
+    for (int j = 0; j < 21; ++j) s += gate * sc[j];
+    k.otex[b] = (s / 21.f) * ((id < 32560 ? 1.f : 0.f) + 0.1f);
+  }
+}
+
+hipError_t launch_freihand_keypoints(const float* det, const float* con, int n, const int* idx, const float* total, const float* j2d_gt,
+                                     int semi_below, int B, float* odet, float* ocon, float* otex, hipStream_t st) {
+  if (B <= 0 || n <= 0) return hipErrorInvalidValue;
+  const KeypointArgs k{det, con, idx, total, j2d_gt, n, B, semi_below, odet, ocon, otex};
+  hipLaunchKernelGGL(freihand_keypoints_kernel, dim3(B), dim3(64), 0, st, k);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // HO-3D sample assembly (the HO-3D half): the hand crop of reference data/dataset.py:1105-1215 --
 // `func_transforms.resized_crop(image, y1, x1, size, size, [224, 224])` for the frame (bilinear) and for the hand mask (bicubic), i.e.

@@ -1302,6 +1302,22 @@ int hifihr_joint_terms_bwd(const float* j2d, const float* j2d_gt, const float* j
   return HIFIHR_OK;
 }
 
+int hifihr_open2d_terms_fwd(const float* j2d, const float* open_2dj, const float* open_2dj_con, int B, int J, const float* lam3_host,
+                            float* out3, void* stream) {
+  if (!j2d || !open_2dj || !open_2dj_con || !lam3_host || !out3 || B <= 0 || J != 21)
+    return fail(HIFIHR_EINVAL, "hifihr_open2d_terms_fwd: bad argument (J must be 21)");
+  HIP_TRY(hifihr::launch_open2d_terms_fwd(j2d, open_2dj, open_2dj_con, B, J, lam3_host, out3, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_open2d_terms_bwd(const float* j2d, const float* open_2dj, const float* open_2dj_con, int B, int J, const float* lam3_host,
+                            const float* gout3, float* g_j2d, void* stream) {
+  if (!j2d || !open_2dj || !open_2dj_con || !lam3_host || !gout3 || !g_j2d || B <= 0 || J != 21)
+    return fail(HIFIHR_EINVAL, "hifihr_open2d_terms_bwd: bad argument (J must be 21)");
+  HIP_TRY(hifihr::launch_open2d_terms_bwd(j2d, open_2dj, open_2dj_con, B, J, lam3_host, gout3, g_j2d, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
 int hifihr_geom_loss_bwd(const float* joints, const float* joints_gt, const float* verts, const float* verts_gt, const float* shape,
                          const float* pose, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_idx, int B, int J, int V,
                          int F, int NS, int NP, int mse, const float* lambda5, const float* gout, float* gj, float* gv, float* gshape,
@@ -1856,6 +1872,17 @@ int hifihr_freihand_batch_step(const uint32_t* img_rgbx, const uint8_t* mask, co
                                         out_Ps, out_joints, out_verts, out_j2d, out_scales, out_idxs,
                                         hifihr::BatchStepOut{root_id, image_size, out_root, out_joints_rel, out_verts_rel, out_cam_ndc},
                                         (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_freihand_keypoints(const float* open_2dj, const float* open_2dj_con, int n, const int* idx, const float* total,
+                              const float* j2d_gt, int semi_below, int B, float* out_open_2dj, float* out_con, float* out_texture_con,
+                              void* stream) {
+  if (!open_2dj || !open_2dj_con || !idx || !total || n <= 0 || B <= 0 || semi_below < 0 || (semi_below > 0 && !j2d_gt) ||
+      (!out_open_2dj && !out_con && !out_texture_con))
+    return fail(HIFIHR_EINVAL, "hifihr_freihand_keypoints: bad argument");
+  HIP_TRY(hifihr::launch_freihand_keypoints(open_2dj, open_2dj_con, n, idx, total, j2d_gt, semi_below, B, out_open_2dj, out_con,
+                                            out_texture_con, (hipStream_t)stream));
   return HIFIHR_OK;
 }
 

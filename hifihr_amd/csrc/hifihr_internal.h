@@ -483,6 +483,9 @@ hipError_t launch_freihand_batch(const uint32_t* img, const uint8_t* mask, const
                                  const float* scales, int J, int V, const int* packed, int B, int H, int W, float* out_img, float* out_mask,
                                  long long* out_segm, float* oKs, float* oPs, float* ojoints, float* overts, float* oj2d, float* oscales,
                                  long long* oidx, const BatchStepOut& step, hipStream_t st);
+// the detections of a FreiHAND batch (augment.hip): gather, forward affine of the image warp, texture_con, the semi-supervised mix
+hipError_t launch_freihand_keypoints(const float* det, const float* con, int n, const int* idx, const float* total, const float* j2d_gt,
+                                     int semi_below, int B, float* odet, float* ocon, float* otex, hipStream_t st);
 size_t ho3d_workspace_bytes(int B, int out_size);
 hipError_t launch_ho3d_batch(const uint32_t* img, const uint8_t* mask, const float* Ks, const float* uv21, const float* xyz21, int FH, int FW,
                              const int* packed, int B, int out_size, void* ws, float* out_img, float* out_mask, float* out_K,
@@ -610,5 +613,10 @@ hipError_t launch_joint_terms_fwd(const float* j2d, const float* j2d_gt, const f
                                   const float* lam3, float* out3, hipStream_t st);
 hipError_t launch_joint_terms_bwd(const float* j2d, const float* j2d_gt, const float* j3d, const float* j3d_gt, int B, int J, int mse,
                                   const float* lam3, const float* gout3, float* g_j2d, float* g_j3d, hipStream_t st);
+// open_2dj / open_bone_direc / open_2dj_de (losses.hip): the self-supervised keypoint terms; con [B][21]
+hipError_t launch_open2d_terms_fwd(const float* j2d, const float* det, const float* con, int B, int J, const float* lam3, float* out3,
+                                   hipStream_t st);
+hipError_t launch_open2d_terms_bwd(const float* j2d, const float* det, const float* con, int B, int J, const float* lam3, const float* gout3,
+                                   float* g_j2d, hipStream_t st);
 
 }  // namespace hifihr

@@ -436,4 +436,106 @@ hipError_t launch_joint_terms_bwd(const float* j2d, const float* j2d_gt, const f
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// The self-supervised keypoint terms (reference losses.py:45-63, 79-85 of the deprecated loss_func; utils/losses_util.py:217-283 with the
+// detector's confidences): the projected joints against off-the-shelf 2-D detections det[B][21][2] with confidences con[B][21].
+//   open_2dj        = lam0 sum_bj rho(d_bj) (c_bj w_j)^2 / sum_bj (c_bj w_j)^2,  d = |j2d - det|, rho(d) = d^2 / 10 (d < 5), d - 2.5 (else);
+//                     the normalisation is over the WHOLE batch; a batch whose weights sum to 0 gives exactly 0 (the reference: 0 / 0)
+//   open_bone_direc = lam1 mean over B x 20 bones of |vn - von|^2 c_parent c_child  (the reference's mask-and-gather of the 21 x 21
+//                     confidence products picks, in bone order, exactly the product of a bone's two joints)
+//   open_2dj_de     = lam2 mean (det - j2d)^2  (always MSE in the reference)
+// One single-workgroup launch forward (thread-strided partial sums folded by block_sum: a fixed order); backward: thread = sample, its 21
+// joints' gradients are private to it.  Every backward workgroup first folds the batch's weight sum itself, in one fixed order, so the
+// pair shares no buffer.  No gradient reaches the detections or the confidences.
+// ------------------------------------------------------------------------------------------------
+struct Open2dArgs {
+  const float* j2d; const float* det; const float* con;
+  int B, J;
+  float lam[3];
+};
+__constant__ float kKeypointWeight[21] = {2.f, 1.f, 1.f, 1.f, 1.5f, 1.f, 1.f, 1.f, 1.5f, 1.f, 1.f, 1.f, 1.5f, 1.f, 1.f, 1.f, 1.5f, 1.f, 1.f, 1.f, 1.5f};
+
+__device__ __forceinline__ float open2d_weight(const float* __restrict__ con, int i, int joint) {
+  const float cw = con[i] * kKeypointWeight[joint];
+  return cw * cw;
+}
+
+__global__ __launch_bounds__(256) void open2d_terms_fwd_kernel(Open2dArgs a, float* __restrict__ out) {
+  __shared__ float lds[4 * 4];
+  float s[4] = {0.f, 0.f, 0.f, 0.f};                  // sum rho w, sum w, sum bone terms, sum squared differences
+  for (int i = threadIdx.x; i < a.B * a.J; i += 256) {
+    const int b = i / a.J, joint = i - b * a.J;
+    const float dx = a.j2d[2 * i] - a.det[2 * i], dy = a.j2d[2 * i + 1] - a.det[2 * i + 1];
+    const float d2 = dx * dx + dy * dy, d = sqrtf(d2);
+    const float w = open2d_weight(a.con, i, joint);
+    s[0] += (d < 5.f ? d2 / 10.f : d - 2.5f) * w;
+    s[1] += w;
+    s[3] += base_term(1, dx) + base_term(1, dy);
+  }
+  for (int i = threadIdx.x; i < a.B * 20; i += 256) {
+    const int b = i / 20, bone = i - b * 20;
+    float dn[2], il, vn[2];
+    const float t = bone_term<2>(a.j2d + (size_t)b * a.J * 2, a.det + (size_t)b * a.J * 2, bone, dn, &il, vn);
+    s[2] += t * (a.con[b * a.J + kBoneParent[bone]] * a.con[b * a.J + kBoneChild[bone]]);
+  }
+  block_sum<4>(s, lds);
+  if (threadIdx.x == 0) {
+    out[0] = s[1] > 0.f ? a.lam[0] * s[0] / s[1] : 0.f;
+    out[1] = a.lam[1] * s[2] / (float)(a.B * 20);
+    out[2] = a.lam[2] * s[3] / (float)(a.B * a.J * 2);
+  }
+}
+
+// d rho / d j2d = (j2d - det) / 5 for d < 5 (no square root: 0 at d = 0, where autograd of the reference gives sqrt'(0) x 0 = NaN), else
+// (j2d - det) / d; value and slope of rho agree at d = 5.  The bone part is joint_terms_bwd_kernel's, times the bone's confidence.
+__global__ __launch_bounds__(64) void open2d_terms_bwd_kernel(Open2dArgs a, const float* __restrict__ gout, float* __restrict__ g_j2d) {
+  float wsum = 0.f;                                   // every lane takes part in the fold: no early return above it
+  for (int i = threadIdx.x; i < a.B * a.J; i += 64) wsum += open2d_weight(a.con, i, i % a.J);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) wsum += __shfl_down(wsum, off, 64);
+  wsum = __shfl(wsum, 0, 64);
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= a.B) return;
+  const float c0 = wsum > 0.f ? gout[0] * a.lam[0] / wsum : 0.f;
+  const float c1 = gout[1] * a.lam[1] / (float)(a.B * 20), c2 = 2.f * gout[2] * a.lam[2] / (float)(a.B * a.J * 2);
+  const float* j = a.j2d + (size_t)b * a.J * 2;
+  const float* jd = a.det + (size_t)b * a.J * 2;
+  const float* c = a.con + (size_t)b * a.J;
+  float g[21 * 2];
+  for (int joint = 0; joint < 21; ++joint) {
+    const float dx = j[2 * joint] - jd[2 * joint], dy = j[2 * joint + 1] - jd[2 * joint + 1];
+    const float d2 = dx * dx + dy * dy, d = sqrtf(d2);
+    const float k = c0 * open2d_weight(c, joint, joint) * (d < 5.f ? 0.2f : 1.f / d);
+    g[2 * joint] = k * dx + c2 * dx;
+    g[2 * joint + 1] = k * dy + c2 * dy;
+  }
+  for (int bone = 0; bone < 20; ++bone) {
+    float dn[2], il, vn[2];
+    bone_term<2>(j, jd, bone, dn, &il, vn);
+    const float dot = dn[0] * vn[0] + dn[1] * vn[1];             // (dn . v) / (|v| + eps)
+    const int p = kBoneParent[bone], ch = kBoneChild[bone];
+    const float vx = j[ch * 2] - j[p * 2], vy = j[ch * 2 + 1] - j[p * 2 + 1];
+    const float n = sqrtf(vx * vx + vy * vy), k = 2.f * c1 * (c[p] * c[ch]) * il;
+    const float gx = k * (dn[0] - (n > 0.f ? dot * vx / n : 0.f)), gy = k * (dn[1] - (n > 0.f ? dot * vy / n : 0.f));
+    g[ch * 2] += gx; g[p * 2] -= gx;
+    g[ch * 2 + 1] += gy; g[p * 2 + 1] -= gy;
+  }
+  for (int i = 0; i < 21 * 2; ++i) g_j2d[(size_t)b * a.J * 2 + i] = g[i];
+}
+
+hipError_t launch_open2d_terms_fwd(const float* j2d, const float* det, const float* con, int B, int J, const float* lam3, float* out3,
+                                   hipStream_t st) {
+  if (J != 21 || B <= 0) return hipErrorInvalidValue;
+  Open2dArgs a{j2d, det, con, B, J, {lam3[0], lam3[1], lam3[2]}};
+  hipLaunchKernelGGL(open2d_terms_fwd_kernel, dim3(1), dim3(256), 0, st, a, out3);
+  return hipGetLastError();
+}
+hipError_t launch_open2d_terms_bwd(const float* j2d, const float* det, const float* con, int B, int J, const float* lam3, const float* gout3,
+                                   float* g_j2d, hipStream_t st) {
+  if (J != 21 || B <= 0) return hipErrorInvalidValue;
+  Open2dArgs a{j2d, det, con, B, J, {lam3[0], lam3[1], lam3[2]}};
+  hipLaunchKernelGGL(open2d_terms_bwd_kernel, dim3((B + 63) / 64), dim3(64), 0, st, a, gout3, g_j2d);
+  return hipGetLastError();
+}
+
 }  // namespace hifihr

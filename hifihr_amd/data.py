@@ -63,10 +63,12 @@ def pil_affine_fixed_terms(affine_trans):
     return [fix(a), fix(b), fix(c + a * 0.5 + b * 0.5), fix(d), fix(e), fix(f + d * 0.5 + e * 0.5)]
 
 
-def batch_affine_terms(center, scale, res, rots):
+def batch_affine_terms(center, scale, res, rots, with_total=False):
     """`affine_for_rotation` + `pil_affine_fixed_terms` for a whole batch in stacked numpy calls (the per-sample Python loop
     costs ~1 ms per 32 samples, a tenth of a training step).  Returns (fixed int32 [B,6], post_rot_trans f32 [B,3,3],
-    rot_mat f32 [B,3,3]).  Same operations in the same order on stacked arrays; tests compare it with the per-sample path."""
+    rot_mat f32 [B,3,3]).  Same operations in the same order on stacked arrays; tests compare it with the per-sample path.
+    with_total: also the float32 `total` [B,3,3] itself, the forward affine that carries a pixel of the stored image to the warped one
+    (`affinetrans` of data/dataset.py:245-257: what handutils.transform_coords applies to the 2-D detections)."""
     rots = np.asarray(rots, dtype=np.float64)
     B = rots.shape[0]
     sn, cs = np.sin(rots), np.cos(rots)
@@ -92,6 +94,8 @@ def batch_affine_terms(center, scale, res, rots):
     a, b, cc, d, e, f = inv[:, 0, 0], inv[:, 0, 1], inv[:, 0, 2], inv[:, 1, 0], inv[:, 1, 1], inv[:, 1, 2]
     fix = lambda v: np.floor(v * 65536.0 + 0.5).astype(np.int64)
     fixed = np.stack([fix(a), fix(b), fix(cc + a * 0.5 + b * 0.5), fix(d), fix(e), fix(f + d * 0.5 + e * 0.5)], axis=1).astype(np.int32)
+    if with_total:
+        return fixed, post, rot_mat.astype(np.float32), total
     return fixed, post, rot_mat.astype(np.float32)
 
 
@@ -100,9 +104,13 @@ class FreiHandDeviceCache:
 
     images_u8 [n,H,W,3] uint8, masks_u8 [n,H,W] (or [n,H,W,3]) uint8 in {0,255}, Ks [n,3,3], joints [n,21,3], verts [n,778,3]
     (host tensors / arrays; moved once).  `batch(idxs, rots)` returns the reference's training sample dict
-    {trans_images, trans_Ks, trans_joints, trans_verts, trans_masks, scales, idxs} with every tensor on the device."""
+    {trans_images, trans_Ks, trans_joints, trans_verts, trans_masks, scales, idxs} with every tensor on the device.
+    open_2dj [n,21,2] + open_2dj_con [n,21] or [n,21,1]: off-the-shelf 2-D detections in pixels of the stored images and their
+    confidences, for the self-supervised terms; `batch_examples` then also returns KEYPOINT_KEYS (one more launch).  semi_ratio
+    (args.semi_ratio): the share of the training set whose detections are replaced by the projected ground truth."""
 
-    def __init__(self, images_u8, masks_u8, Ks, joints, verts, scales=None, device="cuda", max_rot=math.pi):
+    def __init__(self, images_u8, masks_u8, Ks, joints, verts, scales=None, device="cuda", max_rot=math.pi, open_2dj=None,
+                 open_2dj_con=None, semi_ratio=None):
         images_u8 = torch.as_tensor(images_u8)
         n, H, W, _ = images_u8.shape
         rgbx = torch.zeros(n, H, W, 4, dtype=torch.uint8)
@@ -118,6 +126,15 @@ class FreiHandDeviceCache:
         self.scales = f32(scales) if scales is not None else (self.joints[:, 9] - self.joints[:, 10]).norm(dim=-1)
         self.n, self.H, self.W, self.device, self.max_rot = n, H, W, torch.device(device), max_rot
         self.lib = get_lib()
+        if (open_2dj is None) != (open_2dj_con is None):
+            raise ValueError("FreiHandDeviceCache: open_2dj and open_2dj_con come together")
+        self.open_2dj = self.open_2dj_con = None
+        if open_2dj is not None:
+            self.open_2dj, self.open_2dj_con = f32(open_2dj).contiguous(), f32(open_2dj_con).contiguous()
+            if tuple(self.open_2dj.shape) != (n, 21, 2) or tuple(self.open_2dj_con.shape) not in ((n, 21), (n, 21, 1)):
+                raise ValueError(f"FreiHandDeviceCache: open_2dj must be [{n},21,2] and open_2dj_con [{n},21] or [{n},21,1], got "
+                                 f"{tuple(self.open_2dj.shape)} and {tuple(self.open_2dj_con.shape)}")
+        self.semi_ratio = semi_ratio
 
     _RING = 32         # pinned staging slots (the device reads a slot when it gets to it, possibly many host steps later)
     _GROUP = 8         # ... released in groups: ONE event per _GROUP steps (an event record is a barrier packet between the batch kernels and the step)
@@ -140,17 +157,28 @@ class FreiHandDeviceCache:
         t = torch.empty(nwords, dtype=torch.int32)
         return t.pin_memory() if self.device.type == "cuda" else t
 
-    def _packed_terms(self, idxs, rots, generator, direct=False):
+    def _packed_terms(self, idxs, rots, generator, direct=False, keypoints=False):
         """Host side of one batch: affine coefficients (numpy, stacked) packed with the indices and the two 3x3 matrices per sample
         into ONE pinned staging buffer that goes over in ONE asynchronous copy.  -> (B, packed int32 [25 B] on the device, slot);
-        direct=True: the pinned buffer itself (see below)."""
+        direct=True: the pinned buffer itself (see below).  keypoints=True: the float32 forward affines of the warp, [B,3,3], go over as
+        well, in a staging buffer of their own that shares the slot's turn (self._total_d; the 25-word layout is unchanged)."""
         idxs = torch.as_tensor(idxs, dtype=torch.int64)
         B = idxs.shape[0]
         if rots is None:                       # np.random.uniform(-max_rot, max_rot) per sample (data/dataset.py:237)
             rots = (2 * torch.rand(B, generator=generator, dtype=torch.float64) - 1) * self.max_rot
         rots = np.asarray(rots, dtype=np.float64)
-        fixed, post, rmat = batch_affine_terms(np.asarray([self.W // 2, self.H // 2]), self.H, [self.H, self.W], rots)
+        fixed, post, rmat, total = batch_affine_terms(np.asarray([self.W // 2, self.H // 2]), self.H, [self.H, self.W], rots, with_total=True)
         slot, host = self._stage(25 * B)
+        if keypoints:
+            if not hasattr(self, "_total_slots"):
+                self._total_slots = [None] * self._RING
+            if self._total_slots[slot] is None or self._total_slots[slot].numel() < 9 * B:
+                t = torch.empty(9 * B, dtype=torch.float32)
+                self._total_slots[slot] = t.pin_memory() if self.device.type == "cuda" else t
+            th = self._total_slots[slot][:9 * B]
+            th.numpy()[:] = total.reshape(-1)
+            self._total_d = torch.empty(B, 3, 3, dtype=torch.float32, device=self.device)
+            self._total_d.view(-1).copy_(th, non_blocking=True)          # (before the slot's release below: one event covers both buffers)
         hv = host.numpy()
         hv[:B] = idxs.numpy().astype(np.int32)
         hv[B:7 * B] = fixed.reshape(-1)
@@ -176,6 +204,8 @@ class FreiHandDeviceCache:
 
     EXAMPLE_KEYS = ("imgs", "masks", "segms_gt", "Ks", "Ps", "joints", "verts", "j2d_gt", "scales", "idxs")
 
+    KEYPOINT_KEYS = ("open_2dj", "open_2dj_con", "texture_con")           # only from a cache that was given detections
+
     STEP_KEYS = ("root_xyz", "joints_rel", "verts_rel", "cam_ndc")      # what a training iteration derives from the batch (root_id given)
 
     def batch_examples(self, idxs, rots=None, generator=None, out=None, root_id=None):
@@ -186,8 +216,13 @@ class FreiHandDeviceCache:
         out: a dict holding tensors for EXAMPLE_KEYS (the static inputs of traineval.GraphedTrainStep) to be written in place.
         root_id (= args.ROOT): the same two launches also emit STEP_KEYS -- root_xyz [B,1,3] = joints[:, root_id], joints_rel / verts_rel
         (train_hrnet.py:62-68) and cam_ndc [B,4] (models_res_nimble.py:184-186,228-235) -- which traineval.forward_backward and
-        Model.forward pick up instead of four elementwise launches per step."""
-        B, packed, slot = self._packed_terms(idxs, rots, generator, direct=_DIRECT_PARAMS and self.device.type == "cuda")
+        Model.forward pick up instead of four elementwise launches per step.
+        A cache that holds detections also returns KEYPOINT_KEYS -- open_2dj [B,21,2] warped like the image, open_2dj_con (the cache's
+        shape per sample), texture_con [B], with the semi-supervised mix when semi_ratio was given -- from ONE more launch
+        (hifihr_freihand_keypoints) and one more staged copy of 36 bytes per sample."""
+        kp = self.open_2dj is not None
+        B, packed, slot = self._packed_terms(idxs, rots, generator, direct=_DIRECT_PARAMS and self.device.type == "cuda", keypoints=kp)
+        kp_shapes = {"open_2dj": (B, 21, 2), "open_2dj_con": (B,) + tuple(self.open_2dj_con.shape[1:]), "texture_con": (B,)} if kp else {}
         dev, J, V = self.device, self.joints.shape[1], self.verts.shape[1]
         if out is None:
             f = lambda *shape: torch.empty(*shape, device=dev)
@@ -197,6 +232,7 @@ class FreiHandDeviceCache:
                    "idxs": torch.empty(B, dtype=torch.int64, device=dev)}
             if root_id is not None:
                 out.update({"root_xyz": f(B, 1, 3), "joints_rel": f(B, J, 3), "verts_rel": f(B, V, 3), "cam_ndc": f(B, 4)})
+            out.update({k: f(*shape) for k, shape in kp_shapes.items()})
         else:
             expect = {"imgs": (B, 3, self.H, self.W), "masks": (B, 3, self.H, self.W), "segms_gt": (B, self.H, self.W), "Ks": (B, 3, 3),
                       "Ps": (B, 3, 4), "joints": (B, J, 3), "verts": (B, V, 3), "j2d_gt": (B, J, 2), "scales": (B,), "idxs": (B,)}
@@ -207,6 +243,7 @@ class FreiHandDeviceCache:
                     if root_id is None:
                         raise ValueError("batch_examples(out=...): `out` holds the step terms (root_xyz, joints_rel, ...) but no root_id was "
                                          "given here or in an earlier call")
+            expect.update(kp_shapes)
             for k, shape in expect.items():
                 if k not in out or tuple(out[k].shape) != shape:
                     raise ValueError(f"batch_examples(out=...): '{k}' must be a tensor of shape {shape}")
@@ -215,6 +252,11 @@ class FreiHandDeviceCache:
             self._root_id = root_id                              # (a later in-place call on the same dict keeps the step terms current)
         self.lib.freihand_batch(self.images, self.masks, self.Ks, self.joints, self.verts, self.scales, packed, B, out,
                                 root_id=root_id, image_size=self.H)
+        if kp:
+            from .traineval import semi_below
+            below = semi_below(self.semi_ratio)
+            self.lib.freihand_keypoints(self.open_2dj, self.open_2dj_con, packed[:B], self._total_d, out["j2d_gt"] if below else None, below,
+                                        out["open_2dj"], out["open_2dj_con"], out["texture_con"])
         self._release(slot)
         return out
 

@@ -8,7 +8,8 @@ reference's uniform-Laplacian term and, not in the reference, its usual partner)
 unwired ChamferLoss): one kernel pair (csrc/chamfer.hip).  point_mesh (not in the
 reference: the distance of the target points to the SURFACE of the predicted mesh): one kernel pair (csrc/point_mesh.hip).  depth (declared and
 never computed in the reference: the mean |rendered depth - depth image| on the model's opt-in depth map, outputs['re_depth']): one kernel pair
-(csrc/depth.hip).  sil_soft / iou_soft (not in the
+(csrc/depth.hip).  open_2dj / open_bone_direc / open_2dj_de (the self-supervised keypoint terms of the reference's deprecated loss_func, which
+its configs still name): one kernel pair (csrc/losses.hip open2d_terms_*).  sil_soft / iou_soft (not in the
 reference: `sil` and `iou` on the model's opt-in differentiable silhouette, outputs['re_sil_soft']): one kernel pair (csrc/soft_sil.hip).  lpips (not in the
 reference: LPIPS(alex), the evaluation pass's texture metric, as an opt-in loss): hifihr_amd/lpips.py with its HIP backward (csrc/lpips.hip).  The rarely used terms (mscale, scale,
 iou, mtex and the self-supervised `*_self` terms) are a handful of torch ops on the same GPU tensors.  The torch restatement of the whole function that the tests
@@ -29,7 +30,7 @@ _BONES = [(0, 1), (1, 2), (2, 3), (3, 4), (0, 5), (5, 6), (6, 7), (7, 8), (0, 9)
 # every name LossFunction.__call__ can produce (a name outside it in `losses` is ignored here and stops traineval's step with a KeyError)
 TERMS = ("joint_3d", "vert_3d", "edge_length", "mshape", "mpose", "joint_2d", "bone_direc", "bone_direc_3d", "mscale", "scale", "texture",
          "mrgb", "ssim_tex", "sil", "texture_self", "mrgb_self", "ssim_tex_self", "perceptual", "iou", "sil_soft", "iou_soft", "triangle",
-         "normal_consistency", "lpips", "chamfer", "point_mesh", "depth", "mtex")
+         "normal_consistency", "lpips", "chamfer", "point_mesh", "depth", "mtex", "open_2dj", "open_bone_direc", "open_2dj_de")
 
 _BONE_IDX = {}
 
@@ -137,7 +138,8 @@ class LossFunction:
         """sum(loss_dic[k] for k in losses) (reference train_hrnet.py:98-104) -- in ONE launch when the requested terms are exactly the
         ones the fused kernels of the last __call__ hold in their output vectors, else as a stack + sum."""
         from . import ops
-        parts = getattr(self, "_total_parts", [])
+        # (a vector none of whose terms is requested -- the photometric block of a rendering model under a keypoint-only list -- is left out)
+        parts = [p for p in getattr(self, "_total_parts", []) if any(k in losses for k in p[2])]
         covered = [k for _, _, names in parts for k in names]
         if (parts and len(parts) <= 4 and sorted(covered) == sorted(losses) and all(p.is_cuda for p, _, _ in parts)
                 and all(loss_dic.get(k) is not None for k in losses)):
@@ -163,6 +165,24 @@ class LossFunction:
             for k, w, v in zip(("joint_2d", "bone_direc", "bone_direc_3d"), want, vals):
                 if w:
                     loss_dic[k] = v
+        if any(k in loss_used for k in ops.OPEN2D_TERMS):
+            # the self-supervised keypoint terms (the reference's deprecated loss_func, losses.py:45-63, 79-85: its LossFunction class
+            # dropped them while its self_superv_* configs still name them): the projected joints against off-the-shelf 2-D detections
+            # weighted by the detector's confidences, one kernel pair (csrc/losses.hip open2d_terms_*); a term that is not requested has
+            # weight 0.  include/hifihr.h states the two decided corners (d = 0; a batch whose confidences are all 0)
+            assert "open_2dj" in examples and "open_2dj_con" in examples and "j2d" in outputs, (
+                "the loss terms 'open_2dj' / 'open_bone_direc' / 'open_2dj_de' need examples['open_2dj'] and examples['open_2dj_con'] (2-D "
+                "detections and their confidences: data_dic passes them through, FreiHandDeviceCache(open_2dj=..., open_2dj_con=...) "
+                "produces them) and outputs['j2d'] (traineval's step projects it when one of the names is in args.losses)")
+            names = [k for k in ops.OPEN2D_TERMS if k in loss_used]
+            vec = ops.open2d_terms(outputs["j2d"], examples["open_2dj"], examples["open_2dj_con"],
+                                   (args.lambda_j2d if "open_2dj" in loss_used else 0.0,
+                                    args.lambda_bone_direc if "open_bone_direc" in loss_used else 0.0,
+                                    args.lambda_j2d_de if "open_2dj_de" in loss_used else 0.0))
+            for k, v in zip(ops.OPEN2D_TERMS, vec.unbind(0)):
+                if k in loss_used:
+                    loss_dic[k] = v
+            self._total_parts.append((vec, 3, names))
         if "mscale" in loss_used:
             bl = torch.sqrt(torch.sum((outputs["joints"][:, 9] - outputs["joints"][:, 10]) ** 2, 1))
             loss_dic["mscale"] = args.lambda_mscale * F.l1_loss(bl, torch.ones_like(bl) * 0.0282)

@@ -2132,6 +2132,39 @@ def joint_terms(j2d, j2d_gt, joints, joints_gt, mse, lam3):
     return _JointTerms.apply(j2d, j2d_gt, joints, joints_gt, bool(mse), tuple(float(v) for v in lam3))
 
 
+OPEN2D_TERMS = ("open_2dj", "open_bone_direc", "open_2dj_de")
+
+
+class _Open2dTerms(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, j2d, open_2dj, open_2dj_con, lam3):
+        lib = get_lib()
+        j2d, open_2dj, open_2dj_con = j2d.contiguous().float(), open_2dj.contiguous().float(), open_2dj_con.contiguous().float()
+        require_cuda(j2d, open_2dj, open_2dj_con)
+        out = torch.empty(3, device=j2d.device)
+        PROFILE.bracket("open2d_terms_fwd", lambda: lib.open2d_terms_fwd(j2d, open_2dj, open_2dj_con, lam3, out))
+        ctx.save_for_backward(j2d, open_2dj, open_2dj_con)
+        ctx.lam3 = lam3
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        j2d, open_2dj, open_2dj_con = ctx.saved_tensors
+        g = None
+        if ctx.needs_input_grad[0]:
+            g = torch.empty_like(j2d)
+            PROFILE.bracket("open2d_terms_bwd", lambda: get_lib().open2d_terms_bwd(j2d, open_2dj, open_2dj_con, ctx.lam3, gout.contiguous(), g))
+        return g, None, None, None
+
+
+def open2d_terms(j2d, open_2dj, open_2dj_con, lam3):
+    """[3] = lambda-weighted (open_2dj, open_bone_direc, open_2dj_de), the self-supervised keypoint terms of the reference's deprecated
+    loss_func (losses.py:45-63, 79-85), in one launch each way (csrc/losses.hip open2d_terms_*; include/hifihr.h states the two decided
+    corners).  j2d / open_2dj [B,21,2] in pixels, open_2dj_con [B,21] or [B,21,1]; lam3 = (lambda_j2d, lambda_bone_direc, lambda_j2d_de),
+    0 = unused.  The gradient goes to j2d only."""
+    return _Open2dTerms.apply(j2d, open_2dj, open_2dj_con, tuple(float(v) for v in lam3))
+
+
 class _PhotoLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgba, imgs, seg, l_tex, l_mrgb, l_sil):

@@ -47,6 +47,10 @@ _DEFAULTS = dict(
     render_depth=False, lambda_depth=1.0, depth_trunc=0.0,
     depth_metric=False,   # the evaluation pass also reports depth_mae (hifihr_amd/evaluate.py Evaluator(depth=True)); needs render_depth and batches with 'depths'
     point_mesh_metric=False,   # the evaluation pass also reports mesh_p2s / mesh_al_p2s (hifihr_amd/evaluate.py Evaluator(point_mesh=True))
+    # weights of the self-supervised keypoint terms "open_2dj" and "open_2dj_de" (hifihr_amd/ops.py open2d_terms; "open_bone_direc" reads
+    # lambda_bone_direc above): the reference's argparse defaults (options/train_options.py:108, 112), untuned here.  semi_ratio above: the share
+    # of the training set whose detections data_dic / FreiHandDeviceCache replace with the ground-truth projection
+    lambda_j2d=1e-3, lambda_j2d_de=1e-4,
     chamfer_metric=False,    # the evaluation pass also reports mesh_chamfer / mesh_al_chamfer (hifihr_amd/evaluate.py Evaluator(chamfer=True))
 )
 

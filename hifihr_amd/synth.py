@@ -13,10 +13,15 @@ from . import ops
 
 @torch.no_grad()
 def make_batch(mano_handle: ops.ManoLayerHandle, renderer: ops.RendererHandle, B: int, first_index: int = 0,
-               device="cuda", image_size=224, images="noise", depth=False):
+               device="cuda", image_size=224, images="noise", depth=False, open_2dj=False):
     """Deterministic in (first_index, B): sample i uses seed 1234 + first_index + i.
     depth: the batch also carries "depths" f32[224,224] per sample, the depth map of the ground-truth mesh (ops.render_depth on the mask
     render's face_id; 0 where the hand covers nothing), the target of the loss term "depth".  Without it the batch is unchanged.
+    open_2dj: the batch also carries seeded stand-ins for an off-the-shelf 2-D detector, the inputs of the self-supervised terms:
+    "trans_open_2dj" f32[21,2] = the projected ground-truth joints + Gaussian noise of 2 px, and "open_2dj_con" f32[21,1] in [0, 1].  About
+    one joint in ten has confidence exactly 0 (a missed joint); they fall on "occluded" samples (every fourth, 4 in 10 of its joints), every other
+    sample keeps all its confidences above 0.1 -- except the first of the batch, which gets one joint below 0.1 (and above 0) so that
+    texture_con's gate (min_j con > 0.1) closes on it.  Without it the batch is unchanged.
     images: "noise" (uniform noise, unrelated to the pose: timing / parity inputs) or "render" (the posed hand, lit, over dim noise:
     an image the pose can be read from, for training runs that are expected to learn)."""
     rows = []
@@ -76,6 +81,21 @@ def make_batch(mano_handle: ops.ManoLayerHandle, renderer: ops.RendererHandle, B
     }
     if depth:
         batch["depths"] = ops.render_depth(renderer, verts_w.contiguous(), cam, face_id)[0][:, 0].cpu()
+    if open_2dj:
+        from .traineval import proj_func
+        det, con = proj_func(batch["trans_joints"], batch["trans_Ks"]).clone(), torch.empty(B, 21, 1)
+        for i in range(B):
+            gk = torch.Generator().manual_seed(977 * (1234 + first_index + i) + 5)        # a stream of its own: the draws above are untouched
+            det[i] += 2.0 * torch.randn(21, 2, generator=gk)
+            con[i, :, 0] = 0.15 + 0.85 * torch.rand(21, generator=gk)
+            occluded = (first_index + i) % 4 == 3
+            missed = torch.rand(21, generator=gk) < 0.4
+            weak, level = int(torch.randint(0, 21, (1,), generator=gk)), 0.09 * float(torch.rand(1, generator=gk)) + 0.005
+            if i == 0:
+                con[i, weak, 0] = level
+            elif occluded:
+                con[i, missed, 0] = 0.0
+        batch["trans_open_2dj"], batch["open_2dj_con"] = det, con
     return batch
 
 

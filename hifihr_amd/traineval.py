@@ -45,6 +45,30 @@ def RHD2Frei(rhd_joints):
     return rhd_joints[:, _RHD_TO_FREI]
 
 
+# the loss terms that read outputs["j2d"], the projection of the predicted joints (the step computes it only for them)
+_J2D_TERMS = ("joint_2d", "bone_direc", "open_2dj", "open_bone_direc", "open_2dj_de")
+
+FREIHAND_TRAIN_SIZE = 32560        # samples of the FreiHAND training set: indices from here on are its augmented copies
+
+
+def _per_sample(flag, like):
+    """A [B] flag shaped to select whole samples of `like` ([B,21], [B,21,1] or [B,21,2])."""
+    return flag.view(-1, *([1] * (like.dim() - 1)))
+
+
+def texture_con_freihand(open_2dj_con, idxs):
+    """utils/traineval_util.py:60-64: mean_j([min_j con > 0.1] con_j) ([idx < 32560] + 0.1) -> [B]."""
+    con = open_2dj_con.reshape(open_2dj_con.shape[0], -1)
+    gate = (torch.min(con, 1)[0] > 0.1).to(con.dtype).unsqueeze(1)
+    return torch.mean(gate * con, 1) * ((idxs < FREIHAND_TRAIN_SIZE).to(con.dtype) + 0.1)
+
+
+def semi_below(semi_ratio):
+    """The integer bound of utils/traineval_util.py:107-108: `raw_idx < 32560 * semi_ratio` among integers is `raw_idx < ceil(...)`."""
+    import math
+    return 0 if semi_ratio is None else max(0, math.ceil(FREIHAND_TRAIN_SIZE * float(semi_ratio)))
+
+
 def data_dic(sample, dat_name, set_name, args, device="cuda", image_size=224):
     """utils/traineval_util.py:21-111 (FreiHand branch; training queries [trans_images, trans_Ks, trans_joints, scales,
     trans_verts, trans_masks], evaluation queries without the prefix) and :156-201 (HO3D branch: crop resized to 224 with
@@ -63,6 +87,12 @@ def data_dic(sample, dat_name, set_name, args, device="cuda", image_size=224):
         joints, verts, masks = g("joints"), g("verts"), g("masks")
         if sample.get("depths") is not None:          # a depth image per sample [B, H, W] in the vertices' unit (0 = no measurement): the term "depth"
             ex["depths"] = to(sample["depths"].float())
+        if "open_2dj" in sample or "trans_open_2dj" in sample:
+            # off-the-shelf 2-D detections for the self-supervised terms (utils/traineval_util.py:55-66): the warped ones when the loader made
+            # them; texture_con, the per-sample confidence of the `*_self` photometric terms, from the confidences as they arrive
+            ex["open_2dj"] = to(sample["trans_open_2dj"] if "trans_open_2dj" in sample else sample["open_2dj"]).float()
+            ex["open_2dj_con"] = to(sample["open_2dj_con"]).float()
+            ex["texture_con"] = texture_con_freihand(ex["open_2dj_con"], ex["idxs"])
     elif dat_name == "HO3D":
         # the reference resizes the crop to 224 (its render resolution is hard-wired to 224); `image_size` is the build-side
         # render resolution of BASELINE configs[4] (512): the photometric terms then run at that size, the encoder reads a 224 resize
@@ -78,6 +108,10 @@ def data_dic(sample, dat_name, set_name, args, device="cuda", image_size=224):
         if sample.get("depth_crop") is not None:      # the reference loader's key; nearest-neighbour like the mask (a depth image is not averaged)
             d = to(sample["depth_crop"].float())
             ex["depths"] = d if d.shape[-1] == image_size else F.interpolate(d.unsqueeze(1), (image_size, image_size))[:, 0]
+        if "open_2dj_crop" in sample:                 # utils/traineval_util.py:187-193 (the detector's joint order is FreiHAND's)
+            ex["open_2dj"] = to(sample["open_2dj_crop"].float())
+            ex["open_2dj_con"] = to(sample["open_2dj_con"]).float()
+            ex["texture_con"] = torch.mean(ex["open_2dj_con"].reshape(ex["open_2dj_con"].shape[0], -1), 1)
         if masks is not None and masks.shape[-1] != image_size:             # the loader's 224 crop at a build-side render resolution
             masks = F.interpolate(to(masks), (image_size, image_size))
     elif dat_name == "RHD":
@@ -104,6 +138,12 @@ def data_dic(sample, dat_name, set_name, args, device="cuda", image_size=224):
         ex["joints"] = to(joints)
         if dat_name == "FreiHand":                 # (the RHD branch's projected 2-D joints are commented out in the reference, :239)
             ex["j2d_gt"] = proj_func(ex["joints"], Ks)
+            if getattr(args, "semi_ratio", None) is not None and training and "open_2dj" in ex:
+                # utils/traineval_util.py:106-111: the first semi_ratio of the training set is supervised -- its detections become the
+                # projected ground truth, its confidences 1 (texture_con above keeps the detector's confidences, as there)
+                sup = (ex["idxs"] % FREIHAND_TRAIN_SIZE) < semi_below(args.semi_ratio)
+                ex["open_2dj"] = torch.where(_per_sample(sup, ex["open_2dj"]), ex["j2d_gt"], ex["open_2dj"])
+                ex["open_2dj_con"] = torch.where(_per_sample(sup, ex["open_2dj_con"]), torch.ones_like(ex["open_2dj_con"]), ex["open_2dj_con"])
     if verts is not None:
         ex["verts"] = to(verts)
     if masks is not None:
@@ -172,7 +212,7 @@ def _forward_backward(model, loss_func, optimizer, examples, args, dat_name):
         ex["joints"] = examples["joints"] - root_xyz
         if "verts" in examples:
             ex["verts"] = examples["verts"] - root_xyz
-    if any(k in args.losses for k in ("joint_2d", "bone_direc")):
+    if any(k in args.losses for k in _J2D_TERMS):
         outputs["j2d"] = trans_proj_j2d(outputs, examples["Ks"], root_xyz=root_xyz)      # only these terms read it
     loss_dic = loss_func(ex, outputs, args.losses, dat_name, args)
     missing = [k for k in args.losses if k not in loss_dic]
@@ -465,7 +505,7 @@ def _forward_only(model, loss_func, optimizer, examples, args, dat_name, root_xy
         ex["joints"] = examples["joints"] - root_xyz
         if "verts" in examples:
             ex["verts"] = examples["verts"] - root_xyz
-    if any(k in args.losses for k in ("joint_2d", "bone_direc")):
+    if any(k in args.losses for k in _J2D_TERMS):
         outputs["j2d"] = trans_proj_j2d(outputs, examples["Ks"], root_xyz=root_xyz)
     loss_dic = loss_func(ex, outputs, args.losses, dat_name, args)
     missing = [k for k in args.losses if k not in loss_dic]

@@ -1185,6 +1185,28 @@ int hifihr_joint_terms_fwd(const float* j2d_d, const float* j2d_gt_d, const floa
                            const float* lam3_host, float* out3_d, void* stream);
 int hifihr_joint_terms_bwd(const float* j2d_d, const float* j2d_gt_d, const float* joints_d, const float* joints_gt_d, int B, int J, int mse,
                            const float* lam3_host, const float* gout3_d, float* g_j2d_d, float* g_joints_d, void* stream);
+/* open_2dj, open_bone_direc, open_2dj_de: the self-supervised keypoint terms of the reference's deprecated loss_func (losses.py:45-63,
+ * 79-85; bone_direction_loss of utils/losses_util.py:217-283 WITH the detector's confidences) in ONE launch per direction.
+ * j2d / open_2dj [B][21][2] in pixels, open_2dj_con [B][21] (or [B][21][1]: the same memory), lam3_host = (lambda_j2d, lambda_bone_direc,
+ * lambda_j2d_de) in host memory (0 = the term is not requested).  out3_d:
+ *   out[0] = lam0 sum_bj rho(d_bj) (c_bj w_j)^2 / sum_bj (c_bj w_j)^2 with d = |j2d - open_2dj|, rho(d) = d^2 / 10 for d < 5, d - 2.5
+ *            otherwise, w = (2, 1, 1, 1, 1.5, 1, 1, 1, 1.5, 1, 1, 1, 1.5, 1, 1, 1, 1.5, 1, 1, 1, 1.5); both sums run over the whole batch
+ *   out[1] = lam1 mean over the B x 20 bones of |vn - von|^2 c_parent c_child, unit bone vectors v / (|v| + 1e-4)
+ *   out[2] = lam2 mean (open_2dj - j2d)^2 (always MSE, as in the reference)
+ * bwd: g_j2d_d [B][21][2] = gradient of sum_k gout3_d[k] out3[k] (overwritten).  No gradient goes to the detections or the confidences.
+ * Decided corners:
+ *   - d = 0: the gradient of rho is (j2d - open_2dj) / 5 for d < 5, so exactly 0 there (autograd of the reference: sqrt'(0) x 0 = NaN);
+ *     value and slope of rho agree at d = 5, so the branch taken at the boundary does not matter.  Coincident joints (|v| = 0): as for
+ *     the bone terms of joint_terms above.
+ *   - a batch whose weights (c w)^2 sum to 0: out[0] = 0 and its gradient is 0, exactly.  A DELIBERATE departure: the reference computes
+ *     0 / 0 = NaN there.  (out[1] is 0 as well: every bone's confidence is 0.)
+ * Both directions are deterministic (one workgroup forward with a fixed summation order; one thread per sample backward, no atomics):
+ * the same bits on a second call.  Nothing is allocated or synchronised.
+ * Refused (HIFIHR_EINVAL, nothing launched or written): J != 21, B <= 0, a NULL pointer. */
+int hifihr_open2d_terms_fwd(const float* j2d_d, const float* open_2dj_d, const float* open_2dj_con_d, int B, int J, const float* lam3_host,
+                            float* out3_d, void* stream);
+int hifihr_open2d_terms_bwd(const float* j2d_d, const float* open_2dj_d, const float* open_2dj_con_d, int B, int J, const float* lam3_host,
+                            const float* gout3_d, float* g_j2d_d, void* stream);
 int hifihr_geom_loss_bwd(const float* joints_d, const float* joints_gt_d, const float* verts_d, const float* verts_gt_d,
                          const float* shape_d, const float* pose_d, const int32_t* faces_d, const int32_t* vf_off_d,
                          const int32_t* vf_idx_d, int B, int J, int V, int F, int NS, int NP, int mse, const float* lambda5_h,
@@ -1382,6 +1404,24 @@ int hifihr_freihand_batch_step(const uint32_t* img_rgbx_d, const uint8_t* mask_d
                                float* out_joints_d, float* out_verts_d, float* out_j2d_d, float* out_scales_d, long long* out_idxs_d,
                                int root_id, float image_size, float* out_root_d, float* out_joints_rel_d, float* out_verts_rel_d,
                                float* out_cam_ndc_d, void* stream);
+/* The 2-D detections of the same batch, for the self-supervised keypoint terms (hifihr_open2d_terms_*) and the `*_self` photometric
+ * terms: ONE more launch behind hifihr_freihand_batch (reference data/dataset.py:196-201, 255-257; utils/traineval_util.py:55-66, 106-111).
+ * Cache (device): open_2dj_d[n][21][2] in pixels of the stored image, open_2dj_con_d[n][21].  idx_d[B] (the first B words of packed_d),
+ * total_d[B][3][3]: the float32 forward affine of each sample's image warp (hifihr_amd.data.batch_affine_terms).  Outputs, any may be NULL
+ * but not all:
+ *   out_open_2dj_d[B][21][2] = total . (x, y, 1), each coordinate as fmaf(t0, x, fmaf(t1, y, t2)): handutils.transform_coords WITHOUT its
+ *                              final truncation to integers (a deliberate departure: the sub-pixel position is kept)
+ *   out_con_d[B][21]         = the cached confidences, bit for bit
+ *   out_texture_con_d[B]     = mean_j([min_j con > 0.1] con_j) x ([idx < 32560] + 0.1), summed in joint order, from the confidences
+ *                              BEFORE the mix below
+ * semi_below > 0 (= ceil(32560 semi_ratio); needs j2d_gt_d[B][21][2], the batch's own out_j2d): a sample with idx % 32560 < semi_below
+ * takes j2d_gt for its detections and 1 for its confidences.  0: no mix.
+ * An index outside 0 .. n - 1 gives that sample zeros (the indices live in device memory: the entry cannot refuse them).
+ * Refused (HIFIHR_EINVAL, nothing launched or written): n / B <= 0, semi_below < 0, semi_below > 0 without j2d_gt_d, NULL open_2dj_d /
+ * open_2dj_con_d / idx_d / total_d, every output NULL. */
+int hifihr_freihand_keypoints(const float* open_2dj_d, const float* open_2dj_con_d, int n, const int* idx_d, const float* total_d,
+                              const float* j2d_gt_d, int semi_below, int B, float* out_open_2dj_d, float* out_con_d,
+                              float* out_texture_con_d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * HO-3D training sample assembly (the HO-3D half): the hand crop of reference data/dataset.py:1105-1215.

@@ -43,6 +43,11 @@ def parse(argv=None):
                     "without it the evaluation pass runs on the training frames with boxes / roots derived from their joints")
     ap.add_argument("--ho3d_cache", default=None, help="npz: images u8 [n,480,640,3], hand_masks u8 [n,480,640], Ks [n,3,3] (camMat . cam_extr), "
                                                        "xyz21 [n,21,3]; default: seeded synthetic frames")
+    ap.add_argument("--openpose_keypoints", default=None, metavar="JSON",
+                    help="2-D detections for the self-supervised terms 'open_2dj' / 'open_bone_direc' / 'open_2dj_de' and the `*_self` photometric "
+                         "terms, in the reference's layout (data/dataset.py:1430-1432): [keypoints [n][21][2], confidences [n][21] or [n][21][1]], "
+                         "in pixels of the cached images, one row per training sample.  The --freihand_cache npz may carry them itself as "
+                         "open_2dj / open_2dj_con; the synthetic set makes seeded ones when a requested loss needs them")
     ap.add_argument("--synthetic_size", type=int, default=512)
     ap.add_argument("--mano_pkl", default=None, help="MANO_RIGHT.pkl (licensed, user supplied); default: synthetic MANO-shaped tables")
     ap.add_argument("--nimble_layer", choices=["mano-stand-in", "synthetic", "synthetic-uv"], default="mano-stand-in",
@@ -100,6 +105,27 @@ def attach_mesh_depths(ex, model, static=None):
     return ex
 
 
+KEYPOINT_LOSSES = ("open_2dj", "open_bone_direc", "open_2dj_de", "texture_self", "mrgb_self", "ssim_tex_self")
+
+
+def wants_keypoints(args):
+    """A requested loss reads the 2-D detections or the texture_con made from their confidences."""
+    return any(k in args.losses for k in KEYPOINT_LOSSES)
+
+
+def load_openpose_keypoints(path, n):
+    """The reference's detection file (data/dataset.py:1430-1432: json [keypoints, confidences]) -> (open_2dj f32 [n,21,2], open_2dj_con f32
+    [n,21,1]) for the first n samples."""
+    with open(path) as fh:
+        both = json.load(fh)
+    if not (isinstance(both, list) and len(both) == 2):
+        raise ValueError(f"{path}: expected the list [keypoints, confidences]")
+    det, con = np.asarray(both[0], dtype=np.float32), np.asarray(both[1], dtype=np.float32)
+    if det.ndim != 3 or det.shape[1:] != (21, 2) or det.shape[0] < n or con.shape[0] != det.shape[0] or con.size != det.shape[0] * 21:
+        raise ValueError(f"{path}: keypoints {det.shape} / confidences {con.shape} do not cover {n} samples of 21 joints")
+    return det[:n], con.reshape(-1, 21, 1)[:n]
+
+
 def optimizer_max_grad_norm(args):
     """FusedAdam's max_grad_norm from the options: 0 (or a missing key) is off."""
     x = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
@@ -148,12 +174,18 @@ def build_args(cli):
     return args
 
 
-def load_or_make_dataset(cli, model, device):
-    """-> (train arrays, eval arrays) as dicts of numpy arrays: images u8 [n,H,W,3], masks u8 [n,H,W], Ks, joints, verts."""
+def load_or_make_dataset(cli, model, device, keypoints=False):
+    """-> (train arrays, eval arrays) as dicts of numpy arrays: images u8 [n,H,W,3], masks u8 [n,H,W], Ks, joints, verts.  The training
+    arrays also hold open_2dj [n,21,2] / open_2dj_con when the npz or --openpose_keypoints carries them, or -- synthetic set, keypoints=True --
+    seeded ones (synth.make_batch(open_2dj=True))."""
     if cli.freihand_cache:
         z = np.load(cli.freihand_cache)
         tr = {k: z[k] for k in ("images", "masks", "Ks", "joints", "verts")}
         ev = {k: z["eval_" + k] for k in tr} if "eval_images" in z else None
+        if "open_2dj" in z and "open_2dj_con" in z:
+            tr["open_2dj"], tr["open_2dj_con"] = z["open_2dj"], z["open_2dj_con"]
+        if getattr(cli, "openpose_keypoints", None):
+            tr["open_2dj"], tr["open_2dj_con"] = load_openpose_keypoints(cli.openpose_keypoints, len(tr["images"]))
         return tr, ev
     from hifihr_amd import synth
     parts, n = [], cli.synthetic_size + 64
@@ -165,13 +197,17 @@ def load_or_make_dataset(cli, model, device):
     else:
         mano, rend = model.hand_layer.handle, model.renderer_p3d
     for first in range(0, n, 64):
-        s = synth.make_batch(mano, rend, min(64, n - first), first_index=first, device=device, images="render")
+        s = synth.make_batch(mano, rend, min(64, n - first), first_index=first, device=device, images="render", open_2dj=keypoints)
         parts.append({"images": (s["trans_images"].permute(0, 2, 3, 1) * 255).round().to(torch.uint8).numpy(),
                       "masks": (s["trans_masks"][:, 0] * 255).to(torch.uint8).numpy(), "Ks": s["trans_Ks"].numpy(),
                       "joints": s["trans_joints"].numpy(), "verts": s["trans_verts"].numpy()})
+        if keypoints:
+            parts[-1].update(open_2dj=s["trans_open_2dj"].numpy(), open_2dj_con=s["open_2dj_con"].numpy())
     full = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
     cut = cli.synthetic_size
-    return {k: v[:cut] for k, v in full.items()}, {k: v[cut:] for k, v in full.items()}
+    if getattr(cli, "openpose_keypoints", None):
+        full["open_2dj"], full["open_2dj_con"] = load_openpose_keypoints(cli.openpose_keypoints, len(full["images"]))
+    return {k: v[:cut] for k, v in full.items()}, {k: v[cut:] for k, v in full.items() if not k.startswith("open_2dj")}
 
 
 def train_ho3d(cli, args, model, loss_func, opt, sched, reducer, current_epoch, rank, world, device, say):
@@ -420,9 +456,13 @@ def main(argv=None):
     dat_name = cli.dataset
     if dat_name == "HO3D":
         return train_ho3d(cli, args, model, loss_func, opt, sched, reducer, current_epoch, rank, world, device, say)
-    train_arrays, eval_arrays = load_or_make_dataset(cli, model, device)
+    train_arrays, eval_arrays = load_or_make_dataset(cli, model, device, keypoints=wants_keypoints(args))
+    if wants_keypoints(args) and "open_2dj" not in train_arrays:
+        raise SystemExit(f"[train_hrnet] the losses {[k for k in args.losses if k in KEYPOINT_LOSSES]} need 2-D detections: give "
+                         "--openpose_keypoints <json>, or open_2dj / open_2dj_con in the --freihand_cache npz")
     cache = FreiHandDeviceCache(train_arrays["images"], train_arrays["masks"], train_arrays["Ks"], train_arrays["joints"],
-                                train_arrays["verts"], device=device)
+                                train_arrays["verts"], device=device, open_2dj=train_arrays.get("open_2dj"),
+                                open_2dj_con=train_arrays.get("open_2dj_con"), semi_ratio=getattr(args, "semi_ratio", None))
     eval_cache = None
     if eval_arrays is not None and len(eval_arrays["images"]):
         eval_cache = FreiHandDeviceCache(eval_arrays["images"], eval_arrays["masks"], eval_arrays["Ks"], eval_arrays["joints"],
