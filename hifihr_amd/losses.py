@@ -1,36 +1,26 @@
 """`LossFunction` with the reference's call signature, loss names and formulas
 (reference losses.py:226-453; helpers utils/losses_util.py:217-301,366-378; utils/pytorch_ssim:17-37).
 
-ONE path: the step's terms run as fused HIP kernels -- SSIM (csrc/ssim.hip), the photometric block and the joint / vertex /
-edge-length / shape / pose terms (csrc/losses.hip: two launches per group instead of ~250 ATen launches) -- on GPU tensors; a CPU
-tensor raises (no fallback).  joint_2d / bone_direc / bone_direc_3d: one more kernel pair (round 3).  triangle / normal_consistency (the
-reference's uniform-Laplacian term and, not in the reference, its usual partner): one kernel pair (csrc/mesh_reg.hip).  chamfer (the reference's
-unwired ChamferLoss): one kernel pair (csrc/chamfer.hip).  point_mesh (not in the
-reference: the distance of the target points to the SURFACE of the predicted mesh): one kernel pair (csrc/point_mesh.hip).  depth (declared and
-never computed in the reference: the mean |rendered depth - depth image| on the model's opt-in depth map, outputs['re_depth']): one kernel pair
-(csrc/depth.hip).  open_2dj / open_bone_direc / open_2dj_de (the self-supervised keypoint terms of the reference's deprecated loss_func, which
-its configs still name): one kernel pair (csrc/losses.hip open2d_terms_*).  sil_soft / iou_soft (not in the
-reference: `sil` and `iou` on the model's opt-in differentiable silhouette, outputs['re_sil_soft']): one kernel pair (csrc/soft_sil.hip).  lpips (not in the
-reference: LPIPS(alex), the evaluation pass's texture metric, as an opt-in loss): hifihr_amd/lpips.py with its HIP backward (csrc/lpips.hip).  The rarely used terms (mscale, scale,
-iou, mtex and the self-supervised `*_self` terms) are a handful of torch ops on the same GPU tensors.  The torch restatement of the whole function that the tests
-compare against is oracle/loss_oracle.py (pinned by the reference's own LossFunction.__call__, tests/golden/loss_dict.npz).
+ONE path: GROUPS below lists every term, group by group, in the order they are evaluated; `LossFunction.__call__` walks it.  A group with
+an `ops` entry runs as one fused HIP kernel pair on GPU tensors (csrc/losses.hip: two launches per group instead of ~250 ATen launches for
+the photometric block and the geometry terms); a CPU tensor raises (no fallback).  The rarely used terms (mscale, scale, iou, mtex and the
+self-supervised `*_self` terms) are a handful of torch ops on the same GPU tensors.  The torch restatement of the whole function that the
+tests compare against is oracle/loss_oracle.py (pinned by the reference's own LossFunction.__call__, tests/golden/loss_dict.npz).
 """
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
 
+from . import ops
+
 # bones of the 21-joint FreiHAND skeleton, (parent, child) per row of mat_20_21 (utils/losses_util.py:226-245)
 _BONES = [(0, 1), (1, 2), (2, 3), (3, 4), (0, 5), (5, 6), (6, 7), (7, 8), (0, 9), (9, 10), (10, 11), (11, 12),
           (0, 13), (13, 14), (14, 15), (15, 16), (0, 17), (17, 18), (18, 19), (19, 20)]
-
-
-# every name LossFunction.__call__ can produce (a name outside it in `losses` is ignored here and stops traineval's step with a KeyError)
-TERMS = ("joint_3d", "vert_3d", "edge_length", "mshape", "mpose", "joint_2d", "bone_direc", "bone_direc_3d", "mscale", "scale", "texture",
-         "mrgb", "ssim_tex", "sil", "texture_self", "mrgb_self", "ssim_tex_self", "perceptual", "iou", "sil_soft", "iou_soft", "triangle",
-         "normal_consistency", "lpips", "chamfer", "point_mesh", "depth", "mtex", "open_2dj", "open_bone_direc", "open_2dj_de")
 
 _BONE_IDX = {}
 
@@ -71,6 +61,249 @@ def iou(s_gt, s_est):
 _GEOM_BRANCH = os.environ.get("HIFIHR_GEOM_BRANCH", "0") != "0"
 
 
+# ---- which mesh, which target: the four selections the mesh terms share ------------------------------------------------------------------
+def _mano_faces(outputs):
+    """The MANO faces [F, 3] int32: the model's own tensor, else (outputs that did not come from models.Model) the reference's key."""
+    faces = outputs.get("_faces_i32")
+    return faces if faces is not None else outputs["mano_faces"][0].int().contiguous()
+
+
+def _callers_mesh(outputs):
+    """(verts, faces [F, 3]) when the caller supplies outputs['verts'] AND outputs['faces'], else None.  They are the reference's keys: it
+    asserts that both are present, and its own model never sets 'faces' (the loss-helpers row).  faces [B, F, 3]: one
+    topology for the batch."""
+    verts, faces = outputs.get("verts"), outputs.get("faces")
+    if verts is None or faces is None:
+        return None
+    return verts, (faces[0] if faces.dim() == 3 else faces)
+
+
+def _skin(outputs, args):
+    """The dense skin of the NIMBLE-shaped layer, made root-relative like mano_verts, else None."""
+    if getattr(args, "hand_model", "mano") == "nimble" and outputs.get("verts") is not None and outputs.get("_pred_root") is not None:
+        return outputs["verts"] - outputs["_pred_root"]
+    return None
+
+
+def _target_points(examples):
+    """The target of chamfer / point_mesh: a point cloud of any size (examples['chamfer_points'], in the root-relative frame of
+    examples['verts']), else the ground-truth vertices."""
+    points = examples.get("chamfer_points")
+    return points if points is not None else examples["verts"]
+
+
+# ---- the groups: fn(c, lam) picks the inputs and calls the one ops entry.  c: what __call__ was given (ex, out, used, dat_name, args, lf)
+# plus `parts` (LossFunction._total_parts) and `join`; lam: the group's weights, 0.0 for a name that is not requested -------------------------
+def _geometry(c, lam):
+    """joint_3d / vert_3d / edge_length / mshape / mpose (reference losses.py:259-266, 283-284, 398-406) in one kernel pair (csrc/losses.hip)."""
+    faces = _mano_faces(c.out) if "edge_length" in c.used else None
+    # a term that is not requested has weight 0: any tensor of the right shape serves as its (absent) ground truth
+    joints_gt = c.ex["joints"] if "joints" in c.ex else c.out["joints"].detach()
+    verts_gt = c.ex["verts"] if "verts" in c.ex else c.out["mano_verts"].detach()
+    # the geometry terms need nothing of the renderer: on a side stream they (and their backward) run beside the render / photometric
+    # chain (ops.side_branch); __call__ joins the branch when every term is enqueued
+    with ops.side_branch(c.out["joints"], "geom", enabled=_GEOM_BRANCH and "re_img" in c.out,
+                         inputs=(joints_gt, c.out["mano_verts"], verts_gt, c.out["shape_params"], c.out["pose_params"])) as br:
+        vec = ops.geom_losses(c.out["joints"], joints_gt, c.out["mano_verts"], verts_gt, c.out["shape_params"], c.out["pose_params"], faces,
+                              c.args.base_loss_fn != "L1", lam)
+    c.join = (br, vec)
+    return vec
+
+
+def _joints(c, lam):
+    """The three supervised joint terms in one kernel pair (csrc/losses.hip joint_terms_*; 21-joint skeleton)."""
+    two, three = "joint_2d" in c.used or "bone_direc" in c.used, "bone_direc_3d" in c.used
+    return ops.joint_terms(c.out["j2d"] if two else None, c.ex["j2d_gt"] if two else None, c.out["joints"] if three else None,
+                           c.ex["joints"] if three else None, c.args.base_loss_fn != "L1", lam)
+
+
+def _open2d(c, lam):
+    """The self-supervised keypoint terms (the reference's deprecated loss_func, losses.py:45-63, 79-85: its LossFunction class dropped
+    them while its self_superv_* configs still name them): the projected joints against off-the-shelf 2-D detections weighted by the
+    detector's confidences, one kernel pair (csrc/losses.hip open2d_terms_*).  include/hifihr.h states the two decided corners (d = 0; a
+    batch whose confidences are all 0)."""
+    assert "open_2dj" in c.ex and "open_2dj_con" in c.ex and "j2d" in c.out, (
+        "the loss terms 'open_2dj' / 'open_bone_direc' / 'open_2dj_de' need examples['open_2dj'] and examples['open_2dj_con'] (2-D "
+        "detections and their confidences: data_dic passes them through, FreiHandDeviceCache(open_2dj=..., open_2dj_con=...) "
+        "produces them) and outputs['j2d'] (traineval's step projects it when one of the names is in args.losses)")
+    return ops.open2d_terms(c.out["j2d"], c.ex["open_2dj"], c.ex["open_2dj_con"], lam)
+
+
+def _bone_9_10(outputs):
+    return torch.sqrt(torch.sum((outputs["joints"][:, 9] - outputs["joints"][:, 10]) ** 2, 1))
+
+
+def _mscale(c, lam):
+    bl = _bone_9_10(c.out)
+    return lam[0] * F.l1_loss(bl, torch.ones_like(bl) * 0.0282)
+
+
+def _scale(c, lam):
+    bl = _bone_9_10(c.out)
+    return lam[0] * F.mse_loss(bl, c.ex["scales"].to(bl.device))
+
+
+def _rendered(c):
+    return "re_img" in c.out and "re_sil" in c.out
+
+
+def _photo_self(c, lam):
+    """The self-supervised photometric terms (losses.py:317-340): confidence-weighted, against the image masked by the RENDERED
+    silhouette (outputs['maskRGBs']) and with the unmasked render."""
+    mask_rgbs, re_img, con = c.out["maskRGBs"], c.out["re_img"], c.ex["texture_con"]
+    b = re_img.shape[0]
+    c2 = con.view(-1) ** 2
+    per = torch.abs(re_img - mask_rgbs).reshape(b, -1).sum(1)
+    dm = torch.abs(torch.mean(re_img.reshape(b, -1), 1) - torch.mean(mask_rgbs.reshape(b, -1), 1))
+    return (lam[0] * (torch.sum(per * c2) / (torch.sum(c2) * (re_img.numel() // b))), lam[1] * (torch.sum(dm * c2) / torch.sum(c2)),
+            ops.ssim_loss(re_img, mask_rgbs, lam[2]))
+
+
+def _photo(c, lam):
+    """The photometric block (losses.py:355-378) + `sil` (:398-403) from the renderer's rgba in one kernel pair, then SSIM (csrc/ssim.hip)
+    on the two images the kernel wrote: lambda * (1 - ssim), scalar glue folded in.  Two tensors, so the group registers its own parts.
+    The kernel weights `sil` whether or not it is requested; an unrequested `sil` is left out of the count instead."""
+    rgba = c.out.get("_rgba")
+    if rgba is None:                         # outputs that did not come from models.Model: alpha = the binarised silhouette
+        rgba = torch.cat([c.out["re_img"], (c.out["re_sil"] > 0).to(c.out["re_img"].dtype)], 1)
+    out, re_img, mask_rgbs = ops.photo_losses(rgba, c.ex["imgs"], c.ex["segms_gt"], lam[0], lam[1], c.args.lambda_silhouette)
+    tex, mrgb, sil, _ = out.unbind(0)
+    ssim_tex = ops.ssim_loss(re_img, mask_rgbs, lam[2])
+    c.parts.append((out, 3, ["texture", "mrgb", "sil"]) if "sil" in c.used else (out, 2, ["texture", "mrgb"]))
+    c.parts.append((ssim_tex, 1, ["ssim_tex"]))
+    return tex, mrgb, ssim_tex, sil
+
+
+def _composite(c):
+    seg = c.ex["segms_gt"].unsqueeze(1)
+    return c.out["re_img"] * seg + c.ex["imgs"] * (1 - seg)
+
+
+def _perceptual(c, lam):
+    if c.lf.perceptual_loss is None:
+        from .perceptual import PerceptualLoss
+        c.lf.perceptual_loss = PerceptualLoss().to(c.out["re_img"].device)
+    return lam[0] * c.lf.perceptual_loss(_composite(c), c.ex["imgs"])
+
+
+def _lpips(c, lam):
+    """Not in the reference (its LPIPS is an evaluation metric): the metric the evaluation pass reports, as a loss on the composite the
+    `perceptual` term uses; images in [0, 1] (normalize=True), the target a constant (hifihr_amd/lpips.py, differentiable=True with its
+    HIP backward, csrc/lpips.hip)."""
+    fn = c.lf._lpips_module(c.args, c.out["re_img"].device)
+    return lam[0] * fn(_composite(c), c.ex["imgs"], normalize=True).mean()
+
+
+def _iou(c, lam):
+    return lam[0] * iou(c.out["re_sil"], c.ex["segms_gt"].unsqueeze(1).float())
+
+
+def _soft_sil(c, lam):
+    """Not in the reference: `sil` and `iou` on the model's opt-in differentiable silhouette, one kernel pair (csrc/soft_sil.hip)."""
+    assert "re_sil_soft" in c.out, ("the loss terms 'sil_soft' / 'iou_soft' need outputs['re_sil_soft']: build the model with "
+                                    "Model(..., soft_silhouette=True) (options: soft_silhouette)")
+    return ops.soft_sil_losses(c.out["re_sil_soft"], c.ex["segms_gt"], *lam)
+
+
+def _mesh_reg(c, lam):
+    """`triangle` (losses.py:421-429: lambda_laplacian * mesh_laplacian_smoothing(Meshes(verts, faces), method="uniform")) and its partner
+    `normal_consistency` (not in the reference), one kernel pair (csrc/mesh_reg.hip).  The term cannot run in the reference (see
+    _callers_mesh); here a caller that supplies both keys gets them, and without them the MANO-topology mesh of the model is regularised."""
+    verts, faces = _callers_mesh(c.out) or (c.out["mano_verts"], None)
+    topo = c.out.get("_mesh_topo") if faces is None else None          # the model's own table is the MANO mesh's
+    if topo is None:                         # the caller's mesh, or outputs that did not come from models.Model: built once per faces tensor
+        topo = ops.mesh_topology_of(faces if faces is not None else _mano_faces(c.out), verts.shape[1])
+    return ops.mesh_regularizers(topo, verts, *lam)
+
+
+def _chamfer(c, lam):
+    """Not wired in the reference (utils/losses_util.py:304-337 ChamferLoss is defined, its import in losses.py:7 is commented out):
+    lambda_chamfer * (mean squared distance to the nearest point, prediction -> target + target -> prediction), one kernel pair
+    (csrc/chamfer.hip).  It needs no correspondence, so it reaches the dense skin of the NIMBLE-shaped layer, which no other geometry
+    term does, and it takes a point cloud of any size as the target."""
+    pred = c.out.get("chamfer_points")
+    pred = pred if pred is not None else _skin(c.out, c.args)
+    pred = pred if pred is not None else c.out["mano_verts"]
+    return ops.chamfer_distance(pred, _target_points(c.ex), lam[0], lam[0])
+
+
+def _point_mesh(c, lam):
+    """Not in the reference: lambda_point_mesh * (mean squared distance of the target points to the closest TRIANGLE of the predicted
+    mesh) + lambda_point_mesh_faces * (mean squared distance of the predicted faces to their closest target point; 0 by default: that
+    direction is then not searched), one kernel pair (csrc/point_mesh.hip).  Zero exactly when the target points lie on the predicted
+    surface, which `chamfer` on vertex sets of different density is not.  The target is the one of `chamfer`; the mesh is the caller's
+    when given, else the dense skin with its faces, else the MANO-topology mesh."""
+    mesh, skin_faces = _callers_mesh(c.out), c.out.get("_skin_faces_i32")
+    if mesh is None and skin_faces is not None and (skin := _skin(c.out, c.args)) is not None:
+        mesh = skin, skin_faces
+    verts, faces = mesh or (c.out["mano_verts"], _mano_faces(c.out))
+    return ops.point_mesh_distance(_target_points(c.ex), verts, faces, lam[0], c.args.lambda_point_mesh_faces)
+
+
+def _depth(c, lam):
+    """Declared, never wired in the reference (options lambda_depth, the dataset's depth_crop, a mention of outputs['re_depth'] in its
+    loss code; its model renders no depth): lambda_depth * mean |re_depth - depths| over the pixels the mesh covers, the depth image
+    measures (> 0), the hand mask keeps and -- with depth_trunc > 0 -- that lie within depth_trunc of the target, one kernel pair
+    (csrc/depth.hip) on the model's opt-in depth map.  Dense, absolute in Z and free of correspondences.  examples['depths'] [B, H, W] is
+    in the unit of the vertices."""
+    assert "re_depth" in c.out and "_re_depth_hits" in c.out, (
+        "the loss term 'depth' needs outputs['re_depth']: build the model with Model(..., render_depth=True) (options: render_depth)")
+    return ops.depth_loss(c.out["re_depth"], c.out["_re_depth_hits"], c.ex["depths"], c.ex.get("segms_gt"), lam[0],
+                          getattr(c.args, "depth_trunc", 0.0))
+
+
+def _mtex(c, lam):
+    return lam[0] * F.mse_loss(c.out["texture_params"], torch.zeros_like(c.out["texture_params"]))
+
+
+class Group(NamedTuple):
+    names: tuple        # in the order of the values fn returns
+    lam: tuple          # per name, the attribute of `args` that carries its weight
+    fn: object          # fn(c, lam) -> a vector whose leading entries are the names' values, a 0-d tensor, or a tuple of 0-d tensors
+    cond: object = None     # cond(c): a further condition for the group to run
+    always: tuple = ()      # names computed and reported whether or not they are requested: the group then runs on `cond` alone
+    needs: dict = {}        # key of outputs that the step must provide -> the names that read it
+    total: int = 0          # > 0: fn's result registers for total()'s one launch with this many leading entries (every entry of a vector
+                            # is a term: the ones that were not asked for carry weight 0)
+
+
+_GEOM_LAM = ("lambda_j3d", "lambda_vert_3d", "lambda_edge_len", "lambda_shape", "lambda_pose")
+_PHOTO, _PHOTO_LAM = ("texture", "mrgb", "ssim_tex"), ("lambda_texture", "lambda_mrgb", "lambda_ssim_tex")
+# in the order of evaluation, which is also the order of loss_dic's keys
+GROUPS = (
+    Group(ops.GEOM_TERMS, _GEOM_LAM, _geometry, total=5),
+    # outside total()'s parts, as ever: the kernel pair (round 3) is older than total(), whose commit registered the geometry and photo
+    # vectors of the default list only, and neither DESIGN.md, docs/HISTORY.md nor a commit message says that this vector was left out
+    # on purpose.  No list the project ships would notice: those that name a joint term (configs[2] / [4]) also carry mtex and
+    # perceptual, torch terms that send total() to stack + sum whatever is registered
+    Group(("joint_2d", "bone_direc", "bone_direc_3d"), ("lambda_j2d_gt", "lambda_bone_direc", "lambda_bone_direc_3d"), _joints,
+          needs={"j2d": ("joint_2d", "bone_direc")}),
+    Group(ops.OPEN2D_TERMS, ("lambda_j2d", "lambda_bone_direc", "lambda_j2d_de"), _open2d, needs={"j2d": ops.OPEN2D_TERMS}, total=3),
+    Group(("mscale",), ("lambda_mscale",), _mscale),
+    Group(("scale",), ("lambda_scale",), _scale, cond=lambda c: c.dat_name in ("FreiHand", "RHD")),
+    Group(tuple(k + "_self" for k in _PHOTO), _PHOTO_LAM, _photo_self, cond=lambda c: _rendered(c) and "texture_con" in c.ex,
+          always=tuple(k + "_self" for k in _PHOTO)),
+    Group(_PHOTO + ("sil",), _PHOTO_LAM + ("lambda_silhouette",), _photo, cond=_rendered, always=_PHOTO),
+    Group(("perceptual",), ("lambda_percep",), _perceptual),
+    Group(("lpips",), ("lambda_lpips",), _lpips),
+    Group(("iou",), ("lambda_iou",), _iou),
+    Group(("sil_soft", "iou_soft"), ("lambda_silhouette_soft", "lambda_iou_soft"), _soft_sil, total=2),
+    Group(ops.MESH_REG_TERMS, ("lambda_laplacian", "lambda_normal_consistency"), _mesh_reg, total=2),
+    Group(("chamfer",), ("lambda_chamfer",), _chamfer, total=1),
+    Group(("point_mesh",), ("lambda_point_mesh",), _point_mesh, total=1),
+    Group(("depth",), ("lambda_depth",), _depth, total=1),
+    Group(("mtex",), ("lambda_tex_reg",), _mtex, cond=lambda c: c.out.get("texture_params") is not None),
+)
+
+# every name LossFunction.__call__ can produce (a name outside it in `losses` is ignored here and stops traineval's step with a KeyError)
+TERMS = tuple(k for g in GROUPS for k in g.names)
+
+
+def requested_needing(key, loss_used):
+    """The names of loss_used that read outputs[key], which the step computes only for them (traineval: 'j2d', the projected joints)."""
+    return [k for k in loss_used if any(k in g.needs.get(key, ()) for g in GROUPS)]
+
+
 class LossFunction:
     def __init__(self, perceptual=None, lpips=None):
         # PerceptualLoss instance; None = built on first use (hifihr_amd/perceptual.py: seeded torchvision-style
@@ -79,6 +312,9 @@ class LossFunction:
         # LPIPS(differentiable=True) instance of the opt-in term `lpips`; None = built on first use (args.lpips_weights when given, else the
         # seeded weights and one warning)
         self.lpips_loss = lpips
+        # (vector, leading entries that are terms, their names) of the last __call__: the terms that live in the fused kernels' output
+        # vectors; `total` sums them in one launch when they are exactly the requested list
+        self._total_parts = []
 
     def _lpips_module(self, args, device):
         if self.lpips_loss is None:
@@ -94,224 +330,32 @@ class LossFunction:
             self.lpips_loss = m.to(device)
         return self.lpips_loss
 
-    def _fused_geometry(self, examples, outputs, loss_used, args, loss_dic):
-        """joint_3d / vert_3d / edge_length / mshape / mpose in one kernel pair (csrc/losses.hip)."""
-        from . import ops
-        lam = [args.lambda_j3d if "joint_3d" in loss_used else 0.0, args.lambda_vert_3d if "vert_3d" in loss_used else 0.0,
-               args.lambda_edge_len if "edge_length" in loss_used else 0.0, args.lambda_shape if "mshape" in loss_used else 0.0,
-               args.lambda_pose if "mpose" in loss_used else 0.0]
-        faces = None
-        if "edge_length" in loss_used:
-            faces = outputs.get("_faces_i32")
-            if faces is None:
-                faces = outputs["mano_faces"][0].int().contiguous()
-        # a term that is not requested has weight 0: any tensor of the right shape serves as its (absent) ground truth
-        joints_gt = examples["joints"] if "joints" in examples else outputs["joints"].detach()
-        verts_gt = examples["verts"] if "verts" in examples else outputs["mano_verts"].detach()
-        # the geometry terms need nothing of the renderer: on a side stream they (and their backward) run beside the render / photometric
-        # chain (ops.side_branch); __call__ joins the branch when every term is enqueued
-        with ops.side_branch(outputs["joints"], "geom", enabled=_GEOM_BRANCH and "re_img" in outputs,
-                             inputs=(joints_gt, outputs["mano_verts"], verts_gt, outputs["shape_params"], outputs["pose_params"])) as br:
-            vec = ops.geom_losses(outputs["joints"], joints_gt, outputs["mano_verts"], verts_gt,
-                                  outputs["shape_params"], outputs["pose_params"], faces, args.base_loss_fn != "L1", lam)
-        self._pending_join = (br, vec)
-        for k, v in zip(ops.GEOM_TERMS, vec.unbind(0)):
-            if k in loss_used:
-                loss_dic[k] = v
-        # (every entry of the vector is a term: the ones that were not asked for carry weight 0)
-        self._total_parts.append((vec, 5, [k for k in ops.GEOM_TERMS if k in loss_used]))
-
     def __call__(self, examples, outputs, loss_used, dat_name, args) -> dict:
-        self._pending_join = None
-        # (vector, leading entries that are terms, their names): the terms that live in the fused kernels' output vectors; `total` sums
-        # them in one launch when they are exactly the requested list
-        self._total_parts = []
+        loss_dic, self._total_parts = {}, []
+        c = SimpleNamespace(ex=examples, out=outputs, used=loss_used, dat_name=dat_name, args=args, lf=self, parts=self._total_parts, join=None)
         try:
-            return self._terms(examples, outputs, loss_used, dat_name, args)
+            for g in GROUPS:
+                report = [k for k in g.names if k in loss_used or k in g.always]
+                if not report or (g.cond is not None and not g.cond(c)):
+                    continue
+                res = g.fn(c, tuple(getattr(args, a) if k in report else 0.0 for k, a in zip(g.names, g.lam)))
+                vals = res if isinstance(res, tuple) else res.unbind(0) if res.dim() else (res,)
+                loss_dic.update((k, v) for k, v in zip(g.names, vals) if k in report)
+                if g.total:
+                    self._total_parts.append((res, g.total, report))
         finally:
-            if self._pending_join is not None:          # the geometry branch meets the main stream behind the last term
-                br, vec = self._pending_join
-                br.join(vec)
-                self._pending_join = None
+            if c.join is not None:           # the geometry branch meets the main stream behind the last term
+                c.join[0].join(c.join[1])
+        return loss_dic
 
     def total(self, loss_dic, losses):
         """sum(loss_dic[k] for k in losses) (reference train_hrnet.py:98-104) -- in ONE launch when the requested terms are exactly the
         ones the fused kernels of the last __call__ hold in their output vectors, else as a stack + sum."""
-        from . import ops
         # (a vector none of whose terms is requested -- the photometric block of a rendering model under a keypoint-only list -- is left out)
-        parts = [p for p in getattr(self, "_total_parts", []) if any(k in losses for k in p[2])]
+        parts = [p for p in self._total_parts if any(k in losses for k in p[2])]
         covered = [k for _, _, names in parts for k in names]
         if (parts and len(parts) <= 4 and sorted(covered) == sorted(losses) and all(p.is_cuda for p, _, _ in parts)
                 and all(loss_dic.get(k) is not None for k in losses)):
             return ops.loss_total([(p, n) for p, n, _ in parts])
         terms = [loss_dic[k] for k in losses]
         return terms[0] if len(terms) == 1 else torch.stack(terms).sum()      # 2 launches instead of a chain of adds
-
-    def _terms(self, examples, outputs, loss_used, dat_name, args) -> dict:
-        from . import ops
-        loss_dic = {}
-        base = F.l1_loss if args.base_loss_fn == "L1" else F.mse_loss
-        if any(k in loss_used for k in ("joint_3d", "vert_3d", "edge_length", "mshape", "mpose")):
-            self._fused_geometry(examples, outputs, loss_used, args, loss_dic)
-            loss_used = [k for k in loss_used if k not in loss_dic]
-        want = [k in loss_used for k in ("joint_2d", "bone_direc", "bone_direc_3d")]
-        if any(want):
-            # one kernel pair for the three supervised joint terms (csrc/losses.hip joint_terms_*; 21-joint skeleton)
-            two, three = want[0] or want[1], want[2]
-            lam3 = (args.lambda_j2d_gt if want[0] else 0.0, args.lambda_bone_direc if want[1] else 0.0, args.lambda_bone_direc_3d if want[2] else 0.0)
-            vals = ops.joint_terms(outputs["j2d"] if two else None, examples["j2d_gt"] if two else None,
-                                   outputs["joints"] if three else None, examples["joints"] if three else None,
-                                   args.base_loss_fn != "L1", lam3).unbind(0)
-            for k, w, v in zip(("joint_2d", "bone_direc", "bone_direc_3d"), want, vals):
-                if w:
-                    loss_dic[k] = v
-        if any(k in loss_used for k in ops.OPEN2D_TERMS):
-            # the self-supervised keypoint terms (the reference's deprecated loss_func, losses.py:45-63, 79-85: its LossFunction class
-            # dropped them while its self_superv_* configs still name them): the projected joints against off-the-shelf 2-D detections
-            # weighted by the detector's confidences, one kernel pair (csrc/losses.hip open2d_terms_*); a term that is not requested has
-            # weight 0.  include/hifihr.h states the two decided corners (d = 0; a batch whose confidences are all 0)
-            assert "open_2dj" in examples and "open_2dj_con" in examples and "j2d" in outputs, (
-                "the loss terms 'open_2dj' / 'open_bone_direc' / 'open_2dj_de' need examples['open_2dj'] and examples['open_2dj_con'] (2-D "
-                "detections and their confidences: data_dic passes them through, FreiHandDeviceCache(open_2dj=..., open_2dj_con=...) "
-                "produces them) and outputs['j2d'] (traineval's step projects it when one of the names is in args.losses)")
-            names = [k for k in ops.OPEN2D_TERMS if k in loss_used]
-            vec = ops.open2d_terms(outputs["j2d"], examples["open_2dj"], examples["open_2dj_con"],
-                                   (args.lambda_j2d if "open_2dj" in loss_used else 0.0,
-                                    args.lambda_bone_direc if "open_bone_direc" in loss_used else 0.0,
-                                    args.lambda_j2d_de if "open_2dj_de" in loss_used else 0.0))
-            for k, v in zip(ops.OPEN2D_TERMS, vec.unbind(0)):
-                if k in loss_used:
-                    loss_dic[k] = v
-            self._total_parts.append((vec, 3, names))
-        if "mscale" in loss_used:
-            bl = torch.sqrt(torch.sum((outputs["joints"][:, 9] - outputs["joints"][:, 10]) ** 2, 1))
-            loss_dic["mscale"] = args.lambda_mscale * F.l1_loss(bl, torch.ones_like(bl) * 0.0282)
-        if "scale" in loss_used and dat_name in ("FreiHand", "RHD"):
-            bl = torch.sqrt(torch.sum((outputs["joints"][:, 9] - outputs["joints"][:, 10]) ** 2, 1))
-            loss_dic["scale"] = args.lambda_scale * F.mse_loss(bl, examples["scales"].to(bl.device))
-        if "re_img" in outputs and "re_sil" in outputs and "texture_con" in examples:
-            # self-supervised photometric terms (losses.py:317-340): confidence-weighted, against the image masked by the RENDERED
-            # silhouette (outputs['maskRGBs']) and with the unmasked render
-            mask_rgbs, re_img, con = outputs["maskRGBs"], outputs["re_img"], examples["texture_con"]
-            b = re_img.shape[0]
-            c2 = con.view(-1) ** 2
-            per = torch.abs(re_img - mask_rgbs).reshape(b, -1).sum(1)
-            loss_dic["texture_self"] = args.lambda_texture * (torch.sum(per * c2) / (torch.sum(c2) * (re_img.numel() // b)))
-            dm = torch.abs(torch.mean(re_img.reshape(b, -1), 1) - torch.mean(mask_rgbs.reshape(b, -1), 1))
-            loss_dic["mrgb_self"] = args.lambda_mrgb * (torch.sum(dm * c2) / torch.sum(c2))
-            loss_dic["ssim_tex_self"] = ops.ssim_loss(re_img, mask_rgbs, args.lambda_ssim_tex)
-        if "re_img" in outputs and "re_sil" in outputs:
-            # photometric block (losses.py:355-378) + `sil` (:398-403) from the renderer's rgba in one kernel pair
-            rgba = outputs.get("_rgba")
-            if rgba is None:                     # outputs that did not come from models.Model: alpha = the binarised silhouette
-                rgba = torch.cat([outputs["re_img"], (outputs["re_sil"] > 0).to(outputs["re_img"].dtype)], 1)
-            out, re_img, mask_rgbs = ops.photo_losses(rgba, examples["imgs"], examples["segms_gt"], args.lambda_texture,
-                                                      args.lambda_mrgb, args.lambda_silhouette)
-            tex, mrgb, sil, _ = out.unbind(0)
-            loss_dic["texture"], loss_dic["mrgb"] = tex, mrgb
-            loss_dic["ssim_tex"] = ops.ssim_loss(re_img, mask_rgbs, args.lambda_ssim_tex)   # lambda * (1 - ssim), scalar glue folded in
-            if "sil" in loss_used:
-                loss_dic["sil"] = sil
-                self._total_parts.append((out, 3, ["texture", "mrgb", "sil"]))
-            else:
-                self._total_parts.append((out, 2, ["texture", "mrgb"]))
-            self._total_parts.append((loss_dic["ssim_tex"], 1, ["ssim_tex"]))
-        if "perceptual" in loss_used:
-            if self.perceptual_loss is None:
-                from .perceptual import PerceptualLoss
-                self.perceptual_loss = PerceptualLoss().to(outputs["re_img"].device)
-            seg = examples["segms_gt"].unsqueeze(1)
-            loss_dic["perceptual"] = args.lambda_percep * self.perceptual_loss(
-                outputs["re_img"] * seg + examples["imgs"] * (1 - seg), examples["imgs"])
-        if "lpips" in loss_used:
-            # not in the reference (its LPIPS is an evaluation metric): the metric the evaluation pass reports, as a loss on the composite the
-            # `perceptual` term uses; images in [0, 1] (normalize=True), the target a constant (hifihr_amd/lpips.py, differentiable=True)
-            seg = examples["segms_gt"].unsqueeze(1)
-            fn = self._lpips_module(args, outputs["re_img"].device)
-            loss_dic["lpips"] = args.lambda_lpips * fn(outputs["re_img"] * seg + examples["imgs"] * (1 - seg), examples["imgs"],
-                                                       normalize=True).mean()
-        if "iou" in loss_used:
-            loss_dic["iou"] = args.lambda_iou * iou(outputs["re_sil"], examples["segms_gt"].unsqueeze(1).float())
-        if "sil_soft" in loss_used or "iou_soft" in loss_used:
-            # the two terms of the differentiable silhouette, one kernel pair (csrc/soft_sil.hip); a term that is not requested has weight 0
-            assert "re_sil_soft" in outputs, ("the loss terms 'sil_soft' / 'iou_soft' need outputs['re_sil_soft']: build the model with "
-                                              "Model(..., soft_silhouette=True) (options: soft_silhouette)")
-            names = [k for k in ("sil_soft", "iou_soft") if k in loss_used]
-            vec = ops.soft_sil_losses(outputs["re_sil_soft"], examples["segms_gt"],
-                                      args.lambda_silhouette_soft if "sil_soft" in loss_used else 0.0,
-                                      args.lambda_iou_soft if "iou_soft" in loss_used else 0.0)
-            for k, v in zip(("sil_soft", "iou_soft"), vec.unbind(0)):
-                if k in loss_used:
-                    loss_dic[k] = v
-            self._total_parts.append((vec, 2, names))
-        if "triangle" in loss_used or "normal_consistency" in loss_used:
-            # `triangle` (losses.py:421-429: lambda_laplacian * mesh_laplacian_smoothing(Meshes(verts, faces), method="uniform")) and its
-            # partner `normal_consistency` (not in the reference), one kernel pair (csrc/mesh_reg.hip); a term that is not requested has
-            # weight 0.  outputs['verts'] / outputs['faces'] are the reference's keys: it asserts that both are present, and its own model
-            # never sets 'faces', so the term cannot run there (SURVEY.md section 2, the loss-helpers row).  A caller that supplies both
-            # gets them; without them the MANO-topology mesh of the model is regularised
-            if outputs.get("verts") is not None and outputs.get("faces") is not None:
-                verts, faces = outputs["verts"], outputs["faces"]              # faces [F, 3], or [B, F, 3] with one topology for the batch
-                topo = ops.mesh_topology_of(faces[0] if faces.dim() == 3 else faces, verts.shape[1])
-            else:
-                verts, topo = outputs["mano_verts"], outputs.get("_mesh_topo")
-                if topo is None:                 # outputs that did not come from models.Model: built once per faces tensor
-                    faces = outputs.get("_faces_i32")
-                    if faces is None:
-                        faces = outputs["mano_faces"][0].int().contiguous()
-                    topo = ops.mesh_topology_of(faces, verts.shape[1])
-            names = [k for k in ops.MESH_REG_TERMS if k in loss_used]
-            vec = ops.mesh_regularizers(topo, verts, args.lambda_laplacian if "triangle" in loss_used else 0.0,
-                                        args.lambda_normal_consistency if "normal_consistency" in loss_used else 0.0)
-            for k, v in zip(ops.MESH_REG_TERMS, vec.unbind(0)):
-                if k in loss_used:
-                    loss_dic[k] = v
-            self._total_parts.append((vec, 2, names))
-        if "chamfer" in loss_used:
-            # not wired in the reference (utils/losses_util.py:304-337 ChamferLoss is defined, its import in losses.py:7 is commented out):
-            # lambda_chamfer * (mean squared distance to the nearest point, prediction -> target + target -> prediction), one kernel pair
-            # (csrc/chamfer.hip).  It needs no correspondence, so it reaches the dense skin of the NIMBLE-shaped layer, which no other geometry
-            # term does, and it takes a point cloud of any size as the target (examples['chamfer_points'], in the root-relative frame of
-            # examples['verts'])
-            target = examples["chamfer_points"] if examples.get("chamfer_points") is not None else examples["verts"]
-            if outputs.get("chamfer_points") is not None:
-                pred = outputs["chamfer_points"]
-            elif getattr(args, "hand_model", "mano") == "nimble" and outputs.get("verts") is not None and outputs.get("_pred_root") is not None:
-                pred = outputs["verts"] - outputs["_pred_root"]             # the dense skin, root-relative like mano_verts
-            else:
-                pred = outputs["mano_verts"]
-            loss_dic["chamfer"] = ops.chamfer_distance(pred, target, args.lambda_chamfer, args.lambda_chamfer)
-            self._total_parts.append((loss_dic["chamfer"], 1, ["chamfer"]))
-        if "point_mesh" in loss_used:
-            # not in the reference: lambda_point_mesh * (mean squared distance of the target points to the closest TRIANGLE of the predicted
-            # mesh) + lambda_point_mesh_faces * (mean squared distance of the predicted faces to their closest target point; 0 by default: that
-            # direction is then not searched), one kernel pair (csrc/point_mesh.hip).  Zero exactly when the target points lie on the predicted
-            # surface, which `chamfer` on vertex sets of different density is not.  The target is the one of `chamfer`; the mesh is the
-            # caller's outputs['verts'] / outputs['faces'] when both are given, else the dense skin of the NIMBLE-shaped layer made
-            # root-relative, else the MANO-topology mesh
-            target = examples["chamfer_points"] if examples.get("chamfer_points") is not None else examples["verts"]
-            if outputs.get("verts") is not None and outputs.get("faces") is not None:
-                verts, faces = outputs["verts"], outputs["faces"]              # faces [F, 3], or [B, F, 3] with one topology for the batch
-                faces = faces[0] if faces.dim() == 3 else faces
-            elif (getattr(args, "hand_model", "mano") == "nimble" and outputs.get("verts") is not None and outputs.get("_pred_root") is not None
-                  and outputs.get("_skin_faces_i32") is not None):
-                verts, faces = outputs["verts"] - outputs["_pred_root"], outputs["_skin_faces_i32"]
-            else:
-                verts, faces = outputs["mano_verts"], outputs.get("_faces_i32")
-                if faces is None:
-                    faces = outputs["mano_faces"][0].int().contiguous()
-            loss_dic["point_mesh"] = ops.point_mesh_distance(target, verts, faces, args.lambda_point_mesh, args.lambda_point_mesh_faces)
-            self._total_parts.append((loss_dic["point_mesh"], 1, ["point_mesh"]))
-        if "depth" in loss_used:
-            # declared, never wired in the reference (options lambda_depth, the dataset's depth_crop, a mention of outputs['re_depth'] in its
-            # loss code; its model renders no depth): lambda_depth * mean |re_depth - depths| over the pixels the mesh covers, the depth image
-            # measures (> 0), the hand mask keeps and -- with depth_trunc > 0 -- that lie within depth_trunc of the target, one kernel pair
-            # (csrc/depth.hip).  Dense, absolute in Z and free of correspondences.  examples['depths'] [B, H, W] is in the unit of the vertices
-            assert "re_depth" in outputs and "_re_depth_hits" in outputs, (
-                "the loss term 'depth' needs outputs['re_depth']: build the model with Model(..., render_depth=True) (options: render_depth)")
-            loss_dic["depth"] = ops.depth_loss(outputs["re_depth"], outputs["_re_depth_hits"], examples["depths"], examples.get("segms_gt"),
-                                               args.lambda_depth, getattr(args, "depth_trunc", 0.0))
-            self._total_parts.append((loss_dic["depth"], 1, ["depth"]))
-        if "mtex" in loss_used and outputs.get("texture_params") is not None:
-            loss_dic["mtex"] = args.lambda_tex_reg * F.mse_loss(outputs["texture_params"], torch.zeros_like(outputs["texture_params"]))
-        return loss_dic

@@ -392,12 +392,16 @@ def soft_silhouette(handle: RendererHandle, verts, cam, sigma=SOFT_SIL_SIGMA, bl
     return _SoftSilhouette.apply(handle, verts, cam, sigma, blur_radius)
 
 
+def _mask_arg(mask):
+    """A hand mask as the loss kernels read it: float32 or int64 (segms_gt) as it is, any other type as float32; contiguous."""
+    return mask.contiguous() if mask.dtype in (torch.float32, torch.int64) else mask.float().contiguous()
+
+
 class _SoftSilLosses(torch.autograd.Function):
     @staticmethod
     def forward(ctx, alpha, mask, lam_sil, lam_iou):
         require_cuda(alpha, mask)
-        alpha = alpha.contiguous()
-        mask = mask.contiguous() if mask.dtype in (torch.float32, torch.int64) else mask.float().contiguous()
+        alpha, mask = alpha.contiguous(), _mask_arg(mask)
         assert mask.numel() == alpha.numel(), (alpha.shape, mask.shape)
         sums = torch.empty(alpha.shape[0], 3, dtype=torch.float64, device=alpha.device)
         out = torch.empty(2, device=alpha.device)
@@ -459,18 +463,24 @@ def render_depth(handle: RendererHandle, verts, cam, face_id):
     return _RenderDepth.apply(handle, verts, cam, face_id)
 
 
+def _depth_loss_run(depth, hits, target, mask, lam, trunc):
+    """hifihr_depth_loss_fwd -> (depth, hits, target, mask as the kernel read them, sums, out)."""
+    require_cuda(depth, hits, target)
+    depth, hits = depth.contiguous(), hits.contiguous()
+    target = target.contiguous() if target.dtype == torch.float32 else target.float().contiguous()
+    if mask is not None:
+        require_cuda(mask)
+        mask = _mask_arg(mask)
+    sums = torch.empty(depth.shape[0], 2, dtype=torch.float64, device=depth.device)
+    out = torch.empty(1, device=depth.device)
+    PROFILE.bracket("depth_loss_fwd", lambda: get_lib().depth_loss_fwd(depth, hits, target, mask, lam, trunc, sums, out))
+    return depth, hits, target, mask, sums, out
+
+
 class _DepthLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depth, hits, target, mask, lam, trunc):
-        require_cuda(depth, hits, target)
-        depth, hits = depth.contiguous(), hits.contiguous()
-        target = target.contiguous() if target.dtype == torch.float32 else target.float().contiguous()
-        if mask is not None:
-            require_cuda(mask)
-            mask = mask.contiguous() if mask.dtype in (torch.float32, torch.int64) else mask.float().contiguous()
-        sums = torch.empty(depth.shape[0], 2, dtype=torch.float64, device=depth.device)
-        out = torch.empty(1, device=depth.device)
-        PROFILE.bracket("depth_loss_fwd", lambda: get_lib().depth_loss_fwd(depth, hits, target, mask, lam, trunc, sums, out))
+        depth, hits, target, mask, sums, out = _depth_loss_run(depth, hits, target, mask, lam, trunc)
         ctx.save_for_backward(depth, hits, target, sums)
         ctx.mask, ctx.params = mask, (lam, trunc)
         return out
@@ -498,16 +508,7 @@ def depth_loss(depth, hits, target, mask=None, lam=1.0, trunc=0.0):
 def depth_loss_sums(depth, hits, target, mask=None, trunc=0.0):
     """float64 [B, 2] on the device: per sample (sum of |depth - target| over the valid pixels, their count), the sums depth_loss divides
     (the same kernel; no gradient): what an evaluation pass accumulates over batches."""
-    require_cuda(depth, hits, target)
-    depth, hits = depth.detach().contiguous(), hits.contiguous()
-    target = target.contiguous() if target.dtype == torch.float32 else target.float().contiguous()
-    if mask is not None:
-        require_cuda(mask)
-        mask = mask.contiguous() if mask.dtype in (torch.float32, torch.int64) else mask.float().contiguous()
-    sums = torch.empty(depth.shape[0], 2, dtype=torch.float64, device=depth.device)
-    out = torch.empty(1, device=depth.device)
-    PROFILE.bracket("depth_loss_fwd", lambda: get_lib().depth_loss_fwd(depth, hits, target, mask, 1.0, float(trunc), sums, out))
-    return sums
+    return _depth_loss_run(depth.detach(), hits, target, mask, 1.0, float(trunc))[4]
 
 
 class MeshTopology:
@@ -530,18 +531,25 @@ class MeshTopology:
 
 
 MESH_REG_TERMS = ("triangle", "normal_consistency")
-_TOPO_CACHE = {}
+_FACES_TABLES = {}
+
+
+def _per_faces(kind, faces, V, build):
+    """build(), called once per (kind of table, faces tensor, vertex count) and kept: what _vertex_face_csr, mesh_topology_of and
+    point_mesh_tables_of derive from a topology.  The key is the tensor's ADDRESS, so the entry keeps the tensor as well: a freed one's
+    address can go to another topology of the same size, which would then be handed this table."""
+    key = (kind, faces.data_ptr(), int(faces.shape[0]), int(V), str(faces.device))
+    hit = _FACES_TABLES.get(key)
+    if hit is None:
+        hit = _FACES_TABLES[key] = (build(), faces)
+    return hit[0]
 
 
 def mesh_topology_of(faces, V):
     """The MeshTopology of a faces tensor [F, 3], built on first use and kept per tensor (as _vertex_face_csr keeps its table): for outputs
     that do not come from models.Model, which builds its own at construction."""
     require_cuda(faces)
-    key = (faces.data_ptr(), int(faces.shape[0]), int(V), str(faces.device))
-    hit = _TOPO_CACHE.get(key)
-    if hit is None:
-        hit = _TOPO_CACHE[key] = MeshTopology(faces.reshape(-1, 3), V)
-    return hit
+    return _per_faces("mesh_topology", faces, V, lambda: MeshTopology(faces.reshape(-1, 3), V))
 
 
 class _MeshReg(torch.autograd.Function):
@@ -623,20 +631,16 @@ def chamfer_sums(x, y):
         return _chamfer_run(x.detach(), y.detach(), 1.0, 1.0)[6]
 
 
-_POINT_MESH_TABLES = {}
-
-
 def point_mesh_tables_of(faces, V):
     """-> (faces int32 [F, 3] contiguous, v2c_off int32 [V + 1], v2c_corner int32 [3 F]) on the faces' device: the vertex -> corner table of
-    hifihr_point_mesh_bwd (include/hifihr.h "Point-to-mesh distance"), built on first use and kept per faces tensor, keyed as
-    mesh_topology_of keys its cache.  The first use copies the faces to the host, validates them (indices in [0, V), no face with a
+    hifihr_point_mesh_bwd (include/hifihr.h "Point-to-mesh distance"), built on first use and kept per faces tensor
+    (_per_faces).  The first use copies the faces to the host, validates them (indices in [0, V), no face with a
     repeated index) and allocates, so it belongs outside a captured step: run the loss once eagerly first, as a captured step's warm-up
     does."""
     require_cuda(faces)
     assert faces.dim() == 2 and faces.shape[1] == 3 and faces.shape[0] > 0 and not faces.dtype.is_floating_point, (faces.shape, faces.dtype)
-    key = (faces.data_ptr(), int(faces.shape[0]), int(V), str(faces.device))
-    hit = _POINT_MESH_TABLES.get(key)
-    if hit is None:
+
+    def build():
         f = faces.detach().cpu().numpy().astype(np.int64)
         if f.min() < 0 or f.max() >= V:
             raise ValueError(f"point_mesh: a face index outside [0, {V}) (found {int(f.min())} .. {int(f.max())})")
@@ -647,9 +651,8 @@ def point_mesh_tables_of(faces, V):
         np.cumsum(np.bincount(flat, minlength=V), out=off[1:])
         corner = np.argsort(flat, kind="stable")             # the corners 3 f + k vertex by vertex, ascending inside a vertex
         dev = faces.device
-        hit = _POINT_MESH_TABLES[key] = (faces.to(torch.int32).contiguous(), torch.as_tensor(off.astype(np.int32)).to(dev),
-                                         torch.as_tensor(corner.astype(np.int32)).to(dev), faces)     # (keeps `faces` alive: the key is its address)
-    return hit[:3]
+        return faces.to(torch.int32).contiguous(), torch.as_tensor(off.astype(np.int32)).to(dev), torch.as_tensor(corner.astype(np.int32)).to(dev)
+    return _per_faces("point_mesh", faces, V, build)
 
 
 def _point_mesh_run(points, verts, faces, w_pf, w_fp):
@@ -2013,16 +2016,12 @@ def bn_relu_maxpool(x, stats, bn: torch.nn.BatchNorm2d):
 # fused losses (csrc/losses.hip)
 # ------------------------------------------------------------------------------------------------
 GEOM_TERMS = ("joint_3d", "vert_3d", "edge_length", "mshape", "mpose")
-_VF_CACHE = {}
 
 
 def _vertex_face_csr(faces, V):
     """faces [F,3] int32 (device) -> (vf_off [V+1], vf_idx [3F]) int32 on the same device: for every vertex the incident
     (face * 4 + corner) entries in ascending face order (same table as the renderer builds, hifihr_api.hip)."""
-    key = (faces.data_ptr(), int(faces.shape[0]), V, str(faces.device))
-    hit = _VF_CACHE.get(key)
-    if hit is None:
-        import numpy as np
+    def build():
         f = faces.detach().cpu().numpy().astype(np.int64)
         flat = f.reshape(-1)
         order = np.argsort(flat, kind="stable")                      # stable: ascending face order within a vertex
@@ -2030,9 +2029,8 @@ def _vertex_face_csr(faces, V):
         np.add.at(off, flat + 1, 1)
         off = np.cumsum(off).astype(np.int32)
         idx = ((order // 3) * 4 + (order % 3)).astype(np.int32)
-        hit = (torch.from_numpy(off).to(faces.device), torch.from_numpy(idx).to(faces.device))
-        _VF_CACHE[key] = hit
-    return hit
+        return torch.from_numpy(off).to(faces.device), torch.from_numpy(idx).to(faces.device)
+    return _per_faces("vertex_face_csr", faces, V, build)
 
 
 class _GeomLoss(torch.autograd.Function):

@@ -45,9 +45,6 @@ def RHD2Frei(rhd_joints):
     return rhd_joints[:, _RHD_TO_FREI]
 
 
-# the loss terms that read outputs["j2d"], the projection of the predicted joints (the step computes it only for them)
-_J2D_TERMS = ("joint_2d", "bone_direc", "open_2dj", "open_bone_direc", "open_2dj_de")
-
 FREIHAND_TRAIN_SIZE = 32560        # samples of the FreiHAND training set: indices from here on are its augmented copies
 
 
@@ -190,6 +187,18 @@ def forward_backward(model, loss_func, optimizer, examples, args, dat_name="Frei
         return _forward_backward(model, loss_func, optimizer, examples, args, dat_name)
 
 
+def _loss_terms(loss_func, ex, outputs, Ks, root_xyz, args, dat_name, why=""):
+    """The shared tail of _forward_backward and _forward_only: loss_dic of args.losses, every one of them produced."""
+    from .losses import requested_needing
+    if requested_needing("j2d", args.losses):
+        outputs["j2d"] = trans_proj_j2d(outputs, Ks, root_xyz=root_xyz)      # the projected joints: only these terms read them
+    loss_dic = loss_func(ex, outputs, args.losses, dat_name, args)
+    missing = [k for k in args.losses if k not in loss_dic]
+    if missing:                              # e.g. 'mtex' on a hand layer without texture_params, 'vert_3d' on a dataset without vertices
+        raise KeyError(f"loss terms {missing} were requested but not produced for {dat_name}{why}")
+    return loss_dic
+
+
 def _forward_backward(model, loss_func, optimizer, examples, args, dat_name):
     # batches assembled by data.FreiHandDeviceCache.batch_examples(root_id=args.ROOT) carry the terms derived here on every iteration
     # (root_xyz, the root-relative ground truth, the NDC camera): four elementwise launches fewer per step
@@ -212,12 +221,8 @@ def _forward_backward(model, loss_func, optimizer, examples, args, dat_name):
         ex["joints"] = examples["joints"] - root_xyz
         if "verts" in examples:
             ex["verts"] = examples["verts"] - root_xyz
-    if any(k in args.losses for k in _J2D_TERMS):
-        outputs["j2d"] = trans_proj_j2d(outputs, examples["Ks"], root_xyz=root_xyz)      # only these terms read it
-    loss_dic = loss_func(ex, outputs, args.losses, dat_name, args)
-    missing = [k for k in args.losses if k not in loss_dic]
-    if missing:                              # e.g. 'mtex' on a hand layer without texture_params, 'vert_3d' on a dataset without vertices
-        raise KeyError(f"loss terms {missing} were requested but not produced for {dat_name}: their inputs are absent from the model outputs / examples")
+    loss_dic = _loss_terms(loss_func, ex, outputs, examples["Ks"], root_xyz, args, dat_name,
+                           ": their inputs are absent from the model outputs / examples")
     if hasattr(loss_func, "total"):
         loss = loss_func.total(loss_dic, args.losses)          # one launch when the terms sit in the fused kernels' vectors
     else:
@@ -505,13 +510,8 @@ def _forward_only(model, loss_func, optimizer, examples, args, dat_name, root_xy
         ex["joints"] = examples["joints"] - root_xyz
         if "verts" in examples:
             ex["verts"] = examples["verts"] - root_xyz
-    if any(k in args.losses for k in _J2D_TERMS):
-        outputs["j2d"] = trans_proj_j2d(outputs, examples["Ks"], root_xyz=root_xyz)
-    loss_dic = loss_func(ex, outputs, args.losses, dat_name, args)
-    missing = [k for k in args.losses if k not in loss_dic]
-    if missing:
-        raise KeyError(f"loss terms {missing} were requested but not produced for {dat_name}")
-    terms = [loss_dic[k] for k in args.losses]
+    loss_dic = _loss_terms(loss_func, ex, outputs, examples["Ks"], root_xyz, args, dat_name)
+    terms = [loss_dic[k] for k in args.losses]         # stack + sum, not loss_func.total: the segmented step cuts the autograd graph here
     loss = terms[0] if len(terms) == 1 else torch.stack(terms).sum()
     loss_dic["loss"] = loss
     optimizer.zero_grad(set_to_none=True)
