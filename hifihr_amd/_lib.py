@@ -229,6 +229,19 @@ class HifihrLib:
         self._run("hifihr_mano_full_bwd", h, pose, beta, saved, gjoints_rel, gverts_rel, gverts_cam, groot, gpose_add, gbeta_add,
                   pose.shape[0], root_id, gpose, gbeta)
 
+    def mano_fit(self, h, pose, beta, root, K, kp2d, conf2d, kp3d, conf3d, prior, lr, iters, weights6, lr_mult4, root_id, trace, grad0, done):
+        """hifihr_mano_fit: the whole keypoint fit in one launch; pose [B,48] / beta [B,10] / root [B,3] are updated in place.
+        prior = (lo, hi, w) [48] each, or None; lr [iters] on the device (None for iters == 0); trace [B,iters+1,8], done int32 [B]."""
+        B = pose.shape[0]
+        assert pose.shape == (B, 48) and beta.shape == (B, 10) and root.shape == (B, 3) and K.shape == (B, 3, 3), (pose.shape, K.shape)
+        assert kp2d.shape == (B, 21, 2) and conf2d.numel() == B * 21 and trace.shape == (B, iters + 1, 8) and done.shape == (B,)
+        assert lr is None or lr.numel() == iters, (iters, None if lr is None else lr.shape)
+        for t, numel in ((kp3d, B * 63), (conf3d, B * 21), (grad0, B * 61)) + tuple((p, 48) for p in (prior or ())):
+            assert t is None or t.numel() == numel, (t.shape, numel)
+        lo, hi, w = prior if prior is not None else (None, None, None)
+        self._run("hifihr_mano_fit", h, pose, beta, root, K, kp2d, conf2d, kp3d, conf3d, lo, hi, w, lr, iters, _floats(weights6, 6),
+                  _floats(lr_mult4, 4), root_id, B, trace, grad0, done)
+
     # ---- generic LBS (NIMBLE-shaped layer) -----------------------------
     def lbs_create(self, v_template, shapedirs, j_regressor, weights, parents) -> c_void_p:
         V, J, S = int(v_template.shape[0]), int(weights.shape[1]), int(shapedirs.shape[2])

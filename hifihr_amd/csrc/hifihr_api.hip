@@ -255,6 +255,20 @@ int hifihr_mano_full_bwd(const hifihr_mano_t* h, const float* pose, const float*
   return HIFIHR_OK;
 }
 
+int hifihr_mano_fit(const hifihr_mano_t* h, float* pose, float* beta, float* root, const float* K, const float* kp2d, const float* conf2d,
+                    const float* kp3d, const float* conf3d, const float* prior_lo, const float* prior_hi, const float* prior_w, const float* lr,
+                    int iters, const float* weights6, const float* lr_mult4, int root_id, int B, float* trace, float* grad0, int32_t* done,
+                    void* stream) {
+  bool ok = h && pose && beta && root && K && kp2d && conf2d && weights6 && lr_mult4 && trace && done && B > 0 && iters >= 0 &&
+            root_id >= 0 && root_id < 21 && (lr || iters == 0) && (!kp3d == !conf3d) && (!prior_lo == !prior_hi) && (!prior_lo == !prior_w);
+  for (int i = 0; ok && i < 6; ++i) ok = weights6[i] >= 0.f && weights6[i] <= 3.402823466e38f;
+  for (int i = 0; ok && i < 4; ++i) ok = lr_mult4[i] >= 0.f && lr_mult4[i] <= 3.402823466e38f;
+  if (!ok) return fail(HIFIHR_EINVAL, "hifihr_mano_fit: bad argument");
+  HIP_TRY(hifihr::launch_mano_fit(h->dev, pose, beta, root, K, kp2d, conf2d, kp3d, conf3d, prior_lo, prior_hi, prior_w, lr, iters, weights6,
+                                  lr_mult4, root_id, B, trace, grad0, done, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
 int hifihr_mano_joints_fwd(const hifihr_mano_t* h, const float* verts, int B, int root_id, float* joints_rel,
                            float* verts_rel, float* root, void* stream) {
   if (!h || !verts || !joints_rel || B < 0 || root_id >= 21) return fail(HIFIHR_EINVAL, "hifihr_mano_joints_fwd: bad argument");

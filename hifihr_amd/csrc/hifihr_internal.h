@@ -60,6 +60,12 @@ hipError_t launch_mano_joints_fwd(const ManoDev& t, const float* verts, int B, i
 hipError_t launch_mano_joints_bwd(const ManoDev& t, const float* gjoints_rel, const float* gverts_rel,
                                   const float* groot, int B, int root_id, float* gverts, hipStream_t st);
 
+// The keypoint fit (csrc/mano_fit.hip): every iteration of the optimisation in one launch, a workgroup per hand
+hipError_t launch_mano_fit(const ManoDev& t, float* pose, float* beta, float* root, const float* K, const float* kp2d, const float* conf2d,
+                           const float* kp3d, const float* conf3d, const float* prior_lo, const float* prior_hi, const float* prior_w,
+                           const float* lr, int iters, const float* weights6, const float* lr_mult4, int root_id, int B, float* trace,
+                           float* grad0, int32_t* done, hipStream_t st);
+
 // Generic linear-blend skinning (csrc/lbs.hip): any vertex / joint / shape-component count, sparse skin weights.
 constexpr int kLbsMaxJ = 32, kLbsMaxS = 32, kLbsMaxK = 8;
 struct LbsDev {

@@ -177,6 +177,51 @@ def mano_full(handle: ManoLayerHandle, pose, beta, root_id=9, root_xyz=None):
     return _ManoFull.apply(handle, pose, beta, root_id, root_xyz)
 
 
+MANO_FIT_LR = (0.01,) * 51 + (0.005,) * 50 + (0.0025,) * 50         # the reference's schedule (utils/traineval_util.py:525-531)
+_FIT_LR_CACHE = {}
+
+
+def _mano_fit_lr(iters, lr, device):
+    """The step sizes [iters] on the device, built once per (iters, schedule, device)."""
+    if iters == 0:
+        return None
+    if isinstance(lr, torch.Tensor):
+        assert lr.numel() == iters, (lr.shape, iters)
+        return lr.to(device=device, dtype=torch.float32).contiguous()
+    sched = MANO_FIT_LR if lr is None else tuple(float(v) for v in lr)
+    if len(sched) < iters:
+        raise ValueError(f"mano_fit: {iters} iterations need {iters} step sizes, the schedule has {len(sched)}")
+    key = (iters, sched[:iters], str(device))
+    if key not in _FIT_LR_CACHE:
+        _FIT_LR_CACHE[key] = torch.tensor(sched[:iters], dtype=torch.float32, device=device)
+    return _FIT_LR_CACHE[key]
+
+
+def mano_fit(handle: ManoLayerHandle, pose, beta, root, K, kp2d, conf2d, kp3d=None, conf3d=None, *, iters=151, lr=None,
+             weights=(1.0, 1.0, 0.0, 1.0, 0.1, 0.01), lr_mult=(1.0, 1.0, 1.0, 0.1), prior=None, root_id=9, grad0=False):
+    """Fit pose [B,48], beta [B,10] and the root position root [B,3] to 2-D keypoints kp2d [B,21,2] / conf2d [B,21] under K [B,3,3] (and
+    optionally root-relative 3-D keypoints kp3d [B,21,3] / conf3d [B,21]) by `iters` Adam iterations in ONE launch (csrc/mano_fit.hip;
+    include/hifihr.h states the objective).  weights = (w2d, wbone, w3d, wprior, wshape, wpca); lr_mult = one factor per group (root
+    rotation, pose coefficients, shape, root position), 0 freezes a group; prior = (lo, hi, w) device tables [48] on the full axis-angle
+    pose, or None; lr = a schedule of at least `iters` step sizes (default: the reference's 51 x 0.01, 50 x 0.005, 50 x 0.0025).
+    The inputs are detached and left unchanged; this is not an autograd node.
+    -> (pose, beta, root, trace [B,iters+1,8], done int32 [B]); with grad0=True also dE/d(pose, beta, root) [B,61] at the start."""
+    require_cuda(pose, beta, root, K, kp2d, conf2d)
+    B, dev = pose.shape[0], pose.device
+    own = lambda t, *shape: t.detach().reshape(*shape).float().clone(memory_format=torch.contiguous_format)
+    inp = lambda t, *shape: None if t is None else t.detach().reshape(*shape).float().contiguous()
+    pose, beta, root = own(pose, B, 48), own(beta, B, 10), own(root, B, 3)
+    trace = torch.empty(B, iters + 1, 8, device=dev)
+    done = torch.empty(B, dtype=torch.int32, device=dev)
+    g0 = torch.empty(B, 61, device=dev) if grad0 else None
+    pr = None if prior is None else tuple(inp(t, 48) for t in prior)
+    lr_d = _mano_fit_lr(iters, lr, dev)
+    PROFILE.bracket("mano_fit", lambda: handle.lib.mano_fit(handle.h, pose, beta, root, inp(K, B, 3, 3), inp(kp2d, B, 21, 2), inp(conf2d, B, 21),
+                                                            inp(kp3d, B, 21, 3), inp(conf3d, B, 21), pr, lr_d, iters, weights, lr_mult, root_id,
+                                                            trace, g0, done))
+    return (pose, beta, root, trace, done, g0) if grad0 else (pose, beta, root, trace, done)
+
+
 def mano_joints_root_relative(handle: ManoLayerHandle, verts, root_id=9):
     """xyz_from_vertice(verts).permute(1,0,2) + the root-relative step (models_res_nimble.py:153,160-166).
     -> joints_rel [B,21,3], verts_rel [B,778,3], pred_root [B,3]."""

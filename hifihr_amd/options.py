@@ -51,6 +51,11 @@ _DEFAULTS = dict(
     # lambda_bone_direc above): the reference's argparse defaults (options/train_options.py:108, 112), untuned here.  semi_ratio above: the share
     # of the training set whose detections data_dic / FreiHandDeviceCache replace with the ground-truth projection
     lambda_j2d=1e-3, lambda_j2d_de=1e-4,
+    # test-time refinement of the evaluation pass (hifihr_amd/fit.py; one launch per batch, csrc/mano_fit.hip): off by default.  fit_target names
+    # the batch's keypoints to fit to ('open_2dj' with its confidences, or 'j2d_gt' at confidence 1); the six weights multiply the 2-D, bone
+    # direction, 3-D, pose-prior, shape and pose-coefficient terms of include/hifihr.h: starting points, not tuned values
+    fit_keypoints=False, fit_iters=151, fit_target="open_2dj",
+    fit_w_2d=1.0, fit_w_bone=1.0, fit_w_3d=0.0, fit_w_prior=1.0, fit_w_shape=0.1, fit_w_pca=0.01,
     chamfer_metric=False,    # the evaluation pass also reports mesh_chamfer / mesh_al_chamfer (hifihr_amd/evaluate.py Evaluator(chamfer=True))
 )
 

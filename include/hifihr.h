@@ -104,6 +104,48 @@ int hifihr_mano_full_bwd(const hifihr_mano_t* h, const float* pose_d, const floa
                          const float* groot_d, const float* gpose_add_d, const float* gbeta_add_d, int B, int root_id,
                          float* gpose_d, float* gbeta_d, void* stream);
 
+/* Test-time fit of the MANO parameters to 2-D / 3-D keypoints (the reference's mano_fitting, utils/traineval_util.py:505-595, on the
+ * live layer's parametrisation) in ONE launch: one workgroup per hand, every iteration inside the kernel, the hands independent.
+ * In / out (updated in place): pose_d[B][48] (3 root axis-angle + 45 PCA coefficients), beta_d[B][10], root_d[B][3] (absolute position of
+ * the root joint, in the unit of the vertices).  In: K_d[B][3][3], kp2d_d[B][21][2] in pixels, conf2d_d[B][21]; kp3d_d[B][21][3] with
+ * conf3d_d[B][21] (both NULL: no 3-D term); prior_lo_d / prior_hi_d / prior_w_d [48] (all NULL: no pose prior); lr_d[iters] (device);
+ * weights6_host = (w2d, wbone, w3d, wprior, wshape, wpca) and lr_mult4_host = (root rotation, pose coefficients, shape, root position),
+ * host memory.  Out: trace_d[B][iters + 1][8], grad0_d[B][61] (may be NULL), done_d[B].
+ * One iteration, in this order:
+ *   1. the layer (hifihr_mano_lbs_fwd without its centring), joints21 = regress(verts), J_rel = joints21 - joints21[root_id];
+ *   2. X = J_rel + root, p = K X, uv = p_xy / p_z.  A joint with X_z <= 1e-4 is left out of the two 2-D terms for this iteration (its
+ *      confidence counts as 0); K is expected to be a pinhole matrix with last row (0, 0, 1), so that p_z = X_z;
+ *   3. E = w2d e2d + wbone ebone + w3d e3d + wprior eprior + wshape eshape + wpca epca, per hand:
+ *        e2d    = sum_j c_j^2 rho(d_j) / sum_j c_j^2, d = |uv - kp2d|, rho and its d = 0 corner as hifihr_open2d_terms_* (no joint weights:
+ *                 a caller folds them into c); sum c^2 = 0: exactly 0 with a zero gradient
+ *        ebone  = mean over the 20 bones of |vn - von|^2 c_parent c_child, unit vectors v / (|v| + 1e-4), corners as hifihr_open2d_terms_*
+ *        e3d    = sum_j c3_j |J_rel_j - kp3d_j|^2 / sum_j c3_j (sum c3 = 0: exactly 0)
+ *        eprior = (1/48) sum_i w_i (max(fp_i - hi_i, 0) + max(lo_i - fp_i, 0)) on the full axis-angle pose fp = (pose[0:3], mean + PCA);
+ *                 strict comparisons (the reference's torch.where, utils/losses_util.py:139-215): the slope is 0 at a bound
+ *        eshape = mean beta^2, epca = mean pose[3:48]^2
+ *      trace[b][i] = (E, e2d, ebone, e3d, eprior, eshape, epca, mean d_j over the joints with c_j > 0 that were not left out), taken at
+ *      the parameters BEFORE update i; row `iters` is taken at the result;
+ *   4. the hand-derived gradient through projection, root-relative step, joint regression, tips and the layer (grad0 = dE / d(pose, beta,
+ *      root) of iteration 0);
+ *   5. Adam in torch's form, beta = (0.9, 0.999), eps = 1e-8, step t = i + 1: m = m + 0.1 (g - m), v = 0.999 v + 0.001 g^2,
+ *      p -= lr_i mult_g / (1 - 0.9^t) x m / (sqrt(v) / sqrt(1 - 0.999^t) + eps); the moments start at 0 and are KEPT across iterations.
+ *      A DELIBERATE departure: the reference builds a new optimiser every iteration, which resets its moments (each step is then
+ *      lr x sign(g)); that is not reproduced.  A group whose multiplier is 0 is not touched: its bits stay.
+ * Decided behaviours:
+ *   - iters == 0 evaluates only (trace row 0, grad0): the parameters keep the bits they came with.
+ *   - a hand whose E, gradient or updated parameters turn non-finite at iteration i stops there: its parameters are those before update i
+ *     (the inputs for i = 0), done[b] = i, trace row i holds what was evaluated and the rows after it are 0.  Otherwise done[b] = iters.
+ *     The other hands are unaffected.  A non-finite keypoint counts even at confidence 0.
+ *   - deterministic: the same bits on a second call, and for a hand whatever the batch around it (fixed summation orders, no atomics).
+ * Nothing is allocated or synchronised; the call can be captured in a graph.
+ * Refused (HIFIHR_EINVAL, nothing launched or written): B <= 0, iters < 0, root_id outside 0 .. 20, a NULL handle / pose / beta / root /
+ * K / kp2d / conf2d / weights / lr_mult / trace / done, NULL lr with iters > 0, kp3d without conf3d or the reverse, a prior table without
+ * the other two, a weight or multiplier that is negative or not finite. */
+int hifihr_mano_fit(const hifihr_mano_t* h, float* pose_d, float* beta_d, float* root_d, const float* K_d, const float* kp2d_d,
+                    const float* conf2d_d, const float* kp3d_d, const float* conf3d_d, const float* prior_lo_d, const float* prior_hi_d,
+                    const float* prior_w_d, const float* lr_d, int iters, const float* weights6_host, const float* lr_mult4_host,
+                    int root_id, int B, float* trace_d, float* grad0_d, int32_t* done_d, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Generic linear-blend skinning (any mesh size / kinematic tree): the NIMBLE-shaped hand layer.
  * Replaces the skinning step of  self.hand_layer(hand_params, handle_collision=False)  when `hand_model: "nimble"`

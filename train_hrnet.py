@@ -71,6 +71,10 @@ def parse(argv=None):
                     help="the model also emits outputs['re_depth'], the depth map of its hard render with a backward pass to the vertices "
                          "(options: render_depth, lambda_depth, depth_trunc); the loss name 'depth' switches it on by itself, and the "
                          "FreiHAND batches then carry the ground-truth mesh's depth map as 'depths'")
+    ap.add_argument("--fit_keypoints", action="store_true",
+                    help="the evaluation pass refines every MANO prediction against the batch's 2-D keypoints before it is scored (options: "
+                         "fit_keypoints, fit_iters, fit_target 'open_2dj' | 'j2d_gt', fit_w_*): the whole fit is one launch per batch "
+                         "(hifihr_amd/fit.py); rendered images and texture metrics stay the network's")
     ap.add_argument("--max_grad_norm", type=float, default=None, metavar="X",
                     help="gradient guard of the optimizer step (options: max_grad_norm): clip the global L2 norm of the gradient to X and skip a "
                          "step whose gradient holds a NaN / inf, all on the device; 'inf' = the skip alone, 0 = off (the default)")
@@ -111,6 +115,12 @@ KEYPOINT_LOSSES = ("open_2dj", "open_bone_direc", "open_2dj_de", "texture_self",
 def wants_keypoints(args):
     """A requested loss reads the 2-D detections or the texture_con made from their confidences."""
     return any(k in args.losses for k in KEYPOINT_LOSSES)
+
+
+def fit_wants_detections(args):
+    """The evaluation pass refines its predictions against the 2-D detections (fit_keypoints with fit_target 'open_2dj'): the arrays the
+    pass runs on have to carry them."""
+    return bool(getattr(args, "fit_keypoints", False)) and getattr(args, "fit_target", "open_2dj") == "open_2dj"
 
 
 def load_openpose_keypoints(path, n):
@@ -158,6 +168,8 @@ def build_args(cli):
         args.render_depth = True
     if getattr(cli, "max_grad_norm", None) is not None:
         args.max_grad_norm = float(cli.max_grad_norm)
+    if getattr(cli, "fit_keypoints", False):
+        args.fit_keypoints = True
     if cli.lpips_weights:
         args.lpips_weights = list(cli.lpips_weights)
     elif isinstance(getattr(args, "lpips_weights", None), str):        # a JSON may name one file
@@ -174,14 +186,17 @@ def build_args(cli):
     return args
 
 
-def load_or_make_dataset(cli, model, device, keypoints=False):
+def load_or_make_dataset(cli, model, device, keypoints=False, eval_keypoints=False):
     """-> (train arrays, eval arrays) as dicts of numpy arrays: images u8 [n,H,W,3], masks u8 [n,H,W], Ks, joints, verts.  The training
     arrays also hold open_2dj [n,21,2] / open_2dj_con when the npz or --openpose_keypoints carries them, or -- synthetic set, keypoints=True --
-    seeded ones (synth.make_batch(open_2dj=True))."""
+    seeded ones (synth.make_batch(open_2dj=True)).  eval_keypoints (the evaluation pass fits to detections): the eval arrays keep theirs too,
+    the npz's eval_open_2dj / eval_open_2dj_con or the synthetic set's rows behind the cut; without it they are as before."""
     if cli.freihand_cache:
         z = np.load(cli.freihand_cache)
         tr = {k: z[k] for k in ("images", "masks", "Ks", "joints", "verts")}
         ev = {k: z["eval_" + k] for k in tr} if "eval_images" in z else None
+        if ev is not None and eval_keypoints and "eval_open_2dj" in z and "eval_open_2dj_con" in z:
+            ev["open_2dj"], ev["open_2dj_con"] = z["eval_open_2dj"], z["eval_open_2dj_con"]
         if "open_2dj" in z and "open_2dj_con" in z:
             tr["open_2dj"], tr["open_2dj_con"] = z["open_2dj"], z["open_2dj_con"]
         if getattr(cli, "openpose_keypoints", None):
@@ -207,7 +222,7 @@ def load_or_make_dataset(cli, model, device, keypoints=False):
     cut = cli.synthetic_size
     if getattr(cli, "openpose_keypoints", None):
         full["open_2dj"], full["open_2dj_con"] = load_openpose_keypoints(cli.openpose_keypoints, len(full["images"]))
-    return {k: v[:cut] for k, v in full.items()}, {k: v[cut:] for k, v in full.items() if not k.startswith("open_2dj")}
+    return {k: v[:cut] for k, v in full.items()}, {k: v[cut:] for k, v in full.items() if eval_keypoints or not k.startswith("open_2dj")}
 
 
 def train_ho3d(cli, args, model, loss_func, opt, sched, reducer, current_epoch, rank, world, device, say):
@@ -360,12 +375,27 @@ def make_evaluator(args, device):
     return Evaluator(lpips_fn=_LPIPS[key], benchmark=bench, chamfer=cham, point_mesh=p2s, depth=dep)
 
 
+def fit_keypoints_log(args, refined):
+    """With the option fit_keypoints on: say whether the summary that follows describes refined predictions."""
+    if not getattr(args, "fit_keypoints", False):
+        return
+    from hifihr_amd.fit import fit_options
+    opt = fit_options(args)
+    if refined:
+        print(f"[train_hrnet] fit_keypoints: the summary describes predictions REFINED by {opt['iters']} fit iterations against "
+              f"'{opt['target']}' in {refined} batches (joints, vertices and j2d; rendered images and texture metrics are the network's)")
+    else:
+        print(f"[train_hrnet] fit_keypoints: no batch carried '{opt['target']}'; the summary describes the network's own predictions")
+
+
 def run_evaluation_ho3d(model, cache, args, device, epoch):
     """The reference's HO-3D evaluation pass (train_hrnet.py:55-64 the evaluation queries, :124-136 joints back in the HO-3D order and
     OpenGL axes, :286-293 `pred.json` for the challenge server; texture metrics when rendering): no ground truth exists for this split,
     the product is the dump.  -> (path, n, texture metrics)."""
+    from hifihr_amd.fit import refine_outputs
     from hifihr_amd.traineval import data_dic
     ev = make_evaluator(args, device)
+    refined = 0
     model.eval()
     with torch.no_grad():
         for lo in range(0, cache.n, args.val_batch):
@@ -373,28 +403,48 @@ def run_evaluation_ho3d(model, cache, args, device, epoch):
             zeros = np.zeros((len(idx), 2), np.float32)
             ex = data_dic(cache.batch(idx, center_noise=zeros, scale_noise=np.ones(len(idx), np.float32)), "HO3D", "evaluation", args, device=device)
             out = model("HO3D", False, ex["imgs"], Ks=ex["Ps"], root_xyz=ex["root_xyz"].unsqueeze(1))
+            if getattr(args, "fit_keypoints", False):
+                out, did = refine_outputs(model, out, ex, args, root_xyz=ex["root_xyz"], root_id=0)
+                refined += did
             ev.collect(out, ex, "HO3D", render=args.render)
     model.train()
+    fit_keypoints_log(args, refined)
     path = os.path.join(args.pred_output, "test", str(epoch), "pred.json")                     # train_hrnet.py:286-290
     n, _ = ev.dump(path)
     return path, n, ev.summary()
 
 
-def run_evaluation(model, cache, arrays, args, device):
+def evaluation_examples(cache, idx, args, device):
+    """The `examples` of one FreiHAND evaluation batch (no rotation).  When the pass fits to detections and the cache holds them, the
+    batch comes from cache.batch_examples, the one-call form of the same dict that also carries open_2dj / open_2dj_con (cache.batch does
+    not); otherwise exactly the two calls made before."""
     from hifihr_amd.traineval import data_dic
+    rots = np.zeros(len(idx))
+    if fit_wants_detections(args) and getattr(cache, "open_2dj", None) is not None:
+        return cache.batch_examples(idx, rots=rots)
+    return data_dic(cache.batch(idx, rots=rots), "FreiHand", "training", args, device=device)
+
+
+def run_evaluation(model, cache, arrays, args, device):
+    from hifihr_amd.fit import refine_outputs
     ev = make_evaluator(args, device)
+    refined = 0
     model.eval()
     n = cache.n
     with torch.no_grad():
         for lo in range(0, n, args.val_batch):
             idx = torch.arange(lo, min(n, lo + args.val_batch))
-            ex = data_dic(cache.batch(idx, rots=np.zeros(len(idx))), "FreiHand", "training", args, device=device)
+            ex = evaluation_examples(cache, idx, args, device)
             if wants_depths(args) and args.render:
                 attach_mesh_depths(ex, model)
             root = ex["joints"][:, args.ROOT, :].unsqueeze(1)
             out = model("FreiHand", False, ex["imgs"], Ks=ex["Ps"], root_xyz=root)
+            if getattr(args, "fit_keypoints", False):
+                out, did = refine_outputs(model, out, ex, args, root_xyz=root)
+                refined += did
             ev.collect(out, ex, "FreiHand", render=args.render)
     model.train()
+    fit_keypoints_log(args, refined)
     return ev.summary(arrays["joints"], arrays["verts"], root_id=args.ROOT)
 
 
@@ -456,17 +506,24 @@ def main(argv=None):
     dat_name = cli.dataset
     if dat_name == "HO3D":
         return train_ho3d(cli, args, model, loss_func, opt, sched, reducer, current_epoch, rank, world, device, say)
-    train_arrays, eval_arrays = load_or_make_dataset(cli, model, device, keypoints=wants_keypoints(args))
+    fit_det = fit_wants_detections(args)
+    train_arrays, eval_arrays = load_or_make_dataset(cli, model, device, keypoints=wants_keypoints(args) or fit_det, eval_keypoints=fit_det)
     if wants_keypoints(args) and "open_2dj" not in train_arrays:
         raise SystemExit(f"[train_hrnet] the losses {[k for k in args.losses if k in KEYPOINT_LOSSES]} need 2-D detections: give "
                          "--openpose_keypoints <json>, or open_2dj / open_2dj_con in the --freihand_cache npz")
+    has_eval = eval_arrays is not None and len(eval_arrays["images"]) > 0
+    if fit_det and "open_2dj" not in (eval_arrays if has_eval else train_arrays):
+        raise SystemExit("[train_hrnet] fit_keypoints with fit_target 'open_2dj' needs 2-D detections for the samples the evaluation pass runs "
+                         "on: give " + ("eval_open_2dj / eval_open_2dj_con" if has_eval else "open_2dj / open_2dj_con (or --openpose_keypoints)") +
+                         " in the --freihand_cache npz, or set fit_target to 'j2d_gt'")
     cache = FreiHandDeviceCache(train_arrays["images"], train_arrays["masks"], train_arrays["Ks"], train_arrays["joints"],
                                 train_arrays["verts"], device=device, open_2dj=train_arrays.get("open_2dj"),
                                 open_2dj_con=train_arrays.get("open_2dj_con"), semi_ratio=getattr(args, "semi_ratio", None))
     eval_cache = None
     if eval_arrays is not None and len(eval_arrays["images"]):
         eval_cache = FreiHandDeviceCache(eval_arrays["images"], eval_arrays["masks"], eval_arrays["Ks"], eval_arrays["joints"],
-                                         eval_arrays["verts"], device=device)
+                                         eval_arrays["verts"], device=device, open_2dj=eval_arrays.get("open_2dj"),
+                                         open_2dj_con=eval_arrays.get("open_2dj_con"))       # (detections only when the pass fits to them)
     say(f"[train_hrnet] {cache.n} training samples resident on {device}; world {world}; encoder {args.pretrain}; losses {args.losses}")
 
     if "evaluation" in args.mode:
