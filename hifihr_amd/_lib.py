@@ -565,6 +565,35 @@ class HifihrLib:
         self._run("hifihr_ho3d_batch", img_rgbx, hand_mask, Ks, uv21, xyz21, FH, FW, packed, B, out_size, ws, _nbytes(ws), g("img_crop"),
                   g("hand_mask_crop"), g("K_crop"), g("uv21_crop"), g("xyz21"))
 
+    def ho3d_keypoints(self, open_2dj, open_2dj_con, packed, B, out_size, out_open_2dj, out_con):
+        """The detections of an HO-3D batch through its crop window (hifihr_ho3d_keypoints): cache open_2dj [n,21,2] / open_2dj_con [n,21] or
+        [n,21,1], packed = hifihr_ho3d_batch's.  Outputs [B,21,2], [B,21] or [B,21,1]; either may be None."""
+        n = open_2dj.shape[0]
+        assert open_2dj.shape[1:] == (21, 2) and open_2dj_con.numel() == n * 21 and packed.numel() >= 8 * B, (open_2dj.shape, open_2dj_con.shape)
+        for t, numel in ((out_open_2dj, B * 42), (out_con, B * 21)):
+            assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == numel)
+        self._run("hifihr_ho3d_keypoints", open_2dj, open_2dj_con, n, packed, B, out_size, out_open_2dj, out_con)
+
+    def ho3d_depth_crop(self, depth_u16, packed, B, out_size, depth_scale, out_depth):
+        """The metric depth of an HO-3D batch through its crop box (hifihr_ho3d_depth_crop): cache depth_u16 [n,FH,FW] (uint16, or int16
+        holding the same bits), packed = hifihr_ho3d_batch's; out_depth fp32 [B,S,S]."""
+        n, FH, FW = depth_u16.shape
+        assert depth_u16.element_size() == 2 and not depth_u16.is_floating_point() and packed.numel() >= 8 * B, depth_u16.dtype
+        assert out_depth.dtype == torch.float32 and tuple(out_depth.shape) == (B, out_size, out_size)
+        self._run("hifihr_ho3d_depth_crop", depth_u16, n, FH, FW, packed, B, out_size, depth_scale, out_depth)
+
+    def depth_points(self, depths, K, mask, draws, origin, points, count, index=None):
+        """hifihr_depth_points: depths fp32 [B,H,W], K [B,3,3], mask [B,H,W] float32 / int64 or None, draws [B,P], origin [B,3] or None;
+        points fp32 [B,P,3], count int32 [B], index int32 [B,P] or None."""
+        B, H, W = depths.shape
+        P = draws.shape[1]
+        assert tuple(K.shape) == (B, 3, 3) and tuple(draws.shape) == (B, P) and tuple(points.shape) == (B, P, 3) and tuple(count.shape) == (B,)
+        assert mask is None or (mask.dtype in (torch.float32, torch.int64) and mask.numel() == B * H * W), None if mask is None else (mask.dtype, mask.shape)
+        assert origin is None or origin.numel() == B * 3
+        assert index is None or tuple(index.shape) == (B, P)
+        self._run("hifihr_depth_points", depths, K, mask, int(mask is not None and mask.dtype == torch.int64), draws, origin, B, H, W, P, points,
+                  count, index)
+
     def freihand_augment(self, img_rgbx, mask, idx, coef_fix, out_img, out_mask):
         """img_rgbx int32/uint8x4 [n,H,W], mask uint8 [n,H,W] (either None with its output), idx int32 [B], coef_fix int32 [B,6]."""
         ref = img_rgbx if img_rgbx is not None else mask

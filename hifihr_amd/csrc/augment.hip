@@ -437,6 +437,67 @@ hipError_t launch_ho3d_batch(const uint32_t* img, const uint8_t* mask, const flo
 
 size_t ho3d_workspace_bytes(int B, int out_size) { return (size_t)B * 4 * out_size * (2 + ho_taps(out_size)) * sizeof(int); }
 
+// The 2-D detections of an HO-3D batch through its crop window (reference data/dataset.py:1199-1203): idx and the window come from the
+// packed buffer of launch_ho3d_batch, the arithmetic is ho3d_meta_kernel's for uv21_crop -- a subtraction, a product and a sum, each
+// rounded to float32 -- so detections equal to uv21 give uv21_crop's bits.  An index outside the cache gives that sample zeros.
+struct Ho3dKeypoints {
+  const float *det, *con;                        // cache: [n][21][2], [n][21]
+  const int* idx;
+  const float* win;                              // [B][3]: crop centre (u, v), scale
+  int n;
+  float *odet, *ocon;
+  float half_res;                                // inp_res // 2
+};
+__global__ __launch_bounds__(64) void ho3d_keypoints_kernel(Ho3dKeypoints k) {
+  const int b = blockIdx.x, t = threadIdx.x, id = k.idx[b];
+  if (t >= 21) return;
+  const bool ok = id >= 0 && id < k.n;
+  const float cu = k.win[b * 3], cv = k.win[b * 3 + 1], s = k.win[b * 3 + 2];
+  if (k.odet) {
+    k.odet[((size_t)b * 21 + t) * 2] = ok ? (k.det[((size_t)id * 21 + t) * 2] - cu) * s + k.half_res : 0.f;
+    k.odet[((size_t)b * 21 + t) * 2 + 1] = ok ? (k.det[((size_t)id * 21 + t) * 2 + 1] - cv) * s + k.half_res : 0.f;
+  }
+  if (k.ocon) k.ocon[(size_t)b * 21 + t] = ok ? k.con[(size_t)id * 21 + t] : 0.f;
+}
+
+hipError_t launch_ho3d_keypoints(const float* det, const float* con, int n, const int* packed, int B, int out_size, float* odet, float* ocon,
+                                 hipStream_t st) {
+  if (B <= 0 || n <= 0 || out_size <= 0) return hipErrorInvalidValue;
+  const Ho3dKeypoints k{det, con, packed, reinterpret_cast<const float*>(packed + 5 * B), n, odet, ocon, (float)(out_size / 2)};
+  hipLaunchKernelGGL(ho3d_keypoints_kernel, dim3(B), dim3(64), 0, st, k);
+  return hipGetLastError();
+}
+
+// The metric depth of an HO-3D batch through the same crop box: Pillow's Image.crop(box).resize((S, S), NEAREST) of the 16-bit frame --
+// output pixel (r, q) reads the source position (y0 + floor((r + 0.5) (y1 - y0) / S), x0 + floor((q + 0.5) (x1 - x0) / S)), the division and
+// the floor in double -- times the metres per unit, one float32 product.  A depth image is gathered, never averaged.  One thread per output
+// pixel.  0 where the position lies outside the frame, for an index outside the cache and for a box that launch_ho3d_batch gives zeros for.
+__global__ __launch_bounds__(256) void ho3d_depth_crop_kernel(const uint16_t* __restrict__ depth, int n, const int* __restrict__ idx,
+                                                             const int* __restrict__ boxes, int FH, int FW, int out_size, float scale,
+                                                             float* __restrict__ out) {
+  const int b = blockIdx.y;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= out_size * out_size) return;
+  const int r = p / out_size, q = p - r * out_size;
+  const int* box = boxes + b * 4;
+  const int bw = box[2] - box[0], bh = box[3] - box[1], id = idx[b];
+  float v = 0.f;
+  if (id >= 0 && id < n && bw > 0 && bh > 0 && bw <= kHoMaxWindow && bh <= kHoMaxWindow) {
+    const int sx = box[0] + (int)floor(((double)q + 0.5) * (double)bw / (double)out_size);
+    const int sy = box[1] + (int)floor(((double)r + 0.5) * (double)bh / (double)out_size);
+    if (sx >= 0 && sx < FW && sy >= 0 && sy < FH) v = (float)depth[((size_t)id * FH + sy) * FW + sx] * scale;
+  }
+  out[(size_t)b * out_size * out_size + p] = v;
+}
+
+hipError_t launch_ho3d_depth_crop(const uint16_t* depth, int n, int FH, int FW, const int* packed, int B, int out_size, float scale, float* out,
+                                  hipStream_t st) {
+  if (B <= 0 || n <= 0 || FH <= 0 || FW <= 0 || out_size <= 0 || out_size > 256) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ho3d_depth_crop_kernel, dim3((out_size * out_size + 255) / 256, B), dim3(256), 0, st, depth, n, packed, packed + B, FH, FW,
+                     out_size, scale, out);
+  return hipGetLastError();
+}
+
 hipError_t launch_freihand_augment(const uint32_t* img, const uint8_t* mask, const int* idx, const int* coef, int B, int H, int W,
                                    float* out_img, float* out_mask, hipStream_t st) {
   if (B <= 0 || H <= 0 || W <= 0 || (long)H * W >= (1L << 24)) return hipErrorInvalidValue;      // (the entry refuses these first)

@@ -1940,4 +1940,30 @@ int hifihr_ho3d_batch(const uint32_t* img_rgbx, const uint8_t* hand_mask, const 
   return HIFIHR_OK;
 }
 
+int hifihr_ho3d_keypoints(const float* open_2dj, const float* open_2dj_con, int n, const int* packed, int B, int out_size,
+                          float* out_open_2dj, float* out_con, void* stream) {
+  if (!open_2dj || !open_2dj_con || !packed || n <= 0 || B <= 0 || out_size <= 0 || out_size > 256 || (!out_open_2dj && !out_con))
+    return fail(HIFIHR_EINVAL, "hifihr_ho3d_keypoints: bad argument (out_size <= 256)");
+  HIP_TRY(hifihr::launch_ho3d_keypoints(open_2dj, open_2dj_con, n, packed, B, out_size, out_open_2dj, out_con, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_ho3d_depth_crop(const uint16_t* depth_u16, int n, int FH, int FW, const int* packed, int B, int out_size, float depth_scale,
+                           float* out_depth, void* stream) {
+  if (!depth_u16 || !packed || !out_depth || n <= 0 || B <= 0 || FH <= 0 || FW <= 0 || out_size <= 0 || out_size > 256)
+    return fail(HIFIHR_EINVAL, "hifihr_ho3d_depth_crop: bad argument (out_size <= 256)");
+  HIP_TRY(hifihr::launch_ho3d_depth_crop(depth_u16, n, FH, FW, packed, B, out_size, depth_scale, out_depth, (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
+int hifihr_depth_points(const float* depths, const float* K, const void* mask, int mask_i64, const float* draws, const float* origin, int B,
+                        int H, int W, int P, float* out_points, int32_t* out_count, int32_t* out_index, void* stream) {
+  if (!depths || !K || !draws || !out_points || !out_count || B <= 0 || P <= 0 || H <= 0 || W <= 0 ||
+      (long long)H * W > hifihr::kDepthPointsMaxPixels)
+    return fail(HIFIHR_EINVAL, "hifihr_depth_points: bad argument (H * W <= %d)", hifihr::kDepthPointsMaxPixels);
+  HIP_TRY(hifihr::launch_depth_points(depths, K, mask, mask_i64, draws, origin, B, H, W, P, out_points, out_count, out_index,
+                                      (hipStream_t)stream));
+  return HIFIHR_OK;
+}
+
 }  // extern "C"

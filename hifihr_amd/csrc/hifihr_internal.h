@@ -496,6 +496,15 @@ size_t ho3d_workspace_bytes(int B, int out_size);
 hipError_t launch_ho3d_batch(const uint32_t* img, const uint8_t* mask, const float* Ks, const float* uv21, const float* xyz21, int FH, int FW,
                              const int* packed, int B, int out_size, void* ws, float* out_img, float* out_mask, float* out_K,
                              float* out_uv, float* out_xyz, hipStream_t st);
+// the HO-3D extras behind launch_ho3d_batch (augment.hip): detections through the crop window, the 16-bit depth frame through the crop box
+hipError_t launch_ho3d_keypoints(const float* det, const float* con, int n, const int* packed, int B, int out_size, float* odet, float* ocon,
+                                 hipStream_t st);
+hipError_t launch_ho3d_depth_crop(const uint16_t* depth, int n, int FH, int FW, const int* packed, int B, int out_size, float scale, float* out,
+                                  hipStream_t st);
+// a fixed-size point cloud from a depth map (depth_points.hip): HIFIHR_DEPTH_POINTS_MAX_PIXELS of include/hifihr.h
+constexpr int kDepthPointsMaxPixels = 512 * 512;
+hipError_t launch_depth_points(const float* depths, const float* K, const void* mask, int mask_i64, const float* draws, const float* origin,
+                               int B, int H, int W, int P, float* points, int* count, int* index, hipStream_t st);
 hipError_t launch_procrustes(const float* pred, const float* gt, int B, int N, float* aligned, float* err_sum, hipStream_t st);
 // benchmark metrics (eval.hip): the thresholds travel by value as kernel arguments, validated on the host
 constexpr int kHistMaxT = 128, kFscoreMaxT = 8;

@@ -315,6 +315,16 @@ def ho3d_crop_windows(uv21, center_noise, scale_noise, inp_res=224, img_wh=(640.
 
 
 HO3D_MAX_WINDOW = 800          # HIFIHR_HO3D_MAX_WINDOW (include/hifihr.h): the longest box edge hifihr_ho3d_batch resamples
+HO3D_DEPTH_SCALE = 0.00012498664727900177      # metres per unit of an HO-3D depth image (reference data/dataset.py:1040)
+
+
+def ho3d_depth_to_u16(rgb_u8):
+    """An HO-3D depth PNG as decoded to [..., 3] uint8 (R, G, B) -> the 16-bit depth it encodes, `rgb[..., 2] + 256 * rgb[..., 1]`
+    (reference data/dataset.py:1041), as uint16: what `HO3DDeviceCache(depth_u16=...)` keeps on the device.  Host helper (numpy)."""
+    rgb = np.asarray(rgb_u8)
+    if rgb.dtype != np.uint8 or rgb.shape[-1] < 3:
+        raise ValueError(f"ho3d_depth_to_u16: expected uint8 [..., 3], got {rgb.dtype} {rgb.shape}")
+    return rgb[..., 2].astype(np.uint16) + np.uint16(256) * rgb[..., 1].astype(np.uint16)
 
 
 class HO3DDeviceCache:
@@ -322,12 +332,23 @@ class HO3DDeviceCache:
     data/dataset.py:1023-1215).  images_u8 [n,480,640,3], hand_masks_u8 [n,480,640] (channel 0 of the reference's mask image, 0 / 255),
     Ks [n,3,3] (camMat . cam_extr as the dataset forms it), xyz21 [n,21,3].  `batch(idxs)` returns the sample dict the HO3D branch of
     `traineval.data_dic` reads -- img_crop, hand_mask_crop, K_crop, uv21_crop, xyz21 -- with every tensor on the device: one staged
-    copy of 32 bytes per sample and three launches (hifihr_ho3d_batch); pixels bit-exact with the reference's PIL path."""
+    copy of 32 bytes per sample and three launches (hifihr_ho3d_batch); pixels bit-exact with the reference's PIL path.
+    Opt-in, each ONE more launch on the same staged copy: detections (`open_2dj_crop`, `open_2dj_con`: hifihr_ho3d_keypoints) and the
+    metric depth (`depth_crop`: hifihr_ho3d_depth_crop).  A cache built without them returns the dict above from the launches above."""
 
-    def __init__(self, images_u8, hand_masks_u8, Ks, xyz21, device="cuda", inp_res=224, bboxes=None, root_xyz=None):
+    KEYPOINT_KEYS = ("open_2dj_crop", "open_2dj_con")      # only from a cache that was given detections
+    DEPTH_KEYS = ("depth_crop",)                           # only from a cache that was given depth frames
+
+    def __init__(self, images_u8, hand_masks_u8, Ks, xyz21, device="cuda", inp_res=224, bboxes=None, root_xyz=None, open_2dj=None,
+                 open_2dj_con=None, depth_u16=None, depth_scale=HO3D_DEPTH_SCALE):
         """bboxes [n,2,2] ((x0, y0), (x1, y1)) + root_xyz [n,3]: the EVALUATION split, which carries a hand bounding box and the root joint
         instead of 21 joints (dataset.py:1071-1080): the crop window is then formed from the box corners, and `batch` also returns
-        `root_xyz` with y / z negated as those lines do."""
+        `root_xyz` with y / z negated as those lines do.
+        open_2dj [n,21,2] (pixels of the stored frame, FreiHAND joint order as data_dic assumes) + open_2dj_con [n,21] or [n,21,1]: 2-D
+        detections; `batch` then also returns open_2dj_crop [B,21,2] = (open_2dj - centre) * scale + inp_res // 2 (dataset.py:1199-1203) and
+        open_2dj_con (the cache's shape per sample), bit for bit.
+        depth_u16 [n,H,W] uint16 (`ho3d_depth_to_u16` of the depth PNGs) with depth_scale metres per unit: `batch` then also returns
+        depth_crop [B,S,S] float32 in metres, the frame through the crop box with NEAREST resampling (include/hifihr.h)."""
         images_u8 = torch.as_tensor(images_u8)
         n, H, W, _ = images_u8.shape
         rgbx = torch.zeros(n, H, W, 4, dtype=torch.uint8)
@@ -347,6 +368,21 @@ class HO3DDeviceCache:
         self.n, self.H, self.W, self.device, self.inp_res = n, H, W, torch.device(device), inp_res
         self.lib = get_lib()
         self._ws = None
+        if (open_2dj is None) != (open_2dj_con is None):
+            raise ValueError("HO3DDeviceCache: open_2dj and open_2dj_con come together (the detections and their confidences)")
+        self.open_2dj = self.open_2dj_con = self.depth_u16 = None
+        if open_2dj is not None:
+            det, con = torch.as_tensor(open_2dj, dtype=torch.float32), torch.as_tensor(open_2dj_con, dtype=torch.float32)
+            if tuple(det.shape) != (n, 21, 2) or tuple(con.shape) not in ((n, 21), (n, 21, 1)):
+                raise ValueError(f"HO3DDeviceCache: open_2dj {tuple(det.shape)} / open_2dj_con {tuple(con.shape)} for {n} frames: expected "
+                                 f"[{n},21,2] and [{n},21] or [{n},21,1]")
+            self.open_2dj, self.open_2dj_con = det.contiguous().to(device), con.contiguous().to(device)
+        if depth_u16 is not None:
+            d = depth_u16 if torch.is_tensor(depth_u16) else torch.from_numpy(np.ascontiguousarray(depth_u16))
+            if d.dtype != torch.uint16 or tuple(d.shape) != (n, H, W):
+                raise ValueError(f"HO3DDeviceCache: depth_u16 {d.dtype} {tuple(d.shape)}: expected uint16 [{n},{H},{W}] (ho3d_depth_to_u16)")
+            self.depth_u16, self.depth_scale = d.contiguous().to(device), float(depth_scale)
+            require_cuda(self.depth_u16)
 
     _RING, _GROUP = FreiHandDeviceCache._RING, FreiHandDeviceCache._GROUP
     _stage = FreiHandDeviceCache._stage
@@ -383,6 +419,13 @@ class HO3DDeviceCache:
                "K_crop": torch.empty(B, 3, 3, device=dev), "uv21_crop": torch.empty(B, 21, 2, device=dev),
                "xyz21": torch.empty(B, 21, 3, device=dev)}
         self.lib.ho3d_batch(self.images, self.masks, self.Ks, self.uv21, self.xyz21, packed, B, S, self._ws, out)
+        if self.open_2dj is not None:
+            out["open_2dj_crop"] = torch.empty(B, 21, 2, device=dev)
+            out["open_2dj_con"] = torch.empty((B,) + tuple(self.open_2dj_con.shape[1:]), device=dev)
+            self.lib.ho3d_keypoints(self.open_2dj, self.open_2dj_con, packed, B, S, out["open_2dj_crop"], out["open_2dj_con"])
+        if self.depth_u16 is not None:
+            out["depth_crop"] = torch.empty(B, S, S, device=dev)
+            self.lib.ho3d_depth_crop(self.depth_u16, packed, B, S, self.depth_scale, out["depth_crop"])
         self._release(slot)
         if self.root_xyz is not None:
             out["root_xyz"] = self.root_xyz[idxs.to(self.device)]

@@ -676,6 +676,40 @@ def chamfer_sums(x, y):
         return _chamfer_run(x.detach(), y.detach(), 1.0, 1.0)[6]
 
 
+@torch.no_grad()
+def depth_points(depths, K, num_points, mask=None, draws=None, origin=None, generator=None, return_index=False):
+    """A fixed-size point cloud from a depth map, the reference's utils/fh_utils.py batch_depth2pc as ONE launch (csrc/depth_points.hip,
+    include/hifihr.h "Depth map to points") -> (points [B, P, 3] f32, count int32 [B]).
+    depths [B, H, W] or [B, 1, H, W] (0 = no measurement, H W <= 512 x 512); K [B, 3, 3] (or [3, 3]) the intrinsics of THAT map; mask
+    [B, H, W] / [B, 1, H, W] (float32 or int64 as they are, any other type as float32) or None; P = num_points draws per sample, uniform and
+    with replacement among the pixels with depth > 0 and mask != 0 in row-major order: draws [B, P] in [0, 1) picks pixel
+    min(n - 1, floor(draw * n)); None: torch.rand on the device from `generator`.  origin [B, 3] / [B, 1, 3] is subtracted (the root, for the
+    root-relative target of `chamfer` / `point_mesh`).  Each point is K^-1 . ((q + 0.5) d, (r + 0.5) d, d) in double, rounded once.
+    count[b] = the sample's valid pixels; a sample without one gets zeros (count 0).  No gradient: the points are a target.
+    return_index: also the chosen pixels int32 [B, P] (r W + q; -1 without a valid pixel)."""
+    require_cuda(depths, K, mask, draws, origin)
+    if depths.dim() == 4:
+        depths = depths[:, 0]
+    B, H, W = depths.shape
+    P = int(num_points)
+    dev = depths.device
+    depths = depths.contiguous() if depths.dtype == torch.float32 else depths.float().contiguous()
+    K = K.float().expand(B, 3, 3).contiguous()
+    if mask is not None:
+        mask = _mask_arg(mask[:, 0] if mask.dim() == 4 else mask)
+    if draws is None:
+        # (a host generator draws on the host: one copy more, the same draws on every device)
+        draws = torch.rand(B, P, device=dev if generator is None else generator.device, generator=generator).to(dev)
+    draws = draws.float().contiguous()
+    if origin is not None:
+        origin = origin.float().reshape(B, 3).contiguous()
+    points = torch.empty(B, P, 3, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    index = torch.empty(B, P, dtype=torch.int32, device=dev) if return_index else None
+    PROFILE.bracket("depth_points", lambda: get_lib().depth_points(depths, K, mask, draws, origin, points, count, index))
+    return (points, count, index) if return_index else (points, count)
+
+
 def point_mesh_tables_of(faces, V):
     """-> (faces int32 [F, 3] contiguous, v2c_off int32 [V + 1], v2c_corner int32 [3 F]) on the faces' device: the vertex -> corner table of
     hifihr_point_mesh_bwd (include/hifihr.h "Point-to-mesh distance"), built on first use and kept per faces tensor

@@ -57,6 +57,10 @@ _DEFAULTS = dict(
     fit_keypoints=False, fit_iters=151, fit_target="open_2dj",
     fit_w_2d=1.0, fit_w_bone=1.0, fit_w_3d=0.0, fit_w_prior=1.0, fit_w_shape=0.1, fit_w_pca=0.01,
     chamfer_metric=False,    # the evaluation pass also reports mesh_chamfer / mesh_al_chamfer (hifihr_amd/evaluate.py Evaluator(chamfer=True))
+    # P > 0: traineval.data_dic builds examples['chamfer_points'] [B,P,3], the target of "chamfer" / "point_mesh", from examples['depths']
+    # (hifihr_amd/ops.py depth_points: P draws with replacement among the depth pixels under the hand mask, back-projected, root-relative).
+    # The reference's batch_depth2pc draws 1000.  0: off; a caller's own chamfer_points always wins
+    depth_points=0,
 )
 
 # lambda values of reference config/FreiHAND/full_rhd_freihand.json, used by the

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 from . import ops
@@ -136,24 +137,29 @@ def to_ho3d_sample(sample: dict, crop: int = 448) -> dict:
     return out
 
 
-def make_ho3d_frames(mano_handle, renderer, n: int, first_index: int = 0, device="cuda", frame_hw=(480, 640), images="noise", depth=False):
+def make_ho3d_frames(mano_handle, renderer, n: int, first_index: int = 0, device="cuda", frame_hw=(480, 640), images="noise", depth=False,
+                     open_2dj=False):
     """Synthetic HO-3D-shaped raw frames for `data.HO3DDeviceCache`: the 224 x 224 synthetic hand of `make_batch` pasted into a 480 x 640
     frame at a per-sample offset (grey background), the intrinsics moved with it, everything in the HO-3D loader's conventions
     (reference data/dataset.py:1065-1068, 1093: `Ks = camMat . cam_extr` with the OpenGL flip, joints in the HO-3D order with y / z negated --
     what utils/traineval_util.py:156-201 undoes).  -> images_u8 [n,480,640,3], hand_masks_u8 [n,480,640], Ks [n,3,3], xyz21 [n,21,3] (host).
-    depth: also "depths" f32 [n,480,640], the hand's depth map pasted at the same offset (0 elsewhere).  `data.HO3DDeviceCache` does not
-    crop a depth frame: a caller that wants the term crops it with the boxes it uses."""
+    depth: also "depths" f32 [n,480,640], the hand's depth map pasted at the same offset (0 elsewhere), and "depth_u16" uint16 [n,480,640] =
+    rint(depths / data.HO3D_DEPTH_SCALE) clipped to 65535, the dataset's 16-bit encoding that `data.HO3DDeviceCache(depth_u16=...)` crops.
+    open_2dj: also "open_2dj" f32 [n,21,2] / "open_2dj_con" f32 [n,21,1], the seeded detections of `make_batch(open_2dj=True)` -- the projected
+    joints in FreiHAND order + 2 px of noise, about one joint in ten missed -- moved into the frame with the hand.
+    Without either the return is unchanged."""
     from .traineval import Frei2HO3D
     FH, FW = frame_hw
     imgs = torch.full((n, FH, FW, 3), 96, dtype=torch.uint8)
     masks = torch.zeros(n, FH, FW, dtype=torch.uint8)
     Ks, xyz = torch.zeros(n, 3, 3), torch.zeros(n, 21, 3)
     depths = torch.zeros(n, FH, FW) if depth else None
+    det, con = (torch.zeros(n, 21, 2), torch.zeros(n, 21, 1)) if open_2dj else (None, None)
     flip = torch.tensor([1.0, -1.0, -1.0])
     step = 32
     for lo in range(0, n, step):
         m = min(step, n - lo)
-        b = make_batch(mano_handle, renderer, m, first_index=first_index + lo, device=device, images=images, depth=depth)
+        b = make_batch(mano_handle, renderer, m, first_index=first_index + lo, device=device, images=images, depth=depth, open_2dj=open_2dj)
         im = (b["trans_images"].clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu()
         mk = (b["trans_masks"][:, 0] > 0.5).to(torch.uint8).mul(255).cpu()
         K, J = b["trans_Ks"].cpu(), b["trans_joints"].cpu()
@@ -164,10 +170,17 @@ def make_ho3d_frames(mano_handle, renderer, n: int, first_index: int = 0, device
             masks[lo + i, oy:oy + 224, ox:ox + 224] = mk[i]
             if depth:
                 depths[lo + i, oy:oy + 224, ox:ox + 224] = b["depths"][i]
+            if open_2dj:
+                det[lo + i] = b["trans_open_2dj"][i] + torch.tensor([float(ox), float(oy)])
+                con[lo + i] = b["open_2dj_con"][i]
             Kf = K[i].clone(); Kf[0, 2] += ox; Kf[1, 2] += oy
             Ks[lo + i] = Kf * flip.view(1, 3)
             xyz[lo + i] = Frei2HO3D((J[i] * flip.view(1, 3)).unsqueeze(0))[0]
     frames = {"images_u8": imgs, "hand_masks_u8": masks, "Ks": Ks, "xyz21": xyz}
     if depth:
+        from .data import HO3D_DEPTH_SCALE
         frames["depths"] = depths
+        frames["depth_u16"] = torch.from_numpy(np.rint(depths.double().numpy() / HO3D_DEPTH_SCALE).clip(0, 65535).astype(np.uint16))
+    if open_2dj:
+        frames["open_2dj"], frames["open_2dj_con"] = det, con
     return frames

@@ -66,12 +66,33 @@ def semi_below(semi_ratio):
     return 0 if semi_ratio is None else max(0, math.ceil(FREIHAND_TRAIN_SIZE * float(semi_ratio)))
 
 
-def data_dic(sample, dat_name, set_name, args, device="cuda", image_size=224):
+def attach_depth_points(ex, args, K=None, generator=None, out=None):
+    """examples['chamfer_points'] [B,P,3], the target of the terms `chamfer` / `point_mesh`, from examples['depths'] when the option
+    depth_points = P > 0 asks for it and the caller supplied none: P draws with replacement among the depth pixels under the hand mask
+    (examples['masks'], channel 0), back-projected through K -- the intrinsics of THAT map, examples['Ks'] when not given -- and made
+    relative to the root (joints[:, ROOT], else root_xyz): the frame of examples['verts'] that losses._target_points expects.  One launch
+    (ops.depth_points).  generator: where the draws come from; out: the tensor a captured step reads, written in place."""
+    P = int(getattr(args, "depth_points", 0) or 0)
+    if P <= 0 or ex.get("depths") is None or (ex.get("chamfer_points") is not None and out is None):
+        return ex
+    from . import ops
+    root = ex["joints"][:, args.ROOT] if "joints" in ex else ex.get("root_xyz")
+    masks = ex.get("masks")
+    pts, _ = ops.depth_points(ex["depths"], ex["Ks"] if K is None else K, P, mask=None if masks is None else masks[:, 0], origin=root,
+                              generator=generator)
+    ex["chamfer_points"] = pts if out is None else out.copy_(pts)
+    return ex
+
+
+def data_dic(sample, dat_name, set_name, args, device="cuda", image_size=224, generator=None):
     """utils/traineval_util.py:21-111 (FreiHand branch; training queries [trans_images, trans_Ks, trans_joints, scales,
     trans_verts, trans_masks], evaluation queries without the prefix) and :156-201 (HO3D branch: crop resized to 224 with
     nearest-neighbour `interpolate`, the OpenGL -> image convention flip of K's columns and of the joints' y / z by
-    (1, -1, -1), HO-3D -> FreiHAND joint order).  Host tensors go to `device`; `Ps = Ks . [I|0]` is a zero column."""
+    (1, -1, -1), HO-3D -> FreiHAND joint order).  Host tensors go to `device`; `Ps = Ks . [I|0]` is a zero column.
+    With the option depth_points = P > 0 a batch that carries a depth image also gets `chamfer_points` [B,P,3] (attach_depth_points; the
+    draws from `generator`), unless the sample brings its own."""
     ex = {}
+    depth_K = None                                     # the intrinsics of ex["depths"] where they are not ex["Ks"]
     to = lambda t: t.to(device, non_blocking=True)
     if dat_name == "FreiHand":
         training = "training" in set_name
@@ -105,6 +126,9 @@ def data_dic(sample, dat_name, set_name, args, device="cuda", image_size=224):
         if sample.get("depth_crop") is not None:      # the reference loader's key; nearest-neighbour like the mask (a depth image is not averaged)
             d = to(sample["depth_crop"].float())
             ex["depths"] = d if d.shape[-1] == image_size else F.interpolate(d.unsqueeze(1), (image_size, image_size))[:, 0]
+            if d.shape[-1] != image_size:              # K_crop belongs to the loader's crop: pixel centres sit at i + 0.5, so the resized map's
+                r = image_size / d.shape[-1]           # intrinsics are diag(r, r, 1) . K
+                depth_K = Ks * torch.tensor([r, r, 1.0], device=Ks.device).view(1, 3, 1)
         if "open_2dj_crop" in sample:                 # utils/traineval_util.py:187-193 (the detector's joint order is FreiHAND's)
             ex["open_2dj"] = to(sample["open_2dj_crop"].float())
             ex["open_2dj_con"] = to(sample["open_2dj_con"]).float()
@@ -146,7 +170,9 @@ def data_dic(sample, dat_name, set_name, args, device="cuda", image_size=224):
     if masks is not None:
         ex["masks"] = to(masks)
         ex["segms_gt"] = ex["masks"][:, 0].long()
-    return ex
+    if sample.get("chamfer_points") is not None:      # a caller's own target points win over the derived ones
+        ex["chamfer_points"] = to(sample["chamfer_points"].float())
+    return attach_depth_points(ex, args, K=depth_K, generator=generator)
 
 
 _BACKWARD_SEED = {}

@@ -1491,6 +1491,66 @@ size_t hifihr_ho3d_workspace_bytes(int B, int out_size);
 int hifihr_ho3d_batch(const uint32_t* img_rgbx_d, const uint8_t* hand_mask_d, const float* Ks_d, const float* uv21_d, const float* xyz21_d,
                       int FH, int FW, const int* packed_d, int B, int out_size, void* ws_d, size_t ws_bytes, float* out_img_d,
                       float* out_mask_d, float* out_K_d, float* out_uv21_d, float* out_xyz21_d, void* stream);
+/* What the HO-3D loader returns besides the crop (reference data/dataset.py:1023-1215: open_2dj_crop, open_2dj_con, depth_crop), each ONE
+ * more launch behind hifihr_ho3d_batch that reads idx, box and window from the SAME packed_d: no further staged copy.
+ *
+ * hifihr_ho3d_keypoints: the 2-D detections through the crop window (:1199-1203).
+ *   Cache (device): open_2dj_d[n][21][2] in pixels of the stored frame (FreiHAND joint order), open_2dj_con_d[n][21].
+ *   out_open_2dj_d[B][21][2] = (open_2dj[idx] - centre) * scale + out_size / 2 (the integer quotient, as a float): a subtraction, a product
+ *                              and a sum, each rounded to float32, the arithmetic of out_uv21_d above -- detections equal to uv21 give
+ *                              out_uv21_d's bits
+ *   out_con_d[B][21]         = the cached confidences, bit for bit
+ *   An index outside 0 .. n - 1 gives that sample zeros (the indices live in device memory: the entry cannot refuse them).
+ *   Refused (HIFIHR_EINVAL, nothing launched or written): n / B <= 0, out_size outside 1 .. 256, NULL open_2dj_d / open_2dj_con_d /
+ *   packed_d, both outputs NULL.
+ *
+ * hifihr_ho3d_depth_crop: the metric depth through the same crop box, one thread per output pixel, a plain gather, no workspace.
+ *   Cache (device): depth_u16_d[n][FH][FW] uint16, the dataset's encoding decoded (blue + 256 green of the depth PNG:
+ *   hifihr_amd.data.ho3d_depth_to_u16); depth_scale = metres per unit (HO-3D: 0.00012498664727900177, :1040).
+ *   out_depth_d[B][S][S], S = out_size: out[b][r][q] = (float)u16[idx[b]][sy(r)][sx(q)] * depth_scale, one float32 product, with
+ *     sx(q) = x0 + floor((q + 0.5) (x1 - x0) / S),  sy(r) = y0 + floor((r + 0.5) (y1 - y0) / S),  the division and the floor in double,
+ *   (x0, y0, x1, y1) the rounded box of packed_d: Pillow's Image.crop(box).resize((S, S), NEAREST) of the 16-bit image.  Exactly 0 where the
+ *   source position lies outside the frame, where the stored value is 0 (no measurement), for an index outside 0 .. n - 1 and for a box that
+ *   is empty, inverted or longer than HIFIHR_HO3D_MAX_WINDOW on an edge.
+ *   A deliberate departure from the reference, which resizes the two byte planes of the encoded image bilinearly and decodes afterwards
+ *   (:1169-1171): wrong wherever the low byte wraps and at every depth edge.  A depth image is gathered, never averaged.
+ *   Refused (HIFIHR_EINVAL, nothing launched or written): n / B / FH / FW <= 0, out_size outside 1 .. 256, NULL depth_u16_d / packed_d /
+ *   out_depth_d. */
+int hifihr_ho3d_keypoints(const float* open_2dj_d, const float* open_2dj_con_d, int n, const int* packed_d, int B, int out_size,
+                          float* out_open_2dj_d, float* out_con_d, void* stream);
+int hifihr_ho3d_depth_crop(const uint16_t* depth_u16_d, int n, int FH, int FW, const int* packed_d, int B, int out_size, float depth_scale,
+                           float* out_depth_d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Depth map to points: a fixed-size point cloud from a depth map, the reference's utils/fh_utils.py:685-717 (batch_depth2pc) as ONE
+ * launch, one workgroup per sample; the input of the `chamfer` / `point_mesh` terms (examples["chamfer_points"]).
+ *   depths_d[B][H][W] fp32 (0 = no measurement), K_d[B][3][3] the intrinsics of THAT map (its resolution, its axes),
+ *   mask_d[B][H][W] float32 (mask_i64 = 0) or int64 (mask_i64 = 1), or NULL; draws_d[B][P] fp32 in [0, 1); origin_d[B][3] or NULL.
+ * Valid pixels: (r, q) of sample b is valid when depths[b][r][q] > 0 and, with a mask, mask[b][r][q] != 0.  n_b is their number,
+ *   out_count_d[b] = n_b; they are ordered row-major.
+ * Draw: k_i = min(n_b - 1, (int)floorf(draws[b][i] * (float)n_b)), the product a float32 multiply (the clamp is needed: 1 - 2^-24 times
+ *   2^17 rounds to 2^17; a draw below 0 or not a number takes k = 0).  Uniform, WITH replacement, over ALL valid pixels: a fixed number of
+ *   points per sample, no per-sample counts.  The reference's randint(0, n - 1) never draws the last valid pixel; that off-by-one is not
+ *   reproduced.
+ * Point: the k_i-th valid pixel (r, q) with d = depths[b][r][q] gives out_points_d[b][i] = K_b^-1 . (u d, v d, d) - origin[b],
+ *   u = q + c, v = r + c, computed in double and rounded ONCE to float32.  K^-1 is the closed-form adjugate over the determinant of the full
+ *   3 x 3 matrix, without contraction; a singular K gives values that are not finite.  d is the PROJECTIVE depth (K p)_z: with a third
+ *   row (0, 0, 1) that is z, with HO-3D's raw (0, 0, -1) it is -z.
+ *   c = 0.5, the pixel-centre offset of this project's camera: the rasteriser's sample i of an S-wide grid sits at NDC (2 i + 1) / S - 1
+ *   (csrc/render_math.h pix_to_ndc), which Model.camera_from_K maps to pixel coordinate i + 0.5; the kernel derives c from pix_to_ndc, and
+ *   the closed-loop test (tests/ho3d_extras_cases.py) holds it there.
+ *   For an upper-triangular K this is the reference's x = (u - cx) z / fx; what remains different is the reference's +1e-5 on the focal
+ *   length, its c = 0 and its float32 arithmetic.
+ *   out_index_d[B][P] int32 (may be NULL): the chosen pixel r W + q.
+ * n_b = 0: that sample's points are zeros (a target at the origin: check out_count_d), its indices -1.  n_b = 1: P copies of the one point.
+ * No atomics, no workspace, no allocation, nothing read back: capturable; the same draws give the same bits on every call.
+ * Refused (HIFIHR_EINVAL, nothing launched or written): B / P / H / W <= 0, H W > HIFIHR_DEPTH_POINTS_MAX_PIXELS (the validity words and
+ * their prefix counts live in LDS), NULL depths_d / K_d / draws_d / out_points_d / out_count_d.
+ * ---------------------------------------------------------------------------------------------- */
+#define HIFIHR_DEPTH_POINTS_MAX_PIXELS (512 * 512)
+int hifihr_depth_points(const float* depths_d, const float* K_d, const void* mask_d /* or NULL */, int mask_i64,
+                        const float* draws_d, const float* origin_d /* or NULL */, int B, int H, int W, int P, float* out_points_d,
+                        int32_t* out_count_d, int32_t* out_index_d /* or NULL */, void* stream);
 
 #ifdef __cplusplus
 }

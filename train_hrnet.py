@@ -12,6 +12,9 @@ package's device-resident pieces:
               projected joints, Pillow-exact crop + resize to 224) on the device; --ho3d_cache <npz> or seeded synthetic frames.  The epoch
               driver's periodic test and the evaluation mode write the challenge dump `<base_out_path>/json/test/<epoch>/pred.json` from the
               evaluation split (--ho3d_eval_cache <npz>: hand boxes + root joints; reference train_hrnet.py:124-136, 286-293).
+              Either npz may also carry open_2dj / open_2dj_con (2-D detections) and depth_u16 (16-bit depth frames): the cache then feeds
+              the self-supervised keypoint terms, fit_keypoints, the term `depth` / depth_mae and, with the option depth_points, the
+              `chamfer_points` of `chamfer` / `point_mesh`; the synthetic frames carry them when something asks for them.
   step        hifihr_amd.traineval.GraphedTrainStep (hipGraph replay) or the eager step (--graph 0)
   multi-GPU   one process per GPU under torch.distributed.run; rank r takes every world-th batch slice; RCCL all-reduce of the
               flat gradient buffer (hifihr_amd/dist.py).  Replaces nn.DataParallel (:560).
@@ -42,7 +45,9 @@ def parse(argv=None):
                     "[n,2,2] ((x0, y0), (x1, y1)), root_xyz [n,3] (the split has a hand box and the root joint, no 21 joints: dataset.py:1071-1080); "
                     "without it the evaluation pass runs on the training frames with boxes / roots derived from their joints")
     ap.add_argument("--ho3d_cache", default=None, help="npz: images u8 [n,480,640,3], hand_masks u8 [n,480,640], Ks [n,3,3] (camMat . cam_extr), "
-                                                       "xyz21 [n,21,3]; default: seeded synthetic frames")
+                                                       "xyz21 [n,21,3]; optional: open_2dj [n,21,2] + open_2dj_con (2-D detections) and depth_u16 "
+                                                       "[n,480,640] (hifihr_amd.data.ho3d_depth_to_u16); default: seeded synthetic frames, "
+                                                       "which carry both when a requested loss, metric or fit_keypoints needs them")
     ap.add_argument("--openpose_keypoints", default=None, metavar="JSON",
                     help="2-D detections for the self-supervised terms 'open_2dj' / 'open_bone_direc' / 'open_2dj_de' and the `*_self` photometric "
                          "terms, in the reference's layout (data/dataset.py:1430-1432): [keypoints [n][21][2], confidences [n][21] or [n][21][1]], "
@@ -96,6 +101,11 @@ def render_depth_kwargs(args):
 def wants_depths(args):
     """The batches need examples['depths']: the loss term 'depth' or the metric depth_mae is requested."""
     return "depth" in args.losses or bool(getattr(args, "depth_metric", False))
+
+
+def wants_depth_points(args):
+    """The batches need examples['chamfer_points'] made from examples['depths'] (the option depth_points > 0 with a term that reads them)."""
+    return int(getattr(args, "depth_points", 0) or 0) > 0 and any(k in args.losses for k in ("chamfer", "point_mesh"))
 
 
 def attach_mesh_depths(ex, model, static=None):
@@ -232,21 +242,32 @@ def train_ho3d(cli, args, model, loss_func, opt, sched, reducer, current_epoch, 
     from hifihr_amd.checkpoint import save_model
     from hifihr_amd.data import HO3DDeviceCache
     from hifihr_amd.traineval import GraphedTrainStep, data_dic, train_step
-    if wants_depths(args):
-        raise SystemExit("[train_hrnet] the HO-3D data path produces no examples['depths'] (decoding and cropping HO-3D depth images is not "
-                         "built): the loss term 'depth' / depth_metric run on --dataset FreiHand, or from a caller that supplies 'depths'")
+    need_depth, need_det = wants_depths(args) or wants_depth_points(args), wants_keypoints(args) or fit_wants_detections(args)
     if cli.ho3d_cache:
         z = np.load(cli.ho3d_cache)
         frames = {"images_u8": z["images"], "hand_masks_u8": z["hand_masks"], "Ks": z["Ks"], "xyz21": z["xyz21"]}
+        frames.update(ho3d_optional_arrays(z))
     else:
         from hifihr_amd import ops
         from hifihr_amd.mano_tables import synthetic_mano_tables
         mt = synthetic_mano_tables(0)
         frames = synth.make_ho3d_frames(ops.ManoLayerHandle(mt), ops.RendererHandle(mt.faces, 778, image_size=224, aa=3), cli.synthetic_size,
-                                        device=device, images="render")
+                                        device=device, images="render", depth=need_depth, open_2dj=need_det)
+        frames.pop("depths", None)                        # (the float map the 16-bit frames were made from)
+    training = "training" in args.mode
+    if training and (wants_depths(args) or wants_depth_points(args)) and "depth_u16" not in frames:
+        raise SystemExit("[train_hrnet] the loss term 'depth' / depth_metric / depth_points need HO-3D depth frames: give depth_u16 "
+                         "(uint16 [n,480,640], hifihr_amd.data.ho3d_depth_to_u16 of the depth PNGs) in the --ho3d_cache npz")
+    if training and wants_keypoints(args) and "open_2dj" not in frames:
+        raise SystemExit(f"[train_hrnet] the losses {[k for k in args.losses if k in KEYPOINT_LOSSES]} need 2-D detections: give open_2dj / "
+                         "open_2dj_con in the --ho3d_cache npz")
     cache = HO3DDeviceCache(**frames, device=device)
     say(f"[train_hrnet] HO3D: {cache.n} frames resident on {device}; world {world}; encoder {args.pretrain}; losses {args.losses}")
     eval_cache = ho3d_eval_cache(cli, frames, device) if rank == 0 else None
+    if eval_cache is not None and fit_wants_detections(args) and eval_cache.open_2dj is None:
+        raise SystemExit("[train_hrnet] fit_keypoints with fit_target 'open_2dj' needs 2-D detections for the HO-3D evaluation split: give "
+                         "open_2dj / open_2dj_con in the --ho3d_eval_cache npz (or in --ho3d_cache when the split is derived from it), or "
+                         "set fit_target to 'j2d_gt'")
     if "training" not in args.mode:                       # evaluation only (reference train_hrnet.py:487-496)
         if rank == 0:
             say("[train_hrnet] HO3D evaluation:", run_evaluation_ho3d(model, eval_cache, args, device, current_epoch))
@@ -257,6 +278,7 @@ def train_ho3d(cli, args, model, loss_func, opt, sched, reducer, current_epoch, 
     B = args.train_batch
     gen = torch.Generator().manual_seed(1000 + current_epoch)
     noise_gen = torch.Generator().manual_seed(77 + rank)
+    points_gen = torch.Generator().manual_seed(177 + rank)             # the draws of depth_points
     stepper, stepper_key, it, t_last = None, None, 0, time.perf_counter()
     for epoch in range(1, args.total_epochs + 1 - current_epoch):
         options.update_lambdas_for_epoch(args, epoch + current_epoch)
@@ -268,7 +290,7 @@ def train_ho3d(cli, args, model, loss_func, opt, sched, reducer, current_epoch, 
         per_step = B * world
         for lo in range(0, cache.n - per_step + 1, per_step):
             idx = perm[lo + rank * B: lo + (rank + 1) * B]
-            ex = data_dic(cache.batch(idx, generator=noise_gen), "HO3D", "training", args, device=device)
+            ex = data_dic(cache.batch(idx, generator=noise_gen), "HO3D", "training", args, device=device, generator=points_gen)
             if cli.graph and stepper is None:
                 ok = 1
                 try:
@@ -323,22 +345,34 @@ def train_ho3d(cli, args, model, loss_func, opt, sched, reducer, current_epoch, 
     return 0
 
 
+def ho3d_optional_arrays(z):
+    """The optional keys of an HO-3D npz -> HO3DDeviceCache keywords: open_2dj [n,21,2] + open_2dj_con [n,21] or [n,21,1] (2-D detections,
+    FreiHAND joint order, pixels of the stored frame) and depth_u16 [n,480,640] uint16 (hifihr_amd.data.ho3d_depth_to_u16 of the depth PNGs)."""
+    extra = {}
+    if "open_2dj" in z and "open_2dj_con" in z:
+        extra.update(open_2dj=z["open_2dj"], open_2dj_con=z["open_2dj_con"])
+    if "depth_u16" in z:
+        extra.update(depth_u16=z["depth_u16"])
+    return extra
+
+
 def ho3d_eval_cache(cli, frames, device):
     """The HO-3D evaluation split as an HO3DDeviceCache (crop window from the hand box, root joint instead of 21 joints: reference
     data/dataset.py:1071-1080).  From --ho3d_eval_cache, else derived from the training frames: box = the projected joints' bounds,
-    root = joint 0 of the HO-3D order."""
+    root = joint 0 of the HO-3D order.  Detections and depth frames travel with either (ho3d_optional_arrays)."""
     from hifihr_amd.data import HO3DDeviceCache
     if cli.ho3d_eval_cache:
         z = np.load(cli.ho3d_eval_cache)
         n = z["images"].shape[0]
         masks = z["hand_masks"] if "hand_masks" in z else np.zeros((n,) + z["images"].shape[1:3], np.uint8)
         return HO3DDeviceCache(z["images"], masks, z["Ks"], np.zeros((n, 21, 3), np.float32) + z["root_xyz"][:, None], device=device,
-                               bboxes=z["bboxes"], root_xyz=z["root_xyz"])
+                               bboxes=z["bboxes"], root_xyz=z["root_xyz"], **ho3d_optional_arrays(z))
     Ks, xyz = np.asarray(frames["Ks"], np.float32), np.asarray(frames["xyz21"], np.float32)
     uvw = np.einsum("nij,nkj->nki", Ks, xyz)
     uv = uvw[..., :2] / uvw[..., 2:3]
     boxes = np.stack([uv.min(1), uv.max(1)], 1)
-    return HO3DDeviceCache(frames["images_u8"], frames["hand_masks_u8"], Ks, xyz, device=device, bboxes=boxes, root_xyz=xyz[:, 0])
+    extra = {k: frames[k] for k in ("open_2dj", "open_2dj_con", "depth_u16") if k in frames}
+    return HO3DDeviceCache(frames["images_u8"], frames["hand_masks_u8"], Ks, xyz, device=device, bboxes=boxes, root_xyz=xyz[:, 0], **extra)
 
 
 _LPIPS = {}
@@ -358,14 +392,15 @@ def depth_renderer(model):
     return _DEPTH_RENDERER[id(model)]
 
 
-def make_evaluator(args, device):
-    """Evaluator of the evaluation pass; with --lpips_weights it also reports LPIPS (the module is built and loaded once per device)."""
+def make_evaluator(args, device, depth=None):
+    """Evaluator of the evaluation pass; with --lpips_weights it also reports LPIPS (the module is built and loaded once per device).
+    depth: overrides the option depth_metric (a pass whose batches carry no depth image cannot report depth_mae)."""
     from hifihr_amd.evaluate import Evaluator
     paths = getattr(args, "lpips_weights", None)
     bench = bool(getattr(args, "benchmark_metrics", True))          # the FreiHAND benchmark's PCK / AUC and F-score keys
     cham = bool(getattr(args, "chamfer_metric", False))             # mesh_chamfer / mesh_al_chamfer beside the F-scores
     p2s = bool(getattr(args, "point_mesh_metric", False))           # mesh_p2s / mesh_al_p2s: ground-truth vertices -> the predicted surface
-    dep = bool(getattr(args, "depth_metric", False))                # depth_mae: the rendered depth map against examples['depths']
+    dep = bool(getattr(args, "depth_metric", False)) if depth is None else bool(depth)      # depth_mae: the rendered depth map against examples['depths']
     if not paths:
         return Evaluator(benchmark=bench, chamfer=cham, point_mesh=p2s, depth=dep)
     key = (str(device), tuple(paths))
@@ -394,7 +429,12 @@ def run_evaluation_ho3d(model, cache, args, device, epoch):
     the product is the dump.  -> (path, n, texture metrics)."""
     from hifihr_amd.fit import refine_outputs
     from hifihr_amd.traineval import data_dic
-    ev = make_evaluator(args, device)
+    # depth_mae is reported when the split carries depth frames (HO3DDeviceCache(depth_u16=...)) and the model renders its depth map
+    if getattr(args, "depth_metric", False) and getattr(cache, "depth_u16", None) is None:
+        print("[train_hrnet] depth_metric: the HO-3D evaluation split carries no depth_u16; depth_mae is not reported")
+        ev = make_evaluator(args, device, depth=False)
+    else:
+        ev = make_evaluator(args, device)
     refined = 0
     model.eval()
     with torch.no_grad():
@@ -468,7 +508,7 @@ def main(argv=None):
     from hifihr_amd.mano_tables import load_mano_pkl, synthetic_mano_tables
     from hifihr_amd.models import Model
     from hifihr_amd.optim import FlatParams, FusedAdam
-    from hifihr_amd.traineval import GraphedTrainStep, data_dic, train_step
+    from hifihr_amd.traineval import GraphedTrainStep, attach_depth_points, data_dic, train_step
 
     rank, local_rank, world = hdist.init_process_group_from_env(timeout_min=cli.dist_timeout_min)
     assert torch.cuda.is_available(), "the hot path has no CPU fallback"
@@ -536,6 +576,7 @@ def main(argv=None):
     B = args.train_batch
     gen = torch.Generator().manual_seed(1000 + current_epoch)         # same permutation on every rank
     rot_gen = torch.Generator().manual_seed(77 + rank)                # ... different rotations
+    points_gen = torch.Generator().manual_seed(177 + rank)            # ... and draws of depth_points
     stepper, stepper_key, it, t_last = None, None, 0, time.perf_counter()
     for epoch in range(1, args.total_epochs + 1 - current_epoch):
         options.update_lambdas_for_epoch(args, epoch + current_epoch)
@@ -549,8 +590,11 @@ def main(argv=None):
             idx = perm[lo + rank * B: lo + (rank + 1) * B]
             # the batch is written straight into the captured step's static inputs (one staged copy + two launches)
             ex = cache.batch_examples(idx, generator=rot_gen, out=stepper.static if stepper is not None else None, root_id=args.ROOT)
-            if "depth" in args.losses:
-                attach_mesh_depths(ex, model, static=stepper.static if stepper is not None else None)
+            if "depth" in args.losses or wants_depth_points(args):
+                static = stepper.static if stepper is not None else None
+                attach_mesh_depths(ex, model, static=static)
+                if wants_depth_points(args):                  # the target points of chamfer / point_mesh from that depth map
+                    attach_depth_points(ex, args, generator=points_gen, out=static.get("chamfer_points") if static is not None else None)
             if cli.graph and stepper is None:
                 ok = 1
                 try:
